@@ -8,11 +8,15 @@ field reset + T fused leapfrog steps incl. pressure-history record + per-cell IR
 reference's background loop does, PvContext.cpp:80-83).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--grid 4096] [--inflight B] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
 
-The block of K steps -- barrier + device sync on both sides, max over ranks -- is timed R times back to back (default 5) in
-one invocation; `ms_per_step` and `value` are the MEDIAN block, `spread` holds every block, min / max and their relative
-spread: one 0.07 s block cannot tell a 3 % change from the box's noise.  `device` says what the line was measured on
+Exactly K steps are timed, after W warm-up steps.  They are split into R consecutive blocks (default 1) -- barrier + device
+sync on both sides of each, max over ranks; `ms_per_step` and `value` are the MEDIAN block's time per step, `spread` holds
+every block, min / max and their relative spread.  Every block starts from an idle GPU and ends by draining it, so a short
+block costs more per step than a long one: compare lines with the same K and R.  `device` says what the line was measured on
 (name, CUs, partition modes, shader clock sampled beside the in-flight warm-up runs and right after the timed blocks).
+--dump-outputs DIR writes what the last timed step computed to DIR (dump_outputs); the inputs of every step follow from the
+arguments alone, so two builds run with the same arguments can be compared output for output.
 
 Runs in flight: independent runs share nothing, so a GPU can work on B of them at once (B solver instances, each with
 its own planes and HIP stream; default B = 2).  One launch of the step kernel fills the chip for ~130 us and then
@@ -57,8 +61,9 @@ def same_bits(a, b):
     return (a.view(np.uint32) == b.view(np.uint32)) | ((a == 0) & (b == 0)) | (np.isnan(a) & np.isnan(b))
 
 
-def verify_records(gathered, scene, open_field, listener_index, grid=4096):
-    """Compare EVERY gathered per-emitter record of the timed runs with the reference, bit for bit.
+def verify_records(gathered, scene, open_field, run0, grid=4096):
+    """Compare EVERY gathered per-emitter record of the timed runs with the reference, bit for bit.  Row k of `gathered`
+    is global run run0 + k, whose listener is LISTENERS[(run0 + k) % 8] (open field: cell (run0 + k) % 64).
     HugeRoom.pv is a closed room: at any Mode A grid size the records equal the reference's 71^2 (25 m) run of the same
     listener / emitters (closed-room isolation); tests/golden/g71_hugeroom_cfg4.npz holds those 8 x 2
     records, generated from the compiled reference (tests/golden/make_golden.py cfg4).  Returns (verified_runs, how);
@@ -68,10 +73,11 @@ def verify_records(gathered, scene, open_field, listener_index, grid=4096):
         # 8192^2 grid's position arithmetic (tests/golden/make_golden.py cfg5; the open field is translation-invariant)
         g = np.load(os.path.join(ROOT, "tests", "golden", "g8192_open_cfg5.npz"))
         want = g["emitter_out"]
-        bad = [k for k in range(gathered.shape[0]) if not same_bits(gathered[k], want[k % len(want)]).all()]
+        bad = [k for k in range(gathered.shape[0]) if not same_bits(gathered[k], want[(run0 + k) % len(want)]).all()]
         if bad:
             raise AssertionError("bench: %d of %d timed runs differ from the reference records, first run %d: got %r "
-                                 "want %r" % (len(bad), gathered.shape[0], bad[0], gathered[bad[0]], want[bad[0] % len(want)]))
+                                 "want %r" % (len(bad), gathered.shape[0], run0 + bad[0], gathered[bad[0]],
+                                              want[(run0 + bad[0]) % len(want)]))
         return int(gathered.shape[0]), ("every timed run's 2 emitter records bit-identical to the pinned oracle's (513^2 "
                                         "window, 8192^2 position arithmetic: tests/golden/g8192_open_cfg5.npz)")
     if open_field or scene != "HugeRoom.pv":
@@ -81,15 +87,40 @@ def verify_records(gathered, scene, open_field, listener_index, grid=4096):
     assert [tuple(l) for l in g["listeners"][:, [0, 2]].tolist()] == [tuple(map(float, l)) for l in LISTENERS]
     bad = []
     for k in range(gathered.shape[0]):
-        if not same_bits(gathered[k], want[listener_index(k)]).all():
+        if not same_bits(gathered[k], want[(run0 + k) % len(LISTENERS)]).all():
             bad.append(k)
     if bad:
         k = bad[0]
         raise AssertionError("bench: %d of %d timed runs differ from the reference records, first run %d: got %r want "
-                             "%r" % (len(bad), gathered.shape[0], k, gathered[k], want[listener_index(k)]))
+                             "%r" % (len(bad), gathered.shape[0], run0 + k, gathered[k], want[(run0 + k) % len(LISTENERS)]))
     return int(gathered.shape[0]), ("every timed run's 2 emitter records (8 floats each) bit-identical to the "
                                     "reference's 71^2 closed-room run of the same listener "
                                     "(tests/golden/g71_hugeroom_cfg4.npz)")
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: all files together stay under this
+
+
+def dump_outputs(path, records, solvers):
+    """--dump-outputs: what the timed path computed in its last step, as float32 arrays in path/<name>.npy.
+    emitter_outputs [runs, 2, 8]: the per-emitter records of the last step's runs, gathered from all ranks, in run order;
+    results_sample [B, S, 8] / delay_sample [B, S]: the result and delay maps each of this rank's solvers holds after the
+    last step, at the S cells (flat row-major indices) of a sorted numpy default_rng(0) draw without replacement -- every
+    cell when the grid fits in DUMP_BYTES.  The cells depend only on grid and B, so two builds are compared cell for cell."""
+    os.makedirs(path, exist_ok=True)
+    records = np.ascontiguousarray(records, np.float32)
+    np.save(os.path.join(path, "emitter_outputs.npy"), records)
+    n = solvers[0].gx * solvers[0].gy
+    S = min(n, (DUMP_BYTES - records.nbytes - 4096) // (len(solvers) * 9 * 4))  # 8 results + 1 delay per cell; 4096: headers
+    cells = np.arange(n) if S == n else np.sort(np.random.default_rng(0).choice(n, S, replace=False))
+    res = np.empty((len(solvers), S, 8), np.float32)
+    delay = np.empty((len(solvers), S), np.float32)
+    for b, sv in enumerate(solvers):
+        r, d = sv.results()
+        res[b] = r.reshape(n, 8)[cells]
+        delay[b] = d.reshape(n)[cells]
+    np.save(os.path.join(path, "results_sample.npy"), res)
+    np.save(os.path.join(path, "delay_sample.npy"), delay)
 
 
 def cpu_baseline(grid_cells=1025, scene="HugeRoom.pv"):
@@ -309,10 +340,16 @@ class GpuHooks:
 def main(argv=None, hooks=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=8, help="timed steps in all (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the block of --steps steps is timed this many times back to back; value = the median block")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="the --steps timed steps are split into this many consecutive blocks, each timed on its own "
+                         "(at most one block per step); value = the median block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32): "
+                         "emitter_outputs [runs, 2, 8] of all ranks, and results_sample [B, S, 8] / delay_sample [B, S]: "
+                         "rank 0's result and delay maps at S cells drawn by numpy default_rng(0) (all cells if they fit "
+                         "in 64 MB)")
     ap.add_argument("--grid", type=int, default=4096)
     ap.add_argument("--scene", default="HugeRoom.pv", help="a .pv file under tests/scenes, or 'none' (empty grid)")
     ap.add_argument("--open-field", action="store_true",
@@ -352,6 +389,8 @@ def main(argv=None, hooks=None):
                     help="N > 0: HIP events around every Nth step-kernel launch instead of around the whole launch loop "
                          "(the extra events cost 0.2-0.5 ms per run)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import torch  # first: libplaneverb_amd.so then binds to the HIP runtime torch already loaded
     import torch.distributed as dist
@@ -497,14 +536,19 @@ def main(argv=None, hooks=None):
             pvd.gather_outputs(warm, B * world, dist, dev)
     comm_init_s = time.perf_counter() - t_comm0  # communicator + first (channel set-up) gather
     n_runs = args.steps * B * world
+    # the --steps timed steps, split into consecutive blocks as evenly as possible; steps are numbered across blocks
+    n_blocks = max(1, min(args.repeats, args.steps))
+    block_steps = [args.steps // n_blocks + (j < args.steps % n_blocks) for j in range(n_blocks)]
     local = {}
+    block_first_step = 0
     fdtd_ms, ana_ms, air_ms, gen_ms, loop_ms, reached = [], [], [], [], [], []
     pending = [None] * B
 
     def collect(b):  # wait for solver b's run, fetch its per-emitter outputs and timings
         sv, k = solvers[b], pending[b]
         sv.sync()
-        local[run_id(k, b)] = sv.queried_outputs()  # gathered behind the run's analysis (PvAmdSetOutputQueries)
+        # keyed by the run's index within the block (gather_outputs orders by it)
+        local[run_id(k - block_first_step, b)] = sv.queried_outputs()  # gathered behind the run's analysis (PvAmdSetOutputQueries)
         t = sv.timings()
         fdtd_ms.append(t.fdtdMs)
         ana_ms.append(t.analysisMs)
@@ -514,11 +558,13 @@ def main(argv=None, hooks=None):
         reached.append(getattr(t, "reachedCells", 0))
         pending[b] = None
 
-    def timed_block():  # EXACTLY args.steps steps between barrier + device sync, max over ranks
+    def timed_block(first, n):  # EXACTLY steps first .. first + n - 1 between barrier + device sync, max over ranks
+        nonlocal block_first_step
+        block_first_step = first
         local.clear()
         sync()
         t0 = time.perf_counter()
-        for k in range(args.steps):
+        for k in range(first, first + n):
             for g in range(G):
                 for b in range(g * NB, (g + 1) * NB):
                     if pending[b] is not None:
@@ -530,9 +576,9 @@ def main(argv=None, hooks=None):
             if pending[b] is not None:
                 collect(b)
         if comm is not None:
-            got = pvd.gather_outputs_native(local, n_runs, comm, n_em=2)  # the one RCCL gather, in C++
+            got = pvd.gather_outputs_native(local, n * B * world, comm, n_em=2)  # the one RCCL gather, in C++
         else:
-            got = pvd.gather_outputs(local, n_runs, dist if use_dist else None, dev)
+            got = pvd.gather_outputs(local, n * B * world, dist if use_dist else None, dev)
         sync()
         mine = time.perf_counter() - t0
         el = mine
@@ -543,14 +589,17 @@ def main(argv=None, hooks=None):
         return el, mine, got
 
     blocks, mine_blocks, gathered_all = [], [], []
-    for _ in range(max(1, args.repeats)):
-        el, mine, got = timed_block()
+    for j, n in enumerate(block_steps):
+        el, mine, got = timed_block(sum(block_steps[:j]), n)
         blocks.append(el)
         mine_blocks.append(mine)
         gathered_all.append(got)
     clock_after = hooks.clock_probe() if hasattr(hooks, "clock_probe") else None
-    elapsed = float(np.median(blocks))
-    gathered = gathered_all[0]
+    ms_blocks = [b / n * 1e3 for b, n in zip(blocks, block_steps)]
+    ms_per_step = float(np.median(ms_blocks))
+    if args.dump_outputs and rank == 0:
+        # before the records are verified: the outputs of a build that fails verification are the ones worth comparing
+        dump_outputs(args.dump_outputs, gathered_all[-1][-B * world:], solvers)
     # per-rank record (a first multi-GPU run must be diagnosable from the one line rank 0 prints)
     rank_rec = {"rank": rank, "local_rank": local_rank, "block_s": [round(x, 6) for x in mine_blocks],
                 "warmup_s": round(warmup_s, 3), "comm_init_and_first_gather_s": round(comm_init_s, 3),
@@ -563,10 +612,11 @@ def main(argv=None, hooks=None):
 
     if rank == 0:
         verified_runs, verified_how = 0, None
-        for got in gathered_all:  # every timed block's records
-            assert got.shape == (n_runs, 2, 8)
-            # run k of the gathered array = global run index k (gather_outputs orders by run index) = listener k mod 8
-            v, verified_how = verify_records(got, args.scene, args.open_field, lambda k: k % len(LISTENERS), args.grid)
+        for j, got in enumerate(gathered_all):  # every timed block's records
+            assert got.shape == (block_steps[j] * B * world, 2, 8)
+            # run k of block j's gathered array = global run index k + (its first step) x B x world (gather_outputs orders
+            # by run index)
+            v, verified_how = verify_records(got, args.scene, args.open_field, sum(block_steps[:j]) * B * world, args.grid)
             verified_runs = None if v is None else verified_runs + v
         info = s.info
         K = info.stepsPerLaunch
@@ -645,17 +695,17 @@ def main(argv=None, hooks=None):
                                "launch_ms / concurrent_launches x effective clock = GRBM_GUI_ACTIVE / 8 / duration)",
                         "collected_at_head": sqprof.get("collected_at_head"),
                         "source": "profiles/%s_sq_pmc.md" % sqprof.get("round", "r02")}
-        value = world * B * cells * T * args.steps / elapsed
+        step_s = ms_per_step * 1e-3
+        value = world * B * cells * T / step_s
         fd = float(np.mean(fdtd_ms)) * 1e-3
-        ms_blocks = [b / args.steps * 1e3 for b in blocks]
-        spread = {"repeats": len(blocks), "ms_per_step_all": [round(x, 4) for x in ms_blocks],
+        spread = {"repeats": len(blocks), "steps_per_block": block_steps, "ms_per_step_all": [round(x, 4) for x in ms_blocks],
                   "ms_per_step_min": min(ms_blocks), "ms_per_step_max": max(ms_blocks),
-                  "ms_per_step_median": float(np.median(ms_blocks)),
-                  "rel_spread": (max(ms_blocks) - min(ms_blocks)) / float(np.median(ms_blocks)),
-                  "value_best": world * B * cells * T * args.steps / min(blocks),
-                  "value_worst": world * B * cells * T * args.steps / max(blocks),
-                  "how": "the block of %d steps timed %d times back to back in this invocation (barrier + device sync "
-                         "around each, max over ranks); value / ms_per_step = the median block" % (args.steps, len(blocks))}
+                  "ms_per_step_median": ms_per_step,
+                  "rel_spread": (max(ms_blocks) - min(ms_blocks)) / ms_per_step,
+                  "value_best": world * B * cells * T / (min(ms_blocks) * 1e-3),
+                  "value_worst": world * B * cells * T / (max(ms_blocks) * 1e-3),
+                  "how": "the %d timed steps in %d consecutive block(s) in this invocation (barrier + device sync around "
+                         "each, max over ranks); value / ms_per_step = the median block's time per step" % (args.steps, len(blocks))}
         device = hooks.device_record() if hasattr(hooks, "device_record") else {}
         device["effective_clock_ghz"] = (float(np.median(clock_loaded)) / 1e3) if clock_loaded else None
         device["effective_clock_how"] = ("one wave's timed s_sleep (812 800 shader-clock cycles against the 100 MHz counter, "
@@ -677,7 +727,7 @@ def main(argv=None, hooks=None):
             ana_prof = None
         analysis = {
             "reached_cells_per_run": n_reached, "cells_per_run": s.gx * s.gy,
-            "reached_ir_per_s": world * B * n_reached * args.steps / elapsed,
+            "reached_ir_per_s": world * B * n_reached / step_s,
             "analysis_only_reached_ir_per_s": (n_reached / ana_s) if ana_s > 0 else None,
             "analysis_ms": ana_s * 1e3, "bound": "latency" if n_reached < 65536 else "hbm",
             "algorithmic_bytes_per_run": ana_alg,
@@ -692,7 +742,7 @@ def main(argv=None, hooks=None):
                     "all-cells-reached workload (Shoebox 25 m at 512^2, T = 3179)"}
         out = {
             "metric": "grid_cell_updates_per_s", "value": value, "unit": "cell-updates/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "repeats": len(blocks), "ms_per_step": elapsed / args.steps * 1e3,
+            "steps": args.steps, "warmup": args.warmup, "repeats": len(blocks), "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s in a %dx%d grid (Mode A: 275 Hz, dx=%.4f m, %.3f m), T=%d; 1 run = reset + T "
                                    "leapfrog steps with pr-history record + per-cell IR analysis for one listener "
@@ -707,13 +757,13 @@ def main(argv=None, hooks=None):
                        "parallelism": "runs sharded round-robin, 1 all-gather of outputs", "gather": gather_how,
                        "backend": backend if use_dist else None},
             "fdtd_cell_updates_per_s": world * B * cells * T / fd,
-            "impulse_responses_per_s": world * B * s.gx * s.gy * args.steps / elapsed,
+            "impulse_responses_per_s": world * B * s.gx * s.gy / step_s,
             "impulse_responses_per_s_note": "all cells of the map incl. the ones without an onset (early-out); "
                                             "roofline.analysis.reached_ir_per_s counts the analysed ones",
             "spread": spread, "device": device, "ranks": ranks,
             "fdtd_ms": fd * 1e3, "analysis_ms": float(np.mean(ana_ms)),
             "hbm_bytes_held": int(info.deviceBytes) * B,
-            "verified_runs": verified_runs, "timed_runs": n_runs * len(blocks), "verified_how": verified_how,
+            "verified_runs": verified_runs, "timed_runs": n_runs, "verified_how": verified_how,
             "roofline": {"bound": "valu", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
                          "basis": "achieved / peak / frac are on SURVEY.md 8d's basis: ALGORITHMIC bytes (24 B per "

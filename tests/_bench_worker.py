@@ -25,13 +25,14 @@ GOLD = np.load(os.path.join(ROOT, "tests", "golden", "g71_hugeroom_cfg4.npz"))
 class FakeBenchSolver:
     """the slice of planeverb_amd.api.Solver that bench.py uses"""
     made = 0
+    runs = 0  # runs started, by all instances
 
     def __init__(self, size, res, **opts):
         FakeBenchSolver.made += 1
         self.opts = opts
-        self.gx = self.gy = 4096
         self.T = 435
         self.dx = float(np.float32(343.21) / np.float32(res) / np.float32(3.5))
+        self.gx = self.gy = int(round(size / self.dx - 0.5))  # bench.py --grid (size = bench.mode_a_size(grid))
         self.listener, self.done, self.q = None, True, None
         self.info = types.SimpleNamespace(stepsPerLaunch=12, tileRows=36, tileCols=40, deviceBytes=1 << 20)
 
@@ -49,6 +50,7 @@ class FakeBenchSolver:
     def run_async(self, listener):
         assert self.done, "run started before the previous one was collected"
         self.listener, self.done = listener, False
+        FakeBenchSolver.runs += 1
 
     def run(self, listener):
         self.run_async(listener)
@@ -60,6 +62,13 @@ class FakeBenchSolver:
     def queried_outputs(self):
         assert self.done and len(self.q) == 2
         return np.array(self._record(), np.float32)
+
+    def results(self):
+        """result map: every cell holds the first emitter's record of the last run; delay map: the cell's flat index"""
+        assert self.done
+        res = np.empty((self.gx, self.gy, 8), np.float32)
+        res[...] = self._record()[0]
+        return res, np.arange(self.gx * self.gy, dtype=np.float32).reshape(self.gx, self.gy)
 
     def timings(self):
         return types.SimpleNamespace(fdtdMs=5.0, analysisMs=0.2, airKernelMs=0.0, generalKernelMs=0.0, stepLoopMs=4.8,
@@ -125,7 +134,7 @@ def main():
     hooks = CpuHooks(comm_mode)
     world = os.environ.get("WORLD_SIZE", "2")
     shape = os.environ.get("PV_BENCH_WORKER_SHAPE", "")
-    argv = ["--gpus", world, "--steps", "3", "--warmup", "2", "--cpu-baseline-cells", "97"]
+    argv = ["--gpus", world, "--steps", "3", "--warmup", "2", "--repeats", "3", "--cpu-baseline-cells", "97"]
     if shape == "config4":  # one run per GPU and step
         argv += ["--inflight", "1"]
     elif shape == "config5":  # two in flight, 4 steps x 2 x 8 ranks = 64 runs

@@ -13,6 +13,7 @@ IR traces, result / delay maps).  No reference source text is stored.
     python tests/golden/make_golden.py cfg5       # 8192^2 open field: records of the 64 seeded listener cells (pinned oracle, ~5 min)
     python tests/golden/make_golden.py cells      # raw reference Cells of a few IRs (GetImpulseResponse layout)
     python tests/golden/make_golden.py findgain   # FindGainA/B/C table from PlaneverbDSP's compiled context file
+    python tests/golden/make_golden.py vsref      # the cases of tests/test_oracle_vs_ref.py (seconds)
 """
 import os
 import sys
@@ -209,10 +210,63 @@ def run_findgain():
     print("findgain ->", path, len(x), "pairs, %.1f kB" % (os.path.getsize(path) / 1e3))
 
 
+# the cases of tests/test_oracle_vs_ref.py: (scene under tests/scenes, listener, res, size) runs, a sequence of geometry edits on
+# an empty 25 m grid at 275 Hz, and (size, res) configs of the free-field energy
+VSREF_SCENES = [
+    ("MiddleWallScene.pv", (10.0, 0.0, 11.0), 275, 25.0),
+    ("UnityReplicationTest.pv", (4.0, 0.0, 4.5), 275, 25.0),
+    ("SingleWall.pv", (3.0, 0.0, 12.0), 275, 25.0),
+    ("SmallRoom.pv", (5.0, 0.0, 5.0), 275, 10.0),
+    ("ExampleProject.pv", (5.0, 0.0, 2.0), 500, 10.0),
+]
+_A, _B, _EDGE = [10, 10, 6, 1, 0.9], [12, 10, 1, 6, 0.8], [24.9, 12, 1, 30, 0.7]
+VSREF_GEOMETRY = [("add", _A), ("add", _B), ("remove", _A), ("add", _EDGE), ("remove", _EDGE), ("add", _A)]
+VSREF_EFREE = [(40.0, 275), (31.7, 300), (18.0, 375), (10.0, 275)]
+
+
+def vsref_snap_ts(T):
+    return (0, 7, T // 2, T - 1)
+
+
+def run_vsref():
+    """the compiled reference on VSREF_*: field snapshots, result and delay maps of each scene run (scene<i>_*), the material
+    planes after each geometry edit (geometry_beta / geometry_R), the free-field energies (efree)"""
+    d = {}
+    for i, (scene, listener, res, size) in enumerate(VSREF_SCENES):
+        r = pvref.RefSolver(size, size, res, pvref.load_pv(os.path.join(ROOT, "tests", "scenes", scene)))
+        r.generate(listener)
+        r.analyze(listener)
+        d["scene%d_dims" % i] = np.array([r.gx, r.gy, r.T, r.fs], np.int32)
+        d["scene%d_efree" % i] = np.float32(r.efree)
+        d["scene%d_snaps" % i] = np.stack([np.stack(r.snapshot(t)) for t in vsref_snap_ts(r.T)])
+        d["scene%d_results" % i], d["scene%d_delay" % i] = r.results()
+        r.close()
+    r = pvref.RefSolver(25.0, 25.0, 275, None, with_free_grid=False)
+    beta, R = [], []
+    for op, box in VSREF_GEOMETRY:
+        getattr(r, op + "_aabb")(np.array(box, np.float32))
+        b, m = r.material()
+        beta.append(b)
+        R.append(m)
+    r.close()
+    d["geometry_beta"], d["geometry_R"] = np.stack(beta), np.stack(R)
+    efree = []
+    for size, res in VSREF_EFREE:
+        r = pvref.RefSolver(size, size, res, None)
+        efree.append(r.efree)
+        r.close()
+    d["efree"] = np.array(efree, np.float32)
+    path = os.path.join(OUT, "g_vsref.npz")
+    np.savez_compressed(path, **d)
+    print("vsref ->", path, "%.1f kB" % (os.path.getsize(path) / 1e3))
+
+
 def main():
     what = sys.argv[1] if len(sys.argv) > 1 else "small"
     if what == "findgain":
         return run_findgain()
+    if what == "vsref":
+        return run_vsref()
     if what == "cells":
         return run_cells()
     if what == "cfg5":

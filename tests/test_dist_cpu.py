@@ -148,10 +148,12 @@ def test_bench_orchestration_gloo_world8(shape, tmp_path):
     for how, j in lines.items():
         assert j["n_gpus"] == W and j["steps"] == steps and j["scaling"] == "weak"
         assert j["config"]["runs_in_flight_per_gpu"] == inflight
-        assert j["timed_runs"] == 5 * steps * inflight * W and j["verified_runs"] == j["timed_runs"], how
+        # exactly --steps timed steps, in the worker's 3 blocks
+        assert j["timed_runs"] == steps * inflight * W and j["verified_runs"] == j["timed_runs"], how
+        assert j["spread"]["steps_per_block"] == ([1, 1, 1] if steps == 3 else [2, 1, 1])
         assert [r["rank"] for r in j["ranks"]] == list(range(W)) and [r["local_rank"] for r in j["ranks"]] == list(range(W))
         for r in j["ranks"]:
-            assert len(r["block_s"]) == 5 and all(b > 0 for b in r["block_s"])
+            assert len(r["block_s"]) == 3 and all(b > 0 for b in r["block_s"])
             assert ("ncclAllGather" in r["gather"]) == (how == "native") and ("PV_BENCH_GATHER=torch" in r["gather"]) == (how == "torch")
         assert j["value"] == pytest.approx(W * inflight * 4097 * 4097 * 435 * steps / (j["ms_per_step"] * steps * 1e-3), rel=1e-9)
     assert lines["native"]["timed_runs"] == lines["torch"]["timed_runs"]
@@ -183,16 +185,16 @@ def test_bench_orchestration_gloo_world2(comm_mode, tmp_path):
     j = json.loads(lines0[0])
     assert j["n_gpus"] == 2 and j["steps"] == 3 and j["warmup"] == 2 and j["scaling"] == "weak"
     assert j["metric"] == "grid_cell_updates_per_s" and j["higher_is_better"] is True
-    # steps x in flight x ranks, in every one of the 5 timed blocks (bench.py --repeats); every block's records verified
-    assert j["repeats"] == 5 and j["timed_runs"] == 5 * 3 * 2 * 2 and j["verified_runs"] == j["timed_runs"]
+    # steps x in flight x ranks, the 3 steps split into 3 timed blocks (bench.py --repeats); every block's records verified
+    assert j["repeats"] == 3 and j["timed_runs"] == 3 * 2 * 2 and j["verified_runs"] == j["timed_runs"]
     sp = j["spread"]
-    assert sp["repeats"] == 5 and len(sp["ms_per_step_all"]) == 5
+    assert sp["repeats"] == 3 and len(sp["ms_per_step_all"]) == 3 and sp["steps_per_block"] == [1, 1, 1]
     assert sp["ms_per_step_min"] <= sp["ms_per_step_median"] <= sp["ms_per_step_max"]
     assert j["ms_per_step"] == pytest.approx(sp["ms_per_step_median"], rel=1e-9)
     # one record per rank: its own block times, warm-up and communicator set-up seconds, how it gathered
     assert [r["rank"] for r in j["ranks"]] == [0, 1]
     for r in j["ranks"]:
-        assert len(r["block_s"]) == 5 and all(b > 0 for b in r["block_s"])
+        assert len(r["block_s"]) == 3 and all(b > 0 for b in r["block_s"])
         assert r["warmup_s"] >= 0 and r["comm_init_and_first_gather_s"] >= 0
         assert "torch.distributed.all_gather_into_tensor" in r["gather"]
         # stream placement is the library's business (round 5): bench.py only says so
@@ -203,3 +205,41 @@ def test_bench_orchestration_gloo_world2(comm_mode, tmp_path):
     assert j["value"] == pytest.approx(2 * 2 * 4097 * 4097 * 435 * 3 / (j["ms_per_step"] * 3e-3), rel=1e-9)
     assert j["cpu_baseline"] is not None and j["cpu_baseline"]["cores"] == 1 and j["cpu_baseline"]["value"] > 0
     assert j["roofline"]["frac"] > 0
+
+
+def test_bench_runs_exactly_the_steps_asked_and_dumps_the_last(tmp_path, monkeypatch, capsys):
+    """bench.py in one process with the stand-in solver (tests/_bench_worker.py): --warmup W --steps K starts exactly (W + K) x B
+    runs, K of them timed, split over the --repeats blocks; --dump-outputs writes the last step's records and a sample of every
+    solver's maps as float32, under 64 MB, and the same files again when the same arguments are run a second time."""
+    import json
+    import _bench_worker as w
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PV_BENCH_FORCE_DIST"):
+        monkeypatch.delenv(k, raising=False)
+    dumped = []
+    for d in ("a", "b"):
+        w.FakeBenchSolver.runs = 0
+        out = tmp_path / d
+        bench.main(["--steps", "5", "--warmup", "3", "--repeats", "2", "--grid", "2048", "--no-cpu-baseline",
+                    "--dump-outputs", str(out)], hooks=w.CpuHooks("fail"))
+        j = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        B = j["config"]["runs_in_flight_per_gpu"]
+        assert B == 2 and w.FakeBenchSolver.runs == (3 + 5) * B
+        assert j["steps"] == 5 and j["spread"]["steps_per_block"] == [3, 2]
+        assert j["timed_runs"] == 5 * B and j["verified_runs"] == j["timed_runs"]
+        files = sorted(os.listdir(out))
+        assert files == ["delay_sample.npy", "emitter_outputs.npy", "results_sample.npy"]
+        assert sum(os.path.getsize(out / f) for f in files) <= 64e6
+        got = {f: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 for a in got.values())
+        # the last step is step 4: runs 8 and 9, listeners 0 and 1 of bench.LISTENERS
+        want = w.GOLD["emitter_out"][[0, 1]]
+        assert np.array_equal(got["emitter_outputs.npy"], want)
+        res, cells = got["results_sample.npy"], got["delay_sample.npy"]
+        assert res.shape[:2] == cells.shape and cells.shape[0] == B and 0 < cells.shape[1] < 2048 * 2048
+        for b in range(B):
+            assert (res[b] == want[b][0]).all()
+        # (the stand-in's delay map holds each cell's index: the sampled cells, sorted, distinct, the same for every solver)
+        assert (np.diff(cells[0]) > 0).all() and cells[0][-1] < 2048 * 2048 and (cells == cells[0]).all()
+        dumped.append(got)
+    assert all(np.array_equal(dumped[0][f], dumped[1][f]) for f in dumped[0])

@@ -1,85 +1,70 @@
-"""CPU, build container only: the restatement against the compiled reference itself (oracle/_ref/libpvref.so) on
-cases beyond the committed fixtures.  Skipped where the reference build is absent."""
+"""CPU: the restatement against the compiled reference itself (oracle/_ref/libpvref.so) on cases beyond the other
+fixtures.  The reference's outputs for these cases are pinned in tests/golden/g_vsref.npz (tests/golden/make_golden.py
+vsref, which also defines the cases), the FindGain table in g_findgain.npz (make_golden.py findgain)."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
-from conftest import SCENES, same_bits
+from conftest import SCENES, golden, same_bits
 
 from oracle import pvref
 
-pytestmark = pytest.mark.skipif(not pvref.available(), reason="oracle/_ref/libpvref.so not built")
+sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
+from make_golden import VSREF_EFREE, VSREF_GEOMETRY, VSREF_SCENES, findgain_inputs, vsref_snap_ts  # noqa: E402
 
 
-@pytest.mark.parametrize("scene,listener,res,size", [
-    ("MiddleWallScene.pv", (10.0, 0.0, 11.0), 275, 25.0),
-    ("UnityReplicationTest.pv", (4.0, 0.0, 4.5), 275, 25.0),
-    ("SingleWall.pv", (3.0, 0.0, 12.0), 275, 25.0),
-    ("SmallRoom.pv", (5.0, 0.0, 5.0), 275, 10.0),
-    ("ExampleProject.pv", (5.0, 0.0, 2.0), 500, 10.0),
-])
+@pytest.mark.parametrize("scene,listener,res,size", VSREF_SCENES)
 def test_restatement_equals_reference(oracle, scene, listener, res, size):
+    g = golden("g_vsref")
+    key = "scene%d_" % VSREF_SCENES.index((scene, listener, res, size))
     boxes = pvref.load_pv(os.path.join(SCENES, scene))
-    r = pvref.RefSolver(size, size, res, boxes)
     o = oracle.OracleGrid(size, size, res, boxes)
-    assert (r.gx, r.gy, r.T, r.fs) == (o.gx, o.gy, o.T, o.fs)
-    r.generate(listener)
-    r.analyze(listener)
+    assert [o.gx, o.gy, o.T, o.fs] == g[key + "dims"].tolist()
     o.fdtd(listener)
     hp, hx, hy = o.history()
-    for t in (0, 7, o.T // 2, o.T - 1):
-        p, x, y = r.snapshot(t)
+    for t, (p, x, y) in zip(vsref_snap_ts(o.T), g[key + "snaps"]):
         assert same_bits(p, hp[t]).all() and same_bits(x, hx[t]).all() and same_bits(y, hy[t]).all()
     ef = oracle.free_energy(size, size, res)
-    assert ef == r.efree
+    assert np.float32(ef) == g[key + "efree"]
     res8, delay, valid = o.analyze(ef, listener)
-    rres, rdelay = r.results()
+    rres, rdelay = g[key + "results"], g[key + "delay"]
     assert same_bits(delay, rdelay).all()
     for k in range(8):
         m = valid if k not in (4, 5) else np.ones_like(valid)
         assert same_bits(res8[..., k][m], rres[..., k][m]).all(), k
-    r.close()
     o.close()
 
 
 def test_dynamic_geometry_sequence(oracle):
     """Add / Remove / overlapping boxes follow Grid::AddAABB / RemoveAABB incl. quirk Q4 (overlap cleared)"""
-    r = pvref.RefSolver(25.0, 25.0, 275, None, with_free_grid=False)
+    g = golden("g_vsref")
     o = oracle.OracleGrid(25.0, 25.0, 275, None, with_history=False)
-    a = np.array([10, 10, 6, 1, 0.9], np.float32)
-    b = np.array([12, 10, 1, 6, 0.8], np.float32)
-    edge = np.array([24.9, 12, 1, 30, 0.7], np.float32)
-    for op, box in [("add", a), ("add", b), ("remove", a), ("add", edge), ("remove", edge), ("add", a)]:
-        getattr(r, op + "_aabb")(box)
-        getattr(o, op + "_aabb")(box)
-        rb, rR = r.material()
+    for (op, box), rb, rR in zip(VSREF_GEOMETRY, g["geometry_beta"], g["geometry_R"]):
+        getattr(o, op + "_aabb")(np.array(box, np.float32))
         ob, oR = o.material()
         assert np.array_equal(rb, ob) and same_bits(rR, oR).all(), op
-    r.close()
     o.close()
 
 
-@pytest.mark.parametrize("size,res", [(40.0, 275), (31.7, 300), (18.0, 375), (10.0, 275)])
+@pytest.mark.parametrize("size,res", VSREF_EFREE)
 def test_free_energy_incl_truncation_quirk(oracle, size, res):
     """FreeGrid passes its centre cell as metres and GenerateResponse truncates it again (FreeGrid.cpp:84,
     FDTD.cpp:97-98): at 40 m / 275 Hz the source lands one cell off in x AND y and EFree drops to 0.028847
     (SURVEY.md H4).  The restatement must follow the reference through that."""
-    r = pvref.RefSolver(size, size, res, None)
-    assert oracle.free_energy(size, size, res) == r.efree
+    efree = golden("g_vsref")["efree"][VSREF_EFREE.index((size, res))]
+    assert np.float32(oracle.free_energy(size, size, res)) == efree
     if (size, res) == (40.0, 275):
-        assert np.float32(r.efree) == np.float32(0.028847147)
-    r.close()
+        assert efree == np.float32(0.028847147)
 
 
-@pytest.mark.skipif(not pvref.dsp_available(), reason="oracle/_ref/libpvrefdsp.so not built")
 def test_find_gains_equal_compiled_reference(oracle):
     """the oracle's restatement of FindGainA/B/C against the reference's own compiled
-    PvDSPContext.cpp:165-228 (oracle/ref_dsp_harness.cpp), dense sweep incl. the 0.5 / 1.0 / 3.0 s edges"""
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    from make_golden import findgain_inputs
-    for rt, w in findgain_inputs():
-        want = np.array(pvref.find_gains(rt, w), np.float32)
+    PvDSPContext.cpp:165-228 (oracle/ref_dsp_harness.cpp), dense sweep incl. the 0.5 / 1.0 / 3.0 s edges: the committed
+    table must hold exactly that sweep"""
+    g = golden("g_findgain")
+    assert np.array_equal(g["inputs"].view(np.uint32), findgain_inputs().view(np.uint32))
+    for (rt, w), want in zip(g["inputs"], g["gains"]):
         got = np.array(oracle.find_gains(rt, w), np.float32)
         assert same_bits(got, want).all(), (rt, w, got, want)

@@ -42,9 +42,9 @@ bench() {  # bench <name> <gpus> <bench args ...>
   local name=$1 n=$2; shift 2
   port=$((port + 1))
   run "$name" 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $port \
-      bench.py --gpus "$n" --steps 4 --warmup 2 --repeats 3 --no-cpu-baseline --no-dense-leg "$@"
+      bench.py --gpus "$n" --steps 12 --warmup 2 --repeats 3 --no-cpu-baseline --no-dense-leg "$@"
 }
-run bench_1gpu 600 python bench.py --steps 4 --warmup 2 --repeats 3 --no-cpu-baseline --no-dense-leg
+run bench_1gpu 600 python bench.py --steps 12 --warmup 2 --repeats 3 --no-cpu-baseline --no-dense-leg
 for n in 2 $N; do
   [ "$n" -gt "$N" ] && continue
   bench "cfg4_n${n}_native" "$n" --inflight 1

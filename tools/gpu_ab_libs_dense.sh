@@ -5,7 +5,7 @@
 rounds=$1; shift
 for i in $(seq 1 $rounds); do
  for so in "$@"; do
-   echo "$so: $(PLANEVERB_AMD_LIB=$PWD/planeverb_amd/$so python bench.py --no-cpu-baseline --steps 8 --warmup 2 --repeats 3 $BENCH_ARGS 2>/dev/null | python -c "
+   echo "$so: $(PLANEVERB_AMD_LIB=$PWD/planeverb_amd/$so python bench.py --no-cpu-baseline --steps 24 --warmup 2 --repeats 3 $BENCH_ARGS 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

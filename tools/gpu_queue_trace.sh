@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out/r05
 for i in 1 2 3 4 5 6 7 8; do
   rm -rf /tmp/qt_$i
-  rocprofv3 --kernel-trace --output-format csv -d /tmp/qt_$i -o q -- python bench.py --no-cpu-baseline --no-dense-leg --steps 4 --repeats 3 > /tmp/qt_$i.json 2>/dev/null
+  rocprofv3 --kernel-trace --output-format csv -d /tmp/qt_$i -o q -- python bench.py --no-cpu-baseline --no-dense-leg --steps 12 --repeats 3 > /tmp/qt_$i.json 2>/dev/null
   python - /tmp/qt_$i /tmp/qt_$i.json <<'PY'
 import csv, glob, json, sys, collections
 f = glob.glob(sys.argv[1] + "/**/q_kernel_trace.csv", recursive=True)[0]
