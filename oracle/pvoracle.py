@@ -147,11 +147,17 @@ class OracleGrid:
         n = self.T * self.ncell
         return tuple(np.ctypeslib.as_array(p, (n,)).reshape(shp) for p in (g.hist_pr, g.hist_vx, g.hist_vy))
 
-    def analyze(self, efree, listener, offset=(0, 0)):
+    def analyze(self, efree, listener, offset=(0, 0), prev=None):
         """offset != (0, 0): this grid is the window at that cell offset of a larger open grid and `listener` is in
-        the larger grid's metres (pvo_analyze_at)"""
+        the larger grid's metres (pvo_analyze_at).
+        prev: the records [gx, gy, 8] a previous run left (chained runs on one context).  A cell without an onset in this
+        run keeps prev's members 0-3 and 6-7 (Analyzer.cpp:160-165); members 4-5 of every cell are recomputed,
+        and the direction walk reads the stale occlusion of such cells.  None: a fresh context (all zeros)."""
         n = self.gx * self.gy
-        res = np.zeros((n, 8), np.float32)
+        if prev is None:
+            res = np.zeros((n, 8), np.float32)
+        else:
+            res = np.array(prev, np.float32, copy=True).reshape(n, 8)
         delay = np.empty(n, np.float32)
         valid = np.zeros(n, np.uint8)
         lib().pvo_analyze_at(self._g, efree, float(listener[0]), float(listener[2]), int(offset[0]), int(offset[1]),

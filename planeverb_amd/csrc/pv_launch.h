@@ -76,9 +76,10 @@ void launchAnalysis(const AnalyzeArgs& a, hipStream_t stream);
 // the three phases of launchAnalysis separately (slab groups run the middle one per slab, the others on the whole map)
 void launchFarCells(const AnalyzeArgs& a, hipStream_t stream);
 void launchAnalysisFar(const AnalyzeArgs& a, hipStream_t stream);  // launchAnalysis' first pass (the lazy far frame, or every far cell)
-// no-onset cells of the window take the six persistent result planes (occlusion, wet gain, decay time, lowpass, source
-// direction x / y) from another solver's maps (pv_rt60.hip; Solver::run's carryFrom)
-void launchCarryResults(const AnalyzeArgs& a, const float* srcOut, hipStream_t stream);
+// no-onset cells of the window and of the block [srcR0, +srcNR) x [srcC0, +srcNC) (the other solver's last window; srcNR = 0:
+// none) take the six persistent result planes (occlusion, wet gain, decay time, lowpass, source direction x / y) from another
+// solver's maps (pv_rt60.hip; Solver::run's carryFrom)
+void launchCarryResults(const AnalyzeArgs& a, const float* srcOut, int srcR0, int srcC0, int srcNR, int srcNC, hipStream_t stream);
 void launchAnalysisCells(const AnalyzeArgs& a, hipStream_t stream);  // = the three below, one after the other
 void launchOnset(const AnalyzeArgs& a, hipStream_t stream);   // onsets of the window's cells into the delay map
 void launchEncode(const AnalyzeArgs& a, hipStream_t stream);  // dry gain, source direction, low-pass (reads the onsets)

@@ -272,14 +272,24 @@ __global__ __launch_bounds__(PV_RT60_TILE_BLOCK) void pv_rt60_tile_kernel(const 
 
 // Live module with two iterations in flight on two solvers (Solver::run's carryFrom): a cell in which this run found no onset
 // keeps what the PREVIOUS iteration left there (the reference never touches m_results[s] then, Analyzer.cpp:160-165) -- the
-// previous iteration ran on the other solver, so its six persistent planes are copied over for exactly those cells
+// previous iteration ran on the other solver, so its six persistent planes are copied over for exactly those cells.  One pass
+// covers this run's window (nr < 0: the block from the device's DynParams), one the block of the previous iteration's window
+// (r0, c0, nr, nc): the two solvers' maps can differ only where that iteration reached cells, which lie inside its window --
+// also outside this run's window when the window is smaller than the grid and the listener moved far
 namespace {
-__global__ __launch_bounds__(256) void pv_carry_results_kernel(const AnalyzeArgs a, const float* __restrict__ src) {
-    const DynParams dyn = *a.dyn;
+__global__ __launch_bounds__(256) void pv_carry_results_kernel(const AnalyzeArgs a, const float* __restrict__ src, int r0, int c0,
+                                                               int nr, int nc) {
     const int wc = blockIdx.x * blockDim.x + threadIdx.x, wr = blockIdx.y;
-    if (wc >= a.winCols) return;
-    const int X = dyn.histRow0 - a.G + wr, Y = dyn.histCol0 - a.G + wc;
-    if (X >= a.gx || Y >= a.gy) return;
+    int X, Y;
+    if (nr < 0) {
+        const DynParams dyn = *a.dyn;
+        if (wc >= a.winCols) return;
+        X = dyn.histRow0 - a.G + wr, Y = dyn.histCol0 - a.G + wc;
+    } else {
+        if (wc >= nc || wr >= nr) return;
+        X = r0 + wr, Y = c0 + wc;
+    }
+    if (X < 0 || Y < 0 || X >= a.gx || Y >= a.gy) return;
     const long long s = (long long)X * a.gy + Y;
     if (a.delay[s] != FLT_MAX) return;
     a.out[s] = src[s];
@@ -291,8 +301,12 @@ __global__ __launch_bounds__(256) void pv_carry_results_kernel(const AnalyzeArgs
 }
 }  // namespace
 
-void launchCarryResults(const AnalyzeArgs& a, const float* srcOut, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_carry_results_kernel, dim3((a.winCols + 255) / 256, a.winRows), dim3(256), 0, stream, a, srcOut);
+void launchCarryResults(const AnalyzeArgs& a, const float* srcOut, int srcR0, int srcC0, int srcNR, int srcNC, hipStream_t stream) {
+    hipLaunchKernelGGL(pv_carry_results_kernel, dim3((a.winCols + 255) / 256, a.winRows), dim3(256), 0, stream, a, srcOut, 0, 0, -1,
+                       0);
+    if (srcNR > 0 && srcNC > 0)
+        hipLaunchKernelGGL(pv_carry_results_kernel, dim3((unsigned)((srcNC + 255) / 256), (unsigned)srcNR), dim3(256), 0, stream, a,
+                           srcOut, srcR0, srcC0, srcNR, srcNC);
 }
 
 // One launch for the sixteen- and four-lane forms, one more for the lane-per-cell form where the caller expects it to be the one

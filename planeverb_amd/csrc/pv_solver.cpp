@@ -1488,7 +1488,13 @@ void Solver::enqueueAnalysis(float lx, float lz) {
         launchEncode(a, stream_);
         launchRt60(a, stream_);
     }
-    if (carry) launchCarryResults(a, carryFrom_->res_, stream_);
+    if (carry) {
+        // (the other solver's run is the iteration before this one: its window holds every cell it reached)
+        Block w = carryFrom_->dynValid_ ? carryFrom_->curWindow() : Block{};
+        const Block mine = curWindow();
+        if (w.r0 == mine.r0 && w.c0 == mine.c0 && w.nr == mine.nr && w.nc == mine.nc) w = Block{};  // (the first pass covers it)
+        launchCarryResults(a, carryFrom_->res_, w.r0, w.c0, w.nr, w.nc, stream_);
+    }
     launchAnalysisDirection(a, stream_);
     if (fork) hipStreamWaitEvent(stream_, anaEv_[1], 0);
     if (lazyFar_) {

@@ -633,8 +633,9 @@ def test_closed_room_isolation_4096(pvlib):
         assert (delay[1000:, :] > 1e30).all() and (delay[:, 1000:] > 1e30).all()
 
 
-def test_second_run_reuses_solver(pvlib):
-    """two consecutive runs with different listeners on one solver == fresh solvers (history window moves)"""
+def test_second_run_reuses_solver(pvlib, oracle):
+    """two consecutive runs with different listeners on one solver == fresh solvers (history window moves); every record of
+    the second run equals the oracle chain's (cells without an onset keep the first run's)"""
     ga, gb = golden("g71_smallroom"), golden("g71_smallroom_L2")
     with pvlib.Solver(25.0, 25.0, 275) as s:
         for b in ga["boxes"]:
@@ -650,6 +651,16 @@ def test_second_run_reuses_solver(pvlib):
         m = valid_mask(gb["delay"], 435, 1443)
         assert same_bits(res[..., 0][m], gb["results"][..., 0][m]).all()
         assert same_bits(res[..., 1][m], gb["results"][..., 1][m]).all()
+    # all eight members on every cell against the oracle chain (OracleGrid.analyze(prev=...))
+    o = oracle.OracleGrid(25.0, 25.0, 275, ga["boxes"])
+    o.fdtd(ga["listener"])
+    ra, da, _ = o.analyze(ga["efree"], ga["listener"])
+    o.fdtd(gb["listener"])
+    rb, db, _ = o.analyze(ga["efree"], gb["listener"], prev=ra)
+    o.close()
+    assert same_bits(delay, db).all()
+    for k, nm in enumerate(NAMES):
+        assert same_bits(res[..., k], rb[..., k]).all(), "%s: %d cells differ" % (nm, int((~same_bits(res[..., k], rb[..., k])).sum()))
 
 
 @pytest.mark.parametrize("size,res,want", [(40.0, 275, 0.028847147), (25.0, 275, 0.0447895788),
