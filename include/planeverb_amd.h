@@ -79,6 +79,19 @@ PVA_EXPORT void PlaneverbRemoveGeometry(int id);
 /* PlaneverbUnity.cpp:131-135 */
 PVA_EXPORT void PlaneverbSetListenerPosition(float x, float y, float z);
 
+/* Extensions next to the geometry calls (no reference counterpart): oriented boxes and convex polygons, the shape model of
+ * PvAmdAddShape below.  Their ids are a table of their own (not the AABB ids).  Queued like the AABB calls and applied at the
+ * same iteration boundary, in call order.  Add returns -1 for a refused shape (PvAmdLastError says why); Update and Remove of
+ * an unknown id, or Update with a refused shape, do nothing. */
+PVA_EXPORT int PlaneverbAddOrientedGeometry(float posX, float posY, float width, float height, float axisX, float axisY,
+                                            float absorption);
+PVA_EXPORT void PlaneverbUpdateOrientedGeometry(int id, float posX, float posY, float width, float height, float axisX,
+                                                float axisY, float absorption);
+PVA_EXPORT void PlaneverbRemoveOrientedGeometry(int id);
+PVA_EXPORT int PlaneverbAddPolygonGeometry(const float* xy, int n, float absorption);
+PVA_EXPORT void PlaneverbUpdatePolygonGeometry(int id, const float* xy, int n, float absorption);
+PVA_EXPORT void PlaneverbRemovePolygonGeometry(int id);
+
 /* Extensions to the live module (not in the reference's flat ABI) */
 /* One sample of an impulse response as the reference stores it (Cell, PvTypes.h:106-121: 16 bytes) */
 typedef struct PlaneverbCell {
@@ -256,8 +269,46 @@ PVA_EXPORT int PvAmdUpdateGeometry(PvAmdSolver* s, int id, float posX, float pos
                                    float absorption);
 PVA_EXPORT int PvAmdRemoveGeometry(PvAmdSolver* s, int id);
 PVA_EXPORT int PvAmdLoadScene(PvAmdSolver* s, const char* pvPath);
-/* Write the current boxes as a .pv file (Editor.cpp:219-243) */
+/* Write the current boxes as a .pv file (Editor.cpp:219-243).  The .pv format is the reference's and holds axis-aligned
+ * boxes only: shapes are not written. */
 PVA_EXPORT int PvAmdSaveScene(PvAmdSolver* s, const char* pvPath);
+
+/* Shapes (no reference counterpart).
+ *
+ * A shape is a convex polygon of 3 to 8 vertices xy[2n] = {x0, y0, x1, y1, ...} in grid metres (x = grid x = world x,
+ * y = grid y = world z, as for the AABBs) with an absorption value.  Refused (-1, PvAmdLastError): a non-finite coordinate or
+ * absorption, fewer than 3 or more than 8 vertices, zero area, a non-convex (or self-intersecting) list.  A clockwise list is
+ * reversed to counter-clockwise.  Absorption is accepted by the rule of PvAmdAddGeometry (any finite value).
+ *
+ * Coverage: cell (x, y), 0 <= x < gx, 0 <= y < gy, is covered when its centre P = (((float)x + 0.5f) * dx,
+ * ((float)y + 0.5f) * dx) satisfies (e.x * (P.y - a.y)) - (e.y * (P.x - a.x)) >= 0 for every edge a -> b, e = b - a, all in
+ * float32 without contraction.  The ghost row and column are never covered.  This is a cell-CENTRE rule, not the reference's
+ * truncation rule for AABBs: an axis-aligned oriented box need not cover the cells of the AABB with the same numbers.
+ *
+ * Composition: shapes are a layer on top of the AABB layer, which stays exactly what it is (quirks included).  A covered cell
+ * is a wall (b = by = 0) with the absorption of the covering shape added or updated most recently; an uncovered cell has
+ * the AABB layer's material.  Removing or moving a shape brings back the AABB layer beneath it: the layer is a pure function
+ * of the current set of shapes.  Shape ids are their own table, recycled last-in first-out like the AABB ids.
+ * PvAmdCopyMaterial and the b / by of PvAmdGetImpulseResponseCells report the composed material.  A solver that never has a
+ * shape runs exactly as before.  Slab groups (PvAmdCreateSlabs) take shapes; slab ranks (PvAmdCreateSlabRank) refuse them. */
+PVA_EXPORT int PvAmdAddShape(PvAmdSolver* s, const float* xy, int n, float absorption);
+PVA_EXPORT int PvAmdUpdateShape(PvAmdSolver* s, int id, const float* xy, int n, float absorption);
+PVA_EXPORT int PvAmdRemoveShape(PvAmdSolver* s, int id);
+/* An oriented box: centre (px, py), full width w along the axis (ax, ay) and full height h along its left normal.  A Unity
+ * caller passes transform.right.x / .z as the axis.  u = (ax, ay) * inv with inv = 1.0f / sqrtf(ax*ax + ay*ay), v = (-u.y, u.x),
+ * vertices (c - w/2 u - h/2 v, c + w/2 u - h/2 v, c + w/2 u + h/2 v, c - w/2 u + h/2 v), as PvAmdHostOrientedBoxVertices
+ * returns them.  A zero axis is refused. */
+PVA_EXPORT int PvAmdAddOrientedBox(PvAmdSolver* s, float px, float py, float w, float h, float ax, float ay, float absorption);
+PVA_EXPORT int PvAmdUpdateOrientedBox(PvAmdSolver* s, int id, float px, float py, float w, float h, float ax, float ay,
+                                      float absorption);
+/* CPU only: the four vertices out8 the library uses for that oriented box (0, or -1 for a refused input) */
+PVA_EXPORT int PvAmdHostOrientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float* out8);
+/* CPU only: the shape the library makes of a vertex list (counter-clockwise, out16 gets 2n floats); returns n, or -1 for a
+ * refused list (PvAmdLastError) */
+PVA_EXPORT int PvAmdHostShape(const float* xy, int n, float absorption, float* out16);
+/* CPU only: the coverage rule on a grid of that configuration: cover[(gx+1)*(gy+1)] = 1 for the cells the shape covers */
+PVA_EXPORT int PvAmdHostShapeCoverage(float gridSizeX, float gridSizeY, int gridResolution, const float* xy, int n,
+                                      uint8_t* cover);
 
 /* One iteration of the reference's background loop (PvContext.cpp:80-83): GenerateResponse + AnalyzeResponses
  * for a listener position; synchronous. */
@@ -319,7 +370,7 @@ PVA_EXPORT int PvAmdCopyFields(PvAmdSolver* s, float* pr, float* vx, float* vy);
 PVA_EXPORT int PvAmdCopyHistoryPlane(PvAmdSolver* s, int t, float* pr);
 /* Gaussian pulse table (Grid.cpp:12-27), T floats */
 PVA_EXPORT int PvAmdCopyPulse(PvAmdSolver* s, float* out);
-/* Material planes after rasterisation: beta (uint8) and R (float), (gx+1)*(gy+1) each */
+/* Material planes after rasterisation: beta (uint8) and R (float), (gx+1)*(gy+1) each (with shapes: the composed material) */
 PVA_EXPORT int PvAmdCopyMaterial(PvAmdSolver* s, uint8_t* beta, float* R);
 /* Overwrite the fields the NEXT PvAmdRunSteps starts from (test / benchmark hook; reference order) */
 PVA_EXPORT int PvAmdSetFields(PvAmdSolver* s, const float* pr, const float* vx, const float* vy);

@@ -110,6 +110,12 @@ SYMBOLS = {
     "PlaneverbUpdateGeometry": (None, [C.c_int] + [C.c_float] * 5),
     "PlaneverbRemoveGeometry": (None, [C.c_int]),
     "PlaneverbSetListenerPosition": (None, [C.c_float] * 3),
+    "PlaneverbAddOrientedGeometry": (C.c_int, [C.c_float] * 7),
+    "PlaneverbUpdateOrientedGeometry": (None, [C.c_int] + [C.c_float] * 7),
+    "PlaneverbRemoveOrientedGeometry": (None, [C.c_int]),
+    "PlaneverbAddPolygonGeometry": (C.c_int, [_fp, C.c_int, C.c_float]),
+    "PlaneverbUpdatePolygonGeometry": (None, [C.c_int, _fp, C.c_int, C.c_float]),
+    "PlaneverbRemovePolygonGeometry": (None, [C.c_int]),
     "PlaneverbLoadScene": (C.c_int, [C.c_char_p]),
     "PlaneverbIterationCount": (C.c_longlong, []),
     "PlaneverbWaitIterations": (C.c_longlong, [C.c_longlong, C.c_int]),
@@ -153,6 +159,14 @@ SYMBOLS = {
     "PvAmdRemoveGeometry": (C.c_int, [_vp, C.c_int]),
     "PvAmdLoadScene": (C.c_int, [_vp, C.c_char_p]),
     "PvAmdSaveScene": (C.c_int, [_vp, C.c_char_p]),
+    "PvAmdAddShape": (C.c_int, [_vp, _fp, C.c_int, C.c_float]),
+    "PvAmdUpdateShape": (C.c_int, [_vp, C.c_int, _fp, C.c_int, C.c_float]),
+    "PvAmdRemoveShape": (C.c_int, [_vp, C.c_int]),
+    "PvAmdAddOrientedBox": (C.c_int, [_vp] + [C.c_float] * 7),
+    "PvAmdUpdateOrientedBox": (C.c_int, [_vp, C.c_int] + [C.c_float] * 7),
+    "PvAmdHostOrientedBoxVertices": (C.c_int, [C.c_float] * 6 + [_fp]),
+    "PvAmdHostShape": (C.c_int, [_fp, C.c_int, C.c_float, _fp]),
+    "PvAmdHostShapeCoverage": (C.c_int, [C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
     "PvAmdRun": (C.c_int, [_vp] + [C.c_float] * 3),
     "PvAmdRunAsync": (C.c_int, [_vp] + [C.c_float] * 3),
     "PvAmdRunAsyncAfter": (C.c_int, [_vp, _vp] + [C.c_float] * 3),
@@ -302,6 +316,42 @@ def RemoveGeometry(gid):
     lib().PlaneverbRemoveGeometry(int(gid))
 
 
+def _xy(vertices):
+    """vertex list [(x, y), ...] or flat [x0, y0, ...] -> (contiguous float32 array, n)"""
+    a = np.ascontiguousarray(vertices, np.float32).reshape(-1)
+    if a.size % 2:
+        raise ValueError("vertex list with an odd number of coordinates")
+    return a, a.size // 2
+
+
+def AddOrientedGeometry(box):
+    """box = (posX, posY, width, height, axisX, axisY, absorption): an oriented box (shape ids, not AABB ids); -1 if refused"""
+    return lib().PlaneverbAddOrientedGeometry(*[float(v) for v in box])
+
+
+def UpdateOrientedGeometry(sid, box):
+    lib().PlaneverbUpdateOrientedGeometry(int(sid), *[float(v) for v in box])
+
+
+def RemoveOrientedGeometry(sid):
+    lib().PlaneverbRemoveOrientedGeometry(int(sid))
+
+
+def AddPolygonGeometry(vertices, absorption):
+    """a convex polygon of 3..8 vertices in grid metres (shape ids); -1 if refused"""
+    a, n = _xy(vertices)
+    return lib().PlaneverbAddPolygonGeometry(_f(a), n, float(absorption))
+
+
+def UpdatePolygonGeometry(sid, vertices, absorption):
+    a, n = _xy(vertices)
+    lib().PlaneverbUpdatePolygonGeometry(int(sid), _f(a), n, float(absorption))
+
+
+def RemovePolygonGeometry(sid):
+    lib().PlaneverbRemovePolygonGeometry(int(sid))
+
+
 def SetListenerPosition(pos):
     lib().PlaneverbSetListenerPosition(*[float(v) for v in pos])
 
@@ -369,6 +419,33 @@ def host_rasterize(size_x, size_y, res, boxes, ops=None):
                                     ops_a.ctypes.data_as(C.POINTER(C.c_int)), len(boxes),
                                     beta.ctypes.data_as(C.POINTER(C.c_ubyte)), _f(R)))
     return beta, R
+
+
+def host_oriented_box_vertices(px, py, w, h, ax, ay):
+    """the 4 counter-clockwise vertices (4 x 2 float32) the library makes of an oriented box"""
+    out = np.empty(8, np.float32)
+    _check(lib().PvAmdHostOrientedBoxVertices(float(px), float(py), float(w), float(h), float(ax), float(ay), _f(out)))
+    return out.reshape(4, 2)
+
+
+def host_shape(vertices, absorption=0.0):
+    """the shape the library makes of a vertex list: n x 2 float32, counter-clockwise (PlaneverbError if refused)"""
+    a, n = _xy(vertices)
+    out = np.empty(16, np.float32)
+    m = lib().PvAmdHostShape(_f(a), n, float(absorption), _f(out))
+    if m < 0:
+        raise PlaneverbError(last_error())
+    return out[:2 * m].reshape(m, 2)
+
+
+def host_shape_coverage(size_x, size_y, res, vertices):
+    """the cells (gx+1) x (gy+1) the shape covers on a grid of that configuration (uint8)"""
+    i = host_grid_info(size_x, size_y, res)
+    a, n = _xy(vertices)
+    cover = np.empty((i.gx + 1, i.gy + 1), np.uint8)
+    _check(lib().PvAmdHostShapeCoverage(float(size_x), float(size_y), int(res), _f(a), n,
+                                        cover.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return cover
 
 
 def load_pv(path, max_boxes=4096):
@@ -705,6 +782,32 @@ class Solver:
 
     def remove_geometry(self, gid):
         _check(lib().PvAmdRemoveGeometry(self._h, int(gid)))
+
+    def add_shape(self, vertices, absorption):
+        """a convex polygon of 3..8 vertices (grid metres); returns its shape id (PlaneverbError if refused)"""
+        a, n = _xy(vertices)
+        sid = lib().PvAmdAddShape(self._h, _f(a), n, float(absorption))
+        if sid < 0:
+            raise PlaneverbError(last_error())
+        return sid
+
+    def add_oriented_box(self, px, py, w, h, ax, ay, absorption):
+        """an oriented box: centre, full width along the axis (ax, ay), full height; returns its shape id"""
+        sid = lib().PvAmdAddOrientedBox(self._h, float(px), float(py), float(w), float(h), float(ax), float(ay), float(absorption))
+        if sid < 0:
+            raise PlaneverbError(last_error())
+        return sid
+
+    def update_shape(self, sid, vertices, absorption):
+        a, n = _xy(vertices)
+        _check(lib().PvAmdUpdateShape(self._h, int(sid), _f(a), n, float(absorption)))
+
+    def update_oriented_box(self, sid, px, py, w, h, ax, ay, absorption):
+        _check(lib().PvAmdUpdateOrientedBox(self._h, int(sid), float(px), float(py), float(w), float(h), float(ax), float(ay),
+                                            float(absorption)))
+
+    def remove_shape(self, sid):
+        _check(lib().PvAmdRemoveShape(self._h, int(sid)))
 
     def run(self, listener):
         _check(lib().PvAmdRun(self._h, *[float(v) for v in listener]))

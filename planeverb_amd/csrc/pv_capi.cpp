@@ -177,6 +177,47 @@ void PlaneverbRemoveGeometry(int id) try {
     if (c) c->removeGeometry(id);
 } PV_API_CATCH_VOID
 
+// shapes in the live module (pv_core.h makeShape / orientedBoxVertices), queued like the AABB changes (pv_context.cpp)
+static bool orientedShape(float px, float py, float w, float h, float ax, float ay, float absorption, Shape* out) {
+    float v[8];
+    return orientedBoxVertices(px, py, w, h, ax, ay, v, &g_lastError) && makeShape(v, 4, absorption, out, &g_lastError);
+}
+
+int PlaneverbAddOrientedGeometry(float posX, float posY, float width, float height, float axisX, float axisY, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    return (c && orientedShape(posX, posY, width, height, axisX, axisY, absorption, &sh)) ? c->addShape(sh) : -1;
+} PV_API_CATCH(-1)
+
+void PlaneverbUpdateOrientedGeometry(int id, float posX, float posY, float width, float height, float axisX, float axisY,
+                                     float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    if (c && orientedShape(posX, posY, width, height, axisX, axisY, absorption, &sh)) c->updateShape(id, sh);
+} PV_API_CATCH_VOID
+
+void PlaneverbRemoveOrientedGeometry(int id) try {
+    Context::Ref c;
+    if (c) c->removeShape(id);
+} PV_API_CATCH_VOID
+
+int PlaneverbAddPolygonGeometry(const float* xy, int n, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    return (c && makeShape(xy, n, absorption, &sh, &g_lastError)) ? c->addShape(sh) : -1;
+} PV_API_CATCH(-1)
+
+void PlaneverbUpdatePolygonGeometry(int id, const float* xy, int n, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    if (c && makeShape(xy, n, absorption, &sh, &g_lastError)) c->updateShape(id, sh);
+} PV_API_CATCH_VOID
+
+void PlaneverbRemovePolygonGeometry(int id) try {
+    Context::Ref c;
+    if (c) c->removeShape(id);
+} PV_API_CATCH_VOID
+
 void PlaneverbSetListenerPosition(float x, float y, float z) try {
     Context::Ref c;
     if (c) c->setListener(x, y, z);
@@ -585,6 +626,54 @@ int PvAmdSaveScene(PvAmdSolver* h, const char* pvPath) try {
     return savePv(pvPath, h->s->boxes(), &g_lastError) ? 0 : -1;
 } PV_API_CATCH(-1)
 
+// shapes (pv_core.h makeShape; Solver::addShape, SlabGroup::addShape).  A slab rank handle refuses them.
+static bool shapesOk(PvAmdSolver* h) {
+    if (h && h->opt.slabCount > 1) {
+        g_lastError = "shapes are not available on a slab rank handle (PvAmdCreateSlabRank): use PvAmdCreateSlabs";
+        return false;
+    }
+    return ensure(h, true);
+}
+
+static int addShape(PvAmdSolver* h, const Shape& sh) {
+    const int id = h->g ? h->g->addShape(sh) : h->s->addShape(sh);
+    if (id < 0) ret(h, false);
+    return id;
+}
+
+int PvAmdAddShape(PvAmdSolver* h, const float* xy, int n, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !makeShape(xy, n, absorption, &sh, &g_lastError)) return -1;
+    return addShape(h, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdUpdateShape(PvAmdSolver* h, int id, const float* xy, int n, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !makeShape(xy, n, absorption, &sh, &g_lastError)) return -1;
+    return ret(h, h->g ? h->g->updateShape(id, sh) : h->s->updateShape(id, sh));
+} PV_API_CATCH(-1)
+
+int PvAmdRemoveShape(PvAmdSolver* h, int id) try {
+    if (!shapesOk(h)) return -1;
+    return ret(h, h->g ? h->g->removeShape(id) : h->s->removeShape(id));
+} PV_API_CATCH(-1)
+
+int PvAmdAddOrientedBox(PvAmdSolver* h, float px, float py, float w, float hgt, float ax, float ay, float absorption) try {
+    float v[8];
+    Shape sh;
+    if (!shapesOk(h) || !orientedBoxVertices(px, py, w, hgt, ax, ay, v, &g_lastError) || !makeShape(v, 4, absorption, &sh, &g_lastError))
+        return -1;
+    return addShape(h, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdUpdateOrientedBox(PvAmdSolver* h, int id, float px, float py, float w, float hgt, float ax, float ay, float absorption) try {
+    float v[8];
+    Shape sh;
+    if (!shapesOk(h) || !orientedBoxVertices(px, py, w, hgt, ax, ay, v, &g_lastError) || !makeShape(v, 4, absorption, &sh, &g_lastError))
+        return -1;
+    return ret(h, h->g ? h->g->updateShape(id, sh) : h->s->updateShape(id, sh));
+} PV_API_CATCH(-1)
+
 int PvAmdRun(PvAmdSolver* h, float lx, float ly, float lz) try {
     if (!wholeGrid(h) || !ensure(h, true)) return -1;
     if (h->g) return ret(h, h->g->run(lx, ly, lz));
@@ -901,6 +990,29 @@ int PvAmdHostRasterize(float sx, float sy, int res, const float* b5, const int* 
     const size_t cells = (size_t)g.NX * g.NY;
     if (beta) std::memcpy(beta, m.beta().data(), cells);
     if (R) std::memcpy(R, m.R().data(), cells * sizeof(float));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostOrientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float* out8) try {
+    return (out8 && orientedBoxVertices(px, py, w, h, ax, ay, out8, &g_lastError)) ? 0 : -1;
+} PV_API_CATCH(-1)
+
+int PvAmdHostShape(const float* xy, int n, float absorption, float* out16) try {
+    Shape sh;
+    if (!out16 || !makeShape(xy, n, absorption, &sh, &g_lastError)) return -1;
+    std::memcpy(out16, sh.xy, (size_t)2 * sh.n * sizeof(float));
+    return sh.n;
+} PV_API_CATCH(-1)
+
+int PvAmdHostShapeCoverage(float sx, float sy, int res, const float* xy, int n, uint8_t* cover) try {
+    Shape sh;
+    if (res < kLowResolution || !cover || !makeShape(xy, n, 0.f, &sh, &g_lastError)) return -1;
+    const GridSpec g = makeGridSpec(sx, sy, res);
+    std::memset(cover, 0, (size_t)g.NX * g.NY);
+    int x0, x1, y0, y1;
+    shapeCellBounds(sh, g, &x0, &x1, &y0, &y1);
+    for (int x = x0; x < x1; ++x)
+        for (int y = y0; y < y1; ++y) cover[(size_t)x * g.NY + y] = shapeCovers(sh, g.dx, x, y) ? 1 : 0;
     return 0;
 } PV_API_CATCH(-1)
 

@@ -586,7 +586,7 @@ int Context::addGeometry(const Box& b) {
         geometryFree_.pop_back();
         geometry_[(size_t)id] = b;
     }
-    changes_.push_back({true, b});
+    changes_.push_back({true, b, -1, Shape{}});
     return id;
 }
 
@@ -595,7 +595,7 @@ void Context::removeGeometry(int id) {
     if (id < 0 || id >= (int)geometry_.size()) return;
     ensureRoom(changes_, 1);
     ensureRoom(geometryFree_, 1);
-    changes_.push_back({false, geometry_[(size_t)id]});  // GeometryManager.cpp:101-110
+    changes_.push_back({false, geometry_[(size_t)id], -1, Shape{}});  // GeometryManager.cpp:101-110
     geometry_[(size_t)id] = Box{0, 0, 0, 0, 0};
     geometryFree_.push_back(id);
 }
@@ -605,9 +605,60 @@ void Context::updateGeometry(int id, const Box& b) {
     std::lock_guard<std::mutex> lock(geomMutex_);
     if (id < 0 || id >= (int)geometry_.size()) return;
     ensureRoom(changes_, 2);
-    changes_.push_back({false, geometry_[(size_t)id]});  // GeometryManager.cpp:112-121
+    changes_.push_back({false, geometry_[(size_t)id], -1, Shape{}});  // GeometryManager.cpp:112-121
     geometry_[(size_t)id] = b;
-    changes_.push_back({true, b});
+    changes_.push_back({true, b, -1, Shape{}});
+}
+
+int Context::addShape(const Shape& sh) {
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    ensureRoom(changes_, 1);
+    ensureRoom(shapeUsed_, 1);
+    int id;
+    if (shapeFree_.empty()) {
+        id = (int)shapeUsed_.size();
+        shapeUsed_.push_back(1);
+    } else {
+        id = shapeFree_.back();
+        shapeFree_.pop_back();
+        shapeUsed_[(size_t)id] = 1;
+    }
+    changes_.push_back({true, Box{0, 0, 0, 0, 0}, id, sh});
+    return id;
+}
+
+void Context::updateShape(int id, const Shape& sh) {
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    if (id < 0 || id >= (int)shapeUsed_.size() || !shapeUsed_[(size_t)id]) return;
+    ensureRoom(changes_, 1);
+    changes_.push_back({true, Box{0, 0, 0, 0, 0}, id, sh});
+}
+
+void Context::removeShape(int id) {
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    if (id < 0 || id >= (int)shapeUsed_.size() || !shapeUsed_[(size_t)id]) return;
+    ensureRoom(changes_, 1);
+    ensureRoom(shapeFree_, 1);
+    changes_.push_back({false, Box{0, 0, 0, 0, 0}, id, Shape{}});
+    shapeUsed_[(size_t)id] = 0;
+    shapeFree_.push_back(id);
+}
+
+void Context::applyChange(Solver* s, const Change& c) {
+    if (c.shapeId >= 0) {
+#ifndef PVA_HOST_TEST  // (the HIP-less fake has no shape layer)
+        // (a failure here -- the device allocation of the first shape -- surfaces as the solver's error at its next run)
+        if (c.add)
+            s->shapeSet(c.shapeId, c.shape);
+        else
+            s->shapeClear(c.shapeId);
+#endif
+        return;
+    }
+    if (c.add)  // GeometryManager.cpp:123-152
+        s->rasterAdd(c.box);
+    else
+        s->rasterRemove(c.box);
 }
 
 void Context::pushGeometryChanges() {
@@ -620,22 +671,12 @@ void Context::pushGeometryChanges() {
         for (auto& pend : pending_) pend.insert(pend.end(), q.begin(), q.end());
         return;
     }
-    for (const Change& c : q) {  // GeometryManager.cpp:123-152, applied in queue order
-        if (c.add)
-            solver_->rasterAdd(c.box);
-        else
-            solver_->rasterRemove(c.box);
-    }
+    for (const Change& c : q) applyChange(solver_, c);  // GeometryManager.cpp:123-152, applied in queue order
 }
 
 void Context::applyPending(const int k) {
     Solver* s = k == 0 ? solver_ : solver2_;
-    for (const Change& c : pending_[k]) {
-        if (c.add)
-            s->rasterAdd(c.box);
-        else
-            s->rasterRemove(c.box);
-    }
+    for (const Change& c : pending_[k]) applyChange(s, c);
     pending_[k].clear();
 }
 

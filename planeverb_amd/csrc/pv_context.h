@@ -86,6 +86,10 @@ public:
     int addGeometry(const Box& b);
     void updateGeometry(int id, const Box& b);
     void removeGeometry(int id);
+    // shapes (pv_core.h Shape, already validated): ids of their own, recycled LIFO; queued with the AABB changes
+    int addShape(const Shape& sh);
+    void updateShape(int id, const Shape& sh);
+    void removeShape(int id);
 
     void setListener(float x, float y, float z);  // PvContext.cpp:50-56
     // Planeverb::GetImpulseResponse (FDTD.cpp:60-70): the IR of the last COMPLETED iteration at a world position as
@@ -170,9 +174,14 @@ private:
     struct Change {
         bool add;
         Box box;
+        int shapeId;  // >= 0: slot shapeId of the shape table takes `shape` (add) or is emptied; box unused
+        Shape shape;
     };
+    static void applyChange(Solver* s, const Change& c);
     std::vector<Box> geometry_;
     std::vector<int> geometryFree_;
+    std::vector<uint8_t> shapeUsed_;
+    std::vector<int> shapeFree_;
     std::vector<Change> changes_;
     std::vector<Change> pending_[2];  // pipelined mode: drained from the queue, not yet rasterised into solver k
     std::mutex geomMutex_;

@@ -142,6 +142,110 @@ void MaterialPlane::init(const GridSpec& g) {
     markAllDirty();
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// shapes
+// ---------------------------------------------------------------------------------------------------------------
+
+bool makeShape(const float* xy, int n, float R, Shape* out, std::string* err) {
+    auto refuse = [&](const char* why) {
+        if (err) *err = why;
+        return false;
+    };
+    if (!xy) return refuse("shape: no vertex list");
+    if (n < 3 || n > kShapeMaxVerts) return refuse("shape: 3 to 8 vertices");
+    if (!std::isfinite(R)) return refuse("shape with a non-finite absorption");
+    for (int i = 0; i < 2 * n; ++i)
+        if (!std::isfinite(xy[i])) return refuse("shape with a non-finite coordinate");
+    // signed area and the turn at every vertex in double: a product of two floats is exact there, differences nearly so
+    double area = 0, turnSum = 0;
+    int pos = 0, neg = 0;
+    for (int i = 0; i < n; ++i) {
+        const int j = (i + 1) % n, k = (i + 2) % n;
+        const double ax = xy[2 * i], ay = xy[2 * i + 1], bx = xy[2 * j], by = xy[2 * j + 1], cx = xy[2 * k], cy = xy[2 * k + 1];
+        area += ax * by - bx * ay;
+        const double ux = bx - ax, uy = by - ay, vx = cx - bx, vy = cy - by;
+        const double cr = ux * vy - uy * vx;
+        pos += cr > 0;
+        neg += cr < 0;
+        turnSum += std::atan2(cr, ux * vx + uy * vy);
+    }
+    if (!(area != 0) || !std::isfinite(area)) return refuse("shape with zero area");
+    // convex and simple: every turn one way (collinear vertices allowed), and the turns add up to one revolution (a pentagram's
+    // add up to two)
+    if ((pos && neg) || std::fabs(std::fabs(turnSum) - 2 * M_PI) > 1e-3) return refuse("shape: the vertex list is not convex");
+    Shape s;
+    s.n = n;
+    s.R = R;
+    for (int i = 0; i < n; ++i) {
+        const int src = area > 0 ? i : n - 1 - i;  // clockwise lists are reversed
+        s.xy[2 * i] = xy[2 * src];
+        s.xy[2 * i + 1] = xy[2 * src + 1];
+    }
+    *out = s;
+    return true;
+}
+
+bool orientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float out8[8], std::string* err) {
+    if (!(std::isfinite(px) && std::isfinite(py) && std::isfinite(w) && std::isfinite(h) && std::isfinite(ax) && std::isfinite(ay))) {
+        if (err) *err = "oriented box with a non-finite input";
+        return false;
+    }
+    const float len2 = ax * ax + ay * ay;
+    if (!(len2 > 0.f) || !std::isfinite(len2)) {
+        if (err) *err = "oriented box with a zero (or too long) axis";
+        return false;
+    }
+    const float inv = 1.0f / std::sqrt(len2);
+    const float ux = ax * inv, uy = ay * inv;
+    const float vx = -uy, vy = ux;
+    const float hw = w / 2.f, hh = h / 2.f;
+    const float wx = hw * ux, wy = hw * uy, hx = hh * vx, hy = hh * vy;
+    // c - w u - h v, c + w u - h v, c + w u + h v, c - w u + h v: counter-clockwise for w, h > 0
+    out8[0] = (px - wx) - hx;
+    out8[1] = (py - wy) - hy;
+    out8[2] = (px + wx) - hx;
+    out8[3] = (py + wy) - hy;
+    out8[4] = (px + wx) + hx;
+    out8[5] = (py + wy) + hy;
+    out8[6] = (px - wx) + hx;
+    out8[7] = (py - wy) + hy;
+    return true;
+}
+
+bool shapeCovers(const Shape& s, float dx, int x, int y) {
+    const float px = ((float)x + 0.5f) * dx, py = ((float)y + 0.5f) * dx;
+    for (int i = 0; i < s.n; ++i) {
+        const int j = i + 1 == s.n ? 0 : i + 1;
+        const float ax = s.xy[2 * i], ay = s.xy[2 * i + 1];
+        const float ex = s.xy[2 * j] - ax, ey = s.xy[2 * j + 1] - ay;
+        if (!((ex * (py - ay)) - (ey * (px - ax)) >= 0.f)) return false;
+    }
+    return true;
+}
+
+void shapeCellBounds(const Shape& s, const GridSpec& g, int* x0, int* x1, int* y0, int* y1) {
+    double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL}, m = std::max(g.gsx, g.gsy) * (double)g.dx;
+    for (int i = 0; i < s.n; ++i)
+        for (int a = 0; a < 2; ++a) {
+            lo[a] = std::min(lo[a], (double)s.xy[2 * i + a]);
+            hi[a] = std::max(hi[a], (double)s.xy[2 * i + a]);
+            m = std::max(m, std::fabs((double)s.xy[2 * i + a]));
+        }
+    // the float32 edge function can accept a centre up to ~16 ulp(m) outside an edge: 2 cells plus that, in cells
+    const double pad = 2.0 + std::ceil(m * 4e-6 / g.dx);
+    const int n[2] = {g.gx, g.gy};
+    int r[4];
+    for (int a = 0; a < 2; ++a) {
+        const double c0 = std::floor(lo[a] / g.dx - 0.5 - pad), c1 = std::ceil(hi[a] / g.dx - 0.5 + pad) + 1;
+        r[2 * a] = (int)std::max(0.0, std::min((double)n[a], c0));
+        r[2 * a + 1] = (int)std::max(0.0, std::min((double)n[a], c1));
+    }
+    *x0 = r[0];
+    *x1 = r[1];
+    *y0 = r[2];
+    *y1 = r[3];
+}
+
 void MaterialPlane::bounds(const Box& b, int* sx, int* sy, int* ex, int* ey) const {
     // Grid.cpp:139-142 : multiply by the reciprocal of dx, truncate toward zero
     const float inv = 1.f / g_.dx;

@@ -83,6 +83,27 @@ private:
     int dirtyLo_ = 0, dirtyHi_ = 0;
 };
 
+// Shapes (no reference counterpart): convex polygons of 3..kShapeMaxVerts vertices in grid metres (x = grid x, y = grid y),
+// counter-clockwise, with an absorption value; rasterised by the cell-centre rule of shapeCovers on top of the AABB layer
+// (Solver::applyGeometry, pv_shapes.hip).  Everything here is float32 without contraction, so that a numpy restatement is exact.
+constexpr int kShapeMaxVerts = 8;
+struct Shape {
+    int n = 0;
+    float xy[2 * kShapeMaxVerts] = {};
+    float R = 0.f;
+};
+// validates (finite coordinates and absorption, 3..8 vertices, non-zero area, convex and simple) and orders the list
+// counter-clockwise; false + *err on a refusal
+bool makeShape(const float* xy, int n, float R, Shape* out, std::string* err);
+// the 4 vertices of an oriented box: centre (px, py), full width w along the axis (ax, ay) (any non-zero length), full
+// height h along its left normal; counter-clockwise.  false + *err for a zero or non-finite axis or a non-finite input.
+bool orientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float out8[8], std::string* err);
+// is the centre of cell (x, y) inside the shape?  ((float)x + 0.5f) * dx etc., every edge a -> b: e.x (P.y - a.y) - e.y (P.x - a.x) >= 0
+bool shapeCovers(const Shape& s, float dx, int x, int y);
+// cells [*x0, *x1) x [*y0, *y1) that contain every cell shapeCovers can accept (padded for the rounding of the edge
+// function), clipped to the grid's cells 0 <= x < gx, 0 <= y < gy (never the ghost row / column); empty when x0 >= x1 or y0 >= y1
+void shapeCellBounds(const Shape& s, const GridSpec& g, int* x0, int* x1, int* y0, int* y1);
+
 // .pv scene files: PlaneverbSandbox/src/Editor/Editor.cpp:219-281
 bool loadPv(const std::string& path, std::vector<Box>* out, std::string* err);
 bool savePv(const std::string& path, const std::vector<std::pair<int, Box>>& boxes, std::string* err);

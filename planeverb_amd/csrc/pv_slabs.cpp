@@ -276,6 +276,28 @@ bool SlabGroup::removeBox(int id) {
     return true;
 }
 
+int SlabGroup::addShape(const Shape& sh) {
+    int id = -1;
+    for (size_t s = 0; s < slabs_.size(); ++s)
+        if ((id = slabs_[s]->addShape(sh)) < 0) {
+            slabFailed((int)s);
+            return -1;
+        }
+    return id;
+}
+
+bool SlabGroup::updateShape(int id, const Shape& sh) {
+    for (size_t s = 0; s < slabs_.size(); ++s)
+        if (!slabs_[s]->updateShape(id, sh)) return slabFailed((int)s);
+    return true;
+}
+
+bool SlabGroup::removeShape(int id) {
+    for (size_t s = 0; s < slabs_.size(); ++s)
+        if (!slabs_[s]->removeShape(id)) return slabFailed((int)s);
+    return true;
+}
+
 AnalyzeArgs SlabGroup::rootArgs(float lx, float lz) const {
     const Solver& s0 = *slabs_[0];
     AnalyzeArgs a{};

@@ -53,6 +53,11 @@ public:
     bool updateBox(int id, const Box& b);
     bool removeBox(int id);
     int numBoxes() const { return slabs_[0]->numBoxes(); }
+    // shapes: every slab holds the whole table and recomposes the rows its coefficient pass reads (identical id sequences)
+    int addShape(const Shape& sh);
+    bool updateShape(int id, const Shape& sh);
+    bool removeShape(int id);
+    int numShapes() const { return slabs_[0]->numShapes(); }
 
     bool run(float lx, float ly, float lz);
     bool getOutput(float ex, float ey, float ez, float out8[8], bool* valid);

@@ -1,5 +1,6 @@
 // pv_solver.cpp -- see pv_solver.h
 #include "pv_solver.h"
+#include "pv_shapes.h"
 
 #include <unistd.h>
 
@@ -637,7 +638,7 @@ Solver::~Solver() {
     if (emTrace_) hipFree(emTrace_);
     void* ptrs[] = {coef_,      matDev_, pulseDev_, hist_,  tileFirst_, tileClass_, generalList_,
                     generalCount_, dynDev_, errFlag_, res8_,     delay_, scratch_, res_, activeCount_, win8_, unitList_, fusedCtl_, labelDev_, nearBox_,
-                    histAbove_, histEdge_, tileDead_, deadCount_};
+                    histAbove_, histEdge_, tileDead_, deadCount_, matBaseDev_, shapeDev_};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (size_t b = 1; b < bandStream_.size(); ++b)
@@ -743,10 +744,207 @@ std::vector<std::pair<int, Box>> Solver::boxes() const {
     return out;
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// shape layer (pv_shapes.h)
+// ----------------------------------------------------------------------------------------------------------------
+
+int Solver::addShape(const Shape& sh) {
+    int id;
+    if (shapeFree_.empty()) {
+        id = (int)shapeTable_.size();
+    } else {
+        id = shapeFree_.back();  // LIFO recycling, as the AABB table
+    }
+    if (!shapeSet(id, sh)) return -1;
+    if (!shapeFree_.empty() && shapeFree_.back() == id) shapeFree_.pop_back();
+    return id;
+}
+
+bool Solver::updateShape(int id, const Shape& sh) {
+    if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
+    return shapeSet(id, sh);
+}
+
+bool Solver::removeShape(int id) {
+    if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
+    if (!shapeClear(id)) return false;
+    shapeFree_.push_back(id);
+    return true;
+}
+
+int Solver::numShapes() const {
+    int n = 0;
+    for (int q : shapeSeq_) n += q >= 0;
+    return n;
+}
+
+void Solver::markShapeDirty(int id) {
+    int r[4];
+    shapeCellBounds(shapeTable_[(size_t)id], g_, &r[0], &r[1], &r[2], &r[3]);
+    if (r[0] < r[1] && r[2] < r[3]) shapeDirty_.insert(shapeDirty_.end(), r, r + 4);
+}
+
+bool Solver::shapeSet(int id, const Shape& sh) {
+    if (id < 0) return fail("invalid shape id");
+    if (!shapesActive_) {  // the first shape (applyGeometry gives the AABB layer its device plane)
+        compBeta_ = mat_.beta();
+        compR_ = mat_.R();
+        shapesActive_ = true;
+    }
+    if (id >= (int)shapeTable_.size()) {
+        shapeTable_.resize((size_t)id + 1);
+        shapeSeq_.resize((size_t)id + 1, -1);
+    }
+    if (shapeSeq_[(size_t)id] >= 0) markShapeDirty(id);  // where it was
+    shapeTable_[(size_t)id] = sh;
+    shapeSeq_[(size_t)id] = shapeSeqNext_++;
+    markShapeDirty(id);
+    return true;
+}
+
+bool Solver::shapeClear(int id) {
+    if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
+    markShapeDirty(id);
+    shapeSeq_[(size_t)id] = -1;
+    shapeTable_[(size_t)id] = Shape{};
+    return true;
+}
+
+// Recompose the dirty bins: the bins of the changed shapes' old and new cell bounds and of the AABB rows [aabbLo, aabbHi).
+// The device writes matDev_ from matBaseDev_ and the table (pv_shape_compose_kernel); the host mirrors -- betaHost_ / byHost_
+// (air components, IR cells) and compBeta_ / compR_ (copyMaterial) -- restate the same rule (shapeCovers) over the same bins
+// and bin lists, cell by cell, so the two agree by construction.  A slab recomposes on the device only the bins that reach
+// the rows its coefficient pass reads (whole-grid coordinates, as pv_coef_kernel with x0).
+bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
+    const int NX = g_.NX, NY = g_.NY;
+    const int nbx = (NX + kShapeBin - 1) / kShapeBin, nby = (NY + kShapeBin - 1) / kShapeBin, nbins = nbx * nby;
+    std::vector<uint8_t> dirty((size_t)nbins, 0);
+    if (aabbLo < aabbHi)
+        for (int bx = aabbLo / kShapeBin; bx <= (aabbHi - 1) / kShapeBin; ++bx) std::fill_n(&dirty[(size_t)bx * nby], nby, 1);
+    for (size_t k = 0; k + 3 < shapeDirty_.size(); k += 4)
+        for (int bx = shapeDirty_[k] / kShapeBin; bx <= (shapeDirty_[k + 1] - 1) / kShapeBin; ++bx)
+            for (int by = shapeDirty_[k + 2] / kShapeBin; by <= (shapeDirty_[k + 3] - 1) / kShapeBin; ++by) dirty[(size_t)bx * nby + by] = 1;
+    // live shapes, highest sequence number first, and their bins
+    std::vector<int> order;
+    for (size_t i = 0; i < shapeSeq_.size(); ++i)
+        if (shapeSeq_[i] >= 0) order.push_back((int)i);
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return shapeSeq_[(size_t)a] > shapeSeq_[(size_t)b]; });
+    const int ns = (int)order.size();
+    std::vector<DevShape> table((size_t)ns);
+    std::vector<int> binStart((size_t)nbins + 1, 0);
+    for (int k = 0; k < ns; ++k) {
+        const Shape& sh = shapeTable_[(size_t)order[k]];
+        DevShape& d = table[(size_t)k];
+        std::memcpy(d.xy, sh.xy, sizeof(d.xy));
+        d.n = sh.n;
+        d.Y = (1.f - sh.R) / (1.f + sh.R);  // (as applyGeometry for the AABB layer)
+        shapeCellBounds(sh, g_, &d.x0, &d.x1, &d.y0, &d.y1);
+        if (d.x0 >= d.x1 || d.y0 >= d.y1) continue;
+        for (int bx = d.x0 / kShapeBin; bx <= (d.x1 - 1) / kShapeBin; ++bx)
+            for (int by = d.y0 / kShapeBin; by <= (d.y1 - 1) / kShapeBin; ++by) ++binStart[(size_t)bx * nby + by + 1];
+    }
+    for (int b = 0; b < nbins; ++b) binStart[(size_t)b + 1] += binStart[(size_t)b];
+    std::vector<int> binList((size_t)binStart[(size_t)nbins]);
+    {
+        std::vector<int> fill(binStart.begin(), binStart.end() - 1);
+        for (int k = 0; k < ns; ++k) {  // (in sequence order, so every bin's list is highest first)
+            const DevShape& d = table[(size_t)k];
+            if (d.x0 >= d.x1 || d.y0 >= d.y1) continue;
+            for (int bx = d.x0 / kShapeBin; bx <= (d.x1 - 1) / kShapeBin; ++bx)
+                for (int by = d.y0 / kShapeBin; by <= (d.y1 - 1) / kShapeBin; ++by) binList[(size_t)fill[(size_t)bx * nby + by]++] = k;
+        }
+    }
+    // device: the table, the bin lists and this slab's dirty bins in one upload, then one launch
+    const int rowLo = x0_ - geo_.G - 1, rowHi = x0_ - geo_.G + geo_.rows;  // array rows pv_coef_kernel reads
+    std::vector<int> devDirty;
+    for (int b = 0; b < nbins; ++b) {
+        if (!dirty[(size_t)b]) continue;
+        const int bx = b / nby;
+        if (!isSlab() || (bx * kShapeBin < rowHi && (bx + 1) * kShapeBin > rowLo)) devDirty.push_back(b);
+    }
+    auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t oTab = 0, oStart = align(table.size() * sizeof(DevShape)), oList = oStart + align(binStart.size() * 4),
+                 oDirty = oList + align(binList.size() * 4), bytes = oDirty + align(devDirty.size() * 4);
+    if (bytes > shapeDevBytes_) {
+        if (shapeDev_) {
+            if (!hipOk(hipStreamSynchronize(stream_), "shape sync")) return false;
+            hipFree(shapeDev_);
+            deviceBytes_ -= (long long)shapeDevBytes_;
+            shapeDev_ = nullptr;
+        }
+        const size_t cap = std::max(bytes * 2, (size_t)1 << 16);
+        unsigned char* p = nullptr;
+        if (!dalloc(&p, cap, false)) return false;
+        shapeDev_ = p;
+        shapeDevBytes_ = cap;
+    }
+    shapeStage_.resize(bytes);
+    std::memcpy(shapeStage_.data() + oTab, table.data(), table.size() * sizeof(DevShape));
+    std::memcpy(shapeStage_.data() + oStart, binStart.data(), binStart.size() * 4);
+    std::memcpy(shapeStage_.data() + oList, binList.data(), binList.size() * 4);
+    std::memcpy(shapeStage_.data() + oDirty, devDirty.data(), devDirty.size() * 4);
+    unsigned char* base = static_cast<unsigned char*>(shapeDev_);
+    if (!hipOk(hipMemcpyAsync(base, shapeStage_.data(), bytes, hipMemcpyHostToDevice, stream_), "shape table upload")) return false;
+    ShapeArgs a;
+    a.base = matBaseDev_;
+    a.mat = matDev_;
+    a.shapes = reinterpret_cast<const DevShape*>(base + oTab);
+    a.binStart = reinterpret_cast<const int*>(base + oStart);
+    a.binList = reinterpret_cast<const int*>(base + oList);
+    a.dirtyBins = reinterpret_cast<const int*>(base + oDirty);
+    a.numDirty = (int)devDirty.size();
+    a.NX = NX;
+    a.NY = NY;
+    a.nby = nby;
+    a.dx = g_.dx;
+    launchShapeCompose(a, stream_);
+    if (!hipOk(hipGetLastError(), "shape compose launch")) return false;
+    // host mirrors over every dirty bin
+    const auto& beta = mat_.beta();
+    const auto& R = mat_.R();
+    const auto& by = mat_.by();
+    bool changed = false;
+    for (int b = 0; b < nbins; ++b) {
+        if (!dirty[(size_t)b]) continue;
+        const int bx = b / nby, bY = b - bx * nby;
+        const int xe = std::min(NX, (bx + 1) * kShapeBin), ye = std::min(NY, (bY + 1) * kShapeBin);
+        for (int x = bx * kShapeBin; x < xe; ++x)
+            for (int y = bY * kShapeBin; y < ye; ++y) {
+                const size_t i = (size_t)x * NY + y;
+                int hit = -1;
+                for (int k = binStart[(size_t)b]; k < binStart[(size_t)b + 1]; ++k) {
+                    const DevShape& d = table[(size_t)binList[(size_t)k]];
+                    if (x < d.x0 || x >= d.x1 || y < d.y0 || y >= d.y1) continue;
+                    if (shapeCovers(shapeTable_[(size_t)order[(size_t)binList[(size_t)k]]], g_.dx, x, y)) {
+                        hit = binList[(size_t)k];
+                        break;
+                    }
+                }
+                const uint8_t bv = hit >= 0 ? 0 : (beta[i] ? 1 : 0);
+                compBeta_[i] = hit >= 0 ? 0 : beta[i];
+                compR_[i] = hit >= 0 ? shapeTable_[(size_t)order[(size_t)hit]].R : R[i];
+                changed = changed || betaHost_[i] != bv;
+                betaHost_[i] = bv;
+                byHost_[i] = hit >= 0 ? 0 : by[i];
+            }
+    }
+    *airChanged = *airChanged || changed;
+    shapeDirty_.clear();
+    return true;
+}
+
 bool Solver::applyGeometry() {
-    if (!geometryDirty_ && mat_.dirtyLo() >= mat_.dirtyHi()) return true;
+    if (!geometryDirty_ && mat_.dirtyLo() >= mat_.dirtyHi() && shapeDirty_.empty()) return true;
     const auto t0 = std::chrono::steady_clock::now();
     int lo = mat_.dirtyLo(), hi = mat_.dirtyHi();
+    if (shapesActive_ && !matBaseDev_) {
+        // the first shape: the AABB layer moves to a plane of its own.  matDev_ holds the AABB material applied so far; the rows
+        // still pending are uploaded to the new plane below.
+        if (!dalloc(&matBaseDev_, (size_t)g_.NX * g_.NY, false) ||
+            !hipOk(hipMemcpyAsync(matBaseDev_, matDev_, (size_t)g_.NX * g_.NY * sizeof(float), hipMemcpyDeviceToDevice, stream_),
+                   "material copy"))
+            return false;
+    }
     bool airChanged = geometryDirty_;  // did any cell change between air and wall?  (else the air components stand: makeLabels)
     if (lo < hi) {
         const auto& beta = mat_.beta();
@@ -759,15 +957,18 @@ bool Solver::applyGeometry() {
                 const size_t i = (size_t)x * g_.NY + y;
                 const float Rv = R[i];
                 matHost_[i] = beta[i] ? std::numeric_limits<float>::quiet_NaN() : (1.f - Rv) / (1.f + Rv);
+                if (shapesActive_) continue;  // (the mirrors are composeShapes')
                 airChanged = airChanged || betaHost_[i] != (beta[i] ? 1 : 0);
                 betaHost_[i] = beta[i] ? 1 : 0;
                 byHost_[i] = mat_.by()[i];
             }
-        if (!hipOk(hipMemcpyAsync(matDev_ + (size_t)lo * g_.NY, matHost_.data() + (size_t)lo * g_.NY,
+        // (with shapes: the AABB layer's own plane, composed into matDev_ below)
+        if (!hipOk(hipMemcpyAsync((shapesActive_ ? matBaseDev_ : matDev_) + (size_t)lo * g_.NY, matHost_.data() + (size_t)lo * g_.NY,
                                   (size_t)(hi - lo) * g_.NY * sizeof(float), hipMemcpyHostToDevice, stream_),
                    "material upload"))
             return false;
     }
+    if (shapesActive_ && !composeShapes(lo, hi, &airChanged)) return false;
     launchCoefs(matDev_, coef_, geo_, stream_);
     if (!hipOk(hipMemsetAsync(generalCount_, 0, sizeof(int), stream_), "memset")) return false;
     launchTileClass(K_, rxi_, coef_, tileClass_, generalList_, generalCount_, geo_, stream_,
@@ -2313,6 +2514,12 @@ bool Solver::copyPulse(float* out) {
 
 bool Solver::copyMaterial(uint8_t* beta, float* R) {
     const size_t n = (size_t)g_.NX * g_.NY;
+    if (shapesActive_) {  // the composed material as the next run uses it (applyGeometry first: shape changes may be pending)
+        if (!hipOk(hipSetDevice(device_), "hipSetDevice") || !applyGeometry()) return false;
+        if (beta) std::memcpy(beta, compBeta_.data(), n);
+        if (R) std::memcpy(R, compR_.data(), n * 4);
+        return true;
+    }
     if (beta) std::memcpy(beta, mat_.beta().data(), n);
     if (R) std::memcpy(R, mat_.R().data(), n * 4);
     return true;

@@ -143,6 +143,17 @@ public:
     void rasterAdd(const Box& b) { mat_.add(b); }
     void rasterRemove(const Box& b) { mat_.remove(b); }
 
+    // Shape layer (pv_shapes.h): convex polygons over the AABB layer, ids of their own with the same LIFO recycling.  The
+    // first shape gives the solver a device plane for the AABB layer; a solver that never has one keeps the AABB-only path.
+    int addShape(const Shape& sh);
+    bool updateShape(int id, const Shape& sh);
+    bool removeShape(int id);
+    int numShapes() const;
+    // raw access for the live context, which keeps the id table itself: slot `id` takes `sh` (added or updated: it becomes the
+    // most recent shape) / is emptied
+    bool shapeSet(int id, const Shape& sh);
+    bool shapeClear(int id);
+
     // carryFrom (live module, two iterations in flight on two solvers): the solver that ran the PREVIOUS iteration.  The cells
     // in which this run finds no onset take their occlusion / wet gain / decay time / lowpass / source direction from that
     // solver's maps, on the device, behind that solver's analysis and in front of this run's listener-direction pass -- what one
@@ -404,6 +415,22 @@ private:
     std::vector<Box> boxTable_;
     std::vector<uint8_t> boxUsed_;
     std::vector<int> boxFree_;
+
+    // shape layer (pv_shapes.h); shapesActive_ from the first shape on
+    bool shapesActive_ = false;
+    std::vector<Shape> shapeTable_;
+    std::vector<int> shapeSeq_;                 // sequence number of the slot's last add / update, -1 = empty slot
+    std::vector<int> shapeFree_;
+    int shapeSeqNext_ = 0;
+    std::vector<int> shapeDirty_;               // cell rectangles (x0, x1, y0, y1) to recompose at the next applyGeometry
+    void markShapeDirty(int id);
+    bool composeShapes(int aabbLo, int aabbHi, bool* airChanged);
+    float* matBaseDev_ = nullptr;               // AABB-layer material (matDev_ holds the composed one)
+    void* shapeDev_ = nullptr;                  // DevShape table + bin lists + dirty bins, one allocation
+    size_t shapeDevBytes_ = 0;
+    std::vector<unsigned char> shapeStage_;     // host image of that allocation
+    std::vector<uint8_t> compBeta_;             // composed beta / R (copyMaterial)
+    std::vector<float> compR_;
 
     // row bands: band b covers tile rows [bandRow_[b], bandRow_[b+1])
     int nb_ = 1;
