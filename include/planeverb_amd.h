@@ -436,6 +436,56 @@ PVA_EXPORT int PvAmdHostCells(float gridSizeX, float gridSizeY, int gridResoluti
 /* PlaneverbDSP reverb-bus split of wetGain by rt60 (PlaneverbDSP/src/PvDSPContext.cpp:165-228) */
 PVA_EXPORT void PvAmdReverbBusGains(float rt60, float wetGain, float* a, float* b, float* c);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Part 4 -- baked probe tables (extension; INTEGRATION.md "Baked probe tables" documents the query rule and the file format)
+ * A bake simulates a lattice of listener positions ("probes") (x0 + i sx, 0, z0 + j sz), i < nx, j < nz, probe k = j nx + i, and
+ * keeps, per probe, the block of emitter-lattice nodes -- result cells (r, c) with r % stride == 0 and c % stride == 0 -- that
+ * its run reached: the bounding box of the reached nodes inside the run's history window, 9 float32 per node (the 8 members in
+ * PvAmdCopyResults order, then the onset delay; an unreached node inside the box: zeros and FLT_MAX).  Probe state: 0 = not
+ * baked, 1 = baked, 2 = baked but invalid (the listener cell (int)((x + 0) / dx), (int)((z + 0) / dx) of FDTD.cpp:97-98 lies
+ * outside the result map or is not air in the composed material: not run).  PvAmdBakeQuery interpolates a record for any
+ * listener / emitter pair from the 4 probes and 4 emitter nodes around them, with no solver.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct PvAmdBake PvAmdBake;
+typedef struct PvAmdBakeInfo {
+    int gx, gy, T, fs, res;
+    float dx;
+    int stride;                 /* emitter-lattice stride d >= 1 (result cells) */
+    float x0, z0, sx, sz;       /* probe lattice origin and spacing, metres */
+    int nx, nz;
+    int probesBaked;            /* probes in state 1 or 2 */
+    int probesInvalid;          /* probes in state 2 */
+    long long records;          /* stored nodes (9 floats each) */
+    unsigned long long materialHash; /* FNV-1a 64 of the composed material: beta ((gx+1)(gy+1) bytes), then R ((gx+1)(gy+1) float32) */
+} PvAmdBakeInfo;
+/* a bake of nothing yet, for the grid (gx, gy, T -- PVA_OPT_NUM_STEPS included --, fs, res, dx) and the material of `like`;
+ * NULL with PvAmdLastError for stride < 1, nx or nz < 1, a non-finite origin or a spacing that is not finite and > 0 */
+PVA_EXPORT PvAmdBake* PvAmdBakeCreate(PvAmdSolver* like, int stride, float x0, float z0, float sx, float sz, int nx, int nz);
+/* bake the probes k with k % world == rank, dealt round-robin over the n solvers (one run in flight each: two solvers on a GPU
+ * keep two runs in flight), through PvAmdRunAsync.  Refused (-1): a solver with another grid or material hash, a slab group or
+ * slab rank, a solver in sparse-emitter mode (PVA_OPT_STREAMING_ANALYSIS) or one that skips the analysis.  The solvers' result
+ * maps change as after their runs; what they carried from earlier runs never enters the bake (only this run's onsets decide
+ * what is reached, unreached nodes are stored as zeros + FLT_MAX). */
+PVA_EXPORT int PvAmdBakeRun(PvAmdBake* b, PvAmdSolver* const* solvers, int n, int rank, int world);
+/* copy src's baked probes (state != 0) into dst; refused for another lattice, grid or material hash, or a probe that both hold
+ * with different contents */
+PVA_EXPORT int PvAmdBakeMerge(PvAmdBake* dst, const PvAmdBake* src);
+PVA_EXPORT int PvAmdBakeSave(const PvAmdBake* b, const char* path);
+/* NULL + PvAmdLastError for a wrong magic or version, inconsistent sizes, offsets or blocks outside the file or the lattice, a
+ * checksum mismatch.  PvAmdBakeSave(PvAmdBakeLoad(f)) reproduces f byte for byte. */
+PVA_EXPORT PvAmdBake* PvAmdBakeLoad(const char* path);
+PVA_EXPORT void PvAmdBakeDestroy(PvAmdBake* b);
+PVA_EXPORT int PvAmdBakeGetInfo(const PvAmdBake* b, PvAmdBakeInfo* out);
+/* probe k: state5 = {state, i0, j0, ni, nj} (the block: lattice nodes [i0, i0 + ni) x [j0, j0 + nj), node (i, j) = result
+ * cell (i stride, j stride)), rec9 (may be NULL) = ni nj x 9 floats, row-major; returns ni nj, or -1 */
+PVA_EXPORT int PvAmdBakeProbe(const PvAmdBake* b, int k, int* state5 /* state, i0, j0, ni, nj */, float* rec9 /* may be NULL */);
+/* n listener / emitter pairs (x, y, z each; y is ignored) -> n records by the query rule; CPU only */
+PVA_EXPORT int PvAmdBakeQuery(const PvAmdBake* b, const float* listenersXYZ, const float* emittersXYZ, int n, PlaneverbOutput* out);
+/* the same on HIP device `device`, one thread per query, bit-identical to PvAmdBakeQuery; the bake is uploaded once per device
+ * and kept there until PvAmdBakeRun or PvAmdBakeMerge changes it */
+PVA_EXPORT int PvAmdBakeQueryDevice(const PvAmdBake* b, int device, const float* listenersXYZ, const float* emittersXYZ, int n,
+                                    PlaneverbOutput* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,13 @@ class PvAmdInfo(C.Structure):
                 ("deviceBytes", C.c_longlong), ("streamFuse", C.c_int), ("residentKernel", C.c_int)]
 
 
+class PvAmdBakeInfo(C.Structure):
+    _fields_ = [("gx", C.c_int), ("gy", C.c_int), ("T", C.c_int), ("fs", C.c_int), ("res", C.c_int), ("dx", C.c_float),
+                ("stride", C.c_int), ("x0", C.c_float), ("z0", C.c_float), ("sx", C.c_float), ("sz", C.c_float),
+                ("nx", C.c_int), ("nz", C.c_int), ("probesBaked", C.c_int), ("probesInvalid", C.c_int),
+                ("records", C.c_longlong), ("materialHash", C.c_ulonglong)]
+
+
 class PvAmdSlabInfo(C.Structure):
     _fields_ = [("nslabs", C.c_int), ("row0", C.c_int * 16), ("rows", C.c_int * 16), ("device", C.c_int * 16),
                 ("haloBytesPerLaunch", C.c_longlong), ("exchangeBytesPerRun", C.c_longlong),
@@ -206,6 +213,16 @@ SYMBOLS = {
     "PvAmdHostLoadPv": (C.c_int, [C.c_char_p, _fp, C.c_int]),
     "PvAmdHostSavePv": (C.c_int, [C.c_char_p, _fp, C.POINTER(C.c_int), C.c_int]),
     "PvAmdHostCells": (C.c_int, [C.c_float, C.c_float, C.c_int, C.c_float, C.c_float] + [C.POINTER(C.c_int)] * 5),
+    "PvAmdBakeCreate": (_vp, [_vp, C.c_int] + [C.c_float] * 4 + [C.c_int, C.c_int]),
+    "PvAmdBakeRun": (C.c_int, [_vp, C.POINTER(_vp), C.c_int, C.c_int, C.c_int]),
+    "PvAmdBakeMerge": (C.c_int, [_vp, _vp]),
+    "PvAmdBakeSave": (C.c_int, [_vp, C.c_char_p]),
+    "PvAmdBakeLoad": (_vp, [C.c_char_p]),
+    "PvAmdBakeDestroy": (None, [_vp]),
+    "PvAmdBakeGetInfo": (C.c_int, [_vp, C.POINTER(PvAmdBakeInfo)]),
+    "PvAmdBakeProbe": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), _fp]),
+    "PvAmdBakeQuery": (C.c_int, [_vp, _fp, _fp, C.c_int, _fp]),
+    "PvAmdBakeQueryDevice": (C.c_int, [_vp, C.c_int, _fp, _fp, C.c_int, _fp]),
 }
 
 _lib = None
@@ -569,6 +586,90 @@ def run_sharded(solvers, listeners, emitters, rank=0, world=1, comm=None):
     _check(lib().PvAmdRunSharded(hs, len(solvers), _f(L), n, _f(Em), E, int(rank), int(world),
                                  comm._h if comm is not None else None, out))
     return np.frombuffer(out, np.float32).reshape(-1, 8)[:n * E].reshape(n, E, 8).copy()
+
+
+class Bake:
+    """A baked listener-probe table (PvAmdBake*, include/planeverb_amd.h Part 4): probes (x0 + i sx, 0, z0 + j sz), k = j nx + i;
+    per probe the block of emitter-lattice nodes (stride `stride` in result cells) its run reached, queried by interpolation.
+
+        b = Bake(solver, stride, x0, z0, sx, sz, nx, nz); b.run([s0, s1]); b.save(path); Bake.load(path).query(L, E)
+    """
+
+    def __init__(self, like, stride, x0, z0, sx, sz, nx, nz):
+        self._h = lib().PvAmdBakeCreate(like._h, int(stride), float(x0), float(z0), float(sx), float(sz), int(nx), int(nz))
+        if not self._h:
+            raise PlaneverbError(last_error())
+
+    @classmethod
+    def load(cls, path):
+        h = lib().PvAmdBakeLoad(os.fsencode(path))
+        if not h:
+            raise PlaneverbError(last_error())
+        b = cls.__new__(cls)
+        b._h = h
+        return b
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().PvAmdBakeDestroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def run(self, solvers, rank=0, world=1):
+        """bake the probes k % world == rank on these solvers (round-robin, one run in flight each)"""
+        hs = (_vp * len(solvers))(*[sv._h for sv in solvers])
+        _check(lib().PvAmdBakeRun(self._h, hs, len(solvers), int(rank), int(world)))
+
+    def merge(self, other):
+        _check(lib().PvAmdBakeMerge(self._h, other._h))
+
+    def save(self, path):
+        _check(lib().PvAmdBakeSave(self._h, os.fsencode(path)))
+
+    def info(self):
+        i = PvAmdBakeInfo()
+        _check(lib().PvAmdBakeGetInfo(self._h, i))
+        return {f: getattr(i, f) for f, _ in PvAmdBakeInfo._fields_}
+
+    def probe(self, k):
+        """(state5 int32 [5] = state, i0, j0, ni, nj;  records float32 [ni, nj, 9])"""
+        st = np.zeros(5, np.int32)
+        n = lib().PvAmdBakeProbe(self._h, int(k), st.ctypes.data_as(C.POINTER(C.c_int)), None)
+        if n < 0:
+            raise PlaneverbError(last_error())
+        rec = np.zeros(max(n, 1) * 9, np.float32)
+        _check(0 if lib().PvAmdBakeProbe(self._h, int(k), st.ctypes.data_as(C.POINTER(C.c_int)), _f(rec)) == n else -1)
+        return st, rec[:n * 9].reshape(int(st[3]), int(st[4]), 9)
+
+    def _pairs(self, listeners, emitters):
+        L = np.ascontiguousarray(listeners, np.float32).reshape(-1, 3)
+        E = np.ascontiguousarray(emitters, np.float32).reshape(-1, 3)
+        if len(L) != len(E):
+            raise ValueError("listeners and emitters must pair up")
+        return L, E, np.zeros((max(len(L), 1), 8), np.float32)
+
+    def query(self, listeners, emitters):
+        """listeners [n, 3], emitters [n, 3] -> float32 [n, 8] (CPU)"""
+        L, E, out = self._pairs(listeners, emitters)
+        _check(lib().PvAmdBakeQuery(self._h, _f(L), _f(E), len(L), _f(out)))
+        return out[:len(L)]
+
+    def query_device(self, listeners, emitters, device=0):
+        """the same on a HIP device (bit-identical)"""
+        L, E, out = self._pairs(listeners, emitters)
+        _check(lib().PvAmdBakeQueryDevice(self._h, int(device), _f(L), _f(E), len(L), _f(out)))
+        return out[:len(L)]
 
 
 def compute_efree(size_x, size_y, res, device=0):

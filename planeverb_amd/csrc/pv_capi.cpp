@@ -10,6 +10,7 @@
 #include "pv_context.h"
 #include "pv_core.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
+#include "pv_bake.h"
 #include "pv_shard.h"
 #include "pv_slabs.h"
 #include "pv_launch.h"
@@ -94,6 +95,15 @@ static bool wholeGrid(PvAmdSolver* h) {
         return false;
     }
     return true;
+}
+
+struct PvAmdBake {
+    std::unique_ptr<Bake> b;
+};
+static bool bakeOk(const PvAmdBake* b) {
+    if (b && b->b) return true;
+    g_lastError = "null bake handle";
+    return false;
 }
 
 static int ret(PvAmdSolver* h, bool ok) {
@@ -1053,5 +1063,123 @@ int PvAmdHostCells(float sx, float sy, int res, float x, float z, int* lcx, int*
 void PvAmdReverbBusGains(float rt60, float wetGain, float* a, float* b, float* c) try {
     reverbBusGains(rt60, wetGain, a, b, c);
 } PV_API_CATCH_VOID
+
+
+#ifndef PVA_HOST_TEST
+// ---------------------------------------------------------------------------------------------------------------
+// Part 4: baked probe tables (pv_bake.h)
+// ---------------------------------------------------------------------------------------------------------------
+PvAmdBake* PvAmdBakeCreate(PvAmdSolver* like, int stride, float x0, float z0, float sx, float sz, int nx, int nz) try {
+    if (!wholeGrid(like) || !ensure(like)) return nullptr;
+    std::unique_ptr<PvAmdBake> h(new PvAmdBake());
+    h->b.reset(Bake::create(like->s, stride, x0, z0, sx, sz, nx, nz, &g_lastError));
+    return h->b ? h.release() : nullptr;
+} PV_API_CATCH(nullptr)
+
+int PvAmdBakeRun(PvAmdBake* b, PvAmdSolver* const* solvers, int n, int rank, int world) try {
+    if (!bakeOk(b)) return -1;
+    if (!solvers || n < 1) {
+        g_lastError = "PvAmdBakeRun: no solvers";
+        return -1;
+    }
+    std::vector<Solver*> sv;
+    for (int i = 0; i < n; ++i) {
+        PvAmdSolver* h = solvers[i];
+        if (h && !h->slabDevices.empty()) {
+            g_lastError = "PvAmdBakeRun: solver " + std::to_string(i) + " is a slab group (slab groups cannot bake)";
+            return -1;
+        }
+        if (h && h->opt.slabCount > 1) {
+            g_lastError = "PvAmdBakeRun: solver " + std::to_string(i) + " is a slab rank (slab ranks cannot bake)";
+            return -1;
+        }
+        if (!ensure(h)) return -1;
+        sv.push_back(h->s);
+    }
+    return b->b->run(sv.data(), n, rank, world, &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+
+int PvAmdBakeMerge(PvAmdBake* dst, const PvAmdBake* src) try {
+    if (!bakeOk(dst) || !bakeOk(src)) return -1;
+    return dst->b->merge(*src->b, &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+
+int PvAmdBakeSave(const PvAmdBake* b, const char* path) try {
+    if (!bakeOk(b)) return -1;
+    if (!path) {
+        g_lastError = "PvAmdBakeSave: null path";
+        return -1;
+    }
+    return b->b->save(path, &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+
+PvAmdBake* PvAmdBakeLoad(const char* path) try {
+    if (!path) {
+        g_lastError = "PvAmdBakeLoad: null path";
+        return nullptr;
+    }
+    std::unique_ptr<PvAmdBake> h(new PvAmdBake());
+    h->b.reset(Bake::load(path, &g_lastError));
+    return h->b ? h.release() : nullptr;
+} PV_API_CATCH(nullptr)
+
+void PvAmdBakeDestroy(PvAmdBake* b) try {
+    delete b;
+} PV_API_CATCH_VOID
+
+int PvAmdBakeGetInfo(const PvAmdBake* b, PvAmdBakeInfo* out) try {
+    if (!bakeOk(b) || !out) return -1;
+    const BakeHeader& h = b->b->h;
+    out->gx = h.gx;
+    out->gy = h.gy;
+    out->T = h.T;
+    out->fs = h.fs;
+    out->res = h.res;
+    out->dx = h.dx;
+    out->stride = h.stride;
+    out->x0 = h.x0;
+    out->z0 = h.z0;
+    out->sx = h.sx;
+    out->sz = h.sz;
+    out->nx = h.nx;
+    out->nz = h.nz;
+    b->b->counts(&out->probesBaked, &out->probesInvalid, &out->records);
+    out->materialHash = h.materialHash;
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdBakeProbe(const PvAmdBake* b, int k, int* state5, float* rec9) try {
+    if (!bakeOk(b)) return -1;
+    if (k < 0 || k >= b->b->probes()) {
+        g_lastError = "PvAmdBakeProbe: probe index outside the lattice";
+        return -1;
+    }
+    const int* p = &b->b->probe5[(size_t)5 * k];
+    if (state5) std::memcpy(state5, p, 5 * sizeof(int));
+    const size_t n = (size_t)p[3] * p[4];
+    if (rec9 && n) std::memcpy(rec9, b->b->records(k), n * kBakeRecFloats * 4);
+    return (int)n;
+} PV_API_CATCH(-1)
+
+int PvAmdBakeQuery(const PvAmdBake* b, const float* listenersXYZ, const float* emittersXYZ, int n, PlaneverbOutput* out) try {
+    if (!bakeOk(b)) return -1;
+    if (n < 0 || (n > 0 && (!listenersXYZ || !emittersXYZ || !out))) {
+        g_lastError = "PvAmdBakeQuery: invalid arguments";
+        return -1;
+    }
+    b->b->query(listenersXYZ, emittersXYZ, n, reinterpret_cast<float*>(out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdBakeQueryDevice(const PvAmdBake* b, int device, const float* listenersXYZ, const float* emittersXYZ, int n,
+                         PlaneverbOutput* out) try {
+    if (!bakeOk(b)) return -1;
+    if (n < 0 || (n > 0 && (!listenersXYZ || !emittersXYZ || !out))) {
+        g_lastError = "PvAmdBakeQueryDevice: invalid arguments";
+        return -1;
+    }
+    return b->b->queryDevice(device, listenersXYZ, emittersXYZ, n, reinterpret_cast<float*>(out), &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+#endif  // !PVA_HOST_TEST
 
 }  // extern "C"

@@ -1933,6 +1933,7 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     // (ev_[2] is also what the OTHER solver of a pipelined pair waits for before its carry pass reads this solver's maps: behind
     // the last kernel here, where it delays nothing of this run)
     if (stampTimed_) hipEventRecord(ev_[2], stream_);
+    enqueueTap();
     statusQueued_ = true;
     pendingTimings_ = true;
     return hipOk(hipGetLastError(), "run launch");
@@ -2295,6 +2296,14 @@ void Solver::enqueueRunStatus() {
 void Solver::enqueueQueries() {
     if (numQueries_ > 0 && !opt_.skipAnalysis)
         launchGatherQueries(res_, (long long)g_.gx * g_.gy, qCellsHost_, numQueries_, qOutHost_, farInfo(), stream_);
+    enqueueTap();
+}
+
+void Solver::enqueueTap() {
+    if (tap_ && !opt_.skipAnalysis) {
+        const Block b = curWindow();
+        tap_->afterRun(res_, delay_, (long long)g_.gx * g_.gy, g_.gy, b.r0, b.c0, b.nr, b.nc, stream_);
+    }
 }
 
 // after sync(): the registered queries' outputs of the last run, straight from pinned memory
@@ -2360,6 +2369,11 @@ bool Solver::copyResultsAsync(float* res8Host) {
 
 size_t Solver::windowCapacity() const {
     return (size_t)std::min(histTilesX_ * rxi_, g_.gx) * (size_t)std::min(histTilesY_ * wi_, g_.gy);
+}
+
+void Solver::windowExtent(int* rows, int* cols) const {
+    *rows = std::min(histTilesX_ * rxi_, g_.gx);
+    *cols = std::min(histTilesY_ * wi_, g_.gy);
 }
 
 bool Solver::publishWindowAsync(float* hostDst, WindowBlock* info, bool overlap) {

@@ -108,6 +108,15 @@ struct QueueClaim {
     void release();  // before the stream itself is destroyed
 };
 
+// Work enqueued on a solver's stream behind every run's analysis and output queries (a baked probe table's gather, pv_bake.cpp),
+// also behind a run that sync() repeats: res = the 8 SoA result planes, delay = the onset map, [r0, r0 + nr) x [c0, c0 + nc) =
+// the run's history-window block of the result map
+struct RunTap {
+    virtual ~RunTap() = default;
+    virtual void afterRun(const float* res, const float* delay, long long resN, int gy, int r0, int c0, int nr, int nc,
+                          hipStream_t stream) = 0;
+};
+
 class Solver {
     friend class SlabGroup;
     friend class SlabRoot;
@@ -188,6 +197,8 @@ public:
         float lx = 0, lz = 0;                // the run's listener position, metres
     };
     size_t windowCapacity() const;  // records: upper bound of nr*nc for any listener position
+    void windowExtent(int* rows, int* cols) const;  // upper bounds of nr and nc for any listener position
+    void setRunTap(RunTap* t) { tap_ = t; }  // (nullptr: none; the caller syncs the solver before it lets the tap go)
     // overlap = true: only the pack runs on the solver's stream; the device -> host copy goes to a second stream, so that the
     // NEXT run's launches need not wait for it (the live module's loop); waitPublish() then waits for that copy alone.
     bool publishWindowAsync(float* hostDst, WindowBlock* info, bool overlap = false);
@@ -247,6 +258,8 @@ private:
     bool ensureFarDirections();
     void enqueueAnalysis(float lx, float lz);
     Solver* carryFrom_ = nullptr;  // for the run being enqueued
+    RunTap* tap_ = nullptr;
+    void enqueueTap();  // behind the run's last kernel
     bool fail(const std::string& what);
     bool hipOk(hipError_t e, const char* what);
     template <typename Tp>
