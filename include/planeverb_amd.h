@@ -51,7 +51,10 @@ PVA_EXPORT void UnityPluginLoad(void* unityInterfaces);
 PVA_EXPORT void UnityPluginUnload(void);
 
 /* PlaneverbUnity.cpp:25-40 -> Planeverb::Init (PvContext.cpp:25-32).  Invalid config (res < 275, size 0,
- * tempFileDir NULL: PvContext.cpp:101-107) leaves the module un-initialised instead of throwing. */
+ * tempFileDir NULL: PvContext.cpp:101-107) leaves the module un-initialised instead of throwing.
+ * gridBoundaryType (PvTypes.h:32-36): 0 = pv_AbsorbingBoundary, the reference's grid edges; 1 = pv_ReflectingBoundary, absorption
+ * R = 1 (a rigid edge) on all four sides of the grid (PvAmdSetGridBoundary).  The reference stores the value and ignores it.
+ * Any other value runs absorbing edges, as before, with one warning on stderr. */
 PVA_EXPORT void PlaneverbInit(float gridSizeX, float gridSizeY, int gridResolution, int gridBoundaryType,
                               char* tempFileDir, int maxThreadUsage, int threadExecutionType);
 /* PlaneverbUnity.cpp:42-46 */
@@ -91,6 +94,10 @@ PVA_EXPORT void PlaneverbRemoveOrientedGeometry(int id);
 PVA_EXPORT int PlaneverbAddPolygonGeometry(const float* xy, int n, float absorption);
 PVA_EXPORT void PlaneverbUpdatePolygonGeometry(int id, const float* xy, int n, float absorption);
 PVA_EXPORT void PlaneverbRemovePolygonGeometry(int id);
+/* Extension: the absorption of the four grid edges (PvAmdSetGridBoundary: xMin = side 0, xMax = 1, zMin = 2, zMax = 3), queued
+ * like the geometry calls and applied to both live solvers at the same iteration boundary.  A non-finite value is refused
+ * (nothing changes; PvAmdLastError says why). */
+PVA_EXPORT void PlaneverbSetGridBoundary(float xMin, float xMax, float zMin, float zMax);
 
 /* Extensions to the live module (not in the reference's flat ABI) */
 /* One sample of an impulse response as the reference stores it (Cell, PvTypes.h:106-121: 16 bytes) */
@@ -301,6 +308,16 @@ PVA_EXPORT int PvAmdRemoveShape(PvAmdSolver* s, int id);
 PVA_EXPORT int PvAmdAddOrientedBox(PvAmdSolver* s, float px, float py, float w, float h, float ax, float ay, float absorption);
 PVA_EXPORT int PvAmdUpdateOrientedBox(PvAmdSolver* s, int id, float px, float py, float w, float h, float ax, float ay,
                                       float absorption);
+/* Grid edges.  absorption4 = R of the sides 0: faces at x = 0 (world x = 0), 1: faces at x = gx, 2: faces at y = 0 (world
+ * z = 0), 3: faces at y = gy, taken as PvAmdAddGeometry takes absorption (any finite value); the admittance of side k is
+ * Y = (1 - R) / (1 + R) in float32.  The edge faces are the reference's absorbing edges (FDTD.cpp:201-223) with Y in place of
+ * 1: x = 0: kx = (cell air && y < gy) ? -Y0 : 0;  x = gx: kx = (y < gy) ? +Y1 : 0;  y = 0 / y = gy likewise with Y2 / Y3.
+ * R = 0 on every side (the default) is the reference's grid, bit for bit; R = 1 is a rigid edge (pv_ReflectingBoundary).
+ * The free-field energy stays that of the open grid, so occlusion stays normalised by the free field.  A change takes effect
+ * at the next run of any form.  NULL or a non-finite value returns -1 and changes nothing.  Slab groups forward the call to
+ * every slab; slab ranks (PvAmdCreateSlabRank) refuse any non-zero side.  The .pv scene format does not hold the boundary. */
+PVA_EXPORT int PvAmdSetGridBoundary(PvAmdSolver* s, const float absorption4[4]);
+PVA_EXPORT int PvAmdGetGridBoundary(PvAmdSolver* s, float out4[4]);
 /* CPU only: the four vertices out8 the library uses for that oriented box (0, or -1 for a refused input) */
 PVA_EXPORT int PvAmdHostOrientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float* out8);
 /* CPU only: the shape the library makes of a vertex list (counter-clockwise, out16 gets 2n floats); returns n, or -1 for a

@@ -171,6 +171,9 @@ SYMBOLS = {
     "PvAmdRemoveShape": (C.c_int, [_vp, C.c_int]),
     "PvAmdAddOrientedBox": (C.c_int, [_vp] + [C.c_float] * 7),
     "PvAmdUpdateOrientedBox": (C.c_int, [_vp, C.c_int] + [C.c_float] * 7),
+    "PvAmdSetGridBoundary": (C.c_int, [_vp, _fp]),
+    "PvAmdGetGridBoundary": (C.c_int, [_vp, _fp]),
+    "PlaneverbSetGridBoundary": (None, [C.c_float] * 4),
     "PvAmdHostOrientedBoxVertices": (C.c_int, [C.c_float] * 6 + [_fp]),
     "PvAmdHostShape": (C.c_int, [_fp, C.c_int, C.c_float, _fp]),
     "PvAmdHostShapeCoverage": (C.c_int, [C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
@@ -288,6 +291,7 @@ def _f(a):
 Config = namedtuple("PlaneverbConfig", "gridSizeInMeters gridResolution gridBoundaryType tempFileDirectory "
                                        "maxThreadUsage threadExecutionType")
 pv_CPU, pv_GPU = 0, 1  # PvTypes.h:13-17 / PlaneverbConfig.cs:23-29
+pv_AbsorbingBoundary, pv_ReflectingBoundary = 0, 1  # gridBoundaryType, PvTypes.h:32-36 / PlaneverbConfig.cs:15-18
 
 
 def Init(config):
@@ -367,6 +371,11 @@ def UpdatePolygonGeometry(sid, vertices, absorption):
 
 def RemovePolygonGeometry(sid):
     lib().PlaneverbRemovePolygonGeometry(int(sid))
+
+
+def SetGridBoundary(xmin, xmax, zmin, zmax):
+    """absorption of the four grid edges (Solver.set_grid_boundary), applied at the next iteration boundary"""
+    lib().PlaneverbSetGridBoundary(float(xmin), float(xmax), float(zmin), float(zmax))
 
 
 def SetListenerPosition(pos):
@@ -909,6 +918,19 @@ class Solver:
 
     def remove_shape(self, sid):
         _check(lib().PvAmdRemoveShape(self._h, int(sid)))
+
+    def set_grid_boundary(self, r4):
+        """absorption R of the grid edges x = 0, x = gx, y = 0 (world z = 0), y = gy, as add_geometry takes it: 0 = absorbing
+        (the default), 1 = rigid.  Takes effect at the next run."""
+        a = np.ascontiguousarray(r4, np.float32).reshape(-1)
+        if a.size != 4:
+            raise ValueError("four absorption values: x = 0, x = gx, y = 0, y = gy")
+        _check(lib().PvAmdSetGridBoundary(self._h, _f(a)))
+
+    def grid_boundary(self):
+        out = np.zeros(4, np.float32)
+        _check(lib().PvAmdGetGridBoundary(self._h, _f(out)))
+        return out
 
     def run(self, listener):
         _check(lib().PvAmdRun(self._h, *[float(v) for v in listener]))

@@ -24,7 +24,9 @@ unsigned long long fnv1a64(const void* p, size_t n, unsigned long long h) {
 
 namespace {
 
-// FNV-1a 64 of the composed material: beta ((gx+1)(gy+1) bytes), then R ((gx+1)(gy+1) float32)
+// FNV-1a 64 of the composed material: beta ((gx+1)(gy+1) bytes), then R ((gx+1)(gy+1) float32), then -- only when some side is
+// not absorbing (Solver::boundaryAbsorbing) -- the four grid-edge absorptions' bits, so that the hashes of bakes of absorbing
+// grids stay what they were
 bool materialOf(Solver* s, std::vector<uint8_t>* beta, unsigned long long* hash, std::string* err) {
     const GridSpec& g = s->spec();
     const size_t n = (size_t)g.NX * g.NY;
@@ -35,6 +37,11 @@ bool materialOf(Solver* s, std::vector<uint8_t>* beta, unsigned long long* hash,
         return false;
     }
     *hash = fnv1a64(R.data(), n * 4, fnv1a64(beta->data(), n));
+    if (!s->boundaryAbsorbing()) {
+        float edges[4];
+        s->gridBoundary(edges);
+        *hash = fnv1a64(edges, sizeof edges, *hash);
+    }
     return true;
 }
 

@@ -140,6 +140,17 @@ void PlaneverbInit(float gridSizeX, float gridSizeY, int gridResolution, int gri
     }
 } PV_API_CATCH_VOID
 
+void PlaneverbSetGridBoundary(float xMin, float xMax, float zMin, float zMax) try {
+    const float R4[4] = {xMin, xMax, zMin, zMax};
+    for (int k = 0; k < 4; ++k)
+        if (!(R4[k] - R4[k] == 0.f)) {
+            g_lastError = "PlaneverbSetGridBoundary: absorption of side " + std::to_string(k) + " is not finite";
+            return;
+        }
+    Context::Ref c;
+    if (c) c->setGridBoundary(R4);
+} PV_API_CATCH_VOID
+
 void PlaneverbExit(void) try {
     Context::exit();
 } PV_API_CATCH_VOID
@@ -682,6 +693,40 @@ int PvAmdUpdateOrientedBox(PvAmdSolver* h, int id, float px, float py, float w, 
     if (!shapesOk(h) || !orientedBoxVertices(px, py, w, hgt, ax, ay, v, &g_lastError) || !makeShape(v, 4, absorption, &sh, &g_lastError))
         return -1;
     return ret(h, h->g ? h->g->updateShape(id, sh) : h->s->updateShape(id, sh));
+} PV_API_CATCH(-1)
+
+int PvAmdSetGridBoundary(PvAmdSolver* h, const float* absorption4) try {
+    if (!absorption4) {
+        g_lastError = "PvAmdSetGridBoundary: null absorption array";
+        return -1;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (!(absorption4[k] - absorption4[k] == 0.f)) {
+            g_lastError = "PvAmdSetGridBoundary: absorption of side " + std::to_string(k) + " is not finite";
+            return -1;
+        }
+    if (h && h->opt.slabCount > 1) {  // a rank would need its neighbours' edges in the halo exchange: out of scope
+        for (int k = 0; k < 4; ++k)
+            if (absorption4[k] != 0.f) {
+                g_lastError = "a slab rank handle (PvAmdCreateSlabRank) has absorbing grid edges only: use PvAmdCreateSlabs";
+                return -1;
+            }
+    }
+    if (!ensure(h, true)) return -1;
+    return ret(h, h->g ? h->g->setGridBoundary(absorption4) : h->s->setGridBoundary(absorption4));
+} PV_API_CATCH(-1)
+
+int PvAmdGetGridBoundary(PvAmdSolver* h, float* out4) try {
+    if (!out4) {
+        g_lastError = "PvAmdGetGridBoundary: null output array";
+        return -1;
+    }
+    if (!ensure(h, true)) return -1;
+    if (h->g)
+        h->g->gridBoundary(out4);
+    else
+        h->s->gridBoundary(out4);
+    return 0;
 } PV_API_CATCH(-1)
 
 int PvAmdRun(PvAmdSolver* h, float lx, float ly, float lz) try {

@@ -113,6 +113,20 @@ bool Context::init(const LiveConfig& cfg, std::string* err) {
         c->solver2_ = Solver::create(spec, device, opt, err);
         if (!c->solver2_) return false;
     }
+#ifndef PVA_HOST_TEST  // (the HIP-less fake has no grid edges)
+    // gridBoundaryType (PvTypes.h:32-36): 1 = pv_ReflectingBoundary, R = 1 on every side of both solvers.  The reference stores
+    // the value and ignores it; any value but 0 and 1 keeps absorbing edges, as before, and says so.
+    if (cfg.boundaryType == 1) {
+        const float rigid[4] = {1.f, 1.f, 1.f, 1.f};
+        if (!c->solver_->setGridBoundary(rigid) || (c->solver2_ && !c->solver2_->setGridBoundary(rigid))) {
+            if (err) *err = "grid boundary: " + c->solver_->lastError();
+            return false;
+        }
+    } else if (cfg.boundaryType != 0) {
+        std::fprintf(stderr, "[planeverb_amd] warning: gridBoundaryType %d is neither pv_AbsorbingBoundary (0) nor "
+                             "pv_ReflectingBoundary (1): absorbing grid edges\n", cfg.boundaryType);
+    }
+#endif
     if (c->streaming_)
         std::fprintf(stderr, "[planeverb_amd] %d x %d grid, T = %d: sparse-emitter mode (wet gain / RT60 for the cells of the "
                              "emitters registered at the start of an iteration)\n", spec.gx, spec.gy, c->solver_->T());
@@ -644,7 +658,22 @@ void Context::removeShape(int id) {
     shapeFree_.push_back(id);
 }
 
+void Context::setGridBoundary(const float R4[4]) {
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    ensureRoom(changes_, 1);
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.boundary = true;
+    for (int k = 0; k < 4; ++k) c.R4[k] = R4[k];
+    changes_.push_back(c);
+}
+
 void Context::applyChange(Solver* s, const Change& c) {
+    if (c.boundary) {
+#ifndef PVA_HOST_TEST
+        s->setGridBoundary(c.R4);  // (validated by the caller: finite values cannot be refused)
+#endif
+        return;
+    }
     if (c.shapeId >= 0) {
 #ifndef PVA_HOST_TEST  // (the HIP-less fake has no shape layer)
         // (a failure here -- the device allocation of the first shape -- surfaces as the solver's error at its next run)

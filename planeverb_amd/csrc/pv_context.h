@@ -90,6 +90,9 @@ public:
     int addShape(const Shape& sh);
     void updateShape(int id, const Shape& sh);
     void removeShape(int id);
+    // grid edges (Solver::setGridBoundary, finite values already checked): queued with the geometry changes, applied to every
+    // solver at the same iteration boundary
+    void setGridBoundary(const float R4[4]);
 
     void setListener(float x, float y, float z);  // PvContext.cpp:50-56
     // Planeverb::GetImpulseResponse (FDTD.cpp:60-70): the IR of the last COMPLETED iteration at a world position as
@@ -176,6 +179,8 @@ private:
         Box box;
         int shapeId;  // >= 0: slot shapeId of the shape table takes `shape` (add) or is emptied; box unused
         Shape shape;
+        bool boundary = false;  // a grid-edge change: R4 replaces the four edge absorptions; the rest is unused
+        float R4[4] = {0.f, 0.f, 0.f, 0.f};
     };
     static void applyChange(Solver* s, const Change& c);
     std::vector<Box> geometry_;

@@ -298,6 +298,14 @@ bool SlabGroup::removeShape(int id) {
     return true;
 }
 
+bool SlabGroup::setGridBoundary(const float R4[4]) {
+    for (int k = 0; k < 4; ++k)  // (checked here first: a refusal changes no slab)
+        if (!(R4[k] - R4[k] == 0.f)) return fail("grid boundary: absorption values must be finite");
+    for (size_t s = 0; s < slabs_.size(); ++s)
+        if (!slabs_[s]->setGridBoundary(R4)) return slabFailed((int)s);
+    return true;
+}
+
 AnalyzeArgs SlabGroup::rootArgs(float lx, float lz) const {
     const Solver& s0 = *slabs_[0];
     AnalyzeArgs a{};

@@ -57,6 +57,9 @@ public:
     int addShape(const Shape& sh);
     bool updateShape(int id, const Shape& sh);
     bool removeShape(int id);
+    // grid edges (Solver::setGridBoundary): every slab holds the four values; its edge pass writes the faces it owns
+    bool setGridBoundary(const float R4[4]);
+    void gridBoundary(float R4[4]) const { slabs_[0]->gridBoundary(R4); }
     int numShapes() const { return slabs_[0]->numShapes(); }
 
     bool run(float lx, float ly, float lz);

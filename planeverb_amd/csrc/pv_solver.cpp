@@ -1,5 +1,6 @@
 // pv_solver.cpp -- see pv_solver.h
 #include "pv_solver.h"
+#include "pv_boundary.h"
 #include "pv_shapes.h"
 
 #include <unistd.h>
@@ -933,8 +934,36 @@ bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
     return true;
 }
 
+bool Solver::setGridBoundary(const float R4[4]) {
+    for (int k = 0; k < 4; ++k)
+        if (!(R4[k] - R4[k] == 0.f)) return fail("grid boundary: absorption values must be finite");
+    for (int k = 0; k < 4; ++k) {
+        if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
+        edgeR_[k] = R4[k];
+    }
+    return true;
+}
+
+void Solver::gridBoundary(float R4[4]) const {
+    for (int k = 0; k < 4; ++k) R4[k] = edgeR_[k];
+}
+
+// the edge admittances, in the expression applyGeometry uses for wall cells (FDTD.cpp:150,156)
+static EdgeY edgeAdmittance(const float R[4]) {
+    EdgeY e;
+    for (int k = 0; k < 4; ++k) e.y[k] = (1.f - R[k]) / (1.f + R[k]);
+    return e;
+}
+
+bool Solver::boundaryAbsorbing() const {
+    const EdgeY e = edgeAdmittance(edgeR_);
+    for (int k = 0; k < 4; ++k)
+        if (e.y[k] != 1.f) return false;
+    return true;
+}
+
 bool Solver::applyGeometry() {
-    if (!geometryDirty_ && mat_.dirtyLo() >= mat_.dirtyHi() && shapeDirty_.empty()) return true;
+    if (!geometryDirty_ && !boundaryDirty_ && mat_.dirtyLo() >= mat_.dirtyHi() && shapeDirty_.empty()) return true;
     const auto t0 = std::chrono::steady_clock::now();
     int lo = mat_.dirtyLo(), hi = mat_.dirtyHi();
     if (shapesActive_ && !matBaseDev_) {
@@ -970,6 +999,9 @@ bool Solver::applyGeometry() {
     }
     if (shapesActive_ && !composeShapes(lo, hi, &airChanged)) return false;
     launchCoefs(matDev_, coef_, geo_, stream_);
+    // non-absorbing grid edges: their faces are wall faces of admittance Y != 1 (pv_boundary.hip).  Edge tiles (class 2) match the
+    // absorbing pattern only, so the tiles along such a side fall to the general arm by the classification below.
+    if (!boundaryAbsorbing()) launchEdgeCoefs(coef_, geo_, edgeAdmittance(edgeR_), stream_);
     if (!hipOk(hipMemsetAsync(generalCount_, 0, sizeof(int), stream_), "memset")) return false;
     launchTileClass(K_, rxi_, coef_, tileClass_, generalList_, generalCount_, geo_, stream_,
                     opt_.edgeTiles);
@@ -1008,6 +1040,7 @@ bool Solver::applyGeometry() {
     if ((airChanged || !labelsValid_) && !makeLabels()) return false;
     mat_.clearDirty();
     geometryDirty_ = false;
+    boundaryDirty_ = false;
     planesDirty_ = true;  // a tile that is dead now may hold an earlier scene's fields
     dynValid_ = false;
     dropGraph();  // tile classes / list capacity may have changed

@@ -163,6 +163,12 @@ public:
     bool shapeSet(int id, const Shape& sh);
     bool shapeClear(int id);
 
+    // Grid edges (pv_boundary.h): absorption R of sides x = 0, x = gx, y = 0, y = gy, as PlaneverbAddGeometry takes it; all 0
+    // (the default) is the reference's absorbing grid.  A change takes effect at the next run of any form.  Finite values only.
+    bool setGridBoundary(const float R4[4]);
+    void gridBoundary(float R4[4]) const;
+    bool boundaryAbsorbing() const;  // every side has Y = 1 (the edge pass is not launched)
+
     // carryFrom (live module, two iterations in flight on two solvers): the solver that ran the PREVIOUS iteration.  The cells
     // in which this run finds no onset take their occlusion / wet gain / decay time / lowpass / source direction from that
     // solver's maps, on the device, behind that solver's analysis and in front of this run's listener-direction pass -- what one
@@ -419,6 +425,8 @@ private:
     int numGeneral_ = 0;
     int launchCap_ = 0;  // general-list entries the general kernel's grid is sized for
     bool geometryDirty_ = true;
+    float edgeR_[4] = {0.f, 0.f, 0.f, 0.f};  // setGridBoundary
+    bool boundaryDirty_ = false;             // edgeR_ changed since the last applyGeometry (no flood fill: air is unchanged)
     float efree_ = 0.f;
     DynParams dynCur_{};
     bool dynValid_ = false;
