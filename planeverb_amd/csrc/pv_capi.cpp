@@ -553,6 +553,7 @@ int PvAmdSetOption(PvAmdSolver* h, int key, long long value) try {
         case PVA_OPT_STREAM_PRIORITY: h->opt.streamPriority = (int)value; break;
         case PVA_OPT_ALTERNATE_SWEEPS: h->opt.alternateSweeps = (int)value; break;
         case PVA_OPT_XCD_REGIONS: h->opt.xcdRegions = (int)value; break;
+        case PVA_OPT_REACH_BOUND: h->opt.reachBound = (int)value; break;
         default: g_lastError = "unknown option"; return -1;
     }
     return 0;

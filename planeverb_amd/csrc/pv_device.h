@@ -121,7 +121,26 @@ struct StepArgs {
                            // a run set it (PVA_OPT_ALTERNATE_SWEEPS): a launch then reads first what the previous launch wrote last,
                            // i.e. what is still in the 256 MiB Infinity Cache, instead of streaming through it.  bit 1: 2 x 4 regions
                            // instead of 8 strips of tile columns (PVA_OPT_XCD_REGIONS)
+    // Reach-bounded launch of a run (PVA_OPT_REACH_BOUND, Solver::reachWindow): winTis > 0 = only the tiles for which
+    // tileInReach(..., reach) holds are advanced; the air blocks walk the tile window [winTi0, +winTis) x [winTj0, +winTjs)
+    // (the bounding rectangle of those tiles) instead of the grid.  winTis = 0 (zero-initialised arguments): full sweep.
+    int reach;             // Manhattan radius around the listener cell (reachRow, reachCol: padded) beyond which every field is 0
+    int reachGrow;         // cells by which a tile's output rectangle is grown to cover everything the tile loads
+    int reachRow, reachCol;
+    int winTi0, winTj0, winTis, winTjs;
 };
+
+// Reach-bounded runs: can tile (ti, tj) load a non-zero value in a launch whose input fields are zero farther than R cells
+// (Manhattan distance) from the listener cell (lrow, lcol; padded)?  Its output rectangle -- padded rows [G + ti*rxi, +rxi) x
+// columns [G + tj*wi, +wi) -- grown by `grow` cells on every side must then come within distance R of the listener.  A tile
+// for which this is false loads only zeros, so a full sweep would compute zeros for it, find it inactive and record nothing.
+__host__ __device__ inline bool tileInReach(int ti, int tj, int rxi, int wi, int G, int grow, int lrow, int lcol, int R) {
+    const int r0 = G + ti * rxi - grow, r1 = G + (ti + 1) * rxi - 1 + grow;
+    const int c0 = G + tj * wi - grow, c1 = G + (tj + 1) * wi - 1 + grow;
+    const int dx = lrow < r0 ? r0 - lrow : (lrow > r1 ? lrow - r1 : 0);
+    const int dy = lcol < c0 ? c0 - lcol : (lcol > c1 ? lcol - c1 : 0);
+    return dx + dy <= R;
+}
 
 // Batched launch (pv_step_batch_kernel): up to kBatchMax independent runs of identically configured solvers advance
 // in ONE launch, blockIdx.y = run.  The whole table travels by value in the kernarg segment (scalar loads).

@@ -1615,6 +1615,20 @@ __device__ __forceinline__ bool xcdTile(const StepArgs& a, int b, int wave, int*
     return xcdTileAt(a, b & 7, (b >> 3) * 4 + wave, ti, tj);  // position inside the XCD's share
 }
 
+// reach-bounded launch (StepArgs::winTis > 0): block b, wave w -> tile of the launch's window.  XCD x = b % 8 owns a contiguous
+// eighth of the window's row-major tile sequence (a window of a few hundred tiles: the XCD split hardly matters); tiles of the
+// window that the fields cannot have reached (tileInReach) are left alone, like the tiles outside the window
+template <int K, int RXI>
+__device__ __forceinline__ bool reachTile(const StepArgs& a, int b, int wave, int* ti, int* tj) {
+    const int n = a.winTis * a.winTjs, per = (n + 7) >> 3;
+    const int q = (b >> 3) * 4 + wave, t = (b & 7) * per + q;
+    if (q >= per || t >= n) return false;
+    const int r = t / a.winTjs;
+    *ti = a.winTi0 + r;
+    *tj = a.winTj0 + (t - r * a.winTjs);
+    return tileInReach(*ti, *tj, RXI, 64 - 2 * K, a.G, a.reachGrow, a.reachRow, a.reachCol, a.reach);
+}
+
 // air tiles: one wave per tile, 4 tiles per 256-thread block; tiles of the other class exit immediately.
 // XCD-aware tile order: workgroup b is dispatched to XCD b % 8 (observed, speed only), and each XCD has a private
 // 4 MiB L2.  XCD x therefore owns a contiguous band of tile rows and walks it column by column, so the tiles that
@@ -1679,13 +1693,21 @@ __global__ __launch_bounds__(256, WPS) void pv_step_merged_kernel(const StepArgs
         if ((int)blockIdx.x >= a.dyn->numGeneral) return;
         const int tile = __builtin_amdgcn_readfirstlane(a.generalList[blockIdx.x]);
         if (deadTileSkippable<K, RXI>(a, tile)) return;  // (block-uniform)
+        if (a.winTis > 0) {  // reach-bounded launch: a general tile the fields cannot have reached stays zero (block-uniform)
+            const int ti = tile / a.nty;
+            if (!tileInReach(ti, tile - ti * a.nty, RXI, 64 - 2 * K, a.G, a.reachGrow, a.reachRow, a.reachCol, a.reach)) return;
+        }
         // (s_setprio(3) for these few, long, barrier-bound waves: +2 % with one run in flight, -3 % with two -- round 5, not kept)
         stepTileGeneral4<K, RXI, GP>(a, tile, wave, lane, gsh);
         return;
     }
     const int b = blockIdx.x - gblocks;
     int ti, tj;
-    if (!xcdTile(a, b, wave, &ti, &tj)) return;
+    if (a.winTis > 0) {
+        if (!reachTile<K, RXI>(a, b, wave, &ti, &tj)) return;
+    } else if (!xcdTile(a, b, wave, &ti, &tj)) {
+        return;
+    }
     const int tile = ti * a.nty + tj;
     const int cls = a.tileClass[tile];
     if (cls == 1) return;
@@ -2022,6 +2044,7 @@ void launchStepSeg(int, int, const StepArgs&, hipStream_t) {}
 
 // positions an XCD's band needs under the chosen order (sub-bands are padded to whole multiples of H rows)
 static int bandPositions(const StepArgs& a) {
+    if (a.winTis > 0) return (a.winTis * a.winTjs + 7) / 8;  // reach-bounded launch: its tile window (reachTile)
     if (a.tileOrder <= 1) return (a.ntiles + 7) / 8;
     if (a.tileOrder == 3) return max(a.ntx * ((a.nty + 7) / 8), ((a.ntx + 1) / 2) * ((a.nty + 3) / 4));  // (8 strips / 2 x 4 regions)
     if (a.tileOrder < 4) return a.bandRows * a.nty;
@@ -2233,6 +2256,18 @@ __global__ void pv_zero_kernel(float4* p, long long n4) {
 void launchZero(float* p, long long n, hipStream_t stream) {
     const long long n4 = n / 4;
     hipLaunchKernelGGL(pv_zero_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (float4*)p, n4);
+}
+
+// rows [r0, r0 + nr) x columns [c0, c0 + nc) of six planes of pitch `pitch` floats (blockIdx.y = plane)
+__global__ void pv_zero_rect_kernel(ZeroRectArgs z) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= z.nr * z.nc) return;
+    const int r = i / z.nc;
+    z.p[blockIdx.y][(long long)(z.r0 + r) * z.pitch + z.c0 + (i - r * z.nc)] = 0.f;
+}
+void launchZeroRect(const ZeroRectArgs& z, hipStream_t stream) {
+    if (z.nr <= 0 || z.nc <= 0) return;
+    hipLaunchKernelGGL(pv_zero_rect_kernel, dim3((unsigned)((z.nr * z.nc + 255) / 256), 6), dim3(256), 0, stream, z);
 }
 
 void launchBeginRun(const BeginArgs& a, hipStream_t stream) {

@@ -69,6 +69,12 @@ void residentDumpTrace();  // development builds: the phase stamps of the last l
 bool smallGridFits(int NX, int NY);
 void launchSmallGrid(const SmallArgs& a, hipStream_t stream);
 void launchZero(float* p, long long n, hipStream_t stream);
+// rows [r0, r0 + nr) x columns [c0, c0 + nc) of six padded planes set to zero (reach-bounded runs: Solver::clearReachPlanes)
+struct ZeroRectArgs {
+    float* p[6];
+    int pitch, r0, nr, c0, nc;
+};
+void launchZeroRect(const ZeroRectArgs& z, hipStream_t stream);
 void launchBeginRun(const BeginArgs& a, hipStream_t stream);
 void launchCoefs(const float* mat, FaceCoef* coef, const Geometry& g, hipStream_t stream);
 void launchLaneSelfTest(float* out128, hipStream_t stream);

@@ -1330,6 +1330,7 @@ StepArgs Solver::baseStepArgs(bool withPulse, bool record) const {
     a.record = record ? 1 : 0;
     a.dense = opt_.denseHistory ? 1 : 0;
     a.courant = g_.courant;
+    a.winTis = 0;  // full sweep (setReachArgs)
     return a;
 }
 
@@ -1349,6 +1350,80 @@ void Solver::setLaunchArgs(StepArgs& a, int t0, int k, bool firstOfRun, int li) 
     a.nzOut = nz_[(li & 1) ^ 1];
     // bit 0: this launch walks the XCDs' tiles backwards (odd launches of a run); bit 1: 2 x 4 regions instead of 8 strips
     a.sweepReverse = opt_.tileOrder == 3 ? (((opt_.alternateSweeps == 1) ? (li & 1) : 0) | (opt_.xcdRegions == 1 ? 2 : 0)) : 0;
+}
+
+// Reach-bounded runs (PVA_OPT_REACH_BOUND).  A run starts from zero fields and its only source is the pulse, added to the
+// listener's pressure at the end of every step (FDTD.cpp:235).  Within a step the pressure of a cell reads its own velocity
+// faces, then each velocity face reads the new pressures of its two cells (FDTD.cpp:124-199); the edge overrides
+// (FDTD.cpp:201-223, csrc pv_kernels.hip edgeStepMirror) tie a face to the pressure of its own cell.  Place p(x, y) at (x, y),
+// vx(x, y) at (x - 1/2, y) and vy(x, y) at (x, y - 1/2): every read is then half a cell away, so a step moves the support of
+// the fields by at most one position unit -- half for the pressures, half for the faces behind them.  After step 0 only
+// p(listener) is non-zero; after step s >= 1 the pressures lie within distance s - 1 and the faces within s - 1/2 (cell index
+// within s).  So when a launch starts at step t0, every pr / vx / vy of a cell farther than t0 - 1 (Manhattan distance, cell
+// indices) from the listener is exactly 0, whatever the geometry.  A tile whose loaded region lies entirely farther than that
+// loads zeros only: a full sweep would compute zeros for it, find it inactive (no tileFirst, no history, nzOut = 0) and store
+// zeros over the zeros its output tiles already hold -- this launch may leave it alone.  Margins, both free at 36 x 40-cell
+// tiles: the radius is t0 + 2 instead of t0 - 1, and a tile's output rectangle is grown by K + 8 cells (its K halo cells,
+// plus the rows a general tile reads beyond them) for the test.  The radius grows from launch to launch, so a tile advanced
+// once is advanced by every later launch of the run; one left alone has never been written since clearReachPlanes.
+void Solver::setReachArgs(StepArgs& a, int t0) {
+    const int R = t0 + 2, grow = K_ + 8;
+    const int lrow = dynCur_.lrow, lcol = dynCur_.lcol;
+    // the window: tiles whose grown rows / columns alone come within R (the diamond's bounding box, in tiles)
+    int ti0 = geo_.ntx, ti1 = -1, tj0 = geo_.nty, tj1 = -1;
+    for (int ti = 0; ti < geo_.ntx; ++ti)
+        if (tileInReach(ti, 0, rxi_, wi_, geo_.G, grow, lrow, geo_.G, R)) {
+            ti0 = std::min(ti0, ti);
+            ti1 = ti;
+        }
+    for (int tj = 0; tj < geo_.nty; ++tj)
+        if (tileInReach(0, tj, rxi_, wi_, geo_.G, grow, geo_.G, lcol, R)) {
+            tj0 = std::min(tj0, tj);
+            tj1 = tj;
+        }
+    a.reach = R;
+    a.reachGrow = grow;
+    a.reachRow = lrow;
+    a.reachCol = lcol;
+    a.winTi0 = ti0;
+    a.winTj0 = tj0;
+    a.winTis = ti1 - ti0 + 1;  // (>= 1: the listener lies inside the grid, reachEligible)
+    a.winTjs = tj1 - tj0 + 1;
+    reachRect_[0] = ti0;
+    reachRect_[1] = a.winTis;
+    reachRect_[2] = tj0;
+    reachRect_[3] = a.winTjs;
+}
+
+// the plain merged-launch path of a run whose listener lies inside the grid; every other path sweeps the grid
+bool Solver::reachEligible(bool graph, bool small) const {
+    const bool mergedLaunch = !stepConfigStacked(K_, rxi_) && opt_.merged == 1 && mergedConfigOk(K_, rxi_);
+    return opt_.reachBound != 0 && mergedLaunch && !graph && !small && !useResident_ && !opt_.streaming && !bandedRun_ &&
+           !segActive_ && !usePatch_ && !opt_.denseHistory && !opt_.edgeTiles && !isSlab() && opt_.timeKernels == 0 &&
+           dynCur_.lrow >= geo_.G && dynCur_.lrow <= geo_.G + g_.gx && dynCur_.lcol >= geo_.G && dynCur_.lcol <= geo_.G + g_.gy;
+}
+
+// Before a reach-bounded run: zeros in both buffer sets wherever its launches do not write.  After a run of another path,
+// raw stepping, setFields or a geometry change, all six planes are cleared; after a reach-bounded run, the rectangle it wrote
+// (its last window's output rectangles and the guard cells around them).  Kernels, not hipMemsetAsync: see enqueueSteps.
+bool Solver::clearReachPlanes() {
+    float* planes[6] = {pr_[0], vx_[0], vy_[0], pr_[1], vx_[1], vy_[1]};
+    if (planesDirty_ || sweptDirty_) {
+        for (float* p : planes) launchZero(p, (long long)geo_.rows * geo_.pitch, stream_);
+        planesDirty_ = false;
+        sweptDirty_ = false;
+    } else if (reachRect_[1] > 0 && reachRect_[3] > 0) {
+        ZeroRectArgs z{};
+        for (int i = 0; i < 6; ++i) z.p[i] = planes[i];
+        z.pitch = geo_.pitch;
+        z.r0 = reachRect_[0] * rxi_;  // (= G + ti0 * rxi - G)
+        z.nr = std::min(geo_.rows, 2 * geo_.G + (reachRect_[0] + reachRect_[1]) * rxi_) - z.r0;
+        z.c0 = reachRect_[2] * wi_;
+        z.nc = std::min(geo_.pitch, 2 * geo_.G + (reachRect_[2] + reachRect_[3]) * wi_) - z.c0;
+        launchZeroRect(z, stream_);
+    }
+    for (int& v : reachRect_) v = 0;
+    return hipOk(hipGetLastError(), "plane clear");
 }
 
 bool Solver::bandsActive() const { return bandedRun_; }
@@ -1444,6 +1519,7 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
     while (done < nsteps) {
         const int k = std::min(K_, nsteps - done);
         setLaunchArgs(a, firstStep + done, k, fromZero && done == 0, li);
+        if (reachRun_) setReachArgs(a, firstStep + done);
         if (opt_.timeKernels > 0) {  // 4 timing events per sampled launch: air begin/end on stream_, general begin/end
             while ((int)kev_.size() < kevUsed_ + 4) {
                 hipEvent_t e;
@@ -1767,6 +1843,13 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     const bool small = smallWanted && opt_.K == 0 && opt_.rxi == 0 && !opt_.timeKernels &&
                        opt_.useGraph != 1 && !opt_.streaming && smallGridFits(g_.NX, g_.NY) &&
                        histTilesX_ == geo_.ntx && histTilesY_ == geo_.nty;
+    // reach-bounded (setReachArgs): the plain merged-launch path below; every other path leaves fields anywhere
+    const bool reach = reachEligible(graph, small);
+    if (reach) {
+        if (!clearReachPlanes()) return false;
+    } else {
+        sweptDirty_ = true;
+    }
     if (opt_.streaming) {
         // sparse-emitter mode: ring history; forward sums advanced after every `ring_` steps
         const size_t nres = (size_t)g_.gx * g_.gy;
@@ -1953,7 +2036,10 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
         }
     } else {
         launchCap_ = numGeneral_;
-        if (!enqueueResetAndSteps()) return false;
+        reachRun_ = reach;
+        const bool ok = enqueueResetAndSteps();
+        reachRun_ = false;
+        if (!ok) return false;
     }
     if (!stampTimed_) hipEventRecord(ev_[1], stream_);
     if (!opt_.skipAnalysis) enqueueAnalysis(lx, lz);
@@ -2071,6 +2157,7 @@ bool Solver::runBatch(Solver* const* s, int n, const float* lxyz, bool wait, std
         v.kevUsed_ = 0;
         v.loopTimed_ = false;
         v.cur_ = 0;
+        v.sweptDirty_ = true;  // (full sweeps: clearReachPlanes)
         v.launchCap_ = v.numGeneral_;
         gcap = std::max(gcap, v.numGeneral_);
         v.stampTimed_ = false;

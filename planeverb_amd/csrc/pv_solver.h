@@ -67,6 +67,8 @@ struct SolverOptions {
                                // -1 = default, 0 = off, 1 = on
     int rowBands = 0;     // B > 1: each sweep = B launches (bands of tile rows, one stream each) with 3-point
                           // dependencies between consecutive sweeps; 0 = auto, 1 = off
+    int reachBound = -1;  // PVA_OPT_REACH_BOUND: runs of the plain merged-launch path advance only the tiles the pulse can have
+                          // reached by each launch (Solver::setReachArgs); -1 = default (on), 0 = full sweeps, 1 = on
 };
 
 struct SolverTimings {
@@ -329,6 +331,16 @@ private:
     int* deadCount_ = nullptr;
     int numDead_ = 0;
     bool planesDirty_ = false;      // the field planes may hold non-zero values inside dead tiles
+    // Reach-bounded runs (PVA_OPT_REACH_BOUND) write only the tiles of their launches' windows, so both buffer sets must hold
+    // zeros everywhere else when one starts (clearReachPlanes).  sweptDirty_: a run of another path has left fields anywhere
+    // since the last full clear; reachRect_: tile rows [0], +[1] x tile columns [2], +[3] = the last reach-bounded run's final
+    // window (the windows of a run only grow), the only place that run left non-zero values.
+    bool sweptDirty_ = true;
+    int reachRect_[4] = {0, 0, 0, 0};
+    bool reachRun_ = false;         // enqueueSteps: the run being enqueued is reach-bounded
+    bool reachEligible(bool graph, bool small) const;
+    bool clearReachPlanes();
+    void setReachArgs(StepArgs& a, int t0);
     int* generalList_ = nullptr;
     int* generalCount_ = nullptr;
     DynParams* dynDev_ = nullptr;
