@@ -98,6 +98,10 @@ PVA_EXPORT void PlaneverbRemovePolygonGeometry(int id);
  * like the geometry calls and applied to both live solvers at the same iteration boundary.  A non-finite value is refused
  * (nothing changes; PvAmdLastError says why). */
 PVA_EXPORT void PlaneverbSetGridBoundary(float xMin, float xMax, float zMin, float zMax);
+/* Extension: graded absorbing layers of widths xMin (side x = 0), xMax (x = gx), zMin (y = 0), zMax (y = gy) in cells
+ * (PvAmdSetEdgeLayer), queued like PlaneverbSetGridBoundary and applied to both live solvers at the same iteration boundary.
+ * Refused (nothing changes; PvAmdLastError says why) in sparse-emitter mode and for widths PvAmdSetEdgeLayer refuses. */
+PVA_EXPORT void PlaneverbSetEdgeLayer(int xMin, int xMax, int zMin, int zMax);
 
 /* Extensions to the live module (not in the reference's flat ABI) */
 /* One sample of an impulse response as the reference stores it (Cell, PvTypes.h:106-121: 16 bytes) */
@@ -319,6 +323,39 @@ PVA_EXPORT int PvAmdUpdateOrientedBox(PvAmdSolver* s, int id, float px, float py
  * every slab; slab ranks (PvAmdCreateSlabRank) refuse any non-zero side.  The .pv scene format does not hold the boundary. */
 PVA_EXPORT int PvAmdSetGridBoundary(PvAmdSolver* s, const float absorption4[4]);
 PVA_EXPORT int PvAmdGetGridBoundary(PvAmdSolver* s, float out4[4]);
+/* Graded absorbing layers (PML-style damping bands) along the grid edges, for open scenes: the absorbing edge above reflects a
+ * wave that meets it at an angle (about (cos t - 1) / (cos t + 1) of it).  width4 = widths in cells of the sides in the order of
+ * PvAmdSetGridBoundary (x = 0, x = gx, y = 0, y = gy), 0..64, 0 = no layer (the default: every path and result as without this
+ * call).  A layer is the outermost w cells of its side, inside the grid: coordinates, gx / gy and the result map do not change,
+ * and the cells of a layer get results like any other cell, but those results are NOT physical (the field is being damped
+ * there).  The damping is eight float32 tables (PvAmdHostEdgeLayerTables); in the stencil only two expressions change,
+ * multiplications only, without contraction (C = the Courant number, div / grad as in FDTD.cpp:124-199):
+ *   pressure: pr' = beta * ((apx[x] * apy[y]) * pr - (bpx[x] * bpy[y]) * (C * div))
+ *   vx, air : ax[x] * vx - bx[x] * (C * grad_x)          vy, air : ay[y] * vy - by[y] * (C * grad_y)
+ * The wall-face terms, the beta blend, the grid-edge rule (with PvAmdSetGridBoundary's R: a layer may sit in front of a rigid
+ * edge) and the record-then-pulse order are unchanged; every factor is exactly 1 outside the layers.  The library records the
+ * pressure only and re-derives velocities without the damping, so the source direction (srcDir) and the impulse-response
+ * velocities of cells inside a layer are not the damped stencil's either.
+ * Refused (-1, nothing changes): NULL, a width below 0 or above 64, widths that leave fewer than 8 cells between two opposite
+ * layers (or a layer and the far edge), sparse-emitter (PVA_OPT_STREAMING_ANALYSIS) solvers, slab groups and slab ranks, edge
+ * tiles (PVA_OPT_EDGE_TILES) and tile configurations without a layer kernel (the product library's tiles have one).
+ * A solver with a layer runs the tile path: merged launches plus one layer launch per K-step sweep, as a captured graph or plain
+ * launches, reach-bounded where PVA_OPT_REACH_BOUND applies.  The resident kernel, the small-grid kernel, the stacked, segment
+ * and patch forms, row bands and the two-kernel form need a layer-free grid and resolve off (PvAmdInfo.residentKernel = 0);
+ * batched runs (PvAmdRunBatch) refuse a solver with a layer.  A change takes effect at the next run of any form.  Bakes fold the
+ * widths into the material hash when some width is non-zero.  The .pv scene format does not hold the layer. */
+PVA_EXPORT int PvAmdSetEdgeLayer(PvAmdSolver* s, const int width4[4]);
+PVA_EXPORT int PvAmdGetEdgeLayer(PvAmdSolver* s, int out4[4]);
+/* CPU only: the layer tables of the grid (sizeX, sizeY, res) with widths width4, into out[4 (gx + 1) + 4 (gy + 1)] in this order:
+ * apx[gx + 1], bpx[gx + 1], ax[gx + 1], bx[gx + 1], apy[gy + 1], bpy[gy + 1], ay[gy + 1], by[gy + 1] (index = cell row x for apx
+ * / bpx, velocity face x -- between cells x - 1 and x -- for ax / bx; y likewise).  For a damping value s:
+ * a = (1 - s) / (1 + s), b = 1 / (1 + s), computed in double and rounded to float.  Cells sit at half depths, faces at whole
+ * depths: with a layer of width w on side 0, face x has depth w - x (x <= w) and cell x depth w - x - 1/2 (x < w); on side 1,
+ * face x has depth x - (gx - w) (x >= gx - w) and cell x depth x + 1/2 - (gx - w) (gx - w <= x < gx); the ghost cell x = gx
+ * lies outside every layer.  s = s_max * (depth / w)^2 for depth > 0, else 0; s_max = 3 C ln(1 / R0) / (4 w) (the grading rule
+ * with m = 2) with R0 = 0.1 and C the grid's float32 Courant number taken to double.  Returns the number of floats written,
+ * or -1 (a refused width, res < 275, NULL). */
+PVA_EXPORT int PvAmdHostEdgeLayerTables(float gridSizeX, float gridSizeY, int gridResolution, const int width4[4], float* out);
 /* CPU only: the four vertices out8 the library uses for that oriented box (0, or -1 for a refused input) */
 PVA_EXPORT int PvAmdHostOrientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float* out8);
 /* CPU only: the shape the library makes of a vertex list (counter-clockwise, out16 gets 2n floats); returns n, or -1 for a

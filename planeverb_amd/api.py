@@ -175,6 +175,10 @@ SYMBOLS = {
     "PvAmdSetGridBoundary": (C.c_int, [_vp, _fp]),
     "PvAmdGetGridBoundary": (C.c_int, [_vp, _fp]),
     "PlaneverbSetGridBoundary": (None, [C.c_float] * 4),
+    "PvAmdSetEdgeLayer": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "PvAmdGetEdgeLayer": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "PlaneverbSetEdgeLayer": (None, [C.c_int] * 4),
+    "PvAmdHostEdgeLayerTables": (C.c_int, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), _fp]),
     "PvAmdHostOrientedBoxVertices": (C.c_int, [C.c_float] * 6 + [_fp]),
     "PvAmdHostShape": (C.c_int, [_fp, C.c_int, C.c_float, _fp]),
     "PvAmdHostShapeCoverage": (C.c_int, [C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
@@ -379,6 +383,12 @@ def SetGridBoundary(xmin, xmax, zmin, zmax):
     lib().PlaneverbSetGridBoundary(float(xmin), float(xmax), float(zmin), float(zmax))
 
 
+def SetEdgeLayer(xmin, xmax, zmin, zmax):
+    """widths in cells of the graded absorbing layers along the four grid edges (Solver.set_edge_layer), applied at the next
+    iteration boundary; a refusal (sparse-emitter mode, widths the grid cannot hold) changes nothing and sets last_error()"""
+    lib().PlaneverbSetEdgeLayer(int(xmin), int(xmax), int(zmin), int(zmax))
+
+
 def SetListenerPosition(pos):
     lib().PlaneverbSetListenerPosition(*[float(v) for v in pos])
 
@@ -473,6 +483,31 @@ def host_shape_coverage(size_x, size_y, res, vertices):
     _check(lib().PvAmdHostShapeCoverage(float(size_x), float(size_y), int(res), _f(a), n,
                                         cover.ctypes.data_as(C.POINTER(C.c_ubyte))))
     return cover
+
+
+EDGE_LAYER_DEFAULT_WIDTH = 24  # cells: the width the edge-layer documentation and tests use (any 1..64 is accepted)
+
+
+def _w4(w4):
+    a = np.ascontiguousarray(w4, np.int32).reshape(-1)
+    if a.size != 4:
+        raise ValueError("four widths: x = 0, x = gx, y = 0, y = gy")
+    return a
+
+
+def edge_layer_tables(size_x, size_y, res, w4):
+    """the eight float32 damping tables of edge layers of widths w4 (PvAmdHostEdgeLayerTables, CPU only): a dict of apx, bpx,
+    ax, bx (gx + 1 each) and apy, bpy, ay, by (gy + 1 each)"""
+    i = host_grid_info(size_x, size_y, res)
+    a = _w4(w4)
+    out = np.empty(4 * (i.gx + 1) + 4 * (i.gy + 1), np.float32)
+    n = lib().PvAmdHostEdgeLayerTables(float(size_x), float(size_y), int(res), a.ctypes.data_as(C.POINTER(C.c_int)), _f(out))
+    if n < 0:
+        raise PlaneverbError(last_error())
+    nx, ny = i.gx + 1, i.gy + 1
+    names = ["apx", "bpx", "ax", "bx", "apy", "bpy", "ay", "by"]
+    offs = [0, nx, 2 * nx, 3 * nx, 4 * nx, 4 * nx + ny, 4 * nx + 2 * ny, 4 * nx + 3 * ny]
+    return {k: out[o:o + (nx if j < 4 else ny)].copy() for j, (k, o) in enumerate(zip(names, offs))}
 
 
 def load_pv(path, max_boxes=4096):
@@ -932,6 +967,19 @@ class Solver:
     def grid_boundary(self):
         out = np.zeros(4, np.float32)
         _check(lib().PvAmdGetGridBoundary(self._h, _f(out)))
+        return out
+
+    def set_edge_layer(self, w4):
+        """widths in cells (0..64, 0 = none) of graded absorbing layers along the grid edges x = 0, x = gx, y = 0, y = gy
+        (include/planeverb_amd.h PvAmdSetEdgeLayer).  Cells inside a layer get results, but not physical ones.  Takes effect
+        at the next run."""
+        a = _w4(w4)
+        _check(lib().PvAmdSetEdgeLayer(self._h, a.ctypes.data_as(C.POINTER(C.c_int))))
+        _check(lib().PvAmdGetInfo(self._h, self.info))  # (residentKernel: 0 while a layer is set)
+
+    def edge_layer(self):
+        out = np.zeros(4, np.int32)
+        _check(lib().PvAmdGetEdgeLayer(self._h, out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
 
     def run(self, listener):

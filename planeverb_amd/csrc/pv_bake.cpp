@@ -42,6 +42,11 @@ bool materialOf(Solver* s, std::vector<uint8_t>* beta, unsigned long long* hash,
         s->gridBoundary(edges);
         *hash = fnv1a64(edges, sizeof edges, *hash);
     }
+    if (s->layerActive()) {  // then -- only when some side has one -- the four edge-layer widths (int32)
+        int w[4];
+        s->edgeLayer(w);
+        *hash = fnv1a64(w, sizeof w, *hash);
+    }
     return true;
 }
 

@@ -14,6 +14,7 @@
 #include "pv_shard.h"
 #include "pv_slabs.h"
 #include "pv_launch.h"
+#include "pv_layer.h"
 #include "pv_solver.h"
 #endif
 
@@ -149,6 +150,17 @@ void PlaneverbSetGridBoundary(float xMin, float xMax, float zMin, float zMax) tr
         }
     Context::Ref c;
     if (c) c->setGridBoundary(R4);
+} PV_API_CATCH_VOID
+
+void PlaneverbSetEdgeLayer(int xMin, int xMax, int zMin, int zMax) try {
+    const int w4[4] = {xMin, xMax, zMin, zMax};
+    Context::Ref c;
+    if (!c) {
+        g_lastError = "PlaneverbSetEdgeLayer: the module is not initialised";
+        return;
+    }
+    std::string err;
+    if (!c->setEdgeLayer(w4, &err)) g_lastError = err;
 } PV_API_CATCH_VOID
 
 void PlaneverbExit(void) try {
@@ -306,7 +318,7 @@ const char* PlaneverbWorkerError(void) try {
     w = (c && c->failed()) ? c->workerError() : std::string();
     return w.c_str();
 } PV_API_CATCH("")
-const char* PvAmdVersion(void) try { return "planeverb_amd 0.2 (gfx950)"; } PV_API_CATCH("")
+const char* PvAmdVersion(void) try { return "planeverb_amd 0.3 (gfx950)"; } PV_API_CATCH("")
 
 #ifndef PVA_HOST_TEST
 int PvAmdDeviceCount(void) try {
@@ -717,6 +729,35 @@ int PvAmdSetGridBoundary(PvAmdSolver* h, const float* absorption4) try {
     return ret(h, h->g ? h->g->setGridBoundary(absorption4) : h->s->setGridBoundary(absorption4));
 } PV_API_CATCH(-1)
 
+int PvAmdSetEdgeLayer(PvAmdSolver* h, const int* width4) try {
+    if (!width4) {
+        g_lastError = "PvAmdSetEdgeLayer: null width array";
+        return -1;
+    }
+    const bool any = width4[0] != 0 || width4[1] != 0 || width4[2] != 0 || width4[3] != 0;
+    if (h && any && (h->opt.slabCount > 1 || !h->slabDevices.empty())) {
+        g_lastError = "PvAmdSetEdgeLayer: edge layers are not available on slab groups or slab ranks";
+        return -1;
+    }
+    if (h && !h->slabDevices.empty()) return 0;  // (all widths 0 on a slab group: nothing to change)
+    if (!ensure(h)) return -1;
+    return ret(h, h->s->setEdgeLayer(width4));
+} PV_API_CATCH(-1)
+
+int PvAmdGetEdgeLayer(PvAmdSolver* h, int* out4) try {
+    if (!out4) {
+        g_lastError = "PvAmdGetEdgeLayer: null output array";
+        return -1;
+    }
+    if (h && !h->slabDevices.empty()) {
+        for (int k = 0; k < 4; ++k) out4[k] = 0;
+        return 0;
+    }
+    if (!ensure(h)) return -1;
+    h->s->edgeLayer(out4);
+    return 0;
+} PV_API_CATCH(-1)
+
 int PvAmdGetGridBoundary(PvAmdSolver* h, float* out4) try {
     if (!out4) {
         g_lastError = "PvAmdGetGridBoundary: null output array";
@@ -1070,6 +1111,25 @@ int PvAmdHostShapeCoverage(float sx, float sy, int res, const float* xy, int n, 
     for (int x = x0; x < x1; ++x)
         for (int y = y0; y < y1; ++y) cover[(size_t)x * g.NY + y] = shapeCovers(sh, g.dx, x, y) ? 1 : 0;
     return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostEdgeLayerTables(float sx, float sy, int res, const int* width4, float* out) try {
+    if (res < kLowResolution || !width4 || !out) {
+        g_lastError = "PvAmdHostEdgeLayerTables: resolution below 275 or a null array";
+        return -1;
+    }
+    const GridSpec g = makeGridSpec(sx, sy, res);
+    if (g.gx < 1 || g.gy < 1) {
+        g_lastError = "PvAmdHostEdgeLayerTables: grid has no cells";
+        return -1;
+    }
+    const char* why = edgeLayerRefusal(g.gx, g.gy, width4);
+    if (*why) {
+        g_lastError = std::string("PvAmdHostEdgeLayerTables: ") + why;
+        return -1;
+    }
+    edgeLayerTables(g.gx, g.gy, g.courant, width4, out);
+    return 4 * (g.NX + g.NY);
 } PV_API_CATCH(-1)
 
 int PvAmdHostLoadPv(const char* path, float* b5, int maxBoxes) try {

@@ -1,5 +1,8 @@
 // pv_context.cpp -- see pv_context.h
 #include "pv_context.h"
+#ifndef PVA_HOST_TEST
+#include "pv_layer.h"
+#endif
 
 #include <algorithm>
 #include <chrono>
@@ -667,7 +670,39 @@ void Context::setGridBoundary(const float R4[4]) {
     changes_.push_back(c);
 }
 
+bool Context::setEdgeLayer(const int w4[4], std::string* err) {
+#ifndef PVA_HOST_TEST
+    if (streaming_) {
+        *err = "PlaneverbSetEdgeLayer: edge layers are not available in sparse-emitter mode";
+        return false;
+    }
+    const GridSpec& g = spec();
+    const char* why = edgeLayerRefusal(g.gx, g.gy, w4);
+    if (*why) {
+        *err = std::string("PlaneverbSetEdgeLayer: ") + why;
+        return false;
+    }
+    if ((w4[0] || w4[1] || w4[2] || w4[3]) && !layerConfigOk(solver_->K(), solver_->rxi())) {
+        *err = "PlaneverbSetEdgeLayer: no layer kernel for this grid's tile configuration";
+        return false;
+    }
+#endif
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    ensureRoom(changes_, 1);
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.layer = true;
+    for (int k = 0; k < 4; ++k) c.W4[k] = w4[k];
+    changes_.push_back(c);
+    return true;
+}
+
 void Context::applyChange(Solver* s, const Change& c) {
+    if (c.layer) {
+#ifndef PVA_HOST_TEST
+        s->setEdgeLayer(c.W4);  // (validated by setEdgeLayer: the widths fit the grid and the configuration)
+#endif
+        return;
+    }
     if (c.boundary) {
 #ifndef PVA_HOST_TEST
         s->setGridBoundary(c.R4);  // (validated by the caller: finite values cannot be refused)

@@ -412,4 +412,45 @@ std::vector<SegRect> planSegments(const uint8_t* air, int ntx, int nty, int rxi,
     return out;
 }
 
+const char* edgeLayerRefusal(int gx, int gy, const int w4[4]) {
+    for (int k = 0; k < 4; ++k)
+        if (w4[k] < 0 || w4[k] > kEdgeLayerMaxWidth) return "edge layer widths run from 0 to 64 cells";
+    if ((w4[0] > 0 || w4[1] > 0) && gx - w4[0] - w4[1] < kEdgeLayerMinInterior)
+        return "edge layers along x leave fewer than 8 interior cells";
+    if ((w4[2] > 0 || w4[3] > 0) && gy - w4[2] - w4[3] < kEdgeLayerMinInterior)
+        return "edge layers along y leave fewer than 8 interior cells";
+    return "";
+}
+
+// one axis of n = g cells (+ the ghost): cell and face tables for layers of widths wlo (index 0 side) and whi (index g side)
+static void axisTables(int g, int wlo, int whi, double C, float* ap, float* bp, float* a, float* b) {
+    auto sOf = [&](double depth, int w) {
+        if (w <= 0 || depth <= 0.0) return 0.0;
+        const double smax = 3.0 * C * std::log(1.0 / kEdgeLayerR0) / (4.0 * w);
+        const double u = depth / w;
+        return smax * (u * u);
+    };
+    for (int x = 0; x <= g; ++x) {
+        double sc = 0.0, sf = 0.0;
+        if (x < g) {  // (the ghost cell x = g lies outside every layer)
+            if (x < wlo) sc += sOf(wlo - x - 0.5, wlo);
+            if (x >= g - whi) sc += sOf(x + 0.5 - (g - whi), whi);
+        }
+        if (x <= wlo) sf += sOf((double)(wlo - x), wlo);
+        if (x >= g - whi) sf += sOf((double)(x - (g - whi)), whi);
+        ap[x] = (float)((1.0 - sc) / (1.0 + sc));
+        bp[x] = (float)(1.0 / (1.0 + sc));
+        a[x] = (float)((1.0 - sf) / (1.0 + sf));
+        b[x] = (float)(1.0 / (1.0 + sf));
+    }
+}
+
+void edgeLayerTables(int gx, int gy, float courant, const int w4[4], float* out) {
+    const int nx = gx + 1, ny = gy + 1;
+    float* o = out;
+    axisTables(gx, w4[0], w4[1], (double)courant, o, o + nx, o + 2 * nx, o + 3 * nx);
+    o += 4 * nx;
+    axisTables(gy, w4[2], w4[3], (double)courant, o, o + ny, o + 2 * ny, o + 3 * ny);
+}
+
 }  // namespace pva

@@ -104,6 +104,24 @@ bool shapeCovers(const Shape& s, float dx, int x, int y);
 // function), clipped to the grid's cells 0 <= x < gx, 0 <= y < gy (never the ghost row / column); empty when x0 >= x1 or y0 >= y1
 void shapeCellBounds(const Shape& s, const GridSpec& g, int* x0, int* x1, int* y0, int* y1);
 
+// Graded absorbing layers at the grid edges (pv_layer.h: the model and the layer kernel)
+constexpr int kEdgeLayerMaxWidth = 64;
+constexpr int kEdgeLayerMinInterior = 8;  // cells between two opposite layers (or a layer and the far edge)
+constexpr int kEdgeLayerDefaultWidth = 24;
+// the grading rule's design reflection: s_max = (m + 1) * C * ln(1 / R0) / (4 w), m = 2 (tuned by tests/test_host_layer.py)
+constexpr double kEdgeLayerR0 = 0.1;
+
+// The tables of a gx x gy grid (cell array (gx + 1) x (gy + 1)), into out[4 (gx + 1) + 4 (gy + 1)] in this order:
+//   apx[gx + 1], bpx[gx + 1], ax[gx + 1], bx[gx + 1], apy[gy + 1], bpy[gy + 1], ay[gy + 1], by[gy + 1]
+// For a damping value s: a = (1 - s) / (1 + s), b = 1 / (1 + s), in double, rounded to float.  Cells sit at half depths and
+// velocity faces at whole depths: along x with a layer of width w on side 0, face x (between cells x - 1 and x) has depth
+// w - x for x <= w and cell x has depth w - x - 1/2 for x < w; on side 1, face x has depth x - (gx - w) for x >= gx - w and
+// cell x depth x + 1/2 - (gx - w) for gx - w <= x < gx.  s = s_max (depth / w)^2, 0 outside the layers (depth <= 0, the
+// ghost cell x = gx included); y likewise with sides 2 and 3.  courant = the grid's Courant number (GridSpec::courant).
+void edgeLayerTables(int gx, int gy, float courant, const int w4[4], float* out);
+// why w4 is refused for a gx x gy grid ("" = accepted)
+const char* edgeLayerRefusal(int gx, int gy, const int w4[4]);
+
 // .pv scene files: PlaneverbSandbox/src/Editor/Editor.cpp:219-281
 bool loadPv(const std::string& path, std::vector<Box>* out, std::string* err);
 bool savePv(const std::string& path, const std::vector<std::pair<int, Box>>& boxes, std::string* err);

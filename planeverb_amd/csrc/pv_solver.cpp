@@ -1,6 +1,7 @@
 // pv_solver.cpp -- see pv_solver.h
 #include "pv_solver.h"
 #include "pv_boundary.h"
+#include "pv_layer.h"
 #include "pv_shapes.h"
 
 #include <unistd.h>
@@ -635,6 +636,8 @@ Solver::~Solver() {
     if (useResident_) residentDumpTrace();
 #endif
     if (resFlags_) hipFree(resFlags_);
+    if (layerList_) hipFree(layerList_);
+    if (layerTab_) hipFree(layerTab_);
     if (emCells_) hipFree(emCells_);
     if (emTrace_) hipFree(emTrace_);
     void* ptrs[] = {coef_,      matDev_, pulseDev_, hist_,  tileFirst_, tileClass_, generalList_,
@@ -962,8 +965,79 @@ bool Solver::boundaryAbsorbing() const {
     return true;
 }
 
+bool Solver::setEdgeLayer(const int w4[4]) {
+    if (opt_.streaming) return fail("edge layers: not on a sparse-emitter (streaming-analysis) solver");
+    if (isSlab()) return fail("edge layers: not on slabs");
+    if (opt_.edgeTiles) return fail("edge layers: not with edge tiles (PVA_OPT_EDGE_TILES)");
+    const bool any = w4[0] > 0 || w4[1] > 0 || w4[2] > 0 || w4[3] > 0;
+    if (any && (!layerConfigOk(K_, rxi_) || stepConfigStacked(K_, rxi_) || !mergedConfigOk(K_, rxi_)))
+        return fail("edge layers: no layer kernel for this tile configuration");
+    const char* why = edgeLayerRefusal(g_.gx, g_.gy, w4);
+    if (*why) return fail(why);
+    for (int k = 0; k < 4; ++k) {
+        if (layerW_[k] != w4[k]) layerDirty_ = true;
+        layerW_[k] = w4[k];
+    }
+    return true;
+}
+
+void Solver::edgeLayer(int w4[4]) const {
+    for (int k = 0; k < 4; ++k) w4[k] = layerW_[k];
+}
+
+// Layer tiles: every tile whose loaded region (interior + K halo rows / columns) holds a cell of a layer.  They get class 1 (the
+// merged launch's air arm leaves them) and leave the general list; the layer launch advances them.  The tables go up as padded
+// planes with 1 in the padding, so that the kernel indexes them by padded row / column.
+bool Solver::classifyLayer() {
+    numLayer_ = 0;
+    if (!layerActive()) return true;
+    const int ntiles = geo_.ntx * geo_.nty, rows = geo_.rows, pitch = geo_.pitch, G = geo_.G;
+    if (!layerList_ && !dalloc(&layerList_, (size_t)ntiles, false)) return false;
+    if (!layerTab_ && !dalloc(&layerTab_, (size_t)4 * (rows + pitch), false)) return false;
+    const int ROWS = rxi_ + 2 * K_;
+    const int xlo = layerW_[0], xhi = g_.gx - layerW_[1], ylo = layerW_[2], yhi = g_.gy - layerW_[3];
+    std::vector<int> list;
+    for (int ti = 0; ti < geo_.ntx; ++ti) {
+        const int r0 = ti * rxi_ - K_, r1 = r0 + ROWS;  // grid rows [r0, r1)
+        const bool rowsHit = (r0 < xlo && r1 > 0) || (r1 > xhi && r0 < g_.gx);
+        for (int tj = 0; tj < geo_.nty; ++tj) {
+            const int c0 = tj * wi_ - K_, c1 = c0 + 64;
+            const bool colsHit = (c0 < ylo && c1 > 0) || (c1 > yhi && c0 < g_.gy);
+            if (rowsHit || colsHit) list.push_back(ti * geo_.nty + tj);
+        }
+    }
+    std::vector<uint8_t> isLayer((size_t)ntiles, 0);
+    for (int t : list) {
+        isLayer[(size_t)t] = 1;
+        tileClassHost_[(size_t)t] = 1;
+    }
+    std::vector<int> walls;
+    for (int t : wallTiles_)
+        if (!isLayer[(size_t)t]) walls.push_back(t);
+    wallTiles_.swap(walls);
+    std::vector<float> t((size_t)4 * (g_.NX + g_.NY));
+    edgeLayerTables(g_.gx, g_.gy, g_.courant, layerW_, t.data());
+    layerTabHost_.assign((size_t)4 * (rows + pitch), 1.f);
+    for (int k = 0; k < 4; ++k) {
+        for (int x = 0; x < g_.NX; ++x) layerTabHost_[(size_t)k * rows + G + x] = t[(size_t)k * g_.NX + x];
+        for (int y = 0; y < g_.NY; ++y)
+            layerTabHost_[(size_t)4 * rows + (size_t)k * pitch + G + y] = t[(size_t)4 * g_.NX + (size_t)k * g_.NY + y];
+    }
+    layerListHost_ = list;
+    numLayer_ = (int)list.size();
+    // (pageable sources: staged before the calls return; the stream is synchronised right after)
+    if (!hipOk(hipMemcpyAsync(tileClass_, tileClassHost_.data(), tileClassHost_.size(), hipMemcpyHostToDevice, stream_),
+               "class upload") ||
+        !hipOk(hipMemcpyAsync(layerTab_, layerTabHost_.data(), layerTabHost_.size() * 4, hipMemcpyHostToDevice, stream_),
+               "layer tables") ||
+        (numLayer_ > 0 && !hipOk(hipMemcpyAsync(layerList_, layerListHost_.data(), sizeof(int) * (size_t)numLayer_,
+                                                hipMemcpyHostToDevice, stream_), "layer list")))
+        return false;
+    return hipOk(hipStreamSynchronize(stream_), "layer sync");
+}
+
 bool Solver::applyGeometry() {
-    if (!geometryDirty_ && !boundaryDirty_ && mat_.dirtyLo() >= mat_.dirtyHi() && shapeDirty_.empty()) return true;
+    if (!geometryDirty_ && !boundaryDirty_ && !layerDirty_ && mat_.dirtyLo() >= mat_.dirtyHi() && shapeDirty_.empty()) return true;
     const auto t0 = std::chrono::steady_clock::now();
     int lo = mat_.dirtyLo(), hi = mat_.dirtyHi();
     if (shapesActive_ && !matBaseDev_) {
@@ -1027,6 +1101,8 @@ bool Solver::applyGeometry() {
         !hipOk(hipStreamSynchronize(stream_), "geometry sync"))
         return false;
     std::sort(wallTiles_.begin(), wallTiles_.end());
+    if (!classifyLayer()) return false;
+    count = (int)wallTiles_.size();
     {
         // Scenes with many wall tiles (>= 8 % general: the 25 m rooms at 4096^2 / 8192^2 have 13-16 %) take the merged kernel
         // whose general arm is the packed one also at K = 12 (launchStep, kStepGeneralPacked); decided per geometry, so a
@@ -1041,6 +1117,7 @@ bool Solver::applyGeometry() {
     mat_.clearDirty();
     geometryDirty_ = false;
     boundaryDirty_ = false;
+    layerDirty_ = false;
     planesDirty_ = true;  // a tile that is dead now may hold an earlier scene's fields
     dynValid_ = false;
     dropGraph();  // tile classes / list capacity may have changed
@@ -1153,7 +1230,7 @@ int Solver::globalWindowTileRow0(int lcx) const {
 }
 
 bool Solver::prepareDyn(int lcx, int lcy, bool withPulse, bool banded) {
-    bandedRun_ = banded && nb_ > 1;
+    bandedRun_ = banded && nb_ > 1 && !layerActive();  // (a layer: one launch per sweep beside the layer launch)
     DynParams d{};
     const bool inside = withPulse && lcx >= 0 && lcx <= g_.gx && lcy >= 0 && lcy <= g_.gy;
     d.lrow = inside ? lcx - x0_ + geo_.G : -100000;  // (a slab: possibly far outside its own rows)
@@ -1198,7 +1275,7 @@ bool Solver::prepareDyn(int lcx, int lcy, bool withPulse, bool banded) {
     dynHost_->numGeneral = n;
     if (const char* v = getenv("PLANEVERB_AMD_VERBOSE"); v && atoi(v) > 0)
         std::fprintf(stderr, "[planeverb_amd] %d x %d tiles (K %d, %d rows): %d general, %d dead\n", geo_.ntx, geo_.nty, K_, rxi_, n, numDead_);
-    segActive_ = useSeg_ && !bandedRun_;
+    segActive_ = useSeg_ && !bandedRun_ && !layerActive();
     numSeg_ = 0;
     if (segActive_) buildSegments(n);
     segActive_ = segActive_ && numSeg_ > 0;
@@ -1464,8 +1541,9 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
     // tiles of the other set, so launch i+1 of EITHER kernel must wait for launch i of BOTH (RAW on the halos it
     // reads, WAR on the tiles it overwrites): one event per kernel per launch.
     // merged: one launch per K steps on one stream (no cross-stream hand-shake); not with the streaming kernel
+    // (a layer: always merged -- setEdgeLayer refused the configurations without a merged kernel)
     const bool mergedLaunch =
-        stepConfigStacked(K_, rxi_) || (opt_.merged == 1 && mergedConfigOk(K_, rxi_));
+        stepConfigStacked(K_, rxi_) || ((opt_.merged == 1 || numLayer_ > 0) && mergedConfigOk(K_, rxi_));
     const bool two = launchCap_ > 0 && !mergedLaunch;
     const int nl = ceilDiv(nsteps, K_);
     if (two) {
@@ -1569,13 +1647,24 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
                     hipEventRecord(openEv_[2 + (li & 1)], openStream_);
                     openPending_ = true;
                 }
-            } else if (usePatch_) {
+            } else if (usePatch_ && numLayer_ == 0) {
                 // general tiles in their 4-wave blocks, then the air tiles by the resident workgroups (disjoint tiles of
                 // the same output set; neither reads what the other writes)
                 launchStep(K_, rxi_, a, stream_, 16);
                 launchStepPatch(K_, rxi_, a, patchBlocks_, stream_);
             } else {
                 launchStep(K_, rxi_, a, stream_, stepWhich_);
+            }
+            if (numLayer_ > 0) {  // the layer tiles, behind the merged launch on the same stream (disjoint tiles)
+                LayerArgs l{};
+                l.a = a;
+                l.list = layerList_;
+                l.count = numLayer_;
+                l.rows = geo_.rows;
+                l.cols = geo_.pitch;
+                l.rowTab = layerTab_;
+                l.colTab = layerTab_ + (size_t)4 * geo_.rows;
+                launchStepLayer(K_, rxi_, l, stream_);
             }
             if (te) {
                 hipEventRecord(te[1], stream_);
@@ -1842,7 +1931,7 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     const bool smallWanted = opt_.smallGrid == 1 || (opt_.smallGrid == 0 && (long long)g_.NX * g_.NY <= 1536);
     const bool small = smallWanted && opt_.K == 0 && opt_.rxi == 0 && !opt_.timeKernels &&
                        opt_.useGraph != 1 && !opt_.streaming && smallGridFits(g_.NX, g_.NY) &&
-                       histTilesX_ == geo_.ntx && histTilesY_ == geo_.nty;
+                       histTilesX_ == geo_.ntx && histTilesY_ == geo_.nty && !layerActive();
     // reach-bounded (setReachArgs): the plain merged-launch path below; every other path leaves fields anywhere
     const bool reach = reachEligible(graph, small);
     if (reach) {
@@ -1928,7 +2017,7 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     // resident kernel: one launch per run.  Its blocks wait for each other, so they must all be on the chip at once: a run
     // takes its blocks out of the device's budget until sync(); when concurrent runs of other solvers have used the budget
     // up, this run goes out as the replayed graph instead (never a wait, never a deadlock)
-    bool resident = useResident_ && !(small && opt_.resident != 1);
+    bool resident = useResident_ && !(small && opt_.resident != 1) && !layerActive();
     releaseResident();  // (a run enqueued without a sync() behind the previous one: its reservation goes back first)
     if (resident) {
         const int budget = residentBudget_;
@@ -2134,6 +2223,7 @@ bool Solver::runBatch(Solver* const* s, int n, const float* lxyz, bool wait, std
             v.geo_.nty != lead.geo_.nty || v.g_.gx != lead.g_.gx || v.g_.gy != lead.g_.gy ||
             v.opt_.tileOrder != lead.opt_.tileOrder)
             return bad("batched solvers must share device, grid and tile configuration");
+        if (v.layerActive()) return bad("batched runs: not with edge layers (PvAmdSetEdgeLayer)");
         if (v.opt_.streaming || v.opt_.timeKernels > 0 || v.opt_.merged != 1 ||
             !v.opt_.packed || !batchConfigOk(v.K_, v.rxi_))
             return bad("batched runs need the default merged packed-math kernel of a batch configuration, without "

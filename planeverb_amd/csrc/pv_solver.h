@@ -132,6 +132,7 @@ public:
     const Geometry& geometry() const { return geo_; }
     int device() const { return device_; }
     int K() const { return K_; }
+    int rxi() const { return rxi_; }
     float efree() const { return efree_; }
     void setEfree(float e) { efree_ = e; }  // slab ranks: computed once for the whole grid
     int T() const { return T_; }
@@ -140,7 +141,7 @@ public:
     int histPitch() const { return histPitch_; }
     const std::string& lastError() const { return err_; }
     bool streamFuse() const { return streamFuse_; }
-    bool residentKernel() const { return useResident_; }  // runs of this solver go through pv_resident_kernel (when the
+    bool residentKernel() const { return useResident_ && !layerActive(); }  // runs of this solver go through pv_resident_kernel (when the
                                                           // device's resident-block budget allows: else the replayed graph)
     SolverOptions& options() { return opt_; }
 
@@ -170,6 +171,14 @@ public:
     bool setGridBoundary(const float R4[4]);
     void gridBoundary(float R4[4]) const;
     bool boundaryAbsorbing() const;  // every side has Y = 1 (the edge pass is not launched)
+
+    // Graded absorbing layers (pv_layer.h): widths in cells of sides x = 0, x = gx, y = 0, y = gy, 0..64, 0 = none.  A change
+    // takes effect at the next run of any form (tiles reclassified, a captured graph dropped).  Refused on sparse-emitter solvers,
+    // slabs, edge-tile solvers and tile configurations without a layer kernel.  A solver with a layer runs the tile path: merged
+    // launches + the layer launch; the resident, small-grid, segment, patch, row-band and two-kernel forms resolve off.
+    bool setEdgeLayer(const int w4[4]);
+    void edgeLayer(int w4[4]) const;
+    bool layerActive() const { return layerW_[0] > 0 || layerW_[1] > 0 || layerW_[2] > 0 || layerW_[3] > 0; }
 
     // carryFrom (live module, two iterations in flight on two solvers): the solver that ran the PREVIOUS iteration.  The cells
     // in which this run finds no onset take their occlusion / wet gain / decay time / lowpass / source direction from that
@@ -439,6 +448,14 @@ private:
     bool geometryDirty_ = true;
     float edgeR_[4] = {0.f, 0.f, 0.f, 0.f};  // setGridBoundary
     bool boundaryDirty_ = false;             // edgeR_ changed since the last applyGeometry (no flood fill: air is unchanged)
+    int layerW_[4] = {0, 0, 0, 0};  // setEdgeLayer
+    bool layerDirty_ = false;       // layerW_ changed since the last applyGeometry
+    float* layerTab_ = nullptr;     // LayerArgs::rowTab (4 x rows) then colTab (4 x pitch)
+    int* layerList_ = nullptr;      // the layer tiles (capacity: every tile)
+    int numLayer_ = 0;
+    std::vector<float> layerTabHost_;
+    std::vector<int> layerListHost_;
+    bool classifyLayer();           // applyGeometry: layer tiles off the air / general lists, onto layerList_; tables uploaded
     float efree_ = 0.f;
     DynParams dynCur_{};
     bool dynValid_ = false;
