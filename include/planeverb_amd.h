@@ -102,6 +102,9 @@ PVA_EXPORT void PlaneverbSetGridBoundary(float xMin, float xMax, float zMin, flo
  * (PvAmdSetEdgeLayer), queued like PlaneverbSetGridBoundary and applied to both live solvers at the same iteration boundary.
  * Refused (nothing changes; PvAmdLastError says why) in sparse-emitter mode and for widths PvAmdSetEdgeLayer refuses. */
 PVA_EXPORT void PlaneverbSetEdgeLayer(int xMin, int xMax, int zMin, int zMax);
+/* Extension: the same widths with the split-field model (PvAmdSetEdgeLayerSplit) at r0 = PVA_EDGE_LAYER_SPLIT_R0, queued and
+ * refused like PlaneverbSetEdgeLayer; PlaneverbSetEdgeLayer afterwards selects the unsplit model again. */
+PVA_EXPORT void PlaneverbSetEdgeLayerSplit(int xMin, int xMax, int zMin, int zMax);
 
 /* Extensions to the live module (not in the reference's flat ABI) */
 /* One sample of an impulse response as the reference stores it (Cell, PvTypes.h:106-121: 16 bytes) */
@@ -346,6 +349,30 @@ PVA_EXPORT int PvAmdGetGridBoundary(PvAmdSolver* s, float out4[4]);
  * widths into the material hash when some width is non-zero.  The .pv scene format does not hold the layer. */
 PVA_EXPORT int PvAmdSetEdgeLayer(PvAmdSolver* s, const int width4[4]);
 PVA_EXPORT int PvAmdGetEdgeLayer(PvAmdSolver* s, int out4[4]);
+/* Split-field (Berenger) edge layers: the same widths, tables and refusals as PvAmdSetEdgeLayer, with the design reflection r0
+ * of the tables given (PvAmdHostEdgeLayerTablesR0) and the pressure of a layer cell -- a cell with apx[x] != 1 or apy[y] != 1 --
+ * carried in two parts, each damped by its own axis only.  The unsplit layer damps the whole pressure (apx * apy), the part of
+ * its divergence that comes from the velocity along the layer included; a wave that meets it at an angle sees that mismatch
+ * and it reflects, the more the stronger the grading.  The split layer does not: on an open 160^2 grid at 275 Hz (width 24 on
+ * every side) it cuts the error energy outside the layers 43 dB below plain absorbing edges, against 11 dB for the unsplit
+ * layer (profiles/edge_layer.txt).  Layer cells are the cells of depth > 0 along either axis (so the ghost row's cells inside a
+ * y layer too, and the ghost column's inside an x layer).  A layer cell carries px, the x part of its pressure; the y part is
+ * pr - px.  Per
+ * step, strict IEEE float32 without contraction, dvx / dvy = the stencil's own velocity differences along x / y:
+ *   nx = beta * ((apx[x] * px) - bpx[x] * (C * dvx))      ny = beta * ((apy[y] * (pr - px)) - bpy[y] * (C * dvy))
+ *   pr' = nx + ny        px' = nx
+ * Every other cell: the reference's beta * (pr - C * div), px = 0.  The velocities, wall terms, beta blend, grid-edge rule,
+ * record-then-pulse order and the recording of pr only are the unsplit layer's; the pulse goes into pr only (a listener inside
+ * a layer puts it into the y part).  px is part of the fields: zero at the start of every run, after PvAmdSetFields and after
+ * every geometry, layer or model change, carried between PvAmdRunSteps calls, never exposed.  Refused (-1, nothing changes):
+ * whatever PvAmdSetEdgeLayer refuses, and r0 that is NaN or outside (0, 1).  PvAmdSetEdgeLayer afterwards selects the unsplit
+ * model again.  A width, model or r0 change takes effect at the next run.  Bakes of a solver with the split model and some
+ * non-zero width fold a model tag and r0 into the material hash after the widths.  Recommended r0: PVA_EDGE_LAYER_SPLIT_R0
+ * (a sweep over widths 8-24 on the grid above). */
+#define PVA_EDGE_LAYER_SPLIT_R0 1e-4
+PVA_EXPORT int PvAmdSetEdgeLayerSplit(PvAmdSolver* s, const int width4[4], double r0);
+/* the model of the solver's layers: *split = 1 for the split-field model (with its *r0), 0 for the unsplit one (*r0 = 0.1) */
+PVA_EXPORT int PvAmdGetEdgeLayerModel(PvAmdSolver* s, int* split, double* r0);
 /* CPU only: the layer tables of the grid (sizeX, sizeY, res) with widths width4, into out[4 (gx + 1) + 4 (gy + 1)] in this order:
  * apx[gx + 1], bpx[gx + 1], ax[gx + 1], bx[gx + 1], apy[gy + 1], bpy[gy + 1], ay[gy + 1], by[gy + 1] (index = cell row x for apx
  * / bpx, velocity face x -- between cells x - 1 and x -- for ax / bx; y likewise).  For a damping value s:
@@ -356,6 +383,10 @@ PVA_EXPORT int PvAmdGetEdgeLayer(PvAmdSolver* s, int out4[4]);
  * with m = 2) with R0 = 0.1 and C the grid's float32 Courant number taken to double.  Returns the number of floats written,
  * or -1 (a refused width, res < 275, NULL). */
 PVA_EXPORT int PvAmdHostEdgeLayerTables(float gridSizeX, float gridSizeY, int gridResolution, const int width4[4], float* out);
+/* CPU only: PvAmdHostEdgeLayerTables with the design reflection R0 = r0 (0 < r0 < 1, else -1) in s_max, computed in double;
+ * r0 = 0.1 gives PvAmdHostEdgeLayerTables' bits.  The tables of PvAmdSetEdgeLayerSplit. */
+PVA_EXPORT int PvAmdHostEdgeLayerTablesR0(float gridSizeX, float gridSizeY, int gridResolution, const int width4[4], double r0,
+                                          float* out);
 /* CPU only: the four vertices out8 the library uses for that oriented box (0, or -1 for a refused input) */
 PVA_EXPORT int PvAmdHostOrientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float* out8);
 /* CPU only: the shape the library makes of a vertex list (counter-clockwise, out16 gets 2n floats); returns n, or -1 for a

@@ -178,6 +178,10 @@ SYMBOLS = {
     "PvAmdSetEdgeLayer": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "PvAmdGetEdgeLayer": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "PlaneverbSetEdgeLayer": (None, [C.c_int] * 4),
+    "PvAmdSetEdgeLayerSplit": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_double]),
+    "PvAmdGetEdgeLayerModel": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "PlaneverbSetEdgeLayerSplit": (None, [C.c_int] * 4),
+    "PvAmdHostEdgeLayerTablesR0": (C.c_int, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_double, _fp]),
     "PvAmdHostEdgeLayerTables": (C.c_int, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), _fp]),
     "PvAmdHostOrientedBoxVertices": (C.c_int, [C.c_float] * 6 + [_fp]),
     "PvAmdHostShape": (C.c_int, [_fp, C.c_int, C.c_float, _fp]),
@@ -389,6 +393,12 @@ def SetEdgeLayer(xmin, xmax, zmin, zmax):
     lib().PlaneverbSetEdgeLayer(int(xmin), int(xmax), int(zmin), int(zmax))
 
 
+def SetEdgeLayerSplit(xmin, xmax, zmin, zmax):
+    """SetEdgeLayer with the split-field model at EDGE_LAYER_SPLIT_R0 (Solver.set_edge_layer_split); SetEdgeLayer afterwards
+    selects the unsplit model again"""
+    lib().PlaneverbSetEdgeLayerSplit(int(xmin), int(xmax), int(zmin), int(zmax))
+
+
 def SetListenerPosition(pos):
     lib().PlaneverbSetListenerPosition(*[float(v) for v in pos])
 
@@ -486,6 +496,7 @@ def host_shape_coverage(size_x, size_y, res, vertices):
 
 
 EDGE_LAYER_DEFAULT_WIDTH = 24  # cells: the width the edge-layer documentation and tests use (any 1..64 is accepted)
+EDGE_LAYER_SPLIT_R0 = 1e-4  # PVA_EDGE_LAYER_SPLIT_R0: the split-field model's recommended design reflection
 
 
 def _w4(w4):
@@ -495,13 +506,18 @@ def _w4(w4):
     return a
 
 
-def edge_layer_tables(size_x, size_y, res, w4):
+def edge_layer_tables(size_x, size_y, res, w4, r0=None):
     """the eight float32 damping tables of edge layers of widths w4 (PvAmdHostEdgeLayerTables, CPU only): a dict of apx, bpx,
-    ax, bx (gx + 1 each) and apy, bpy, ay, by (gy + 1 each)"""
+    ax, bx (gx + 1 each) and apy, bpy, ay, by (gy + 1 each).  r0: the design reflection (PvAmdHostEdgeLayerTablesR0, the
+    split model's tables); None = the unsplit model's tables"""
     i = host_grid_info(size_x, size_y, res)
     a = _w4(w4)
     out = np.empty(4 * (i.gx + 1) + 4 * (i.gy + 1), np.float32)
-    n = lib().PvAmdHostEdgeLayerTables(float(size_x), float(size_y), int(res), a.ctypes.data_as(C.POINTER(C.c_int)), _f(out))
+    wp = a.ctypes.data_as(C.POINTER(C.c_int))
+    if r0 is None:
+        n = lib().PvAmdHostEdgeLayerTables(float(size_x), float(size_y), int(res), wp, _f(out))
+    else:
+        n = lib().PvAmdHostEdgeLayerTablesR0(float(size_x), float(size_y), int(res), wp, float(r0), _f(out))
     if n < 0:
         raise PlaneverbError(last_error())
     nx, ny = i.gx + 1, i.gy + 1
@@ -981,6 +997,20 @@ class Solver:
         out = np.zeros(4, np.int32)
         _check(lib().PvAmdGetEdgeLayer(self._h, out.ctypes.data_as(C.POINTER(C.c_int))))
         return out
+
+    def set_edge_layer_split(self, w4, r0=EDGE_LAYER_SPLIT_R0):
+        """set_edge_layer with the split-field model (include/planeverb_amd.h PvAmdSetEdgeLayerSplit): each layer cell's
+        pressure is carried as an x and a y part, each damped by its own axis; r0 = the tables' design reflection, 0 < r0 < 1.
+        set_edge_layer afterwards selects the unsplit model again.  Takes effect at the next run."""
+        a = _w4(w4)
+        _check(lib().PvAmdSetEdgeLayerSplit(self._h, a.ctypes.data_as(C.POINTER(C.c_int)), float(r0)))
+        _check(lib().PvAmdGetInfo(self._h, self.info))  # (residentKernel: 0 while a layer is set)
+
+    def edge_layer_model(self):
+        """("split", r0) or ("unsplit", 0.1): the model of the solver's edge layers"""
+        sp, r0 = C.c_int(0), C.c_double(0.0)
+        _check(lib().PvAmdGetEdgeLayerModel(self._h, C.byref(sp), C.byref(r0)))
+        return ("split" if sp.value else "unsplit"), r0.value
 
     def run(self, listener):
         _check(lib().PvAmdRun(self._h, *[float(v) for v in listener]))

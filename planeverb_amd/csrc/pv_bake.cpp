@@ -46,6 +46,14 @@ bool materialOf(Solver* s, std::vector<uint8_t>* beta, unsigned long long* hash,
         int w[4];
         s->edgeLayer(w);
         *hash = fnv1a64(w, sizeof w, *hash);
+        bool split;
+        double r0;
+        s->edgeLayerModel(&split, &r0);
+        if (split) {  // then -- the split-field model only -- a model tag (int32 1) and its r0 (double)
+            const int tag = 1;
+            *hash = fnv1a64(&tag, sizeof tag, *hash);
+            *hash = fnv1a64(&r0, sizeof r0, *hash);
+        }
     }
     return true;
 }

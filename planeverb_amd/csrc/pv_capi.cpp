@@ -163,6 +163,17 @@ void PlaneverbSetEdgeLayer(int xMin, int xMax, int zMin, int zMax) try {
     if (!c->setEdgeLayer(w4, &err)) g_lastError = err;
 } PV_API_CATCH_VOID
 
+void PlaneverbSetEdgeLayerSplit(int xMin, int xMax, int zMin, int zMax) try {
+    const int w4[4] = {xMin, xMax, zMin, zMax};
+    Context::Ref c;
+    if (!c) {
+        g_lastError = "PlaneverbSetEdgeLayerSplit: the module is not initialised";
+        return;
+    }
+    std::string err;
+    if (!c->setEdgeLayer(w4, &err, true, kEdgeLayerSplitR0)) g_lastError = err;
+} PV_API_CATCH_VOID
+
 void PlaneverbExit(void) try {
     Context::exit();
 } PV_API_CATCH_VOID
@@ -729,19 +740,49 @@ int PvAmdSetGridBoundary(PvAmdSolver* h, const float* absorption4) try {
     return ret(h, h->g ? h->g->setGridBoundary(absorption4) : h->s->setGridBoundary(absorption4));
 } PV_API_CATCH(-1)
 
-int PvAmdSetEdgeLayer(PvAmdSolver* h, const int* width4) try {
+// PvAmdSetEdgeLayer (split = false) and PvAmdSetEdgeLayerSplit: the same refusals, plus r0 for the split model
+static int setEdgeLayerModel(PvAmdSolver* h, const int* width4, bool split, double r0, const char* name) {
     if (!width4) {
-        g_lastError = "PvAmdSetEdgeLayer: null width array";
+        g_lastError = std::string(name) + ": null width array";
+        return -1;
+    }
+    if (split && !edgeLayerR0Ok(r0)) {
+        g_lastError = std::string(name) + ": r0 must lie strictly between 0 and 1";
         return -1;
     }
     const bool any = width4[0] != 0 || width4[1] != 0 || width4[2] != 0 || width4[3] != 0;
     if (h && any && (h->opt.slabCount > 1 || !h->slabDevices.empty())) {
-        g_lastError = "PvAmdSetEdgeLayer: edge layers are not available on slab groups or slab ranks";
+        g_lastError = std::string(name) + ": edge layers are not available on slab groups or slab ranks";
         return -1;
     }
     if (h && !h->slabDevices.empty()) return 0;  // (all widths 0 on a slab group: nothing to change)
     if (!ensure(h)) return -1;
-    return ret(h, h->s->setEdgeLayer(width4));
+    return ret(h, h->s->setEdgeLayer(width4, split, split ? r0 : kEdgeLayerR0));
+}
+
+int PvAmdSetEdgeLayer(PvAmdSolver* h, const int* width4) try {
+    return setEdgeLayerModel(h, width4, false, kEdgeLayerR0, "PvAmdSetEdgeLayer");
+} PV_API_CATCH(-1)
+
+int PvAmdSetEdgeLayerSplit(PvAmdSolver* h, const int* width4, double r0) try {
+    return setEdgeLayerModel(h, width4, true, r0, "PvAmdSetEdgeLayerSplit");
+} PV_API_CATCH(-1)
+
+int PvAmdGetEdgeLayerModel(PvAmdSolver* h, int* split, double* r0) try {
+    if (!split || !r0) {
+        g_lastError = "PvAmdGetEdgeLayerModel: null output";
+        return -1;
+    }
+    if (h && !h->slabDevices.empty()) {  // (slab groups hold no layer)
+        *split = 0;
+        *r0 = kEdgeLayerR0;
+        return 0;
+    }
+    if (!ensure(h)) return -1;
+    bool sp;
+    h->s->edgeLayerModel(&sp, r0);
+    *split = sp ? 1 : 0;
+    return 0;
 } PV_API_CATCH(-1)
 
 int PvAmdGetEdgeLayer(PvAmdSolver* h, int* out4) try {
@@ -1113,23 +1154,35 @@ int PvAmdHostShapeCoverage(float sx, float sy, int res, const float* xy, int n, 
     return 0;
 } PV_API_CATCH(-1)
 
-int PvAmdHostEdgeLayerTables(float sx, float sy, int res, const int* width4, float* out) try {
+static int hostEdgeLayerTables(float sx, float sy, int res, const int* width4, double r0, float* out, const char* name) {
     if (res < kLowResolution || !width4 || !out) {
-        g_lastError = "PvAmdHostEdgeLayerTables: resolution below 275 or a null array";
+        g_lastError = std::string(name) + ": resolution below 275 or a null array";
+        return -1;
+    }
+    if (!edgeLayerR0Ok(r0)) {
+        g_lastError = std::string(name) + ": r0 must lie strictly between 0 and 1";
         return -1;
     }
     const GridSpec g = makeGridSpec(sx, sy, res);
     if (g.gx < 1 || g.gy < 1) {
-        g_lastError = "PvAmdHostEdgeLayerTables: grid has no cells";
+        g_lastError = std::string(name) + ": grid has no cells";
         return -1;
     }
     const char* why = edgeLayerRefusal(g.gx, g.gy, width4);
     if (*why) {
-        g_lastError = std::string("PvAmdHostEdgeLayerTables: ") + why;
+        g_lastError = std::string(name) + ": " + why;
         return -1;
     }
-    edgeLayerTables(g.gx, g.gy, g.courant, width4, out);
+    edgeLayerTables(g.gx, g.gy, g.courant, width4, out, r0);
     return 4 * (g.NX + g.NY);
+}
+
+int PvAmdHostEdgeLayerTables(float sx, float sy, int res, const int* width4, float* out) try {
+    return hostEdgeLayerTables(sx, sy, res, width4, kEdgeLayerR0, out, "PvAmdHostEdgeLayerTables");
+} PV_API_CATCH(-1)
+
+int PvAmdHostEdgeLayerTablesR0(float sx, float sy, int res, const int* width4, double r0, float* out) try {
+    return hostEdgeLayerTables(sx, sy, res, width4, r0, out, "PvAmdHostEdgeLayerTablesR0");
 } PV_API_CATCH(-1)
 
 int PvAmdHostLoadPv(const char* path, float* b5, int maxBoxes) try {

@@ -670,20 +670,21 @@ void Context::setGridBoundary(const float R4[4]) {
     changes_.push_back(c);
 }
 
-bool Context::setEdgeLayer(const int w4[4], std::string* err) {
+bool Context::setEdgeLayer(const int w4[4], std::string* err, bool split, double r0) {
 #ifndef PVA_HOST_TEST
+    const std::string nm = split ? "PlaneverbSetEdgeLayerSplit: " : "PlaneverbSetEdgeLayer: ";
     if (streaming_) {
-        *err = "PlaneverbSetEdgeLayer: edge layers are not available in sparse-emitter mode";
+        *err = nm + "edge layers are not available in sparse-emitter mode";
         return false;
     }
     const GridSpec& g = spec();
     const char* why = edgeLayerRefusal(g.gx, g.gy, w4);
     if (*why) {
-        *err = std::string("PlaneverbSetEdgeLayer: ") + why;
+        *err = nm + why;
         return false;
     }
     if ((w4[0] || w4[1] || w4[2] || w4[3]) && !layerConfigOk(solver_->K(), solver_->rxi())) {
-        *err = "PlaneverbSetEdgeLayer: no layer kernel for this grid's tile configuration";
+        *err = nm + "no layer kernel for this grid's tile configuration";
         return false;
     }
 #endif
@@ -692,6 +693,8 @@ bool Context::setEdgeLayer(const int w4[4], std::string* err) {
     Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
     c.layer = true;
     for (int k = 0; k < 4; ++k) c.W4[k] = w4[k];
+    c.split = split;
+    c.r0 = split ? r0 : kEdgeLayerR0;
     changes_.push_back(c);
     return true;
 }
@@ -699,7 +702,7 @@ bool Context::setEdgeLayer(const int w4[4], std::string* err) {
 void Context::applyChange(Solver* s, const Change& c) {
     if (c.layer) {
 #ifndef PVA_HOST_TEST
-        s->setEdgeLayer(c.W4);  // (validated by setEdgeLayer: the widths fit the grid and the configuration)
+        s->setEdgeLayer(c.W4, c.split, c.r0);  // (validated by setEdgeLayer: the widths fit the grid and the configuration)
 #endif
         return;
     }

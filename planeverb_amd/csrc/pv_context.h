@@ -95,7 +95,8 @@ public:
     void setGridBoundary(const float R4[4]);
     // edge layers (Solver::setEdgeLayer): refused in sparse-emitter mode and for widths the grid cannot hold (false + *err);
     // else queued with the geometry changes and applied to every solver at the same iteration boundary
-    bool setEdgeLayer(const int w4[4], std::string* err);
+    // (split, r0: the model, Solver::setEdgeLayer)
+    bool setEdgeLayer(const int w4[4], std::string* err, bool split = false, double r0 = kEdgeLayerR0);
 
     void setListener(float x, float y, float z);  // PvContext.cpp:50-56
     // Planeverb::GetImpulseResponse (FDTD.cpp:60-70): the IR of the last COMPLETED iteration at a world position as
@@ -186,6 +187,8 @@ private:
         float R4[4] = {0.f, 0.f, 0.f, 0.f};
         bool layer = false;  // an edge-layer change: W4 replaces the four widths
         int W4[4] = {0, 0, 0, 0};
+        bool split = false;  // ... and the model
+        double r0 = kEdgeLayerR0;
     };
     static void applyChange(Solver* s, const Change& c);
     std::vector<Box> geometry_;

@@ -423,10 +423,10 @@ const char* edgeLayerRefusal(int gx, int gy, const int w4[4]) {
 }
 
 // one axis of n = g cells (+ the ghost): cell and face tables for layers of widths wlo (index 0 side) and whi (index g side)
-static void axisTables(int g, int wlo, int whi, double C, float* ap, float* bp, float* a, float* b) {
+static void axisTables(int g, int wlo, int whi, double C, double r0, float* ap, float* bp, float* a, float* b) {
     auto sOf = [&](double depth, int w) {
         if (w <= 0 || depth <= 0.0) return 0.0;
-        const double smax = 3.0 * C * std::log(1.0 / kEdgeLayerR0) / (4.0 * w);
+        const double smax = 3.0 * C * std::log(1.0 / r0) / (4.0 * w);
         const double u = depth / w;
         return smax * (u * u);
     };
@@ -445,12 +445,12 @@ static void axisTables(int g, int wlo, int whi, double C, float* ap, float* bp, 
     }
 }
 
-void edgeLayerTables(int gx, int gy, float courant, const int w4[4], float* out) {
+void edgeLayerTables(int gx, int gy, float courant, const int w4[4], float* out, double r0) {
     const int nx = gx + 1, ny = gy + 1;
     float* o = out;
-    axisTables(gx, w4[0], w4[1], (double)courant, o, o + nx, o + 2 * nx, o + 3 * nx);
+    axisTables(gx, w4[0], w4[1], (double)courant, r0, o, o + nx, o + 2 * nx, o + 3 * nx);
     o += 4 * nx;
-    axisTables(gy, w4[2], w4[3], (double)courant, o, o + ny, o + 2 * ny, o + 3 * ny);
+    axisTables(gy, w4[2], w4[3], (double)courant, r0, o, o + ny, o + 2 * ny, o + 3 * ny);
 }
 
 }  // namespace pva

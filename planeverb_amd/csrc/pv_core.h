@@ -110,6 +110,8 @@ constexpr int kEdgeLayerMinInterior = 8;  // cells between two opposite layers (
 constexpr int kEdgeLayerDefaultWidth = 24;
 // the grading rule's design reflection: s_max = (m + 1) * C * ln(1 / R0) / (4 w), m = 2 (tuned by tests/test_host_layer.py)
 constexpr double kEdgeLayerR0 = 0.1;
+// the split-field model's default design reflection (PVA_EDGE_LAYER_SPLIT_R0; the sweep: profiles/edge_layer.txt)
+constexpr double kEdgeLayerSplitR0 = 1e-4;
 
 // The tables of a gx x gy grid (cell array (gx + 1) x (gy + 1)), into out[4 (gx + 1) + 4 (gy + 1)] in this order:
 //   apx[gx + 1], bpx[gx + 1], ax[gx + 1], bx[gx + 1], apy[gy + 1], bpy[gy + 1], ay[gy + 1], by[gy + 1]
@@ -117,8 +119,11 @@ constexpr double kEdgeLayerR0 = 0.1;
 // velocity faces at whole depths: along x with a layer of width w on side 0, face x (between cells x - 1 and x) has depth
 // w - x for x <= w and cell x has depth w - x - 1/2 for x < w; on side 1, face x has depth x - (gx - w) for x >= gx - w and
 // cell x depth x + 1/2 - (gx - w) for gx - w <= x < gx.  s = s_max (depth / w)^2, 0 outside the layers (depth <= 0, the
-// ghost cell x = gx included); y likewise with sides 2 and 3.  courant = the grid's Courant number (GridSpec::courant).
-void edgeLayerTables(int gx, int gy, float courant, const int w4[4], float* out);
+// ghost cell x = gx included); y likewise with sides 2 and 3.  courant = the grid's Courant number (GridSpec::courant); r0 =
+// the design reflection R0 in s_max (kEdgeLayerR0 for the unsplit model, 0 < r0 < 1).
+void edgeLayerTables(int gx, int gy, float courant, const int w4[4], float* out, double r0 = kEdgeLayerR0);
+// is r0 a design reflection the split model accepts (finite, 0 < r0 < 1)?
+inline bool edgeLayerR0Ok(double r0) { return r0 > 0.0 && r0 < 1.0; }
 // why w4 is refused for a gx x gy grid ("" = accepted)
 const char* edgeLayerRefusal(int gx, int gy, const int w4[4]);
 

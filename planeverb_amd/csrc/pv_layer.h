@@ -6,6 +6,10 @@
 //   pressure: pr' = beta * ((apx[x] * apy[y]) * pr - (bpx[x] * bpy[y]) * (C * div))
 //   vx, air : ax[x] * vx - bx[x] * (C * (pr[x, y] - pr[x - 1, y]))      vy, air : ay[y] * vy - by[y] * (C * (pr[x, y] - pr[x, y - 1]))
 // Every factor is exactly 1 outside the layers, where the expressions give the reference's bits.
+// The split-field model (Solver::setEdgeLayer(..., split = true, r0)) changes the pressure of the layer cells only (apx[x] != 1
+// or apy[y] != 1): such a cell carries px, the x part of its pressure (the y part is pr - px), in a plane of its own, and
+//   nx = beta * ((apx * px) - bpx * (C * dvx))    ny = beta * ((apy * (pr - px)) - bpy * (C * dvy))    pr' = nx + ny, px' = nx
+// every other cell: beta * (pr - C * div), px = 0.  The velocities are the unsplit model's.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,6 +29,10 @@ struct LayerArgs {
     int rows, cols;      // pitches of the two tables (Geometry::rows, Geometry::pitch)
     const float* rowTab;  // apx, bpx, ax, bx
     const float* colTab;  // apy, bpy, ay, by
+    // the split-field model (Solver::setEdgeLayerSplit): the x part of the pressure of the layer cells, a padded plane per
+    // buffer set (read set n, write set n + 1; 0 in every other cell).  pxOut == NULL: the unsplit model
+    const float* pxIn;
+    float* pxOut;
 };
 
 // is there a layer kernel for this (K, rows) configuration (the product library's tiles)?

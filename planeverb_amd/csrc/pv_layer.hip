@@ -2,7 +2,8 @@
 //
 // The layer tiles are advanced by a launch of their own beside each merged launch (Solver::enqueueSteps).  Its tile body is the
 // two-kernel form's scalar general tile (pv_kernels.hip stepTile<..., GENERAL = true>, leapfrogStepCoef) restated with the
-// damping behind a compile-time flag; pv_kernels.hip itself is untouched, so the merged kernel compiles to what it did.
+// damping behind a compile-time flag (and the split-field pressure behind a second one); pv_kernels.hip itself is untouched, so
+// the merged kernel compiles to what it did.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -19,19 +20,33 @@ namespace pva {
 
 // leapfrogStepCoef with the damping (DAMP) or without it (the general tile's expressions, unchanged).  Per-row factors are
 // wave-uniform (rf: apx, bpx, ax, bx of the row), per-column ones (apy, bpy, ay, by) one value per lane.
-template <int ROWS, bool DAMP>
-__device__ __forceinline__ void leapfrogStepLayer(float (&pr)[ROWS], float (&vx)[ROWS], float (&vy)[ROWS],
+// SPLIT (the split-field model, DAMP too): a layer cell (apx != 1 or apy != 1) carries px, the x part of its pressure (the y
+// part is pr - px), and damps each part by its own axis only; every other cell takes the general tile's expression, px = 0:
+//   nx = beta * ((apx * px) - bpx * (C * dvx))    ny = beta * ((apy * (pr - px)) - bpy * (C * dvy))    pr' = nx + ny, px' = nx
+template <int ROWS, bool DAMP, bool SPLIT>
+__device__ __forceinline__ void leapfrogStepLayer(float (&pr)[ROWS], float (&px)[ROWS], float (&vx)[ROWS], float (&vy)[ROWS],
                                                   const float (&kx)[ROWS], const float (&ky)[ROWS], const float (&bt)[ROWS],
                                                   const float* __restrict__ rf, const int rpitch, const float apy,
                                                   const float bpy, const float ay, const float by, const float C) {
+    static_assert(DAMP || !SPLIT, "the split form is a damped form");
+    const bool colLayer = apy != 1.f;  // (per lane)
 #pragma unroll
     for (int r = 0; r < ROWS - 1; ++r) {
         const float vyR = laneNext(vy[r]);
-        const float div = (vx[r + 1] - vx[r]) + (vyR - vy[r]);
-        if constexpr (DAMP)
-            pr[r] = bt[r] * ((rf[r] * apy) * pr[r] - (rf[rpitch + r] * bpy) * (C * div));
-        else
-            pr[r] = bt[r] * (pr[r] - C * div);
+        const float dvx = vx[r + 1] - vx[r], dvy = vyR - vy[r];
+        if constexpr (SPLIT) {
+            const float apx = rf[r];  // (wave-uniform: the row flag)
+            const bool layer = apx != 1.f || colLayer;
+            const float nx = bt[r] * ((apx * px[r]) - rf[rpitch + r] * (C * dvx));
+            const float ny = bt[r] * ((apy * (pr[r] - px[r])) - bpy * (C * dvy));
+            const float plain = bt[r] * (pr[r] - C * (dvx + dvy));
+            pr[r] = layer ? nx + ny : plain;
+            px[r] = layer ? nx : 0.f;
+        } else if constexpr (DAMP) {
+            pr[r] = bt[r] * ((rf[r] * apy) * pr[r] - (rf[rpitch + r] * bpy) * (C * (dvx + dvy)));
+        } else {
+            pr[r] = bt[r] * (pr[r] - C * (dvx + dvy));
+        }
     }
 #pragma unroll
     for (int r = ROWS - 1; r >= 1; --r) {
@@ -59,8 +74,8 @@ __device__ __forceinline__ void leapfrogStepLayer(float (&pr)[ROWS], float (&vx)
 }
 
 // a general tile's `part`-th slice of SUB interior rows (+ K halo rows either side): walls, the listener's pulse, history
-// recording, tileFirst and nzOut exactly as stepTile<K, RXI, SUB, true> does them
-template <int K, int RXI, int SUB, bool DAMP>
+// recording, tileFirst and nzOut exactly as stepTile<K, RXI, SUB, true> does them; SPLIT: px from l.pxIn, to l.pxOut
+template <int K, int RXI, int SUB, bool DAMP, bool SPLIT>
 __device__ __forceinline__ void stepLayerTile(const LayerArgs& l, const int tile, const int part, const int lane) {
     const StepArgs& a = l.a;
     constexpr int ROWS = SUB + 2 * K;
@@ -78,11 +93,13 @@ __device__ __forceinline__ void stepLayerTile(const LayerArgs& l, const int tile
     const rsrc_t rCoef = makeRsrc(a.coef, a.planeBytes * 3);
     typedef unsigned int u3v __attribute__((ext_vector_type(3)));
 
-    float pr[ROWS], vx[ROWS], vy[ROWS], kx[ROWS], ky[ROWS], bt[ROWS];
+    float pr[ROWS], px[ROWS], vx[ROWS], vy[ROWS], kx[ROWS], ky[ROWS], bt[ROWS];
+    const rsrc_t rPxIn = makeRsrc(l.pxIn, SPLIT ? a.inBytes : 0);  // (a run's first launch: zero extent, as the fields)
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
         const int so = soff0 + r * pitchB;
         pr[r] = bufLoadF(rPrIn, voff, so);
+        px[r] = SPLIT ? bufLoadF(rPxIn, voff, so) : 0.f;
         vx[r] = bufLoadF(rVxIn, voff, so);
         vy[r] = bufLoadF(rVyIn, voff, so);
         const u3v c = __builtin_amdgcn_raw_buffer_load_b96(rCoef, lane * 12, 3 * so, 0);
@@ -124,7 +141,7 @@ __device__ __forceinline__ void stepLayerTile(const LayerArgs& l, const int tile
 
 #pragma unroll 1
     for (int s = 0; s < a.nsteps; ++s) {
-        leapfrogStepLayer<ROWS, DAMP>(pr, vx, vy, kx, ky, bt, rf, l.rows, apy, bpy, ay, by, C);
+        leapfrogStepLayer<ROWS, DAMP, SPLIT>(pr, px, vx, vy, kx, ky, bt, rf, l.rows, apy, bpy, ay, by, C);
         if (rec) {  // the pressure of this step before the pulse (FDTD.cpp:226-234)
             const rsrc_t rH = makeRsrc(hplane, a.histPlane * 4);
             if (inCols) {
@@ -152,11 +169,16 @@ __device__ __forceinline__ void stepLayerTile(const LayerArgs& l, const int tile
             bufStoreF(vx[r], rVxOut, voff, so);
             bufStoreF(vy[r], rVyOut, voff, so);
         }
+        if constexpr (SPLIT) {
+            const rsrc_t rPxOut = makeRsrc(l.pxOut, a.planeBytes);
+#pragma unroll
+            for (int r = K; r < ROWS - K; ++r) bufStoreF(px[r], rPxOut, voff, soff0 + r * pitchB);
+        }
     }
 }
 
 // one wave per SUB-row slice of a layer tile, RXI / SUB slices per tile, four waves per block
-template <int K, int RXI, int SUB>
+template <int K, int RXI, int SUB, bool SPLIT>
 __global__ __launch_bounds__(256) void pv_step_layer_kernel(const LayerArgs l) {
     constexpr int S = RXI / SUB;
     static_assert(S * SUB == RXI, "layer-tile split must divide the tile");
@@ -173,7 +195,7 @@ __global__ __launch_bounds__(256) void pv_step_layer_kernel(const LayerArgs l) {
     }
     // reach-bounded launch: a tile the fields cannot have reached stays zero, as in the merged launch's arms
     if (a.winTis > 0 && !tileInReach(ti, tj, RXI, 64 - 2 * K, a.G, a.reachGrow, a.reachRow, a.reachCol, a.reach)) return;
-    stepLayerTile<K, RXI, SUB, true>(l, tile, idx % S, lane);
+    stepLayerTile<K, RXI, SUB, true, SPLIT>(l, tile, idx % S, lane);
 }
 
 // (K steps per launch, interior rows per tile, rows per slice): the product library's tiles (pv_kernels.hip
@@ -188,16 +210,23 @@ bool layerConfigOk(int K, int rxi) {
     return false;
 }
 
-template <int K, int RXI, int SUB>
+template <int K, int RXI, int SUB, bool SPLIT>
 static void launchStepLayerT(const LayerArgs& l, hipStream_t stream) {
     const int blocks = (l.count * (RXI / SUB) + 3) / 4;
-    hipLaunchKernelGGL((pv_step_layer_kernel<K, RXI, SUB>), dim3(blocks), dim3(256), 0, stream, l);
+    hipLaunchKernelGGL((pv_step_layer_kernel<K, RXI, SUB, SPLIT>), dim3(blocks), dim3(256), 0, stream, l);
 }
 
 void launchStepLayer(int K, int rxi, const LayerArgs& l, hipStream_t stream) {
     if (l.count <= 0) return;
+    if (l.pxOut) {  // (the split form fits the same slices: no scratch, profiles/edge_layer.txt)
 #define X(k, r, sub) \
-    if (K == k && rxi == r) return launchStepLayerT<k, r, sub>(l, stream);
+    if (K == k && rxi == r) return launchStepLayerT<k, r, sub, true>(l, stream);
+        PV_LAYER_CONFIGS(X)
+#undef X
+        return;
+    }
+#define X(k, r, sub) \
+    if (K == k && rxi == r) return launchStepLayerT<k, r, sub, false>(l, stream);
     PV_LAYER_CONFIGS(X)
 #undef X
 }

@@ -638,6 +638,7 @@ Solver::~Solver() {
     if (resFlags_) hipFree(resFlags_);
     if (layerList_) hipFree(layerList_);
     if (layerTab_) hipFree(layerTab_);
+    if (px_[0]) hipFree(px_[0]);  // (px_[1] lives in the same allocation)
     if (emCells_) hipFree(emCells_);
     if (emTrace_) hipFree(emTrace_);
     void* ptrs[] = {coef_,      matDev_, pulseDev_, hist_,  tileFirst_, tileClass_, generalList_,
@@ -965,7 +966,7 @@ bool Solver::boundaryAbsorbing() const {
     return true;
 }
 
-bool Solver::setEdgeLayer(const int w4[4]) {
+bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (opt_.streaming) return fail("edge layers: not on a sparse-emitter (streaming-analysis) solver");
     if (isSlab()) return fail("edge layers: not on slabs");
     if (opt_.edgeTiles) return fail("edge layers: not with edge tiles (PVA_OPT_EDGE_TILES)");
@@ -974,10 +975,15 @@ bool Solver::setEdgeLayer(const int w4[4]) {
         return fail("edge layers: no layer kernel for this tile configuration");
     const char* why = edgeLayerRefusal(g_.gx, g_.gy, w4);
     if (*why) return fail(why);
+    if (!split) r0 = kEdgeLayerR0;
+    if (!edgeLayerR0Ok(r0)) return fail("edge layers: the split model's r0 must lie strictly between 0 and 1");
     for (int k = 0; k < 4; ++k) {
         if (layerW_[k] != w4[k]) layerDirty_ = true;
         layerW_[k] = w4[k];
     }
+    if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
+    layerSplit_ = split;
+    layerR0_ = r0;
     return true;
 }
 
@@ -994,6 +1000,14 @@ bool Solver::classifyLayer() {
     const int ntiles = geo_.ntx * geo_.nty, rows = geo_.rows, pitch = geo_.pitch, G = geo_.G;
     if (!layerList_ && !dalloc(&layerList_, (size_t)ntiles, false)) return false;
     if (!layerTab_ && !dalloc(&layerTab_, (size_t)4 * (rows + pitch), false)) return false;
+    if (layerSplit_) {  // (zero wherever the six field planes are: here after every geometry, layer or model change)
+        const size_t plane = (size_t)rows * pitch;
+        if (!px_[0]) {
+            if (!dalloc(&px_[0], 2 * plane, false)) return false;
+            px_[1] = px_[0] + plane;
+        }
+        if (!hipOk(hipMemsetAsync(px_[0], 0, 2 * plane * 4, stream_), "split plane clear")) return false;
+    }
     const int ROWS = rxi_ + 2 * K_;
     const int xlo = layerW_[0], xhi = g_.gx - layerW_[1], ylo = layerW_[2], yhi = g_.gy - layerW_[3];
     std::vector<int> list;
@@ -1016,7 +1030,7 @@ bool Solver::classifyLayer() {
         if (!isLayer[(size_t)t]) walls.push_back(t);
     wallTiles_.swap(walls);
     std::vector<float> t((size_t)4 * (g_.NX + g_.NY));
-    edgeLayerTables(g_.gx, g_.gy, g_.courant, layerW_, t.data());
+    edgeLayerTables(g_.gx, g_.gy, g_.courant, layerW_, t.data(), layerR0_);
     layerTabHost_.assign((size_t)4 * (rows + pitch), 1.f);
     for (int k = 0; k < 4; ++k) {
         for (int x = 0; x < g_.NX; ++x) layerTabHost_[(size_t)k * rows + G + x] = t[(size_t)k * g_.NX + x];
@@ -1339,7 +1353,8 @@ bool Solver::zeroPlanesIfNeeded() {
     for (int i = 0; i < 2; ++i)
         if (!hipOk(hipMemsetAsync(pr_[i], 0, bytes, stream_), "plane clear") ||
             !hipOk(hipMemsetAsync(vx_[i], 0, bytes, stream_), "plane clear") ||
-            !hipOk(hipMemsetAsync(vy_[i], 0, bytes, stream_), "plane clear"))
+            !hipOk(hipMemsetAsync(vy_[i], 0, bytes, stream_), "plane clear") ||
+            (px_[i] && !hipOk(hipMemsetAsync(px_[i], 0, bytes, stream_), "plane clear")))
             return false;
     planesDirty_ = false;
     return true;
@@ -1487,6 +1502,8 @@ bool Solver::clearReachPlanes() {
     float* planes[6] = {pr_[0], vx_[0], vy_[0], pr_[1], vx_[1], vy_[1]};
     if (planesDirty_ || sweptDirty_) {
         for (float* p : planes) launchZero(p, (long long)geo_.rows * geo_.pitch, stream_);
+        for (float* p : px_)
+            if (p) launchZero(p, (long long)geo_.rows * geo_.pitch, stream_);
         planesDirty_ = false;
         sweptDirty_ = false;
     } else if (reachRect_[1] > 0 && reachRect_[3] > 0) {
@@ -1498,6 +1515,10 @@ bool Solver::clearReachPlanes() {
         z.c0 = reachRect_[2] * wi_;
         z.nc = std::min(geo_.pitch, 2 * geo_.G + (reachRect_[2] + reachRect_[3]) * wi_) - z.c0;
         launchZeroRect(z, stream_);
+        if (px_[0]) {  // (the split planes: the same rectangle, each plane named three times)
+            for (int i = 0; i < 6; ++i) z.p[i] = px_[i & 1];
+            launchZeroRect(z, stream_);
+        }
     }
     for (int& v : reachRect_) v = 0;
     return hipOk(hipGetLastError(), "plane clear");
@@ -1664,6 +1685,11 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
                 l.cols = geo_.pitch;
                 l.rowTab = layerTab_;
                 l.colTab = layerTab_ + (size_t)4 * geo_.rows;
+                if (layerSplit_) {
+                    if (!px_[0]) return fail("split edge layer: no split planes (applyGeometry did not run)");
+                    l.pxIn = px_[cur_];
+                    l.pxOut = px_[cur_ ^ 1];
+                }
                 launchStepLayer(K_, rxi_, l, stream_);
             }
             if (te) {
@@ -2710,6 +2736,8 @@ bool Solver::setFields(const float* pr, const float* vx, const float* vy) {
     const float* src[3] = {pr, vx, vy};
     float* dst[3] = {pr_[cur_], vx_[cur_], vy_[cur_]};
     const size_t planeBytes = (size_t)geo_.rows * geo_.pitch * 4;
+    for (float* p : px_)  // (the split model's x part: zero, as after every field change)
+        if (p && !hipOk(hipMemsetAsync(p, 0, planeBytes, stream_), "field clear")) return false;
     for (int i = 0; i < 3; ++i) {
         if (!hipOk(hipMemsetAsync(dst[i], 0, planeBytes, stream_), "field clear")) return false;
         if (!src[i]) continue;

@@ -176,8 +176,14 @@ public:
     // takes effect at the next run of any form (tiles reclassified, a captured graph dropped).  Refused on sparse-emitter solvers,
     // slabs, edge-tile solvers and tile configurations without a layer kernel.  A solver with a layer runs the tile path: merged
     // launches + the layer launch; the resident, small-grid, segment, patch, row-band and two-kernel forms resolve off.
-    bool setEdgeLayer(const int w4[4]);
+    // split = the split-field model (pv_layer.h) with design reflection r0 (0 < r0 < 1, else refused); split = false: the
+    // unsplit model, R0 = kEdgeLayerR0.  A width, model or R0 change reclassifies and drops a captured graph alike.
+    bool setEdgeLayer(const int w4[4], bool split = false, double r0 = kEdgeLayerR0);
     void edgeLayer(int w4[4]) const;
+    void edgeLayerModel(bool* split, double* r0) const {
+        *split = layerSplit_;
+        *r0 = layerR0_;
+    }
     bool layerActive() const { return layerW_[0] > 0 || layerW_[1] > 0 || layerW_[2] > 0 || layerW_[3] > 0; }
 
     // carryFrom (live module, two iterations in flight on two solvers): the solver that ran the PREVIOUS iteration.  The cells
@@ -449,7 +455,11 @@ private:
     float edgeR_[4] = {0.f, 0.f, 0.f, 0.f};  // setGridBoundary
     bool boundaryDirty_ = false;             // edgeR_ changed since the last applyGeometry (no flood fill: air is unchanged)
     int layerW_[4] = {0, 0, 0, 0};  // setEdgeLayer
-    bool layerDirty_ = false;       // layerW_ changed since the last applyGeometry
+    bool layerSplit_ = false;       // the split-field model (else unsplit)
+    double layerR0_ = kEdgeLayerR0;  // the tables' design reflection
+    bool layerDirty_ = false;       // layerW_, layerSplit_ or layerR0_ changed since the last applyGeometry
+    float* px_[2] = {nullptr, nullptr};  // the split model's x part of the pressure, one padded plane per buffer set (one
+                                         // allocation, made by the first applyGeometry with the split model; 0 outside layers)
     float* layerTab_ = nullptr;     // LayerArgs::rowTab (4 x rows) then colTab (4 x pitch)
     int* layerList_ = nullptr;      // the layer tiles (capacity: every tile)
     int numLayer_ = 0;

@@ -1,8 +1,9 @@
 """GPU: first measurements of graded edge layers (profiles/edge_layer.txt).
 
-Whole-run time (host wall clock around PvAmdRun, which waits for the run) and PvAmdTimings.fdtdMs of an open grid without and
-with layers of the default width (api.EDGE_LAYER_DEFAULT_WIDTH on every side) at 127^2, 254^2, 1024^2 and 4096^2 (275 Hz), the
-listener at the centre.  The two solvers of a size alternate run by run; medians of N runs.  The layer launch's share of a sweep
+Whole-run time (host wall clock around PvAmdRun, which waits for the run) and PvAmdTimings.fdtdMs of an open grid without
+layers, with unsplit layers and with split-field layers (default R0) of the default width (api.EDGE_LAYER_DEFAULT_WIDTH on every
+side) at 127^2, 254^2, 1024^2 and 4096^2 (275 Hz), the listener at the centre.  The three solvers of a size alternate run by
+run; medians of N runs.  The layer launch's share of a sweep
 is in a kernel trace of this script: rocprofv3 --kernel-trace --stats -- python tools/gpu_layer_measure.py ...
 
     python tools/gpu_layer_measure.py [runs] [out.json]
@@ -26,12 +27,15 @@ def measure(n, runs):
     L = ((n // 2 + 0.5) * float(DX), 0.0, (n // 2 + 0.5) * float(DX))
     w = api.EDGE_LAYER_DEFAULT_WIDTH
     pair = []
-    for w4 in ((0, 0, 0, 0), (w, w, w, w)):
+    for w4, split in (((0, 0, 0, 0), False), ((w, w, w, w), False), ((w, w, w, w), True)):
         s = api.Solver(size, size, 275)
-        s.set_edge_layer(w4)
+        if split:
+            s.set_edge_layer_split(w4)
+        else:
+            s.set_edge_layer(w4)
         s.run(L)  # warm-up: classification, graph capture
         pair.append(s)
-    ms, fdtd = [[], []], [[], []]
+    ms, fdtd = [[], [], []], [[], [], []]
     for _ in range(runs):
         for k, s in enumerate(pair):
             t0 = time.perf_counter()
@@ -39,7 +43,7 @@ def measure(n, runs):
             ms[k].append((time.perf_counter() - t0) * 1e3)
             fdtd[k].append(s.timings().fdtdMs)
     out = dict(grid=n, layer_width=w)
-    for k, tag in enumerate(("no_layer", "layer")):
+    for k, tag in enumerate(("no_layer", "layer", "split_layer")):
         out[tag] = dict(resident=int(pair[k].info.residentKernel), run_ms_median=round(float(np.median(ms[k])), 4),
                         run_ms_min=round(float(np.min(ms[k])), 4), fdtd_ms_median=round(float(np.median(fdtd[k])), 4))
     for s in pair:
