@@ -29,6 +29,17 @@ void UpdateGeometry(PlaneObjectID id, const AABB* t) {
 }
 void RemoveGeometry(PlaneObjectID id) { PlaneverbRemoveGeometry((int)id); }
 void SetListenerPosition(const vec3& p) { PlaneverbSetListenerPosition(p.x, p.y, p.z); }
+// Extensions with no counterpart in Planeverb.h: round and concave objects (planeverb_amd.h, "Round and concave shapes").  Grid
+// metres (x = world x, y = world z); ids are the shape table's, not AABB ids; any of the Remove calls takes a shape of any kind.
+int AddDiscGeometry(const vec2& c, float radius, float absorption) { return PlaneverbAddDiscGeometry(c.x, c.y, radius, absorption); }
+void UpdateDiscGeometry(int id, const vec2& c, float radius, float absorption) { PlaneverbUpdateDiscGeometry(id, c.x, c.y, radius, absorption); }
+void RemoveDiscGeometry(int id) { PlaneverbRemoveDiscGeometry(id); }
+int AddWallPathGeometry(const float* xy, int n, float radius, float absorption) { return PlaneverbAddWallPathGeometry(xy, n, radius, absorption); }
+void UpdateWallPathGeometry(int id, const float* xy, int n, float radius, float absorption) { PlaneverbUpdateWallPathGeometry(id, xy, n, radius, absorption); }
+void RemoveWallPathGeometry(int id) { PlaneverbRemoveWallPathGeometry(id); }
+int AddConcavePolygonGeometry(const float* xy, int n, float absorption) { return PlaneverbAddConcavePolygonGeometry(xy, n, absorption); }
+void UpdateConcavePolygonGeometry(int id, const float* xy, int n, float absorption) { PlaneverbUpdateConcavePolygonGeometry(id, xy, n, absorption); }
+void RemoveConcavePolygonGeometry(int id) { PlaneverbRemoveConcavePolygonGeometry(id); }
 // Planeverb.h:47, FDTD.cpp:60-79.  The reference returns a pointer into its IR cube; here the AoS Cells are
 // materialised on demand (the GPU keeps a pressure history and re-derives vx, vy) into a buffer this binding owns:
 // valid until the calling thread's next GetImpulseResponse, like upstream's until the next iteration overwrites it.

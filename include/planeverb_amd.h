@@ -94,6 +94,17 @@ PVA_EXPORT void PlaneverbRemoveOrientedGeometry(int id);
 PVA_EXPORT int PlaneverbAddPolygonGeometry(const float* xy, int n, float absorption);
 PVA_EXPORT void PlaneverbUpdatePolygonGeometry(int id, const float* xy, int n, float absorption);
 PVA_EXPORT void PlaneverbRemovePolygonGeometry(int id);
+/* Round and concave objects, the models of PvAmdAddDisc / PvAmdAddWallPath / PvAmdAddPolygon below, in the same id table and
+ * the same queue as the two calls above (any Remove...Geometry of this group removes a shape of any kind). */
+PVA_EXPORT int PlaneverbAddDiscGeometry(float posX, float posY, float radius, float absorption);
+PVA_EXPORT void PlaneverbUpdateDiscGeometry(int id, float posX, float posY, float radius, float absorption);
+PVA_EXPORT void PlaneverbRemoveDiscGeometry(int id);
+PVA_EXPORT int PlaneverbAddWallPathGeometry(const float* xy, int n, float radius, float absorption);
+PVA_EXPORT void PlaneverbUpdateWallPathGeometry(int id, const float* xy, int n, float radius, float absorption);
+PVA_EXPORT void PlaneverbRemoveWallPathGeometry(int id);
+PVA_EXPORT int PlaneverbAddConcavePolygonGeometry(const float* xy, int n, float absorption);
+PVA_EXPORT void PlaneverbUpdateConcavePolygonGeometry(int id, const float* xy, int n, float absorption);
+PVA_EXPORT void PlaneverbRemoveConcavePolygonGeometry(int id);
 /* Extension: the absorption of the four grid edges (PvAmdSetGridBoundary: xMin = side 0, xMax = 1, zMin = 2, zMax = 3), queued
  * like the geometry calls and applied to both live solvers at the same iteration boundary.  A non-finite value is refused
  * (nothing changes; PvAmdLastError says why). */
@@ -285,7 +296,7 @@ PVA_EXPORT int PvAmdUpdateGeometry(PvAmdSolver* s, int id, float posX, float pos
 PVA_EXPORT int PvAmdRemoveGeometry(PvAmdSolver* s, int id);
 PVA_EXPORT int PvAmdLoadScene(PvAmdSolver* s, const char* pvPath);
 /* Write the current boxes as a .pv file (Editor.cpp:219-243).  The .pv format is the reference's and holds axis-aligned
- * boxes only: shapes are not written. */
+ * boxes only: shapes of any kind (convex, disc, capsule, wall path, polygon) are not written. */
 PVA_EXPORT int PvAmdSaveScene(PvAmdSolver* s, const char* pvPath);
 
 /* Shapes (no reference counterpart).
@@ -316,6 +327,46 @@ PVA_EXPORT int PvAmdRemoveShape(PvAmdSolver* s, int id);
 PVA_EXPORT int PvAmdAddOrientedBox(PvAmdSolver* s, float px, float py, float w, float h, float ax, float ay, float absorption);
 PVA_EXPORT int PvAmdUpdateOrientedBox(PvAmdSolver* s, int id, float px, float py, float w, float h, float ax, float ay,
                                       float absorption);
+/* Round and concave shapes (no reference counterpart): three more kinds in the SAME layer.  They share the id table, the
+ * sequence rule (the shape added or updated most recently wins), the composition over the AABB layer and PvAmdRemoveShape
+ * with the convex shapes above; an Update call may change a shape's kind.  Coordinates are grid metres, P is the cell centre
+ * of the convex rule, every operation below is float32 without contraction, in the order the brackets give, and the ghost row
+ * and column are never covered.
+ *
+ * Disc: centre c, radius r.  d = P - c; covered when (d.x*d.x) + (d.y*d.y) <= r*r.
+ * Capsule (a thick wall segment): end points a, b, radius r (half the wall's thickness).  e = b - a, w = P - a,
+ *   ee = (e.x*e.x) + (e.y*e.y); t = 0 when ee == 0, else t = ((w.x*e.x) + (w.y*e.y)) / ee, then t = 0 if t < 0, 1 if t > 1;
+ *   q = (w.x - (t*e.x), w.y - (t*e.y)); covered when (q.x*q.x) + (q.y*q.y) <= r*r.  (The t = 0 case is decided by the float32
+ *   value ee, not by e, so that an e whose squares underflow is a disc too.)  a == b gives the disc's bits.
+ * Wall path: a polyline xy[2n] of 2 to PVA_POLY_MAX_VERTS points with one radius: ONE shape (one id, one sequence number)
+ *   that covers a cell when any of its n - 1 capsules (xy[i], xy[i+1]) does.  Consecutive capsules share an end point, so
+ *   corners are round and have neither notch nor overlap.
+ * Simple polygon: 3 to PVA_POLY_MAX_VERTS vertices, concave allowed, either winding (the list is kept as given).  Even-odd
+ *   crossing count over the edges a -> b (the last vertex back to the first): an edge toggles the cell when
+ *   (a.y > P.y) != (b.y > P.y) and P.x < (((b.x - a.x) * (P.y - a.y)) / (b.y - a.y)) + a.x; covered after an odd number of
+ *   toggles.  This rule and the convex half-plane rule of PvAmdAddShape may differ on cells whose centre lies exactly on an
+ *   edge (there the convex rule covers on every edge, this one on some of them only), which is why this is an entry
+ *   point of its own and not a relaxation of PvAmdAddShape.  Holes are not supported.
+ *
+ * Refused (-1, PvAmdLastError, the table unchanged): a non-finite coordinate, radius or absorption; a radius <= 0 (or whose
+ * float32 square is 0 or infinite); a segment whose ee is infinite; a wall path of fewer than 2 or more than
+ * PVA_POLY_MAX_VERTS points; a polygon of fewer than 3 or more than PVA_POLY_MAX_VERTS vertices, of zero area (shoelace sum
+ * in double), or self-intersecting.  Self-intersection is checked on the host in O(n^2), in double, with
+ * o(p, q, r) = (q.x - p.x)*(r.y - p.y) - (q.y - p.y)*(r.x - p.x): refused are a zero-length edge; two neighbouring edges p -> v,
+ * v -> q that fold back (o(p, v, q) == 0 and (p - v).(q - v) > 0); and two other edges p1p2, p3p4 that cross (o(p3,p4,p1) and
+ * o(p3,p4,p2) of opposite strict signs, and o(p1,p2,p3) and o(p1,p2,p4) too) or touch (one of those four is 0 and its point
+ * lies in the other edge's bounding box).  Collinear runs of vertices are accepted.  A radius below half a cell may cover
+ * no cell at all: that is a valid shape.  Slab groups take these kinds, slab ranks refuse them, as for PvAmdAddShape.  The .pv
+ * scene format holds axis-aligned boxes only: none of these is written by PvAmdSaveScene. */
+#define PVA_POLY_MAX_VERTS 64
+PVA_EXPORT int PvAmdAddDisc(PvAmdSolver* s, float cx, float cy, float radius, float absorption);
+PVA_EXPORT int PvAmdUpdateDisc(PvAmdSolver* s, int id, float cx, float cy, float radius, float absorption);
+PVA_EXPORT int PvAmdAddCapsule(PvAmdSolver* s, float ax, float ay, float bx, float by, float radius, float absorption);
+PVA_EXPORT int PvAmdUpdateCapsule(PvAmdSolver* s, int id, float ax, float ay, float bx, float by, float radius, float absorption);
+PVA_EXPORT int PvAmdAddWallPath(PvAmdSolver* s, const float* xy, int n, float radius, float absorption);
+PVA_EXPORT int PvAmdUpdateWallPath(PvAmdSolver* s, int id, const float* xy, int n, float radius, float absorption);
+PVA_EXPORT int PvAmdAddPolygon(PvAmdSolver* s, const float* xy, int n, float absorption);
+PVA_EXPORT int PvAmdUpdatePolygon(PvAmdSolver* s, int id, const float* xy, int n, float absorption);
 /* Grid edges.  absorption4 = R of the sides 0: faces at x = 0 (world x = 0), 1: faces at x = gx, 2: faces at y = 0 (world
  * z = 0), 3: faces at y = gy, taken as PvAmdAddGeometry takes absorption (any finite value); the admittance of side k is
  * Y = (1 - R) / (1 + R) in float32.  The edge faces are the reference's absorbing edges (FDTD.cpp:201-223) with Y in place of
@@ -395,6 +446,15 @@ PVA_EXPORT int PvAmdHostShape(const float* xy, int n, float absorption, float* o
 /* CPU only: the coverage rule on a grid of that configuration: cover[(gx+1)*(gy+1)] = 1 for the cells the shape covers */
 PVA_EXPORT int PvAmdHostShapeCoverage(float gridSizeX, float gridSizeY, int gridResolution, const float* xy, int n,
                                       uint8_t* cover);
+/* CPU only: the coverage rules of the round and concave kinds on a grid of that configuration, with the refusals of the Add
+ * calls.  kind: PVA_SHAPE_DISC (xy[2], n = 1), PVA_SHAPE_CAPSULE (xy[4], n = 2), PVA_SHAPE_WALL_PATH (xy[2n]) or
+ * PVA_SHAPE_POLYGON (xy[2n], radius ignored).  cover[(gx+1)*(gy+1)] = 1 for the covered cells. */
+#define PVA_SHAPE_DISC 1
+#define PVA_SHAPE_CAPSULE 2
+#define PVA_SHAPE_WALL_PATH 3
+#define PVA_SHAPE_POLYGON 4
+PVA_EXPORT int PvAmdHostRoundShapeCoverage(float gridSizeX, float gridSizeY, int gridResolution, int kind, const float* xy,
+                                           int n, float radius, uint8_t* cover);
 
 /* One iteration of the reference's background loop (PvContext.cpp:80-83): GenerateResponse + AnalyzeResponses
  * for a listener position; synchronous. */

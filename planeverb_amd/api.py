@@ -124,6 +124,15 @@ SYMBOLS = {
     "PlaneverbAddPolygonGeometry": (C.c_int, [_fp, C.c_int, C.c_float]),
     "PlaneverbUpdatePolygonGeometry": (None, [C.c_int, _fp, C.c_int, C.c_float]),
     "PlaneverbRemovePolygonGeometry": (None, [C.c_int]),
+    "PlaneverbAddDiscGeometry": (C.c_int, [C.c_float] * 4),
+    "PlaneverbUpdateDiscGeometry": (None, [C.c_int] + [C.c_float] * 4),
+    "PlaneverbRemoveDiscGeometry": (None, [C.c_int]),
+    "PlaneverbAddWallPathGeometry": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float]),
+    "PlaneverbUpdateWallPathGeometry": (None, [C.c_int, _fp, C.c_int, C.c_float, C.c_float]),
+    "PlaneverbRemoveWallPathGeometry": (None, [C.c_int]),
+    "PlaneverbAddConcavePolygonGeometry": (C.c_int, [_fp, C.c_int, C.c_float]),
+    "PlaneverbUpdateConcavePolygonGeometry": (None, [C.c_int, _fp, C.c_int, C.c_float]),
+    "PlaneverbRemoveConcavePolygonGeometry": (None, [C.c_int]),
     "PlaneverbLoadScene": (C.c_int, [C.c_char_p]),
     "PlaneverbIterationCount": (C.c_longlong, []),
     "PlaneverbWaitIterations": (C.c_longlong, [C.c_longlong, C.c_int]),
@@ -172,6 +181,14 @@ SYMBOLS = {
     "PvAmdRemoveShape": (C.c_int, [_vp, C.c_int]),
     "PvAmdAddOrientedBox": (C.c_int, [_vp] + [C.c_float] * 7),
     "PvAmdUpdateOrientedBox": (C.c_int, [_vp, C.c_int] + [C.c_float] * 7),
+    "PvAmdAddDisc": (C.c_int, [_vp] + [C.c_float] * 4),
+    "PvAmdUpdateDisc": (C.c_int, [_vp, C.c_int] + [C.c_float] * 4),
+    "PvAmdAddCapsule": (C.c_int, [_vp] + [C.c_float] * 6),
+    "PvAmdUpdateCapsule": (C.c_int, [_vp, C.c_int] + [C.c_float] * 6),
+    "PvAmdAddWallPath": (C.c_int, [_vp, _fp, C.c_int, C.c_float, C.c_float]),
+    "PvAmdUpdateWallPath": (C.c_int, [_vp, C.c_int, _fp, C.c_int, C.c_float, C.c_float]),
+    "PvAmdAddPolygon": (C.c_int, [_vp, _fp, C.c_int, C.c_float]),
+    "PvAmdUpdatePolygon": (C.c_int, [_vp, C.c_int, _fp, C.c_int, C.c_float]),
     "PvAmdSetGridBoundary": (C.c_int, [_vp, _fp]),
     "PvAmdGetGridBoundary": (C.c_int, [_vp, _fp]),
     "PlaneverbSetGridBoundary": (None, [C.c_float] * 4),
@@ -186,6 +203,8 @@ SYMBOLS = {
     "PvAmdHostOrientedBoxVertices": (C.c_int, [C.c_float] * 6 + [_fp]),
     "PvAmdHostShape": (C.c_int, [_fp, C.c_int, C.c_float, _fp]),
     "PvAmdHostShapeCoverage": (C.c_int, [C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
+    "PvAmdHostRoundShapeCoverage": (C.c_int, [C.c_float, C.c_float, C.c_int, C.c_int, _fp, C.c_int, C.c_float,
+                                              C.POINTER(C.c_ubyte)]),
     "PvAmdRun": (C.c_int, [_vp] + [C.c_float] * 3),
     "PvAmdRunAsync": (C.c_int, [_vp] + [C.c_float] * 3),
     "PvAmdRunAsyncAfter": (C.c_int, [_vp, _vp] + [C.c_float] * 3),
@@ -382,6 +401,49 @@ def RemovePolygonGeometry(sid):
     lib().PlaneverbRemovePolygonGeometry(int(sid))
 
 
+def AddDiscGeometry(cx, cy, radius, absorption):
+    """a disc in grid metres (shape ids); -1 if refused"""
+    return lib().PlaneverbAddDiscGeometry(float(cx), float(cy), float(radius), float(absorption))
+
+
+def UpdateDiscGeometry(sid, cx, cy, radius, absorption):
+    lib().PlaneverbUpdateDiscGeometry(int(sid), float(cx), float(cy), float(radius), float(absorption))
+
+
+def RemoveDiscGeometry(sid):
+    lib().PlaneverbRemoveDiscGeometry(int(sid))
+
+
+def AddWallPathGeometry(points, radius, absorption):
+    """a polyline of 2..64 points with a radius (half the wall's thickness): one shape; -1 if refused"""
+    a, n = _xy(points)
+    return lib().PlaneverbAddWallPathGeometry(_f(a), n, float(radius), float(absorption))
+
+
+def UpdateWallPathGeometry(sid, points, radius, absorption):
+    a, n = _xy(points)
+    lib().PlaneverbUpdateWallPathGeometry(int(sid), _f(a), n, float(radius), float(absorption))
+
+
+def RemoveWallPathGeometry(sid):
+    lib().PlaneverbRemoveWallPathGeometry(int(sid))
+
+
+def AddConcavePolygonGeometry(vertices, absorption):
+    """a simple polygon of 3..64 vertices, concave allowed, either winding (shape ids); -1 if refused"""
+    a, n = _xy(vertices)
+    return lib().PlaneverbAddConcavePolygonGeometry(_f(a), n, float(absorption))
+
+
+def UpdateConcavePolygonGeometry(sid, vertices, absorption):
+    a, n = _xy(vertices)
+    lib().PlaneverbUpdateConcavePolygonGeometry(int(sid), _f(a), n, float(absorption))
+
+
+def RemoveConcavePolygonGeometry(sid):
+    lib().PlaneverbRemoveConcavePolygonGeometry(int(sid))
+
+
 def SetGridBoundary(xmin, xmax, zmin, zmax):
     """absorption of the four grid edges (Solver.set_grid_boundary), applied at the next iteration boundary"""
     lib().PlaneverbSetGridBoundary(float(xmin), float(xmax), float(zmin), float(zmax))
@@ -483,6 +545,21 @@ def host_shape(vertices, absorption=0.0):
     if m < 0:
         raise PlaneverbError(last_error())
     return out[:2 * m].reshape(m, 2)
+
+
+SHAPE_DISC, SHAPE_CAPSULE, SHAPE_WALL_PATH, SHAPE_POLYGON = 1, 2, 3, 4
+POLY_MAX_VERTS = 64
+
+
+def host_coverage(size_x, size_y, res, kind, points, radius=0.0):
+    """the cells (gx+1) x (gy+1) a disc / capsule / wall path / simple polygon covers on a grid of that configuration (uint8);
+    kind = SHAPE_DISC (one point), SHAPE_CAPSULE (two), SHAPE_WALL_PATH or SHAPE_POLYGON; PlaneverbError if refused"""
+    a, n = _xy(points)
+    g = host_grid_info(size_x, size_y, res)
+    cover = np.empty((g.gx + 1, g.gy + 1), np.uint8)
+    _check(lib().PvAmdHostRoundShapeCoverage(float(size_x), float(size_y), int(res), int(kind), _f(a), n, float(radius),
+                                             cover.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return cover
 
 
 def host_shape_coverage(size_x, size_y, res, vertices):
@@ -968,6 +1045,45 @@ class Solver:
     def update_oriented_box(self, sid, px, py, w, h, ax, ay, absorption):
         _check(lib().PvAmdUpdateOrientedBox(self._h, int(sid), float(px), float(py), float(w), float(h), float(ax), float(ay),
                                             float(absorption)))
+
+    def _added(self, sid):
+        if sid < 0:
+            raise PlaneverbError(last_error())
+        return sid
+
+    def add_disc(self, cx, cy, radius, absorption):
+        """a disc (grid metres); returns its shape id (PlaneverbError if refused)"""
+        return self._added(lib().PvAmdAddDisc(self._h, float(cx), float(cy), float(radius), float(absorption)))
+
+    def update_disc(self, sid, cx, cy, radius, absorption):
+        _check(lib().PvAmdUpdateDisc(self._h, int(sid), float(cx), float(cy), float(radius), float(absorption)))
+
+    def add_capsule(self, a, b, radius, absorption):
+        """a thick wall segment a -> b of half thickness radius; returns its shape id"""
+        return self._added(lib().PvAmdAddCapsule(self._h, float(a[0]), float(a[1]), float(b[0]), float(b[1]), float(radius),
+                                                 float(absorption)))
+
+    def update_capsule(self, sid, a, b, radius, absorption):
+        _check(lib().PvAmdUpdateCapsule(self._h, int(sid), float(a[0]), float(a[1]), float(b[0]), float(b[1]), float(radius),
+                                        float(absorption)))
+
+    def add_wall_path(self, points, radius, absorption):
+        """a polyline of 2..64 points, one capsule per segment, as ONE shape; returns its shape id"""
+        p, n = _xy(points)
+        return self._added(lib().PvAmdAddWallPath(self._h, _f(p), n, float(radius), float(absorption)))
+
+    def update_wall_path(self, sid, points, radius, absorption):
+        p, n = _xy(points)
+        _check(lib().PvAmdUpdateWallPath(self._h, int(sid), _f(p), n, float(radius), float(absorption)))
+
+    def add_polygon(self, vertices, absorption):
+        """a simple polygon of 3..64 vertices, concave allowed, either winding; returns its shape id"""
+        p, n = _xy(vertices)
+        return self._added(lib().PvAmdAddPolygon(self._h, _f(p), n, float(absorption)))
+
+    def update_polygon(self, sid, vertices, absorption):
+        p, n = _xy(vertices)
+        _check(lib().PvAmdUpdatePolygon(self._h, int(sid), _f(p), n, float(absorption)))
 
     def remove_shape(self, sid):
         _check(lib().PvAmdRemoveShape(self._h, int(sid)))

@@ -262,6 +262,75 @@ void PlaneverbRemovePolygonGeometry(int id) try {
     if (c) c->removeShape(id);
 } PV_API_CATCH_VOID
 
+// round and concave shapes (pv_core.h makeRound / makePolygon): the same queue and the same ids
+static_assert(PVA_POLY_MAX_VERTS == kPolyMaxVerts, "planeverb_amd.h vs pv_core.h");
+static bool discShape(float cx, float cy, float radius, float absorption, Shape* out) {
+    const float c[2] = {cx, cy};
+    return makeRound(c, 1, radius, absorption, out, &g_lastError);
+}
+static bool capsuleShape(float ax, float ay, float bx, float by, float radius, float absorption, Shape* out) {
+    const float p[4] = {ax, ay, bx, by};
+    return makeRound(p, 2, radius, absorption, out, &g_lastError);
+}
+static bool wallPathShape(const float* xy, int n, float radius, float absorption, Shape* out) {
+    if (n < 2) {
+        g_lastError = "wall path: 2 to 64 points";
+        return false;
+    }
+    return makeRound(xy, n, radius, absorption, out, &g_lastError);
+}
+
+int PlaneverbAddDiscGeometry(float posX, float posY, float radius, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    return (c && discShape(posX, posY, radius, absorption, &sh)) ? c->addShape(sh) : -1;
+} PV_API_CATCH(-1)
+
+void PlaneverbUpdateDiscGeometry(int id, float posX, float posY, float radius, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    if (c && discShape(posX, posY, radius, absorption, &sh)) c->updateShape(id, sh);
+} PV_API_CATCH_VOID
+
+void PlaneverbRemoveDiscGeometry(int id) try {
+    Context::Ref c;
+    if (c) c->removeShape(id);
+} PV_API_CATCH_VOID
+
+int PlaneverbAddWallPathGeometry(const float* xy, int n, float radius, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    return (c && wallPathShape(xy, n, radius, absorption, &sh)) ? c->addShape(sh) : -1;
+} PV_API_CATCH(-1)
+
+void PlaneverbUpdateWallPathGeometry(int id, const float* xy, int n, float radius, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    if (c && wallPathShape(xy, n, radius, absorption, &sh)) c->updateShape(id, sh);
+} PV_API_CATCH_VOID
+
+void PlaneverbRemoveWallPathGeometry(int id) try {
+    Context::Ref c;
+    if (c) c->removeShape(id);
+} PV_API_CATCH_VOID
+
+int PlaneverbAddConcavePolygonGeometry(const float* xy, int n, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    return (c && makePolygon(xy, n, absorption, &sh, &g_lastError)) ? c->addShape(sh) : -1;
+} PV_API_CATCH(-1)
+
+void PlaneverbUpdateConcavePolygonGeometry(int id, const float* xy, int n, float absorption) try {
+    Context::Ref c;
+    Shape sh;
+    if (c && makePolygon(xy, n, absorption, &sh, &g_lastError)) c->updateShape(id, sh);
+} PV_API_CATCH_VOID
+
+void PlaneverbRemoveConcavePolygonGeometry(int id) try {
+    Context::Ref c;
+    if (c) c->removeShape(id);
+} PV_API_CATCH_VOID
+
 void PlaneverbSetListenerPosition(float x, float y, float z) try {
     Context::Ref c;
     if (c) c->setListener(x, y, z);
@@ -719,6 +788,58 @@ int PvAmdUpdateOrientedBox(PvAmdSolver* h, int id, float px, float py, float w, 
     return ret(h, h->g ? h->g->updateShape(id, sh) : h->s->updateShape(id, sh));
 } PV_API_CATCH(-1)
 
+static int updateShape(PvAmdSolver* h, int id, const Shape& sh) {
+    return ret(h, h->g ? h->g->updateShape(id, sh) : h->s->updateShape(id, sh));
+}
+
+int PvAmdAddDisc(PvAmdSolver* h, float cx, float cy, float radius, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !discShape(cx, cy, radius, absorption, &sh)) return -1;
+    return addShape(h, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdUpdateDisc(PvAmdSolver* h, int id, float cx, float cy, float radius, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !discShape(cx, cy, radius, absorption, &sh)) return -1;
+    return updateShape(h, id, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdAddCapsule(PvAmdSolver* h, float ax, float ay, float bx, float by, float radius, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !capsuleShape(ax, ay, bx, by, radius, absorption, &sh)) return -1;
+    return addShape(h, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdUpdateCapsule(PvAmdSolver* h, int id, float ax, float ay, float bx, float by, float radius, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !capsuleShape(ax, ay, bx, by, radius, absorption, &sh)) return -1;
+    return updateShape(h, id, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdAddWallPath(PvAmdSolver* h, const float* xy, int n, float radius, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !wallPathShape(xy, n, radius, absorption, &sh)) return -1;
+    return addShape(h, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdUpdateWallPath(PvAmdSolver* h, int id, const float* xy, int n, float radius, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !wallPathShape(xy, n, radius, absorption, &sh)) return -1;
+    return updateShape(h, id, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdAddPolygon(PvAmdSolver* h, const float* xy, int n, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !makePolygon(xy, n, absorption, &sh, &g_lastError)) return -1;
+    return addShape(h, sh);
+} PV_API_CATCH(-1)
+
+int PvAmdUpdatePolygon(PvAmdSolver* h, int id, const float* xy, int n, float absorption) try {
+    Shape sh;
+    if (!shapesOk(h) || !makePolygon(xy, n, absorption, &sh, &g_lastError)) return -1;
+    return updateShape(h, id, sh);
+} PV_API_CATCH(-1)
+
 int PvAmdSetGridBoundary(PvAmdSolver* h, const float* absorption4) try {
     if (!absorption4) {
         g_lastError = "PvAmdSetGridBoundary: null absorption array";
@@ -1145,6 +1266,35 @@ int PvAmdHostShape(const float* xy, int n, float absorption, float* out16) try {
 int PvAmdHostShapeCoverage(float sx, float sy, int res, const float* xy, int n, uint8_t* cover) try {
     Shape sh;
     if (res < kLowResolution || !cover || !makeShape(xy, n, 0.f, &sh, &g_lastError)) return -1;
+    const GridSpec g = makeGridSpec(sx, sy, res);
+    std::memset(cover, 0, (size_t)g.NX * g.NY);
+    int x0, x1, y0, y1;
+    shapeCellBounds(sh, g, &x0, &x1, &y0, &y1);
+    for (int x = x0; x < x1; ++x)
+        for (int y = y0; y < y1; ++y) cover[(size_t)x * g.NY + y] = shapeCovers(sh, g.dx, x, y) ? 1 : 0;
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostRoundShapeCoverage(float sx, float sy, int res, int kind, const float* xy, int n, float radius, uint8_t* cover) try {
+    Shape sh;
+    if (res < kLowResolution || !cover) {
+        g_lastError = "PvAmdHostRoundShapeCoverage: resolution below 275 or a null array";
+        return -1;
+    }
+    bool ok = false;
+    if (kind == PVA_SHAPE_POLYGON) {
+        ok = makePolygon(xy, n, 0.f, &sh, &g_lastError);
+    } else if (kind == PVA_SHAPE_WALL_PATH) {
+        ok = wallPathShape(xy, n, radius, 0.f, &sh);
+    } else if (kind == PVA_SHAPE_DISC || kind == PVA_SHAPE_CAPSULE) {
+        if (n != kind)  // (1 point, 2 points)
+            g_lastError = kind == PVA_SHAPE_DISC ? "disc: one point" : "capsule: two points";
+        else
+            ok = makeRound(xy, n, radius, 0.f, &sh, &g_lastError);
+    } else {
+        g_lastError = "PvAmdHostRoundShapeCoverage: unknown kind";
+    }
+    if (!ok) return -1;
     const GridSpec g = makeGridSpec(sx, sy, res);
     std::memset(cover, 0, (size_t)g.NX * g.NY);
     int x0, x1, y0, y1;

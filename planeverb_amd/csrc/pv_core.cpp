@@ -185,6 +185,86 @@ bool makeShape(const float* xy, int n, float R, Shape* out, std::string* err) {
     return true;
 }
 
+bool makeRound(const float* xy, int n, float radius, float R, Shape* out, std::string* err) {
+    auto refuse = [&](const char* why) {
+        if (err) *err = why;
+        return false;
+    };
+    if (!xy) return refuse("round shape: no point list");
+    if (n < 1 || n > kPolyMaxVerts) return refuse("round shape: 1 to 64 points");
+    if (!std::isfinite(R)) return refuse("round shape with a non-finite absorption");
+    if (!std::isfinite(radius)) return refuse("round shape with a non-finite radius");
+    if (!(radius > 0.f) || !(radius * radius > 0.f)) return refuse("round shape: the radius must be positive");
+    if (!std::isfinite(radius * radius)) return refuse("round shape: the radius is too large");
+    for (int i = 0; i < 2 * n; ++i)
+        if (!std::isfinite(xy[i])) return refuse("round shape with a non-finite coordinate");
+    for (int i = 0; i + 1 < n; ++i) {
+        const float ex = xy[2 * i + 2] - xy[2 * i], ey = xy[2 * i + 3] - xy[2 * i + 1];
+        if (!std::isfinite((ex * ex) + (ey * ey))) return refuse("round shape: a segment is too long");
+    }
+    Shape s;
+    s.kind = kShapeRound;
+    s.n = n;
+    s.R = R;
+    s.r = radius;
+    std::memcpy(s.xy, xy, sizeof(float) * 2 * (size_t)n);
+    *out = s;
+    return true;
+}
+
+bool polygonSelfIntersects(const float* xy, int n) {
+    struct P {
+        double x, y;
+    };
+    auto pt = [&](int i) { return P{xy[2 * (i % n)], xy[2 * (i % n) + 1]}; };
+    auto o = [](P p, P q, P r) { return (q.x - p.x) * (r.y - p.y) - (q.y - p.y) * (r.x - p.x); };
+    auto inBox = [](P p, P q, P r) {
+        return std::min(p.x, q.x) <= r.x && r.x <= std::max(p.x, q.x) && std::min(p.y, q.y) <= r.y && r.y <= std::max(p.y, q.y);
+    };
+    for (int i = 0; i < n; ++i) {
+        const P p = pt(i), v = pt(i + 1), q = pt(i + 2);
+        if (p.x == v.x && p.y == v.y) return true;  // zero-length edge
+        if (o(p, v, q) == 0 && (p.x - v.x) * (q.x - v.x) + (p.y - v.y) * (q.y - v.y) > 0) return true;  // fold-back
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 2; j < n; ++j) {
+            if (i == 0 && j == n - 1) continue;  // neighbours through the closing vertex
+            const P p1 = pt(i), p2 = pt(i + 1), p3 = pt(j), p4 = pt(j + 1);
+            const double d1 = o(p3, p4, p1), d2 = o(p3, p4, p2), d3 = o(p1, p2, p3), d4 = o(p1, p2, p4);
+            if (((d1 > 0 && d2 < 0) || (d1 < 0 && d2 > 0)) && ((d3 > 0 && d4 < 0) || (d3 < 0 && d4 > 0))) return true;
+            if ((d1 == 0 && inBox(p3, p4, p1)) || (d2 == 0 && inBox(p3, p4, p2)) || (d3 == 0 && inBox(p1, p2, p3)) ||
+                (d4 == 0 && inBox(p1, p2, p4)))
+                return true;
+        }
+    return false;
+}
+
+bool makePolygon(const float* xy, int n, float R, Shape* out, std::string* err) {
+    auto refuse = [&](const char* why) {
+        if (err) *err = why;
+        return false;
+    };
+    if (!xy) return refuse("polygon: no vertex list");
+    if (n < 3 || n > kPolyMaxVerts) return refuse("polygon: 3 to 64 vertices");
+    if (!std::isfinite(R)) return refuse("polygon with a non-finite absorption");
+    for (int i = 0; i < 2 * n; ++i)
+        if (!std::isfinite(xy[i])) return refuse("polygon with a non-finite coordinate");
+    double area = 0;  // (shoelace in double, as makeShape)
+    for (int i = 0; i < n; ++i) {
+        const int j = (i + 1) % n;
+        area += (double)xy[2 * i] * xy[2 * j + 1] - (double)xy[2 * j] * xy[2 * i + 1];
+    }
+    if (!(area != 0) || !std::isfinite(area)) return refuse("polygon with zero area");
+    if (polygonSelfIntersects(xy, n)) return refuse("polygon: the vertex list intersects itself");
+    Shape s;
+    s.kind = kShapePolygon;
+    s.n = n;
+    s.R = R;
+    std::memcpy(s.xy, xy, sizeof(float) * 2 * (size_t)n);
+    *out = s;
+    return true;
+}
+
 bool orientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float out8[8], std::string* err) {
     if (!(std::isfinite(px) && std::isfinite(py) && std::isfinite(w) && std::isfinite(h) && std::isfinite(ax) && std::isfinite(ay))) {
         if (err) *err = "oriented box with a non-finite input";
@@ -214,6 +294,34 @@ bool orientedBoxVertices(float px, float py, float w, float h, float ax, float a
 
 bool shapeCovers(const Shape& s, float dx, int x, int y) {
     const float px = ((float)x + 0.5f) * dx, py = ((float)y + 0.5f) * dx;
+    if (s.kind == kShapeRound) {
+        const float rr = s.r * s.r;
+        const int segs = s.n > 1 ? s.n - 1 : 1;
+        for (int i = 0; i < segs; ++i) {
+            const int j = i + 1 < s.n ? i + 1 : i;
+            const float ax = s.xy[2 * i], ay = s.xy[2 * i + 1];
+            const float ex = s.xy[2 * j] - ax, ey = s.xy[2 * j + 1] - ay;
+            const float wx = px - ax, wy = py - ay;
+            const float ee = (ex * ex) + (ey * ey);
+            float t = 0.f;
+            if (ee != 0.f) {
+                t = ((wx * ex) + (wy * ey)) / ee;
+                t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+            }
+            const float qx = wx - (t * ex), qy = wy - (t * ey);
+            if ((qx * qx) + (qy * qy) <= rr) return true;
+        }
+        return false;
+    }
+    if (s.kind == kShapePolygon) {
+        bool in = false;
+        for (int i = 0; i < s.n; ++i) {
+            const int j = i + 1 == s.n ? 0 : i + 1;
+            const float ax = s.xy[2 * i], ay = s.xy[2 * i + 1], bx = s.xy[2 * j], by = s.xy[2 * j + 1];
+            if ((ay > py) != (by > py) && px < (((bx - ax) * (py - ay)) / (by - ay)) + ax) in = !in;
+        }
+        return in;
+    }
     for (int i = 0; i < s.n; ++i) {
         const int j = i + 1 == s.n ? 0 : i + 1;
         const float ax = s.xy[2 * i], ay = s.xy[2 * i + 1];
@@ -231,6 +339,16 @@ void shapeCellBounds(const Shape& s, const GridSpec& g, int* x0, int* x1, int* y
             hi[a] = std::max(hi[a], (double)s.xy[2 * i + a]);
             m = std::max(m, std::fabs((double)s.xy[2 * i + a]));
         }
+    // a round shape reaches r beyond its points: q = w - t e with 0 <= t <= 1 stays within rounding of the segment's box, and
+    // q.q <= r r holds |q.x|, |q.y| to r (1 + 2^-22).  A polygon's crossing rule compares P.y with the vertices exactly, and its
+    // float32 intersection abscissa leaves the vertices' x range by a few ulp(m) at most.  The pad below covers both.
+    if (s.kind == kShapeRound) {
+        for (int a = 0; a < 2; ++a) {
+            lo[a] -= (double)s.r;
+            hi[a] += (double)s.r;
+        }
+        m += (double)s.r;
+    }
     // the float32 edge function can accept a centre up to ~16 ulp(m) outside an edge: 2 cells plus that, in cells
     const double pad = 2.0 + std::ceil(m * 4e-6 / g.dx);
     const int n[2] = {g.gx, g.gy};

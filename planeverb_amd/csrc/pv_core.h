@@ -87,18 +87,42 @@ private:
 // counter-clockwise, with an absorption value; rasterised by the cell-centre rule of shapeCovers on top of the AABB layer
 // (Solver::applyGeometry, pv_shapes.hip).  Everything here is float32 without contraction, so that a numpy restatement is exact.
 constexpr int kShapeMaxVerts = 8;
+// Round and concave kinds in the same layer (include/planeverb_amd.h, "Round and concave shapes"): a round shape is a chain of
+// n >= 1 points with a radius -- n = 1 a disc, n = 2 a capsule, more a wall path, covered where any of its capsules covers -- and
+// a simple polygon is 3..kPolyMaxVerts vertices in either winding under the even-odd crossing rule.
+constexpr int kPolyMaxVerts = 64;
+enum ShapeKind : int { kShapeConvex = 0, kShapeRound = 1, kShapePolygon = 2 };
+// The point list is inline and of the largest size (528 bytes a Shape, 76 before these kinds), also where the live module queues
+// a Shape by value beside every change (pv_context.h Change, AABB and grid-edge changes included) and in every table slot: a
+// fixed-size record cannot fail to allocate, which keeps the queue's "room first, then push" guarantee under allocation failure
+// (tests/host/alloc_fault*.cpp) as simple as it was.  The price is a queue entry about five times the size; the device side has
+// the pooled table instead (pv_shapes.h).
 struct Shape {
+    int kind = kShapeConvex;
     int n = 0;
-    float xy[2 * kShapeMaxVerts] = {};
+    float xy[2 * kPolyMaxVerts] = {};  // (a convex shape uses the first kShapeMaxVerts)
     float R = 0.f;
+    float r = 0.f;                     // radius of a round shape
 };
 // validates (finite coordinates and absorption, 3..8 vertices, non-zero area, convex and simple) and orders the list
 // counter-clockwise; false + *err on a refusal
 bool makeShape(const float* xy, int n, float R, Shape* out, std::string* err);
+// a disc / capsule / wall path: finite points and absorption, 1..kPolyMaxVerts points, finite radius > 0, every segment's
+// float32 squared length finite; false + *err on a refusal
+bool makeRound(const float* xy, int n, float radius, float R, Shape* out, std::string* err);
+// a simple polygon: finite vertices and absorption, 3..kPolyMaxVerts vertices, non-zero area, no two edges with a point in
+// common other than the vertex two neighbours share (polygonSelfIntersects); the list is kept as given
+bool makePolygon(const float* xy, int n, float R, Shape* out, std::string* err);
+// O(n^2), in double: a zero-length edge; neighbours that fold back onto each other (o = 0 and (p - v) . (q - v) > 0 at their
+// shared vertex v); or two other edges p1p2, p3p4 that cross (o(p3,p4,p1), o(p3,p4,p2) of opposite strict signs and
+// o(p1,p2,p3), o(p1,p2,p4) too) or touch (some o = 0 with that point inside the other edge's bounding box), where
+// o(p, q, r) = (q.x - p.x) (r.y - p.y) - (q.y - p.y) (r.x - p.x)
+bool polygonSelfIntersects(const float* xy, int n);
 // the 4 vertices of an oriented box: centre (px, py), full width w along the axis (ax, ay) (any non-zero length), full
 // height h along its left normal; counter-clockwise.  false + *err for a zero or non-finite axis or a non-finite input.
 bool orientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float out8[8], std::string* err);
-// is the centre of cell (x, y) inside the shape?  ((float)x + 0.5f) * dx etc., every edge a -> b: e.x (P.y - a.y) - e.y (P.x - a.x) >= 0
+// is the centre of cell (x, y) inside the shape?  ((float)x + 0.5f) * dx etc.; convex: every edge a -> b: e.x (P.y - a.y) - e.y (P.x - a.x) >= 0;
+// round and polygon: the rules of include/planeverb_amd.h, restated in pv_core.cpp and pv_shapes.hip
 bool shapeCovers(const Shape& s, float dx, int x, int y);
 // cells [*x0, *x1) x [*y0, *y1) that contain every cell shapeCovers can accept (padded for the rounding of the edge
 // function), clipped to the grid's cells 0 <= x < gx, 0 <= y < gy (never the ghost row / column); empty when x0 >= x1 or y0 >= y1

@@ -14,8 +14,11 @@ namespace pva {
 constexpr int kShapeBin = 64;  // cells per bin side
 
 struct DevShape {
-    float xy[2 * kShapeMaxVerts];  // counter-clockwise vertices, grid metres
+    float xy[2 * kShapeMaxVerts];  // convex: counter-clockwise vertices, grid metres; round / polygon: the points when n <= 8
     int n;
+    int kind;                      // ShapeKind (pv_core.h)
+    float r;                       // radius of a round shape
+    int off;                       // n > kShapeMaxVerts: the points are pool[off .. off + 2 n)
     float Y;                       // admittance (1 - R) / (1 + R), float32 as applyGeometry computes it for AABBs
     int x0, x1, y0, y1;            // cells [x0, x1) x [y0, y1) that can be covered (shapeCellBounds)
 };
@@ -24,6 +27,7 @@ struct ShapeArgs {
     const float* base;        // AABB-layer material, NX x NY (NaN = air, else Y)
     float* mat;               // composed material, NX x NY
     const DevShape* shapes;
+    const float* pool;        // point lists longer than kShapeMaxVerts (nullptr when no shape has one)
     const int* binStart;      // nbx * nby + 1 offsets into binList
     const int* binList;       // per bin: shape indices, highest sequence number first
     const int* dirtyBins;     // bins to recompose

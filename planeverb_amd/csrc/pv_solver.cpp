@@ -837,11 +837,19 @@ bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
     const int ns = (int)order.size();
     std::vector<DevShape> table((size_t)ns);
     std::vector<int> binStart((size_t)nbins + 1, 0);
+    std::vector<float> pool;
     for (int k = 0; k < ns; ++k) {
         const Shape& sh = shapeTable_[(size_t)order[k]];
         DevShape& d = table[(size_t)k];
         std::memcpy(d.xy, sh.xy, sizeof(d.xy));
         d.n = sh.n;
+        d.kind = sh.kind;
+        d.r = sh.r;
+        d.off = 0;
+        if (sh.n > kShapeMaxVerts) {  // (round and polygon kinds only: the pooled point table, absent until a shape needs it)
+            d.off = (int)pool.size();
+            pool.insert(pool.end(), sh.xy, sh.xy + 2 * sh.n);
+        }
         d.Y = (1.f - sh.R) / (1.f + sh.R);  // (as applyGeometry for the AABB layer)
         shapeCellBounds(sh, g_, &d.x0, &d.x1, &d.y0, &d.y1);
         if (d.x0 >= d.x1 || d.y0 >= d.y1) continue;
@@ -869,7 +877,8 @@ bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
     }
     auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t oTab = 0, oStart = align(table.size() * sizeof(DevShape)), oList = oStart + align(binStart.size() * 4),
-                 oDirty = oList + align(binList.size() * 4), bytes = oDirty + align(devDirty.size() * 4);
+                 oDirty = oList + align(binList.size() * 4), oPool = oDirty + align(devDirty.size() * 4),
+                 bytes = oPool + align(pool.size() * 4);
     if (bytes > shapeDevBytes_) {
         if (shapeDev_) {
             if (!hipOk(hipStreamSynchronize(stream_), "shape sync")) return false;
@@ -888,12 +897,14 @@ bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
     std::memcpy(shapeStage_.data() + oStart, binStart.data(), binStart.size() * 4);
     std::memcpy(shapeStage_.data() + oList, binList.data(), binList.size() * 4);
     std::memcpy(shapeStage_.data() + oDirty, devDirty.data(), devDirty.size() * 4);
+    if (!pool.empty()) std::memcpy(shapeStage_.data() + oPool, pool.data(), pool.size() * 4);
     unsigned char* base = static_cast<unsigned char*>(shapeDev_);
     if (!hipOk(hipMemcpyAsync(base, shapeStage_.data(), bytes, hipMemcpyHostToDevice, stream_), "shape table upload")) return false;
     ShapeArgs a;
     a.base = matBaseDev_;
     a.mat = matDev_;
     a.shapes = reinterpret_cast<const DevShape*>(base + oTab);
+    a.pool = pool.empty() ? nullptr : reinterpret_cast<const float*>(base + oPool);
     a.binStart = reinterpret_cast<const int*>(base + oStart);
     a.binList = reinterpret_cast<const int*>(base + oList);
     a.dirtyBins = reinterpret_cast<const int*>(base + oDirty);

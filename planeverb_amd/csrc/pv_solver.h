@@ -155,7 +155,8 @@ public:
     void rasterAdd(const Box& b) { mat_.add(b); }
     void rasterRemove(const Box& b) { mat_.remove(b); }
 
-    // Shape layer (pv_shapes.h): convex polygons over the AABB layer, ids of their own with the same LIFO recycling.  The
+    // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
+    // ids of their own with the same LIFO recycling.  The
     // first shape gives the solver a device plane for the AABB layer; a solver that never has one keeps the AABB-only path.
     int addShape(const Shape& sh);
     bool updateShape(int id, const Shape& sh);
