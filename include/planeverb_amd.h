@@ -215,6 +215,7 @@ enum {
     PVA_OPT_ALTERNATE_SWEEPS = 26, /* tile order 3 only: 1 = odd launches of a run walk every XCD's strip of tiles from its last tile row to its first, so that a launch reads first what the previous launch wrote last (still in the 256 MiB Infinity Cache) instead of streaming through the cache in the order that evicts everything before it is read again.  Results do not depend on it.  -1 = default, 0 = off */
     PVA_OPT_XCD_REGIONS = 27, /* tile order 3 only: 1 = every XCD owns one of 2 x 4 regions of the grid (walked row-major) instead of one of 8 strips of tile columns: a region is twice as wide, so half as many cache lines on its sides are fetched by two XCDs, and a tile's vertical neighbours are still close enough for the XCD's L2.  Results do not depend on it.  -1 = default (on), 0 = strips */
     PVA_OPT_REACH_BOUND = 30, /* runs that go out as plain merged launches (grids of more than 4096 tiles, or with PVA_OPT_USE_GRAPH set to 2; not with row bands, slabs, streaming analysis, dense history, edge tiles, kernel timing or a listener outside the grid): 1 = every K-step launch advances only the tiles that the pulse can have reached by then (a run starts from zero fields and a value moves one cell per step), the rest of both buffer sets is kept at zero.  Bit-identical to full sweeps.  -1 = default (on), 0 = every launch sweeps the whole grid */
+    PVA_OPT_RESIDENT_WINDOW = 31, /* runs that would go out reach-bounded (PVA_OPT_REACH_BOUND) on the large-grid tile (steps per launch 12, tile rows 36: grids from 3072^2): 1 = when the listener's 4-connected air component is walled in and the tile window around it (bounding box + one cell, rounded out to tiles) lies inside the run's history window and fits the device's resident-block budget at that moment, the run's T steps are ONE launch of the resident kernel over that window (three 12-row resident tiles per 36-row tile) instead of T / 12 dependent launches: pressure never crosses a wall cell, so nothing outside the window can become non-zero.  Every other run -- open field, listener inside a wall, window too large, budget taken by runs in flight -- is reach-bounded as before.  Bit-identical.  PvAmdLastRunResidentWindow tells which path the last run took.  -1 = default (on), 0 = off */
     PVA_OPT_DEBUG_LOSE_FIRST_CAPTURE = 24, /* validation: 1 = the solver's first run-graph capture counts as lost (what a legacy-stream operation of another host thread does to it): that run goes out as plain launches, the next one captures again (tests/test_gpu_parity.py) */
     PVA_OPT_PATCH_STRIP = 18,  /* patch columns per strip of the patch kernel's walk over the grid (development; default 3) */
     PVA_OPT_EDGE_TILES = 15    /* 1 = tiles whose only non-air faces are the grid's absorbing edges run the air-tile code + edge overrides (tile class 2) instead of the general path.  Only the batched kernels of the mirror-pair tiles (K, rows = (8,40), (10,36), (12,36)) have that arm -- inside the merged kernel it slows the air tiles by 25-40 %, DESIGN.md 8.4 -- so every run of such a solver goes through PvAmdRunBatch's kernel (PvAmdRun = a batch of one) and PvAmdRunSteps is refused; ignored for other configurations.  Default 0 */
@@ -438,6 +439,15 @@ PVA_EXPORT int PvAmdHostEdgeLayerTables(float gridSizeX, float gridSizeY, int gr
  * r0 = 0.1 gives PvAmdHostEdgeLayerTables' bits.  The tables of PvAmdSetEdgeLayerSplit. */
 PVA_EXPORT int PvAmdHostEdgeLayerTablesR0(float gridSizeX, float gridSizeY, int gridResolution, const int width4[4], double r0,
                                           float* out);
+/* CPU only: the enclosure search of the resident-window runs (PVA_OPT_RESIDENT_WINDOW).  beta[nx * ny] (index x * ny + y, non-zero =
+ * air): the 4-connected air component of cell (seedX, seedY), walked until the tile window around it -- its bounding box grown by
+ * one cell, clipped to the grid, rounded out to tileRows x tileCols-cell tiles -- holds more than maxTiles tiles; at most
+ * maxTiles * tileRows * tileCols cells are visited whatever the grid's size.  out10 = {found, cells visited, box r0, c0, r1, c1
+ * (inclusive), window first tile row, first tile column, tile rows, tile columns}; found = 1: the component was walked completely
+ * (cells = its size) and the window fits; a seed in a wall or outside the grid: found = 0, no cell visited.  Returns the cells
+ * visited, or -1 for bad arguments. */
+PVA_EXPORT int PvAmdHostEnclosure(const uint8_t* beta, int nx, int ny, int seedX, int seedY, int tileRows, int tileCols, int maxTiles,
+                                  int* out10);
 /* CPU only: the four vertices out8 the library uses for that oriented box (0, or -1 for a refused input) */
 PVA_EXPORT int PvAmdHostOrientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float* out8);
 /* CPU only: the shape the library makes of a vertex list (counter-clockwise, out16 gets 2n floats); returns n, or -1 for a
@@ -486,6 +496,9 @@ PVA_EXPORT float PvAmdClockProbe(int device, float* byMemtimeMHz);
  * own; call it on an idle device.  0, or -1 on failure.  bench.py's roofline record. */
 PVA_EXPORT int PvAmdBandwidthProbe(int device, float* gbPerS4);
 PVA_EXPORT int PvAmdGetTimings(PvAmdSolver* s, PvAmdTimings* out);
+/* 1: the last run (PvAmdRun / PvAmdRunAsync + PvAmdSync) went out as one resident-kernel launch over the tile window around the
+ * listener's walled-in air component (PVA_OPT_RESIDENT_WINDOW), 0: by any other path, -1: error.  Results do not depend on it. */
+PVA_EXPORT int PvAmdLastRunResidentWindow(PvAmdSolver* s);
 
 /* Streaming-analysis (sparse-emitter) mode only -- SURVEY.md 8f N3.  Registers the emitter positions (n x {x,y,z})
  * whose wet gain and RT60 the next runs compute; onset, occlusion, lowpass, source directivity and listener direction

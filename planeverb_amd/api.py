@@ -53,6 +53,7 @@ PVA_OPT_XCD_REGIONS = 27
 PVA_OPT_ANALYSIS_FORK = 28
 PVA_OPT_FUSED_ANALYSIS = 29
 PVA_OPT_REACH_BOUND = 30
+PVA_OPT_RESIDENT_WINDOW = 31
 
 
 class PlaneverbOutput(C.Structure):
@@ -200,6 +201,7 @@ SYMBOLS = {
     "PlaneverbSetEdgeLayerSplit": (None, [C.c_int] * 4),
     "PvAmdHostEdgeLayerTablesR0": (C.c_int, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), C.c_double, _fp]),
     "PvAmdHostEdgeLayerTables": (C.c_int, [C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), _fp]),
+    "PvAmdHostEnclosure": (C.c_int, [C.POINTER(C.c_ubyte)] + [C.c_int] * 7 + [C.POINTER(C.c_int)]),
     "PvAmdHostOrientedBoxVertices": (C.c_int, [C.c_float] * 6 + [_fp]),
     "PvAmdHostShape": (C.c_int, [_fp, C.c_int, C.c_float, _fp]),
     "PvAmdHostShapeCoverage": (C.c_int, [C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
@@ -211,6 +213,7 @@ SYMBOLS = {
     "PvAmdSync": (C.c_int, [_vp]),
     "PvAmdRunBatch": (C.c_int, [C.POINTER(_vp), C.c_int, _fp, C.c_int]),
     "PvAmdGetTimings": (C.c_int, [_vp, C.POINTER(PvAmdTimings)]),
+    "PvAmdLastRunResidentWindow": (C.c_int, [_vp]),
     "PvAmdClockProbe": (C.c_float, [C.c_int, _fp]),
     "PvAmdBandwidthProbe": (C.c_int, [C.c_int, _fp]),
     "PvAmdSetEmitters": (C.c_int, [_vp, _fp, C.c_int]),
@@ -603,6 +606,19 @@ def edge_layer_tables(size_x, size_y, res, w4, r0=None):
     return {k: out[o:o + (nx if j < 4 else ny)].copy() for j, (k, o) in enumerate(zip(names, offs))}
 
 
+def host_enclosure(beta, seed, tile_rows=36, tile_cols=40, max_tiles=128):
+    """PvAmdHostEnclosure: the air component of cell `seed` = (x, y) of beta[nx, ny] (non-zero = air) and the tile window around
+    it, as a dict(found, cells, box=(r0, c0, r1, c1), window=(ti0, tj0, tis, tjs)); found = 0 when the seed is no air cell or the
+    window would hold more than max_tiles tiles"""
+    b = np.ascontiguousarray(beta, np.uint8)
+    out = np.zeros(10, np.int32)
+    if lib().PvAmdHostEnclosure(b.ctypes.data_as(C.POINTER(C.c_ubyte)), b.shape[0], b.shape[1], int(seed[0]), int(seed[1]),
+                                int(tile_rows), int(tile_cols), int(max_tiles), out.ctypes.data_as(C.POINTER(C.c_int))) < 0:
+        raise PlaneverbError(last_error())
+    v = [int(x) for x in out]
+    return dict(found=v[0], cells=v[1], box=tuple(v[2:6]), window=tuple(v[6:10]))
+
+
 def load_pv(path, max_boxes=4096):
     """.pv scene -> (n, 5) float32 array of (posX, posY, width, height, absorption)"""
     buf = np.empty((max_boxes, 5), np.float32)
@@ -975,7 +991,7 @@ class Solver:
                 "debug_lose_first_capture": PVA_OPT_DEBUG_LOSE_FIRST_CAPTURE, "stream_priority": PVA_OPT_STREAM_PRIORITY,
                 "alternate_sweeps": PVA_OPT_ALTERNATE_SWEEPS, "xcd_regions": PVA_OPT_XCD_REGIONS,
                 "analysis_fork": PVA_OPT_ANALYSIS_FORK, "fused_analysis": PVA_OPT_FUSED_ANALYSIS,
-                "reach_bound": PVA_OPT_REACH_BOUND}
+                "reach_bound": PVA_OPT_REACH_BOUND, "resident_window": PVA_OPT_RESIDENT_WINDOW}
         for k, v in options.items():
             _check(lib().PvAmdSetOption(self._h, keys[k], int(v)))
         self.info = PvAmdInfo()
@@ -1143,6 +1159,13 @@ class Solver:
 
     def run_steps(self, nsteps, with_pulse=False, listener=(0.0, 0.0, 0.0)):
         _check(lib().PvAmdRunSteps(self._h, int(nsteps), int(with_pulse), float(listener[0]), float(listener[2])))
+
+    def last_run_resident_window(self):
+        """True when the last run went out as one resident-kernel launch over the window around the listener's room"""
+        rc = lib().PvAmdLastRunResidentWindow(self._h)
+        if rc < 0:
+            raise PlaneverbError(last_error())
+        return rc == 1
 
     def timings(self):
         t = PvAmdTimings()

@@ -1,5 +1,7 @@
 // pv_capi.cpp -- extern "C" boundary of libplaneverb_amd.so (declared in include/planeverb_amd.h).
 // No C++ exception leaves this file; the reference's sentinels are kept (-1 ids, occlusion = -1).
+#include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -646,6 +648,7 @@ int PvAmdSetOption(PvAmdSolver* h, int key, long long value) try {
         case PVA_OPT_ALTERNATE_SWEEPS: h->opt.alternateSweeps = (int)value; break;
         case PVA_OPT_XCD_REGIONS: h->opt.xcdRegions = (int)value; break;
         case PVA_OPT_REACH_BOUND: h->opt.reachBound = (int)value; break;
+        case PVA_OPT_RESIDENT_WINDOW: h->opt.residentWindow = (int)value; break;
         default: g_lastError = "unknown option"; return -1;
     }
     return 0;
@@ -1004,6 +1007,11 @@ int PvAmdGetTimings(PvAmdSolver* h, PvAmdTimings* out) try {
     return 0;
 } PV_API_CATCH(-1)
 
+int PvAmdLastRunResidentWindow(PvAmdSolver* h) try {
+    if (!wholeGrid(h) || !ensure(h, true)) return -1;
+    return h->s->lastRunResidentWindow() ? 1 : 0;
+} PV_API_CATCH(-1)
+
 int PvAmdSetEmitters(PvAmdSolver* h, const float* xyz, int n) try {
     if (!wholeGrid(h) || !ensure(h) || (n > 0 && !xyz)) return -1;
     return ret(h, h->s->setEmitters(xyz, n));
@@ -1333,6 +1341,18 @@ int PvAmdHostEdgeLayerTables(float sx, float sy, int res, const int* width4, flo
 
 int PvAmdHostEdgeLayerTablesR0(float sx, float sy, int res, const int* width4, double r0, float* out) try {
     return hostEdgeLayerTables(sx, sy, res, width4, r0, out, "PvAmdHostEdgeLayerTablesR0");
+} PV_API_CATCH(-1)
+
+int PvAmdHostEnclosure(const uint8_t* beta, int nx, int ny, int seedX, int seedY, int tileRows, int tileCols, int maxTiles,
+                       int* out10) try {
+    if (!beta || !out10 || nx < 1 || ny < 1 || tileRows < 1 || tileCols < 1 || (long long)nx * ny > INT_MAX) {
+        g_lastError = "PvAmdHostEnclosure: bad arguments";
+        return -1;
+    }
+    const Enclosure e = findEnclosure(beta, nx, ny, seedX, seedY, tileRows, tileCols, maxTiles, nullptr);
+    const int v[10] = {e.found, e.cells, e.r0, e.c0, e.r1, e.c1, e.ti0, e.tj0, e.tis, e.tjs};
+    std::copy(v, v + 10, out10);
+    return e.cells;
 } PV_API_CATCH(-1)
 
 int PvAmdHostLoadPv(const char* path, float* b5, int maxBoxes) try {

@@ -571,4 +571,76 @@ void edgeLayerTables(int gx, int gy, float courant, const int w4[4], float* out,
     axisTables(gy, w4[2], w4[3], (double)courant, r0, o, o + ny, o + 2 * ny, o + 3 * ny);
 }
 
+Enclosure findEnclosure(const uint8_t* beta, int NX, int NY, int seedX, int seedY, int rxi, int wi, int maxTiles,
+                        std::vector<int>* visited) {
+    Enclosure e{};
+    if (visited) visited->clear();
+    if (seedX < 0 || seedX >= NX || seedY < 0 || seedY >= NY || maxTiles < 1 || !beta[(size_t)seedX * NY + seedY]) return e;
+    const long long cap = (long long)maxTiles * rxi * wi;  // cells of the largest window: no component beyond that fits
+    // the cells seen so far: an open-addressing table sized for the cap (nothing of the grid's size is touched)
+    size_t tab = 1024;
+    while ((long long)tab < 2 * cap + 16) tab <<= 1;
+    std::vector<int> seen(tab, -1);
+    auto mark = [&](int i) {  // true: i was not in the table yet
+        size_t h = ((size_t)(unsigned)i * 2654435761u) & (tab - 1);
+        while (seen[h] >= 0) {
+            if (seen[h] == i) return false;
+            h = (h + 1) & (tab - 1);
+        }
+        seen[h] = i;
+        return true;
+    };
+    std::vector<int> todo;
+    todo.push_back(seedX * NY + seedY);
+    mark(todo[0]);
+    e.r0 = e.r1 = seedX;
+    e.c0 = e.c1 = seedY;
+    bool fits = true;
+    auto window = [&]() {
+        const int lo = std::max(e.r0 - 1, 0), hi = std::min(e.r1 + 1, NX - 1);
+        const int lc = std::max(e.c0 - 1, 0), hc = std::min(e.c1 + 1, NY - 1);
+        e.ti0 = lo / rxi;
+        e.tis = hi / rxi - e.ti0 + 1;
+        e.tj0 = lc / wi;
+        e.tjs = hc / wi - e.tj0 + 1;
+        return (long long)e.tis * e.tjs <= maxTiles;
+    };
+    for (size_t head = 0; head < todo.size() && fits; ++head) {
+        const int i = todo[head], x = i / NY, y = i - x * NY;
+        if (x < e.r0 || x > e.r1 || y < e.c0 || y > e.c1) {
+            e.r0 = std::min(e.r0, x);
+            e.r1 = std::max(e.r1, x);
+            e.c0 = std::min(e.c0, y);
+            e.c1 = std::max(e.c1, y);
+            fits = window();
+        }
+        if (!fits) break;
+        const int nb[4] = {x > 0 ? i - NY : -1, x + 1 < NX ? i + NY : -1, y > 0 ? i - 1 : -1, y + 1 < NY ? i + 1 : -1};
+        for (int j : nb)
+            if (j >= 0 && beta[(size_t)j] && mark(j)) {
+                if ((long long)todo.size() >= cap) {  // one cell more than any window holds
+                    fits = false;
+                    break;
+                }
+                todo.push_back(j);
+            }
+    }
+    // (the queue's cells are all marked air cells of the component; on a give-up the unprocessed ones count as visited too)
+    e.cells = (int)todo.size();
+    for (int i : todo) {
+        const int x = i / NY, y = i - x * NY;
+        e.r0 = std::min(e.r0, x);
+        e.r1 = std::max(e.r1, x);
+        e.c0 = std::min(e.c0, y);
+        e.c1 = std::max(e.c1, y);
+    }
+    const bool w = window();
+    e.found = fits && w ? 1 : 0;
+    if (visited) {
+        std::sort(todo.begin(), todo.end());
+        visited->swap(todo);
+    }
+    return e;
+}
+
 }  // namespace pva

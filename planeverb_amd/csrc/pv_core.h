@@ -168,4 +168,26 @@ struct SegRect {
 };
 std::vector<SegRect> planSegments(const uint8_t* air, int ntx, int nty, int rxi, int wmax, int target);
 
+// Enclosure of a cell (resident-window runs, Solver::windowFor): the 4-connected component of air cells (beta != 0) that
+// holds the seed, as long as the TILE WINDOW around it stays small.  beta: NX x NY cells, index x * NY + y.  The window is
+// the component's bounding box grown by one cell on every side, clipped to the grid and rounded out to rxi x wi-cell tiles
+// (tile (ti, tj) = rows [ti rxi, +rxi) x columns [tj wi, +wi)).  The fill gives up -- found = 0 -- as soon as that window
+// holds more than maxTiles tiles, so it visits at most maxTiles * rxi * wi cells whatever the grid's size; a seed outside
+// the grid or inside a wall gives found = 0 with no cell visited.
+// Why the window bounds a run exactly: the pressure of a non-air cell is identically 0 (beta = 0, FDTD.cpp:139); the face
+// between two non-air cells has coefficient 0; the face between a wall cell and an air cell of ANOTHER component multiplies
+// two pressures that are both zero for the whole run.  In a run whose pulse enters at the seed, non-zero values therefore live
+// only in the component's pressures and in the faces that touch a component cell -- face (x, y) lies between cells (x - 1, y)
+// and (x, y), so those are cell indices [min, max + 1] of the bounding box: inside the one-cell ring.  Grid edges need no
+// special case: they are ordinary face coefficients.
+struct Enclosure {
+    int found;            // 1: the component was walked completely and its window holds <= maxTiles tiles
+    int cells;            // cells visited (found: the component's size)
+    int r0, c0, r1, c1;   // inclusive bounding box of the visited cells
+    int ti0, tj0, tis, tjs;  // the tile window (of the visited cells' box: meaningful when found)
+};
+// visited (optional): the visited cells' indices, ascending
+Enclosure findEnclosure(const uint8_t* beta, int NX, int NY, int seedX, int seedY, int rxi, int wi, int maxTiles,
+                        std::vector<int>* visited);
+
 }  // namespace pva

@@ -205,8 +205,9 @@ struct ResidentArgs {
     float* vy[2];          // the two buffer sets: epoch e reads set e & 1 (nothing for e = 0) and publishes into the other
     const FaceCoef* coef;
     const float* pulse;    // >= T floats
-    float* hist;           // window base (the window is the whole grid), plane stride histPlane
-    int* tileFirst;        // per tile: first step block in which the tile was non-zero (every block resets its own tile's entry)
+    float* hist;           // history window base, plane stride histPlane
+    int* tileFirst;        // per tile of the grid: first step block in which the tile was non-zero (whole-grid runs: every block
+                           // resets its own tile's entry)
     DynParams dynVal;      // the run's parameters, by value: no begin-run launch in front of this kernel (it read them from pinned
                            // host memory, 7-8 us of a 0.3 ms run); block 0 leaves a copy at dynOut for the analysis kernels
     DynParams* dynOut;
@@ -223,6 +224,15 @@ struct ResidentArgs {
     float courant;
     unsigned long long* stamp;  // pinned host words, or NULL: stamp[0] = the 100 MHz counter when the block that holds tile 0 starts
                                 // (Solver::stampTimed_: a run's timings without event packets between its kernels)
+    // Resident window (Solver::enqueueWindowRun): the launch's tiles cover a tile-aligned window of a LARGER grid whose own
+    // tiles are histSub resident tiles high (same columns, same K).  The plane and coefficient pointers above then point at the
+    // window's first cell row / column (planeBytes: what is left of the plane from there) and ntx = histSub x window tile rows.
+    // Whole-grid runs: histSub = 1 and zeros in the rest -- the addressing of the presets.
+    int histSub;           // resident tiles stacked in one tile of the history planes / of the tileFirst table (1 or 3)
+    int winTi0, winTj0;    // the window's first tile in the grid's tile table (history tile height = histSub * RXI)
+    int gridNty;           // tile columns of that table
+    int winRow0, winCol0;  // cells from the grid's origin to the window's (the listener's row / column in dynVal are the grid's)
+    int window;            // 1: tileFirst entries are shared by histSub blocks -- reset before the launch, only atomicMin here
 };
 
 // slab decomposition, neighbours on one device: words in device memory instead of cross-queue events (pv_halo_push_kernel)

@@ -24,6 +24,11 @@
 // block -- only blocks that ARE on the target XCD take part -- and if fewer than ntiles of them turn up there (another
 // dispatch pattern or partition mode) the claim check below gives the run up within milliseconds (errFlag 4) and the host
 // repeats it in the placement-independent mode.
+// WINDOW OF A LARGER GRID (ResidentArgs::window, Solver::enqueueWindowRun): the same kernel over a tile-aligned window of a grid
+// whose own tiles are histSub = 3 of these tiles high -- a run whose listener is walled in.  Only addressing differs, all of it
+// outside the step loop: the plane pointers start at the window, a block's history rows and tileFirst entry are those of the grid
+// tile that holds it (three blocks share an entry: atomicMin only, the host resets the table), the listener's cell is taken
+// relative to the window.  Cells outside the window are zero in both buffer sets and stay zero (no air path leads there).
 // No assumption about dispatch order or workgroup -> XCD placement is made; all blocks must be co-resident (the host caps
 // the grid and keeps a per-device budget), and every wait is bounded: a block that waits longer than ~2 s raises the abort
 // word, every other block leaves at its next wait, and the run fails with an error instead of hanging the device.
@@ -326,11 +331,17 @@ __global__ __launch_bounds__(64 * W) void pv_resident_kernel(const ResidentArgs 
         *a.dynOut = a.dynVal;
         if (a.stamp) a.stamp[0] = wall_clock64();
     }
-    if (threadIdx.x == 0) a.tileFirst[tile] = INT_MAX;  // (only this block ever touches the entry during the run)
+    // the grid tile this block's history rows and tileFirst entry belong to: the block's own tile -- or, in a window of a
+    // larger grid (ResidentArgs::window), the histSub x RXI-row tile that holds it
+    const int hSub = a.histSub, gti = a.winTi0 + ti / hSub, gtj = a.winTj0 + tj;
+    int* const tileFirst = a.tileFirst + (gti * a.gridNty + gtj);
+    // (whole grid: only this block ever touches the entry during the run.  Window: histSub blocks share it -- the host resets it
+    // in front of the launch, and the minimum over the sub-tiles is the tile's value: their loaded regions tile its loaded region)
+    if (threadIdx.x == 0 && !a.window) *tileFirst = INT_MAX;
     // listener row inside this wave's window: rows 0..R-2 hold a live pressure (row 0 = the copy of the previous wave's
     // last row), row R-1 does not
-    const int lr = dyn.lrow - row0;
-    const int lc = dyn.lcol - col0;
+    const int lr = dyn.lrow - a.winRow0 - row0;
+    const int lc = dyn.lcol - a.winCol0 - col0;
     const bool hasL = lr >= 0 && lr <= R - 2 && lc >= 0 && lc < 64;
     // a listener inside a wall: the reference adds the pulse to a pressure that its next sweep zeroes before anything reads it
     // (FDTD.cpp:139,234) -- only the LAST sample survives, in the final field; here a wall cell's pressure must stay 0
@@ -338,12 +349,12 @@ __global__ __launch_bounds__(64 * W) void pv_resident_kernel(const ResidentArgs 
 #pragma unroll
     for (int r = 0; r < R - 1; ++r)
         if (r == lr) lAir = rowGet(cb, r) != 0.f;
-    const int lrT = dyn.lrow - (row0 - ws);
+    const int lrT = dyn.lrow - a.winRow0 - (row0 - ws);
     const bool tileHasL = lrT >= 0 && lrT < Gm::L && lc >= 0 && lc < 64;
-    const int hti = ti - dyn.histTileX0, htj = tj - dyn.histTileY0;  // (the window is the whole grid: host precondition)
+    const int hti = gti - dyn.histTileX0, htj = gtj - dyn.histTileY0;  // (inside the history window: host precondition)
     const bool inCols = lane >= K && lane < 64 - K;
     constexpr int hpitchB = WI * 4;
-    const int hsoff0 = ((hti * dyn.histTilesY + htj) * RXI - K + ws) * hpitchB;
+    const int hsoff0 = (((hti * dyn.histTilesY + htj) * hSub + (ti - (ti / hSub) * hSub)) * RXI - K + ws) * hpitchB;
     const int hvoff = (lane - K) * 4;
     bool seen = false;  // tileFirst[tile] already holds an epoch of this run
 
@@ -407,7 +418,7 @@ __global__ __launch_bounds__(64 * W) void pv_resident_kernel(const ResidentArgs 
                        __float_as_uint(vx[i].y) | __float_as_uint(vy[i].x) | __float_as_uint(vy[i].y)) & 0x7fffffffu;
             if (tileHasL || __ballot(nz != 0u) != 0ull) {
                 seen = true;
-                if (lane == 0) atomicMin(&a.tileFirst[tile], t0);
+                if (lane == 0) atomicMin(tileFirst, t0);
             }
         }
 

@@ -534,7 +534,18 @@ bool Solver::init(const GridSpec& spec, int device, const SolverOptions& opt) {
             residentBudget_ = cap * 3 / 4;  // (an occupancy query and the device properties: once, not per 0.3 ms run)
             if (ntiles > std::min(residentBudget_, kResidentMaxTiles)) useResident_ = false;  // (= the run-time budget of enqueueRun)
         }
-        if (useResident_ && !dalloc(&resFlags_, (size_t)ntiles + 2, true)) return false;
+        resFlagWords_ = useResident_ ? ntiles + 2 : 0;
+        // Resident window: the large-grid tile is three resident tiles high and as wide (64 - 2K columns, the same K halo), so a
+        // tile-aligned window of this grid is a grid of pv_resident_kernel<12, 12> tiles.  Whether a run takes the path is
+        // decided per run (windowFor); the flag words are sized for the largest window it takes.
+        windowOk_ = opt_.residentWindow != 0 && !useResident_ && K_ == 12 && rxi_ == 36 && residentConfigOk(K_, 12) &&
+                    wi_ == 64 - 2 * K_ && kGuard >= K_ + residentExtraRows(K_, 12) && !opt_.streaming && !isSlab() && T_ >= 1;
+        if (windowOk_) {
+            residentBudget_ = residentMaxBlocks(K_, 12, device_) * 3 / 4;
+            resFlagWords_ = std::min(residentBudget_, kResidentMaxTiles) + 2;
+            if (residentBudget_ < 3) windowOk_ = false;
+        }
+        if (resFlagWords_ > 0 && !dalloc(&resFlags_, (size_t)resFlagWords_, true)) return false;
         if (useResident_) {
             static std::atomic<int> turn{0};
             xcdTarget_ = turn.fetch_add(1) & 7;
@@ -1138,6 +1149,10 @@ bool Solver::applyGeometry() {
     }
     // (an update that only changes absorption values -- or re-adds a box where it was -- leaves the air components as they are: no
     // flood fill over the grid, no upload: 15-20 ms of a 1024^2 live iteration with moving absorbers)
+    if (airChanged) {  // (the air components are not what they were: windowFor)
+        enclosures_.clear();
+        windowOff_ = false;
+    }
     if ((airChanged || !labelsValid_) && !makeLabels()) return false;
     mat_.clearDirty();
     geometryDirty_ = false;
@@ -1392,7 +1407,7 @@ void Solver::enqueueBeginRun(bool resetTiles) {
     b.dynBands = dynBandsDev_;
     b.nbands = bandedRun_ ? nb_ : 0;
     b.zeroWords = resFlags_;
-    b.nZero = resFlags_ ? geo_.ntx * geo_.nty + 2 : 0;
+    b.nZero = resFlags_ ? resFlagWords_ : 0;
     launchBeginRun(b, stream_);
 }
 
@@ -1504,6 +1519,93 @@ bool Solver::reachEligible(bool graph, bool small) const {
     return opt_.reachBound != 0 && mergedLaunch && !graph && !small && !useResident_ && !opt_.streaming && !bandedRun_ &&
            !segActive_ && !usePatch_ && !opt_.denseHistory && !opt_.edgeTiles && !isSlab() && opt_.timeKernels == 0 &&
            dynCur_.lrow >= geo_.G && dynCur_.lrow <= geo_.G + g_.gx && dynCur_.lcol >= geo_.G && dynCur_.lcol <= geo_.G + g_.gy;
+}
+
+// Resident window.  The listener's air component, from the cache of this geometry's answers or by a bounded flood fill over the
+// host's copy of beta (findEnclosure, pv_core.cpp: O(component), and never more cells than the largest window holds).  Both
+// answers are kept with the cells they were found for: the bench's eight listeners share one room -- one fill, then a binary
+// search per run -- and a listener that wanders through an open field re-runs the give-up only when it leaves the walked part.
+const Enclosure* Solver::enclosureOf(int lcx, int lcy) {
+    if (lcx < 0 || lcx >= g_.NX || lcy < 0 || lcy >= g_.NY || !betaHost_[(size_t)lcx * g_.NY + lcy]) return nullptr;
+    const int cell = lcx * g_.NY + lcy;
+    for (const EnclosureRec& r : enclosures_)
+        if (lcx >= r.e.r0 && lcx <= r.e.r1 && lcy >= r.e.c0 && lcy <= r.e.c1 && std::binary_search(r.cells.begin(), r.cells.end(), cell))
+            return &r.e;
+    if (enclosures_.size() >= 16) enclosures_.erase(enclosures_.begin());  // (the oldest answer: bounded memory)
+    enclosures_.emplace_back();
+    EnclosureRec& r = enclosures_.back();
+    r.e = findEnclosure(betaHost_.data(), g_.NX, g_.NY, lcx, lcy, rxi_, wi_, std::min(residentBudget_, kResidentMaxTiles) / 3, &r.cells);
+    return &r.e;
+}
+
+// Does the run about to be enqueued (reach-eligible, listener cell (lcx, lcy), dynCur_ set) take the resident-window path?
+// win = {first tile row, tile rows, first tile column, tile columns} of the window.  The device's resident budget is reserved
+// here (residentHeld_): two solvers in flight both reserve, and a run that finds the budget used up goes out reach-bounded.
+bool Solver::windowFor(int lcx, int lcy, int win[4]) {
+    if (!windowOk_ || windowOff_ || layerActive() || x0_ != 0) return false;
+    const Enclosure* e = enclosureOf(lcx, lcy);
+    if (!e || !e->found) return false;
+    const DynParams& d = dynCur_;
+    if (e->ti0 < d.histTileX0 || e->ti0 + e->tis > d.histTileX0 + d.histTilesX || e->tj0 < d.histTileY0 ||
+        e->tj0 + e->tjs > d.histTileY0 + d.histTilesY || e->ti0 + e->tis > geo_.ntx || e->tj0 + e->tjs > geo_.nty)
+        return false;
+    const int blocks = 3 * e->tis * e->tjs;
+    if (blocks > std::min(residentBudget_, kResidentMaxTiles)) return false;
+    std::atomic<int>& inFlight = residentInFlight(device_);
+    if (inFlight.fetch_add(blocks) + blocks > residentBudget_) {
+        inFlight.fetch_sub(blocks);
+        return false;
+    }
+    residentHeld_ = blocks;
+    win[0] = e->ti0;
+    win[1] = e->tis;
+    win[2] = e->tj0;
+    win[3] = e->tjs;
+    return true;
+}
+
+// The T steps of a run as ONE launch of the resident kernel over the tile window `win` (pv_resident.hip, ResidentArgs::window):
+// the same planes, history rows, tileFirst entries and -- through the unchanged analysis -- result maps as the T / K merged
+// launches, which would advance the window's tiles to the same values and everything else from zeros to zeros.
+void Solver::enqueueWindowRun(const int win[4]) {
+    enqueueBeginRun(true);  // the run's parameters, tileFirst = INT_MAX for every tile, flag words and error flag at zero
+    const long long off = (long long)win[0] * rxi_ * geo_.pitch + (long long)win[2] * wi_;  // floats: the window's first cell
+    ResidentArgs ra{};
+    for (int i = 0; i < 2; ++i) {
+        ra.pr[i] = pr_[i] + off;
+        ra.vx[i] = vx_[i] + off;
+        ra.vy[i] = vy_[i] + off;
+    }
+    ra.coef = coef_ + off;
+    ra.pulse = pulseDev_;
+    ra.hist = hist_;
+    ra.tileFirst = tileFirst_;
+    ra.dynVal = dynCur_;
+    ra.dynOut = dynDev_;
+    ra.errFlag = errFlag_;
+    ra.flags = resFlags_;
+    ra.histPlane = histPlane_;
+    ra.planeBytes = ((long long)geo_.rows * geo_.pitch - off) * 4;
+    ra.pitch = geo_.pitch;
+    ra.G = geo_.G;
+    ra.ntx = 3 * win[1];
+    ra.nty = win[3];
+    ra.ntiles = ra.ntx * ra.nty;
+    ra.T = T_;
+    ra.courant = g_.courant;
+    ra.stamp = stampTimed_ ? stampsHost_ : nullptr;
+    ra.histSub = 3;
+    ra.winTi0 = win[0];
+    ra.winTj0 = win[2];
+    ra.gridNty = geo_.nty;
+    ra.winRow0 = win[0] * rxi_;
+    ra.winCol0 = win[2] * wi_;
+    ra.window = 1;
+    if (stampTimed_) stampsHost_[0] = stampsHost_[1] = stampsHost_[2] = 0ull;  // (the previous run has been synced: enqueueRun's head)
+    launchResident(K_, 12, ra, stream_);
+    tim_.stepLaunches = ceilDiv(T_, K_);
+    cur_ = tim_.stepLaunches & 1;  // where T / K launches would leave it
+    for (int i = 0; i < 4; ++i) reachRect_[i] = win[i];  // what the next reach-bounded or window run has to clear
 }
 
 // Before a reach-bounded run: zeros in both buffer sets wherever its launches do not write.  After a run of another path,
@@ -1959,6 +2061,7 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     loopTimed_ = false;
     cur_ = 0;  // the reset clears set 0; a run never depends on the previous run's fields
     stampTimed_ = false;
+    windowRun_ = false;
     if (opt_.streaming) hipEventRecord(ev_[0], stream_);  // (the other paths: below, once it is known whether the run is a resident one)
     // (an explicit tile configuration means "use the tile kernels")
     // The whole-grid-resident kernel wins where a run is a chain of tiny launches even as a replayed graph: measured on
@@ -2056,6 +2159,8 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     // up, this run goes out as the replayed graph instead (never a wait, never a deadlock)
     bool resident = useResident_ && !(small && opt_.resident != 1) && !layerActive();
     releaseResident();  // (a run enqueued without a sync() behind the previous one: its reservation goes back first)
+    int win[4] = {0, 0, 0, 0};
+    windowRun_ = reach && windowFor(lcx, lcy, win);  // (reach-eligible runs never have useResident_)
     if (resident) {
         const int budget = residentBudget_;
         std::atomic<int>& inFlight = residentInFlight(device_);
@@ -2066,9 +2171,13 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
             residentHeld_ = ntiles;
         }
     }
-    stampTimed_ = resident && stampsHost_ != nullptr;
+    stampTimed_ = (resident || windowRun_) && stampsHost_ != nullptr;
     if (!stampTimed_) hipEventRecord(ev_[0], stream_);
-    if (resident) {
+    if (windowRun_) {
+        lastLcx_ = lcx;
+        lastLcy_ = lcy;
+        enqueueWindowRun(win);
+    } else if (resident) {
         // one-XCD mode where the grid fits one XCD's CUs and that XCD is not taken by another solver's run
         bool xcd = xcdOk_ && ntiles <= kResidentXcdMaxTiles;
         if (xcd) {
@@ -2111,6 +2220,8 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
         ra.T = T_;
         ra.courant = g_.courant;
         ra.stamp = stampTimed_ ? stampsHost_ : nullptr;
+        ra.histSub = 1;  // (the grid's tiles are the kernel's: ResidentArgs::window = 0)
+        ra.gridNty = geo_.nty;
         if (stampTimed_) stampsHost_[0] = stampsHost_[1] = stampsHost_[2] = 0ull;  // (the previous run has been synced: enqueueRun's head)
         launchResident(K_, rxi_, ra, stream_);
         tim_.stepLaunches = ceilDiv(T_, K_);
@@ -2174,7 +2285,7 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     // last kernel of the run: the registered queries' outputs and the status words, both into pinned memory
     launchRunFinish(res_, (long long)g_.gx * g_.gy, qCellsHost_, opt_.skipAnalysis ? 0 : numQueries_, qOutHost_, farInfo(), errFlag_,
                     activeCount_, lastRunXcd_ ? resFlags_ + geo_.ntx * geo_.nty + 1 : nullptr, statusHost_, resFlags_,
-                    resFlags_ ? geo_.ntx * geo_.nty + 2 : 0, stampTimed_ ? stampsHost_ : nullptr, stream_);
+                    resFlags_ ? resFlagWords_ : 0, stampTimed_ ? stampsHost_ : nullptr, stream_);
     // (ev_[2] is also what the OTHER solver of a pipelined pair waits for before its carry pass reads this solver's maps: behind
     // the last kernel here, where it delays nothing of this run)
     if (stampTimed_) hipEventRecord(ev_[2], stream_);
@@ -2288,6 +2399,7 @@ bool Solver::runBatch(Solver* const* s, int n, const float* lxyz, bool wait, std
         v.launchCap_ = v.numGeneral_;
         gcap = std::max(gcap, v.numGeneral_);
         v.stampTimed_ = false;
+        v.windowRun_ = false;
         hipEventRecord(v.ev_[0], v.stream_);
         v.enqueueBeginRun(true);
         if (i > 0) {  // the shared step loop starts when every run's parameters are on the device
@@ -2403,6 +2515,7 @@ bool Solver::sync() {
         }
         tim_.stepLoopMs = 0.f;
         if (loopTimed_) hipEventElapsedTime(&tim_.stepLoopMs, ev_[3], ev_[1]);
+        if (windowRun_) tim_.stepLoopMs = tim_.fdtdMs;  // (the one launch is the run's T / K epochs: nothing else between the stamps)
         if (opt_.timeKernels && kevUsed_ > 0) {
             double air = 0, gen = 0;
             const int n = kevUsed_ / 4;
@@ -2452,6 +2565,15 @@ bool Solver::sync() {
                                  "not spread over the XCDs as expected); using the placement-independent hand-off\n");
             return enqueueRun(lastLcx_, lastLcy_, lastLx_, lastLz_) && sync();
         }
+        if (flag == 3 && windowRun_) {
+            // A window run's workgroup waited ~2 s for a neighbour (the device is shared: see below).  The reach-bounded launches
+            // need no co-residency and give the same bits: the run is repeated as such, and so is every run until the geometry
+            // changes.  (reachRect_ is the window: the repeat clears what the aborted launch left.)
+            windowOff_ = true;
+            std::fprintf(stderr, "[planeverb_amd] resident window: a workgroup gave up waiting for its neighbours (the device is "
+                                 "shared?); this solver's runs go out as reach-bounded launches until its geometry changes\n");
+            return enqueueRun(lastLcx_, lastLcy_, lastLx_, lastLz_) && sync();
+        }
         if (flag == 3 && useResident_) {
             // A workgroup waited ~2 s for a neighbour: the blocks were not all on the chip (another process, or a long kernel
             // of the host application, holds CUs -- the per-process budget cannot see those).  The replayed-graph path needs no
@@ -2496,6 +2618,7 @@ bool Solver::runSteps(int nsteps, bool withPulse, float lx, float lz) {
     planesDirty_ = true;
     enqueueBeginRun(false);
     stampTimed_ = false;
+    windowRun_ = false;
     hipEventRecord(ev_[0], stream_);
     if (!enqueueSteps(0, nsteps, withPulse, false)) return false;
     hipEventRecord(ev_[1], stream_);

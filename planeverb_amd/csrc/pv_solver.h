@@ -69,6 +69,9 @@ struct SolverOptions {
                           // dependencies between consecutive sweeps; 0 = auto, 1 = off
     int reachBound = -1;  // PVA_OPT_REACH_BOUND: runs of the plain merged-launch path advance only the tiles the pulse can have
                           // reached by each launch (Solver::setReachArgs); -1 = default (on), 0 = full sweeps, 1 = on
+    int residentWindow = -1;  // PVA_OPT_RESIDENT_WINDOW: a reach-bounded run whose listener is walled in steps only the tile window
+                              // around its air component, in one launch of the resident kernel (Solver::enqueueWindowRun);
+                              // -1 = default (on), 0 = off, 1 = on
 };
 
 struct SolverTimings {
@@ -141,6 +144,7 @@ public:
     int histPitch() const { return histPitch_; }
     const std::string& lastError() const { return err_; }
     bool streamFuse() const { return streamFuse_; }
+    bool lastRunResidentWindow() const { return windowRun_; }
     bool residentKernel() const { return useResident_ && !layerActive(); }  // runs of this solver go through pv_resident_kernel (when the
                                                           // device's resident-block budget allows: else the replayed graph)
     SolverOptions& options() { return opt_; }
@@ -415,6 +419,20 @@ private:
     bool lastRunXcd_ = false;          // the run in flight went out in the one-XCD mode
     int lastLcx_ = 0, lastLcy_ = 0;    // (a run given up by the claim check is repeated in the placement-independent mode)
     void releaseResident();
+    // Resident window: on the large-grid tile a run whose listener's air component is walled in and small goes out
+    // as ONE launch of the resident kernel over the tile window around that component instead of T / K reach-bounded launches
+    bool windowOk_ = false;            // this solver's configuration has the path (init)
+    bool windowOff_ = false;           // a window run was given up (errFlag 3): reach-bounded runs until the geometry changes
+    bool windowRun_ = false;           // the run in flight / the last run took the path
+    int resFlagWords_ = 0;             // words of resFlags_
+    struct EnclosureRec {
+        Enclosure e;
+        std::vector<int> cells;        // ascending cell indices of the component (or of the part walked before the give-up)
+    };
+    std::vector<EnclosureRec> enclosures_;  // answers of findEnclosure for this geometry (dropped when a cell changes between air and wall)
+    const Enclosure* enclosureOf(int lcx, int lcy);
+    bool windowFor(int lcx, int lcy, int win[4]);
+    void enqueueWindowRun(const int win[4]);
     float* scratch_ = nullptr;  // max(3T, NX*NY) floats
     size_t scratchCount_ = 0;
 
