@@ -643,4 +643,61 @@ Enclosure findEnclosure(const uint8_t* beta, int NX, int NY, int seedX, int seed
     return e;
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// which path a run takes (pv_core.h)
+// ----------------------------------------------------------------------------------------------------------------
+
+RunPlan planRun(const PathCaps& c, const PathRun& r) {
+    RunPlan p;
+    p.kind = r.kind;
+    const bool run = r.kind == PathRun::Run;
+    // -- the launch form -------------------------------------------------------------------------------------------
+    // merged: one launch per K steps on one stream (no cross-stream hand-shake); not with the streaming kernel
+    // (a layer: always merged -- setEdgeLayer refused the configurations without a merged kernel)
+    p.oneLaunch = c.stacked || ((c.merged == 1 || r.layerTiles) && c.mergedOk);
+    p.plainMerged = plainMergedLaunch(c);
+    p.layer = r.layerTiles;  // the layer tiles, behind the merged launch on the same stream (disjoint tiles)
+    p.patch = c.usePatch && !r.layerTiles;
+    // the replayed graph: automatic up to 4096 tiles; it holds no timing events, and the sparse-emitter ring is driven from the host
+    const bool graph = !c.timeKernels && !c.streaming && (c.useGraph == 1 || (c.useGraph == 0 && c.ntiles <= 4096));
+    // row bands: a run that is not replayed from a graph, and raw stepping; never the callers that drive the launches themselves
+    // (a layer: one launch per sweep beside the layer launch)
+    const bool bandsWanted = run ? !graph : r.kind == PathRun::Raw;
+    p.banded = bandsWanted && c.bands > 1 && !r.layerActive;
+    p.segments = c.useSeg && !p.banded && !r.layerActive && r.segmentsFound;
+    if (!run) return p;  // (Launches, full sweeps)
+
+    // -- the path --------------------------------------------------------------------------------------------------
+    // (an explicit tile configuration means "use the tile kernels")
+    // The whole-grid-resident kernel wins where a run is a chain of tiny launches even as a replayed graph: measured on
+    // MI355X (profiles/r03_presets.txt) 0.47 vs 0.62 ms at 28^2 and 0.67 vs 0.82 ms at 38^2 -- but 0.81 vs 0.69 ms at 39^2,
+    // 0.88 vs 0.71 ms at the Sandbox's 70^2 and 1.60 vs 0.97 ms at 95^2, where its two barriers per step over 5-9 cells per
+    // thread are slower than the 4-wave general tiles.  auto = up to 1536 array cells; 1 = whenever the grid fits one CU.
+    const bool smallWanted = c.smallGrid == 1 || (c.smallGrid == 0 && c.cells <= 1536);
+    const bool small = smallWanted && !c.explicitTile && !c.timeKernels && c.useGraph != 1 && !c.streaming && c.smallFits &&
+                       c.wholeWindow && !r.layerActive;
+    // reach-bounded (Solver::setReachArgs): the plain merged-launch path of a run whose listener lies inside the grid
+    // (DESIGN.md 4.1); every other path sweeps the grid and leaves fields anywhere
+    p.reach = c.reachBound != 0 && p.plainMerged && !graph && !small && !c.useResident && !c.streaming && !p.banded && !p.segments &&
+              !c.usePatch && !c.denseHistory && !c.edgeTiles && !c.slab && c.timeKernels == 0 && r.listenerInside;
+    // resident kernel: one launch per run; it loses to the small-grid kernel unless asked for by name
+    const bool resident = c.useResident && !(small && c.resident != 1) && !r.layerActive;
+    const StepPath tiles = graph ? StepPath::Graph : StepPath::Launches;
+    if (c.streaming) {
+        p.path = StepPath::Streaming;  // sparse-emitter mode: ring history; forward sums advanced after every `ring` steps
+    } else if (p.reach && c.windowOk && !r.windowOff && !r.layerActive) {
+        p.path = StepPath::Window;     // (reach-eligible runs never have useResident; whether the listener is walled in: the solver)
+    } else if (resident) {
+        p.path = StepPath::Resident;
+    } else if (small) {
+        p.path = StepPath::SmallGrid;
+    } else {
+        p.path = tiles;
+    }
+    p.fallback = p.path == StepPath::Resident ? (small ? StepPath::SmallGrid : tiles)
+                 : (p.path == StepPath::Window || p.path == StepPath::Graph) ? StepPath::Launches
+                                                                             : p.path;
+    return p;
+}
+
 }  // namespace pva

@@ -190,4 +190,71 @@ struct Enclosure {
 Enclosure findEnclosure(const uint8_t* beta, int NX, int NY, int seedX, int seedY, int rxi, int wi, int maxTiles,
                         std::vector<int>* visited);
 
+// ----------------------------------------------------------------------------------------------------------------
+// Which path a run takes ("Which path a run takes").  Solver::init resolves a PathCaps once, every run head
+// (Solver::beginRun) states a PathRun, and planRun -- pure, no device -- answers with the RunPlan the solver keeps for the
+// run in flight.  What needs the device or a counter shared between solvers (the resident budgets, the enclosure lookup, a
+// lost graph capture) is applied to the plan afterwards as a demotion to RunPlan::fallback.  Every path computes the same
+// bits, so no parity test notices a run on the wrong one: tests/test_host_run_plan.py checks this function instead.
+// ----------------------------------------------------------------------------------------------------------------
+struct PathCaps {
+    // the tile configuration's answers (pv_launch.h)
+    bool stacked = false;       // stepConfigStacked
+    bool mergedOk = false;      // mergedConfigOk
+    bool smallFits = false;     // smallGridFits: the whole grid fits one CU's LDS
+    // the options as resolved by init (SolverOptions)
+    int useGraph = 0;           // 0 = auto, 1 = always, 2 = never
+    int smallGrid = 0;          // 0 = auto, 1 = whenever it fits, 2 = never
+    int resident = 0;           // 0 = auto, 1 = also beside the small-grid kernel / with an explicit tile, 2 = never
+    int merged = 1;
+    int reachBound = -1;        // 0 = full sweeps
+    int timeKernels = 0;
+    bool streaming = false, denseHistory = false, edgeTiles = false;
+    bool explicitTile = false;  // K or rxi given by the caller (any non-zero value)
+    // the solver
+    bool slab = false;
+    int ntiles = 0;
+    long long cells = 0;        // NX * NY array cells
+    int bands = 1;              // row bands (1 = none)
+    bool wholeWindow = false;   // the history window is the whole grid
+    // the forms init resolved from all of the above, the device's occupancy answers and the plane size
+    bool useSeg = false, usePatch = false, windowOk = false;
+    bool useResident = false;   // NOT fixed at init like the rest: Solver::sync() clears it for good when a resident run was given up
+};
+
+struct PathRun {
+    enum Kind { Run, Raw, Shared };  // a run of this solver alone; raw stepping (runSteps); a member of a batch or a slab group,
+    Kind kind = Run;                 // whose caller drives the launches: full sweeps, plain launches
+    bool listenerInside = false;     // the pulse enters inside the grid
+    bool layerActive = false;        // an edge layer is set ...
+    bool layerTiles = false;         // ... and has tiles (numLayer > 0)
+    bool windowOff = false;          // a window run was given up on this geometry
+    bool segmentsFound = true;       // false: the run's segment plan came out empty (known once prepareDyn has made it)
+};
+
+enum class StepPath { Streaming, Window, Resident, SmallGrid, Graph, Launches };
+
+struct RunPlan {
+    StepPath path = StepPath::Launches;
+    // what the run goes out as when the device says no: Window -> the reach-bounded launches (no enclosure, budget used up, a
+    // workgroup gave up), Resident -> the small-grid kernel / the replayed graph / launches (budget used up), Graph -> launches
+    // (the capture was lost); = path where nothing can say no
+    StepPath fallback = StepPath::Launches;
+    // the launch form of enqueueSteps
+    bool oneLaunch = false;    // the sweep is one launch per K steps on one stream (else the air kernel, beside the general kernel
+                               // on a second stream where general tiles exist)
+    bool plainMerged = false;  // ... and it is the plain merged kernel of an unstacked tile: what reach, bands and patch require
+    bool banded = false;       // per-band run parameters and lists; the sweep = one launch per row band
+    bool segments = false;     // row-streaming air segments
+    bool patch = false;        // air tiles by the persistent patch kernel
+    bool reach = false;        // only the tiles the pulse can have reached (Window: the planes are cleared as for such a run)
+    bool layer = false;        // the layer launch behind every merged launch
+    PathRun::Kind kind = PathRun::Run;
+    bool oneXcd = false;       // Resident: the one-XCD hand-off (set by the solver: it needs the XCD's budget)
+};
+
+// "the plain merged path": what the patch kernel, row bands and the reach bound require
+inline bool plainMergedLaunch(const PathCaps& c) { return !c.stacked && c.merged == 1 && c.mergedOk; }
+RunPlan planRun(const PathCaps& c, const PathRun& r);
+
 }  // namespace pva

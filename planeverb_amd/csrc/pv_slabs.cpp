@@ -348,15 +348,7 @@ bool SlabGroup::run(float lx, float ly, float lz) {
     for (int s = 0; s < S; ++s) {
         Solver& v = *slabs_[(size_t)s];
         if (!hipOk(hipSetDevice(v.device_), "hipSetDevice")) return false;
-        if (v.pendingTimings_ && !v.sync()) return slabFailed(s);
-        if (!v.applyGeometry() || !v.prepareDyn(lcx, lcy, true, false) || !v.zeroPlanesIfNeeded()) return slabFailed(s);
-        v.lastLx_ = lx;
-        v.lastLz_ = lz;
-        v.tim_.stepLaunches = 0;
-        v.kevUsed_ = 0;
-        v.loopTimed_ = false;
-        v.cur_ = 0;
-        v.launchCap_ = v.numGeneral_;
+        if (!v.beginRun(PathRun::Shared, lcx, lcy, true, lx, lz)) return slabFailed(s);
         hipStreamWaitEvent(v.stream_, rootEv_[0], 0);  // (the previous run's gathers have read this slab's maps)
         v.enqueueBeginRun(true);
     }
@@ -651,15 +643,7 @@ bool SlabRankOps::begin(Solver& v, float lx, float ly, float lz) {
     if (!v.hipOk(hipSetDevice(v.device_), "hipSetDevice")) return false;
     int lcx, lcy;
     listenerCell(v.g_, lx, lz, &lcx, &lcy);
-    if (v.pendingTimings_ && !v.sync()) return false;
-    if (!v.applyGeometry() || !v.prepareDyn(lcx, lcy, true, false) || !v.zeroPlanesIfNeeded()) return false;
-    v.lastLx_ = lx;
-    v.lastLz_ = lz;
-    v.tim_.stepLaunches = 0;
-    v.kevUsed_ = 0;
-    v.loopTimed_ = false;
-    v.cur_ = 0;
-    v.launchCap_ = v.numGeneral_;
+    if (!v.beginRun(PathRun::Shared, lcx, lcy, true, lx, lz)) return false;
     v.enqueueBeginRun(true);
     return v.hipOk(hipGetLastError(), "begin run");
 }

@@ -464,14 +464,33 @@ bool Solver::init(const GridSpec& spec, int device, const SolverOptions& opt) {
     if (!hipOk(hipHostMalloc((void**)&qCellsHost_, kMaxQueries * sizeof(long long)), "hipHostMalloc")) return false;
     if (!hipOk(hipHostMalloc((void**)&qOutHost_, kMaxQueries * 8 * sizeof(float)), "hipHostMalloc")) return false;
     if (!hipOk(hipHostMalloc((void**)&listHost_, sizeof(int) * (size_t)listCap_), "hipHostMalloc")) return false;
-    // row-streaming air segments (opt-in: measured slower than the tile kernels at 4096^2, DESIGN.md 4.11): grids whose
+    // What planRun (pv_core.h) needs of the configuration and the options; the resolved forms follow below
+    caps_.stacked = stepConfigStacked(K_, rxi_);
+    caps_.mergedOk = mergedConfigOk(K_, rxi_);
+    caps_.smallFits = smallGridFits(g_.NX, g_.NY);
+    caps_.useGraph = opt_.useGraph;
+    caps_.smallGrid = opt_.smallGrid;
+    caps_.resident = opt_.resident;
+    caps_.merged = opt_.merged;
+    caps_.reachBound = opt_.reachBound;
+    caps_.timeKernels = opt_.timeKernels;
+    caps_.streaming = opt_.streaming;
+    caps_.denseHistory = opt_.denseHistory;
+    caps_.edgeTiles = opt_.edgeTiles;
+    caps_.explicitTile = opt_.K != 0 || opt_.rxi != 0;
+    caps_.slab = isSlab();
+    caps_.ntiles = ntiles;
+    caps_.cells = (long long)g_.NX * g_.NY;
+    caps_.wholeWindow = histTilesX_ == geo_.ntx && histTilesY_ == geo_.nty;
+    const bool mergedLaunch = plainMergedLaunch(caps_);
+    // row-streaming air segments (opt-in: measured slower than the tile kernels at 4096^2): grids whose
     // configuration has a segment kernel; not with the modes whose launches are cut differently (slabs, row bands,
     // batched / edge-tile kernel, graphs) or record every tile (sparse-emitter ring)
     segWMax_ = segConfigMaxTileColumns(K_, rxi_);
-    useSeg_ = segWMax_ > 0 && opt_.segments > 0 && !opt_.streaming && !isSlab() && !opt_.edgeTiles && opt_.merged == 1 &&
+    caps_.useSeg = segWMax_ > 0 && opt_.segments > 0 && !opt_.streaming && !isSlab() && !opt_.edgeTiles && opt_.merged == 1 &&
               opt_.timeKernels == 0 && opt_.useGraph != 1 && (opt_.useGraph == 2 || ntiles > 4096) &&
               plane * 12 <= (size_t)INT_MAX;
-    if (useSeg_) {
+    if (caps_.useSeg) {
         segCap_ = 2 * ntiles + 8;
         if (!dalloc(&segList_, (size_t)segCap_, true)) return false;
         if (!hipOk(hipHostMalloc((void**)&segHost_, sizeof(SegDesc) * (size_t)segCap_), "hipHostMalloc")) return false;
@@ -480,12 +499,11 @@ bool Solver::init(const GridSpec& spec, int device, const SolverOptions& opt) {
     // Persistent patch kernel for the air tiles (pv_patch.h): the large-grid tile only; one descriptor spans a buffer
     // set's three planes, so they must fit 31 bits
     {
-        const bool mergedLaunch = !stepConfigStacked(K_, rxi_) && opt_.merged == 1 && mergedConfigOk(K_, rxi_);
         int want = opt_.patch;
         if (want < 0) want = kDefaultPatch;
-        usePatch_ = want > 0 && patchConfigOk(K_, rxi_) && mergedLaunch && opt_.packed && !opt_.streaming && !isSlab() &&
-                    !opt_.edgeTiles && opt_.timeKernels == 0 && !useSeg_ && plane * 12 <= (size_t)INT_MAX;
-        if (usePatch_) {
+        caps_.usePatch = want > 0 && patchConfigOk(K_, rxi_) && mergedLaunch && opt_.packed && !opt_.streaming && !isSlab() &&
+                    !opt_.edgeTiles && opt_.timeKernels == 0 && !caps_.useSeg && plane * 12 <= (size_t)INT_MAX;
+        if (caps_.usePatch) {
             hipDeviceProp_t prop;
             if (!hipOk(hipGetDeviceProperties(&prop, device_), "hipGetDeviceProperties")) return false;
             patchBlocks_ = std::max(8, prop.multiProcessorCount / 8 * 8);
@@ -497,13 +515,12 @@ bool Solver::init(const GridSpec& spec, int device, const SolverOptions& opt) {
 
     // Row bands (see enqueueSteps): worth it where a sweep is thousands of tiles; measured on MI355X at 4096^2 / 8192^2
     {
-        const bool mergedLaunch = !stepConfigStacked(K_, rxi_) && opt_.merged == 1 && mergedConfigOk(K_, rxi_);
         int want = opt_.rowBands;
         if (want == 0) want = kAutoRowBands;
         if (!mergedLaunch || opt_.streaming || opt_.edgeTiles || opt_.timeKernels > 0) want = 1;
         // a band must be tall enough that only ADJACENT bands share halos: >= 2 tile rows each
         want = std::max(1, std::min(want, geo_.ntx / 2));
-        nb_ = want;
+        nb_ = caps_.bands = want;
         bandRow_.resize((size_t)nb_ + 1);
         for (int b = 0; b <= nb_; ++b) bandRow_[(size_t)b] = (int)((long long)geo_.ntx * b / nb_);
         bandStream_.assign((size_t)nb_, stream_);
@@ -526,27 +543,29 @@ bool Solver::init(const GridSpec& spec, int device, const SolverOptions& opt) {
     {
         const bool explicitTile = opt.K > 0 || opt.rxi > 0;
         const bool wanted = opt_.resident == 1 || (opt_.resident == 0 && !explicitTile && opt_.useGraph != 1);
-        useResident_ = wanted && residentConfigOk(K_, rxi_) && !opt_.streaming && !isSlab() && opt_.timeKernels == 0 &&
-                       !opt_.denseHistory && !opt_.edgeTiles && opt_.merged == 1 && histTilesX_ == geo_.ntx &&
-                       histTilesY_ == geo_.nty && kGuard >= K_ + residentExtraRows(K_, rxi_) && T_ >= 1;
-        if (useResident_) {
+        bool& useResident = caps_.useResident;
+        useResident = wanted && residentConfigOk(K_, rxi_) && !opt_.streaming && !isSlab() && opt_.timeKernels == 0 &&
+                       !opt_.denseHistory && !opt_.edgeTiles && opt_.merged == 1 && caps_.wholeWindow &&
+                      kGuard >= K_ + residentExtraRows(K_, rxi_) && T_ >= 1;
+        if (useResident) {
             const int cap = residentMaxBlocks(K_, rxi_, device_);
             residentBudget_ = cap * 3 / 4;  // (an occupancy query and the device properties: once, not per 0.3 ms run)
-            if (ntiles > std::min(residentBudget_, kResidentMaxTiles)) useResident_ = false;  // (= the run-time budget of enqueueRun)
+            if (ntiles > std::min(residentBudget_, kResidentMaxTiles)) useResident = false;  // (= the run-time budget of enqueueRun)
         }
-        resFlagWords_ = useResident_ ? ntiles + 2 : 0;
+        resFlagWords_ = useResident ? ntiles + 2 : 0;
         // Resident window: the large-grid tile is three resident tiles high and as wide (64 - 2K columns, the same K halo), so a
         // tile-aligned window of this grid is a grid of pv_resident_kernel<12, 12> tiles.  Whether a run takes the path is
         // decided per run (windowFor); the flag words are sized for the largest window it takes.
-        windowOk_ = opt_.residentWindow != 0 && !useResident_ && K_ == 12 && rxi_ == 36 && residentConfigOk(K_, 12) &&
+        bool& windowOk = caps_.windowOk;
+        windowOk = opt_.residentWindow != 0 && !useResident && K_ == 12 && rxi_ == 36 && residentConfigOk(K_, 12) &&
                     wi_ == 64 - 2 * K_ && kGuard >= K_ + residentExtraRows(K_, 12) && !opt_.streaming && !isSlab() && T_ >= 1;
-        if (windowOk_) {
+        if (windowOk) {
             residentBudget_ = residentMaxBlocks(K_, 12, device_) * 3 / 4;
             resFlagWords_ = std::min(residentBudget_, kResidentMaxTiles) + 2;
-            if (residentBudget_ < 3) windowOk_ = false;
+            if (residentBudget_ < 3) windowOk = false;
         }
         if (resFlagWords_ > 0 && !dalloc(&resFlags_, (size_t)resFlagWords_, true)) return false;
-        if (useResident_) {
+        if (useResident) {
             static std::atomic<int> turn{0};
             xcdTarget_ = turn.fetch_add(1) & 7;
             // (validation: an XCD that does not exist -- the first run is then given up by the claim check and repeated)
@@ -593,7 +612,7 @@ bool Solver::init(const GridSpec& spec, int device, const SolverOptions& opt) {
     // the device / partition mode, found out by a run that fails its claim check (errFlag 4) and is repeated in sync().  Find it out
     // HERE, with a throw-away run of the stencil alone: the live module publishes a run's results before it calls sync(), and its
     // first iteration on each solver would otherwise publish the aborted run's (silent) maps.
-    if (useResident_ && xcdOk_ && ntiles <= kResidentXcdMaxTiles && !opt_.skipAnalysis) {
+    if (caps_.useResident && xcdOk_ && ntiles <= kResidentXcdMaxTiles && !opt_.skipAnalysis) {
         opt_.skipAnalysis = true;
         const bool ok = enqueueRun(g_.gx / 2, g_.gy / 2, 0.f, 0.f) && sync();
         opt_.skipAnalysis = false;
@@ -644,7 +663,7 @@ Solver::~Solver() {
     if (idleHost_) hipHostFree(idleHost_);
     releaseResident();
 #ifdef PV_RESIDENT_TRACE
-    if (useResident_) residentDumpTrace();
+    if (caps_.useResident) residentDumpTrace();
 #endif
     if (resFlags_) hipFree(resFlags_);
     if (layerList_) hipFree(layerList_);
@@ -1269,8 +1288,7 @@ int Solver::globalWindowTileRow0(int lcx) const {
     return std::min(std::max(floorDiv(std::min(std::max(lcx, 0), g_.gx) - reach, rxi_), 0), ntxG_ - histTilesXG_);
 }
 
-bool Solver::prepareDyn(int lcx, int lcy, bool withPulse, bool banded) {
-    bandedRun_ = banded && nb_ > 1 && !layerActive();  // (a layer: one launch per sweep beside the layer launch)
+bool Solver::prepareDyn(int lcx, int lcy, bool withPulse) {
     DynParams d{};
     const bool inside = withPulse && lcx >= 0 && lcx <= g_.gx && lcy >= 0 && lcy <= g_.gy;
     d.lrow = inside ? lcx - x0_ + geo_.G : -100000;  // (a slab: possibly far outside its own rows)
@@ -1315,13 +1333,11 @@ bool Solver::prepareDyn(int lcx, int lcy, bool withPulse, bool banded) {
     dynHost_->numGeneral = n;
     if (const char* v = getenv("PLANEVERB_AMD_VERBOSE"); v && atoi(v) > 0)
         std::fprintf(stderr, "[planeverb_amd] %d x %d tiles (K %d, %d rows): %d general, %d dead\n", geo_.ntx, geo_.nty, K_, rxi_, n, numDead_);
-    segActive_ = useSeg_ && !bandedRun_ && !layerActive();
     numSeg_ = 0;
-    if (segActive_) buildSegments(n);
-    segActive_ = segActive_ && numSeg_ > 0;
+    if (plan_.segments) buildSegments(n);  // (none came out: beginRun plans again)
     dynCur_.numSeg = numSeg_;
     dynHost_->numSeg = numSeg_;
-    if (bandedRun_) {
+    if (plan_.banded) {
         // the list, band by band, as LOCAL tile ids of each band's own tile-row range; each band gets its own view of
         // the run parameters (the kernels then see a grid that starts at the band's first tile row)
         std::vector<int> all(listHost_, listHost_ + n);
@@ -1400,12 +1416,12 @@ void Solver::enqueueBeginRun(bool resetTiles) {
     b.ntiles = geo_.ntx * geo_.nty;
     b.tileFirstInit = opt_.denseHistory ? 0 : INT_MAX;
     b.listCap = listCap_;
-    b.segHost = segActive_ ? segHost_ : nullptr;
+    b.segHost = plan_.segments ? segHost_ : nullptr;
     b.seg = segList_;
     b.segCap = segCap_;
-    b.dynBandsHost = bandedRun_ ? dynBandsHost_ : nullptr;
+    b.dynBandsHost = plan_.banded ? dynBandsHost_ : nullptr;
     b.dynBands = dynBandsDev_;
-    b.nbands = bandedRun_ ? nb_ : 0;
+    b.nbands = plan_.banded ? nb_ : 0;
     b.zeroWords = resFlags_;
     b.nZero = resFlags_ ? resFlagWords_ : 0;
     launchBeginRun(b, stream_);
@@ -1424,8 +1440,8 @@ StepArgs Solver::baseStepArgs(bool withPulse, bool record) const {
     a.tileDead = (record && numDead_ > 0) ? tileDead_ : nullptr;
     a.generalList = generalList_;
     a.numGeneral = launchCap_;
-    a.segList = segActive_ ? segList_ : nullptr;
-    a.numSeg = segActive_ ? numSeg_ : 0;
+    a.segList = plan_.segments ? segList_ : nullptr;
+    a.numSeg = plan_.segments ? numSeg_ : 0;
     a.dyn = dynDev_;
     a.tileOpen = opt_.streaming ? tileOpen_ : nullptr;
     a.errFlag = errFlag_;
@@ -1505,20 +1521,12 @@ void Solver::setReachArgs(StepArgs& a, int t0) {
     a.reachCol = lcol;
     a.winTi0 = ti0;
     a.winTj0 = tj0;
-    a.winTis = ti1 - ti0 + 1;  // (>= 1: the listener lies inside the grid, reachEligible)
+    a.winTis = ti1 - ti0 + 1;  // (>= 1: the listener lies inside the grid, planRun)
     a.winTjs = tj1 - tj0 + 1;
     reachRect_[0] = ti0;
     reachRect_[1] = a.winTis;
     reachRect_[2] = tj0;
     reachRect_[3] = a.winTjs;
-}
-
-// the plain merged-launch path of a run whose listener lies inside the grid; every other path sweeps the grid
-bool Solver::reachEligible(bool graph, bool small) const {
-    const bool mergedLaunch = !stepConfigStacked(K_, rxi_) && opt_.merged == 1 && mergedConfigOk(K_, rxi_);
-    return opt_.reachBound != 0 && mergedLaunch && !graph && !small && !useResident_ && !opt_.streaming && !bandedRun_ &&
-           !segActive_ && !usePatch_ && !opt_.denseHistory && !opt_.edgeTiles && !isSlab() && opt_.timeKernels == 0 &&
-           dynCur_.lrow >= geo_.G && dynCur_.lrow <= geo_.G + g_.gx && dynCur_.lcol >= geo_.G && dynCur_.lcol <= geo_.G + g_.gy;
 }
 
 // Resident window.  The listener's air component, from the cache of this geometry's answers or by a bounded flood fill over the
@@ -1538,11 +1546,21 @@ const Enclosure* Solver::enclosureOf(int lcx, int lcy) {
     return &r.e;
 }
 
-// Does the run about to be enqueued (reach-eligible, listener cell (lcx, lcy), dynCur_ set) take the resident-window path?
+// A run's blocks out of a budget the solvers of a device share, into *held until releaseResident().  Never a wait: a run that
+// finds the budget used up by concurrent runs is demoted to its plan's fallback.
+static bool reserveBlocks(std::atomic<int>& inFlight, int blocks, int budget, int* held) {
+    if (inFlight.fetch_add(blocks) + blocks > budget) {
+        inFlight.fetch_sub(blocks);
+        return false;
+    }
+    *held = blocks;
+    return true;
+}
+
+// Is the listener of the run about to be enqueued (planned for the window path, listener cell (lcx, lcy), dynCur_ set) walled in?
 // win = {first tile row, tile rows, first tile column, tile columns} of the window.  The device's resident budget is reserved
 // here (residentHeld_): two solvers in flight both reserve, and a run that finds the budget used up goes out reach-bounded.
 bool Solver::windowFor(int lcx, int lcy, int win[4]) {
-    if (!windowOk_ || windowOff_ || layerActive() || x0_ != 0) return false;
     const Enclosure* e = enclosureOf(lcx, lcy);
     if (!e || !e->found) return false;
     const DynParams& d = dynCur_;
@@ -1551,12 +1569,7 @@ bool Solver::windowFor(int lcx, int lcy, int win[4]) {
         return false;
     const int blocks = 3 * e->tis * e->tjs;
     if (blocks > std::min(residentBudget_, kResidentMaxTiles)) return false;
-    std::atomic<int>& inFlight = residentInFlight(device_);
-    if (inFlight.fetch_add(blocks) + blocks > residentBudget_) {
-        inFlight.fetch_sub(blocks);
-        return false;
-    }
-    residentHeld_ = blocks;
+    if (!reserveBlocks(residentInFlight(device_), blocks, residentBudget_, &residentHeld_)) return false;
     win[0] = e->ti0;
     win[1] = e->tis;
     win[2] = e->tj0;
@@ -1569,7 +1582,21 @@ bool Solver::windowFor(int lcx, int lcy, int win[4]) {
 // launches, which would advance the window's tiles to the same values and everything else from zeros to zeros.
 void Solver::enqueueWindowRun(const int win[4]) {
     enqueueBeginRun(true);  // the run's parameters, tileFirst = INT_MAX for every tile, flag words and error flag at zero
-    const long long off = (long long)win[0] * rxi_ * geo_.pitch + (long long)win[2] * wi_;  // floats: the window's first cell
+    launchResidentRun(12, win);
+    for (int i = 0; i < 4; ++i) reachRect_[i] = win[i];  // what the next reach-bounded or window run has to clear
+}
+
+void Solver::launchResidentRun(int tileRows, const int* win) {
+    if (stampTimed()) stampsHost_[0] = stampsHost_[1] = stampsHost_[2] = 0ull;  // (the previous run has been synced: beginRun)
+    launchResident(K_, tileRows, residentArgs(win), stream_);
+    tim_.stepLaunches = ceilDiv(T_, K_);
+    cur_ = tim_.stepLaunches & 1;  // where T / K launches would leave it
+}
+
+// The arguments of the resident kernel for the whole grid (win = nullptr: the grid's tiles are the kernel's) or for the tile window
+// win = {first tile row, tile rows, first tile column, tile columns}, whose tiles are three resident tiles high.
+ResidentArgs Solver::residentArgs(const int* win) const {
+    const long long off = win ? (long long)win[0] * rxi_ * geo_.pitch + (long long)win[2] * wi_ : 0;  // floats: the first cell
     ResidentArgs ra{};
     for (int i = 0; i < 2; ++i) {
         ra.pr[i] = pr_[i] + off;
@@ -1584,28 +1611,28 @@ void Solver::enqueueWindowRun(const int win[4]) {
     ra.dynOut = dynDev_;
     ra.errFlag = errFlag_;
     ra.flags = resFlags_;
+    ra.xcdMode = plan_.oneXcd ? 1 : 0;
+    ra.xcdTarget = win ? 0 : xcdTarget_;
     ra.histPlane = histPlane_;
     ra.planeBytes = ((long long)geo_.rows * geo_.pitch - off) * 4;
     ra.pitch = geo_.pitch;
     ra.G = geo_.G;
-    ra.ntx = 3 * win[1];
-    ra.nty = win[3];
+    ra.ntx = win ? 3 * win[1] : geo_.ntx;
+    ra.nty = win ? win[3] : geo_.nty;
     ra.ntiles = ra.ntx * ra.nty;
     ra.T = T_;
     ra.courant = g_.courant;
-    ra.stamp = stampTimed_ ? stampsHost_ : nullptr;
-    ra.histSub = 3;
-    ra.winTi0 = win[0];
-    ra.winTj0 = win[2];
+    ra.stamp = stampTimed() ? stampsHost_ : nullptr;
+    ra.histSub = win ? 3 : 1;
     ra.gridNty = geo_.nty;
-    ra.winRow0 = win[0] * rxi_;
-    ra.winCol0 = win[2] * wi_;
-    ra.window = 1;
-    if (stampTimed_) stampsHost_[0] = stampsHost_[1] = stampsHost_[2] = 0ull;  // (the previous run has been synced: enqueueRun's head)
-    launchResident(K_, 12, ra, stream_);
-    tim_.stepLaunches = ceilDiv(T_, K_);
-    cur_ = tim_.stepLaunches & 1;  // where T / K launches would leave it
-    for (int i = 0; i < 4; ++i) reachRect_[i] = win[i];  // what the next reach-bounded or window run has to clear
+    if (win) {
+        ra.winTi0 = win[0];
+        ra.winTj0 = win[2];
+        ra.winRow0 = win[0] * rxi_;
+        ra.winCol0 = win[2] * wi_;
+        ra.window = 1;
+    }
+    return ra;
 }
 
 // Before a reach-bounded run: zeros in both buffer sets wherever its launches do not write.  After a run of another path,
@@ -1636,8 +1663,6 @@ bool Solver::clearReachPlanes() {
     for (int& v : reachRect_) v = 0;
     return hipOk(hipGetLastError(), "plane clear");
 }
-
-bool Solver::bandsActive() const { return bandedRun_; }
 
 // the launch arguments of band b: the same kernels, shown a grid that starts at the band's first tile row
 StepArgs Solver::bandStepArgs(const StepArgs& a, int b) const {
@@ -1674,10 +1699,8 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
     // listener: few tiles, latency-bound) concurrently on stream2_.  Both read buffer set `cur` and write disjoint
     // tiles of the other set, so launch i+1 of EITHER kernel must wait for launch i of BOTH (RAW on the halos it
     // reads, WAR on the tiles it overwrites): one event per kernel per launch.
-    // merged: one launch per K steps on one stream (no cross-stream hand-shake); not with the streaming kernel
-    // (a layer: always merged -- setEdgeLayer refused the configurations without a merged kernel)
-    const bool mergedLaunch =
-        stepConfigStacked(K_, rxi_) || ((opt_.merged == 1 || numLayer_ > 0) && mergedConfigOk(K_, rxi_));
+    // merged (planRun): one launch per K steps on one stream (no cross-stream hand-shake)
+    const bool mergedLaunch = plan_.oneLaunch;
     const bool two = launchCap_ > 0 && !mergedLaunch;
     const int nl = ceilDiv(nsteps, K_);
     if (two) {
@@ -1698,7 +1721,7 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
     // purpose: as nodes of a replayed graph the three large plane memsets were observed to be skipped after a
     // hipDeviceSynchronize on ROCm 7.0's runtime.)
     (void)fromZero;
-    if (mergedLaunch && bandsActive()) {
+    if (mergedLaunch && plan_.banded) {
         // Row bands: sweep n of band b reads buffer set A (its own rows + K halo rows of bands b-1, b+1) and writes its
         // rows of set B.  So sweep n+1 of band b -- which reads set B around band b and overwrites set A's rows of band b
         // -- may start as soon as sweep n of bands b-1, b, b+1 is complete: its own stream orders it behind band b, two
@@ -1731,7 +1754,7 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
     while (done < nsteps) {
         const int k = std::min(K_, nsteps - done);
         setLaunchArgs(a, firstStep + done, k, fromZero && done == 0, li);
-        if (reachRun_) setReachArgs(a, firstStep + done);
+        if (plan_.reach) setReachArgs(a, firstStep + done);
         if (opt_.timeKernels > 0) {  // 4 timing events per sampled launch: air begin/end on stream_, general begin/end
             while ((int)kev_.size() < kevUsed_ + 4) {
                 hipEvent_t e;
@@ -1781,7 +1804,7 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
                     hipEventRecord(openEv_[2 + (li & 1)], openStream_);
                     openPending_ = true;
                 }
-            } else if (usePatch_ && numLayer_ == 0) {
+            } else if (plan_.patch) {
                 // general tiles in their 4-wave blocks, then the air tiles by the resident workgroups (disjoint tiles of
                 // the same output set; neither reads what the other writes)
                 launchStep(K_, rxi_, a, stream_, 16);
@@ -1789,7 +1812,7 @@ bool Solver::enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record
             } else {
                 launchStep(K_, rxi_, a, stream_, stepWhich_);
             }
-            if (numLayer_ > 0) {  // the layer tiles, behind the merged launch on the same stream (disjoint tiles)
+            if (plan_.layer) {  // the layer tiles, behind the merged launch on the same stream (disjoint tiles)
                 LayerArgs l{};
                 l.a = a;
                 l.list = layerList_;
@@ -1927,7 +1950,7 @@ AnalyzeArgs Solver::analyzeArgs(float lx, float lz) const {
     listenerCellRecip(g_, lx, lz, &a.lcx, &a.lcy);
     a.lazyFar = lazyFar_ ? 1 : 0;
     a.labels = labelDev_;
-    a.stamp = stampTimed_ ? stampsHost_ : nullptr;
+    a.stamp = stampTimed() ? stampsHost_ : nullptr;
     a.labelNY = g_.NY;
     a.wholeWindow = (!isSlab() && !opt_.streaming && histTilesX_ == geo_.ntx && histTilesY_ == geo_.nty) ? 1 : 0;
     a.prevR0 = farWin_.r0;
@@ -2043,268 +2066,230 @@ void Solver::enqueueAnalysis(float lx, float lz) {
     nearBoxValid_ = a.box != nullptr;
 }
 
-bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
-    const auto inUse = queue_.lockUse();  // (against another solver's creation probing this stream: QueueClaim::use)
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+// The head of every run (run, runBatch, runSteps, SlabGroup::run, SlabRankOps::begin).  Raw stepping goes on from the caller's
+// fields: nothing is cleared, the buffer set and the run's listener stay.
+bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
     if (!applyGeometry()) return false;
-    const int ntiles = geo_.ntx * geo_.nty;
-    const bool graph = !opt_.timeKernels && !opt_.streaming &&
-                       (opt_.useGraph == 1 || (opt_.useGraph == 0 && ntiles <= 4096));
-    if (!prepareDyn(lcx, lcy, true, /*banded=*/!graph)) return false;
+    PathRun r;
+    r.kind = kind;
+    r.listenerInside = withPulse && lcx >= 0 && lcx <= g_.gx && lcy >= 0 && lcy <= g_.gy;
+    r.layerActive = layerActive();
+    r.layerTiles = numLayer_ > 0;
+    r.windowOff = windowOff_;
+    plan_ = planRun(caps_, r);
+    if (!prepareDyn(lcx, lcy, withPulse)) return false;
+    if (plan_.segments && numSeg_ == 0) {
+        r.segmentsFound = false;
+        plan_ = planRun(caps_, r);
+    }
+    tim_.stepLaunches = 0;
+    kevUsed_ = 0;
+    launchCap_ = numGeneral_;
+    if (kind == PathRun::Raw) {
+        planesDirty_ = true;
+        return true;
+    }
     if (!zeroPlanesIfNeeded()) return false;
     lastLx_ = lx;
     lastLz_ = lz;
-    tim_.stepLaunches = 0;
-    kevUsed_ = 0;
-    loopTimed_ = false;
     cur_ = 0;  // the reset clears set 0; a run never depends on the previous run's fields
-    stampTimed_ = false;
-    windowRun_ = false;
-    if (opt_.streaming) hipEventRecord(ev_[0], stream_);  // (the other paths: below, once it is known whether the run is a resident one)
-    // (an explicit tile configuration means "use the tile kernels")
-    // The whole-grid-resident kernel wins where a run is a chain of tiny launches even as a replayed graph: measured on
-    // MI355X (profiles/r03_presets.txt) 0.47 vs 0.62 ms at 28^2 and 0.67 vs 0.82 ms at 38^2 -- but 0.81 vs 0.69 ms at 39^2,
-    // 0.88 vs 0.71 ms at the Sandbox's 70^2 and 1.60 vs 0.97 ms at 95^2, where its two barriers per step over 5-9 cells per
-    // thread are slower than the 4-wave general tiles.  auto = up to 1536 array cells; 1 = whenever the grid fits one CU.
-    const bool smallWanted = opt_.smallGrid == 1 || (opt_.smallGrid == 0 && (long long)g_.NX * g_.NY <= 1536);
-    const bool small = smallWanted && opt_.K == 0 && opt_.rxi == 0 && !opt_.timeKernels &&
-                       opt_.useGraph != 1 && !opt_.streaming && smallGridFits(g_.NX, g_.NY) &&
-                       histTilesX_ == geo_.ntx && histTilesY_ == geo_.nty && !layerActive();
-    // reach-bounded (setReachArgs): the plain merged-launch path below; every other path leaves fields anywhere
-    const bool reach = reachEligible(graph, small);
-    if (reach) {
-        if (!clearReachPlanes()) return false;
-    } else {
-        sweptDirty_ = true;
-    }
-    if (opt_.streaming) {
-        // sparse-emitter mode: ring history; forward sums advanced after every `ring_` steps
-        const size_t nres = (size_t)g_.gx * g_.gy;
-        if (!hipOk(hipMemsetAsync(sOnset_, 0xff, nres * 4, stream_), "state reset")) return false;  // onset = -1
-        for (float* p : sState_)
-            if (!hipOk(hipMemsetAsync(p, 0, nres * 4, stream_), "state reset")) return false;
-        if (numEmitters_ > 0 &&
-            !hipOk(hipMemsetAsync(emTrace_, 0, (size_t)numEmitters_ * T_ * 4, stream_), "trace reset"))
-            return false;
-        if (streamFuse_ && (!hipOk(hipMemsetAsync(cellsOpen2_, 1, (size_t)2 * ntiles, stream_), "open flags") ||
-                            !hipOk(hipMemsetAsync(openCount_, 0, 2 * sizeof(int), stream_), "open count")))
-            return false;
-        launchCap_ = numGeneral_;
-        enqueueBeginRun(true);
-        if (streamFuse_) {
-            // what is left to the ring and the accumulate pass: the run's general list (walls, edges, the tiles whose loaded
-            // region holds the listener: prepareDyn) and the tiles of the registered emitters -- the complement of
-            // fusedTile() (pv_stream.h)
-            std::vector<uint8_t> in((size_t)ntiles, 0);
-            int n = 0;
-            auto add = [&](int t) {
-                if (!in[(size_t)t]) {
-                    in[(size_t)t] = 1;
-                    ringHost_[n++] = t;
-                }
-            };
-            for (int i = 0; i < numGeneral_; ++i) add(listHost_[i]);
-            for (int t = 0; t < ntiles; ++t)
-                if (tileClassHost_[(size_t)t] != 0 || (t < (int)emTilesHost_.size() && emTilesHost_[(size_t)t])) add(t);
-            numRing_ = n;
-            if (n > 0 && !hipOk(hipMemcpyAsync(ringList_, ringHost_, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream_),
-                                "ring list"))
-                return false;
-        }
-        AnalyzeArgs aa = analyzeArgs(lx, lz);
-        if (streamEv_[0] == nullptr)
-            for (auto& e : streamEv_)
-                if (!hipOk(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) return false;
-        // Half h of the ring: [steps fill it on stream_] -> stepDone[h] -> [accumulate pass on stream2_] -> accDone[h] ->
-        // [steps may overwrite it].  The passes stay in order on stream2_ (they carry per-cell state from one to the next);
-        // the per-tile "history still wanted" flags they produce reach the step kernels half a ring later than in a serial
-        // schedule, which only means a tile may record a few planes nobody reads.
-        int pass = 0;
-        fuseIdle_ = false;
-        if (streamFuse_) idleHost_[0] = idleHost_[1] = 0;
-        for (int tA = 0; tA < T_; tA += halfRing_, ++pass) {
-            const int n = std::min(halfRing_, T_ - tA), h = pass & 1;
-            if (streamFuse_ && !fuseIdle_ && pass >= 2) {
-                // Feedback from the device, two passes old (the GPU keeps pass - 1 queued while the host waits here): once
-                // every fused tile has closed for good -- the wave front has passed and the dry windows behind it are over,
-                // a third of the way into a Mode B run -- the rest of the run needs neither the classify pass nor the
-                // open-tile kernel, i.e. one launch per sweep instead of three.
-                if (!hipOk(hipEventSynchronize(streamEv_[2 + h]), "pass sync")) return false;
-                fuseIdle_ = idleHost_[h] != 0;
-            }
-            if (pass >= 2) hipStreamWaitEvent(stream_, streamEv_[2 + h], 0);
-            if (!enqueueSteps(tA, n, true, true, tA == 0)) return false;
-            hipEventRecord(streamEv_[h], stream_);
-            hipStreamWaitEvent(stream2_, streamEv_[h], 0);
-            aa.tA = tA;
-            aa.tB = tA + n;
-            launchStreamAccum(aa, tileEmit_, tileOpen_, ntiles, stream2_);
-            if (streamFuse_ && !fuseIdle_) launchStreamIdle(classifyArgs(baseStepArgs(true, true), 0, true), idleHost_ + h, stream2_);
-            hipEventRecord(streamEv_[2 + h], stream2_);
-        }
-        hipStreamWaitEvent(stream_, streamEv_[2], 0);
-        if (pass >= 2) hipStreamWaitEvent(stream_, streamEv_[3], 0);
-        hipEventRecord(ev_[1], stream_);
-        launchStreamFinalize(aa, stream_);
-        hipEventRecord(ev_[2], stream_);
-        lastRunBatched_ = false;
-        enqueueQueries();
-        pendingTimings_ = true;
-        return hipOk(hipGetLastError(), "run launch");
-    }
-    // resident kernel: one launch per run.  Its blocks wait for each other, so they must all be on the chip at once: a run
-    // takes its blocks out of the device's budget until sync(); when concurrent runs of other solvers have used the budget
-    // up, this run goes out as the replayed graph instead (never a wait, never a deadlock)
-    bool resident = useResident_ && !(small && opt_.resident != 1) && !layerActive();
+    if (plan_.reach) return clearReachPlanes();
+    sweptDirty_ = true;  // (full sweeps: clearReachPlanes)
+    return true;
+}
+
+bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
+    const auto inUse = queue_.lockUse();  // (against another solver's creation probing this stream: QueueClaim::use)
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (!beginRun(PathRun::Run, lcx, lcy, true, lx, lz)) return false;
+    if (plan_.path == StepPath::Streaming) return enqueueStreamingRun(lx, lz);
+    lastLcx_ = lcx;
+    lastLcy_ = lcy;
+    // What the plan cannot know.  The resident kernel's blocks wait for each other, so they must all be on the chip at once: a
+    // run takes its blocks out of the device's budget until sync(); when concurrent runs of other solvers have used the budget
+    // up -- or the listener of a window run is not walled in -- the run is demoted to its fallback (never a wait, never a deadlock)
     releaseResident();  // (a run enqueued without a sync() behind the previous one: its reservation goes back first)
     int win[4] = {0, 0, 0, 0};
-    windowRun_ = reach && windowFor(lcx, lcy, win);  // (reach-eligible runs never have useResident_)
-    if (resident) {
-        const int budget = residentBudget_;
-        std::atomic<int>& inFlight = residentInFlight(device_);
-        if (inFlight.fetch_add(ntiles) + ntiles > budget) {
-            inFlight.fetch_sub(ntiles);
-            resident = false;
-        } else {
-            residentHeld_ = ntiles;
-        }
-    }
-    stampTimed_ = (resident || windowRun_) && stampsHost_ != nullptr;
-    if (!stampTimed_) hipEventRecord(ev_[0], stream_);
-    if (windowRun_) {
-        lastLcx_ = lcx;
-        lastLcy_ = lcy;
-        enqueueWindowRun(win);
-    } else if (resident) {
-        // one-XCD mode where the grid fits one XCD's CUs and that XCD is not taken by another solver's run
-        bool xcd = xcdOk_ && ntiles <= kResidentXcdMaxTiles;
-        if (xcd) {
-            std::atomic<int>& onXcd = residentXcdInFlight(device_, xcdTarget_);
-            if (onXcd.fetch_add(ntiles) + ntiles > kResidentXcdMaxTiles) {
-                onXcd.fetch_sub(ntiles);
-                xcd = false;
-            } else {
-                xcdHeld_ = ntiles;
-            }
-        }
-        lastLcx_ = lcx;
-        lastLcy_ = lcy;
-        // (no begin-run launch: the run's parameters travel in the kernel's arguments, every block resets its own tile's entry, and
-        // the flag words and the error flag were cleared by the previous run's last kernel -- or by the allocation)
-        ResidentArgs ra{};
-        for (int i = 0; i < 2; ++i) {
-            ra.pr[i] = pr_[i];
-            ra.vx[i] = vx_[i];
-            ra.vy[i] = vy_[i];
-        }
-        ra.coef = coef_;
-        ra.pulse = pulseDev_;
-        ra.hist = hist_;
-        ra.tileFirst = tileFirst_;
-        ra.dynVal = dynCur_;
-        ra.dynOut = dynDev_;
-        ra.errFlag = errFlag_;
-        ra.flags = resFlags_;
-        ra.xcdMode = xcd ? 1 : 0;
-        ra.xcdTarget = xcdTarget_;
-        lastRunXcd_ = xcd;
-        ra.histPlane = histPlane_;
-        ra.planeBytes = (long long)geo_.rows * geo_.pitch * 4;
-        ra.pitch = geo_.pitch;
-        ra.G = geo_.G;
-        ra.ntx = geo_.ntx;
-        ra.nty = geo_.nty;
-        ra.ntiles = ntiles;
-        ra.T = T_;
-        ra.courant = g_.courant;
-        ra.stamp = stampTimed_ ? stampsHost_ : nullptr;
-        ra.histSub = 1;  // (the grid's tiles are the kernel's: ResidentArgs::window = 0)
-        ra.gridNty = geo_.nty;
-        if (stampTimed_) stampsHost_[0] = stampsHost_[1] = stampsHost_[2] = 0ull;  // (the previous run has been synced: enqueueRun's head)
-        launchResident(K_, rxi_, ra, stream_);
-        tim_.stepLaunches = ceilDiv(T_, K_);
-        cur_ = tim_.stepLaunches & 1;
-    } else if (small) {
-        // the whole grid lives in one CU's LDS for all T steps: one launch, every cell recorded from step 0
-        enqueueBeginRun(false);
-        if (!hipOk(hipMemsetAsync(tileFirst_, 0, sizeof(int) * (size_t)ntiles, stream_), "tileFirst")) return false;
-        SmallArgs sa{};
-        sa.prOut = pr_[0];
-        sa.vxOut = vx_[0];
-        sa.vyOut = vy_[0];
-        sa.coef = coef_;
-        sa.pulse = pulseDev_;
-        sa.hist = hist_;
-        sa.dyn = dynDev_;
-        sa.histPlane = histPlane_;
-        sa.histPitch = histPitch_;
-        sa.pitch = geo_.pitch;
-        sa.G = geo_.G;
-        sa.NX = g_.NX;
-        sa.NY = g_.NY;
-        sa.T = T_;
-        sa.record = 1;
-        sa.courant = g_.courant;
-        sa.rxi = rxi_;
-        sa.wi = wi_;
-        launchSmallGrid(sa, stream_);
-        tim_.stepLaunches = 1;
-    } else if (graph) {
-        // the grid of the general kernel is captured for a capacity; the live count is read from dyn on the device
-        // (+ the tiles whose loaded region can hold the listener: ceil(loaded rows / tile rows) x ceil(64 / tile columns) --
-        // 2 x 2 for every tile of rounds 1-2, 3 x 2 for the 12-row tile at K = 12, whose two extra listener tiles fell off a
-        // capacity of "+ 4" and were advanced by nobody: tools/gpu_fuzz.py seeds 30051 / 30098 / 30172)
-        const int rowsL = rxi_ + 2 * K_ + (stepConfigStacked(K_, rxi_) ? stepConfigExtraRows(K_, rxi_) : 0);
-        const int cap = (int)wallTiles_.size() + ceilDiv(rowsL, rxi_) * ceilDiv(64, wi_);
-        if ((!graphExec_ || graphCap_ != cap) && !buildGraph(cap)) {
-            // The capture did not survive: some legacy-stream operation of another host thread while this stream was capturing
-            // invalidates it (this library issues none any more -- see applyGeometry -- but a host application may).  This
-            // run goes out as plain launches; the next one captures again.
-            (void)hipGetLastError();
-            err_.clear();
-            launchCap_ = numGeneral_;
+    if (plan_.path == StepPath::Window && !windowFor(lcx, lcy, win)) plan_.path = plan_.fallback;
+    if (plan_.path == StepPath::Resident && !reserveBlocks(residentInFlight(device_), caps_.ntiles, residentBudget_, &residentHeld_))
+        plan_.path = plan_.fallback;
+    if (!stampTimed()) hipEventRecord(ev_[0], stream_);
+    switch (plan_.path) {
+        case StepPath::Window: enqueueWindowRun(win); break;
+        case StepPath::Resident: enqueueResidentRun(); break;
+        case StepPath::SmallGrid:
+            if (!enqueueSmallGridRun()) return false;
+            break;
+        case StepPath::Graph:
+            if (!enqueueGraphRun()) return false;
+            break;
+        case StepPath::Launches:
             if (!enqueueResetAndSteps()) return false;
-        } else {
-            if (!hipOk(hipGraphLaunch(graphExec_, stream_), "hipGraphLaunch")) return false;
-            tim_.stepLaunches = ceilDiv(T_, K_);
-            cur_ = tim_.stepLaunches & 1;
-        }
-    } else {
-        launchCap_ = numGeneral_;
-        reachRun_ = reach;
-        const bool ok = enqueueResetAndSteps();
-        reachRun_ = false;
-        if (!ok) return false;
+            break;
+        case StepPath::Streaming: break;  // (went out above)
     }
-    if (!stampTimed_) hipEventRecord(ev_[1], stream_);
+    if (!stampTimed()) hipEventRecord(ev_[1], stream_);
     if (!opt_.skipAnalysis) enqueueAnalysis(lx, lz);
-    if (!stampTimed_) hipEventRecord(ev_[2], stream_);
+    if (!stampTimed()) hipEventRecord(ev_[2], stream_);
     lastRunBatched_ = false;
     // last kernel of the run: the registered queries' outputs and the status words, both into pinned memory
     launchRunFinish(res_, (long long)g_.gx * g_.gy, qCellsHost_, opt_.skipAnalysis ? 0 : numQueries_, qOutHost_, farInfo(), errFlag_,
-                    activeCount_, lastRunXcd_ ? resFlags_ + geo_.ntx * geo_.nty + 1 : nullptr, statusHost_, resFlags_,
-                    resFlags_ ? resFlagWords_ : 0, stampTimed_ ? stampsHost_ : nullptr, stream_);
+                    activeCount_, plan_.oneXcd ? resFlags_ + geo_.ntx * geo_.nty + 1 : nullptr, statusHost_, resFlags_,
+                    resFlags_ ? resFlagWords_ : 0, stampTimed() ? stampsHost_ : nullptr, stream_);
     // (ev_[2] is also what the OTHER solver of a pipelined pair waits for before its carry pass reads this solver's maps: behind
     // the last kernel here, where it delays nothing of this run)
-    if (stampTimed_) hipEventRecord(ev_[2], stream_);
+    if (stampTimed()) hipEventRecord(ev_[2], stream_);
     enqueueTap();
     statusQueued_ = true;
     pendingTimings_ = true;
     return hipOk(hipGetLastError(), "run launch");
 }
 
+// sparse-emitter mode: ring history; forward sums advanced after every `ring_` steps
+bool Solver::enqueueStreamingRun(float lx, float lz) {
+    const int ntiles = geo_.ntx * geo_.nty;
+    hipEventRecord(ev_[0], stream_);
+    const size_t nres = (size_t)g_.gx * g_.gy;
+    if (!hipOk(hipMemsetAsync(sOnset_, 0xff, nres * 4, stream_), "state reset")) return false;  // onset = -1
+    for (float* p : sState_)
+        if (!hipOk(hipMemsetAsync(p, 0, nres * 4, stream_), "state reset")) return false;
+    if (numEmitters_ > 0 &&
+        !hipOk(hipMemsetAsync(emTrace_, 0, (size_t)numEmitters_ * T_ * 4, stream_), "trace reset"))
+        return false;
+    if (streamFuse_ && (!hipOk(hipMemsetAsync(cellsOpen2_, 1, (size_t)2 * ntiles, stream_), "open flags") ||
+                        !hipOk(hipMemsetAsync(openCount_, 0, 2 * sizeof(int), stream_), "open count")))
+        return false;
+    enqueueBeginRun(true);
+    if (streamFuse_) {
+        // what is left to the ring and the accumulate pass: the run's general list (walls, edges, the tiles whose loaded
+        // region holds the listener: prepareDyn) and the tiles of the registered emitters -- the complement of
+        // fusedTile() (pv_stream.h)
+        std::vector<uint8_t> in((size_t)ntiles, 0);
+        int n = 0;
+        auto add = [&](int t) {
+            if (!in[(size_t)t]) {
+                in[(size_t)t] = 1;
+                ringHost_[n++] = t;
+            }
+        };
+        for (int i = 0; i < numGeneral_; ++i) add(listHost_[i]);
+        for (int t = 0; t < ntiles; ++t)
+            if (tileClassHost_[(size_t)t] != 0 || (t < (int)emTilesHost_.size() && emTilesHost_[(size_t)t])) add(t);
+        numRing_ = n;
+        if (n > 0 && !hipOk(hipMemcpyAsync(ringList_, ringHost_, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, stream_),
+                            "ring list"))
+            return false;
+    }
+    AnalyzeArgs aa = analyzeArgs(lx, lz);
+    if (streamEv_[0] == nullptr)
+        for (auto& e : streamEv_)
+            if (!hipOk(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) return false;
+    // Half h of the ring: [steps fill it on stream_] -> stepDone[h] -> [accumulate pass on stream2_] -> accDone[h] ->
+    // [steps may overwrite it].  The passes stay in order on stream2_ (they carry per-cell state from one to the next);
+    // the per-tile "history still wanted" flags they produce reach the step kernels half a ring later than in a serial
+    // schedule, which only means a tile may record a few planes nobody reads.
+    int pass = 0;
+    fuseIdle_ = false;
+    if (streamFuse_) idleHost_[0] = idleHost_[1] = 0;
+    for (int tA = 0; tA < T_; tA += halfRing_, ++pass) {
+        const int n = std::min(halfRing_, T_ - tA), h = pass & 1;
+        if (streamFuse_ && !fuseIdle_ && pass >= 2) {
+            // Feedback from the device, two passes old (the GPU keeps pass - 1 queued while the host waits here): once
+            // every fused tile has closed for good -- the wave front has passed and the dry windows behind it are over,
+            // a third of the way into a Mode B run -- the rest of the run needs neither the classify pass nor the
+            // open-tile kernel, i.e. one launch per sweep instead of three.
+            if (!hipOk(hipEventSynchronize(streamEv_[2 + h]), "pass sync")) return false;
+            fuseIdle_ = idleHost_[h] != 0;
+        }
+        if (pass >= 2) hipStreamWaitEvent(stream_, streamEv_[2 + h], 0);
+        if (!enqueueSteps(tA, n, true, true, tA == 0)) return false;
+        hipEventRecord(streamEv_[h], stream_);
+        hipStreamWaitEvent(stream2_, streamEv_[h], 0);
+        aa.tA = tA;
+        aa.tB = tA + n;
+        launchStreamAccum(aa, tileEmit_, tileOpen_, ntiles, stream2_);
+        if (streamFuse_ && !fuseIdle_) launchStreamIdle(classifyArgs(baseStepArgs(true, true), 0, true), idleHost_ + h, stream2_);
+        hipEventRecord(streamEv_[2 + h], stream2_);
+    }
+    hipStreamWaitEvent(stream_, streamEv_[2], 0);
+    if (pass >= 2) hipStreamWaitEvent(stream_, streamEv_[3], 0);
+    hipEventRecord(ev_[1], stream_);
+    launchStreamFinalize(aa, stream_);
+    hipEventRecord(ev_[2], stream_);
+    lastRunBatched_ = false;
+    enqueueQueries();
+    pendingTimings_ = true;
+    return hipOk(hipGetLastError(), "run launch");
+}
+
+// the whole-grid run of the resident kernel: one-XCD mode where the grid fits one XCD's CUs and that XCD is not taken by another
+// solver's run
+void Solver::enqueueResidentRun() {
+    plan_.oneXcd = xcdOk_ && caps_.ntiles <= kResidentXcdMaxTiles &&
+                   reserveBlocks(residentXcdInFlight(device_, xcdTarget_), caps_.ntiles, kResidentXcdMaxTiles, &xcdHeld_);
+    // (no begin-run launch: the run's parameters travel in the kernel's arguments, every block resets its own tile's entry, and
+    // the flag words and the error flag were cleared by the previous run's last kernel -- or by the allocation)
+    launchResidentRun(rxi_, nullptr);
+}
+
+// the whole grid lives in one CU's LDS for all T steps: one launch, every cell recorded from step 0
+bool Solver::enqueueSmallGridRun() {
+    enqueueBeginRun(false);
+    if (!hipOk(hipMemsetAsync(tileFirst_, 0, sizeof(int) * (size_t)caps_.ntiles, stream_), "tileFirst")) return false;
+    SmallArgs sa{};
+    sa.prOut = pr_[0];
+    sa.vxOut = vx_[0];
+    sa.vyOut = vy_[0];
+    sa.coef = coef_;
+    sa.pulse = pulseDev_;
+    sa.hist = hist_;
+    sa.dyn = dynDev_;
+    sa.histPlane = histPlane_;
+    sa.histPitch = histPitch_;
+    sa.pitch = geo_.pitch;
+    sa.G = geo_.G;
+    sa.NX = g_.NX;
+    sa.NY = g_.NY;
+    sa.T = T_;
+    sa.record = 1;
+    sa.courant = g_.courant;
+    sa.rxi = rxi_;
+    sa.wi = wi_;
+    launchSmallGrid(sa, stream_);
+    tim_.stepLaunches = 1;
+    return true;
+}
+
+bool Solver::enqueueGraphRun() {
+    // the grid of the general kernel is captured for a capacity; the live count is read from dyn on the device
+    // (+ the tiles whose loaded region can hold the listener: ceil(loaded rows / tile rows) x ceil(64 / tile columns) --
+    // 2 x 2 for every tile of rounds 1-2, 3 x 2 for the 12-row tile at K = 12, whose two extra listener tiles fell off a
+    // capacity of "+ 4" and were advanced by nobody: tools/gpu_fuzz.py seeds 30051 / 30098 / 30172)
+    const int rowsL = rxi_ + 2 * K_ + (stepConfigStacked(K_, rxi_) ? stepConfigExtraRows(K_, rxi_) : 0);
+    const int cap = (int)wallTiles_.size() + ceilDiv(rowsL, rxi_) * ceilDiv(64, wi_);
+    if ((!graphExec_ || graphCap_ != cap) && !buildGraph(cap)) {
+        // The capture did not survive: some legacy-stream operation of another host thread while this stream was capturing
+        // invalidates it (this library issues none any more -- see applyGeometry -- but a host application may).  This
+        // run goes out as plain launches; the next one captures again.
+        (void)hipGetLastError();
+        err_.clear();
+        launchCap_ = numGeneral_;
+        plan_.path = plan_.fallback;
+        return enqueueResetAndSteps();
+    }
+    if (!hipOk(hipGraphLaunch(graphExec_, stream_), "hipGraphLaunch")) return false;
+    tim_.stepLaunches = ceilDiv(T_, K_);
+    cur_ = tim_.stepLaunches & 1;
+    return true;
+}
+
 // reset pr / vx / vy (FDTD.cpp:109-119) + the T-step loop; this is what a captured graph contains
 bool Solver::enqueueResetAndSteps() {
     enqueueBeginRun(true);
     // graph capture cannot hold timing events; plain launches get one more event so that the launch loop is timed alone
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    hipStreamIsCapturing(stream_, &cs);
-    if (cs == hipStreamCaptureStatusNone) {
-        hipEventRecord(ev_[3], stream_);
-        loopTimed_ = true;
-    }
+    if (loopTimed()) hipEventRecord(ev_[3], stream_);
     return enqueueSteps(0, T_, true, true, true);
 }
 
@@ -2384,22 +2369,11 @@ bool Solver::runBatch(Solver* const* s, int n, const float* lxyz, bool wait, std
         const float lx = lxyz[3 * i], lz = lxyz[3 * i + 2];
         int lcx, lcy;
         listenerCell(v.g_, lx, lz, &lcx, &lcy);
-        if ((v.pendingTimings_ && !v.sync()) || !v.applyGeometry() || !v.prepareDyn(lcx, lcy, true, false) ||
-            !v.zeroPlanesIfNeeded()) {
+        if (!v.beginRun(PathRun::Shared, lcx, lcy, true, lx, lz)) {
             if (err) *err = v.err_;
             return false;
         }
-        v.lastLx_ = lx;
-        v.lastLz_ = lz;
-        v.tim_.stepLaunches = 0;
-        v.kevUsed_ = 0;
-        v.loopTimed_ = false;
-        v.cur_ = 0;
-        v.sweptDirty_ = true;  // (full sweeps: clearReachPlanes)
-        v.launchCap_ = v.numGeneral_;
         gcap = std::max(gcap, v.numGeneral_);
-        v.stampTimed_ = false;
-        v.windowRun_ = false;
         hipEventRecord(v.ev_[0], v.stream_);
         v.enqueueBeginRun(true);
         if (i > 0) {  // the shared step loop starts when every run's parameters are on the device
@@ -2505,7 +2479,7 @@ bool Solver::sync() {
     releaseResident();
     if (pendingTimings_) {
         pendingTimings_ = false;
-        if (stampTimed_) {  // 100 MHz ticks: the run's first kernel, the analysis' first kernel (0: none ran), the run's last kernel
+        if (stampTimed()) {  // 100 MHz ticks: the run's first kernel, the analysis' first kernel (0: none ran), the run's last kernel
             const unsigned long long s0 = stampsHost_[0], s2 = stampsHost_[2], s1 = stampsHost_[1] ? stampsHost_[1] : s2;
             tim_.fdtdMs = (s0 && s1 > s0) ? (float)((double)(s1 - s0) * 1e-5) : 0.f;
             tim_.analysisMs = (s2 > s1) ? (float)((double)(s2 - s1) * 1e-5) : 0.f;
@@ -2514,8 +2488,8 @@ bool Solver::sync() {
             hipEventElapsedTime(&tim_.analysisMs, ev_[1], ev_[2]);
         }
         tim_.stepLoopMs = 0.f;
-        if (loopTimed_) hipEventElapsedTime(&tim_.stepLoopMs, ev_[3], ev_[1]);
-        if (windowRun_) tim_.stepLoopMs = tim_.fdtdMs;  // (the one launch is the run's T / K epochs: nothing else between the stamps)
+        if (loopTimed()) hipEventElapsedTime(&tim_.stepLoopMs, ev_[3], ev_[1]);
+        if (plan_.path == StepPath::Window) tim_.stepLoopMs = tim_.fdtdMs;  // (the one launch is the run's T / K epochs: nothing else between the stamps)
         if (opt_.timeKernels && kevUsed_ > 0) {
             double air = 0, gen = 0;
             const int n = kevUsed_ / 4;
@@ -2539,13 +2513,11 @@ bool Solver::sync() {
             counts[0] = statusHost_[1];
             counts[1] = statusHost_[2];
             tim_.silentCells = statusHost_[4];
-            if (lastRunXcd_ && statusHost_[3] >= 0 && statusHost_[3] < geo_.ntx * geo_.nty && flag == 0) flag = 4;
-            lastRunXcd_ = false;
+            if (plan_.oneXcd && statusHost_[3] >= 0 && statusHost_[3] < geo_.ntx * geo_.nty && flag == 0) flag = 4;
         } else {
             // (raw stepping: no status kernel.)  The error flag, never through the legacy stream (applyGeometry), and by the kind
             // of run -- read behind stream_, the batched launches of a batch member's NEXT step loop took twice as long
             // (profiles/r03_ab_errflag.txt) -- through the solver's second stream, which the batched mode does not use.
-            lastRunXcd_ = false;
             hipStream_t fs = lastRunBatched_ ? stream2_ : stream_;  // (stream2_ is idle in the batched mode)
             if (!hipOk(hipMemcpyAsync(&flag, errFlag_, sizeof(int), hipMemcpyDeviceToHost, fs), "errFlag copy") ||
                 !hipOk(hipMemcpyAsync(counts, activeCount_, sizeof(counts), hipMemcpyDeviceToHost, fs), "count copy") ||
@@ -2556,33 +2528,39 @@ bool Solver::sync() {
         tim_.reachedCells = counts[1];
         lastReached_ = counts[1];
         tim_.activeCells = counts[0];
-        if (flag == 4 && xcdOk_) {
-            // one-XCD mode: fewer workgroups than tiles turned up on this solver's XCD (another dispatch pattern / partition
-            // mode than the one observed).  Nothing was computed; from now on the placement-independent hand-off, and the run
-            // is repeated in it.
-            xcdOk_ = false;
-            std::fprintf(stderr, "[planeverb_amd] resident kernel: one-XCD mode not available on this device (workgroups are "
-                                 "not spread over the XCDs as expected); using the placement-independent hand-off\n");
-            return enqueueRun(lastLcx_, lastLcy_, lastLx_, lastLz_) && sync();
-        }
-        if (flag == 3 && windowRun_) {
-            // A window run's workgroup waited ~2 s for a neighbour (the device is shared: see below).  The reach-bounded launches
-            // need no co-residency and give the same bits: the run is repeated as such, and so is every run until the geometry
-            // changes.  (reachRect_ is the window: the repeat clears what the aborted launch left.)
-            windowOff_ = true;
-            std::fprintf(stderr, "[planeverb_amd] resident window: a workgroup gave up waiting for its neighbours (the device is "
-                                 "shared?); this solver's runs go out as reach-bounded launches until its geometry changes\n");
-            return enqueueRun(lastLcx_, lastLcy_, lastLx_, lastLz_) && sync();
-        }
-        if (flag == 3 && useResident_) {
-            // A workgroup waited ~2 s for a neighbour: the blocks were not all on the chip (another process, or a long kernel
-            // of the host application, holds CUs -- the per-process budget cannot see those).  The replayed-graph path needs no
-            // co-residency and gives the same bits: this solver uses it from now on, and the run is repeated in it.
-            useResident_ = false;
-            std::fprintf(stderr, "[planeverb_amd] resident kernel: a workgroup gave up waiting for its neighbours (the device is "
-                                 "shared?); this solver runs its steps as a replayed graph from now on\n");
-            return enqueueRun(lastLcx_, lastLcy_, lastLx_, lastLz_) && sync();
-        }
+        // A run that gave up: nothing was computed.  The form that failed is switched off -- the one-XCD mode and the resident kernel
+        // for good, the resident window until the geometry changes -- and the run is repeated on what its plan then says; every
+        // path gives the same bits.
+        //  - one-XCD mode: fewer workgroups than tiles turned up on this solver's XCD (another dispatch pattern / partition mode
+        //    than the one observed).  From now on the placement-independent hand-off.
+        //  - window run: a workgroup waited ~2 s for a neighbour (the device is shared: see below).  The reach-bounded launches
+        //    need no co-residency.  (reachRect_ is the window: the repeat clears what the aborted launch left.)
+        //  - resident kernel: a workgroup waited ~2 s for a neighbour: the blocks were not all on the chip (another process, or a
+        //    long kernel of the host application, holds CUs -- the per-process budget cannot see those).  The replayed-graph path
+        //    needs no co-residency.
+        const struct {
+            int flag;
+            bool applies;
+            bool* form;
+            bool value;
+            const char* message;
+        } giveUps[] = {
+            {4, xcdOk_, &xcdOk_, false,
+             "[planeverb_amd] resident kernel: one-XCD mode not available on this device (workgroups are "
+             "not spread over the XCDs as expected); using the placement-independent hand-off\n"},
+            {3, plan_.path == StepPath::Window, &windowOff_, true,
+             "[planeverb_amd] resident window: a workgroup gave up waiting for its neighbours (the device is "
+             "shared?); this solver's runs go out as reach-bounded launches until its geometry changes\n"},
+            {3, caps_.useResident, &caps_.useResident, false,
+             "[planeverb_amd] resident kernel: a workgroup gave up waiting for its neighbours (the device is "
+             "shared?); this solver runs its steps as a replayed graph from now on\n"},
+        };
+        for (const auto& g : giveUps)
+            if (flag == g.flag && g.applies) {
+                *g.form = g.value;
+                std::fputs(g.message, stderr);
+                return enqueueRun(lastLcx_, lastLcy_, lastLx_, lastLz_) && sync();
+            }
         if (flag == 3 || flag == 4) return fail("resident kernel: a workgroup gave up waiting for its neighbours (run aborted)");
         if (flag == 5) return fail("slab decomposition: a neighbour's halo rows never arrived (run aborted)");
         if (flag == 6) {
@@ -2607,18 +2585,10 @@ bool Solver::runSteps(int nsteps, bool withPulse, float lx, float lz) {
     if (opt_.edgeTiles) return fail("stencil-only stepping is not available with edge tiles (batched kernel only)");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (!applyGeometry()) return false;
     int lcx, lcy;
     listenerCell(g_, lx, lz, &lcx, &lcy);
-    if (!prepareDyn(lcx, lcy, withPulse, true)) return false;
-    tim_.stepLaunches = 0;
-    kevUsed_ = 0;
-    loopTimed_ = false;
-    launchCap_ = numGeneral_;
-    planesDirty_ = true;
+    if (!beginRun(PathRun::Raw, lcx, lcy, withPulse, lx, lz)) return false;
     enqueueBeginRun(false);
-    stampTimed_ = false;
-    windowRun_ = false;
     hipEventRecord(ev_[0], stream_);
     if (!enqueueSteps(0, nsteps, withPulse, false)) return false;
     hipEventRecord(ev_[1], stream_);
@@ -2659,7 +2629,7 @@ bool Solver::setOutputQueries(const float* xyz, int n) {
 
 // last kernel of a run: its status words into pinned memory (sync() then needs no copy and no second synchronisation)
 void Solver::enqueueRunStatus() {
-    launchRunStatus(errFlag_, activeCount_, lastRunXcd_ ? resFlags_ + geo_.ntx * geo_.nty + 1 : nullptr, statusHost_, stream_);
+    launchRunStatus(errFlag_, activeCount_, plan_.oneXcd ? resFlags_ + geo_.ntx * geo_.nty + 1 : nullptr, statusHost_, stream_);
     statusQueued_ = true;
 }
 

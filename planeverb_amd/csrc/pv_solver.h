@@ -144,8 +144,8 @@ public:
     int histPitch() const { return histPitch_; }
     const std::string& lastError() const { return err_; }
     bool streamFuse() const { return streamFuse_; }
-    bool lastRunResidentWindow() const { return windowRun_; }
-    bool residentKernel() const { return useResident_ && !layerActive(); }  // runs of this solver go through pv_resident_kernel (when the
+    bool lastRunResidentWindow() const { return plan_.path == StepPath::Window; }
+    bool residentKernel() const { return caps_.useResident && !layerActive(); }  // runs of this solver go through pv_resident_kernel (when the
                                                           // device's resident-block budget allows: else the replayed graph)
     SolverOptions& options() { return opt_; }
 
@@ -252,11 +252,22 @@ private:
     bool init(const GridSpec& spec, int device, const SolverOptions& opt);
     bool applyGeometry();
     bool computeEfree();
+    // Which path a run takes (pv_core.h planRun): caps_ is resolved by init, plan_ describes the run in flight / the last run.
+    // beginRun is the head of every run, whoever drives its launches: the pending run synced, the geometry applied, the run
+    // planned and its parameters staged (prepareDyn), the per-run counters reset, the planes as the plan's form needs them.
+    PathCaps caps_;
+    RunPlan plan_;
+    bool beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz);
     bool enqueueRun(int lcx, int lcy, float lx, float lz);
+    bool enqueueStreamingRun(float lx, float lz);
+    void enqueueResidentRun();
+    void launchResidentRun(int tileRows, const int* win);
+    bool enqueueSmallGridRun();
+    bool enqueueGraphRun();
     bool enqueueSteps(int firstStep, int nsteps, bool withPulse, bool record, bool fromZero = false);
     StepArgs baseStepArgs(bool withPulse, bool record) const;
     void setLaunchArgs(StepArgs& a, int t0, int k, bool firstOfRun, int li) const;
-    bool prepareDyn(int lcx, int lcy, bool withPulse, bool banded);
+    bool prepareDyn(int lcx, int lcy, bool withPulse);
     void enqueueBeginRun(bool resetTiles);
     bool zeroPlanesIfNeeded();
     AnalyzeArgs analyzeArgs(float lx, float lz) const;
@@ -279,7 +290,7 @@ private:
     // packet: ~7 us of bubble in front of the next kernel, three of them per 0.3 ms run): the run's first kernel, the analysis'
     // first kernel and the run's last kernel write the 100 MHz counter into three pinned words, sync() takes the differences
     unsigned long long* stampsHost_ = nullptr;
-    bool stampTimed_ = false;       // the run in flight is timed that way
+    bool stampTimed() const { return (plan_.path == StepPath::Resident || plan_.path == StepPath::Window) && stampsHost_; }  // the run in flight is timed that way
     bool labelsValid_ = false;      // labelDev_ holds the air components of the current material plane
     int lastReached_ = -1;          // cells with an onset in the last run read back (-1: none yet): AnalyzeArgs::rt60Tile
     FarInfo farInfo() const;
@@ -357,8 +368,6 @@ private:
     // window (the windows of a run only grow), the only place that run left non-zero values.
     bool sweptDirty_ = true;
     int reachRect_[4] = {0, 0, 0, 0};
-    bool reachRun_ = false;         // enqueueSteps: the run being enqueued is reach-bounded
-    bool reachEligible(bool graph, bool small) const;
     bool clearReachPlanes();
     void setReachArgs(StepArgs& a, int t0);
     int* generalList_ = nullptr;
@@ -409,21 +418,17 @@ private:
     float* emTrace_ = nullptr;
     int numEmitters_ = 0, emCap_ = 0;
     // resident kernel (pv_resident.hip)
-    bool useResident_ = false;
     unsigned* resFlags_ = nullptr;     // ntiles epoch counters + 1 abort word
     int residentHeld_ = 0;             // blocks of the device's resident budget held by the run in flight
     // one-XCD mode of the resident kernel (grids of up to kResidentXcdMaxTiles tiles): hand-off through one XCD's L2
     bool xcdOk_ = true;                // false once a launch found fewer blocks on its XCD than tiles (errFlag 4)
     int xcdTarget_ = 0;                // this solver's XCD (solvers take turns, so that pipelined solvers do not share one)
     int xcdHeld_ = 0;                  // blocks of that XCD's budget held by the run in flight
-    bool lastRunXcd_ = false;          // the run in flight went out in the one-XCD mode
     int lastLcx_ = 0, lastLcy_ = 0;    // (a run given up by the claim check is repeated in the placement-independent mode)
     void releaseResident();
     // Resident window: on the large-grid tile a run whose listener's air component is walled in and small goes out
     // as ONE launch of the resident kernel over the tile window around that component instead of T / K reach-bounded launches
-    bool windowOk_ = false;            // this solver's configuration has the path (init)
     bool windowOff_ = false;           // a window run was given up (errFlag 3): reach-bounded runs until the geometry changes
-    bool windowRun_ = false;           // the run in flight / the last run took the path
     int resFlagWords_ = 0;             // words of resFlags_
     struct EnclosureRec {
         Enclosure e;
@@ -432,6 +437,7 @@ private:
     std::vector<EnclosureRec> enclosures_;  // answers of findEnclosure for this geometry (dropped when a cell changes between air and wall)
     const Enclosure* enclosureOf(int lcx, int lcy);
     bool windowFor(int lcx, int lcy, int win[4]);
+    ResidentArgs residentArgs(const int* win) const;  // win = nullptr: the grid's own tiles
     void enqueueWindowRun(const int win[4]);
     float* scratch_ = nullptr;  // max(3T, NX*NY) floats
     size_t scratchCount_ = 0;
@@ -449,11 +455,8 @@ private:
     int* listHost_ = nullptr;
     int listCap_ = 0;
     // row-streaming air segments (pv_seg.h): rebuilt for every run (they avoid the tiles around the listener)
-    bool usePatch_ = false;    // air tiles go through the persistent patch kernel (pv_patch.h)
     int patchBlocks_ = 0;      // its grid: one workgroup per CU, a multiple of 8
     long long* patchTrace_ = nullptr;  // development aid (PV_PATCH_TRACE)
-    bool useSeg_ = false;      // this solver's configuration and options allow them
-    bool segActive_ = false;   // the run being enqueued uses them
     int segWMax_ = 0;          // tile columns a segment can span
     SegDesc* segHost_ = nullptr;  // pinned
     SegDesc* segList_ = nullptr;  // device
@@ -519,15 +522,13 @@ private:
     std::vector<int> bandListOff_, bandListCount_;
     DynParams* dynBandsDev_ = nullptr;
     DynParams* dynBandsHost_ = nullptr;
-    bool bandedRun_ = false;  // the run prepared last is launched band by band
-    bool bandsActive() const;
     StepArgs bandStepArgs(const StepArgs& a, int b) const;
 
     std::vector<hipEvent_t> kev_;  // 3 events per step launch when opt_.timeKernels
     int kevUsed_ = 0;
     SolverTimings tim_;
     bool pendingTimings_ = false;
-    bool loopTimed_ = false;  // ev_[3] was recorded between the reset and the first step launch of this run
+    bool loopTimed() const { return plan_.path == StepPath::Launches && plan_.kind == PathRun::Run; }  // ev_[3] was recorded between the reset and the first step launch of this run
 };
 
 }  // namespace pva
