@@ -527,6 +527,45 @@ PVA_EXPORT int PvAmdGetImpulseResponseCells(PvAmdSolver* s, int cx, int cy, Plan
 PVA_EXPORT int PvAmdCopyFields(PvAmdSolver* s, float* pr, float* vx, float* vy);
 /* Recorded pressure plane of step t (zeros where the history was provably zero and not stored) */
 PVA_EXPORT int PvAmdCopyHistoryPlane(PvAmdSolver* s, int t, float* pr);
+/* ---- Room metrics: clarity C50 / C80, definition D50 and centre time Ts (ISO 3382) of every reached cell ----
+ * The recorded pressure of a reached cell is the impulse response from the listener to that cell; PvAmdComputeRoomMetrics
+ * reduces the history of the LAST COMPLETED run to one record per cell in one pass on the device (pv_metrics.hip).
+ * Definition, for result cell s = X * gy + Y:
+ *   onset   t0 = (int)delay[s], delay = the run's own onset map (FLT_MAX: not reached);
+ *   p(t)    = the recorded pressure, exactly what PvAmdCopyHistoryPlane(t) returns at array cell (X, Y); 0 for t >= T;
+ *   e(t)    = p(t) * p(t);   n50 = (int)(0.05f * (float)fs),  n80 = (int)(0.08f * (float)fs);   k = t - t0, t = t0 .. T - 1;
+ *   e50 = sum e(t) over k < n50      l50 = sum e(t) over k >= n50
+ *   e80 = sum e(t) over k < n80      l80 = sum e(t) over k >= n80
+ *   total = sum e(t)                 moment = sum ((float)k * e(t))
+ *   c50 = 10.0f * log10f(e50 / l50)  c80 = 10.0f * log10f(e80 / l80)   (dB)
+ *   d50 = e50 / (e50 + l50)          ts  = (moment / total) / (float)fs  (seconds)
+ * All arithmetic is float32; every product and every sum is rounded on its own; every sum is sequential in increasing t from
+ * +0.0f; division is correctly rounded; log10f is glibc's.  Nothing is special-cased: a late-onset cell whose late window is
+ * empty (t0 + n50 >= T) has l50 = 0, c50 = +inf and d50 = 1.
+ * A cell WITHOUT an onset in that run holds ten quiet NaNs.  Unlike the result map (PvAmdCopyResults), nothing is carried over
+ * from earlier runs.  Cells inside an edge layer get values like any other cell, as unphysical there as the eight outputs.
+ * Device storage: 10 x 4 bytes per cell of the history window (tile-rounded), allocated by the first call, freed with the
+ * solver; cells outside the window are unreached by construction.  The records stay valid until the next run, geometry,
+ * boundary or layer change on that solver: PvAmdCopyRoomMetrics* / PvAmdGetRoomMetrics then return -1 until computed again.
+ * Refused (-1, nothing changed, PvAmdLastError says why): NULL, no completed run, a last run that ended in error, sparse-emitter
+ * solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks. */
+typedef struct PvAmdRoomMetrics {
+    float c50, c80, d50, ts, e50, l50, e80, l80, total, moment;
+} PvAmdRoomMetrics;
+/* Compute the room metrics of the LAST COMPLETED run of s (waits for a run in flight; works after PvAmdRun, PvAmdRunAsync +
+ * PvAmdSync, PvAmdRunAsyncAfter and a PvAmdRunBatch member, whatever path the run took).  The pass runs on the solver's own
+ * stream and is synchronised before the call returns.  *ms (optional): device time of the pass. */
+PVA_EXPORT int PvAmdComputeRoomMetrics(PvAmdSolver* s, float* ms);
+/* gx*gy*10 floats, AoS records, cell s = X*gy + Y */
+PVA_EXPORT int PvAmdCopyRoomMetrics(PvAmdSolver* s, float* out10);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records, row-major */
+PVA_EXPORT int PvAmdCopyRoomMetricsBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out10);
+/* the record at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map gives ten NaNs
+ * and 0 */
+PVA_EXPORT int PvAmdGetRoomMetrics(PvAmdSolver* s, float ex, float ey, float ez, PvAmdRoomMetrics* out);
+/* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T; the restatement the tests hold the
+ * kernel to */
+PVA_EXPORT int PvAmdHostRoomMetrics(const float* p, int T, int fs, int onset, PvAmdRoomMetrics* out);
 /* Gaussian pulse table (Grid.cpp:12-27), T floats */
 PVA_EXPORT int PvAmdCopyPulse(PvAmdSolver* s, float* out);
 /* Material planes after rasterisation: beta (uint8) and R (float), (gx+1)*(gy+1) each (with shapes: the composed material) */

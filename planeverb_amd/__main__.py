@@ -32,6 +32,8 @@ def main(argv=None):
     ap.add_argument("--listener", type=vec3, default=(5.0, 0.0, 4.0))
     ap.add_argument("--emitter", type=vec3, action="append", default=[])
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--room-metrics", action="store_true",
+                    help="add the room metrics (C50, C80, D50, Ts and their sums) of each emitter's cell")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
@@ -52,6 +54,8 @@ def main(argv=None):
         t = s.timings()
         out = {"scene": a.scene, "grid": [s.gx, s.gy], "T": s.T, "res": a.res, "dx": s.dx, "efree": s.efree,
                "listener": a.listener, "fdtd_ms": t.fdtdMs, "analysis_ms": t.analysisMs, "emitters": []}
+        if a.room_metrics:
+            s.compute_room_metrics()
         for e in emitters:
             o = s.get_output(e)
             ga, gb, gc = api.reverb_bus_gains(o.rt60, o.wetGain)
@@ -59,6 +63,9 @@ def main(argv=None):
                 "position": e, "occlusion": o.occlusion, "wetGain": o.wetGain, "rt60": o.rt60, "lowpass": o.lowpass,
                 "direction": [o.directionX, o.directionY], "sourceDirectivity": [o.sourceDirectionX, o.sourceDirectionY],
                 "reverbBusGains": [ga, gb, gc]})
+            if a.room_metrics:
+                m = s.room_metrics_at(e)
+                out["emitters"][-1]["roomMetrics"] = dict((n, float(v)) for n, v in zip(api.ROOM_METRIC_NAMES, m))
     print(json.dumps(out, indent=1))
     return 0
 

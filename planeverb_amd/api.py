@@ -103,6 +103,16 @@ class PvAmdTimings(C.Structure):
                 ("generalLaunches", C.c_int), ("stepLoopMs", C.c_float), ("reachedCells", C.c_int), ("activeCells", C.c_int), ("silentCells", C.c_int)]
 
 
+ROOM_METRIC_NAMES = ("c50", "c80", "d50", "ts", "e50", "l50", "e80", "l80", "total", "moment")
+
+
+class PvAmdRoomMetrics(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ROOM_METRIC_NAMES]
+
+    def as_array(self):
+        return np.frombuffer(self, np.float32).copy()
+
+
 # every symbol include/planeverb_amd.h declares: name -> (restype, argtypes)
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -226,6 +236,11 @@ SYMBOLS = {
     "PvAmdGetImpulseResponseCells": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(PlaneverbCell)]),
     "PvAmdCopyFields": (C.c_int, [_vp, _fp, _fp, _fp]),
     "PvAmdCopyHistoryPlane": (C.c_int, [_vp, C.c_int, _fp]),
+    "PvAmdComputeRoomMetrics": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyRoomMetrics": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyRoomMetricsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetRoomMetrics": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdRoomMetrics)]),
+    "PvAmdHostRoomMetrics": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdRoomMetrics)]),
     "PvAmdCopyPulse": (C.c_int, [_vp, _fp]),
     "PvAmdCopyMaterial": (C.c_int, [_vp, C.POINTER(C.c_ubyte), _fp]),
     "PvAmdSetFields": (C.c_int, [_vp, _fp, _fp, _fp]),
@@ -634,6 +649,15 @@ def save_pv(path, boxes, ids=None):
     ida = None if ids is None else np.ascontiguousarray(ids, np.int32)
     _check(lib().PvAmdHostSavePv(path.encode(), _f(b), None if ida is None else ida.ctypes.data_as(C.POINTER(C.c_int)),
                                  len(b)))
+
+
+def host_room_metrics(p, fs, onset):
+    """PvAmdHostRoomMetrics: float32 [10] (ROOM_METRIC_NAMES) of one impulse response p[T] with its onset step -- the
+    definition of include/planeverb_amd.h (PvAmdRoomMetrics) on the CPU"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    out = PvAmdRoomMetrics()
+    _check(lib().PvAmdHostRoomMetrics(_f(a) if a.size else None, int(a.size), int(fs), int(onset), out))
+    return out.as_array()
 
 
 def host_cells(size_x, size_y, res, x, z):
@@ -1243,6 +1267,31 @@ class Solver:
         out = np.empty((self.gx + 1, self.gy + 1), np.float32)
         _check(lib().PvAmdCopyHistoryPlane(self._h, int(t), _f(out)))
         return out
+
+    def compute_room_metrics(self):
+        """room metrics (C50, C80, D50, Ts: ROOM_METRIC_NAMES) of the last completed run, one pass on the device; returns
+        the pass's device time in milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeRoomMetrics(self._h, C.byref(ms)))
+        return ms.value
+
+    def room_metrics(self):
+        """float32 [gx, gy, 10] (ROOM_METRIC_NAMES); NaN where the cell has no onset in the run they were computed for"""
+        out = np.empty((self.gx, self.gy, 10), np.float32)
+        _check(lib().PvAmdCopyRoomMetrics(self._h, _f(out)))
+        return out
+
+    def room_metrics_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, 10] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, 10), np.float32)
+        _check(lib().PvAmdCopyRoomMetricsBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def room_metrics_at(self, pos):
+        """float32 [10] at an emitter position (the cell get_output reads); ten NaNs off the map"""
+        out = PvAmdRoomMetrics()
+        _check(lib().PvAmdGetRoomMetrics(self._h, *[float(v) for v in pos], out))
+        return out.as_array()
 
     def pulse(self):
         out = np.empty(self.T, np.float32)

@@ -11,6 +11,7 @@
 #include "../../include/planeverb_amd.h"
 #include "pv_context.h"
 #include "pv_core.h"
+#include "pv_metrics.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
 #include "pv_bake.h"
 #include "pv_shard.h"
@@ -400,7 +401,7 @@ const char* PlaneverbWorkerError(void) try {
     w = (c && c->failed()) ? c->workerError() : std::string();
     return w.c_str();
 } PV_API_CATCH("")
-const char* PvAmdVersion(void) try { return "planeverb_amd 0.3 (gfx950)"; } PV_API_CATCH("")
+const char* PvAmdVersion(void) try { return "planeverb_amd 0.4 (gfx950)"; } PV_API_CATCH("")
 
 #ifndef PVA_HOST_TEST
 int PvAmdDeviceCount(void) try {
@@ -1083,6 +1084,44 @@ int PvAmdCopyHistoryPlane(PvAmdSolver* h, int t, float* pr) try {
     return ret(h, h->g ? h->g->copyHistoryPlane(t, pr) : h->s->copyHistoryPlane(t, pr));
 } PV_API_CATCH(-1)
 
+// room metrics (pv_metrics.hip): single whole-grid solvers only -- slab groups (ensure) and slab ranks (wholeGrid) are refused
+int PvAmdComputeRoomMetrics(PvAmdSolver* h, float* ms) try {
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    return ret(h, h->s->computeRoomMetrics(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyRoomMetrics(PvAmdSolver* h, float* out10) try {
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!out10) {
+        g_lastError = "PvAmdCopyRoomMetrics: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyRoomMetricsBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out10));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyRoomMetricsBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out10) try {
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!out10) {
+        g_lastError = "PvAmdCopyRoomMetricsBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyRoomMetricsBlock(r0, c0, nr, nc, out10));
+} PV_API_CATCH(-1)
+
+int PvAmdGetRoomMetrics(PvAmdSolver* h, float ex, float ey, float ez, PvAmdRoomMetrics* out) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!out) {
+        g_lastError = "PvAmdGetRoomMetrics: null output";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdRoomMetrics) == kRoomMetricFloats * sizeof(float), "ten floats");
+    float v[kRoomMetricFloats];
+    if (!h->s->roomMetricsAt(ex, ez, v)) return ret(h, false);
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
 int PvAmdCopyPulse(PvAmdSolver* h, float* out) try {
     if (!out || !ensure(h, true)) return -1;
     return ret(h, h->g ? h->g->copyPulse(out) : h->s->copyPulse(out));
@@ -1375,6 +1414,18 @@ int PvAmdHostSavePv(const char* path, const float* b5, const int* ids, int n) tr
     for (int i = 0; i < n; ++i)
         boxes.emplace_back(ids ? ids[i] : i, Box{b5[5 * i], b5[5 * i + 1], b5[5 * i + 2], b5[5 * i + 3], b5[5 * i + 4]});
     return savePv(path, boxes, &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+
+int PvAmdHostRoomMetrics(const float* p, int T, int fs, int onset, PvAmdRoomMetrics* out) try {
+    if (!p || !out || T <= 0 || onset < 0 || onset >= T) {
+        g_lastError = "PvAmdHostRoomMetrics: an impulse response p[T], T > 0, 0 <= onset < T and an output record";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdRoomMetrics) == kRoomMetricFloats * sizeof(float), "ten floats");
+    float v[kRoomMetricFloats];
+    roomMetricsOfIr(p, T, fs, onset, v);
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
 } PV_API_CATCH(-1)
 
 int PvAmdHostCells(float sx, float sy, int res, float x, float z, int* lcx, int* lcy, int* rcx, int* rcy,

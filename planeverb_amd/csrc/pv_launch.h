@@ -103,6 +103,9 @@ void launchRunFinish(const float* res, long long n, const long long* cellsHost, 
 // wet gain + decay time (pv_rt60.hip): sixteen / four lanes per cell in one launch, the lane-per-cell form in a second one where
 // AnalyzeArgs::rt60Tile announces it; the form is chosen on the device
 void launchRt60Forms(const AnalyzeArgs& a, hipStream_t stream);
+// room metrics of the last completed run (pv_metrics.hip): out = kRoomMetricFloats planes of a.histPlane floats, indexed by the
+// cell's offset inside a history plane; NaN where the cell has no onset in that run
+void launchRoomMetrics(const AnalyzeArgs& a, float* out, hipStream_t stream);
 // slab halos: src[i] -> dst[i] for up to six blocks of n floats (n % 4 == 0, 16-byte aligned); dst[i] = NULL skips a block
 void launchHaloPush(const float* const src[6], float* const dst[6], long long n, const HaloHandoff& hand, hipStream_t stream);
 void launchHistRow(const AnalyzeArgs& a, int X, float* outTxPitch, hipStream_t stream);

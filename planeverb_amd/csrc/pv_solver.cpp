@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "pv_launch.h"
+#include "pv_metrics.h"
 
 namespace pva {
 
@@ -666,6 +667,9 @@ Solver::~Solver() {
     if (caps_.useResident) residentDumpTrace();
 #endif
     if (resFlags_) hipFree(resFlags_);
+    if (metrics_) hipFree(metrics_);
+    for (auto& e : metricsEv_)
+        if (e) hipEventDestroy(e);
     if (layerList_) hipFree(layerList_);
     if (layerTab_) hipFree(layerTab_);
     if (px_[0]) hipFree(px_[0]);  // (px_[1] lives in the same allocation)
@@ -743,6 +747,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
+    metricsValid_ = false;
     return id;
 }
 
@@ -753,6 +758,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
+    metricsValid_ = false;
     return true;
 }
 
@@ -763,6 +769,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
+    metricsValid_ = false;
     return true;
 }
 
@@ -834,12 +841,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
+    metricsValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
+    metricsValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -986,6 +995,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
+    if (boundaryDirty_) metricsValid_ = false;
     return true;
 }
 
@@ -1025,6 +1035,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
+    if (layerDirty_) metricsValid_ = false;
     return true;
 }
 
@@ -2071,6 +2082,8 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
+    metricsValid_ = false;       // (the history the records were made from is about to be overwritten)
+    lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     if (!applyGeometry()) return false;
     PathRun r;
     r.kind = kind;
@@ -2577,6 +2590,7 @@ bool Solver::sync() {
             return fail(m);
         }
         if (flag) return fail("pressure history window overflow (a tile outside the window became non-zero)");
+        lastRun_ = plan_.kind == PathRun::Raw ? LastRun::None : LastRun::Ok;  // (raw stepping records no history)
     }
     return true;
 }
@@ -2861,6 +2875,79 @@ bool Solver::copyHistoryPlane(int t, float* pr) {
     if (!hipOk(hipMemcpyAsync(pr, scratch_, (size_t)lNX_ * g_.NY * 4, hipMemcpyDeviceToHost, stream_), "plane copy"))
         return false;
     return hipOk(hipStreamSynchronize(stream_), "plane sync");
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// room metrics (pv_metrics.hip)
+// ----------------------------------------------------------------------------------------------------------------
+
+bool Solver::computeRoomMetrics(float* ms) {
+    if (isSlab()) return fail("room metrics: not available on a slab");
+    if (opt_.streaming) return fail("room metrics: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("room metrics: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("room metrics: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("room metrics: the last run ended in error");
+    if (!metrics_ && !dalloc(&metrics_, (size_t)kRoomMetricFloats * (size_t)histPlane_, false)) return false;
+    for (auto& e : metricsEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    metricsValid_ = false;
+    metricsHostValid_ = false;
+    hipEventRecord(metricsEv_[0], stream_);
+    launchRoomMetrics(analyzeArgs(lastLx_, lastLz_), metrics_, stream_);
+    hipEventRecord(metricsEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "room metrics launch") || !hipOk(hipStreamSynchronize(stream_), "room metrics sync")) return false;
+    if (ms) hipEventElapsedTime(ms, metricsEv_[0], metricsEv_[1]);
+    metricsDyn_ = dynCur_;
+    metricsValid_ = true;
+    return true;
+}
+
+bool Solver::fetchRoomMetrics() {
+    if (!metricsValid_) return fail("room metrics: not computed for the last run and the current geometry (PvAmdComputeRoomMetrics)");
+    if (metricsHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    metricsHost_.resize((size_t)kRoomMetricFloats * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(metricsHost_.data(), metrics_, metricsHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "room metrics copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "room metrics sync"))
+        return false;
+    metricsHostValid_ = true;
+    return true;
+}
+
+bool Solver::copyRoomMetricsBlock(int r0, int c0, int nr, int nc, float* out10) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("room metrics: block outside the map");
+    if (!fetchRoomMetrics()) return false;
+    // a cell outside the run's history window is unreached by construction; inside, its record sits at its offset in a history
+    // plane (tile-major: pv_prims.h histOffset)
+    const int wr0 = metricsDyn_.histRow0 - geo_.G, wc0 = metricsDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out10 + ((size_t)r * nc + c) * kRoomMetricFloats;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < kRoomMetricFloats; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * metricsDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < kRoomMetricFloats; ++k) o[k] = metricsHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::roomMetricsAt(float ex, float ez, float out10[10]) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!metricsValid_) return fetchRoomMetrics();
+        for (int k = 0; k < kRoomMetricFloats; ++k) out10[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copyRoomMetricsBlock(cx, cy, 1, 1, out10);
 }
 
 bool Solver::copyPulse(float* out) {

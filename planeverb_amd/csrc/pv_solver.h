@@ -156,8 +156,14 @@ public:
     int numBoxes() const;
     std::vector<std::pair<int, Box>> boxes() const;
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
-    void rasterAdd(const Box& b) { mat_.add(b); }
-    void rasterRemove(const Box& b) { mat_.remove(b); }
+    void rasterAdd(const Box& b) {
+        mat_.add(b);
+        metricsValid_ = false;
+    }
+    void rasterRemove(const Box& b) {
+        mat_.remove(b);
+        metricsValid_ = false;
+    }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
     // ids of their own with the same LIFO recycling.  The
@@ -241,6 +247,12 @@ public:
     bool copyFields(float* pr, float* vx, float* vy);
     bool setFields(const float* pr, const float* vx, const float* vy);
     bool copyHistoryPlane(int t, float* pr);
+    // Room metrics (pv_metrics.hip; include/planeverb_amd.h PvAmdRoomMetrics) of the last completed run: one pass over its history
+    // on stream_, synchronised before it returns; *ms (optional) = its device time.  The records stay valid until the next run,
+    // geometry, boundary or layer change.  out10: nr x nc records of ten floats, NaN where the cell has no onset in that run
+    bool computeRoomMetrics(float* ms);
+    bool copyRoomMetricsBlock(int r0, int c0, int nr, int nc, float* out10);
+    bool roomMetricsAt(float ex, float ez, float out10[10]);
     bool copyPulse(float* out);
     bool copyMaterial(uint8_t* beta, float* R);
     bool freeFieldEnergyAt(int cellX, int cellY, int n, float r, float* out);
@@ -440,6 +452,17 @@ private:
     ResidentArgs residentArgs(const int* win) const;  // win = nullptr: the grid's own tiles
     void enqueueWindowRun(const int win[4]);
     float* scratch_ = nullptr;  // max(3T, NX*NY) floats
+    // room metrics: ten planes of histPlane_ floats, indexed by the cell's offset inside a history plane (allocated by the first
+    // computeRoomMetrics); metricsDyn_ = the window of the run they belong to; a host copy is fetched by the first read-back
+    float* metrics_ = nullptr;
+    bool metricsValid_ = false;
+    DynParams metricsDyn_{};
+    std::vector<float> metricsHost_;
+    bool metricsHostValid_ = false;
+    hipEvent_t metricsEv_[2] = {nullptr, nullptr};
+    enum class LastRun { None, Failed, Ok };  // Failed: in flight, or ended in error (a run is Ok once sync() has seen it through)
+    LastRun lastRun_ = LastRun::None;
+    bool fetchRoomMetrics();
     size_t scratchCount_ = 0;
 
     // pinned host staging
