@@ -1,4 +1,5 @@
-// pv_analysis.h -- device helpers shared by the analysis kernels of pv_kernels.hip and pv_rt60.hip (moved here unchanged)
+// pv_analysis.h -- device helpers shared by the analysis kernels (pv_analysis.hip, pv_rt60.hip, pv_fused.hip, pv_metrics.hip), the
+// read-backs of pv_copy.hip and, for fusedTile, the stencil's open-tile arm (pv_stream.h); moved here unchanged
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -97,6 +98,19 @@ __device__ __forceinline__ float efreePerR(float efree, float dx, int lX, int lY
     const float r = sqrtf((ex - lx) * (ex - lx) + (ey - ly) * (ey - ly));
     if (r == 0.f) return efree;
     return efree / r;
+}
+
+// is `tile` one whose forward sums live in the stencil?  (air class, no registered emitter, not the listener's tile -- that
+// one is on the general list for the run)
+__device__ __forceinline__ bool fusedTile(const uint8_t* tileClass, const uint8_t* tileEmit, const DynParams& dyn, int ti,
+                                          int tj, int nty, int G, int K, int rxi, int wi, int rows, int withPulse) {
+    const int t = ti * nty + tj;
+    if (tileClass[t] != 0 || tileEmit[t]) return false;
+    if (withPulse) {
+        const int lr = dyn.lrow - (G - K + ti * rxi), lc = dyn.lcol - (G - K + tj * wi);
+        if (lr >= 0 && lr < rows && lc >= 0 && lc < 64) return false;
+    }
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // pv_analysis_dev.h -- the per-cell bodies of the impulse-response analysis (Analyzer.cpp:139-431) as device functions, shared
-// by the one-pass-per-launch kernels (pv_kernels.hip, pv_rt60.hip) and the fused kernel of the small grids (pv_fused.hip).
+// by the one-pass-per-launch kernels (pv_analysis.hip, pv_rt60.hip) and the fused kernel of the small grids (pv_fused.hip).
 // Moved here from those files in round 5; the arithmetic is unchanged.
 //
 // SC1 (template flag of the functions that exchange data BETWEEN workgroups inside one launch -- the fused kernel): the delay

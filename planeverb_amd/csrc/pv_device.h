@@ -1,4 +1,4 @@
-// pv_device.h -- device-side data layout shared by the HIP kernels (pv_kernels.hip) and the host solver.
+// pv_device.h -- device-side data layout shared by the HIP kernels (the .hip files) and the host solver.
 //
 // HBM layout (all planes share one padded geometry, SoA):
 //   rows  = G + ntx*RXI + G,  pitch = roundup(G + nty*WI + G, 64) floats

@@ -1,25 +1,38 @@
-// pv_kernels.hip -- hand-written HIP kernels for gfx950 (MI355X, CDNA4): the Planeverb FDTD leapfrog stencil with
-// K time steps fused per launch, pr-history recording, and the per-cell impulse-response analysis.
+// pv_kernels.hip -- the stencil: hand-written HIP kernels for gfx950 (MI355X, CDNA4) that advance the Planeverb FDTD leapfrog
+// scheme K time steps per launch and record the pressure history, and nothing else.  What a run needs around them lives in
+// pv_run.hip (start of a run, zeroing, the one-workgroup kernel of the small grids), pv_analysis.hip (impulse-response analysis)
+// and pv_copy.hip (read-backs and copies); the walled-in room's one-launch form is pv_resident.hip.
 //
-// Reference semantics implemented here (paths relative to /root/reference/ProjectPlaneverb):
-//   pv_step_kernel      src/FDTD/FDTD.cpp:122-235   pressure / vx / vy sweeps, edge absorption, record, pulse
+// Contents, in order: the lane primitives' self-test and pv_coef_kernel; the scalar tile (stepTile); the air tile in row-pair
+// and in mirror-pair packed form; the general tile shared by four waves; the stacked air tile; the step, merged, batch and stack
+// kernels; tile classification and dead tiles; the open-tile (pv_stream.h) and, in the experimental build, segment (pv_seg.h)
+// and patch (pv_patch.h) arms; the (K, rows) configuration tables with their launchers.
+//
+// Reference semantics implemented here (paths relative to the reference's ProjectPlaneverb directory):
+//   step kernels        src/FDTD/FDTD.cpp:122-235   pressure / vx / vy sweeps, edge absorption, record, pulse
 //   pv_coef_kernel      src/FDTD/FDTD.cpp:143-223 + src/FDTD/Grid.cpp:88-108   (beta, Y, edges -> face coefficients)
-//   pv_encode_kernel    src/DSP/Analyzer.cpp:139-328  onset, dry gain, source direction, lowpass, wet, RT60
-//   pv_direction_kernel src/DSP/Analyzer.cpp:340-431  listener direction by delay-map descent
-//   pv_efree_kernel     src/FDTD/FreeGrid.cpp:96-110  free-field energy sum
-//   pv_ir_kernel        src/FDTD/FDTD.cpp:60-79       impulse response (pr, vx, vy) of one cell
 //
 // Design (MI355X-first, not a translation of the reference's three AoS sweeps):
 //   * memory-bound 5-point staggered stencil, 24 B of state per cell-step; no MFMA.
-//   * one WAVE owns one (RXI+2K) x 64 tile held entirely in VGPRs (SoA pr/vx/vy, one cell column per lane, lanes
-//     along the contiguous y axis); x-neighbours are the lane's own registers, y-neighbours come from lane+-1 by
-//     DPP wave shifts.  No LDS traffic for the fields, no barriers inside the time loop.
-//   * K leapfrog steps are advanced per launch on the tile+halo (overlapped temporal tiling): HBM traffic per
-//     cell-step drops from 24 B to about (12*(1+halo)+12)/K B.
-//   * beta, wall admittance and the absorbing grid edges are folded into one uint16 face-code per cell that indexes
-//     a 256-entry coefficient LUT in LDS; tiles whose faces are all air|air take a branch-free fast path.
-//   * float32 arithmetic in the reference's operation order; compiled with -ffp-contract=off so that
-//     v - C*(p_i - p_n) stays a separate multiply and subtract (bit-identical fields).
+//   * one WAVE owns one (RXI+2K) x 64 tile held entirely in VGPRs (SoA pr/vx/vy, one cell column per lane, lanes along the
+//     contiguous y axis); x-neighbours are the lane's own registers, y-neighbours come from lane+-1 by DPP wave shifts
+//     (pv_prims.h: the shift rides on the subtract where the operand order allows).  An air tile touches no LDS and has no
+//     barrier inside its time loop.
+//   * K leapfrog steps are advanced per launch on the tile+halo (overlapped temporal tiling): HBM traffic per cell-step drops
+//     from 24 B to about (12*(1+halo)+12)/K B.
+//   * air tiles (every face air|air, no listener) are MIRROR-PAIR register tiles: a 64-bit register pair holds row i of the
+//     tile's top half and the mirrored row of its bottom half, the bottom half's vx negated, so every difference of the three
+//     sweeps is one packed-f32 op on whole pairs and no shuffle is needed (see "air tile, MIRROR-packed" below).
+//   * every plane is reached through a buffer descriptor built from kernel arguments: the per-lane part of an address is the
+//     constant lane*4, everything wave-uniform goes into the scalar offset, and a lane outside a plane loads zero without a
+//     bounds test -- the 3*ROWS loads and stores of a tile cost no address VGPRs.
+//   * beta, wall admittance and the absorbing grid edges are folded by pv_coef_kernel into one FaceCoef {kx, ky, beta} per
+//     cell; a general tile (walls, grid edges, listener) loads them ONCE per launch into registers, its rows are shared by the
+//     four waves of a block, which exchange two boundary faces per step through LDS.
+//   * float32 arithmetic in the reference's operation order; compiled with -ffp-contract=off so that v - C*(p_i - p_n) stays
+//     a separate multiply and subtract (bit-identical fields).
+// The compiled form of the dominant kernel is part of the design: tools/check_kernel_isa.py and the DPP hazard lint of the
+// Makefile read this file's assembly (docs/experiments/step_kernel.md).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,13 +41,10 @@
 #include <climits>
 #include <cstdint>
 
+#include "pv_analysis.h"
 #include "pv_device.h"
 #include "pv_launch.h"
-#include "pv_libm.h"
 #include "pv_prims.h"
-#include "pv_analysis.h"
-#include "pv_analysis_dev.h"
-
 namespace pva {
 
 // self-test of the lane-shift primitives: out[i] = {laneNext(i), lanePrev(i)}
@@ -2227,56 +2237,6 @@ bool stepConfigSupported(int K, int rxi) {
     return false;
 }
 
-// First node of every run: per-run parameters (listener cell, history window, general-tile list) from pinned host
-// memory into HBM, per-tile bookkeeping back to "never non-zero".  Doing this in a kernel keeps the whole run a
-// chain of kernel nodes (no DMA copy or memset node whose ordering against a graph replay would matter).
-__global__ void pv_begin_run_kernel(BeginArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = min(a.dynHost->numGeneral, a.listCap);
-    if (i < n) a.list[i] = a.listHost[i];
-    if (a.segHost && i < min(a.dynHost->numSeg, a.segCap)) a.seg[i] = a.segHost[i];
-    if (i == 0) {
-        *a.dyn = *a.dynHost;
-        *a.errFlag = 0;
-    }
-    if (i < a.nbands) a.dynBands[i] = a.dynBandsHost[i];
-    if (i < a.nZero) a.zeroWords[i] = 0u;
-    if (a.tileFirst && i < a.ntiles) {
-        a.tileFirst[i] = a.tileFirstInit;
-        a.nz0[i] = 0;
-        a.nz1[i] = 0;
-        if (a.tileOpen) a.tileOpen[i] = 1;
-    }
-}
-
-__global__ void pv_zero_kernel(float4* p, long long n4) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n4) p[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-void launchZero(float* p, long long n, hipStream_t stream) {
-    const long long n4 = n / 4;
-    hipLaunchKernelGGL(pv_zero_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (float4*)p, n4);
-}
-
-// rows [r0, r0 + nr) x columns [c0, c0 + nc) of six planes of pitch `pitch` floats (blockIdx.y = plane)
-__global__ void pv_zero_rect_kernel(ZeroRectArgs z) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= z.nr * z.nc) return;
-    const int r = i / z.nc;
-    z.p[blockIdx.y][(long long)(z.r0 + r) * z.pitch + z.c0 + (i - r * z.nc)] = 0.f;
-}
-void launchZeroRect(const ZeroRectArgs& z, hipStream_t stream) {
-    if (z.nr <= 0 || z.nc <= 0) return;
-    hipLaunchKernelGGL(pv_zero_rect_kernel, dim3((unsigned)((z.nr * z.nc + 255) / 256), 6), dim3(256), 0, stream, z);
-}
-
-void launchBeginRun(const BeginArgs& a, hipStream_t stream) {
-    int n = a.ntiles > a.listCap ? a.ntiles : a.listCap;
-    if (a.segHost && a.segCap > n) n = a.segCap;
-    if (a.nZero > n) n = a.nZero;
-    hipLaunchKernelGGL(pv_begin_run_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a);
-}
-
 void launchCoefs(const float* mat, FaceCoef* coef, const Geometry& g, hipStream_t stream) {
     dim3 grid((g.pitch + 255) / 256, g.rows);
     hipLaunchKernelGGL(pv_coef_kernel, grid, dim3(256), 0, stream, mat, coef, g);
@@ -2284,1101 +2244,6 @@ void launchCoefs(const float* mat, FaceCoef* coef, const Geometry& g, hipStream_
 
 void launchLaneSelfTest(float* out, hipStream_t stream) {
     hipLaunchKernelGGL(pv_lane_selftest_kernel, dim3(1), dim3(64), 0, stream, out);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// whole-grid-resident stencil for small grids
-// ---------------------------------------------------------------------------------------------------------------
-
-// Grids up to ~110^2 cells (the sandbox default is 71^2, the Unity demo 38^2) fit one CU: the three fields live in
-// LDS for the whole run (160 KiB per CU on MI355X), each of the 1024 threads owns up to CPT cells whose state and
-// face coefficients stay in registers, and ALL T time steps run inside one launch with two workgroup barriers per
-// step.  Per step a cell reads its four neighbour values from LDS (vx[x+1], vy[y+1] for the pressure update,
-// p[x-1], p[y-1] for the velocity update) and writes its three new values back; the pressure history row is stored
-// to HBM as it is produced.  This replaces ~110 launch-bound kernel launches per run by one.
-constexpr int kSmallThreads = 1024;
-constexpr int kSmallCpt = 12;
-constexpr int kSmallLdsBytes = 160 * 1024;
-
-__host__ __device__ inline int smallLdsFloats(int NX, int NY) { return 3 * ((NX + 2) * NY + 2); }
-
-bool smallGridFits(int NX, int NY) {
-    return NX * NY <= kSmallThreads * kSmallCpt && smallLdsFloats(NX, NY) * 4 <= kSmallLdsBytes;
-}
-
-__global__ __launch_bounds__(kSmallThreads) void pv_small_grid_kernel(const SmallArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int NX = a.NX, NY = a.NY;
-    const int cells = NX * NY;
-    const int plane = (NX + 2) * NY + 2;  // one guard row above and below, +2 slack for the y+1 read of the last cell
-    float* sp = smem + NY;                // cell (x, y) at sp[x*NY + y]; sp[-NY .. -1] is the zero guard row
-    float* sx = sp + plane;
-    float* sy = sx + plane;
-    for (int i = threadIdx.x; i < 3 * plane; i += kSmallThreads) smem[i] = 0.f;
-
-    const DynParams dyn = *a.dyn;
-    const float C = a.courant;
-    const int lcell = (dyn.lrow >= a.G && dyn.lcol >= a.G) ? (dyn.lrow - a.G) * NY + (dyn.lcol - a.G) : -1;
-
-    float p[kSmallCpt], vx[kSmallCpt], vy[kSmallCpt], kx[kSmallCpt], ky[kSmallCpt];
-    int hoff[kSmallCpt];
-    unsigned beta = 0;
-#pragma unroll
-    for (int j = 0; j < kSmallCpt; ++j) {
-        const int i = threadIdx.x + j * kSmallThreads;
-        p[j] = vx[j] = vy[j] = 0.f;
-        kx[j] = ky[j] = 0.f;
-        hoff[j] = 0;
-        if (i < cells) {
-            const int x = i / NY, y = i - x * NY;
-            const size_t ci = (size_t)(x + a.G) * a.pitch + (y + a.G);
-            const FaceCoef c = a.coef[ci];
-            kx[j] = c.kx;
-            ky[j] = c.ky;
-            if (c.beta != 0.f) beta |= 1u << j;
-            hoff[j] = (int)histOffset(x + a.G - dyn.histRow0, y + a.G - dyn.histCol0, a.rxi, a.wi, dyn.histTilesY);
-        }
-    }
-    __syncthreads();
-
-    float* hplane = a.hist;
-#pragma unroll 1
-    for (int t = 0; t < a.T; ++t) {
-        // pressure, FDTD.cpp:124-141 (reads past the last row / element hit the zero guard and are times beta = 0)
-#pragma unroll
-        for (int j = 0; j < kSmallCpt; ++j) {
-            const int i = threadIdx.x + j * kSmallThreads;
-            if (i < cells) {
-                const float div = (sx[i + NY] - vx[j]) + (sy[i + 1] - vy[j]);
-                const float pn = p[j] - C * div;
-                p[j] = (beta >> j) & 1u ? pn : 0.f;
-                sp[i] = p[j];
-            }
-        }
-        __syncthreads();
-        // velocities, FDTD.cpp:143-223 through the face coefficients; record, FDTD.cpp:226-230
-#pragma unroll
-        for (int j = 0; j < kSmallCpt; ++j) {
-            const int i = threadIdx.x + j * kSmallThreads;
-            if (i < cells) {
-                const float pi = p[j];
-                const float pxn = sp[i - NY];
-                const float pyn = (i > 0) ? sp[i - 1] : 0.f;
-                const float ax = vx[j] - C * (pi - pxn), wx = kx[j] * (pi + pxn);
-                const float ay = vy[j] - C * (pi - pyn), wy = ky[j] * (pi + pyn);
-                vx[j] = (kx[j] != kx[j]) ? ax : wx;
-                vy[j] = (ky[j] != ky[j]) ? ay : wy;
-                sx[i] = vx[j];
-                sy[i] = vy[j];
-                if (a.record) hplane[hoff[j]] = pi;
-                if (i == lcell) p[j] = pi + a.pulse[t];  // soft source after the record, FDTD.cpp:234
-            }
-        }
-        hplane += a.histPlane;
-        __syncthreads();
-    }
-#pragma unroll
-    for (int j = 0; j < kSmallCpt; ++j) {
-        const int i = threadIdx.x + j * kSmallThreads;
-        if (i < cells) {
-            const int x = i / NY, y = i - x * NY;
-            const size_t o = (size_t)(x + a.G) * a.pitch + (y + a.G);
-            a.prOut[o] = p[j];
-            a.vxOut[o] = vx[j];
-            a.vyOut[o] = vy[j];
-        }
-    }
-}
-
-void launchSmallGrid(const SmallArgs& a, hipStream_t stream) {
-    static bool attr = false;
-    if (!attr) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(pv_small_grid_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kSmallLdsBytes);
-        attr = true;
-    }
-    const size_t lds = (size_t)smallLdsFloats(a.NX, a.NY) * 4;
-    hipLaunchKernelGGL(pv_small_grid_kernel, dim3(1), dim3(kSmallThreads), lds, stream, a);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// impulse-response analysis
-// ---------------------------------------------------------------------------------------------------------------
-
-// pvLog10f / pvPowf: glibc-2.35-exact log10f and powf, see pv_libm.h
-
-// CH samples (i0, i0-1, ..., i0-CH+1; those below startingPoint are skipped) of the backward Schroeder integration
-// + regression sums, Analyzer.cpp:300-318.  Three passes over the chunk: the running energy (sequential, the
-// reference's order), 10*log10f of each partial sum (independent of each other: branch-free, so the compiler
-// interleaves the CH evaluations -- with one thread per cell and few waves this loop is bound by the latency of one
-// evaluation, ~1800 cycles per sample when they ran one after the other), the two regression sums (sequential).
-template <int CH>
-__device__ __forceinline__ void rt60Chunk(const float (&pc)[CH], const int i0, const int startingPoint, float& edc,
-                                          float& xysum, float& ysum) {
-    float e[CH], y[CH];
-#pragma unroll
-    for (int k = 0; k < CH; ++k) {
-        edc = (i0 - k >= startingPoint) ? edc + pc[k] * pc[k] : edc;
-        e[k] = edc;
-    }
-#pragma unroll
-    for (int k = 0; k < CH; ++k) y[k] = 10.f * pvLog10fNonNeg(e[k]);
-#pragma unroll
-    for (int k = 0; k < CH; ++k) {
-        const bool v = i0 - k >= startingPoint;
-        xysum = v ? xysum + y[k] * (float)(i0 - k - startingPoint) : xysum;
-        ysum = v ? ysum + y[k] : ysum;
-    }
-}
-
-// One thread per result cell (X, Y); lanes along Y so every history read is a coalesced row segment of one
-// recorded plane.  All sums are sequential float32 accumulations in the reference's order.
-// vx / vy are not stored: they are re-derived from the pressure history with the stencil's own recurrence
-// (v_t = v_{t-1} - C*(p_t[i] - p_t[n]) on air|air faces, k*(p_i + p_n) otherwise), bit-identical to the values
-// the step kernel held.
-// The analysis kernels run over the HISTORY WINDOW only (winRows x winCols cells from the window's origin, which
-// lives in dyn so that the launch grid does not depend on the listener): a cell outside it cannot have been reached
-// by the pulse.  What the reference computes for such a cell -- delay = FLT_MAX, direction = the unit vector from
-// the listener to the cell itself -- is written for the whole map by pv_far_cells_kernel first.  (The first version
-// launched one thread per grid cell: 67 M threads at 8192^2 to find the 0.6 M reached cells.)
-__device__ __forceinline__ bool analysisWindowCell(const AnalyzeArgs& a, const DynParams& dyn, int* X, int* Y) {
-    const int wc = blockIdx.x * blockDim.x + threadIdx.x, wr = blockIdx.y;
-    if (wc >= a.winCols) return false;
-    *X = dyn.histRow0 - a.G + wr;
-    *Y = dyn.histCol0 - a.G + wc;
-    return *X < a.gx && *Y < a.gy;
-}
-
-// Onset of every window cell (Analyzer.cpp:146-165: first sample whose |pressure| exceeds the audible threshold), round 5.
-// Rounds 1-4 found it inside pv_encode_kernel, one thread per cell walking forward through time: the kernel lasted as long as
-// its slowest thread, and the slowest threads were the SILENT cells -- air cells of a reached tile that never become audible
-// (the air outside a closed room, in the tiles its walls cross): all T samples, 16 per memory round trip, 280 us of a 370 us
-// kernel at 512^2 / T = 3179 -- and the decay-time pass could only start behind it.  Here the search is parallel IN TIME: a
-// block is 64 consecutive cells of the tile-major plane (planeCell: one coalesced 256-byte read per plane) x 16 waves, wave w
-// scans the samples t = tBeg + (16 j + w) 16 + k; the earliest hit per cell is kept with an LDS minimum, and a wave stops once
-// no cell of the block can improve.  A silent cell costs T / 256 round trips instead of T / 16.  pv_encode_kernel and the
-// decay-time kernels read the onset from the delay map, side by side on two streams.
-#ifndef PV_ONSET_WAVES
-#define PV_ONSET_WAVES 4
-#endif
-#ifndef PV_ONSET_SC
-#define PV_ONSET_SC 32
-#endif
-constexpr int kOnsetWaves = PV_ONSET_WAVES, kOnsetSC = PV_ONSET_SC;
-__global__ __launch_bounds__(64 * kOnsetWaves) void pv_onset_kernel(const AnalyzeArgs a) {
-    __shared__ int found[64];
-    if (analysisAborted(a)) return;
-    const DynParams dyn = *a.dyn;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long long g = (long long)blockIdx.x * 64 + lane;
-    const PlaneCell c = planeCell(a, dyn, g);
-    const int T = a.T;
-    int tF = INT_MAX;
-    bool live = c.inGrid;
-    if (live) {
-        tF = a.tileFirst[c.tile];
-        // never reached by the pulse, or a wall (beta = 0: pr is identically zero, FDTD.cpp:139): no onset
-        live = tF < T && a.coef[(size_t)(c.X + a.G) * a.pitch + (c.Y + a.G)].beta != 0.f;
-    }
-    const bool air = live;  // (an air cell of a reached tile: without an onset it counts as silent)
-    if (a.labels) {
-        // ... nor has a cell that no chain of air cells joins to the listener's (AnalyzeArgs::labels): not scanned
-        const int lX = dyn.lrow - a.G, lY = dyn.lcol - a.G;
-        const int mine = live ? a.labels[(size_t)c.X * a.labelNY + c.Y] : -1;
-        const int theirs = (lX >= 0 && lX <= a.gx && lY >= 0 && lY < a.labelNY) ? a.labels[(size_t)lX * a.labelNY + lY] : -2;
-        live = live && mine == theirs;
-    }
-    if (wave == 0) found[lane] = INT_MAX;
-    if (a.stamp && blockIdx.x == 0 && threadIdx.x == 0) a.stamp[1] = wall_clock64();
-    __syncthreads();
-    // near box (AnalyzeArgs::box): the cells the PREVIOUS run reached get "no onset" back unless this run reaches them again --
-    // every other cell of the map holds it already.  A cell of this window is its own lane's business (below, and where the
-    // search ends); the previous box's cells OUTSIDE this window (the listener moved far) are dealt over the workgroups here.
-    bool inPrev = false;
-    if (a.box) {
-        const int p0 = a.prevBox[0], p1 = a.prevBox[1], p2 = min(a.prevBox[2], a.gx - 1), p3 = min(a.prevBox[3], a.gy - 1);
-        inPrev = c.inGrid && c.X >= p0 && c.X <= p2 && c.Y >= p1 && c.Y <= p3;
-        if (p2 >= p0 && p3 >= p1) {  // (empty: INT_MAX / -1 -- no arithmetic on those)
-            const int wr0 = dyn.histRow0 - a.G, wc0 = dyn.histCol0 - a.G;
-            const int wr1 = wr0 + min(a.winRows, a.gx - wr0) - 1, wc1 = wc0 + min(a.winCols, a.gy - wc0) - 1;
-            if (p0 < wr0 || p2 > wr1 || p1 < wc0 || p3 > wc1)  // (block-uniform)
-                for (int r = p0 + (int)blockIdx.x; r <= p2; r += (int)gridDim.x)
-                    for (int cc = p1 + (int)threadIdx.x; cc <= p3; cc += (int)blockDim.x)
-                        if (r < wr0 || r > wr1 || cc < wc0 || cc > wc1) a.delay[r * a.gy + cc] = FLT_MAX;
-        }
-    }
-    if (a.wholeWindow || a.box) {
-        // no far-frame launch in front of this one: "no onset" for the cells that will not get one, and the count of active cells
-        // (what pv_far_frame_kernel's first block does; the run's last kernel has left the other counters at zero)
-        if (wave == 0 && c.inGrid && !live && (a.wholeWindow || inPrev)) a.delay[c.X * a.gy + c.Y] = FLT_MAX;
-        if (blockIdx.x == 0 && wave == 1) {
-            int n = 0;
-            for (int i = lane; i < dyn.histTilesX * dyn.histTilesY; i += 64) {
-                const int ti = dyn.histTileX0 + i / dyn.histTilesY, tj = dyn.histTileY0 + i % dyn.histTilesY;
-                if (a.tileFirst[ti * a.nty + tj] < T) n += a.rxi * a.wi;
-            }
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) n += __shfl_xor(n, off);
-            if (lane == 0) a.activeCount[0] = n;
-        }
-    }
-    if (__ballot(live) == 0ull) {  // (the same lanes in every wave of the block: block-uniform)
-        const unsigned long long ms = __ballot(air);
-        if (wave == 0 && lane == 0 && ms) atomicAdd(a.activeCount + 3, __popcll(ms));
-        return;
-    }
-    // A run starts from zero fields and the stencil moves a value by one cell per step along one axis (FDTD.cpp:124-199): the
-    // recorded pressure of a cell at Manhattan distance m from the listener is exactly zero up to and including step m,
-    // whatever the geometry.  The search starts there (cells far from the listener: half the samples between the tile's first
-    // recorded step and the onset).  No listener in the grid: no pulse, no onset.
-    const int m = abs(c.X - (dyn.lrow - a.G)) + abs(c.Y - (dyn.lcol - a.G));
-    const int tS = live ? min(max(tF, m), T) : INT_MAX;
-    int tBeg = tS;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) tBeg = min(tBeg, __shfl_xor(tBeg, off));
-    tBeg = __builtin_amdgcn_readfirstlane(tBeg);  // (wave-uniform by value: scalar loop counter, scalar descriptors)
-    const int voff = (int)g * 4;
-    const int planeBytes = (int)(a.histPlane * 4);
-    constexpr int SC = kOnsetSC;
-#pragma unroll 1
-    for (int t = tBeg + wave * SC; t < T; t += kOnsetWaves * SC) {
-        const int best = found[lane];
-        if (__ballot(live && best > t) == 0ull) break;  // nothing at or after t can be the first
-        float pc[SC];
-#pragma unroll
-        for (int k = 0; k < SC; ++k) {
-            const int tt = t + k;
-            const bool want = live && tt >= tS && tt < T && tt < best;  // (a tile's history starts at its first recorded step)
-            pc[k] = bufLoadF(makeRsrc(a.hist + (long long)min(tt, T - 1) * a.histPlane, planeBytes), want ? voff : 0x7fffffff, 0);
-        }
-        int hit = INT_MAX;
-#pragma unroll
-        for (int k = SC - 1; k >= 0; --k) hit = fabsf(pc[k]) > kAudibleThresholdDev ? t + k : hit;
-        if (hit != INT_MAX) atomicMin(&found[lane], hit);
-    }
-    __syncthreads();
-    if (wave != 0) return;
-    const int onset = found[lane];
-    if (live) {
-        if (onset != INT_MAX) a.delay[c.X * a.gy + c.Y] = (float)onset;
-        else if (a.wholeWindow || inPrev) a.delay[c.X * a.gy + c.Y] = FLT_MAX;
-    }
-    // reached cells of this run (bench / PvAmdTimings.reachedCells) and silent ones: one atomic each per block
-    const bool reached = live && onset != INT_MAX;
-    const unsigned long long mr = __ballot(reached), ms = __ballot(air && !reached);
-    if (a.box && mr) {  // the reached cells' bounding box (AnalyzeArgs::box): four atomics per group with work
-        int r0 = reached ? c.X : INT_MAX, c0 = reached ? c.Y : INT_MAX, r1 = reached ? c.X : -1, c1 = reached ? c.Y : -1;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            r0 = min(r0, __shfl_xor(r0, off));
-            c0 = min(c0, __shfl_xor(c0, off));
-            r1 = max(r1, __shfl_xor(r1, off));
-            c1 = max(c1, __shfl_xor(c1, off));
-        }
-        // (an atomic only where the group can still move a bound: in an open field 4 300 groups have work, and four atomics each on
-        // the same four words took 330 us of the kernel -- same-address atomics are served one after the other; the plain reads
-        // may be stale, which only means an atomic that changes nothing)
-        if (lane == 0) {
-            const int b0 = __hip_atomic_load(a.box + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int b1 = __hip_atomic_load(a.box + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int b2 = __hip_atomic_load(a.box + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int b3 = __hip_atomic_load(a.box + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (r0 < b0) atomicMin(a.box + 0, r0);
-            if (c0 < b1) atomicMin(a.box + 1, c0);
-            if (r1 > b2) atomicMax(a.box + 2, r1);
-            if (c1 > b3) atomicMax(a.box + 3, c1);
-        }
-    }
-    if (lane == 0) {
-        if (mr) {
-            atomicAdd(a.activeCount + 1, __popcll(mr));
-            a.unitList[atomicAdd(a.activeCount + 4, 1)] = (int)blockIdx.x;  // this group of 64 cells has work for the passes behind
-        }
-        if (ms) atomicAdd(a.activeCount + 3, __popcll(ms));
-    }
-}
-
-// dry gain, source directivity, low-pass cutoff (+ wet gain beside the lane-per-cell decay-time form) of the cells that have an
-// onset, behind pv_onset_kernel: one wave per entry of the list of 64-cell groups with work (encodeWave, pv_analysis_dev.h)
-__global__ __launch_bounds__(256) void pv_encode_kernel(const AnalyzeArgs a) {
-    if (analysisAborted(a)) return;
-    const DynParams dyn = *a.dyn;
-    const int unit = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
-    if (unit >= a.activeCount[4]) return;
-    const PlaneCell pc0 = planeCell(a, dyn, (long long)a.unitList[unit] * 64 + (threadIdx.x & 63));
-    const float delay = pc0.inGrid ? a.delay[pc0.X * a.gy + pc0.Y] : FLT_MAX;
-    const bool live = delay != FLT_MAX;  // no onset (Analyzer.cpp:160-165): the result record stays as it is
-    if (__ballot(live) == 0ull) return;
-    encodeWave<false>(a, dyn, pc0, live, live ? (int)delay : 0, rt60LanesPerCell(a, a.activeCount[1]) == 1);
-}
-
-// the same pass with L lanes per cell (encodeGroups, pv_analysis_dev.h): the small windows, where the longest walk is the kernel.
-// A 64-cell group of the list is L waves: L / 4 workgroups
-template <int L>
-__global__ __launch_bounds__(256) void pv_encode_groups_kernel(const AnalyzeArgs a) {
-    if (analysisAborted(a)) return;
-    const DynParams dyn = *a.dyn;
-    constexpr int BPU = L / 4;  // workgroups per group of 64 cells
-    const int unit = blockIdx.x / BPU;
-    if (unit >= a.activeCount[4]) return;
-    const int ww = (blockIdx.x % BPU) * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const PlaneCell pc0 = planeCell(a, dyn, (long long)a.unitList[unit] * 64 + ww * (64 / L) + lane / L);
-    const float delay = pc0.inGrid ? a.delay[pc0.X * a.gy + pc0.Y] : FLT_MAX;
-    const bool live = delay != FLT_MAX;
-    if (__ballot(live) == 0ull) return;
-    encodeGroups<L, false>(a, dyn, pc0, lane % L, live, live ? (int)delay : 0);
-}
-
-// every cell of the map: no onset (Analyzer.cpp:64-68), listener direction = towards the cell itself (a walk that
-// finds no neighbour with a smaller delay stays where it is, Analyzer.cpp:365-391).  The window's cells are
-// overwritten by the kernels that follow.
-// Upper bound of the cells the pulse reached: the cells of the window's tiles that were ever non-zero.  Computed by
-// block 0 of pv_far_cells_kernel (the first launch of the analysis); its result chooses, on the device, between the
-// cell form (inside pv_encode_kernel) and the wave form of the wet gain / decay time.
-__device__ __forceinline__ void countActiveCells(const AnalyzeArgs& a) {
-    __shared__ int part[256];
-    const DynParams dyn = *a.dyn;
-    int n = 0;
-    for (int i = threadIdx.x; i < dyn.histTilesX * dyn.histTilesY; i += 256) {
-        const int ti = dyn.histTileX0 + i / dyn.histTilesY, tj = dyn.histTileY0 + i % dyn.histTilesY;
-        if (a.tileFirst[ti * a.nty + tj] < a.T) n += a.rxi * a.wi;
-    }
-    part[threadIdx.x] = n;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        a.activeCount[0] = part[0];
-        a.activeCount[1] = 0;
-        a.activeCount[3] = 0;
-        a.activeCount[4] = 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void pv_far_cells_kernel(const AnalyzeArgs a) {
-    if (analysisAborted(a)) return;  // (grid-uniform)
-    if (blockIdx.x == 0 && a.tileFirst) countActiveCells(a);  // (before any thread leaves: the reduction has barriers)
-    const int index = blockIdx.x * blockDim.x + threadIdx.x;
-    if (index >= a.gx * a.gy) return;
-    a.delay[index] = FLT_MAX;
-    storeDirection(a, index, index);
-}
-
-// The far-cell pass restricted to where something can have changed: blockIdx.z = 0 the previous run's window block,
-// 1 this run's.  Every cell of both gets "no onset" and the default direction; the kernels that follow overwrite this
-// run's reached cells.  All other cells of the map keep delay = FLT_MAX from the solver's creation / their own last reset,
-// and their direction is made on demand (pv_far_dir_kernel, farDirectionOf).
-__global__ __launch_bounds__(256) void pv_far_frame_kernel(const AnalyzeArgs a) {
-    if (analysisAborted(a)) return;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && a.tileFirst) countActiveCells(a);
-    const DynParams dyn = *a.dyn;
-    int r0, c0, nr, nc;
-    if (blockIdx.z == 0) {
-        r0 = a.prevR0, c0 = a.prevC0, nr = a.prevNR, nc = a.prevNC;
-    } else {
-        r0 = dyn.histRow0 - a.G, c0 = dyn.histCol0 - a.G;
-        nr = min(a.winRows, a.gx - r0), nc = min(a.winCols, a.gy - c0);
-    }
-    const int wc = blockIdx.x * blockDim.x + threadIdx.x, wr = blockIdx.y;
-    if (wc >= nc || wr >= nr) return;
-    const int index = (r0 + wr) * a.gy + (c0 + wc);
-    a.delay[index] = FLT_MAX;
-    storeDirection(a, index, index);
-}
-
-// the cells a listener-direction pass covers: one thread per cell of the window block -- with a near box only the cells inside
-// it (the workgroups of the other rows and column blocks leave at once: a closed room's box is ~90 of the window's 3 500
-// workgroups.  A bounded grid whose workgroups stride over the box was measured first: fine for that room, but an open field's
-// box IS the window, and three cells per thread one after the other tripled these latency-bound passes -- 8192^2 open field
-// analysis 0.41 -> 0.75 ms)
-template <class F>
-__device__ __forceinline__ void forDirectionCells(const AnalyzeArgs& a, const DynParams& dyn, F&& f) {
-    int X, Y;
-    if (!analysisWindowCell(a, dyn, &X, &Y)) return;
-    if (a.box && !nearBoxOf(a, dyn).holds(X, Y)) return;
-    f(X * a.gy + Y);
-}
-
-// (farDirectionOf / isFarCell: pv_analysis.h)
-
-// materialise the direction planes of the far cells (whole-map read-backs)
-__global__ __launch_bounds__(256) void pv_far_dir_kernel(float* __restrict__ dirX, float* __restrict__ dirY, long long n,
-                                                         const FarInfo f) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n || !isFarCell(f, i)) return;
-    float ox, oy;
-    farDirectionOf(f, i, &ox, &oy);
-    dirX[i] = ox;
-    dirY[i] = oy;
-}
-
-void launchFarDirections(float* res, long long n, const FarInfo& f, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_far_dir_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, res + 4 * n, res + 5 * n, n, f);
-}
-
-void launchFillDelay(float* delay, long long n, hipStream_t stream);
-
-__device__ __forceinline__ void directionWalkCell(const AnalyzeArgs& a, const int index) {
-    float loudness = a.out[index];
-    int cur = index;
-    float delay = FLT_MAX;
-    const float samplingRate = (float)a.fs;
-    const float wavelength = kCDev / (float)a.res;
-    const float thresholdDist = 0.3f * wavelength;
-
-    while (delay > kDelayCloseDev && loudness < kDistanceGainDev) {
-        const int r = cur / a.gy, c = cur - r * a.gy;
-        float bestLoud = 0.f, bestDelay = FLT_MAX;
-        for (int i = 0; i < 8; ++i) {
-            const int nr = r + neighbourDr(i), nc = c + neighbourDc(i);
-            if (nr < 0 || nc < 0 || nr >= a.gx || nc >= a.gy) continue;
-            const int ni = nr * a.gy + nc;
-            const float occ = a.out[ni];
-            const float d = a.delay[ni];
-            if (occ == 0.f) continue;               // Analyzer.cpp:372 (the (unsigned)delay test never fires)
-            if (d < bestDelay && occ > 0.f) {       // strict <: first neighbour wins ties
-                bestLoud = occ;
-                cur = ni;                           // kept even if the step is rejected below (Analyzer.cpp:377)
-                bestDelay = d;
-            }
-        }
-        if (bestDelay == FLT_MAX || bestDelay >= delay) break;
-        delay = bestDelay;
-        loudness = bestLoud;
-        // line-of-sight test, Analyzer.cpp:393-411
-        const float geodesic = kCDev * bestDelay / samplingRate;
-        const int r2 = cur / a.gy, c2 = cur - r2 * a.gy;
-        const float tx = (float)r2 * a.dx - a.lx, ty = (float)c2 * a.dx - a.lz;
-        const float euclid = sqrtf((tx * tx) + (ty * ty));
-        if (fabsf(geodesic - euclid) < thresholdDist) break;
-    }
-    storeDirection(a, index, cur);
-}
-__global__ __launch_bounds__(256) void pv_direction_kernel(const AnalyzeArgs a) {
-    if (analysisAborted(a)) return;
-    const DynParams dyn = *a.dyn;
-    forDirectionCells(a, dyn, [&](const int index) { directionWalkCell(a, index); });
-}
-
-// listener direction by pointer jumping: the per-cell steps are dirInitCell / dirJumpCell / dirFinalCell (pv_analysis_dev.h)
-__global__ __launch_bounds__(256) void pv_dir_init_kernel(const AnalyzeArgs a, int* J) {
-    if (analysisAborted(a)) return;
-    const DynParams dyn = *a.dyn;
-    forDirectionCells(a, dyn, [&](const int p) { dirInitCell<false>(a, dyn, J, p); });
-}
-
-__global__ __launch_bounds__(256) void pv_dir_jump_kernel(const AnalyzeArgs a, int* J) {
-    if (analysisAborted(a)) return;
-    const DynParams dyn = *a.dyn;
-    forDirectionCells(a, dyn, [&](const int p) { dirJumpCell<false>(a, dyn, J, p); });
-}
-
-__global__ __launch_bounds__(256) void pv_dir_final_kernel(const AnalyzeArgs a, const int* J) {
-    if (analysisAborted(a)) return;
-    const DynParams dyn = *a.dyn;
-    forDirectionCells(a, dyn, [&](const int p) { dirFinalCell<false>(a, dyn, J, p); });
-}
-
-static dim3 analysisWindowGrid(const AnalyzeArgs& a) { return dim3((a.winCols + 255) / 256, a.winRows); }
-
-static void launchDirectionJump(const AnalyzeArgs& a, int* J, hipStream_t stream) {
-    const dim3 grid = analysisWindowGrid(a), block(256);
-    hipLaunchKernelGGL(pv_dir_init_kernel, grid, block, 0, stream, a, J);
-    for (int i = 0; i < dirJumpPasses(a.T); ++i) hipLaunchKernelGGL(pv_dir_jump_kernel, grid, block, 0, stream, a, J);
-    hipLaunchKernelGGL(pv_dir_final_kernel, grid, block, 0, stream, a, J);
-}
-
-__global__ void pv_fill_delay_kernel(float* delay, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) delay[i] = FLT_MAX;  // Analyzer.cpp:64-68
-}
-
-// SoA result planes -> the reference's array of PlaneverbOutput structs (AnalyzerResult, Analyzer.h:11-22)
-__global__ void pv_pack_results_kernel(const float* __restrict__ res, long long n, float* __restrict__ res8) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float4 lo = make_float4(res[i], res[n + i], res[2 * n + i], res[3 * n + i]);
-    float4 hi = make_float4(res[4 * n + i], res[5 * n + i], res[6 * n + i], res[7 * n + i]);
-    reinterpret_cast<float4*>(res8)[2 * i] = lo;
-    reinterpret_cast<float4*>(res8)[2 * i + 1] = hi;
-}
-
-// the nr x nc block of the result map whose first cell is (r0, c0) as AoS records (the live module publishes only
-// the history window's block of every iteration: everything outside it is stale values + a closed-form direction)
-__global__ void pv_pack_window_kernel(const float* __restrict__ res, long long n, int gy, int r0, int c0, int nr, int nc,
-                                      float* __restrict__ out8, const FarInfo f) {
-    const int wc = blockIdx.x * blockDim.x + threadIdx.x, wr = blockIdx.y;
-    if (wc >= nc || wr >= nr) return;
-    const long long i = (long long)(r0 + wr) * gy + (c0 + wc);
-    const long long o = (long long)wr * nc + wc;
-    float4 lo = make_float4(res[i], res[n + i], res[2 * n + i], res[3 * n + i]);
-    float4 hi = make_float4(res[4 * n + i], res[5 * n + i], res[6 * n + i], res[7 * n + i]);
-    if (isFarCell(f, i)) farDirectionOf(f, i, &hi.x, &hi.y);  // (a far cell: its direction is not in the planes)
-    reinterpret_cast<float4*>(out8)[2 * o] = lo;
-    reinterpret_cast<float4*>(out8)[2 * o + 1] = hi;
-}
-
-void launchPackWindow(const float* res, long long n, int gy, int r0, int c0, int nr, int nc, float* out8, const FarInfo& far,
-                      hipStream_t stream) {
-    if (nr <= 0 || nc <= 0) return;
-    hipLaunchKernelGGL(pv_pack_window_kernel, dim3((unsigned)((nc + 255) / 256), (unsigned)nr), dim3(256), 0, stream, res,
-                       n, gy, r0, c0, nr, nc, out8, far);
-}
-
-// one cell of the result map -> 8 floats in pinned host memory (Analyzer::GetResponseResult, Analyzer.cpp:106-116)
-__global__ void pv_gather_output_kernel(const float* __restrict__ res, long long n, long long cell, float* out8,
-                                        const FarInfo f) {
-    if (threadIdx.x < 8) {
-        float v = res[threadIdx.x * n + cell];
-        if ((threadIdx.x == 4 || threadIdx.x == 5) && isFarCell(f, cell)) {  // a far cell: its direction is not in the planes
-            float ox, oy;
-            farDirectionOf(f, cell, &ox, &oy);
-            v = threadIdx.x == 4 ? ox : oy;
-        }
-        out8[threadIdx.x] = v;
-    }
-}
-
-void launchGatherOutput(const float* res, long long n, long long cell, float* out8Host, const FarInfo& f, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_gather_output_kernel, dim3(1), dim3(64), 0, stream, res, n, cell, out8Host, f);
-}
-
-// the registered output queries of a run (PvAmdSetOutputQueries): nq result cells -> nq x 8 floats in pinned host
-// memory, enqueued behind the analysis so that the caller's one stream sync also delivers the outputs.
-// cells[] lives in pinned host memory too (cell < 0: position outside the result map, left to the host's sentinel)
-__global__ void pv_gather_queries_kernel(const float* __restrict__ res, long long n, const long long* cells, int nq,
-                                         float* out, const FarInfo f) {
-    const int q = threadIdx.x >> 3, k = threadIdx.x & 7;
-    if (q < nq) {
-        const long long c = cells[q];
-        float v = c >= 0 ? res[k * n + c] : 0.f;
-        if (c >= 0 && (k == 4 || k == 5) && isFarCell(f, c)) {
-            float ox, oy;
-            farDirectionOf(f, c, &ox, &oy);
-            v = k == 4 ? ox : oy;
-        }
-        out[q * 8 + k] = v;
-    }
-}
-
-void launchGatherQueries(const float* res, long long n, const long long* cellsHost, int nq, float* outHost, const FarInfo& f,
-                         hipStream_t stream) {
-    hipLaunchKernelGGL(pv_gather_queries_kernel, dim3(1), dim3(512), 0, stream, res, n, cellsHost, nq, outHost, f);
-}
-
-void launchPackResults(const float* res, long long n, float* res8, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_pack_results_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, res, n, res8);
-}
-
-// One row of the history window over all T steps as a dense [T][histPitch] array (zeros where the tile had not been
-// reached yet): what the slab BELOW this one needs for the vx recurrence of its first row (AnalyzeArgs::histAbove).
-__global__ void pv_hist_row_kernel(const AnalyzeArgs a, int X, float* __restrict__ out) {
-    const int wc = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
-    if (wc >= a.histPitch || t >= a.T) return;
-    const DynParams dyn = *a.dyn;
-    const int pcol = dyn.histCol0 + wc, prow = X + a.G;
-    float v = 0.f;
-    const int ti = X / a.rxi, tj = (pcol - a.G) / a.wi;
-    const int wti = ti - dyn.histTileX0, wtj = tj - dyn.histTileY0;
-    if (wc < a.winCols && pcol >= a.G && wti >= 0 && wti < dyn.histTilesX && wtj >= 0 && wtj < dyn.histTilesY &&
-        t >= a.tileFirst[ti * a.nty + tj])
-        v = a.hist[(long long)t * a.histPlane + histOffset(prow - dyn.histRow0, wc, a.rxi, a.wi, dyn.histTilesY)];
-    out[(long long)t * a.histPitch + wc] = v;
-}
-
-void launchHistRow(const AnalyzeArgs& a, int X, float* out, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_hist_row_kernel, dim3((a.histPitch + 255) / 256, a.T), dim3(256), 0, stream, a, X, out);
-}
-
-// nplanes planes: the nr x nc block at (sr0, sc0) of src planes (row pitch spitch, plane stride sstride) into the block at
-// (dr0, dc0) of dst planes -- a slab's part of the history window into the whole grid's result / delay maps
-__global__ void pv_copy_block_kernel(const float* __restrict__ src, long long sstride, int spitch, int sr0, int sc0,
-                                     float* __restrict__ dst, long long dstride, int dpitch, int dr0, int dc0, int nr,
-                                     int nc, const int* srcPlanes, const int* dstPlanes, const unsigned* abortWord) {
-    if (abortWord && *abortWord != 0u) return;  // (AnalyzeArgs::abortWord)
-    const int c = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-    const int ks = srcPlanes ? srcPlanes[blockIdx.z] : blockIdx.z, kd = dstPlanes ? dstPlanes[blockIdx.z] : blockIdx.z;
-    if (c >= nc || r >= nr) return;
-    dst[kd * dstride + (long long)(dr0 + r) * dpitch + dc0 + c] = src[ks * sstride + (long long)(sr0 + r) * spitch + sc0 + c];
-}
-
-void launchCopyBlock(const float* src, long long sstride, int spitch, int sr0, int sc0, float* dst, long long dstride,
-                     int dpitch, int dr0, int dc0, int nr, int nc, int nplanes, const int* srcPlanesDev,
-                     const int* dstPlanesDev, hipStream_t stream, const unsigned* abortWord) {
-    if (nr <= 0 || nc <= 0) return;
-    hipLaunchKernelGGL(pv_copy_block_kernel, dim3((unsigned)((nc + 255) / 256), (unsigned)nr, (unsigned)nplanes), dim3(256),
-                       0, stream, src, sstride, spitch, sr0, sc0, dst, dstride, dpitch, dr0, dc0, nr, nc, srcPlanesDev,
-                       dstPlanesDev, abortWord);
-}
-
-// Slab decomposition (pv_slabs.cpp): after a K-step launch a slab PUSHES the K rows next to each of its boundaries into the
-// neighbour's guard band -- one launch for all six blocks (3 planes x 2 directions) instead of six hipMemcpyAsync on the
-// receiver's stream (each a 5 us copy kernel of its own: 20-85 us per sweep in round 2).  Every block is K whole padded
-// rows = a contiguous run of floats (a multiple of 64); the destination may live on another device (peer access is
-// enabled by the group: plain stores over xGMI).
-struct HaloPushArgs {
-    const float* src[6];
-    float* dst[6];
-    long long n;  // floats per block
-    HaloHandoff h;
-};
-// Device-side hand-off between slabs on ONE device (HaloHandoff, pv_device.h).  A cross-queue event wait per slab and sweep
-// costs ~50 us on this runtime (the waiting queue is parked until the command processor looks at it again: a 2048^2 run with two
-// slabs took 95 us per sweep for 37 us of stencil, profiles/r04_slabs.txt); a word in memory costs 2-3 us.  So the push kernel
-// of sweep li (a) copies its rows, (b) fence + count: the block that completes the count raises the words its neighbours
-// look at to li + 1, (c) that same block then waits until the slab's own words -- raised by the neighbours' pushes of the
-// same sweep -- have reached li + 1.  The slab's next step launch follows in stream order: behind the neighbours' halos,
-// without an event.  (Write-after-read: a neighbour's push of sweep li comes behind its step li, which came behind its wait
-// for THIS slab's push li - 1, which came behind this slab's step li - 1 -- the last reader of the guard rows it overwrites.)
-// One wave spins, bounded; the others leave: the neighbours' kernels never lack a place to run.
-__global__ __launch_bounds__(256) void pv_halo_push_kernel(const HaloPushArgs h) {
-    typedef unsigned int v4u __attribute__((__vector_size__(16)));
-    const int b = blockIdx.y;
-    const bool hand = h.h.count != nullptr;
-    if (h.dst[b]) {
-        // (with the hand-off the rows are written THROUGH to memory -- sc1 -- so that nothing has to be flushed before the word
-        // is raised: a release fence here writes back and invalidates the whole L2 under the other slab's running step kernel,
-        // measured 65 us per sweep)
-        const rsrc_t rs = makeRsrc(h.src[b], h.n * 4), rd = makeRsrc(h.dst[b], h.n * 4);
-        const int n4 = (int)(h.n >> 2);
-        for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
-            const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, i * 16, 0, 0);
-            if (hand)
-                __builtin_amdgcn_raw_buffer_store_b128(v, rd, i * 16, 0, 16 /* sc1 */);
-            else
-                __builtin_amdgcn_raw_buffer_store_b128(v, rd, i * 16, 0, 0);
-        }
-    }
-    if (!hand) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this thread's rows are in memory
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const unsigned nblocks = gridDim.x * gridDim.y;
-    if (__hip_atomic_fetch_add(h.h.count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u != h.h.seq * nblocks) return;
-    for (int i = 0; i < 2; ++i)
-        if (h.h.raise[i]) __hip_atomic_store(h.h.raise[i], h.h.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int i = 0; i < 2; ++i) {
-        if (!h.h.await[i]) continue;
-        int spins = 0;
-        while (__hip_atomic_load(h.h.await[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < h.h.seq) {
-            __builtin_amdgcn_s_sleep(2);
-            if (++spins > (1 << 19)) {  // (~0.5 s: a neighbour whose launches do not run beside this one must not hang the device;
-                                        // SlabGroup::run then repeats the run with events -- the abort word keeps this run's
-                                        // analysis away from the result maps)
-                atomicExch(h.h.err, 5);
-                if (h.h.abortWord) __hip_atomic_store(h.h.abortWord, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return;
-            }
-        }
-    }
-}
-
-void launchHaloPush(const float* const src[6], float* const dst[6], long long n, const HaloHandoff& hand, hipStream_t stream) {
-    HaloPushArgs h;
-    for (int i = 0; i < 6; ++i) {
-        h.src[i] = src[i];
-        h.dst[i] = dst[i];
-    }
-    h.n = n;
-    h.h = hand;
-    const unsigned bx = (unsigned)std::min<long long>(64, (n / 4 + 255) / 256);
-    hipLaunchKernelGGL(pv_halo_push_kernel, dim3(bx, 6), dim3(256), 0, stream, h);
-}
-
-// far cells of the whole map (delay = FLT_MAX, default listener direction): the first analysis launch
-void launchFarCells(const AnalyzeArgs& a, hipStream_t stream) {
-    const int n = a.gx * a.gy;
-    hipLaunchKernelGGL(pv_far_cells_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a);
-}
-
-// onset, dry gain, source directivity, lowpass, wet gain, decay time of the window's cells (everything but the listener
-// direction, which needs the delay / occlusion maps of the WHOLE window: launchAnalysisDirection)
-void launchOnset(const AnalyzeArgs& a, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_onset_kernel, dim3((unsigned)((a.histPlane + 63) / 64)), dim3(64 * kOnsetWaves), 0, stream, a);
-}
-void launchEncode(const AnalyzeArgs& a, hipStream_t stream) {
-    // lanes per cell by the window's size (an upper bound of the cells with work): sixteen where a cell's walk IS the kernel's
-    // duration, four up to the sizes the four-lane decay-time form serves, one (which then also takes the wet gain beside the
-    // lane-per-cell decay-time form) above
-    const unsigned units = (unsigned)((a.histPlane + 63) / 64);
-    if (a.rt60Lanes != 1 && a.histPlane <= 16384)
-        hipLaunchKernelGGL(pv_encode_groups_kernel<16>, dim3(units * 4), dim3(256), 0, stream, a);
-    else if (a.rt60Lanes != 1 && a.histPlane <= kRt60TileMinCells)
-        hipLaunchKernelGGL(pv_encode_groups_kernel<4>, dim3(units), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL(pv_encode_kernel, dim3((unsigned)((a.histPlane + 255) / 256)), dim3(256), 0, stream, a);
-}
-// wet gain + decay time (pv_rt60.hip): the form is decided on the device from the number of cells with an onset
-void launchRt60(const AnalyzeArgs& a, hipStream_t stream) { launchRt60Forms(a, stream); }
-
-void launchAnalysisCells(const AnalyzeArgs& a, hipStream_t stream) {
-    launchOnset(a, stream);
-    launchEncode(a, stream);
-    launchRt60(a, stream);
-}
-
-void launchAnalysisDirection(const AnalyzeArgs& a, hipStream_t stream) {
-    const dim3 grid = analysisWindowGrid(a);
-    // (the whole pass in ONE workgroup with the table in LDS -- no kernel boundaries between init, jumps and final -- was built and
-    // measured for the windows of up to 16 384 cells: 25-80 us slower, one CU's memory pipeline does the 17 loads per cell of
-    // init and final for everybody: docs/experiments/fused_analysis.md)
-    if (a.dirJump)
-        launchDirectionJump(a, a.dirScratch, stream);
-    else
-        hipLaunchKernelGGL(pv_direction_kernel, grid, dim3(256), 0, stream, a);
-}
-
-void launchFillDelay(float* delay, long long n, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_fill_delay_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, delay, (int)n);
-}
-
-void launchAnalysisFar(const AnalyzeArgs& a, hipStream_t stream) {
-    if (a.wholeWindow || a.box) return;  // (no far-cell pass: pv_onset_kernel does what is left of it)
-    const int n = a.gx * a.gy;
-    if (a.lazyFar) {
-        const int nr = max(a.prevNR, min(a.winRows, a.gx)), nc = max(a.prevNC, min(a.winCols, a.gy));
-        hipLaunchKernelGGL(pv_far_frame_kernel, dim3((unsigned)((max(nc, 1) + 255) / 256), (unsigned)max(nr, 1), 2), dim3(256), 0,
-                           stream, a);
-    } else {
-        hipLaunchKernelGGL(pv_far_cells_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a);
-    }
-}
-
-void launchAnalysis(const AnalyzeArgs& a, hipStream_t stream) {
-    launchAnalysisFar(a, stream);
-    launchAnalysisCells(a, stream);
-    // listener direction: the plain walk where walks are short (small windows: rooms, the sandbox's grids), pointer
-    // jumping where a window is wide enough for hundreds of steps (a dozen tiny launches, path-length independent)
-    launchAnalysisDirection(a, stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// streaming analysis (sparse-emitter mode)
-// ---------------------------------------------------------------------------------------------------------------
-// With T in the tens of thousands (a 25 m scene at a 4096^2 grid: T = 25432) the full pressure history cannot be
-// kept.  What needs ALL of a cell's samples is only the wet gain and the RT60 regression; onset, dry energy and
-// flux are forward sums that close N_dry samples after the onset.  So the history becomes a ring of `ring` planes;
-// after every `ring` steps pv_stream_accum_kernel advances the forward sums of every open cell in the reference's
-// sample order (state carried in per-cell planes), and the pressure of the REGISTERED emitter cells is copied to
-// per-emitter traces, from which wet gain and RT60 are computed at the end exactly as pv_encode_kernel does.
-
-__global__ __launch_bounds__(256) void pv_stream_accum_kernel(const AnalyzeArgs a) {
-    int X, Y;
-    if (a.ringList) {
-        // forward sums of the air tiles inside the stencil (pv_stream.h): this pass serves only the listed tiles (walls, grid
-        // edges, listener, registered emitters) -- blockIdx.x = list entry * chunks + 256-cell chunk of the tile (a grid's y
-        // extent stops at 65 535: a 16k^2 scene with many wall tiles has more list entries than that)
-        const int chunks = (a.rxi * a.wi + 255) / 256;
-        const int entry = blockIdx.x / chunks;
-        const int t = a.ringList[entry];
-        const int idx = (blockIdx.x - entry * chunks) * blockDim.x + threadIdx.x;
-        if (idx >= a.rxi * a.wi) return;
-        const int ti = t / a.nty, r = idx / a.wi;
-        X = ti * a.rxi + r;
-        Y = (t - ti * a.nty) * a.wi + (idx - r * a.wi);
-    } else {
-        Y = blockIdx.x * blockDim.x + threadIdx.x;
-        X = blockIdx.y;
-    }
-    if (Y >= a.gy || X >= a.gx) return;
-    const int s = X * a.gy + Y;
-    const DynParams dyn = *a.dyn;
-    const int tile = (X / a.rxi) * a.nty + (Y / a.wi);
-    // tiles whose sums advance inside the stencil (pv_stream.h) are not this pass's business
-    if (a.fuseClass && !a.ringList &&
-        fusedTile(a.fuseClass, a.fuseEmit, dyn, X / a.rxi, Y / a.wi, a.nty, a.G, a.fuseK, a.rxi, a.wi, a.rxi + 2 * a.fuseK, 1))
-        return;
-    const int tFirst = a.tileFirst[tile];
-    if (tFirst == INT_MAX || tFirst >= a.tB) return;
-    int onset = a.sOnset[s];
-    int sourceDirEnd = onset >= 0 ? onset + a.nDir : INT_MAX;
-    int directEnd = onset >= 0 ? onset + a.nDry : INT_MAX;
-    if (a.tA >= directEnd) return;  // this cell's dry window is closed
-    // a wall cell's pressure is identically zero: it never has an onset and must not keep its tile recording
-    if (a.coef[(size_t)(X + a.G) * a.pitch + (Y + a.G)].beta == 0.f) return;
-
-    const int prow = X + a.G, pcol = Y + a.G;
-    const int hr = prow - dyn.histRow0, hcol = pcol - dyn.histCol0;
-    const long long hoff = histOffset(hr, hcol, a.rxi, a.wi, dyn.histTilesY);
-    int tFx = INT_MAX, tFy = INT_MAX;
-    if (X > 0 && prow - 1 >= dyn.histRow0) tFx = a.tileFirst[((X - 1) / a.rxi) * a.nty + (Y / a.wi)];
-    if (Y > 0 && pcol - 1 >= dyn.histCol0) tFy = a.tileFirst[(X / a.rxi) * a.nty + ((Y - 1) / a.wi)];
-    const float* hc = a.hist + hoff;
-    const float* hx = a.hist + (tFx != INT_MAX ? histOffset(hr - 1, hcol, a.rxi, a.wi, dyn.histTilesY) : hoff);
-    const float* hy = a.hist + (tFy != INT_MAX ? histOffset(hr, hcol - 1, a.rxi, a.wi, dyn.histTilesY) : hoff);
-    const FaceCoef fc = a.coef[(size_t)prow * a.pitch + pcol];
-    const float kx = fc.kx, ky = fc.ky;
-    const bool airX = kx != kx, airY = ky != ky;
-    const float C = a.courant;
-
-    float Edry = a.sEdry[s], fluxX = a.sFx[s], fluxY = a.sFy[s], vx = a.sVx[s], vy = a.sVy[s];
-    constexpr int CH = 8;
-    bool done = false;
-    const int tEnd = min(a.tB, a.T);
-    for (int t0 = max(a.tA, tFirst); t0 < tEnd && !done; t0 += CH) {
-        float pc[CH], pxc[CH], pyc[CH];
-        const bool needVChunk = t0 < sourceDirEnd;
-#pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            const int tt = min(t0 + k, tEnd - 1);
-            const long long o = (long long)(tt % a.ring) * a.histPlane;
-            pc[k] = hc[o];
-            pxc[k] = (needVChunk && tt >= tFx) ? hx[o] : 0.f;
-            pyc[k] = (needVChunk && tt >= tFy) ? hy[o] : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < CH; ++k) {
-            const int t = t0 + k;
-            if (done || t >= tEnd || t >= directEnd) {
-                done = done || t >= directEnd;
-                continue;
-            }
-            const float p = pc[k];
-            if (t < sourceDirEnd) {
-                const float pxn = pxc[k], pyn = pyc[k];
-                const float ax = vx - C * (p - pxn), wx = kx * (p + pxn);
-                const float ay = vy - C * (p - pyn), wy = ky * (p + pyn);
-                vx = airX ? ax : wx;
-                vy = airY ? ay : wy;
-            }
-            if (onset < 0 && fabsf(p) > kAudibleThresholdDev) {
-                onset = t;
-                sourceDirEnd = t + a.nDir;
-                directEnd = t + a.nDry;
-                if (t >= directEnd) {
-                    done = true;
-                    continue;
-                }
-            }
-            Edry += p * p;
-            if (t < sourceDirEnd) {
-                fluxX += p * vx;
-                fluxY += p * vy;
-            }
-        }
-    }
-    // still open after this pass?  (no onset yet, or the dry window reaches past tB) -> keep the tile recording
-    if (onset < 0 || a.tB < directEnd) a.tileOpenOut[tile] = 1;
-    a.sOnset[s] = onset;
-    a.sEdry[s] = Edry;
-    a.sFx[s] = fluxX;
-    a.sFy[s] = fluxY;
-    a.sVx[s] = vx;
-    a.sVy[s] = vy;
-}
-
-// pressure of the registered emitter cells for steps [tA, tB): ring -> per-emitter trace
-__global__ void pv_stream_trace_kernel(const AnalyzeArgs a) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = a.tB - a.tA;
-    if (i >= a.numEmitters * n) return;
-    const int e = i / n, t = a.tA + (i - e * n);
-    if (t >= a.T) return;
-    const DynParams dyn = *a.dyn;
-    const int cell = a.emCells[e];
-    const int X = cell / a.gy, Y = cell - X * a.gy;
-    const int tFirst = a.tileFirst[(X / a.rxi) * a.nty + (Y / a.wi)];
-    float v = 0.f;
-    if (t >= tFirst)
-        v = a.hist[(long long)(t % a.ring) * a.histPlane +
-                   histOffset(X + a.G - dyn.histRow0, Y + a.G - dyn.histCol0, a.rxi, a.wi, dyn.histTilesY)];
-    a.emTrace[(size_t)e * a.T + t] = v;
-}
-
-// end of run: onset map + the outputs that come from the forward sums (Analyzer.cpp:197-230), every cell
-__global__ __launch_bounds__(256) void pv_stream_finalize_kernel(const AnalyzeArgs a) {
-    const int Y = blockIdx.x * blockDim.x + threadIdx.x;
-    const int X = blockIdx.y;
-    if (Y >= a.gy || X >= a.gx) return;
-    const int s = X * a.gy + Y;
-    const int onset = a.sOnset[s];
-    if (onset < 0) {
-        a.delay[s] = FLT_MAX;
-        return;
-    }
-    a.delay[s] = (float)onset;
-    const float Edry = a.sEdry[s], fluxX = a.sFx[s], fluxY = a.sFy[s];
-    const float EfreePr = efreePerR(a.efree, a.dx, a.lcx, a.lcy, X, Y);
-    const float occ = sqrtf(Edry / EfreePr);
-    float norm = sqrtf(fluxX * fluxX + fluxY * fluxY);
-    norm = -1.0f / (norm > 0.0f ? norm : 1.0f);
-    const float rr = 1.0f / ((0.001f < occ) ? occ : 0.001f);
-    a.out[s] = occ;
-    a.out[3 * a.resN + s] = -147.f + (18390.f) / (1.f + pvPowf(rr / 12.f, 0.8f));
-    a.out[6 * a.resN + s] = norm * fluxX;
-    a.out[7 * a.resN + s] = norm * fluxY;
-}
-
-// wet gain + RT60 of the registered emitter cells from their traces (Analyzer.cpp:235-327); one thread each
-__global__ void pv_stream_emitter_kernel(const AnalyzeArgs a) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= a.numEmitters) return;
-    const int s = a.emCells[e];
-    const int onset = a.sOnset[s];
-    if (onset < 0) return;
-    const float* tr = a.emTrace + (size_t)e * a.T;
-    const int T = a.T;
-    const int directEnd = onset + a.nDry;
-    float wetEnergy = 0.f;
-    {
-        int end = directEnd + 1 + a.nWet;
-        if (T < end) end = T;
-        for (int j = directEnd + 1; j < end; ++j) wetEnergy += tr[j] * tr[j];
-    }
-    const int startingPoint = directEnd + 1;
-    const int endPoint = T - a.nCut;
-    const float rn = (float)(endPoint - startingPoint);
-    const float xmean = (rn - 1.0f) * 0.5f;
-    const float xsum = rn * xmean;
-    const float denominator = (1.0f / 12.0f) * rn * (rn * rn - 1.0f);
-    float edc = 0.f, xysum = 0.f, ysum = 0.f;
-    for (int i = T - 1; i >= endPoint && i >= 0; --i) edc += tr[i] * tr[i];
-    constexpr int CH = 8;
-    for (int i0 = endPoint - 1; i0 >= startingPoint; i0 -= CH) {
-        float pc[CH];
-#pragma unroll
-        for (int k = 0; k < CH; ++k) pc[k] = tr[max(i0 - k, 0)];
-        rt60Chunk<CH>(pc, i0, startingPoint, edc, xysum, ysum);
-    }
-    const float ymean = ysum / rn;
-    const float numerator = xysum - ymean * xsum - xmean * ysum + rn * xmean * ymean;
-    const float slopePerSec = (numerator / denominator) * (float)a.fs;
-    a.out[a.resN + s] = sqrtf(wetEnergy / a.efree);
-    a.out[2 * a.resN + s] = -60.f / slopePerSec;
-}
-
-// tileOpen[tile] for the next launches: some cell marked it open in this pass, or the wave has not reached it yet,
-// or it holds a registered emitter (its whole trace is needed)
-__global__ void pv_stream_tilegate_kernel(const uint8_t* marks, const uint8_t* hasEmitter, const int* tileFirst, int tB,
-                                          uint8_t* tileOpen, int ntiles) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < ntiles) tileOpen[t] = (marks[t] || hasEmitter[t] || tileFirst[t] >= tB) ? 1 : 0;
-}
-
-void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
-                       hipStream_t stream) {
-    dim3 grid((a.gy + 255) / 256, a.gx);
-    if (a.ringList) grid = dim3((unsigned)((a.rxi * a.wi + 255) / 256) * (unsigned)(a.numRing > 0 ? a.numRing : 1), 1);
-    hipMemsetAsync(a.tileOpenOut, 0, (size_t)ntiles, stream);
-    if (!a.ringList || a.numRing > 0) hipLaunchKernelGGL(pv_stream_accum_kernel, grid, dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(pv_stream_tilegate_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, stream, a.tileOpenOut,
-                       hasEmitter, a.tileFirst, a.tB, tileOpen, ntiles);
-    const int n = a.numEmitters * (a.tB - a.tA);
-    if (n > 0) hipLaunchKernelGGL(pv_stream_trace_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a);
-}
-
-void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream) {
-    dim3 grid((a.gy + 255) / 256, a.gx);
-    const int n = a.gx * a.gy;
-    hipLaunchKernelGGL(pv_fill_delay_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a.delay, n);
-    hipLaunchKernelGGL(pv_stream_finalize_kernel, grid, dim3(256), 0, stream, a);
-    if (a.numEmitters > 0)
-        hipLaunchKernelGGL(pv_stream_emitter_kernel, dim3((a.numEmitters + 63) / 64), dim3(64), 0, stream, a);
-    // T is large in this mode: resolve the delay-map descent by pointer jumping (the window is the whole grid here)
-    launchDirectionJump(a, a.dirScratch, stream);
-}
-
-// FreeGrid::CalculateEFree + SimulateFreeFieldEnergy tail, FreeGrid.cpp:86-110: sequential float sum of p^2 over
-// the first n samples at one cell, times the discrete distance r.
-__global__ void pv_efree_kernel(const float* hist, long long plane, long long cellOff, int n, float r,
-                                float* out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    float e = 0.f;
-    for (int i = 0; i < n; ++i) {
-        const float p = hist[(long long)i * plane + cellOff];
-        e += p * p;
-    }
-    out[0] = e * r;
-}
-
-void launchEfree(const float* hist, long long plane, long long cellOff, int n, float r, float* out,
-                 hipStream_t stream) {
-    hipLaunchKernelGGL(pv_efree_kernel, dim3(1), dim3(64), 0, stream, hist, plane, cellOff, n, r, out);
-}
-
-// Grid::GetResponse, FDTD.cpp:74-79: the (pr, vx, vy) impulse response of one array cell, rebuilt from the
-// pressure history (see pv_encode_kernel).  out = T x 3 floats.
-__global__ void pv_ir_kernel(const AnalyzeArgs a, int X, int Y, float* out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const DynParams dyn = *a.dyn;
-    const int prow = X + a.G, pcol = Y + a.G;
-    const int tj = (Y / a.wi), ti = (X / a.rxi);
-    const int wti = ti - dyn.histTileX0, wtj = tj - dyn.histTileY0;
-    const bool inWin = wti >= 0 && wti < dyn.histTilesX && wtj >= 0 && wtj < dyn.histTilesY;
-    const int tFirst = inWin ? a.tileFirst[ti * a.nty + tj] : INT_MAX;
-    const long long hoff = inWin ? histOffset(prow - dyn.histRow0, pcol - dyn.histCol0, a.rxi, a.wi, dyn.histTilesY) : 0;
-    int tFx = INT_MAX, tFy = INT_MAX;
-    if (X > 0 && prow - 1 >= dyn.histRow0) tFx = a.tileFirst[((X - 1) / a.rxi) * a.nty + tj];
-    if (Y > 0 && pcol - 1 >= dyn.histCol0) tFy = a.tileFirst[ti * a.nty + ((Y - 1) / a.wi)];
-    const long long hoffX = tFx != INT_MAX ? histOffset(prow - 1 - dyn.histRow0, pcol - dyn.histCol0, a.rxi, a.wi, dyn.histTilesY) : 0;
-    const long long hoffY = tFy != INT_MAX ? histOffset(prow - dyn.histRow0, pcol - 1 - dyn.histCol0, a.rxi, a.wi, dyn.histTilesY) : 0;
-    const FaceCoef fc = a.coef[(size_t)prow * a.pitch + pcol];
-    const float kx = fc.kx, ky = fc.ky;
-    const bool airX = kx != kx, airY = ky != ky;
-    const bool above = X == 0 && a.histAbove;  // first row of a slab: the row above lives in the neighbouring slab
-    float vx = 0.f, vy = 0.f;
-    for (int t = 0; t < a.T; ++t) {
-        float p = 0.f;
-        if (t >= tFirst) {
-            p = a.hist[(long long)t * a.histPlane + hoff];
-            const float pxn = above ? a.histAbove[(long long)t * a.histPitch + (pcol - dyn.histCol0)]
-                                    : (t >= tFx) ? a.hist[(long long)t * a.histPlane + hoffX] : 0.f;
-            const float pyn = (t >= tFy) ? a.hist[(long long)t * a.histPlane + hoffY] : 0.f;
-            const float ax = vx - a.courant * (p - pxn), wx = kx * (p + pxn);
-            const float ay = vy - a.courant * (p - pyn), wy = ky * (p + pyn);
-            vx = airX ? ax : wx;
-            vy = airY ? ay : wy;
-        }
-        out[3 * t + 0] = p;
-        out[3 * t + 1] = vx;
-        out[3 * t + 2] = vy;
-    }
-}
-
-void launchIr(const AnalyzeArgs& a, int X, int Y, float* out, hipStream_t stream) {
-    hipLaunchKernelGGL(pv_ir_kernel, dim3(1), dim3(64), 0, stream, a, X, Y, out);
-}
-
-// gather / scatter between the reference's dense (gx+1)x(gy+1) order and the padded device planes
-__global__ void pv_unpad_kernel(const float* padded, float* dense, Geometry g) {
-    const int y = blockIdx.x * blockDim.x + threadIdx.x;
-    const int x = blockIdx.y;
-    if (y < g.NY && x < g.NX) dense[(size_t)x * g.NY + y] = padded[(size_t)(x + g.G) * g.pitch + (y + g.G)];
-}
-__global__ void pv_pad_kernel(const float* dense, float* padded, Geometry g) {
-    const int y = blockIdx.x * blockDim.x + threadIdx.x;
-    const int x = blockIdx.y;
-    if (y < g.NY && x < g.NX) padded[(size_t)(x + g.G) * g.pitch + (y + g.G)] = dense[(size_t)x * g.NY + y];
-}
-// recorded pressure plane t -> dense order, zero where nothing was stored
-__global__ void pv_histplane_kernel(const AnalyzeArgs a, int t, float* dense, int NX, int NY, int histRows) {
-    const int y = blockIdx.x * blockDim.x + threadIdx.x;
-    const int x = blockIdx.y;
-    if (y >= NY || x >= NX) return;
-    const DynParams dyn = *a.dyn;
-    const int hr = x + a.G - dyn.histRow0, hcn = y + a.G - dyn.histCol0;
-    float v = 0.f;
-    if (hr >= 0 && hr < histRows && hcn >= 0 && hcn < dyn.histTilesY * a.wi) {
-        const int tF = a.tileFirst[(x / a.rxi) * a.nty + (y / a.wi)];
-        if (t >= tF) v = a.hist[(long long)t * a.histPlane + histOffset(hr, hcn, a.rxi, a.wi, dyn.histTilesY)];
-    }
-    dense[(size_t)x * NY + y] = v;
-}
-
-void launchUnpad(const float* padded, float* dense, const Geometry& g, hipStream_t stream) {
-    dim3 grid((g.NY + 255) / 256, g.NX);
-    hipLaunchKernelGGL(pv_unpad_kernel, grid, dim3(256), 0, stream, padded, dense, g);
-}
-void launchPad(const float* dense, float* padded, const Geometry& g, hipStream_t stream) {
-    dim3 grid((g.NY + 255) / 256, g.NX);
-    hipLaunchKernelGGL(pv_pad_kernel, grid, dim3(256), 0, stream, dense, padded, g);
-}
-void launchHistPlane(const AnalyzeArgs& a, int t, float* dense, int NX, int NY, int histRows,
-                     hipStream_t stream) {
-    dim3 grid((NY + 255) / 256, NX);
-    hipLaunchKernelGGL(pv_histplane_kernel, grid, dim3(256), 0, stream, a, t, dense, NX, NY, histRows);
 }
 
 }  // namespace pva

@@ -1,4 +1,5 @@
-// pv_launch.h -- host-callable launchers for the kernels in pv_kernels.hip
+// pv_launch.h -- host-callable launchers and configuration queries of the kernel translation units (the .hip files of this
+// directory that the host code calls into), grouped by the file that implements them
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 
 namespace pva {
 
+// ---- pv_kernels.hip: the stencil
 // supported (K steps per launch, interior rows per tile) instantiations of the fused stencil
 bool stepConfigSupported(int K, int rxi);
 bool mergedConfigOk(int K, int rxi);
@@ -49,11 +51,20 @@ void launchTileClass(int K, int rxi, const FaceCoef* coef, uint8_t* tileClass, i
                      const Geometry& g, hipStream_t stream, bool allowEdge);
 // dead tiles (all-wall interior): dead[tile] = 1, *count += number of them
 void launchTileDead(const FaceCoef* coef, uint8_t* dead, int* count, const Geometry& g, int K, hipStream_t stream);
+void launchCoefs(const float* mat, FaceCoef* coef, const Geometry& g, hipStream_t stream);
+void launchLaneSelfTest(float* out128, hipStream_t stream);
+
+// ---- pv_resident.hip: a walled-in room's run as one launch
 // resident kernel (pv_resident.hip): one launch per run; a.ntiles workgroups that must all be co-resident
 bool residentConfigOk(int K, int rxi);
 int residentExtraRows(int K, int rxi);   // rows its blocks load beyond rxi + 2K at the bottom
 int residentMaxBlocks(int K, int rxi, int device);
 void launchResident(int K, int rxi, const ResidentArgs& a, hipStream_t stream);
+#ifdef PV_RESIDENT_TRACE
+void residentDumpTrace();  // development builds: the phase stamps of the last launch to stderr
+#endif
+
+// ---- pv_probe.hip: queue / clock / bandwidth probes, the run's status words
 // do the two (idle) streams share a hardware queue?  stamps = 4 words of pinned host memory (pv_probe.hip)
 bool streamsShareQueue(hipStream_t a, hipStream_t b, unsigned long long* stamps);
 // shader clock of the moment (pv_probe.hip): MHz by a timed s_sleep, or 0
@@ -62,9 +73,8 @@ float clockProbeMHz(int device, float* byMemtime);
 bool bandwidthProbeGBs(int device, float out[4]);
 // error flag, {cells of non-zero tiles, cells with an onset}, resident claim counter (or NULL) -> 4 ints of pinned host memory
 void launchRunStatus(int* err, int* counts, const unsigned* claims, int* outHost, hipStream_t stream);
-#ifdef PV_RESIDENT_TRACE
-void residentDumpTrace();  // development builds: the phase stamps of the last launch to stderr
-#endif
+
+// ---- pv_run.hip: start of a run, zeroing, the small grids' one-workgroup kernel
 // cells = NX*NY must satisfy smallGridFits()
 bool smallGridFits(int NX, int NY);
 void launchSmallGrid(const SmallArgs& a, hipStream_t stream);
@@ -76,21 +86,34 @@ struct ZeroRectArgs {
 };
 void launchZeroRect(const ZeroRectArgs& z, hipStream_t stream);
 void launchBeginRun(const BeginArgs& a, hipStream_t stream);
-void launchCoefs(const float* mat, FaceCoef* coef, const Geometry& g, hipStream_t stream);
-void launchLaneSelfTest(float* out128, hipStream_t stream);
+
+// ---- pv_analysis.hip: impulse-response analysis, one pass per launch, and its streaming form
 void launchAnalysis(const AnalyzeArgs& a, hipStream_t stream);
 // the three phases of launchAnalysis separately (slab groups run the middle one per slab, the others on the whole map)
 void launchFarCells(const AnalyzeArgs& a, hipStream_t stream);
 void launchAnalysisFar(const AnalyzeArgs& a, hipStream_t stream);  // launchAnalysis' first pass (the lazy far frame, or every far cell)
-// no-onset cells of the window and of the block [srcR0, +srcNR) x [srcC0, +srcNC) (the other solver's last window; srcNR = 0:
-// none) take the six persistent result planes (occlusion, wet gain, decay time, lowpass, source direction x / y) from another
-// solver's maps (pv_rt60.hip; Solver::run's carryFrom)
-void launchCarryResults(const AnalyzeArgs& a, const float* srcOut, int srcR0, int srcC0, int srcNR, int srcNC, hipStream_t stream);
 void launchAnalysisCells(const AnalyzeArgs& a, hipStream_t stream);  // = the three below, one after the other
 void launchOnset(const AnalyzeArgs& a, hipStream_t stream);   // onsets of the window's cells into the delay map
 void launchEncode(const AnalyzeArgs& a, hipStream_t stream);  // dry gain, source direction, low-pass (reads the onsets)
 void launchRt60(const AnalyzeArgs& a, hipStream_t stream);    // wet gain, decay time (reads the onsets)
 void launchAnalysisDirection(const AnalyzeArgs& a, hipStream_t stream);
+// direction planes of the far cells, for whole-map read-backs; delay plane = "no onset" everywhere (solver creation)
+void launchFarDirections(float* res, long long n, const FarInfo& far, hipStream_t stream);
+void launchFillDelay(float* delay, long long n, hipStream_t stream);
+void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
+                       hipStream_t stream);
+void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream);
+
+// ---- pv_rt60.hip: wet gain and decay time; results carried over from another solver
+// no-onset cells of the window and of the block [srcR0, +srcNR) x [srcC0, +srcNC) (the other solver's last window; srcNR = 0:
+// none) take the six persistent result planes (occlusion, wet gain, decay time, lowpass, source direction x / y) from another
+// solver's maps (pv_rt60.hip; Solver::run's carryFrom)
+void launchCarryResults(const AnalyzeArgs& a, const float* srcOut, int srcR0, int srcC0, int srcNR, int srcNC, hipStream_t stream);
+// wet gain + decay time (pv_rt60.hip): sixteen / four lanes per cell in one launch, the lane-per-cell form in a second one where
+// AnalyzeArgs::rt60Tile announces it; the form is chosen on the device
+void launchRt60Forms(const AnalyzeArgs& a, hipStream_t stream);
+
+// ---- pv_fused.hip: the analysis as one launch (experimental build), the last kernel of a run
 // the whole analysis of a grid whose history window is the grid, in one launch (pv_fused.hip); fusedAnalysisOk: its phase
 // counters fit; launchRunFinish: a run's output queries + status words in one launch (last kernel of a run)
 bool fusedAnalysisBuilt();  // false in the product build: the arm lives in the experimental build only
@@ -100,12 +123,13 @@ void launchAnalysisFused(const FusedArgs& f, hipStream_t stream);
 void launchRunFinish(const float* res, long long n, const long long* cellsHost, int nq, float* outHost, const FarInfo& far,
                      int* err, int* counts, const unsigned* claims, int* statusHost, unsigned* zeroWords, int nZero,
                      unsigned long long* stamp, hipStream_t stream);
-// wet gain + decay time (pv_rt60.hip): sixteen / four lanes per cell in one launch, the lane-per-cell form in a second one where
-// AnalyzeArgs::rt60Tile announces it; the form is chosen on the device
-void launchRt60Forms(const AnalyzeArgs& a, hipStream_t stream);
+
+// ---- pv_metrics.hip: room-acoustic metrics
 // room metrics of the last completed run (pv_metrics.hip): out = kRoomMetricFloats planes of a.histPlane floats, indexed by the
 // cell's offset inside a history plane; NaN where the cell has no onset in that run
 void launchRoomMetrics(const AnalyzeArgs& a, float* out, hipStream_t stream);
+
+// ---- pv_copy.hip: read-backs and copies
 // slab halos: src[i] -> dst[i] for up to six blocks of n floats (n % 4 == 0, 16-byte aligned); dst[i] = NULL skips a block
 void launchHaloPush(const float* const src[6], float* const dst[6], long long n, const HaloHandoff& hand, hipStream_t stream);
 void launchHistRow(const AnalyzeArgs& a, int X, float* outTxPitch, hipStream_t stream);
@@ -116,15 +140,9 @@ void launchCopyBlock(const float* src, long long sstride, int spitch, int sr0, i
 void launchGatherQueries(const float* res, long long n, const long long* cellsHost, int nq, float* outHost, const FarInfo& far,
                          hipStream_t stream);  // nq <= 64
 void launchGatherOutput(const float* res, long long n, long long cell, float* out8Host, const FarInfo& far, hipStream_t stream);
-// direction planes of the far cells, for whole-map read-backs; delay plane = "no onset" everywhere (solver creation)
-void launchFarDirections(float* res, long long n, const FarInfo& far, hipStream_t stream);
-void launchFillDelay(float* delay, long long n, hipStream_t stream);
 void launchPackResults(const float* res, long long n, float* res8, hipStream_t stream);
 void launchPackWindow(const float* res, long long n, int gy, int r0, int c0, int nr, int nc, float* out8, const FarInfo& far,
                       hipStream_t stream);
-void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
-                       hipStream_t stream);
-void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream);
 void launchEfree(const float* hist, long long plane, long long cellOff, int n, float r, float* out,
                  hipStream_t stream);
 void launchIr(const AnalyzeArgs& a, int X, int Y, float* out3T, hipStream_t stream);

@@ -1,4 +1,4 @@
-// pv_prims.h -- device primitives shared by the kernel translation units (pv_kernels.hip, pv_resident.hip): lane shifts
+// pv_prims.h -- device primitives shared by the kernel translation units: lane shifts
 // by DPP, buffer (SRSRC) addressing, the tile-major history offset.  Moved here unchanged from pv_kernels.hip.
 #pragma once
 

@@ -2178,7 +2178,7 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
     if (streamFuse_) {
         // what is left to the ring and the accumulate pass: the run's general list (walls, edges, the tiles whose loaded
         // region holds the listener: prepareDyn) and the tiles of the registered emitters -- the complement of
-        // fusedTile() (pv_stream.h)
+        // fusedTile() (pv_analysis.h)
         std::vector<uint8_t> in((size_t)ntiles, 0);
         int n = 0;
         auto add = [&](int t) {

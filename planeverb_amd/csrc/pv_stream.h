@@ -26,18 +26,7 @@
 
 namespace pva {
 
-// is `tile` one whose forward sums live in the stencil?  (air class, no registered emitter, not the listener's tile -- that
-// one is on the general list for the run)
-__device__ __forceinline__ bool fusedTile(const uint8_t* tileClass, const uint8_t* tileEmit, const DynParams& dyn, int ti,
-                                          int tj, int nty, int G, int K, int rxi, int wi, int rows, int withPulse) {
-    const int t = ti * nty + tj;
-    if (tileClass[t] != 0 || tileEmit[t]) return false;
-    if (withPulse) {
-        const int lr = dyn.lrow - (G - K + ti * rxi), lc = dyn.lcol - (G - K + tj * wi);
-        if (lr >= 0 && lr < rows && lc >= 0 && lc < 64) return false;
-    }
-    return true;
-}
+// (fusedTile: pv_analysis.h -- the streaming analysis of pv_analysis.hip asks the same question)
 
 __global__ __launch_bounds__(256) void pv_stream_classify_kernel(const ClassifyArgs c) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
