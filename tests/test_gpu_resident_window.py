@@ -1,7 +1,8 @@
 """Resident-window runs (PVA_OPT_RESIDENT_WINDOW, csrc/pv_solver.cpp Solver::windowFor / enqueueWindowRun): a run whose listener
 is walled in steps only the tile window around its air component, in one launch of the resident kernel.  Every case compares
 with the reach-bounded launches (resident_window=0) bit for bit -- final pr / vx / vy of the whole grid, result and onset maps,
-queried outputs -- and asserts which path the runs took: a case that silently fell back would prove nothing."""
+queried outputs -- and asserts which path the runs took: a case that silently fell back would prove nothing.  The comparisons with
+the oracle (grids of 226^2 ... 280^2 that reach the path through an explicit (12, 36) tile) are in test_gpu_resident_window_small.py."""
 import os
 
 import numpy as np

@@ -126,6 +126,10 @@ def plan(exe, **kw):
 LARGE = dict(mergedOk=1, ntiles=11742, cells=4097 * 4097, windowOk=1)                      # 4096^2: tile (12, 36), windowed history
 PRESET70 = dict(mergedOk=1, ntiles=12, cells=71 * 71, wholeWindow=1, useResident=1, smallFits=1)  # the Sandbox's 70^2: tile (12, 12)
 PRESET28 = dict(mergedOk=1, ntiles=3, cells=29 * 29, wholeWindow=1, useResident=1, smallFits=1)
+# ... and for steps_per_launch=12, tile_rows=36, use_graph=2 on a 252 x 280 grid (253 x 281 array cells, 8 x 8 tiles): the explicit
+# tile keeps the whole-grid resident kernel and the small-grid kernel away, "no graph" leaves the reach-bounded launches, and the
+# (12, 36) tile is the window's -- how tests/test_gpu_resident_window_small.py reaches the window path on grids the oracle can run
+FORCED_252x280 = dict(mergedOk=1, ntiles=64, cells=253 * 281, wholeWindow=1, explicitTile=1, useGraph=2, windowOk=1)
 
 
 def test_named_cases(enum_plans):
@@ -143,6 +147,12 @@ def test_named_cases(enum_plans):
     p = plan(enum_plans, listenerInside=1, **PRESET28)
     assert (p["path"], p["reach"]) == ("SmallGrid", 0)
     assert plan(enum_plans, listenerInside=1, resident=1, **PRESET28)["path"] == "Resident"
+    # the forced (12, 36) tile without a graph on a small grid: the window path; with the automatic graph (64 tiles): the graph
+    p = plan(enum_plans, listenerInside=1, **FORCED_252x280)
+    assert (p["path"], p["fallback"], p["reach"]) == ("Window", "Launches", 1)
+    p = plan(enum_plans, listenerInside=1, **dict(FORCED_252x280, useGraph=0))
+    assert (p["path"], p["reach"]) == ("Graph", 0)
+    assert plan(enum_plans, listenerInside=0, **FORCED_252x280)["path"] == "Launches"  # (a listener outside the grid)
     # any layer: the tile kernels (replayed from a graph where the grid is small), merged launch + layer launch, no bands
     for base in (LARGE, PRESET70, PRESET28, dict(LARGE, bands=4, useGraph=2), dict(LARGE, useSeg=1, useGraph=2)):
         p = plan(enum_plans, listenerInside=1, layerActive=1, layerTiles=1, **base)
