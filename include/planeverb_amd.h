@@ -566,6 +566,60 @@ PVA_EXPORT int PvAmdGetRoomMetrics(PvAmdSolver* s, float ex, float ey, float ez,
 /* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T; the restatement the tests hold the
  * kernel to */
 PVA_EXPORT int PvAmdHostRoomMetrics(const float* p, int T, int fs, int onset, PvAmdRoomMetrics* out);
+/* ---- Spectrum: the transfer function from the listener to every reached cell, at chosen frequencies ----
+ * How loud the room is at ONE frequency at one position (room modes and their nodal lines, comb filtering behind an obstacle,
+ * per-band gains): PvAmdComputeSpectrum reduces the history of the LAST COMPLETED run to three floats per bin and cell in one
+ * pass on the device per block of bins (pv_spectrum.hip).  Definition (T = the run's steps, PvAmdInfo::T):
+ *   bins     n frequencies hz[j], 1 <= n <= PVA_SPECTRUM_MAX_BINS, each finite and 0 <= hz[j] <= fs / 2; neither sorted nor
+ *            distinct;
+ *   tables   c[t * n + j] = (float)cos(ph), s[t * n + j] = (float)sin(ph), t = 0 .. T - 1, with
+ *            ph = (2.0 * M_PI * (double)hz[j] * (double)t) / (double)fs in double and the host libm's cos / sin: ABSOLUTE run
+ *            time, phase zero is the start of the run, not the cell's onset.  The device evaluates no trigonometric function;
+ *   sums     for result cell s = X * gy + Y with onset t0 = (int)delay[s] (the run's own onset map) and p(t) exactly what
+ *            PvAmdCopyHistoryPlane(t) returns at array cell (X, Y):
+ *              re_j = sum_{t = t0}^{T - 1} (p(t) * c[t * n + j])      im_j = sum_{t = t0}^{T - 1} (p(t) * s[t * n + j])
+ *            so X(f_j) = re_j - i im_j; samples before the onset do not enter;
+ *   source   the same sums over the run's pulse table (PvAmdCopyPulse, its first T floats) with onset 0: sre_j, sim_j and
+ *            spow_j = (sre * sre) + (sim * sim), computed on the host when the bins are set;
+ *   record   re, im, level = 10.0f * log10f(((re * re) + (im * im)) / spow_j)  (dB re the source).
+ * All arithmetic is float32; every product and every sum is rounded on its own; every sum is sequential in increasing t from
+ * +0.0f; denormals are kept; division is correctly rounded; log10f is glibc's.  Nothing is special-cased: spow_j = 0 gives
+ * +-inf or NaN as IEEE says.
+ * A level is meaningful only inside the pulse's band (up to about the grid resolution in Hz): above it spow_j is the square of
+ * rounding noise.  Cells inside an edge layer get records like any other cell, as unphysical there as their other outputs.
+ * A cell WITHOUT an onset in that run holds 3 n quiet NaNs; nothing is carried over from earlier runs.
+ * Device storage: the tables (2 x 4 bytes per step and bin, padded to the register block) from PvAmdSetSpectrumBins on, and
+ * 3 n x 4 bytes per cell of the history window from the first PvAmdComputeSpectrum on (allocated again when n changes).
+ * Lifetime: the records stay valid until the next run, geometry, boundary or layer change on that solver -- exactly as the room
+ * metrics' -- or a change of the bins; the read-backs then return -1 until computed again.  Room metrics and spectrum do not
+ * invalidate each other.  Options (PVA_OPT_NUM_STEPS among them) are fixed before the first call, so T cannot change under
+ * the tables.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "spectrum: ..."): no bins set, no completed run, a last run that ended
+ * in error, sparse-emitter solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks. */
+#define PVA_SPECTRUM_MAX_BINS 32
+/* Set the bins (copied).  n = 0 clears them and frees the device storage; waits for a run in flight.  Refused with -1 and nothing
+ * changed: hz = NULL with n > 0, n outside 0 .. PVA_SPECTRUM_MAX_BINS, a frequency that is not finite, negative or above fs / 2 */
+PVA_EXPORT int PvAmdSetSpectrumBins(PvAmdSolver* s, const float* hz, int n);
+/* the bins as set: up to cap of them into hz (may be NULL); returns n */
+PVA_EXPORT int PvAmdGetSpectrumBins(PvAmdSolver* s, float* hz, int cap);
+/* sre, sim, spow of every bin: 3 n floats */
+PVA_EXPORT int PvAmdGetSpectrumSource(PvAmdSolver* s, float* out3n);
+/* Compute the records of the LAST COMPLETED run of s (waits for a run in flight; works after every form of run, as
+ * PvAmdComputeRoomMetrics).  Synchronous on the solver's own stream.  *ms (optional): device time of the passes. */
+PVA_EXPORT int PvAmdComputeSpectrum(PvAmdSolver* s, float* ms);
+/* gx*gy*n*3 floats: cell-major (s = X*gy + Y), then bin, then {re, im, level} */
+PVA_EXPORT int PvAmdCopySpectrum(PvAmdSolver* s, float* out);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc x n x 3 floats, row-major */
+PVA_EXPORT int PvAmdCopySpectrumBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out);
+/* the n records at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map gives 3 n NaNs
+ * and 0 */
+PVA_EXPORT int PvAmdGetSpectrum(PvAmdSolver* s, float ex, float ey, float ez, float* out3n);
+/* CPU only: the tables of the definition above, T * n floats each */
+PVA_EXPORT int PvAmdHostSpectrumTables(int T, int fs, const float* hz, int n, float* cosTn, float* sinTn);
+/* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T and the pulse table pulseT[T]; the
+ * restatement the tests hold the kernel to.  The bins are checked by the rule of PvAmdSetSpectrumBins */
+PVA_EXPORT int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const float* hz, int n, const float* pulseT,
+                                 float* out3n);
 /* Gaussian pulse table (Grid.cpp:12-27), T floats */
 PVA_EXPORT int PvAmdCopyPulse(PvAmdSolver* s, float* out);
 /* Material planes after rasterisation: beta (uint8) and R (float), (gx+1)*(gy+1) each (with shapes: the composed material) */

@@ -241,6 +241,15 @@ SYMBOLS = {
     "PvAmdCopyRoomMetricsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "PvAmdGetRoomMetrics": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdRoomMetrics)]),
     "PvAmdHostRoomMetrics": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdRoomMetrics)]),
+    "PvAmdSetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
+    "PvAmdGetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
+    "PvAmdGetSpectrumSource": (C.c_int, [_vp, _fp]),
+    "PvAmdComputeSpectrum": (C.c_int, [_vp, _fp]),
+    "PvAmdCopySpectrum": (C.c_int, [_vp, _fp]),
+    "PvAmdCopySpectrumBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetSpectrum": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
+    "PvAmdHostSpectrumTables": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
+    "PvAmdHostSpectrum": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
     "PvAmdCopyPulse": (C.c_int, [_vp, _fp]),
     "PvAmdCopyMaterial": (C.c_int, [_vp, C.POINTER(C.c_ubyte), _fp]),
     "PvAmdSetFields": (C.c_int, [_vp, _fp, _fp, _fp]),
@@ -660,6 +669,33 @@ def host_room_metrics(p, fs, onset):
     return out.as_array()
 
 
+SPECTRUM_MAX_BINS = 32  # PVA_SPECTRUM_MAX_BINS
+
+
+def host_spectrum_tables(T, fs, hz):
+    """PvAmdHostSpectrumTables: the twiddle tables (cos, sin), float32 [T, n] each, of the spectrum definition of
+    include/planeverb_amd.h for the bins hz -- absolute run time, computed in double on the CPU"""
+    h = np.ascontiguousarray(hz, np.float32).reshape(-1)
+    c = np.empty((max(int(T), 0), h.size), np.float32)
+    s = np.empty_like(c)
+    _check(lib().PvAmdHostSpectrumTables(int(T), int(fs), _f(h) if h.size else None, int(h.size), _f(c), _f(s)))
+    return c, s
+
+
+def host_spectrum(p, fs, onset, hz, pulse):
+    """PvAmdHostSpectrum: float32 [n, 3] (re, im, level in dB) of one impulse response p[T] with its onset step and the
+    pulse table pulse[T] -- the spectrum definition of include/planeverb_amd.h on the CPU"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    q = np.ascontiguousarray(pulse, np.float32).reshape(-1)
+    h = np.ascontiguousarray(hz, np.float32).reshape(-1)
+    if q.size != a.size:
+        raise ValueError("the pulse table and the impulse response differ in length")
+    out = np.empty((h.size, 3), np.float32)
+    _check(lib().PvAmdHostSpectrum(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(h) if h.size else None,
+                                   int(h.size), _f(q) if q.size else None, _f(out)))
+    return out
+
+
 def host_cells(size_x, size_y, res, x, z):
     v = [C.c_int() for _ in range(5)]
     _check(lib().PvAmdHostCells(float(size_x), float(size_y), int(res), float(x), float(z), *v))
@@ -1022,6 +1058,7 @@ class Solver:
         _check(lib().PvAmdGetInfo(self._h, self.info))
         i = self.info
         self.gx, self.gy, self.T, self.fs, self.dx, self.dt, self.efree = i.gx, i.gy, i.T, i.fs, i.dx, i.dt, i.efree
+        self._pulse_len = host_grid_info(size_x, size_y, res).T  # (the grid's own pulse table: T may differ, num_steps)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1293,10 +1330,57 @@ class Solver:
         _check(lib().PvAmdGetRoomMetrics(self._h, *[float(v) for v in pos], out))
         return out.as_array()
 
-    def pulse(self):
-        out = np.empty(self.T, np.float32)
-        _check(lib().PvAmdCopyPulse(self._h, _f(out)))
+    def set_spectrum_bins(self, hz):
+        """the frequencies (Hz, at most SPECTRUM_MAX_BINS, each in [0, fs / 2]) compute_spectrum evaluates; an empty list clears
+        them and frees the device storage"""
+        h = np.ascontiguousarray(hz, np.float32).reshape(-1)
+        _check(lib().PvAmdSetSpectrumBins(self._h, _f(h) if h.size else None, int(h.size)))
+
+    def spectrum_bins(self):
+        """float32 [n]: the bins as set"""
+        out = np.empty(SPECTRUM_MAX_BINS, np.float32)
+        n = lib().PvAmdGetSpectrumBins(self._h, _f(out), SPECTRUM_MAX_BINS)
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return out[:n].copy()
+
+    def spectrum_source(self):
+        """float32 [n, 3]: sre, sim, spow of the run's pulse at every bin (what the levels are relative to)"""
+        out = np.empty((len(self.spectrum_bins()), 3), np.float32)
+        _check(lib().PvAmdGetSpectrumSource(self._h, _f(out)))
         return out
+
+    def compute_spectrum(self):
+        """transfer functions of the last completed run at the bins of set_spectrum_bins, on the device; returns the device
+        time of the passes in milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeSpectrum(self._h, C.byref(ms)))
+        return ms.value
+
+    def spectrum(self):
+        """float32 [gx, gy, n, 3] (re, im, level in dB; X(f) = re - i im); NaN where the cell has no onset in the run they were
+        computed for"""
+        out = np.empty((self.gx, self.gy, len(self.spectrum_bins()), 3), np.float32)
+        _check(lib().PvAmdCopySpectrum(self._h, _f(out)))
+        return out
+
+    def spectrum_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, n, 3] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, len(self.spectrum_bins()), 3), np.float32)
+        _check(lib().PvAmdCopySpectrumBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def spectrum_at(self, pos):
+        """float32 [n, 3] at an emitter position (the cell get_output reads); NaNs off the map"""
+        out = np.empty((len(self.spectrum_bins()), 3), np.float32)
+        _check(lib().PvAmdGetSpectrum(self._h, *[float(v) for v in pos], _f(out)))
+        return out
+
+    def pulse(self):
+        """float32 [T]: the pulse table of a run (T = the run's steps; zero past the grid's own table)"""
+        out = np.zeros(max(self.T, self._pulse_len), np.float32)  # (PvAmdCopyPulse writes the grid's own table)
+        _check(lib().PvAmdCopyPulse(self._h, _f(out)))
+        return out[:self.T].copy()
 
     def material(self):
         shp = (self.gx + 1, self.gy + 1)

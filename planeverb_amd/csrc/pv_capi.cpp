@@ -12,6 +12,7 @@
 #include "pv_context.h"
 #include "pv_core.h"
 #include "pv_metrics.h"
+#include "pv_spectrum.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
 #include "pv_bake.h"
 #include "pv_shard.h"
@@ -401,7 +402,7 @@ const char* PlaneverbWorkerError(void) try {
     w = (c && c->failed()) ? c->workerError() : std::string();
     return w.c_str();
 } PV_API_CATCH("")
-const char* PvAmdVersion(void) try { return "planeverb_amd 0.4 (gfx950)"; } PV_API_CATCH("")
+const char* PvAmdVersion(void) try { return "planeverb_amd 0.4.1 (gfx950)"; } PV_API_CATCH("")
 
 #ifndef PVA_HOST_TEST
 int PvAmdDeviceCount(void) try {
@@ -1122,6 +1123,70 @@ int PvAmdGetRoomMetrics(PvAmdSolver* h, float ex, float ey, float ez, PvAmdRoomM
     return 0;
 } PV_API_CATCH(-1)
 
+// spectrum (pv_spectrum.hip): single whole-grid solvers only, as the room metrics.  The bins are checked against the handle's
+// own grid before anything else happens (pv_spectrum.h spectrumBinsError, the rule the host calls apply too)
+int PvAmdSetSpectrumBins(PvAmdSolver* h, const float* hz, int n) try {
+    if (!h) {
+        g_lastError = "null solver handle";
+        return -1;
+    }
+    if (n != 0) {
+        if (const char* e = spectrumBinsError(hz, n, (int)h->spec.fs)) {
+            g_lastError = e;
+            return -1;
+        }
+    }
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    return ret(h, h->s->setSpectrumBins(hz, n));
+} PV_API_CATCH(-1)
+
+int PvAmdGetSpectrumBins(PvAmdSolver* h, float* hz, int cap) try {
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    return h->s->spectrumBins(hz, cap);
+} PV_API_CATCH(-1)
+
+int PvAmdGetSpectrumSource(PvAmdSolver* h, float* out3n) try {
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!out3n) {
+        g_lastError = "PvAmdGetSpectrumSource: null output";
+        return -1;
+    }
+    return ret(h, h->s->spectrumSource(out3n));
+} PV_API_CATCH(-1)
+
+int PvAmdComputeSpectrum(PvAmdSolver* h, float* ms) try {
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    return ret(h, h->s->computeSpectrum(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopySpectrum(PvAmdSolver* h, float* out) try {
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!out) {
+        g_lastError = "PvAmdCopySpectrum: null output";
+        return -1;
+    }
+    return ret(h, h->s->copySpectrumBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out));
+} PV_API_CATCH(-1)
+
+int PvAmdCopySpectrumBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out) try {
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!out) {
+        g_lastError = "PvAmdCopySpectrumBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copySpectrumBlock(r0, c0, nr, nc, out));
+} PV_API_CATCH(-1)
+
+int PvAmdGetSpectrum(PvAmdSolver* h, float ex, float ey, float ez, float* out3n) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!out3n) {
+        g_lastError = "PvAmdGetSpectrum: null output";
+        return -1;
+    }
+    return ret(h, h->s->spectrumAt(ex, ez, out3n));
+} PV_API_CATCH(-1)
+
 int PvAmdCopyPulse(PvAmdSolver* h, float* out) try {
     if (!out || !ensure(h, true)) return -1;
     return ret(h, h->g ? h->g->copyPulse(out) : h->s->copyPulse(out));
@@ -1425,6 +1490,35 @@ int PvAmdHostRoomMetrics(const float* p, int T, int fs, int onset, PvAmdRoomMetr
     float v[kRoomMetricFloats];
     roomMetricsOfIr(p, T, fs, onset, v);
     std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostSpectrumTables(int T, int fs, const float* hz, int n, float* cosTn, float* sinTn) try {
+    if (T <= 0 || fs <= 0 || !cosTn || !sinTn) {
+        g_lastError = "PvAmdHostSpectrumTables: T > 0, fs > 0 and two tables of T * n floats";
+        return -1;
+    }
+    if (const char* e = spectrumBinsError(hz, n, fs)) {
+        g_lastError = e;
+        return -1;
+    }
+    spectrumTables(T, fs, hz, n, cosTn, sinTn);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const float* hz, int n, const float* pulseT, float* out3n) try {
+    if (!p || !pulseT || !out3n || T <= 0 || fs <= 0 || onset < 0 || onset >= T) {
+        g_lastError = "PvAmdHostSpectrum: an impulse response p[T] and a pulse table of T floats, T > 0, fs > 0, 0 <= onset < T and an output of 3 n floats";
+        return -1;
+    }
+    if (const char* e = spectrumBinsError(hz, n, fs)) {
+        g_lastError = e;
+        return -1;
+    }
+    std::vector<float> c((size_t)T * n), s((size_t)T * n), src((size_t)3 * n);
+    spectrumTables(T, fs, hz, n, c.data(), s.data());
+    spectrumSource(pulseT, T, c.data(), s.data(), n, src.data());
+    spectrumOfIr(p, T, onset, c.data(), s.data(), n, src.data(), out3n);
     return 0;
 } PV_API_CATCH(-1)
 

@@ -129,6 +129,16 @@ void launchRunFinish(const float* res, long long n, const long long* cellsHost, 
 // cell's offset inside a history plane; NaN where the cell has no onset in that run
 void launchRoomMetrics(const AnalyzeArgs& a, float* out, hipStream_t stream);
 
+// ---- pv_spectrum.hip: per-cell transfer functions at chosen frequencies
+// One pass over the history of the last completed run for `bins` bins held `block` to a lane (spectrumBlockOk(block); bins <=
+// block).  tab: the pass's twiddles on the device, row t = {cos, sin} pairs of its `block` bins (2 * block floats, bins past
+// `bins` zero), rows 0 .. T - 1 + kSpectrumTablePad (rows past T - 1 zero); spow: the bins' source powers (device); out: the
+// pass's 3 * bins planes of a.histPlane floats -- re, im, level of each bin, indexed by the cell's offset inside a history
+// plane; NaN where the cell has no onset in that run.
+constexpr int kSpectrumTablePad = 64;
+bool spectrumBlockOk(int block);
+void launchSpectrum(const AnalyzeArgs& a, int block, int bins, const float* tab, const float* spow, float* out, hipStream_t stream);
+
 // ---- pv_copy.hip: read-backs and copies
 // slab halos: src[i] -> dst[i] for up to six blocks of n floats (n % 4 == 0, 16-byte aligned); dst[i] = NULL skips a block
 void launchHaloPush(const float* const src[6], float* const dst[6], long long n, const HaloHandoff& hand, hipStream_t stream);

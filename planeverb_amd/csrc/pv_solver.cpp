@@ -19,6 +19,7 @@
 
 #include "pv_launch.h"
 #include "pv_metrics.h"
+#include "pv_spectrum.h"
 
 namespace pva {
 
@@ -670,6 +671,10 @@ Solver::~Solver() {
     if (metrics_) hipFree(metrics_);
     for (auto& e : metricsEv_)
         if (e) hipEventDestroy(e);
+    for (float* p : {specTab_, specPow_, spectrum_})
+        if (p) hipFree(p);
+    for (auto& e : spectrumEv_)
+        if (e) hipEventDestroy(e);
     if (layerList_) hipFree(layerList_);
     if (layerTab_) hipFree(layerTab_);
     if (px_[0]) hipFree(px_[0]);  // (px_[1] lives in the same allocation)
@@ -747,7 +752,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = false;
+    metricsValid_ = spectrumValid_ = false;
     return id;
 }
 
@@ -758,7 +763,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = false;
+    metricsValid_ = spectrumValid_ = false;
     return true;
 }
 
@@ -769,7 +774,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = false;
+    metricsValid_ = spectrumValid_ = false;
     return true;
 }
 
@@ -841,14 +846,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = false;
+    metricsValid_ = spectrumValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = false;
+    metricsValid_ = spectrumValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -995,7 +1000,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = false;
+    if (boundaryDirty_) metricsValid_ = spectrumValid_ = false;
     return true;
 }
 
@@ -1035,7 +1040,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = false;
+    if (layerDirty_) metricsValid_ = spectrumValid_ = false;
     return true;
 }
 
@@ -2082,7 +2087,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = false;       // (the history the records were made from is about to be overwritten)
+    metricsValid_ = spectrumValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     if (!applyGeometry()) return false;
     PathRun r;
@@ -2948,6 +2953,175 @@ bool Solver::roomMetricsAt(float ex, float ez, float out10[10]) {
         return true;
     }
     return copyRoomMetricsBlock(cx, cy, 1, 1, out10);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// spectrum (pv_spectrum.hip)
+// ----------------------------------------------------------------------------------------------------------------
+
+// The register block that takes the next of `left` bins: time goes with the bins a pass holds, padding included, and B = 16 was
+// the fastest form for 32 bins, B = 8 for 8 (docs/experiments/spectrum.md).  PLANEVERB_AMD_SPECTRUM_BLOCK = 8 / 16 forces one
+// form (measurement).
+static int spectrumBlockFor(int left) {
+    static const int forced = [] {
+        const char* e = std::getenv("PLANEVERB_AMD_SPECTRUM_BLOCK");
+        const int b = e ? std::atoi(e) : 0;
+        return spectrumBlockOk(b) ? b : 0;
+    }();
+    if (forced) return forced;
+    return left <= 8 ? 8 : 16;
+}
+
+bool Solver::setSpectrumBins(const float* hz, int n) {
+    if (isSlab()) return fail("spectrum: not available on a slab");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    spectrumValid_ = false;
+    spectrumHostValid_ = false;
+    for (float** p : {&specTab_, &specPow_})
+        if (*p) {
+            hipFree(*p);
+            *p = nullptr;
+        }
+    specHz_.clear();
+    specPasses_.clear();
+    if (n == 0) {
+        if (spectrum_) hipFree(spectrum_);
+        spectrum_ = nullptr;
+        spectrumPlanes_ = 0;
+        specCos_.clear();
+        specSin_.clear();
+        specSource_.clear();
+        return true;
+    }
+    const int T = T_;  // the run's steps (PVA_OPT_NUM_STEPS): the planes of the history; pulse_ holds at least as many
+    specHz_.assign(hz, hz + n);
+    specCos_.resize((size_t)T * n);
+    specSin_.resize((size_t)T * n);
+    spectrumTables(T, (int)g_.fs, hz, n, specCos_.data(), specSin_.data());
+    specSource_.resize((size_t)3 * n);
+    pva::spectrumSource(pulse_.data(), T, specCos_.data(), specSin_.data(), n, specSource_.data());
+    // the device tables: per pass, rows of {cos, sin} pairs of the pass's block (bins past the slice and rows past T - 1: zero)
+    const size_t rows = (size_t)T + kSpectrumTablePad;
+    size_t total = 0;
+    for (int b0 = 0; b0 < n;) {
+        const int block = spectrumBlockFor(n - b0), bins = std::min(block, n - b0);
+        specPasses_.push_back(SpecPass{b0, bins, block, total});
+        total += rows * 2 * (size_t)block;
+        b0 += bins;
+    }
+    std::vector<float> tab(total, 0.f), pw((size_t)n);
+    for (const SpecPass& ps : specPasses_)
+        for (int t = 0; t < T; ++t)
+            for (int j = 0; j < ps.bins; ++j) {
+                float* w = &tab[ps.tabOff + ((size_t)t * ps.block + j) * 2];
+                w[0] = specCos_[(size_t)t * n + ps.bin0 + j];
+                w[1] = specSin_[(size_t)t * n + ps.bin0 + j];
+            }
+    for (int j = 0; j < n; ++j) pw[(size_t)j] = specSource_[(size_t)3 * j + 2];
+    const bool ok = dalloc(&specTab_, total, false) && dalloc(&specPow_, (size_t)n, false) &&
+                    hipOk(hipMemcpyAsync(specTab_, tab.data(), total * 4, hipMemcpyHostToDevice, stream_), "spectrum table upload") &&
+                    hipOk(hipMemcpyAsync(specPow_, pw.data(), (size_t)n * 4, hipMemcpyHostToDevice, stream_), "spectrum table upload") &&
+                    hipOk(hipStreamSynchronize(stream_), "spectrum table sync");
+    if (!ok) {  // (nothing half-set: no bins)
+        specHz_.clear();
+        specPasses_.clear();
+    }
+    return ok;
+}
+
+int Solver::spectrumBins(float* hz, int cap) const {
+    const int n = (int)specHz_.size();
+    for (int j = 0; j < n && j < cap && hz; ++j) hz[j] = specHz_[(size_t)j];
+    return n;
+}
+
+bool Solver::spectrumSource(float* out3n) {
+    if (specHz_.empty()) return fail("spectrum: no bins set (PvAmdSetSpectrumBins)");
+    std::memcpy(out3n, specSource_.data(), specSource_.size() * 4);
+    return true;
+}
+
+bool Solver::computeSpectrum(float* ms) {
+    if (isSlab()) return fail("spectrum: not available on a slab");
+    if (opt_.streaming) return fail("spectrum: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("spectrum: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    if (specHz_.empty()) return fail("spectrum: no bins set (PvAmdSetSpectrumBins)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("spectrum: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("spectrum: the last run ended in error");
+    const int n = (int)specHz_.size();
+    if (spectrum_ && spectrumPlanes_ != 3 * n) {
+        hipFree(spectrum_);
+        spectrum_ = nullptr;
+    }
+    if (!spectrum_) {
+        if (!dalloc(&spectrum_, (size_t)3 * n * (size_t)histPlane_, false)) return false;
+        spectrumPlanes_ = 3 * n;
+    }
+    for (auto& e : spectrumEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    spectrumValid_ = false;
+    spectrumHostValid_ = false;
+    const AnalyzeArgs a = analyzeArgs(lastLx_, lastLz_);
+    hipEventRecord(spectrumEv_[0], stream_);
+    for (const SpecPass& ps : specPasses_)
+        launchSpectrum(a, ps.block, ps.bins, specTab_ + ps.tabOff, specPow_ + ps.bin0, spectrum_ + (size_t)3 * ps.bin0 * (size_t)histPlane_, stream_);
+    hipEventRecord(spectrumEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "spectrum launch") || !hipOk(hipStreamSynchronize(stream_), "spectrum sync")) return false;
+    if (ms) hipEventElapsedTime(ms, spectrumEv_[0], spectrumEv_[1]);
+    spectrumDyn_ = dynCur_;
+    spectrumValid_ = true;
+    return true;
+}
+
+bool Solver::fetchSpectrum() {
+    if (specHz_.empty()) return fail("spectrum: no bins set (PvAmdSetSpectrumBins)");
+    if (!spectrumValid_) return fail("spectrum: not computed for the last run, the current geometry and the current bins (PvAmdComputeSpectrum)");
+    if (spectrumHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    spectrumHost_.resize((size_t)spectrumPlanes_ * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(spectrumHost_.data(), spectrum_, spectrumHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "spectrum copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "spectrum sync"))
+        return false;
+    spectrumHostValid_ = true;
+    return true;
+}
+
+bool Solver::copySpectrumBlock(int r0, int c0, int nr, int nc, float* out) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("spectrum: block outside the map");
+    if (!fetchSpectrum()) return false;
+    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
+    const int wr0 = spectrumDyn_.histRow0 - geo_.G, wc0 = spectrumDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const int nf = spectrumPlanes_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < nf; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * spectrumDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < nf; ++k) o[k] = spectrumHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::spectrumAt(float ex, float ez, float* out3n) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!fetchSpectrum()) return false;
+        for (int k = 0; k < spectrumPlanes_; ++k) out3n[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copySpectrumBlock(cx, cy, 1, 1, out3n);
 }
 
 bool Solver::copyPulse(float* out) {

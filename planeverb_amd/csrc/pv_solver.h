@@ -158,11 +158,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = false;
+        metricsValid_ = spectrumValid_ = false;
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = false;
+        metricsValid_ = spectrumValid_ = false;
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -253,6 +253,15 @@ public:
     bool computeRoomMetrics(float* ms);
     bool copyRoomMetricsBlock(int r0, int c0, int nr, int nc, float* out10);
     bool roomMetricsAt(float ex, float ez, float out10[10]);
+    // Spectrum (pv_spectrum.hip; include/planeverb_amd.h Spectrum): transfer functions of the last completed run at the bins set
+    // here, lifetime and refusals as the room metrics'.  setSpectrumBins: the caller has validated hz (pv_spectrum.h
+    // spectrumBinsError); n = 0 clears and frees; waits for a run in flight.  out: nr x nc x n records of three floats
+    bool setSpectrumBins(const float* hz, int n);
+    int spectrumBins(float* hz, int cap) const;
+    bool spectrumSource(float* out3n);
+    bool computeSpectrum(float* ms);
+    bool copySpectrumBlock(int r0, int c0, int nr, int nc, float* out);
+    bool spectrumAt(float ex, float ez, float* out3n);
     bool copyPulse(float* out);
     bool copyMaterial(uint8_t* beta, float* R);
     bool freeFieldEnergyAt(int cellX, int cellY, int n, float r, float* out);
@@ -463,6 +472,27 @@ private:
     enum class LastRun { None, Failed, Ok };  // Failed: in flight, or ended in error (a run is Ok once sync() has seen it through)
     LastRun lastRun_ = LastRun::None;
     bool fetchRoomMetrics();
+    // spectrum (pv_spectrum.h): the bins, their tables c / s [T * n] and source values (sre, sim, spow per bin) on the host; the
+    // passes the bins are dealt to (specPasses_: a slice of the bins, the register block that takes it, where its table slice
+    // starts in specTab_); 3 n planes of histPlane_ floats -- re, im, level of bin j at planes 3 j .. 3 j + 2 -- allocated by the
+    // first computeSpectrum and again when n changes.  spectrumValid_ follows metricsValid_ and is also cleared by a bin change;
+    // neither computation touches the other's flag.
+    struct SpecPass {
+        int bin0, bins, block;
+        size_t tabOff;
+    };
+    std::vector<float> specHz_, specCos_, specSin_, specSource_;
+    std::vector<SpecPass> specPasses_;
+    float* specTab_ = nullptr;
+    float* specPow_ = nullptr;
+    float* spectrum_ = nullptr;
+    int spectrumPlanes_ = 0;  // 3 n of the allocation
+    bool spectrumValid_ = false;
+    DynParams spectrumDyn_{};
+    std::vector<float> spectrumHost_;
+    bool spectrumHostValid_ = false;
+    hipEvent_t spectrumEv_[2] = {nullptr, nullptr};
+    bool fetchSpectrum();
     size_t scratchCount_ = 0;
 
     // pinned host staging
