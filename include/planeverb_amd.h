@@ -566,6 +566,69 @@ PVA_EXPORT int PvAmdGetRoomMetrics(PvAmdSolver* s, float ex, float ey, float ez,
 /* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T; the restatement the tests hold the
  * kernel to */
 PVA_EXPORT int PvAmdHostRoomMetrics(const float* p, int T, int fs, int onset, PvAmdRoomMetrics* out);
+/* ---- Decay times: EDT, T20 and T30 (ISO 3382) of every reached cell, read off the backward-integrated (Schroeder) curve ----
+ * PvAmdComputeDecayTimes reduces the history of the LAST COMPLETED run to one record per cell on the device (pv_decay.hip):
+ * the one pass that walks the history backwards in time, and it walks it twice (E0 is needed before the first ratio).
+ * Definition, for result cell s = X * gy + Y, with p(t) exactly what PvAmdCopyHistoryPlane(t) returns at array cell (X, Y)
+ * and delay the run's own onset map:
+ *   t0    = (int)delay[s]                      (FLT_MAX: not reached)
+ *   tailN = (int)(0.01f * (float)fs)           (the reference's PV_SCHROEDER_OFFSET_S rule: the curve's last 10 ms dip
+ *   tEnd  = T - tailN                           towards 0 because the record ends, and enter no fit)
+ *   e(t)  = p(t) * p(t)                                                        float32
+ *   E(T)  = +0.0f;  E(t) = E(t + 1) + e(t),  t = T-1 down to t0                float32, sequential in DECREASING t
+ *   E0    = E(t0)
+ *   r(t)  = E(t) / E0                          correctly rounded float32 division;  r(t0) == 1.0f
+ *   L(t)  = 10.0f * log10f(r(t))               glibc's log10f
+ *   k     = t - t0
+ *   ranges (hi, lo), as float literals:
+ *      EDT  (1.0f,        0.1f)                 0 .. -10 dB
+ *      T20  (0.31622776f, 0.0031622776f)       -5 .. -25 dB
+ *      T30  (0.31622776f, 0.00031622776f)      -5 .. -35 dB
+ *   a step t in [t0, tEnd) belongs to a range iff  r(t) <= hi && r(t) >= lo
+ *   per range, over its steps in DECREASING t:
+ *      n    = their number;  kmax / kmin = largest / smallest k among them
+ *      Sy   = sum (double)L(t)                  double, from +0.0, every sum rounded on its own
+ *      Sky  = sum ((double)k * (double)L(t))    double (the product is exact)
+ *      kbar  = ((double)kmin + (double)kmax) * 0.5
+ *      slope = (Sky - (kbar * Sy)) / ((((double)n * (((double)n * (double)n) - 1.0))) / 12.0)        dB per step
+ *      value = (float)((-60.0 / slope) / (double)fs)                                                  seconds for 60 dB
+ *   a range is COMPLETE iff  t0 < tEnd  &&  r(tEnd - 1) < lo     (the curve fell below the lower limit before the tail)
+ *   value = quiet NaN (0x7fc00000) unless the range is complete and n >= 2; otherwise nothing is special-cased
+ *           (slope >= 0 gives -inf or a negative value, as IEEE says)
+ *   depth = t0 < tEnd ? L(tEnd - 1) : quiet NaN                   (how deep the usable curve goes, dB)
+ *   record (8 floats): edt, t20, t30, (float)n_edt, (float)n_t20, (float)n_t30, E0, depth
+ * Because e(t) >= 0, E and therefore r never increase with t: each range's steps form one contiguous interval, kbar is its
+ * exact midpoint and n (n^2 - 1) / 12 its exact centred sum of squares -- the reference's own centred regression
+ * (Analyzer.cpp:290-294) without a pass that finds the interval first.  The two regression sums are double because
+ * Sky - kbar Sy cancels.  Nothing is fused: no FMA, in float or in double.
+ * The records describe the recorded T steps only: a decay that has not fallen below a range's lower limit before the tail
+ * leaves that range incomplete (NaN) rather than extrapolated.  depth and the three n are there so that a caller can apply a
+ * headroom rule of their own, for example require depth <= lower limit - 10 dB.  The reference's rt60 (PvAmdCopyResults) is
+ * another quantity -- one float32 regression over the whole curve -- and stays as it is.
+ * A cell WITHOUT an onset in that run holds eight quiet NaNs; nothing is carried over from earlier runs.  Cells inside an edge
+ * layer get records like any other cell, as unphysical there as their other outputs.
+ * Device storage: 8 x 4 bytes per cell of the history window (tile-rounded), allocated by the first call, freed with the
+ * solver; cells outside the window are unreached by construction.  The records stay valid until the next run, geometry,
+ * boundary or layer change on that solver: PvAmdCopyDecayTimes* / PvAmdGetDecayTimes then return -1 until computed again.
+ * Room metrics, spectrum and decay times do not invalidate each other.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "decay times: ..."): NULL, no completed run, a last run that ended in
+ * error, sparse-emitter solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks. */
+typedef struct PvAmdDecayTimes {
+    float edt, t20, t30, n_edt, n_t20, n_t30, e0, depth;
+} PvAmdDecayTimes;
+/* Compute the decay times of the LAST COMPLETED run of s (waits for a run in flight; works after every form of run, as
+ * PvAmdComputeRoomMetrics).  Synchronous on the solver's own stream.  *ms (optional): device time of the pass. */
+PVA_EXPORT int PvAmdComputeDecayTimes(PvAmdSolver* s, float* ms);
+/* gx*gy*8 floats, AoS records, cell s = X*gy + Y */
+PVA_EXPORT int PvAmdCopyDecayTimes(PvAmdSolver* s, float* out8);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records, row-major */
+PVA_EXPORT int PvAmdCopyDecayTimesBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out8);
+/* the record at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map gives eight NaNs
+ * and 0 */
+PVA_EXPORT int PvAmdGetDecayTimes(PvAmdSolver* s, float ex, float ey, float ez, PvAmdDecayTimes* out);
+/* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T (refused otherwise); the restatement
+ * the tests hold the kernel to */
+PVA_EXPORT int PvAmdHostDecayTimes(const float* p, int T, int fs, int onset, PvAmdDecayTimes* out);
 /* ---- Spectrum: the transfer function from the listener to every reached cell, at chosen frequencies ----
  * How loud the room is at ONE frequency at one position (room modes and their nodal lines, comb filtering behind an obstacle,
  * per-band gains): PvAmdComputeSpectrum reduces the history of the LAST COMPLETED run to three floats per bin and cell in one

@@ -113,6 +113,16 @@ class PvAmdRoomMetrics(C.Structure):
         return np.frombuffer(self, np.float32).copy()
 
 
+DECAY_TIME_NAMES = ("edt", "t20", "t30", "n_edt", "n_t20", "n_t30", "e0", "depth")
+
+
+class PvAmdDecayTimes(C.Structure):
+    _fields_ = [(n, C.c_float) for n in DECAY_TIME_NAMES]
+
+    def as_array(self):
+        return np.frombuffer(self, np.float32).copy()
+
+
 # every symbol include/planeverb_amd.h declares: name -> (restype, argtypes)
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -241,6 +251,11 @@ SYMBOLS = {
     "PvAmdCopyRoomMetricsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "PvAmdGetRoomMetrics": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdRoomMetrics)]),
     "PvAmdHostRoomMetrics": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdRoomMetrics)]),
+    "PvAmdComputeDecayTimes": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyDecayTimes": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyDecayTimesBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetDecayTimes": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdDecayTimes)]),
+    "PvAmdHostDecayTimes": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdDecayTimes)]),
     "PvAmdSetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetSpectrumSource": (C.c_int, [_vp, _fp]),
@@ -666,6 +681,15 @@ def host_room_metrics(p, fs, onset):
     a = np.ascontiguousarray(p, np.float32).reshape(-1)
     out = PvAmdRoomMetrics()
     _check(lib().PvAmdHostRoomMetrics(_f(a) if a.size else None, int(a.size), int(fs), int(onset), out))
+    return out.as_array()
+
+
+def host_decay_times(p, fs, onset):
+    """PvAmdHostDecayTimes: float32 [8] (DECAY_TIME_NAMES) of one impulse response p[T] with its onset step -- the
+    definition of include/planeverb_amd.h (PvAmdDecayTimes) on the CPU"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    out = PvAmdDecayTimes()
+    _check(lib().PvAmdHostDecayTimes(_f(a) if a.size else None, int(a.size), int(fs), int(onset), out))
     return out.as_array()
 
 
@@ -1328,6 +1352,32 @@ class Solver:
         """float32 [10] at an emitter position (the cell get_output reads); ten NaNs off the map"""
         out = PvAmdRoomMetrics()
         _check(lib().PvAmdGetRoomMetrics(self._h, *[float(v) for v in pos], out))
+        return out.as_array()
+
+    def compute_decay_times(self):
+        """decay times (EDT, T20, T30: DECAY_TIME_NAMES) of the last completed run, two backward walks of its history on the
+        device; returns the pass's device time in milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeDecayTimes(self._h, C.byref(ms)))
+        return ms.value
+
+    def decay_times(self):
+        """float32 [gx, gy, 8] (DECAY_TIME_NAMES); NaN where the cell has no onset in the run they were computed for, and in
+        edt / t20 / t30 where the recorded curve does not fall through the range"""
+        out = np.empty((self.gx, self.gy, 8), np.float32)
+        _check(lib().PvAmdCopyDecayTimes(self._h, _f(out)))
+        return out
+
+    def decay_times_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, 8] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, 8), np.float32)
+        _check(lib().PvAmdCopyDecayTimesBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def decay_times_at(self, pos):
+        """float32 [8] at an emitter position (the cell get_output reads); eight NaNs off the map"""
+        out = PvAmdDecayTimes()
+        _check(lib().PvAmdGetDecayTimes(self._h, *[float(v) for v in pos], out))
         return out.as_array()
 
     def set_spectrum_bins(self, hz):

@@ -11,6 +11,7 @@
 #include "../../include/planeverb_amd.h"
 #include "pv_context.h"
 #include "pv_core.h"
+#include "pv_decay.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
@@ -1123,6 +1124,50 @@ int PvAmdGetRoomMetrics(PvAmdSolver* h, float ex, float ey, float ez, PvAmdRoomM
     return 0;
 } PV_API_CATCH(-1)
 
+// decay times (pv_decay.hip): single whole-grid solvers only, as the room metrics; every refusal says "decay times: ..."
+static bool decayHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "decay times: " + g_lastError;
+    return false;
+}
+
+int PvAmdComputeDecayTimes(PvAmdSolver* h, float* ms) try {
+    if (!decayHandle(h)) return -1;
+    return ret(h, h->s->computeDecayTimes(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyDecayTimes(PvAmdSolver* h, float* out8) try {
+    if (!decayHandle(h)) return -1;
+    if (!out8) {
+        g_lastError = "decay times: PvAmdCopyDecayTimes: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyDecayTimesBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out8));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyDecayTimesBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out8) try {
+    if (!decayHandle(h)) return -1;
+    if (!out8) {
+        g_lastError = "decay times: PvAmdCopyDecayTimesBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyDecayTimesBlock(r0, c0, nr, nc, out8));
+} PV_API_CATCH(-1)
+
+int PvAmdGetDecayTimes(PvAmdSolver* h, float ex, float ey, float ez, PvAmdDecayTimes* out) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!decayHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "decay times: PvAmdGetDecayTimes: null output";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdDecayTimes) == kDecayFloats * sizeof(float), "eight floats");
+    float v[kDecayFloats];
+    if (!h->s->decayTimesAt(ex, ez, v)) return ret(h, false);
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
 // spectrum (pv_spectrum.hip): single whole-grid solvers only, as the room metrics.  The bins are checked against the handle's
 // own grid before anything else happens (pv_spectrum.h spectrumBinsError, the rule the host calls apply too)
 int PvAmdSetSpectrumBins(PvAmdSolver* h, const float* hz, int n) try {
@@ -1489,6 +1534,18 @@ int PvAmdHostRoomMetrics(const float* p, int T, int fs, int onset, PvAmdRoomMetr
     static_assert(sizeof(PvAmdRoomMetrics) == kRoomMetricFloats * sizeof(float), "ten floats");
     float v[kRoomMetricFloats];
     roomMetricsOfIr(p, T, fs, onset, v);
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostDecayTimes(const float* p, int T, int fs, int onset, PvAmdDecayTimes* out) try {
+    if (!p || !out || T <= 0 || onset < 0 || onset >= T) {
+        g_lastError = "decay times: PvAmdHostDecayTimes: an impulse response p[T], T > 0, 0 <= onset < T and an output record";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdDecayTimes) == kDecayFloats * sizeof(float), "eight floats");
+    float v[kDecayFloats];
+    decayTimesOfIr(p, T, fs, onset, v);
     std::memcpy(out, v, sizeof(*out));
     return 0;
 } PV_API_CATCH(-1)

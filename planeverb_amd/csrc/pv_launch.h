@@ -129,6 +129,12 @@ void launchRunFinish(const float* res, long long n, const long long* cellsHost, 
 // cell's offset inside a history plane; NaN where the cell has no onset in that run
 void launchRoomMetrics(const AnalyzeArgs& a, float* out, hipStream_t stream);
 
+// ---- pv_decay.hip: per-cell decay times
+// decay times (EDT, T20, T30) of the last completed run (pv_decay.hip): out = kDecayFloats planes of a.histPlane floats, indexed
+// by the cell's offset inside a history plane; NaN where the cell has no onset in that run.  twoLaunches: the two walks of the
+// curve as a launch each (measurement; the records are the same bits)
+void launchDecayTimes(const AnalyzeArgs& a, float* out, bool twoLaunches, hipStream_t stream);
+
 // ---- pv_spectrum.hip: per-cell transfer functions at chosen frequencies
 // One pass over the history of the last completed run for `bins` bins held `block` to a lane (spectrumBlockOk(block); bins <=
 // block).  tab: the pass's twiddles on the device, row t = {cos, sin} pairs of its `block` bins (2 * block floats, bins past

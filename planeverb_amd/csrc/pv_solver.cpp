@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "pv_launch.h"
+#include "pv_decay.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
 
@@ -671,6 +672,9 @@ Solver::~Solver() {
     if (metrics_) hipFree(metrics_);
     for (auto& e : metricsEv_)
         if (e) hipEventDestroy(e);
+    if (decay_) hipFree(decay_);
+    for (auto& e : decayEv_)
+        if (e) hipEventDestroy(e);
     for (float* p : {specTab_, specPow_, spectrum_})
         if (p) hipFree(p);
     for (auto& e : spectrumEv_)
@@ -752,7 +756,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = false;
     return id;
 }
 
@@ -763,7 +767,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = false;
     return true;
 }
 
@@ -774,7 +778,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = false;
     return true;
 }
 
@@ -846,14 +850,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -1000,7 +1004,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = spectrumValid_ = false;
+    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = false;
     return true;
 }
 
@@ -1040,7 +1044,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = spectrumValid_ = false;
+    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = false;
     return true;
 }
 
@@ -2087,7 +2091,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = spectrumValid_ = false;       // (the history the records were made from is about to be overwritten)
+    metricsValid_ = spectrumValid_ = decayValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     if (!applyGeometry()) return false;
     PathRun r;
@@ -2953,6 +2957,87 @@ bool Solver::roomMetricsAt(float ex, float ez, float out10[10]) {
         return true;
     }
     return copyRoomMetricsBlock(cx, cy, 1, 1, out10);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// decay times (pv_decay.hip): everything as the room metrics above, with eight planes
+// ----------------------------------------------------------------------------------------------------------------
+
+// PLANEVERB_AMD_DECAY_LAUNCHES = 2: the two walks of the curve as a launch each (measurement: profiles/decay_times.txt)
+static bool decayTwoLaunches() {
+    static const bool two = [] {
+        const char* e = std::getenv("PLANEVERB_AMD_DECAY_LAUNCHES");
+        return e && std::atoi(e) == 2;
+    }();
+    return two;
+}
+
+bool Solver::computeDecayTimes(float* ms) {
+    if (isSlab()) return fail("decay times: not available on a slab");
+    if (opt_.streaming) return fail("decay times: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("decay times: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("decay times: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("decay times: the last run ended in error");
+    if (!decay_ && !dalloc(&decay_, (size_t)kDecayFloats * (size_t)histPlane_, false)) return false;
+    for (auto& e : decayEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    decayValid_ = false;
+    decayHostValid_ = false;
+    hipEventRecord(decayEv_[0], stream_);
+    launchDecayTimes(analyzeArgs(lastLx_, lastLz_), decay_, decayTwoLaunches(), stream_);
+    hipEventRecord(decayEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "decay times launch") || !hipOk(hipStreamSynchronize(stream_), "decay times sync")) return false;
+    if (ms) hipEventElapsedTime(ms, decayEv_[0], decayEv_[1]);
+    decayDyn_ = dynCur_;
+    decayValid_ = true;
+    return true;
+}
+
+bool Solver::fetchDecayTimes() {
+    if (!decayValid_) return fail("decay times: not computed for the last run and the current geometry (PvAmdComputeDecayTimes)");
+    if (decayHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    decayHost_.resize((size_t)kDecayFloats * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(decayHost_.data(), decay_, decayHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "decay times copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "decay times sync"))
+        return false;
+    decayHostValid_ = true;
+    return true;
+}
+
+bool Solver::copyDecayTimesBlock(int r0, int c0, int nr, int nc, float* out8) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("decay times: block outside the map");
+    if (!fetchDecayTimes()) return false;
+    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
+    const int wr0 = decayDyn_.histRow0 - geo_.G, wc0 = decayDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out8 + ((size_t)r * nc + c) * kDecayFloats;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < kDecayFloats; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * decayDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < kDecayFloats; ++k) o[k] = decayHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::decayTimesAt(float ex, float ez, float out8[8]) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!decayValid_) return fetchDecayTimes();
+        for (int k = 0; k < kDecayFloats; ++k) out8[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copyDecayTimesBlock(cx, cy, 1, 1, out8);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

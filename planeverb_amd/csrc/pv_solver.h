@@ -158,11 +158,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = spectrumValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = false;
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = spectrumValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = false;
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -253,6 +253,12 @@ public:
     bool computeRoomMetrics(float* ms);
     bool copyRoomMetricsBlock(int r0, int c0, int nr, int nc, float* out10);
     bool roomMetricsAt(float ex, float ez, float out10[10]);
+    // Decay times (pv_decay.hip; include/planeverb_amd.h PvAmdDecayTimes) of the last completed run: EDT, T20, T30 off the
+    // backward-integrated curve of its history; stream, synchronisation, lifetime and refusals as the room metrics'.  out8: nr x nc
+    // records of eight floats, NaN where the cell has no onset in that run
+    bool computeDecayTimes(float* ms);
+    bool copyDecayTimesBlock(int r0, int c0, int nr, int nc, float* out8);
+    bool decayTimesAt(float ex, float ez, float out8[8]);
     // Spectrum (pv_spectrum.hip; include/planeverb_amd.h Spectrum): transfer functions of the last completed run at the bins set
     // here, lifetime and refusals as the room metrics'.  setSpectrumBins: the caller has validated hz (pv_spectrum.h
     // spectrumBinsError); n = 0 clears and frees; waits for a run in flight.  out: nr x nc x n records of three floats
@@ -472,6 +478,15 @@ private:
     enum class LastRun { None, Failed, Ok };  // Failed: in flight, or ended in error (a run is Ok once sync() has seen it through)
     LastRun lastRun_ = LastRun::None;
     bool fetchRoomMetrics();
+    // decay times: eight planes of histPlane_ floats, kept exactly as the room metrics' ten (allocated by the first
+    // computeDecayTimes); decayValid_ follows metricsValid_, and neither computation touches the other's flag
+    float* decay_ = nullptr;
+    bool decayValid_ = false;
+    DynParams decayDyn_{};
+    std::vector<float> decayHost_;
+    bool decayHostValid_ = false;
+    hipEvent_t decayEv_[2] = {nullptr, nullptr};
+    bool fetchDecayTimes();
     // spectrum (pv_spectrum.h): the bins, their tables c / s [T * n] and source values (sre, sim, spow per bin) on the host; the
     // passes the bins are dealt to (specPasses_: a slice of the bins, the register block that takes it, where its table slice
     // starts in specTab_); 3 n planes of histPlane_ floats -- re, im, level of bin j at planes 3 j .. 3 j + 2 -- allocated by the
