@@ -629,6 +629,65 @@ PVA_EXPORT int PvAmdGetDecayTimes(PvAmdSolver* s, float ex, float ey, float ez, 
 /* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T (refused otherwise); the restatement
  * the tests hold the kernel to */
 PVA_EXPORT int PvAmdHostDecayTimes(const float* p, int T, int fs, int onset, PvAmdDecayTimes* out);
+/* ---- Lateral energy fraction and early-sound direction: the spatial measure of ISO 3382-1 (LF, A.2) of every reached cell ----
+ * The share of the first 80 ms of energy that arrives from the side, as seen by a figure-of-eight microphone whose null points
+ * at the source -- here: along the direction the early sound travels in.  A pressure-only tool cannot compute it; an FDTD
+ * solver can, because the particle velocity is part of its state.  PvAmdComputeLateralFraction reduces the history of the LAST
+ * COMPLETED run to one record per cell on the device (pv_lateral.hip), re-deriving vx, vy of every reached cell from the
+ * recorded pressure with the stencil's own recurrence through the whole window.
+ * Definition, for result cell s = X * gy + Y, with delay the run's own onset map and p(t), vx(t), vy(t) exactly what
+ * PvAmdGetImpulseResponse returns for array cell (X, Y).  vx, vy are the library's velocity of a cell:
+ *   on an air|air face     v(t) = v(t - 1) - C * (p(t)[cell] - p(t)[neighbour])      neighbours (X - 1, Y) for vx, (X, Y - 1) for vy
+ *   otherwise              v(t) = k * (p(t)[cell] + p(t)[neighbour])                 k the face's wall coefficient
+ *   the recurrence starts from 0 at the cell's first recorded sample, not at its onset.
+ * Inside an edge layer this is the UNDAMPED recurrence (the layer's damping of the velocity is not applied), as it already is
+ * for the source directivity of the eight outputs.
+ *   onset = (int)delay[s]                      (FLT_MAX: not reached)
+ *   n5    = (int)(0.005f * (float)fs)          the direct sound: the first 5 ms give the direction
+ *   n80   = (int)(0.08f * (float)fs)
+ *   tEnd  = min(onset + n80, T)
+ *   for t = onset .. tEnd - 1, k = t - onset, every sum float32, sequential in increasing t from +0.0f:
+ *      e80 = e80 + p*p
+ *      fx  = fx  + (k <  n5 ? p*vx  : 0.f)      fy  = fy  + (k <  n5 ? p*vy  : 0.f)
+ *      sxx = sxx + (k >= n5 ? vx*vx : 0.f)      sxy = sxy + (k >= n5 ? vx*vy : 0.f)      syy = syy + (k >= n5 ? vy*vy : 0.f)
+ *   norm = sqrtf(fx*fx + fy*fy);  dx = fx / norm;  dy = fy / norm
+ *   lat  = ((sxx * (dy*dy)) - (2.0f * (sxy * (dx*dy)))) + (syy * (dx*dx))
+ *   lf   = lat / e80
+ *   record (11 floats): lf, dir_x, dir_y, n = (float)(tEnd - onset), e80, lateral, fx, fy, sxx, sxy, syy
+ * Every product, sum and quotient is rounded on its own (no FMA).  lat is the energy of the velocity component perpendicular
+ * to (dx, dy) over the steps after the direct sound: the three second moments make it a quadratic form in the direction, which
+ * therefore need not be known while the window is walked.  Pressure and velocity are in the solver's own units, so lf is the
+ * library's measure, comparable between cells and scenes of one resolution; an open field reads near 0, a closed room 0.1 .. 0.5,
+ * and values above 1 occur beside walls and at pressure nodes and are kept.
+ * (dx, dy) is the direction in which the early sound TRAVELS at the cell (away from the listener); it is not negated as the
+ * source directivity of the eight outputs is.
+ * Nothing is special-cased: a zero flux gives NaN for dx, dy and lf (the sums stay numbers), and a window cut off by T is
+ * reported through n < n80.
+ * A cell WITHOUT an onset in that run holds eleven quiet NaNs; nothing is carried over from earlier runs.  Cells inside an edge
+ * layer get records like any other cell.
+ * Device storage: 11 x 4 bytes per cell of the history window (tile-rounded), allocated by the first call, freed with the
+ * solver.  The records stay valid until the next run, geometry, boundary or layer change on that solver:
+ * PvAmdCopyLateralFraction* / PvAmdGetLateralFraction then return -1 until computed again.  Room metrics, spectrum, decay times
+ * and lateral fraction do not invalidate each other.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "lateral fraction: ..."): NULL, no completed run, a last run that ended
+ * in error, sparse-emitter solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks. */
+typedef struct PvAmdLateralFraction {
+    float lf, dir_x, dir_y, n, e80, lateral, fx, fy, sxx, sxy, syy;
+} PvAmdLateralFraction;
+/* Compute the lateral-fraction records of the LAST COMPLETED run of s (waits for a run in flight; works after every form of run,
+ * as PvAmdComputeRoomMetrics).  Synchronous on the solver's own stream.  *ms (optional): device time of the pass. */
+PVA_EXPORT int PvAmdComputeLateralFraction(PvAmdSolver* s, float* ms);
+/* gx*gy*11 floats, AoS records, cell s = X*gy + Y */
+PVA_EXPORT int PvAmdCopyLateralFraction(PvAmdSolver* s, float* out11);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records, row-major */
+PVA_EXPORT int PvAmdCopyLateralFractionBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out11);
+/* the record at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map gives eleven NaNs
+ * and 0 */
+PVA_EXPORT int PvAmdGetLateralFraction(PvAmdSolver* s, float ex, float ey, float ez, PvAmdLateralFraction* out);
+/* CPU only: the definition above applied to one impulse response p[T], vx[T], vy[T] with 0 <= onset < T (refused otherwise);
+ * the restatement the tests hold the kernel to */
+PVA_EXPORT int PvAmdHostLateralFraction(const float* p, const float* vx, const float* vy, int T, int fs, int onset,
+                                        PvAmdLateralFraction* out);
 /* ---- Spectrum: the transfer function from the listener to every reached cell, at chosen frequencies ----
  * How loud the room is at ONE frequency at one position (room modes and their nodal lines, comb filtering behind an obstacle,
  * per-band gains): PvAmdComputeSpectrum reduces the history of the LAST COMPLETED run to three floats per bin and cell in one

@@ -36,6 +36,8 @@ def main(argv=None):
                     help="add the room metrics (C50, C80, D50, Ts and their sums) of each emitter's cell")
     ap.add_argument("--decay-times", action="store_true",
                     help="add the decay times (EDT, T20, T30, their point counts, E0 and the curve's depth) of each emitter's cell")
+    ap.add_argument("--lateral-fraction", action="store_true",
+                    help="add the early lateral energy fraction, the early-sound direction and their sums of each emitter's cell")
     ap.add_argument("--spectrum", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the transfer function (re, im, level in dB re the source) of each emitter's cell at these frequencies")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
@@ -62,6 +64,8 @@ def main(argv=None):
             s.compute_room_metrics()
         if a.decay_times:
             s.compute_decay_times()
+        if a.lateral_fraction:
+            s.compute_lateral_fraction()
         if a.spectrum:
             s.set_spectrum_bins(a.spectrum)
             s.compute_spectrum()
@@ -78,6 +82,9 @@ def main(argv=None):
             if a.decay_times:
                 m = s.decay_times_at(e)
                 out["emitters"][-1]["decayTimes"] = dict((n, float(v)) for n, v in zip(api.DECAY_TIME_NAMES, m))
+            if a.lateral_fraction:
+                m = s.lateral_fraction_at(e)
+                out["emitters"][-1]["lateralFraction"] = dict((n, float(v)) for n, v in zip(api.LATERAL_FRACTION_NAMES, m))
             if a.spectrum:
                 m = s.spectrum_at(e)
                 out["emitters"][-1]["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],

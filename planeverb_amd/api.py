@@ -123,6 +123,16 @@ class PvAmdDecayTimes(C.Structure):
         return np.frombuffer(self, np.float32).copy()
 
 
+LATERAL_FRACTION_NAMES = ("lf", "dir_x", "dir_y", "n", "e80", "lateral", "fx", "fy", "sxx", "sxy", "syy")
+
+
+class PvAmdLateralFraction(C.Structure):
+    _fields_ = [(n, C.c_float) for n in LATERAL_FRACTION_NAMES]
+
+    def as_array(self):
+        return np.frombuffer(self, np.float32).copy()
+
+
 # every symbol include/planeverb_amd.h declares: name -> (restype, argtypes)
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -256,6 +266,11 @@ SYMBOLS = {
     "PvAmdCopyDecayTimesBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "PvAmdGetDecayTimes": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdDecayTimes)]),
     "PvAmdHostDecayTimes": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdDecayTimes)]),
+    "PvAmdComputeLateralFraction": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyLateralFraction": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyLateralFractionBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetLateralFraction": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdLateralFraction)]),
+    "PvAmdHostLateralFraction": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdLateralFraction)]),
     "PvAmdSetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetSpectrumSource": (C.c_int, [_vp, _fp]),
@@ -690,6 +705,18 @@ def host_decay_times(p, fs, onset):
     a = np.ascontiguousarray(p, np.float32).reshape(-1)
     out = PvAmdDecayTimes()
     _check(lib().PvAmdHostDecayTimes(_f(a) if a.size else None, int(a.size), int(fs), int(onset), out))
+    return out.as_array()
+
+
+def host_lateral_fraction(p, vx, vy, fs, onset):
+    """PvAmdHostLateralFraction: float32 [11] (LATERAL_FRACTION_NAMES) of one impulse response p[T] with its velocities vx[T],
+    vy[T] and its onset step -- the definition of include/planeverb_amd.h (PvAmdLateralFraction) on the CPU"""
+    a, x, y = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (p, vx, vy))
+    if not (a.size == x.size == y.size):
+        raise ValueError("host_lateral_fraction: p, vx and vy must have the same length")
+    out = PvAmdLateralFraction()
+    ptr = [_f(v) if v.size else None for v in (a, x, y)]
+    _check(lib().PvAmdHostLateralFraction(ptr[0], ptr[1], ptr[2], int(a.size), int(fs), int(onset), out))
     return out.as_array()
 
 
@@ -1378,6 +1405,33 @@ class Solver:
         """float32 [8] at an emitter position (the cell get_output reads); eight NaNs off the map"""
         out = PvAmdDecayTimes()
         _check(lib().PvAmdGetDecayTimes(self._h, *[float(v) for v in pos], out))
+        return out.as_array()
+
+    def compute_lateral_fraction(self):
+        """early lateral energy fraction and early-sound direction (LATERAL_FRACTION_NAMES) of the last completed run: the
+        velocity recurrence through the 80 ms window of every reached cell, on the device; returns the pass's device time in
+        milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeLateralFraction(self._h, C.byref(ms)))
+        return ms.value
+
+    def lateral_fraction(self):
+        """float32 [gx, gy, 11] (LATERAL_FRACTION_NAMES); NaN where the cell has no onset in the run they were computed for, and
+        in lf / dir_x / dir_y where the early flux is zero"""
+        out = np.empty((self.gx, self.gy, 11), np.float32)
+        _check(lib().PvAmdCopyLateralFraction(self._h, _f(out)))
+        return out
+
+    def lateral_fraction_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, 11] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, 11), np.float32)
+        _check(lib().PvAmdCopyLateralFractionBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def lateral_fraction_at(self, pos):
+        """float32 [11] at an emitter position (the cell get_output reads); eleven NaNs off the map"""
+        out = PvAmdLateralFraction()
+        _check(lib().PvAmdGetLateralFraction(self._h, *[float(v) for v in pos], out))
         return out.as_array()
 
     def set_spectrum_bins(self, hz):

@@ -12,6 +12,7 @@
 #include "pv_context.h"
 #include "pv_core.h"
 #include "pv_decay.h"
+#include "pv_lateral.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
@@ -1168,6 +1169,50 @@ int PvAmdGetDecayTimes(PvAmdSolver* h, float ex, float ey, float ez, PvAmdDecayT
     return 0;
 } PV_API_CATCH(-1)
 
+// lateral fraction (pv_lateral.hip): single whole-grid solvers only, as the room metrics; every refusal says "lateral fraction: ..."
+static bool lateralHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "lateral fraction: " + g_lastError;
+    return false;
+}
+
+int PvAmdComputeLateralFraction(PvAmdSolver* h, float* ms) try {
+    if (!lateralHandle(h)) return -1;
+    return ret(h, h->s->computeLateralFraction(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyLateralFraction(PvAmdSolver* h, float* out11) try {
+    if (!lateralHandle(h)) return -1;
+    if (!out11) {
+        g_lastError = "lateral fraction: PvAmdCopyLateralFraction: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyLateralFractionBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out11));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyLateralFractionBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out11) try {
+    if (!lateralHandle(h)) return -1;
+    if (!out11) {
+        g_lastError = "lateral fraction: PvAmdCopyLateralFractionBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyLateralFractionBlock(r0, c0, nr, nc, out11));
+} PV_API_CATCH(-1)
+
+int PvAmdGetLateralFraction(PvAmdSolver* h, float ex, float ey, float ez, PvAmdLateralFraction* out) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!lateralHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "lateral fraction: PvAmdGetLateralFraction: null output";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdLateralFraction) == kLateralFloats * sizeof(float), "eleven floats");
+    float v[kLateralFloats];
+    if (!h->s->lateralFractionAt(ex, ez, v)) return ret(h, false);
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
 // spectrum (pv_spectrum.hip): single whole-grid solvers only, as the room metrics.  The bins are checked against the handle's
 // own grid before anything else happens (pv_spectrum.h spectrumBinsError, the rule the host calls apply too)
 int PvAmdSetSpectrumBins(PvAmdSolver* h, const float* hz, int n) try {
@@ -1546,6 +1591,19 @@ int PvAmdHostDecayTimes(const float* p, int T, int fs, int onset, PvAmdDecayTime
     static_assert(sizeof(PvAmdDecayTimes) == kDecayFloats * sizeof(float), "eight floats");
     float v[kDecayFloats];
     decayTimesOfIr(p, T, fs, onset, v);
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostLateralFraction(const float* p, const float* vx, const float* vy, int T, int fs, int onset,
+                             PvAmdLateralFraction* out) try {
+    if (!p || !vx || !vy || !out || T <= 0 || onset < 0 || onset >= T) {
+        g_lastError = "lateral fraction: PvAmdHostLateralFraction: an impulse response p[T], vx[T], vy[T], T > 0, 0 <= onset < T and an output record";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdLateralFraction) == kLateralFloats * sizeof(float), "eleven floats");
+    float v[kLateralFloats];
+    lateralFractionOfIr(p, vx, vy, T, fs, onset, v);
     std::memcpy(out, v, sizeof(*out));
     return 0;
 } PV_API_CATCH(-1)

@@ -135,6 +135,12 @@ void launchRoomMetrics(const AnalyzeArgs& a, float* out, hipStream_t stream);
 // curve as a launch each (measurement; the records are the same bits)
 void launchDecayTimes(const AnalyzeArgs& a, float* out, bool twoLaunches, hipStream_t stream);
 
+// ---- pv_lateral.hip: per-cell lateral energy fraction and early-sound direction
+// lateral-fraction records of the last completed run (pv_lateral.hip): out = kLateralFloats planes of a.histPlane floats, indexed
+// by the cell's offset inside a history plane; NaN where the cell has no onset in that run.  Whole-grid solvers only (the pass
+// does not read a slab's histAbove)
+void launchLateralFraction(const AnalyzeArgs& a, float* out, hipStream_t stream);
+
 // ---- pv_spectrum.hip: per-cell transfer functions at chosen frequencies
 // One pass over the history of the last completed run for `bins` bins held `block` to a lane (spectrumBlockOk(block); bins <=
 // block).  tab: the pass's twiddles on the device, row t = {cos, sin} pairs of its `block` bins (2 * block floats, bins past

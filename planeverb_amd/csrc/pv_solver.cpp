@@ -19,6 +19,7 @@
 
 #include "pv_launch.h"
 #include "pv_decay.h"
+#include "pv_lateral.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
 
@@ -675,6 +676,9 @@ Solver::~Solver() {
     if (decay_) hipFree(decay_);
     for (auto& e : decayEv_)
         if (e) hipEventDestroy(e);
+    if (lateral_) hipFree(lateral_);
+    for (auto& e : lateralEv_)
+        if (e) hipEventDestroy(e);
     for (float* p : {specTab_, specPow_, spectrum_})
         if (p) hipFree(p);
     for (auto& e : spectrumEv_)
@@ -756,7 +760,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     return id;
 }
 
@@ -767,7 +771,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     return true;
 }
 
@@ -778,7 +782,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     return true;
 }
 
@@ -850,14 +854,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -1004,7 +1008,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = false;
+    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     return true;
 }
 
@@ -1044,7 +1048,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = false;
+    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     return true;
 }
 
@@ -2091,7 +2095,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = spectrumValid_ = decayValid_ = false;       // (the history the records were made from is about to be overwritten)
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     if (!applyGeometry()) return false;
     PathRun r;
@@ -3038,6 +3042,78 @@ bool Solver::decayTimesAt(float ex, float ez, float out8[8]) {
         return true;
     }
     return copyDecayTimesBlock(cx, cy, 1, 1, out8);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// lateral energy fraction and early-sound direction (pv_lateral.hip): everything as the decay times above, with eleven planes
+// ----------------------------------------------------------------------------------------------------------------
+
+bool Solver::computeLateralFraction(float* ms) {
+    if (isSlab()) return fail("lateral fraction: not available on a slab");
+    if (opt_.streaming) return fail("lateral fraction: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("lateral fraction: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("lateral fraction: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("lateral fraction: the last run ended in error");
+    if (!lateral_ && !dalloc(&lateral_, (size_t)kLateralFloats * (size_t)histPlane_, false)) return false;
+    for (auto& e : lateralEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    lateralValid_ = false;
+    lateralHostValid_ = false;
+    hipEventRecord(lateralEv_[0], stream_);
+    launchLateralFraction(analyzeArgs(lastLx_, lastLz_), lateral_, stream_);
+    hipEventRecord(lateralEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "lateral fraction launch") || !hipOk(hipStreamSynchronize(stream_), "lateral fraction sync")) return false;
+    if (ms) hipEventElapsedTime(ms, lateralEv_[0], lateralEv_[1]);
+    lateralDyn_ = dynCur_;
+    lateralValid_ = true;
+    return true;
+}
+
+bool Solver::fetchLateralFraction() {
+    if (!lateralValid_) return fail("lateral fraction: not computed for the last run and the current geometry (PvAmdComputeLateralFraction)");
+    if (lateralHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    lateralHost_.resize((size_t)kLateralFloats * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(lateralHost_.data(), lateral_, lateralHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "lateral fraction copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "lateral fraction sync"))
+        return false;
+    lateralHostValid_ = true;
+    return true;
+}
+
+bool Solver::copyLateralFractionBlock(int r0, int c0, int nr, int nc, float* out11) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("lateral fraction: block outside the map");
+    if (!fetchLateralFraction()) return false;
+    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
+    const int wr0 = lateralDyn_.histRow0 - geo_.G, wc0 = lateralDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out11 + ((size_t)r * nc + c) * kLateralFloats;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < kLateralFloats; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * lateralDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < kLateralFloats; ++k) o[k] = lateralHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::lateralFractionAt(float ex, float ez, float out11[11]) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!lateralValid_) return fetchLateralFraction();
+        for (int k = 0; k < kLateralFloats; ++k) out11[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copyLateralFractionBlock(cx, cy, 1, 1, out11);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

@@ -158,11 +158,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -259,6 +259,12 @@ public:
     bool computeDecayTimes(float* ms);
     bool copyDecayTimesBlock(int r0, int c0, int nr, int nc, float* out8);
     bool decayTimesAt(float ex, float ez, float out8[8]);
+    // Lateral energy fraction and early-sound direction (pv_lateral.hip; include/planeverb_amd.h PvAmdLateralFraction) of the last
+    // completed run: vx, vy of every reached cell re-derived from its history through the 80 ms window; stream, synchronisation,
+    // lifetime and refusals as the room metrics'.  out11: nr x nc records of eleven floats, NaN where the cell has no onset in that run
+    bool computeLateralFraction(float* ms);
+    bool copyLateralFractionBlock(int r0, int c0, int nr, int nc, float* out11);
+    bool lateralFractionAt(float ex, float ez, float out11[11]);
     // Spectrum (pv_spectrum.hip; include/planeverb_amd.h Spectrum): transfer functions of the last completed run at the bins set
     // here, lifetime and refusals as the room metrics'.  setSpectrumBins: the caller has validated hz (pv_spectrum.h
     // spectrumBinsError); n = 0 clears and frees; waits for a run in flight.  out: nr x nc x n records of three floats
@@ -487,6 +493,15 @@ private:
     bool decayHostValid_ = false;
     hipEvent_t decayEv_[2] = {nullptr, nullptr};
     bool fetchDecayTimes();
+    // lateral fraction: eleven planes of histPlane_ floats, kept exactly as the decay times' eight (allocated by the first
+    // computeLateralFraction); lateralValid_ follows metricsValid_, and no computation touches another's flag
+    float* lateral_ = nullptr;
+    bool lateralValid_ = false;
+    DynParams lateralDyn_{};
+    std::vector<float> lateralHost_;
+    bool lateralHostValid_ = false;
+    hipEvent_t lateralEv_[2] = {nullptr, nullptr};
+    bool fetchLateralFraction();
     // spectrum (pv_spectrum.h): the bins, their tables c / s [T * n] and source values (sre, sim, spow per bin) on the host; the
     // passes the bins are dealt to (specPasses_: a slice of the bins, the register block that takes it, where its table slice
     // starts in specTab_); 3 n planes of histPlane_ floats -- re, im, level of bin j at planes 3 j .. 3 j + 2 -- allocated by the
