@@ -688,6 +688,68 @@ PVA_EXPORT int PvAmdGetLateralFraction(PvAmdSolver* s, float ex, float ey, float
  * the restatement the tests hold the kernel to */
 PVA_EXPORT int PvAmdHostLateralFraction(const float* p, const float* vx, const float* vy, int T, int fs, int onset,
                                         PvAmdLateralFraction* out);
+/* ---- Band metrics: decay times and clarity of every reached cell per octave or third-octave band ----
+ * The records above are broadband: the decay of a cell is that of whichever part of the pulse's band decays slowest there.
+ * PvAmdComputeBandMetrics filters each reached cell's recorded pressure into the bands set by PvAmdSetBands and reduces every
+ * band's output to one record of twelve floats on the device (pv_bands.hip).  It touches no run and no result map.
+ * Bands: n centres fc (Hz), 0 <= n <= PVA_BANDS_MAX, and fraction 1 (octave) or 3 (third octave); in double
+ *   f1 = fc * 2^(-1 / (2 fraction)),  f2 = fc * 2^(+1 / (2 fraction));  refused unless fc is finite, f1 > 0 and f2 < fs / 2
+ * Filter: a 4th-order Butterworth band-pass, designed on the host in double (host libm):
+ *   the order-2 low-pass prototype (poles exp(+-i 3 pi / 4));  W1 = tan(pi f1 / fs), W2 = tan(pi f2 / fs)  (pre-warped edges)
+ *   LP -> BP:  s -> (s^2 + W1 W2) / ((W2 - W1) s)   -- two conjugate pole pairs;  bilinear:  z = (1 + s) / (1 - s)
+ *   two biquads, one per pole pair, the one whose pole angle |arg z| is smaller FIRST;  per section
+ *      a1 = -2 Re z,  a2 = |z|^2,  zeros at z = +1 and z = -1:  b0 = g, b1 = 0, b2 = -g
+ *      g  = unit gain at the pre-warped geometric centre  w0 = 2 atan(sqrt(W1 W2))  (|H(exp(i w0))| = 1 for the section)
+ *   each coefficient rounded to float32 ONCE: b0, b1, b2, a1, a2 of section 1, then of section 2 -- 10 floats per band.
+ *   The whole band-pass has 0 dB at w0 and -3.01 dB at f1 and f2.  PvAmdGetBandCoefs returns exactly what the device uses.
+ * Filtering runs BACKWARDS in time (the time-reversed filtering of Jacobsen & Rindel: the filter's own ringing, which would
+ * otherwise mask decays shorter than its impulse response, falls before the onset), the direction the Schroeder integral walks.
+ * For result cell s = X * gy + Y, with x(t) = p(t) exactly what PvAmdCopyHistoryPlane(t) returns there, t0 = (int)delay[s]:
+ *   per section, transposed direct form II, float32, state z1 = z2 = +0.0f at t = T - 1, t = T-1 down to t0:
+ *      y  = (b0 * x) + z1
+ *      z1 = ((b1 * x) - (a1 * y)) + z2
+ *      z2 = (b2 * x) - (a2 * y)
+ *   section 2 takes section 1's y as its x;  y(t) = section 2's y.  Every product and sum is rounded on its own (no FMA),
+ *   denormals are kept.  The walk STOPS at t0: what the reversed filter would ring out below the onset is not in the record.
+ * Record per band (12 floats): edt, t20, t30, n_edt, n_t20, n_t30, e0, depth, c50, c80, d50, ts
+ *   the first eight: PvAmdDecayTimes above, word for word, with  e(t) = y(t) * y(t)  in place of p(t) * p(t)
+ *   the last four, with E the same backward curve, k = t - t0, n50 = (int)(0.05f * (float)fs), n80 = (int)(0.08f * (float)fs):
+ *      l50    = E(min(t0 + n50, T))   (a value of the curve itself; +0.0f where t0 + n50 >= T)      l80 likewise
+ *      e50    = sum of e(t) over k < n50,  from +0.0f, sequential in DECREASING t                    e80 likewise
+ *      moment = sum of ((float)k * e(t)) over all k, likewise
+ *      c50 = 10.0f * log10f(e50 / l50),  c80 likewise,  d50 = e50 / (e50 + l50),  ts = (moment / e0) / (float)fs
+ *   Nothing is special-cased: a band without energy gives e0 = 0 and what IEEE then gives (NaN ratios).
+ * A cell WITHOUT an onset in that run holds 12 n quiet NaNs; nothing is carried over from earlier runs.
+ * Device storage: 12 n x 4 bytes per cell of the history window, allocated by the first PvAmdComputeBandMetrics (again when n
+ * changes), freed by PvAmdSetBands(n = 0) and with the solver.  Lifetime and refusals are the decay times' ("band metrics: ...");
+ * besides, computing or reading with no bands set is refused ("no bands set"), and PvAmdSetBands invalidates the records.  Room
+ * metrics, spectrum, decay times, lateral fraction and band metrics do not invalidate each other. */
+#define PVA_BANDS_MAX 8
+typedef struct PvAmdBandMetrics {
+    float edt, t20, t30, n_edt, n_t20, n_t30, e0, depth, c50, c80, d50, ts;
+} PvAmdBandMetrics;
+/* Set (n > 0) or clear (n = 0: the device storage is freed) the bands; waits for a run in flight.  -1 and nothing changed:
+ * centreHz = NULL with n > 0, n outside 0 .. PVA_BANDS_MAX, fraction other than 1 or 3, a centre that is not finite, f1 <= 0 or
+ * f2 >= fs / 2 */
+PVA_EXPORT int PvAmdSetBands(PvAmdSolver* s, const float* centreHz, int n, int fraction);
+/* the number of bands set; the first min(n, cap) centres to centreHz and the fraction to *fraction (both optional) */
+PVA_EXPORT int PvAmdGetBands(PvAmdSolver* s, float* centreHz, int cap, int* fraction);
+/* the 10 n float32 coefficients the device uses */
+PVA_EXPORT int PvAmdGetBandCoefs(PvAmdSolver* s, float* out10n);
+/* Compute the band records of the LAST COMPLETED run of s (waits for a run in flight; works after every form of run, as
+ * PvAmdComputeDecayTimes).  Synchronous on the solver's own stream.  *ms (optional): device time of the pass. */
+PVA_EXPORT int PvAmdComputeBandMetrics(PvAmdSolver* s, float* ms);
+/* gx*gy*n*12 floats: cell s = X*gy + Y, then band, then the 12 floats */
+PVA_EXPORT int PvAmdCopyBandMetrics(PvAmdSolver* s, float* out12n);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc x n records, row-major */
+PVA_EXPORT int PvAmdCopyBandMetricsBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out12n);
+/* the n records at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map gives NaNs and 0 */
+PVA_EXPORT int PvAmdGetBandMetrics(PvAmdSolver* s, float ex, float ey, float ez, PvAmdBandMetrics* out12n);
+/* CPU only: the coefficients of the design above for a sampling rate fs, without a solver (the same refusals) */
+PVA_EXPORT int PvAmdHostBandCoefs(int fs, const float* centreHz, int n, int fraction, float* out10n);
+/* CPU only: filter and record above applied to one impulse response p[T] with 0 <= onset < T and n (1 .. PVA_BANDS_MAX)
+ * coefficient sets of 10 floats; the restatement the tests hold the kernel to */
+PVA_EXPORT int PvAmdHostBandMetrics(const float* p, int T, int fs, int onset, const float* coefs10n, int n, PvAmdBandMetrics* out12n);
 /* ---- Spectrum: the transfer function from the listener to every reached cell, at chosen frequencies ----
  * How loud the room is at ONE frequency at one position (room modes and their nodal lines, comb filtering behind an obstacle,
  * per-band gains): PvAmdComputeSpectrum reduces the history of the LAST COMPLETED run to three floats per bin and cell in one

@@ -40,6 +40,10 @@ def main(argv=None):
                     help="add the early lateral energy fraction, the early-sound direction and their sums of each emitter's cell")
     ap.add_argument("--spectrum", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the transfer function (re, im, level in dB re the source) of each emitter's cell at these frequencies")
+    ap.add_argument("--bands", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
+                    help="add the band metrics (decay times and clarity of the band-filtered response) of each emitter's cell for "
+                         "the bands centred at these frequencies")
+    ap.add_argument("--band-fraction", type=int, default=1, choices=(1, 3), help="octave (1, default) or third-octave (3) bands")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
@@ -66,6 +70,9 @@ def main(argv=None):
             s.compute_decay_times()
         if a.lateral_fraction:
             s.compute_lateral_fraction()
+        if a.bands:
+            s.set_bands(a.bands, a.band_fraction)
+            s.compute_band_metrics()
         if a.spectrum:
             s.set_spectrum_bins(a.spectrum)
             s.compute_spectrum()
@@ -85,6 +92,11 @@ def main(argv=None):
             if a.lateral_fraction:
                 m = s.lateral_fraction_at(e)
                 out["emitters"][-1]["lateralFraction"] = dict((n, float(v)) for n, v in zip(api.LATERAL_FRACTION_NAMES, m))
+            if a.bands:
+                m = s.band_metrics_at(e)
+                out["emitters"][-1]["bandMetrics"] = [
+                    dict([("hz", float(hz)), ("fraction", a.band_fraction)] + [(n, float(v)) for n, v in zip(api.BAND_METRIC_NAMES, r)])
+                    for hz, r in zip(a.bands, m)]
             if a.spectrum:
                 m = s.spectrum_at(e)
                 out["emitters"][-1]["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],

@@ -271,6 +271,15 @@ SYMBOLS = {
     "PvAmdCopyLateralFractionBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "PvAmdGetLateralFraction": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdLateralFraction)]),
     "PvAmdHostLateralFraction": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdLateralFraction)]),
+    "PvAmdSetBands": (C.c_int, [_vp, _fp, C.c_int, C.c_int]),
+    "PvAmdGetBands": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(C.c_int)]),
+    "PvAmdGetBandCoefs": (C.c_int, [_vp, _fp]),
+    "PvAmdComputeBandMetrics": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyBandMetrics": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyBandMetricsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetBandMetrics": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
+    "PvAmdHostBandCoefs": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, _fp]),
+    "PvAmdHostBandMetrics": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
     "PvAmdSetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetSpectrumSource": (C.c_int, [_vp, _fp]),
@@ -718,6 +727,31 @@ def host_lateral_fraction(p, vx, vy, fs, onset):
     ptr = [_f(v) if v.size else None for v in (a, x, y)]
     _check(lib().PvAmdHostLateralFraction(ptr[0], ptr[1], ptr[2], int(a.size), int(fs), int(onset), out))
     return out.as_array()
+
+
+BANDS_MAX = 8  # PVA_BANDS_MAX
+BAND_METRIC_NAMES = ("edt", "t20", "t30", "n_edt", "n_t20", "n_t30", "e0", "depth", "c50", "c80", "d50", "ts")
+
+
+def host_band_coefs(fs, hz, fraction=1):
+    """PvAmdHostBandCoefs: float32 [n, 10] (b0, b1, b2, a1, a2 of section 1, then of section 2) of the octave (fraction 1) or
+    third-octave (fraction 3) Butterworth band-passes centred at hz for the sampling rate fs -- the design of
+    include/planeverb_amd.h (PvAmdBandMetrics), in double on the CPU, rounded to float32 once"""
+    h = np.ascontiguousarray(hz, np.float32).reshape(-1)
+    out = np.empty((h.size, 10), np.float32)
+    _check(lib().PvAmdHostBandCoefs(int(fs), _f(h) if h.size else None, int(h.size), int(fraction), _f(out)))
+    return out
+
+
+def host_band_metrics(p, fs, onset, coefs):
+    """PvAmdHostBandMetrics: float32 [n, 12] (BAND_METRIC_NAMES) of one impulse response p[T] with its onset step, filtered
+    backwards in time through the n coefficient sets coefs[n, 10] -- the definition of include/planeverb_amd.h on the CPU"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    c = np.ascontiguousarray(coefs, np.float32).reshape(-1, 10)
+    out = np.empty((c.shape[0], 12), np.float32)
+    _check(lib().PvAmdHostBandMetrics(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(c) if c.size else None,
+                                      int(c.shape[0]), _f(out)))
+    return out
 
 
 SPECTRUM_MAX_BINS = 32  # PVA_SPECTRUM_MAX_BINS
@@ -1433,6 +1467,52 @@ class Solver:
         out = PvAmdLateralFraction()
         _check(lib().PvAmdGetLateralFraction(self._h, *[float(v) for v in pos], out))
         return out.as_array()
+
+    def set_bands(self, hz, fraction=1):
+        """the band centres (Hz, at most BANDS_MAX) compute_band_metrics filters into, octaves (fraction 1) or third octaves
+        (fraction 3), each with its upper edge below fs / 2; an empty list clears them and frees the device storage"""
+        h = np.ascontiguousarray(hz, np.float32).reshape(-1)
+        _check(lib().PvAmdSetBands(self._h, _f(h) if h.size else None, int(h.size), int(fraction)))
+
+    def bands(self):
+        """(float32 [n], fraction): the band centres as set"""
+        out = np.empty(BANDS_MAX, np.float32)
+        fr = C.c_int(1)
+        n = lib().PvAmdGetBands(self._h, _f(out), BANDS_MAX, C.byref(fr))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return out[:n].copy(), fr.value
+
+    def band_coefs(self):
+        """float32 [n, 10]: the filter coefficients the device uses (host_band_coefs of the solver's fs)"""
+        out = np.empty((len(self.bands()[0]), 10), np.float32)
+        _check(lib().PvAmdGetBandCoefs(self._h, _f(out)))
+        return out
+
+    def compute_band_metrics(self):
+        """decay times and clarity per band (BAND_METRIC_NAMES) of the last completed run at the bands of set_bands, on the
+        device; returns the device time of the passes in milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeBandMetrics(self._h, C.byref(ms)))
+        return ms.value
+
+    def band_metrics(self):
+        """float32 [gx, gy, n, 12] (BAND_METRIC_NAMES); NaN where the cell has no onset in the run they were computed for"""
+        out = np.empty((self.gx, self.gy, len(self.bands()[0]), 12), np.float32)
+        _check(lib().PvAmdCopyBandMetrics(self._h, _f(out)))
+        return out
+
+    def band_metrics_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, n, 12] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, len(self.bands()[0]), 12), np.float32)
+        _check(lib().PvAmdCopyBandMetricsBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def band_metrics_at(self, pos):
+        """float32 [n, 12] at an emitter position (the cell get_output reads); NaNs off the map"""
+        out = np.empty((len(self.bands()[0]), 12), np.float32)
+        _check(lib().PvAmdGetBandMetrics(self._h, *[float(v) for v in pos], _f(out)))
+        return out
 
     def set_spectrum_bins(self, hz):
         """the frequencies (Hz, at most SPECTRUM_MAX_BINS, each in [0, fs / 2]) compute_spectrum evaluates; an empty list clears

@@ -11,6 +11,7 @@
 #include "../../include/planeverb_amd.h"
 #include "pv_context.h"
 #include "pv_core.h"
+#include "pv_bands.h"
 #include "pv_decay.h"
 #include "pv_lateral.h"
 #include "pv_metrics.h"
@@ -1213,6 +1214,81 @@ int PvAmdGetLateralFraction(PvAmdSolver* h, float ex, float ey, float ez, PvAmdL
     return 0;
 } PV_API_CATCH(-1)
 
+// band metrics (pv_bands.hip): single whole-grid solvers only, as the decay times; every refusal says "band metrics: ...".  The
+// bands are checked against the handle's own grid before anything else happens (pv_bands.h bandsError, the rule
+// PvAmdHostBandCoefs applies too)
+static bool bandsHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "band metrics: " + g_lastError;
+    return false;
+}
+
+int PvAmdSetBands(PvAmdSolver* h, const float* centreHz, int n, int fraction) try {
+    if (!h) {
+        g_lastError = "band metrics: null solver handle";
+        return -1;
+    }
+    if (n != 0) {
+        if (const char* e = bandsError(centreHz, n, fraction, (int)h->spec.fs)) {
+            g_lastError = e;
+            return -1;
+        }
+    } else if (fraction != 1 && fraction != 3) {
+        g_lastError = "band metrics: fraction is 1 (octave) or 3 (third octave)";
+        return -1;
+    }
+    if (!bandsHandle(h)) return -1;
+    return ret(h, h->s->setBands(centreHz, n, fraction));
+} PV_API_CATCH(-1)
+
+int PvAmdGetBands(PvAmdSolver* h, float* centreHz, int cap, int* fraction) try {
+    if (!bandsHandle(h)) return -1;
+    return h->s->bands(centreHz, cap, fraction);
+} PV_API_CATCH(-1)
+
+int PvAmdGetBandCoefs(PvAmdSolver* h, float* out10n) try {
+    if (!bandsHandle(h)) return -1;
+    if (!out10n) {
+        g_lastError = "band metrics: PvAmdGetBandCoefs: null output";
+        return -1;
+    }
+    return ret(h, h->s->bandCoefs(out10n));
+} PV_API_CATCH(-1)
+
+int PvAmdComputeBandMetrics(PvAmdSolver* h, float* ms) try {
+    if (!bandsHandle(h)) return -1;
+    return ret(h, h->s->computeBandMetrics(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyBandMetrics(PvAmdSolver* h, float* out12n) try {
+    if (!bandsHandle(h)) return -1;
+    if (!out12n) {
+        g_lastError = "band metrics: PvAmdCopyBandMetrics: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyBandMetricsBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out12n));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyBandMetricsBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out12n) try {
+    if (!bandsHandle(h)) return -1;
+    if (!out12n) {
+        g_lastError = "band metrics: PvAmdCopyBandMetricsBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyBandMetricsBlock(r0, c0, nr, nc, out12n));
+} PV_API_CATCH(-1)
+
+int PvAmdGetBandMetrics(PvAmdSolver* h, float ex, float ey, float ez, PvAmdBandMetrics* out12n) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!bandsHandle(h)) return -1;
+    if (!out12n) {
+        g_lastError = "band metrics: PvAmdGetBandMetrics: null output";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdBandMetrics) == kBandFloats * sizeof(float), "twelve floats");
+    return ret(h, h->s->bandMetricsAt(ex, ez, reinterpret_cast<float*>(out12n)));
+} PV_API_CATCH(-1)
+
 // spectrum (pv_spectrum.hip): single whole-grid solvers only, as the room metrics.  The bins are checked against the handle's
 // own grid before anything else happens (pv_spectrum.h spectrumBinsError, the rule the host calls apply too)
 int PvAmdSetSpectrumBins(PvAmdSolver* h, const float* hz, int n) try {
@@ -1605,6 +1681,31 @@ int PvAmdHostLateralFraction(const float* p, const float* vx, const float* vy, i
     float v[kLateralFloats];
     lateralFractionOfIr(p, vx, vy, T, fs, onset, v);
     std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostBandCoefs(int fs, const float* centreHz, int n, int fraction, float* out10n) try {
+    if (const char* e = bandsError(centreHz, n, fraction, fs)) {
+        g_lastError = e;
+        return -1;
+    }
+    if (!out10n) {
+        g_lastError = "band metrics: PvAmdHostBandCoefs: null output";
+        return -1;
+    }
+    bandCoefs(fs, centreHz, n, fraction, out10n);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostBandMetrics(const float* p, int T, int fs, int onset, const float* coefs10n, int n, PvAmdBandMetrics* out12n) try {
+    if (!p || !coefs10n || !out12n || T <= 0 || fs <= 0 || onset < 0 || onset >= T || n < 1 || n > kBandsMax) {
+        g_lastError =
+            "band metrics: PvAmdHostBandMetrics: an impulse response p[T], T > 0, fs > 0, 0 <= onset < T, 1 .. 8 coefficient sets and an "
+            "output of n records";
+        return -1;
+    }
+    for (int j = 0; j < n; ++j)
+        bandMetricsOfIr(p, T, fs, onset, coefs10n + (size_t)kBandCoefs * j, reinterpret_cast<float*>(out12n) + (size_t)kBandFloats * j);
     return 0;
 } PV_API_CATCH(-1)
 

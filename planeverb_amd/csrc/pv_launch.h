@@ -141,6 +141,14 @@ void launchDecayTimes(const AnalyzeArgs& a, float* out, bool twoLaunches, hipStr
 // does not read a slab's histAbove)
 void launchLateralFraction(const AnalyzeArgs& a, float* out, hipStream_t stream);
 
+// ---- pv_bands.hip: per-cell, per-band decay times and clarity
+// band records of the last completed run (pv_bands.hip) for n bands: coefs = n x kBandCoefs floats on the HOST (they travel as
+// kernel arguments), out = n x kBandFloats planes of a.histPlane floats (band j, float k at plane j * kBandFloats + k), indexed by
+// the cell's offset inside a history plane; NaN where the cell has no onset in that run.  One launch per block of
+// bandMetricsBlock() bands
+void launchBandMetrics(const AnalyzeArgs& a, const float* coefs, int n, float* out, hipStream_t stream);
+int bandMetricsBlock();
+
 // ---- pv_spectrum.hip: per-cell transfer functions at chosen frequencies
 // One pass over the history of the last completed run for `bins` bins held `block` to a lane (spectrumBlockOk(block); bins <=
 // block).  tab: the pass's twiddles on the device, row t = {cos, sin} pairs of its `block` bins (2 * block floats, bins past

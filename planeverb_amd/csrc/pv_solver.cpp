@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "pv_launch.h"
+#include "pv_bands.h"
 #include "pv_decay.h"
 #include "pv_lateral.h"
 #include "pv_metrics.h"
@@ -676,6 +677,9 @@ Solver::~Solver() {
     if (decay_) hipFree(decay_);
     for (auto& e : decayEv_)
         if (e) hipEventDestroy(e);
+    if (bands_) hipFree(bands_);
+    for (auto& e : bandsEv_)
+        if (e) hipEventDestroy(e);
     if (lateral_) hipFree(lateral_);
     for (auto& e : lateralEv_)
         if (e) hipEventDestroy(e);
@@ -760,7 +764,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     return id;
 }
 
@@ -771,7 +775,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     return true;
 }
 
@@ -782,7 +786,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     return true;
 }
 
@@ -854,14 +858,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -1008,7 +1012,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     return true;
 }
 
@@ -1048,7 +1052,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     return true;
 }
 
@@ -2095,7 +2099,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;       // (the history the records were made from is about to be overwritten)
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     if (!applyGeometry()) return false;
     PathRun r;
@@ -3114,6 +3118,125 @@ bool Solver::lateralFractionAt(float ex, float ez, float out11[11]) {
         return true;
     }
     return copyLateralFractionBlock(cx, cy, 1, 1, out11);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// band metrics (pv_bands.hip): everything as the decay times above, with 12 planes per band and the bands as the spectrum's bins
+// ----------------------------------------------------------------------------------------------------------------
+
+bool Solver::setBands(const float* centreHz, int n, int fraction) {
+    if (isSlab()) return fail("band metrics: not available on a slab");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    bandsValid_ = false;
+    bandsHostValid_ = false;
+    bandHz_.clear();
+    bandCoefs_.clear();
+    if (n == 0) {
+        if (bands_) hipFree(bands_);
+        bands_ = nullptr;
+        bandsPlanes_ = 0;
+        return true;
+    }
+    bandHz_.assign(centreHz, centreHz + n);
+    bandFraction_ = fraction;
+    bandCoefs_.resize((size_t)kBandCoefs * n);
+    pva::bandCoefs((int)g_.fs, centreHz, n, fraction, bandCoefs_.data());
+    return true;
+}
+
+int Solver::bands(float* centreHz, int cap, int* fraction) const {
+    const int n = (int)bandHz_.size();
+    for (int j = 0; j < n && j < cap && centreHz; ++j) centreHz[j] = bandHz_[(size_t)j];
+    if (fraction && n) *fraction = bandFraction_;
+    return n;
+}
+
+bool Solver::bandCoefs(float* out10n) {
+    if (bandHz_.empty()) return fail("band metrics: no bands set (PvAmdSetBands)");
+    std::memcpy(out10n, bandCoefs_.data(), bandCoefs_.size() * 4);
+    return true;
+}
+
+bool Solver::computeBandMetrics(float* ms) {
+    if (isSlab()) return fail("band metrics: not available on a slab");
+    if (opt_.streaming) return fail("band metrics: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("band metrics: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    if (bandHz_.empty()) return fail("band metrics: no bands set (PvAmdSetBands)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("band metrics: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("band metrics: the last run ended in error");
+    const int n = (int)bandHz_.size();
+    if (bands_ && bandsPlanes_ != kBandFloats * n) {
+        hipFree(bands_);
+        bands_ = nullptr;
+    }
+    if (!bands_) {
+        if (!dalloc(&bands_, (size_t)kBandFloats * n * (size_t)histPlane_, false)) return false;
+        bandsPlanes_ = kBandFloats * n;
+    }
+    for (auto& e : bandsEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    bandsValid_ = false;
+    bandsHostValid_ = false;
+    hipEventRecord(bandsEv_[0], stream_);
+    launchBandMetrics(analyzeArgs(lastLx_, lastLz_), bandCoefs_.data(), n, bands_, stream_);
+    hipEventRecord(bandsEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "band metrics launch") || !hipOk(hipStreamSynchronize(stream_), "band metrics sync")) return false;
+    if (ms) hipEventElapsedTime(ms, bandsEv_[0], bandsEv_[1]);
+    bandsDyn_ = dynCur_;
+    bandsValid_ = true;
+    return true;
+}
+
+bool Solver::fetchBandMetrics() {
+    if (bandHz_.empty()) return fail("band metrics: no bands set (PvAmdSetBands)");
+    if (!bandsValid_)
+        return fail("band metrics: not computed for the last run, the current geometry and the current bands (PvAmdComputeBandMetrics)");
+    if (bandsHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    bandsHost_.resize((size_t)bandsPlanes_ * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(bandsHost_.data(), bands_, bandsHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "band metrics copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "band metrics sync"))
+        return false;
+    bandsHostValid_ = true;
+    return true;
+}
+
+bool Solver::copyBandMetricsBlock(int r0, int c0, int nr, int nc, float* out) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("band metrics: block outside the map");
+    if (!fetchBandMetrics()) return false;
+    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
+    const int wr0 = bandsDyn_.histRow0 - geo_.G, wc0 = bandsDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const int nf = bandsPlanes_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < nf; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * bandsDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < nf; ++k) o[k] = bandsHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::bandMetricsAt(float ex, float ez, float* out12n) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!fetchBandMetrics()) return false;
+        for (int k = 0; k < bandsPlanes_; ++k) out12n[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copyBandMetricsBlock(cx, cy, 1, 1, out12n);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

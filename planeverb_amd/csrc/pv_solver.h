@@ -158,11 +158,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -265,6 +265,16 @@ public:
     bool computeLateralFraction(float* ms);
     bool copyLateralFractionBlock(int r0, int c0, int nr, int nc, float* out11);
     bool lateralFractionAt(float ex, float ez, float out11[11]);
+    // Band metrics (pv_bands.hip; include/planeverb_amd.h PvAmdBandMetrics): decay times and clarity of the last completed run per
+    // octave or third-octave band set here; lifetime and refusals as the decay times', and a change of bands invalidates the
+    // records.  setBands: the caller has validated the centres (pv_bands.h bandsError); n = 0 clears and frees; waits for a run
+    // in flight.  out: nr x nc x n records of twelve floats, NaN where the cell has no onset in that run
+    bool setBands(const float* centreHz, int n, int fraction);
+    int bands(float* centreHz, int cap, int* fraction) const;
+    bool bandCoefs(float* out10n);
+    bool computeBandMetrics(float* ms);
+    bool copyBandMetricsBlock(int r0, int c0, int nr, int nc, float* out);
+    bool bandMetricsAt(float ex, float ez, float* out12n);
     // Spectrum (pv_spectrum.hip; include/planeverb_amd.h Spectrum): transfer functions of the last completed run at the bins set
     // here, lifetime and refusals as the room metrics'.  setSpectrumBins: the caller has validated hz (pv_spectrum.h
     // spectrumBinsError); n = 0 clears and frees; waits for a run in flight.  out: nr x nc x n records of three floats
@@ -502,6 +512,20 @@ private:
     bool lateralHostValid_ = false;
     hipEvent_t lateralEv_[2] = {nullptr, nullptr};
     bool fetchLateralFraction();
+    // band metrics (pv_bands.h): the centres, their fraction and the 10 float32 coefficients per band on the host (the kernel takes
+    // them as arguments); 12 n planes of histPlane_ floats -- band j at planes 12 j .. 12 j + 11 -- allocated by the first
+    // computeBandMetrics and again when n changes.  bandsValid_ follows metricsValid_ and is also cleared by a change of bands; no
+    // computation touches another's flag
+    std::vector<float> bandHz_, bandCoefs_;
+    int bandFraction_ = 1;
+    float* bands_ = nullptr;
+    int bandsPlanes_ = 0;  // 12 n of the allocation
+    bool bandsValid_ = false;
+    DynParams bandsDyn_{};
+    std::vector<float> bandsHost_;
+    bool bandsHostValid_ = false;
+    hipEvent_t bandsEv_[2] = {nullptr, nullptr};
+    bool fetchBandMetrics();
     // spectrum (pv_spectrum.h): the bins, their tables c / s [T * n] and source values (sre, sim, spow per bin) on the host; the
     // passes the bins are dealt to (specPasses_: a slice of the bins, the register block that takes it, where its table slice
     // starts in specTab_); 3 n planes of histPlane_ floats -- re, im, level of bin j at planes 3 j .. 3 j + 2 -- allocated by the
