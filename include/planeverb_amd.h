@@ -448,6 +448,13 @@ PVA_EXPORT int PvAmdHostEdgeLayerTablesR0(float gridSizeX, float gridSizeY, int 
  * visited, or -1 for bad arguments. */
 PVA_EXPORT int PvAmdHostEnclosure(const uint8_t* beta, int nx, int ny, int seedX, int seedY, int tileRows, int tileCols, int maxTiles,
                                   int* out10);
+/* CPU only: what a reach-bounded (windowRun = 0) or resident-window (1) run clears in front of its first launch.  win4 = the run's
+ * tile window, prevRect4 = the rectangle the previous such run wrote, both {first tile row, tile rows, first tile column, tile
+ * columns}; planesDirty / sweptDirty: the planes were written by something else since; splitPlanes: an edge layer's split planes
+ * are in use.  Returns 0: nothing (a window run over the very window of the previous run), 1: prevRect4 in every plane, 2: every
+ * plane, whole; -1 for bad arguments. */
+PVA_EXPORT int PvAmdHostWindowClear(int windowRun, const int* win4, const int* prevRect4, int planesDirty, int sweptDirty,
+                                    int splitPlanes);
 /* CPU only: the four vertices out8 the library uses for that oriented box (0, or -1 for a refused input) */
 PVA_EXPORT int PvAmdHostOrientedBoxVertices(float px, float py, float w, float h, float ax, float ay, float* out8);
 /* CPU only: the shape the library makes of a vertex list (counter-clockwise, out16 gets 2n floats); returns n, or -1 for a
@@ -499,6 +506,10 @@ PVA_EXPORT int PvAmdGetTimings(PvAmdSolver* s, PvAmdTimings* out);
 /* 1: the last run (PvAmdRun / PvAmdRunAsync + PvAmdSync) went out as one resident-kernel launch over the tile window around the
  * listener's walled-in air component (PVA_OPT_RESIDENT_WINDOW), 0: by any other path, -1: error.  Results do not depend on it. */
 PVA_EXPORT int PvAmdLastRunResidentWindow(PvAmdSolver* s);
+/* 1: the last run was one resident-kernel launch -- over the whole grid or over a window -- whose workgroups handed their tiles over
+ * through ONE XCD's L2 (launches of up to 32 workgroups, PLANEVERB_AMD_RESIDENT_XCD), 0: the placement-independent hand-off or
+ * another path, -1: error.  Results do not depend on it. */
+PVA_EXPORT int PvAmdLastRunOneXcd(PvAmdSolver* s);
 
 /* Streaming-analysis (sparse-emitter) mode only -- SURVEY.md 8f N3.  Registers the emitter positions (n x {x,y,z})
  * whose wet gain and RT60 the next runs compute; onset, occlusion, lowpass, source directivity and listener direction

@@ -244,6 +244,8 @@ SYMBOLS = {
     "PvAmdRunBatch": (C.c_int, [C.POINTER(_vp), C.c_int, _fp, C.c_int]),
     "PvAmdGetTimings": (C.c_int, [_vp, C.POINTER(PvAmdTimings)]),
     "PvAmdLastRunResidentWindow": (C.c_int, [_vp]),
+    "PvAmdLastRunOneXcd": (C.c_int, [_vp]),
+    "PvAmdHostWindowClear": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int]),
     "PvAmdClockProbe": (C.c_float, [C.c_int, _fp]),
     "PvAmdBandwidthProbe": (C.c_int, [C.c_int, _fp]),
     "PvAmdSetEmitters": (C.c_int, [_vp, _fp, C.c_int]),
@@ -680,6 +682,16 @@ def host_enclosure(beta, seed, tile_rows=36, tile_cols=40, max_tiles=128):
         raise PlaneverbError(last_error())
     v = [int(x) for x in out]
     return dict(found=v[0], cells=v[1], box=tuple(v[2:6]), window=tuple(v[6:10]))
+
+
+def host_window_clear(window_run, win, prev_rect, planes_dirty, swept_dirty, split_planes):
+    """PvAmdHostWindowClear: what a run clears in front of its first launch -- 0 nothing, 1 the previous run's tile rectangle, 2 all
+    planes; win, prev_rect = (first tile row, tile rows, first tile column, tile columns)"""
+    w, p = ((C.c_int * 4)(*[int(v) for v in r]) for r in (win, prev_rect))
+    rc = lib().PvAmdHostWindowClear(int(bool(window_run)), w, p, int(bool(planes_dirty)), int(bool(swept_dirty)), int(bool(split_planes)))
+    if rc < 0:
+        raise PlaneverbError(last_error())
+    return rc
 
 
 def load_pv(path, max_boxes=4096):
@@ -1309,6 +1321,13 @@ class Solver:
     def last_run_resident_window(self):
         """True when the last run went out as one resident-kernel launch over the window around the listener's room"""
         rc = lib().PvAmdLastRunResidentWindow(self._h)
+        if rc < 0:
+            raise PlaneverbError(last_error())
+        return rc == 1
+
+    def last_run_one_xcd(self):
+        """True when the last run's resident-kernel launch handed its tiles over through one XCD's L2"""
+        rc = lib().PvAmdLastRunOneXcd(self._h)
         if rc < 0:
             raise PlaneverbError(last_error())
         return rc == 1

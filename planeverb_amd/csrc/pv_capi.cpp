@@ -1017,6 +1017,11 @@ int PvAmdLastRunResidentWindow(PvAmdSolver* h) try {
     return h->s->lastRunResidentWindow() ? 1 : 0;
 } PV_API_CATCH(-1)
 
+int PvAmdLastRunOneXcd(PvAmdSolver* h) try {
+    if (!wholeGrid(h) || !ensure(h, true)) return -1;
+    return h->s->lastRunOneXcd() ? 1 : 0;
+} PV_API_CATCH(-1)
+
 int PvAmdSetEmitters(PvAmdSolver* h, const float* xyz, int n) try {
     if (!wholeGrid(h) || !ensure(h) || (n > 0 && !xyz)) return -1;
     return ret(h, h->s->setEmitters(xyz, n));
@@ -1623,6 +1628,14 @@ int PvAmdHostEnclosure(const uint8_t* beta, int nx, int ny, int seedX, int seedY
     const int v[10] = {e.found, e.cells, e.r0, e.c0, e.r1, e.c1, e.ti0, e.tj0, e.tis, e.tjs};
     std::copy(v, v + 10, out10);
     return e.cells;
+} PV_API_CATCH(-1)
+
+int PvAmdHostWindowClear(int windowRun, const int* win4, const int* prevRect4, int planesDirty, int sweptDirty, int splitPlanes) try {
+    if (!win4 || !prevRect4) {
+        g_lastError = "PvAmdHostWindowClear: bad arguments";
+        return -1;
+    }
+    return (int)planClear(windowRun != 0, win4, prevRect4, planesDirty != 0, sweptDirty != 0, splitPlanes != 0);
 } PV_API_CATCH(-1)
 
 int PvAmdHostLoadPv(const char* path, float* b5, int maxBoxes) try {

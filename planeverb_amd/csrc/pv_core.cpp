@@ -643,6 +643,12 @@ Enclosure findEnclosure(const uint8_t* beta, int NX, int NY, int seedX, int seed
     return e;
 }
 
+PlaneClear planClear(bool windowRun, const int win[4], const int prevRect[4], bool planesDirty, bool sweptDirty, bool splitPlanes) {
+    if (planesDirty || sweptDirty) return PlaneClear::All;
+    const bool same = win[1] > 0 && win[3] > 0 && std::equal(win, win + 4, prevRect);
+    return (windowRun && same && !splitPlanes) ? PlaneClear::None : PlaneClear::Rect;
+}
+
 // ----------------------------------------------------------------------------------------------------------------
 // which path a run takes (pv_core.h)
 // ----------------------------------------------------------------------------------------------------------------

@@ -190,6 +190,19 @@ struct Enclosure {
 Enclosure findEnclosure(const uint8_t* beta, int NX, int NY, int seedX, int seedY, int rxi, int wi, int maxTiles,
                         std::vector<int>* visited);
 
+// What a reach-eligible run (RunPlan::reach: the reach-bounded launches or a resident-window run) clears in front of its first
+// launch (Solver::clearReachPlanes).  Such a run writes only inside its tile rectangle, so both buffer sets must hold zeros
+// everywhere else; prevRect = {first tile row, tile rows, first tile column, tile columns} is the only place the previous such run
+// left values, and the flags say that something else wrote the planes since (planesDirty: a geometry change, setFields, raw stepping;
+// sweptDirty: a run of a sweeping path).  A WINDOW run over the very rectangle of the previous run needs no clear at all: the
+// resident kernel starts from zero registers, loads nothing in its first epoch, and every later epoch reads only what the epoch
+// before published -- the blocks' interiors tile the window exactly, so a stale value inside it is overwritten before anything
+// reads it, in either buffer set and for every step count (pv_resident.hip).  The reach-bounded launches load their tiles from the
+// first launch on, and the split planes (an edge layer's, splitPlanes) are not the resident kernel's to overwrite.
+//   None: no launch.  Rect: prevRect, in all planes (an empty one: nothing to clear).  All: every plane, whole.
+enum class PlaneClear { None = 0, Rect = 1, All = 2 };
+PlaneClear planClear(bool windowRun, const int win[4], const int prevRect[4], bool planesDirty, bool sweptDirty, bool splitPlanes);
+
 // ----------------------------------------------------------------------------------------------------------------
 // Which path a run takes ("Which path a run takes").  Solver::init resolves a PathCaps once, every run head
 // (Solver::beginRun) states a PathRun, and planRun -- pure, no device -- answers with the RunPlan the solver keeps for the
@@ -250,7 +263,7 @@ struct RunPlan {
     bool reach = false;        // only the tiles the pulse can have reached (Window: the planes are cleared as for such a run)
     bool layer = false;        // the layer launch behind every merged launch
     PathRun::Kind kind = PathRun::Run;
-    bool oneXcd = false;       // Resident: the one-XCD hand-off (set by the solver: it needs the XCD's budget)
+    bool oneXcd = false;       // Resident, Window: the one-XCD hand-off (set by the solver: it needs the XCD's budget)
 };
 
 // "the plain merged path": what the patch kernel, row bands and the reach bound require

@@ -570,7 +570,7 @@ bool Solver::init(const GridSpec& spec, int device, const SolverOptions& opt) {
             if (residentBudget_ < 3) windowOk = false;
         }
         if (resFlagWords_ > 0 && !dalloc(&resFlags_, (size_t)resFlagWords_, true)) return false;
-        if (useResident) {
+        if (useResident || windowOk) {  // (one turn counter: two solvers in flight sit on different XCDs, whatever their kind)
             static std::atomic<int> turn{0};
             xcdTarget_ = turn.fetch_add(1) & 7;
             // (validation: an XCD that does not exist -- the first run is then given up by the claim check and repeated)
@@ -627,6 +627,29 @@ bool Solver::init(const GridSpec& spec, int device, const SolverOptions& opt) {
         dynValid_ = false;
         tim_ = SolverTimings{};
         lastReached_ = -1;
+    }
+    // The same for the window runs of this solver, which take the one-XCD hand-off per run (enqueueRun): a throw-away, stencil-only
+    // launch over the ONE-tile window (0, 0) -- three blocks, whatever the geometry -- with the listener in its first cell.  A window
+    // run takes the mode only after this launch has passed its claim check (xcdWindowOk_); where the plan of that launch is not the
+    // window path (an option that keeps runs off it) the solver's window runs stay placement-independent.  reachRect_ is left naming
+    // that tile and the planes clean: the first real run clears the rectangle.
+    PathRun first;
+    first.listenerInside = true;
+    first.layerActive = layerActive();
+    first.layerTiles = numLayer_ > 0;
+    if (caps_.windowOk && xcdOk_ && !opt_.skipAnalysis && planRun(caps_, first).path == StepPath::Window) {
+        opt_.skipAnalysis = true;
+        probeWindow_ = true;
+        const bool ok = enqueueRun(0, 0, 0.f, 0.f) && sync();
+        probeWindow_ = false;
+        opt_.skipAnalysis = false;
+        if (!ok) return false;
+        xcdWindowOk_ = xcdOk_ && plan_.path == StepPath::Window && plan_.oneXcd;
+        dynValid_ = false;
+        tim_ = SolverTimings{};
+        lastReached_ = -1;
+        lastRun_ = LastRun::None;
+        plan_ = RunPlan{};
     }
     return true;
 }
@@ -1589,6 +1612,12 @@ static bool reserveBlocks(std::atomic<int>& inFlight, int blocks, int budget, in
 // win = {first tile row, tile rows, first tile column, tile columns} of the window.  The device's resident budget is reserved
 // here (residentHeld_): two solvers in flight both reserve, and a run that finds the budget used up goes out reach-bounded.
 bool Solver::windowFor(int lcx, int lcy, int win[4]) {
+    if (probeWindow_) {  // (init: tile (0, 0), inside every history window whose listener is cell (0, 0))
+        if (!reserveBlocks(residentInFlight(device_), 3, residentBudget_, &residentHeld_)) return false;
+        win[0] = win[2] = 0;
+        win[1] = win[3] = 1;
+        return true;
+    }
     const Enclosure* e = enclosureOf(lcx, lcy);
     if (!e || !e->found) return false;
     const DynParams& d = dynCur_;
@@ -1609,6 +1638,12 @@ bool Solver::windowFor(int lcx, int lcy, int win[4]) {
 // the same planes, history rows, tileFirst entries and -- through the unchanged analysis -- result maps as the T / K merged
 // launches, which would advance the window's tiles to the same values and everything else from zeros to zeros.
 void Solver::enqueueWindowRun(const int win[4]) {
+    // the hand-off through one XCD's L2 where the window's blocks fit one XCD, the device is known to spread a launch's workgroups
+    // over its XCDs (init found out) and this solver's XCD is not taken by another solver's run; else placement-independent
+    const int blocks = 3 * win[1] * win[3];
+    plan_.oneXcd = xcdOk_ && (xcdWindowOk_ || probeWindow_) && blocks <= kResidentXcdMaxTiles &&
+                   reserveBlocks(residentXcdInFlight(device_, xcdTarget_), blocks, kResidentXcdMaxTiles, &xcdHeld_);
+    runTiles_ = blocks;
     enqueueBeginRun(true);  // the run's parameters, tileFirst = INT_MAX for every tile, flag words and error flag at zero
     launchResidentRun(12, win);
     for (int i = 0; i < 4; ++i) reachRect_[i] = win[i];  // what the next reach-bounded or window run has to clear
@@ -1640,7 +1675,7 @@ ResidentArgs Solver::residentArgs(const int* win) const {
     ra.errFlag = errFlag_;
     ra.flags = resFlags_;
     ra.xcdMode = plan_.oneXcd ? 1 : 0;
-    ra.xcdTarget = win ? 0 : xcdTarget_;
+    ra.xcdTarget = xcdTarget_;
     ra.histPlane = histPlane_;
     ra.planeBytes = ((long long)geo_.rows * geo_.pitch - off) * 4;
     ra.pitch = geo_.pitch;
@@ -1663,12 +1698,17 @@ ResidentArgs Solver::residentArgs(const int* win) const {
     return ra;
 }
 
-// Before a reach-bounded run: zeros in both buffer sets wherever its launches do not write.  After a run of another path,
-// raw stepping, setFields or a geometry change, all six planes are cleared; after a reach-bounded run, the rectangle it wrote
-// (its last window's output rectangles and the guard cells around them).  Kernels, not hipMemsetAsync: see enqueueSteps.
-bool Solver::clearReachPlanes() {
+// Before a reach-bounded or resident-window run: zeros in both buffer sets wherever its launches do not write.  After a run of
+// another path, raw stepping, setFields or a geometry change, all six planes are cleared; after a reach-bounded or window run, the
+// rectangle it wrote (its last window's output rectangles and the guard cells around them) -- unless this run is a window run
+// (win = its window) over that very rectangle, which clears nothing (planClear, pv_core.h).  Kernels, not hipMemsetAsync: see
+// enqueueSteps.
+bool Solver::clearReachPlanes(const int* win) {
     float* planes[6] = {pr_[0], vx_[0], vy_[0], pr_[1], vx_[1], vy_[1]};
-    if (planesDirty_ || sweptDirty_) {
+    const int none[4] = {0, 0, 0, 0};
+    const PlaneClear what = planClear(win != nullptr, win ? win : none, reachRect_, planesDirty_, sweptDirty_, px_[0] != nullptr);
+    if (what == PlaneClear::None) return true;  // (reachRect_ stays: it is this run's window)
+    if (what == PlaneClear::All) {
         for (float* p : planes) launchZero(p, (long long)geo_.rows * geo_.pitch, stream_);
         for (float* p : px_)
             if (p) launchZero(p, (long long)geo_.rows * geo_.pitch, stream_);
@@ -2125,7 +2165,7 @@ bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, floa
     lastLx_ = lx;
     lastLz_ = lz;
     cur_ = 0;  // the reset clears set 0; a run never depends on the previous run's fields
-    if (plan_.reach) return clearReachPlanes();
+    if (plan_.reach) return true;  // (what such a run clears depends on the path it ends up on: enqueueRun)
     sweptDirty_ = true;  // (full sweeps: clearReachPlanes)
     return true;
 }
@@ -2145,6 +2185,9 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     if (plan_.path == StepPath::Window && !windowFor(lcx, lcy, win)) plan_.path = plan_.fallback;
     if (plan_.path == StepPath::Resident && !reserveBlocks(residentInFlight(device_), caps_.ntiles, residentBudget_, &residentHeld_))
         plan_.path = plan_.fallback;
+    // (reach-eligible runs -- only runs that come through here are: planRun -- clear behind the window lookup: a window run over
+    // the previous run's window clears nothing.  The repeat of a run that was given up clears as a reach-bounded run would.)
+    if (plan_.reach && !clearReachPlanes(plan_.path == StepPath::Window && !repeating_ ? win : nullptr)) return false;
     if (!stampTimed()) hipEventRecord(ev_[0], stream_);
     switch (plan_.path) {
         case StepPath::Window: enqueueWindowRun(win); break;
@@ -2166,7 +2209,7 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     lastRunBatched_ = false;
     // last kernel of the run: the registered queries' outputs and the status words, both into pinned memory
     launchRunFinish(res_, (long long)g_.gx * g_.gy, qCellsHost_, opt_.skipAnalysis ? 0 : numQueries_, qOutHost_, farInfo(), errFlag_,
-                    activeCount_, plan_.oneXcd ? resFlags_ + geo_.ntx * geo_.nty + 1 : nullptr, statusHost_, resFlags_,
+                    activeCount_, plan_.oneXcd ? resFlags_ + runTiles_ + 1 : nullptr, statusHost_, resFlags_,
                     resFlags_ ? resFlagWords_ : 0, stampTimed() ? stampsHost_ : nullptr, stream_);
     // (ev_[2] is also what the OTHER solver of a pipelined pair waits for before its carry pass reads this solver's maps: behind
     // the last kernel here, where it delays nothing of this run)
@@ -2259,6 +2302,7 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
 void Solver::enqueueResidentRun() {
     plan_.oneXcd = xcdOk_ && caps_.ntiles <= kResidentXcdMaxTiles &&
                    reserveBlocks(residentXcdInFlight(device_, xcdTarget_), caps_.ntiles, kResidentXcdMaxTiles, &xcdHeld_);
+    runTiles_ = caps_.ntiles;
     // (no begin-run launch: the run's parameters travel in the kernel's arguments, every block resets its own tile's entry, and
     // the flag words and the error flag were cleared by the previous run's last kernel -- or by the allocation)
     launchResidentRun(rxi_, nullptr);
@@ -2543,7 +2587,7 @@ bool Solver::sync() {
             counts[0] = statusHost_[1];
             counts[1] = statusHost_[2];
             tim_.silentCells = statusHost_[4];
-            if (plan_.oneXcd && statusHost_[3] >= 0 && statusHost_[3] < geo_.ntx * geo_.nty && flag == 0) flag = 4;
+            if (plan_.oneXcd && statusHost_[3] >= 0 && statusHost_[3] < runTiles_ && flag == 0) flag = 4;
         } else {
             // (raw stepping: no status kernel.)  The error flag, never through the legacy stream (applyGeometry), and by the kind
             // of run -- read behind stream_, the batched launches of a batch member's NEXT step loop took twice as long
@@ -2589,7 +2633,10 @@ bool Solver::sync() {
             if (flag == g.flag && g.applies) {
                 *g.form = g.value;
                 std::fputs(g.message, stderr);
-                return enqueueRun(lastLcx_, lastLcy_, lastLx_, lastLz_) && sync();
+                repeating_ = true;
+                const bool ok = enqueueRun(lastLcx_, lastLcy_, lastLx_, lastLz_);
+                repeating_ = false;
+                return ok && sync();
             }
         if (flag == 3 || flag == 4) return fail("resident kernel: a workgroup gave up waiting for its neighbours (run aborted)");
         if (flag == 5) return fail("slab decomposition: a neighbour's halo rows never arrived (run aborted)");
@@ -2660,7 +2707,7 @@ bool Solver::setOutputQueries(const float* xyz, int n) {
 
 // last kernel of a run: its status words into pinned memory (sync() then needs no copy and no second synchronisation)
 void Solver::enqueueRunStatus() {
-    launchRunStatus(errFlag_, activeCount_, plan_.oneXcd ? resFlags_ + geo_.ntx * geo_.nty + 1 : nullptr, statusHost_, stream_);
+    launchRunStatus(errFlag_, activeCount_, plan_.oneXcd ? resFlags_ + runTiles_ + 1 : nullptr, statusHost_, stream_);
     statusQueued_ = true;
 }
 

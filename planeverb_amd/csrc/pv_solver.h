@@ -145,6 +145,7 @@ public:
     const std::string& lastError() const { return err_; }
     bool streamFuse() const { return streamFuse_; }
     bool lastRunResidentWindow() const { return plan_.path == StepPath::Window; }
+    bool lastRunOneXcd() const { return plan_.oneXcd; }  // the last run's hand-off went through one XCD's L2 (pv_resident.hip)
     bool residentKernel() const { return caps_.useResident && !layerActive(); }  // runs of this solver go through pv_resident_kernel (when the
                                                           // device's resident-block budget allows: else the replayed graph)
     SolverOptions& options() { return opt_; }
@@ -411,7 +412,7 @@ private:
     // window (the windows of a run only grow), the only place that run left non-zero values.
     bool sweptDirty_ = true;
     int reachRect_[4] = {0, 0, 0, 0};
-    bool clearReachPlanes();
+    bool clearReachPlanes(const int* win);  // win: the window of a window run, nullptr: reach-bounded launches
     void setReachArgs(StepArgs& a, int t0);
     int* generalList_ = nullptr;
     int* generalCount_ = nullptr;
@@ -467,6 +468,10 @@ private:
     bool xcdOk_ = true;                // false once a launch found fewer blocks on its XCD than tiles (errFlag 4)
     int xcdTarget_ = 0;                // this solver's XCD (solvers take turns, so that pipelined solvers do not share one)
     int xcdHeld_ = 0;                  // blocks of that XCD's budget held by the run in flight
+    int runTiles_ = 0;                 // tiles of the resident launch in flight (the grid's or the window's): its claim counter is flag word runTiles_ + 1
+    bool xcdWindowOk_ = false;         // window runs may take the mode: init's throw-away window launch passed its claim check
+    bool probeWindow_ = false;         // ... which is the run being enqueued (windowFor answers with tile (0, 0))
+    bool repeating_ = false;           // sync() is repeating a run that was given up (it clears as a reach-bounded run would)
     int lastLcx_ = 0, lastLcy_ = 0;    // (a run given up by the claim check is repeated in the placement-independent mode)
     void releaseResident();
     // Resident window: on the large-grid tile a run whose listener's air component is walled in and small goes out
