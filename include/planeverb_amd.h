@@ -699,6 +699,64 @@ PVA_EXPORT int PvAmdGetLateralFraction(PvAmdSolver* s, float ex, float ey, float
  * the restatement the tests hold the kernel to */
 PVA_EXPORT int PvAmdHostLateralFraction(const float* p, const float* vx, const float* vy, int T, int fs, int onset,
                                         PvAmdLateralFraction* out);
+/* ---- Directional echogram: the energy and the flux of every reached cell per time slot after its onset ----
+ * Every record above folds the impulse response into a few scalars; none says WHEN the energy arrives after the direct sound
+ * and FROM WHERE.  The echogram (energy-time curve) does, one tap per time slot with a gain and a direction -- what a room-
+ * acoustics user looks at first and what an early-reflection renderer is driven by.  The energy per slot a pressure-only tool
+ * can give; the direction each slot's sound travels in needs the particle velocity.  PvAmdComputeEchogram reduces the history of
+ * the LAST COMPLETED run to 1 + 3 nSlots floats per cell on the device (pv_echogram.hip), with the velocity recurrence of the
+ * lateral-fraction pass carried through the window the caller chooses.  It touches no run and no result map.
+ * Slots: nSlots of them, 0 .. PVA_ECHOGRAM_MAX_SLOTS, each of
+ *   ns = (int)(slotSeconds * (float)fs)        in float32 -- the expression of n5 above, so slotSeconds = 0.005f gives ns == n5
+ * steps.  nSlots = 0 clears the setting and frees the device storage.  Refused with -1 and nothing changed unless slotSeconds is
+ * finite and 1 <= ns <= (1 << 20).
+ * Definition, for result cell s = X * gy + Y, with delay the run's own onset map and p(t), vx(t), vy(t) exactly what
+ * PvAmdGetImpulseResponse returns for array cell (X, Y) -- the library's velocity, the UNDAMPED recurrence of the lateral-fraction
+ * section above, started from 0 at the cell's first recorded sample:
+ *   onset = (int)delay[s]                      (FLT_MAX: not reached)
+ *   tEnd  = min(onset + ns * nSlots, T)
+ *   for t = onset .. tEnd - 1,  k = t - onset,  j = k / ns        (integer division; 0 <= j < nSlots)
+ *      e[j]  = e[j]  + (p * p)
+ *      ix[j] = ix[j] + (p * vx)
+ *      iy[j] = iy[j] + (p * vy)
+ *   record (1 + 3 nSlots floats): n = (float)(tEnd - onset), then e[0], ix[0], iy[0], e[1], ix[1], iy[1], ...
+ * Everything is float32, every product and sum rounded on its own (no FMA); every slot's three sums start at +0.0f and are
+ * sequential in increasing t.  Nothing is special-cased: a slot the record does not reach (onset + j * ns >= T) holds three
+ * +0.0f, a slot cut by T holds its partial sums, and n < ns * nSlots reports either case.
+ * (ix[j], iy[j]) is the net direction in which slot j's sound TRAVELS (away from its source); it is neither negated nor
+ * normalised: a caller normalises it, and negates it for a direction of arrival.  Levels, 10 log10(e[j] / e[0]), are left to
+ * the caller, and so is any picking of discrete reflections: the pulse is band-limited, and local maxima of the slot energies
+ * are mostly its ringing.
+ * A cell WITHOUT an onset in that run holds 1 + 3 nSlots quiet NaNs (0x7fc00000); nothing is carried over from earlier runs.
+ * Cells inside an edge layer get records like any other cell.
+ * Device storage: (1 + 3 nSlots) x 4 bytes per cell of the history window, allocated by the first PvAmdComputeEchogram (again
+ * when nSlots changes), freed by PvAmdSetEchogram(..., 0) and with the solver.  The records stay valid until the next run, a
+ * geometry, boundary or layer change, or a PvAmdSetEchogram call on that solver: PvAmdCopyEchogram* / PvAmdGetEchogram then
+ * return -1 until computed again.  The echogram and the five record kinds above and below (room metrics, spectrum, decay times,
+ * lateral fraction, band metrics) do not invalidate each other.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "echogram: ..."): NULL, no slots set ("echogram: no slots set"), no
+ * completed run, a last run that ended in error, sparse-emitter solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab
+ * groups and slab ranks. */
+#define PVA_ECHOGRAM_MAX_SLOTS 32
+/* Set (nSlots > 0) or clear (nSlots = 0: the device storage is freed) the slots; waits for a run in flight */
+PVA_EXPORT int PvAmdSetEchogram(PvAmdSolver* s, float slotSeconds, int nSlots);
+/* returns nSlots; slotSeconds as set and ns to *slotSeconds and *slotSteps (both optional; untouched when no slots are set) */
+PVA_EXPORT int PvAmdGetEchogramSlots(PvAmdSolver* s, float* slotSeconds, int* slotSteps);
+/* Compute the echogram records of the LAST COMPLETED run of s (waits for a run in flight; works after every form of run, as
+ * PvAmdComputeLateralFraction).  Synchronous on the solver's own stream.  *ms (optional): device time of the pass. */
+PVA_EXPORT int PvAmdComputeEchogram(PvAmdSolver* s, float* ms);
+/* gx*gy*(1+3n) floats, AoS records, cell s = X*gy + Y */
+PVA_EXPORT int PvAmdCopyEchogram(PvAmdSolver* s, float* out);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records, row-major */
+PVA_EXPORT int PvAmdCopyEchogramBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out);
+/* the record (1+3n floats) at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map gives
+ * NaNs and 0 */
+PVA_EXPORT int PvAmdGetEchogram(PvAmdSolver* s, float ex, float ey, float ez, float* out);
+/* CPU only: the definition above applied to one impulse response p[T], vx[T], vy[T] with 0 <= onset < T and 1 <= nSlots <=
+ * PVA_ECHOGRAM_MAX_SLOTS (refused otherwise, as a slotSeconds PvAmdSetEchogram would refuse at that fs); out: 1 + 3 nSlots
+ * floats; the restatement the tests hold the kernel to */
+PVA_EXPORT int PvAmdHostEchogram(const float* p, const float* vx, const float* vy, int T, int fs, int onset,
+                                 float slotSeconds, int nSlots, float* out);
 /* ---- Band metrics: decay times and clarity of every reached cell per octave or third-octave band ----
  * The records above are broadband: the decay of a cell is that of whichever part of the pulse's band decays slowest there.
  * PvAmdComputeBandMetrics filters each reached cell's recorded pressure into the bands set by PvAmdSetBands and reduces every

@@ -22,6 +22,13 @@ def vec3(s):
     return tuple(v)
 
 
+def echogram_setting(s):
+    v = s.split(",")
+    if len(v) != 2:
+        raise argparse.ArgumentTypeError("expected slotSeconds,nSlots")
+    return float(v[0]), int(v[1])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m planeverb_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -38,6 +45,9 @@ def main(argv=None):
                     help="add the decay times (EDT, T20, T30, their point counts, E0 and the curve's depth) of each emitter's cell")
     ap.add_argument("--lateral-fraction", action="store_true",
                     help="add the early lateral energy fraction, the early-sound direction and their sums of each emitter's cell")
+    ap.add_argument("--echogram", metavar="SECONDS,SLOTS", type=echogram_setting,
+                    help="add the directional echogram of each emitter's cell: energy and flux (ix, iy: the direction the sound "
+                         "travels in) per time slot after the onset, e.g. 0.005,16")
     ap.add_argument("--spectrum", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the transfer function (re, im, level in dB re the source) of each emitter's cell at these frequencies")
     ap.add_argument("--bands", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
@@ -70,6 +80,9 @@ def main(argv=None):
             s.compute_decay_times()
         if a.lateral_fraction:
             s.compute_lateral_fraction()
+        if a.echogram:
+            s.set_echogram(*a.echogram)
+            s.compute_echogram()
         if a.bands:
             s.set_bands(a.bands, a.band_fraction)
             s.compute_band_metrics()
@@ -92,6 +105,11 @@ def main(argv=None):
             if a.lateral_fraction:
                 m = s.lateral_fraction_at(e)
                 out["emitters"][-1]["lateralFraction"] = dict((n, float(v)) for n, v in zip(api.LATERAL_FRACTION_NAMES, m))
+            if a.echogram:
+                m = s.echogram_at(e)
+                out["emitters"][-1]["echogram"] = {"slotSteps": s.echogram_slots()[2], "n": float(m[0]),
+                                                   "e": [float(v) for v in m[1::3]], "ix": [float(v) for v in m[2::3]],
+                                                   "iy": [float(v) for v in m[3::3]]}
             if a.bands:
                 m = s.band_metrics_at(e)
                 out["emitters"][-1]["bandMetrics"] = [

@@ -273,6 +273,13 @@ SYMBOLS = {
     "PvAmdCopyLateralFractionBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "PvAmdGetLateralFraction": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdLateralFraction)]),
     "PvAmdHostLateralFraction": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdLateralFraction)]),
+    "PvAmdSetEchogram": (C.c_int, [_vp, C.c_float, C.c_int]),
+    "PvAmdGetEchogramSlots": (C.c_int, [_vp, _fp, C.POINTER(C.c_int)]),
+    "PvAmdComputeEchogram": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyEchogram": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyEchogramBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetEchogram": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
+    "PvAmdHostEchogram": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp]),
     "PvAmdSetBands": (C.c_int, [_vp, _fp, C.c_int, C.c_int]),
     "PvAmdGetBands": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(C.c_int)]),
     "PvAmdGetBandCoefs": (C.c_int, [_vp, _fp]),
@@ -739,6 +746,22 @@ def host_lateral_fraction(p, vx, vy, fs, onset):
     ptr = [_f(v) if v.size else None for v in (a, x, y)]
     _check(lib().PvAmdHostLateralFraction(ptr[0], ptr[1], ptr[2], int(a.size), int(fs), int(onset), out))
     return out.as_array()
+
+
+ECHOGRAM_MAX_SLOTS = 32  # PVA_ECHOGRAM_MAX_SLOTS
+
+
+def host_echogram(p, vx, vy, fs, onset, slot_seconds, n_slots):
+    """PvAmdHostEchogram: float32 [1 + 3 n_slots] (n, then e, ix, iy per slot) of one impulse response p[T] with its velocities
+    vx[T], vy[T] and its onset step -- the definition of include/planeverb_amd.h (PvAmdSetEchogram) on the CPU"""
+    a, x, y = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (p, vx, vy))
+    if not (a.size == x.size == y.size):
+        raise ValueError("host_echogram: p, vx and vy must have the same length")
+    out = np.empty(1 + 3 * max(int(n_slots), 0), np.float32)
+    ptr = [_f(v) if v.size else None for v in (a, x, y)]
+    _check(lib().PvAmdHostEchogram(ptr[0], ptr[1], ptr[2], int(a.size), int(fs), int(onset), float(slot_seconds), int(n_slots),
+                                   _f(out)))
+    return out
 
 
 BANDS_MAX = 8  # PVA_BANDS_MAX
@@ -1486,6 +1509,46 @@ class Solver:
         out = PvAmdLateralFraction()
         _check(lib().PvAmdGetLateralFraction(self._h, *[float(v) for v in pos], out))
         return out.as_array()
+
+    def set_echogram(self, slot_seconds, n_slots):
+        """the time slots compute_echogram sums into: n_slots (at most ECHOGRAM_MAX_SLOTS) of (int)(slot_seconds * fs) steps each,
+        from every cell's own onset on; n_slots = 0 clears them and frees the device storage"""
+        _check(lib().PvAmdSetEchogram(self._h, float(slot_seconds), int(n_slots)))
+
+    def echogram_slots(self):
+        """(n, slot_seconds, slot_steps): the slots as set; (0, 0.0, 0) when none are"""
+        sec, steps = C.c_float(0.0), C.c_int(0)
+        n = lib().PvAmdGetEchogramSlots(self._h, C.byref(sec), C.byref(steps))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return n, sec.value, steps.value
+
+    def compute_echogram(self):
+        """directional echogram of the last completed run at the slots of set_echogram: energy p^2 and flux p vx, p vy of
+        every reached cell per slot, the velocity by the stencil's recurrence, on the device; returns the pass's device time in
+        milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeEchogram(self._h, C.byref(ms)))
+        return ms.value
+
+    def echogram(self):
+        """float32 [gx, gy, 1 + 3 n]: n = the steps summed, then e, ix, iy of each slot; NaN where the cell has no onset in the
+        run they were computed for.  (ix, iy) is the direction slot j's sound travels in, neither normalised nor negated"""
+        out = np.empty((self.gx, self.gy, 1 + 3 * self.echogram_slots()[0]), np.float32)
+        _check(lib().PvAmdCopyEchogram(self._h, _f(out)))
+        return out
+
+    def echogram_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, 1 + 3 n] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, 1 + 3 * self.echogram_slots()[0]), np.float32)
+        _check(lib().PvAmdCopyEchogramBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def echogram_at(self, pos):
+        """float32 [1 + 3 n] at an emitter position (the cell get_output reads); NaNs off the map"""
+        out = np.empty(1 + 3 * self.echogram_slots()[0], np.float32)
+        _check(lib().PvAmdGetEchogram(self._h, *[float(v) for v in pos], _f(out)))
+        return out
 
     def set_bands(self, hz, fraction=1):
         """the band centres (Hz, at most BANDS_MAX) compute_band_metrics filters into, octaves (fraction 1) or third octaves

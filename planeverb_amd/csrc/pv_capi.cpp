@@ -13,6 +13,7 @@
 #include "pv_core.h"
 #include "pv_bands.h"
 #include "pv_decay.h"
+#include "pv_echogram.h"
 #include "pv_lateral.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
@@ -1219,6 +1220,73 @@ int PvAmdGetLateralFraction(PvAmdSolver* h, float ex, float ey, float ez, PvAmdL
     return 0;
 } PV_API_CATCH(-1)
 
+// echogram (pv_echogram.hip): single whole-grid solvers only, as the lateral fraction; every refusal says "echogram: ...".  The
+// setting is checked against the handle's own grid before anything else happens (pv_echogram.h echogramSlotOk, the rule
+// PvAmdHostEchogram applies too)
+static bool echogramHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "echogram: " + g_lastError;
+    return false;
+}
+
+static const char* echogramSettingError(float slotSeconds, int nSlots, int fs) {
+    if (nSlots < 0 || nSlots > kEchogramMaxSlots) return "echogram: nSlots is 0 .. PVA_ECHOGRAM_MAX_SLOTS (32)";
+    if (nSlots > 0 && !echogramSlotOk(slotSeconds, fs))
+        return "echogram: slotSeconds must be finite and give 1 .. 2^20 steps per slot ((int)(slotSeconds * (float)fs))";
+    return nullptr;
+}
+
+int PvAmdSetEchogram(PvAmdSolver* h, float slotSeconds, int nSlots) try {
+    if (!h) {
+        g_lastError = "echogram: null solver handle";
+        return -1;
+    }
+    if (const char* e = echogramSettingError(slotSeconds, nSlots, (int)h->spec.fs)) {
+        g_lastError = e;
+        return -1;
+    }
+    if (!echogramHandle(h)) return -1;
+    return ret(h, h->s->setEchogram(slotSeconds, nSlots));
+} PV_API_CATCH(-1)
+
+int PvAmdGetEchogramSlots(PvAmdSolver* h, float* slotSeconds, int* slotSteps) try {
+    if (!echogramHandle(h)) return -1;
+    return h->s->echogramSlots(slotSeconds, slotSteps);
+} PV_API_CATCH(-1)
+
+int PvAmdComputeEchogram(PvAmdSolver* h, float* ms) try {
+    if (!echogramHandle(h)) return -1;
+    return ret(h, h->s->computeEchogram(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyEchogram(PvAmdSolver* h, float* out) try {
+    if (!echogramHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "echogram: PvAmdCopyEchogram: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyEchogramBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyEchogramBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out) try {
+    if (!echogramHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "echogram: PvAmdCopyEchogramBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyEchogramBlock(r0, c0, nr, nc, out));
+} PV_API_CATCH(-1)
+
+int PvAmdGetEchogram(PvAmdSolver* h, float ex, float ey, float ez, float* out) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!echogramHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "echogram: PvAmdGetEchogram: null output";
+        return -1;
+    }
+    return ret(h, h->s->echogramAt(ex, ez, out));
+} PV_API_CATCH(-1)
+
 // band metrics (pv_bands.hip): single whole-grid solvers only, as the decay times; every refusal says "band metrics: ...".  The
 // bands are checked against the handle's own grid before anything else happens (pv_bands.h bandsError, the rule
 // PvAmdHostBandCoefs applies too)
@@ -1694,6 +1762,22 @@ int PvAmdHostLateralFraction(const float* p, const float* vx, const float* vy, i
     float v[kLateralFloats];
     lateralFractionOfIr(p, vx, vy, T, fs, onset, v);
     std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostEchogram(const float* p, const float* vx, const float* vy, int T, int fs, int onset, float slotSeconds, int nSlots,
+                      float* out) try {
+    if (!p || !vx || !vy || !out || T <= 0 || onset < 0 || onset >= T || nSlots < 1 || nSlots > kEchogramMaxSlots) {
+        g_lastError =
+            "echogram: PvAmdHostEchogram: an impulse response p[T], vx[T], vy[T], T > 0, 0 <= onset < T, 1 .. 32 slots and an output of "
+            "1 + 3 nSlots floats";
+        return -1;
+    }
+    if (!echogramSlotOk(slotSeconds, fs)) {
+        g_lastError = "echogram: slotSeconds must be finite and give 1 .. 2^20 steps per slot ((int)(slotSeconds * (float)fs))";
+        return -1;
+    }
+    echogramOfIr(p, vx, vy, T, onset, echogramSlotSteps(slotSeconds, fs), nSlots, out);
     return 0;
 } PV_API_CATCH(-1)
 

@@ -141,6 +141,12 @@ void launchDecayTimes(const AnalyzeArgs& a, float* out, bool twoLaunches, hipStr
 // does not read a slab's histAbove)
 void launchLateralFraction(const AnalyzeArgs& a, float* out, hipStream_t stream);
 
+// ---- pv_echogram.hip: per-cell directional echogram
+// echogram records of the last completed run (pv_echogram.hip) for nSlots slots (1 .. kEchogramMaxSlots) of ns >= 1 steps:
+// out = 1 + 3 nSlots planes of a.histPlane floats (n, then e, ix, iy of slot j at planes 1 + 3 j ..), indexed by the cell's
+// offset inside a history plane; NaN where the cell has no onset in that run.  Whole-grid solvers only, as the lateral fraction
+void launchEchogram(const AnalyzeArgs& a, float* out, int ns, int nSlots, hipStream_t stream);
+
 // ---- pv_bands.hip: per-cell, per-band decay times and clarity
 // band records of the last completed run (pv_bands.hip) for n bands: coefs = n x kBandCoefs floats on the HOST (they travel as
 // kernel arguments), out = n x kBandFloats planes of a.histPlane floats (band j, float k at plane j * kBandFloats + k), indexed by

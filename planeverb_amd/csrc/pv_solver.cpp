@@ -20,6 +20,7 @@
 #include "pv_launch.h"
 #include "pv_bands.h"
 #include "pv_decay.h"
+#include "pv_echogram.h"
 #include "pv_lateral.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
@@ -706,6 +707,9 @@ Solver::~Solver() {
     if (lateral_) hipFree(lateral_);
     for (auto& e : lateralEv_)
         if (e) hipEventDestroy(e);
+    if (echo_) hipFree(echo_);
+    for (auto& e : echoEv_)
+        if (e) hipEventDestroy(e);
     for (float* p : {specTab_, specPow_, spectrum_})
         if (p) hipFree(p);
     for (auto& e : spectrumEv_)
@@ -787,7 +791,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     return id;
 }
 
@@ -798,7 +802,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     return true;
 }
 
@@ -809,7 +813,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     return true;
 }
 
@@ -881,14 +885,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -1035,7 +1039,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     return true;
 }
 
@@ -1075,7 +1079,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     return true;
 }
 
@@ -2139,7 +2143,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;       // (the history the records were made from is about to be overwritten)
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     if (!applyGeometry()) return false;
     PathRun r;
@@ -3165,6 +3169,118 @@ bool Solver::lateralFractionAt(float ex, float ez, float out11[11]) {
         return true;
     }
     return copyLateralFractionBlock(cx, cy, 1, 1, out11);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// directional echogram (pv_echogram.hip): everything as the lateral fraction above, with 1 + 3 nSlots planes and the slots as the
+// band metrics' bands
+// ----------------------------------------------------------------------------------------------------------------
+
+bool Solver::setEchogram(float slotSeconds, int nSlots) {
+    if (isSlab()) return fail("echogram: not available on a slab");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    echoValid_ = false;
+    echoHostValid_ = false;
+    if (nSlots == 0) {
+        if (echo_) hipFree(echo_);
+        echo_ = nullptr;
+        echoPlanes_ = 0;
+        echoSeconds_ = 0.f;
+        echoSteps_ = echoSlots_ = 0;
+        return true;
+    }
+    echoSeconds_ = slotSeconds;
+    echoSteps_ = echogramSlotSteps(slotSeconds, (int)g_.fs);
+    echoSlots_ = nSlots;
+    return true;
+}
+
+int Solver::echogramSlots(float* slotSeconds, int* slotSteps) const {
+    if (slotSeconds && echoSlots_) *slotSeconds = echoSeconds_;
+    if (slotSteps && echoSlots_) *slotSteps = echoSteps_;
+    return echoSlots_;
+}
+
+bool Solver::computeEchogram(float* ms) {
+    if (isSlab()) return fail("echogram: not available on a slab");
+    if (opt_.streaming) return fail("echogram: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("echogram: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    if (!echoSlots_) return fail("echogram: no slots set (PvAmdSetEchogram)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("echogram: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("echogram: the last run ended in error");
+    const int nf = echogramFloats(echoSlots_);
+    if (echo_ && echoPlanes_ != nf) {
+        hipFree(echo_);
+        echo_ = nullptr;
+    }
+    if (!echo_) {
+        if (!dalloc(&echo_, (size_t)nf * (size_t)histPlane_, false)) return false;
+        echoPlanes_ = nf;
+    }
+    for (auto& e : echoEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    echoValid_ = false;
+    echoHostValid_ = false;
+    hipEventRecord(echoEv_[0], stream_);
+    launchEchogram(analyzeArgs(lastLx_, lastLz_), echo_, echoSteps_, echoSlots_, stream_);
+    hipEventRecord(echoEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "echogram launch") || !hipOk(hipStreamSynchronize(stream_), "echogram sync")) return false;
+    if (ms) hipEventElapsedTime(ms, echoEv_[0], echoEv_[1]);
+    echoDyn_ = dynCur_;
+    echoValid_ = true;
+    return true;
+}
+
+bool Solver::fetchEchogram() {
+    if (!echoSlots_) return fail("echogram: no slots set (PvAmdSetEchogram)");
+    if (!echoValid_)
+        return fail("echogram: not computed for the last run, the current geometry and the current slots (PvAmdComputeEchogram)");
+    if (echoHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    echoHost_.resize((size_t)echoPlanes_ * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(echoHost_.data(), echo_, echoHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "echogram copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "echogram sync"))
+        return false;
+    echoHostValid_ = true;
+    return true;
+}
+
+bool Solver::copyEchogramBlock(int r0, int c0, int nr, int nc, float* out) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("echogram: block outside the map");
+    if (!fetchEchogram()) return false;
+    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
+    const int wr0 = echoDyn_.histRow0 - geo_.G, wc0 = echoDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const int nf = echoPlanes_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < nf; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * echoDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < nf; ++k) o[k] = echoHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::echogramAt(float ex, float ez, float* out) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!fetchEchogram()) return false;
+        for (int k = 0; k < echoPlanes_; ++k) out[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copyEchogramBlock(cx, cy, 1, 1, out);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

@@ -159,11 +159,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -266,6 +266,16 @@ public:
     bool computeLateralFraction(float* ms);
     bool copyLateralFractionBlock(int r0, int c0, int nr, int nc, float* out11);
     bool lateralFractionAt(float ex, float ez, float out11[11]);
+    // Directional echogram (pv_echogram.hip; include/planeverb_amd.h PvAmdSetEchogram): energy and flux of the last completed run
+    // per time slot after each cell's onset, for the slots set here; lifetime and refusals as the lateral fraction's, and a
+    // change of slots invalidates the records.  setEchogram: the caller has validated the setting (pv_echogram.h echogramSlotOk,
+    // 0 <= nSlots <= kEchogramMaxSlots); nSlots = 0 clears and frees; waits for a run in flight.  out: nr x nc records of
+    // 1 + 3 nSlots floats, NaN where the cell has no onset in that run
+    bool setEchogram(float slotSeconds, int nSlots);
+    int echogramSlots(float* slotSeconds, int* slotSteps) const;
+    bool computeEchogram(float* ms);
+    bool copyEchogramBlock(int r0, int c0, int nr, int nc, float* out);
+    bool echogramAt(float ex, float ez, float* out);
     // Band metrics (pv_bands.hip; include/planeverb_amd.h PvAmdBandMetrics): decay times and clarity of the last completed run per
     // octave or third-octave band set here; lifetime and refusals as the decay times', and a change of bands invalidates the
     // records.  setBands: the caller has validated the centres (pv_bands.h bandsError); n = 0 clears and frees; waits for a run
@@ -517,6 +527,19 @@ private:
     bool lateralHostValid_ = false;
     hipEvent_t lateralEv_[2] = {nullptr, nullptr};
     bool fetchLateralFraction();
+    // echogram (pv_echogram.h): the slot length as given and in steps, the slots; 1 + 3 nSlots planes of histPlane_ floats -- n,
+    // then e, ix, iy of slot j at planes 1 + 3 j .. -- allocated by the first computeEchogram and again when nSlots changes.
+    // echoValid_ follows metricsValid_ and is also cleared by a change of the setting; no computation touches another's flag
+    float echoSeconds_ = 0.f;
+    int echoSteps_ = 0, echoSlots_ = 0;
+    float* echo_ = nullptr;
+    int echoPlanes_ = 0;  // 1 + 3 nSlots of the allocation
+    bool echoValid_ = false;
+    DynParams echoDyn_{};
+    std::vector<float> echoHost_;
+    bool echoHostValid_ = false;
+    hipEvent_t echoEv_[2] = {nullptr, nullptr};
+    bool fetchEchogram();
     // band metrics (pv_bands.h): the centres, their fraction and the 10 float32 coefficients per band on the host (the kernel takes
     // them as arguments); 12 n planes of histPlane_ floats -- band j at planes 12 j .. 12 j + 11 -- allocated by the first
     // computeBandMetrics and again when n changes.  bandsValid_ follows metricsValid_ and is also cleared by a change of bands; no
