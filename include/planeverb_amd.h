@@ -757,6 +757,66 @@ PVA_EXPORT int PvAmdGetEchogram(PvAmdSolver* s, float ex, float ey, float ez, fl
  * floats; the restatement the tests hold the kernel to */
 PVA_EXPORT int PvAmdHostEchogram(const float* p, const float* vx, const float* vy, int T, int fs, int onset,
                                  float slotSeconds, int nSlots, float* out);
+/* ---- Echo criterion (Dietsch and Kraak, Acustica 60, 1986; the "EK" of room-acoustics programs), speech and music ----
+ * Will this position hear a distinct echo, and at what delay?  The echogram above leaves picking to the caller because local
+ * maxima of its slot energies are mostly the band-limited pulse's ringing.  The echo criterion tracks the running centre time of
+ * the |p|^n-weighted response and takes its difference quotient over a short window, which smooths the ringing away by
+ * construction, and it comes with published thresholds.  PvAmdComputeEchoCriterion reduces the history of the LAST COMPLETED run
+ * to one record of ten floats per cell in one forward pass on the device (pv_echo.hip).  It touches no run and no result map.
+ * Definition, for result cell s = X * gy + Y:
+ *   onset   t0 = (int)delay[s], delay = the run's own onset map (FLT_MAX: not reached);
+ *   p(t)    = the recorded pressure, exactly what PvAmdCopyHistoryPlane(t) returns at array cell (X, Y);
+ *   k = t - t0 for t = t0 .. T - 1,   N = T - t0,   a(t) = fabsf(p(t));
+ *   variant   weight w(t)                              lag nD                       echo limit nL
+ *   speech    powf(a, PVA_ECHO_SPEECH_EXPONENT)        (int)(0.009f * (float)fs)    n50 = (int)(0.05f * (float)fs)
+ *   music     a                                        (int)(0.014f * (float)fs)    n80 = (int)(0.08f * (float)fs)
+ * and per variant, sequential in increasing k from +0.0f:
+ *   A(k) = A(k-1) + w                     B(k) = B(k-1) + ((float)k * w)
+ *   c(k) = B(k) / A(k)                                            (centre of the build-up, in steps)
+ *   x(k) = (c(k) - (k >= nD ? c(k - nD) : +0.0f)) / (float)nD
+ *   ek, kk         start at +0.0f, 0;   if (x(k) > ek) { ek = x(k); kk = k; }                          for every k
+ *   ekLate, kkLate start at +0.0f, 0;   if (k >= nL && x(k) > ekLate) { ekLate = x(k); kkLate = k; }
+ *   ts = c(N - 1) / (float)fs
+ *   record (5 floats): ek, (float)kk / (float)fs, ekLate, (float)kkLate / (float)fs, ts
+ * The whole record is the speech variant's five floats, then the music variant's (PvAmdEchoCriterion).
+ * All arithmetic is float32; every product, sum and quotient is rounded on its own (no FMA); division is correctly rounded; powf
+ * is glibc's.  The comparison is strict: the first maximum wins and a NaN x never does.  Nothing is special-cased: A = 0 gives
+ * 0 / 0 as IEEE says (an all-zero response has ek = +0 and ts = NaN), and a response shorter than nL leaves ekLate = +0,
+ * kkLate = 0.
+ * Reading the values: a position is said to hear an echo where ek exceeds PVA_ECHO_SPEECH_CRIT (speech) or PVA_ECHO_MUSIC_CRIT
+ * (music), for half of the listeners; tk says at which delay after the direct sound.  CAVEAT: the published thresholds were
+ * derived for test signals of 700 - 1400 Hz (speech) and 700 - 2800 Hz (music).  Here the response is the grid's band-limited
+ * one, and at the low presets the direct pulse alone is a good part of nD wide: in an empty, open scene it reaches ek of about
+ * 0.75 - 0.96 by itself.  ekLate / tkLate, the maximum over k >= nL only, is the part that lies past the fusion limit
+ * (50 ms / 80 ms), where the direct pulse's own build-up no longer counts.
+ * A cell WITHOUT an onset in that run holds ten quiet NaNs; nothing is carried over from earlier runs.  Cells inside an edge
+ * layer get records like any other cell.
+ * Device storage: 10 x 4 bytes per cell of the history window, allocated by the first call, freed with the solver.  The records
+ * stay valid until the next run, geometry, boundary or layer change on that solver: PvAmdCopyEchoCriterion* /
+ * PvAmdGetEchoCriterion then return -1 until computed again.  The echo criterion and the six other record kinds (room metrics,
+ * spectrum, decay times, lateral fraction, echogram, band metrics) do not invalidate each other.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "echo: ..."): what the room metrics refuse (NULL, no completed run, a
+ * last run that ended in error, sparse-emitter solvers, PVA_OPT_SKIP_ANALYSIS, slab groups and slab ranks), and a sampling rate
+ * whose speech lag is below one step, (int)(0.009f * (float)fs) < 1, i.e. fs < 112. */
+#define PVA_ECHO_SPEECH_EXPONENT 0.6666667f /* (float)(2.0 / 3.0) */
+#define PVA_ECHO_SPEECH_CRIT 1.0f
+#define PVA_ECHO_MUSIC_CRIT 1.8f
+typedef struct PvAmdEchoCriterion {
+    float sEk, sTk, sEkLate, sTkLate, sTs, mEk, mTk, mEkLate, mTkLate, mTs;
+} PvAmdEchoCriterion;
+/* Compute the echo-criterion records of the LAST COMPLETED run of s (waits for a run in flight; works after every form of run,
+ * as PvAmdComputeRoomMetrics).  Synchronous on the solver's own stream.  *ms (optional): device time of the pass. */
+PVA_EXPORT int PvAmdComputeEchoCriterion(PvAmdSolver* s, float* ms);
+/* gx*gy*10 floats, AoS records, cell s = X*gy + Y */
+PVA_EXPORT int PvAmdCopyEchoCriterion(PvAmdSolver* s, float* out10);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records, row-major */
+PVA_EXPORT int PvAmdCopyEchoCriterionBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out10);
+/* the record at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map gives ten NaNs
+ * and 0 */
+PVA_EXPORT int PvAmdGetEchoCriterion(PvAmdSolver* s, float ex, float ey, float ez, PvAmdEchoCriterion* out);
+/* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T and a sampling rate the criterion
+ * accepts (fs >= 112); the restatement the tests hold the kernel to */
+PVA_EXPORT int PvAmdHostEchoCriterion(const float* p, int T, int fs, int onset, PvAmdEchoCriterion* out);
 /* ---- Band metrics: decay times and clarity of every reached cell per octave or third-octave band ----
  * The records above are broadband: the decay of a cell is that of whichever part of the pulse's band decays slowest there.
  * PvAmdComputeBandMetrics filters each reached cell's recorded pressure into the bands set by PvAmdSetBands and reduces every

@@ -48,6 +48,9 @@ def main(argv=None):
     ap.add_argument("--echogram", metavar="SECONDS,SLOTS", type=echogram_setting,
                     help="add the directional echogram of each emitter's cell: energy and flux (ix, iy: the direction the sound "
                          "travels in) per time slot after the onset, e.g. 0.005,16")
+    ap.add_argument("--echo-criterion", action="store_true",
+                    help="add the echo criterion (Dietsch and Kraak: EK, its delay, the late EK, its delay and Ts, for speech "
+                         "and for music) of each emitter's cell")
     ap.add_argument("--spectrum", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the transfer function (re, im, level in dB re the source) of each emitter's cell at these frequencies")
     ap.add_argument("--bands", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
@@ -78,6 +81,8 @@ def main(argv=None):
             s.compute_room_metrics()
         if a.decay_times:
             s.compute_decay_times()
+        if a.echo_criterion:
+            s.compute_echo_criterion()
         if a.lateral_fraction:
             s.compute_lateral_fraction()
         if a.echogram:
@@ -102,6 +107,9 @@ def main(argv=None):
             if a.decay_times:
                 m = s.decay_times_at(e)
                 out["emitters"][-1]["decayTimes"] = dict((n, float(v)) for n, v in zip(api.DECAY_TIME_NAMES, m))
+            if a.echo_criterion:
+                m = s.echo_criterion_at(e)
+                out["emitters"][-1]["echoCriterion"] = dict((n, float(v)) for n, v in zip(api.ECHO_CRITERION_NAMES, m))
             if a.lateral_fraction:
                 m = s.lateral_fraction_at(e)
                 out["emitters"][-1]["lateralFraction"] = dict((n, float(v)) for n, v in zip(api.LATERAL_FRACTION_NAMES, m))

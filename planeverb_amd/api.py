@@ -133,6 +133,18 @@ class PvAmdLateralFraction(C.Structure):
         return np.frombuffer(self, np.float32).copy()
 
 
+ECHO_CRITERION_NAMES = ("s_ek", "s_tk", "s_ek_late", "s_tk_late", "s_ts", "m_ek", "m_tk", "m_ek_late", "m_tk_late", "m_ts")
+ECHO_SPEECH_CRIT = 1.0  # PVA_ECHO_SPEECH_CRIT
+ECHO_MUSIC_CRIT = 1.8   # PVA_ECHO_MUSIC_CRIT
+
+
+class PvAmdEchoCriterion(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("sEk", "sTk", "sEkLate", "sTkLate", "sTs", "mEk", "mTk", "mEkLate", "mTkLate", "mTs")]
+
+    def as_array(self):
+        return np.frombuffer(self, np.float32).copy()
+
+
 # every symbol include/planeverb_amd.h declares: name -> (restype, argtypes)
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
@@ -268,6 +280,11 @@ SYMBOLS = {
     "PvAmdCopyDecayTimesBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "PvAmdGetDecayTimes": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdDecayTimes)]),
     "PvAmdHostDecayTimes": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdDecayTimes)]),
+    "PvAmdComputeEchoCriterion": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyEchoCriterion": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyEchoCriterionBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetEchoCriterion": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PvAmdEchoCriterion)]),
+    "PvAmdHostEchoCriterion": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(PvAmdEchoCriterion)]),
     "PvAmdComputeLateralFraction": (C.c_int, [_vp, _fp]),
     "PvAmdCopyLateralFraction": (C.c_int, [_vp, _fp]),
     "PvAmdCopyLateralFractionBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
@@ -733,6 +750,15 @@ def host_decay_times(p, fs, onset):
     a = np.ascontiguousarray(p, np.float32).reshape(-1)
     out = PvAmdDecayTimes()
     _check(lib().PvAmdHostDecayTimes(_f(a) if a.size else None, int(a.size), int(fs), int(onset), out))
+    return out.as_array()
+
+
+def host_echo_criterion(p, fs, onset):
+    """PvAmdHostEchoCriterion: float32 [10] (ECHO_CRITERION_NAMES) of one impulse response p[T] with its onset step -- the
+    definition of include/planeverb_amd.h (PvAmdEchoCriterion) on the CPU"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    out = PvAmdEchoCriterion()
+    _check(lib().PvAmdHostEchoCriterion(_f(a) if a.size else None, int(a.size), int(fs), int(onset), out))
     return out.as_array()
 
 
@@ -1481,6 +1507,31 @@ class Solver:
         """float32 [8] at an emitter position (the cell get_output reads); eight NaNs off the map"""
         out = PvAmdDecayTimes()
         _check(lib().PvAmdGetDecayTimes(self._h, *[float(v) for v in pos], out))
+        return out.as_array()
+
+    def compute_echo_criterion(self):
+        """echo criterion (Dietsch and Kraak, speech and music: ECHO_CRITERION_NAMES) of the last completed run, one forward
+        pass over its history on the device; returns the pass's device time in milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeEchoCriterion(self._h, C.byref(ms)))
+        return ms.value
+
+    def echo_criterion(self):
+        """float32 [gx, gy, 10] (ECHO_CRITERION_NAMES); NaN where the cell has no onset in the run they were computed for"""
+        out = np.empty((self.gx, self.gy, 10), np.float32)
+        _check(lib().PvAmdCopyEchoCriterion(self._h, _f(out)))
+        return out
+
+    def echo_criterion_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, 10] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, 10), np.float32)
+        _check(lib().PvAmdCopyEchoCriterionBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def echo_criterion_at(self, pos):
+        """float32 [10] at an emitter position (the cell get_output reads); ten NaNs off the map"""
+        out = PvAmdEchoCriterion()
+        _check(lib().PvAmdGetEchoCriterion(self._h, *[float(v) for v in pos], out))
         return out.as_array()
 
     def compute_lateral_fraction(self):

@@ -13,6 +13,7 @@
 #include "pv_core.h"
 #include "pv_bands.h"
 #include "pv_decay.h"
+#include "pv_echo.h"
 #include "pv_echogram.h"
 #include "pv_lateral.h"
 #include "pv_metrics.h"
@@ -1220,6 +1221,50 @@ int PvAmdGetLateralFraction(PvAmdSolver* h, float ex, float ey, float ez, PvAmdL
     return 0;
 } PV_API_CATCH(-1)
 
+// echo criterion (pv_echo.hip): single whole-grid solvers only, as the room metrics; every refusal says "echo: ..."
+static bool echoCritHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "echo: " + g_lastError;
+    return false;
+}
+
+int PvAmdComputeEchoCriterion(PvAmdSolver* h, float* ms) try {
+    if (!echoCritHandle(h)) return -1;
+    return ret(h, h->s->computeEchoCriterion(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyEchoCriterion(PvAmdSolver* h, float* out10) try {
+    if (!echoCritHandle(h)) return -1;
+    if (!out10) {
+        g_lastError = "echo: PvAmdCopyEchoCriterion: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyEchoCriterionBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out10));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyEchoCriterionBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out10) try {
+    if (!echoCritHandle(h)) return -1;
+    if (!out10) {
+        g_lastError = "echo: PvAmdCopyEchoCriterionBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyEchoCriterionBlock(r0, c0, nr, nc, out10));
+} PV_API_CATCH(-1)
+
+int PvAmdGetEchoCriterion(PvAmdSolver* h, float ex, float ey, float ez, PvAmdEchoCriterion* out) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!echoCritHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "echo: PvAmdGetEchoCriterion: null output";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdEchoCriterion) == kEchoFloats * sizeof(float), "ten floats");
+    float v[kEchoFloats];
+    if (!h->s->echoCriterionAt(ex, ez, v)) return ret(h, false);
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
 // echogram (pv_echogram.hip): single whole-grid solvers only, as the lateral fraction; every refusal says "echogram: ...".  The
 // setting is checked against the handle's own grid before anything else happens (pv_echogram.h echogramSlotOk, the rule
 // PvAmdHostEchogram applies too)
@@ -1761,6 +1806,22 @@ int PvAmdHostLateralFraction(const float* p, const float* vx, const float* vy, i
     static_assert(sizeof(PvAmdLateralFraction) == kLateralFloats * sizeof(float), "eleven floats");
     float v[kLateralFloats];
     lateralFractionOfIr(p, vx, vy, T, fs, onset, v);
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostEchoCriterion(const float* p, int T, int fs, int onset, PvAmdEchoCriterion* out) try {
+    if (!p || !out || T <= 0 || onset < 0 || onset >= T) {
+        g_lastError = "echo: PvAmdHostEchoCriterion: an impulse response p[T], T > 0, 0 <= onset < T and an output record";
+        return -1;
+    }
+    if (!echoFsOk(fs)) {
+        g_lastError = "echo: the sampling rate gives a speech lag below one step ((int)(0.009f * (float)fs) < 1)";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdEchoCriterion) == kEchoFloats * sizeof(float), "ten floats");
+    float v[kEchoFloats];
+    echoCriterionOfIr(p, T, fs, onset, v);
     std::memcpy(out, v, sizeof(*out));
     return 0;
 } PV_API_CATCH(-1)

@@ -155,6 +155,11 @@ void launchEchogram(const AnalyzeArgs& a, float* out, int ns, int nSlots, hipStr
 void launchBandMetrics(const AnalyzeArgs& a, const float* coefs, int n, float* out, hipStream_t stream);
 int bandMetricsBlock();
 
+// ---- pv_echo.hip: per-cell echo criterion (speech and music)
+// echo criterion of the last completed run (pv_echo.hip): out = kEchoFloats planes of a.histPlane floats, indexed by the cell's
+// offset inside a history plane; NaN where the cell has no onset in that run.  The caller has checked echoFsOk(a.fs)
+void launchEchoCriterion(const AnalyzeArgs& a, float* out, hipStream_t stream);
+
 // ---- pv_spectrum.hip: per-cell transfer functions at chosen frequencies
 // One pass over the history of the last completed run for `bins` bins held `block` to a lane (spectrumBlockOk(block); bins <=
 // block).  tab: the pass's twiddles on the device, row t = {cos, sin} pairs of its `block` bins (2 * block floats, bins past

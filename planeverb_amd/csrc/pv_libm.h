@@ -9,7 +9,8 @@
 //   * logf, powf: sysdeps/ieee754/flt-32/e_logf.c, e_powf.c + e_powf_log2_data.c, e_exp2f_data.c (ARM Optimized
 //     Routines, Szabolcs Nagy): 16-entry log tables, 32-entry exp2 table, polynomials evaluated in double.
 // tools/libm_check.cpp compares them with the host libm: every positive finite float for log10f (2 139 095 039
-// values) and every non-negative float for powf(x, 0.8f) (2 139 095 041 values) match bit for bit on this image.
+// values) and every non-negative float for powf(x, 0.8f) and powf(x, (float)(2.0 / 3.0)) (2 139 095 041 values each,
+// through pvPowf and through pvPowfNonNeg) match bit for bit on this image.
 // Must be compiled without FP contraction (-ffp-contract=off); results do not depend on it for these inputs (checked
 // both ways), but the step kernels need the flag anyway.
 //
@@ -305,5 +306,82 @@ PV_HD inline float pvPowf(float x, float y) {
     e = e * sc;
     return (float)e;
 }
+
+// The same function with its two tables behind a functor and without control flow, for the echo-criterion pass (pv_echo.hip),
+// which evaluates |p|^(2/3) once or twice per sample and lane: a per-lane index into a constant array is a global load at the
+// head of every evaluation's dependent chain, so the kernel keeps the 32 + 32 doubles in LDS (PvPowTabLds there).  Same domain
+// as pvPowf (x >= +0, inf and NaN included; y positive and finite with |y * log2(x)| < 126), the same operations in the same
+// order, NOTHING fused (unlike the logarithm above, the exp2 stage has not been checked with fused pairs), zero / inf / NaN and
+// the subnormal scaling as selects.  Bit-identical to pvPowf and to the host libm for y = 0.8f and y = (float)(2.0 / 3.0), every
+// non-negative float (tools/libm_check.cpp).
+struct PvPowTabConst {
+    PV_HD void log2(int i, double* invc, double* logc) const {
+        constexpr double LT[16][2] = {
+            {0x1.661ec79f8f3bep+0, -0x1.efec65b963019p-2}, {0x1.571ed4aaf883dp+0, -0x1.b0b6832d4fca4p-2},
+            {0x1.49539f0f010bp+0, -0x1.7418b0a1fb77bp-2},  {0x1.3c995b0b80385p+0, -0x1.39de91a6dcf7bp-2},
+            {0x1.30d190c8864a5p+0, -0x1.01d9bf3f2b631p-2}, {0x1.25e227b0b8eap+0, -0x1.97c1d1b3b7afp-3},
+            {0x1.1bb4a4a1a343fp+0, -0x1.2f9e393af3c9fp-3}, {0x1.12358f08ae5bap+0, -0x1.960cbbf788d5cp-4},
+            {0x1.0953f419900a7p+0, -0x1.a6f9db6475fcep-5}, {0x1p+0, 0x0p+0},
+            {0x1.e608cfd9a47acp-1, 0x1.338ca9f24f53dp-4},  {0x1.ca4b31f026aap-1, 0x1.476a9543891bap-3},
+            {0x1.b2036576afce6p-1, 0x1.e840b4ac4e4d2p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.40645f0c6651cp-2},
+            {0x1.886e6037841edp-1, 0x1.88e9c2c1b9ff8p-2},  {0x1.767dcf5534862p-1, 0x1.ce0a44eb17bccp-2}};
+        *invc = LT[i][0];
+        *logc = LT[i][1];
+    }
+    PV_HD uint64_t exp2(int j) const {
+        constexpr uint64_t ET[32] = {
+            0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
+            0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull,
+            0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull,
+            0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull,
+            0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
+            0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull,
+            0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
+            0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+        return ET[j];
+    }
+};
+
+template <class TabF>
+PV_HD inline float pvPowfNonNegT(float x, float y, const TabF& tab) {
+    const uint32_t ix0 = pvBitsF(x);
+    const bool odd = ix0 - 0x00800000u >= 0x7f800000u - 0x00800000u;  // zero, subnormal, inf, NaN
+    const bool square = 2u * ix0 - 1u >= 2u * 0x7f800000u - 1u;       // +0 -> 0, inf -> inf, NaN -> NaN (y > 0)
+    const uint32_t ixs = (pvBitsF(x * 0x1p23f) & 0x7fffffffu) - (23u << 23);  // subnormal: scaled up
+    const uint32_t ix = odd ? ixs : ix0;  // (zero / inf / NaN: the value computed from it is not used)
+    const uint32_t tmp = ix - 0x3f330000u;
+    const int i = (int)((tmp >> 19) & 15u);
+    const uint32_t top = tmp & 0xff800000u;
+    const uint32_t iz = ix - top;
+    const int k = (int)top >> 23;
+    double invc, logc;
+    tab.log2(i, &invc, &logc);
+    const double z = (double)pvFloatBits(iz);
+    const double r = z * invc - 1.0;
+    const double y0 = logc + (double)k;
+    const double r2 = r * r;
+    double yy = 0x1.27616c9496e0bp-2 * r + -0x1.71969a075c67ap-2;
+    const double p = 0x1.ec70a6ca7baddp-2 * r + -0x1.7154748bef6c8p-1;
+    const double r4 = r2 * r2;
+    double q = 0x1.71547652ab82bp+0 * r + y0;
+    q = p * r2 + q;
+    yy = yy * r4 + q;                       // log2(x)
+    const double xd = (double)y * yy;
+    double kd = xd + 0x1.8p+47;             // round to a multiple of 1/32
+    const uint64_t ki = __builtin_bit_cast(uint64_t, kd);
+    kd -= 0x1.8p+47;
+    const double rr = xd - kd;
+    uint64_t t = tab.exp2((int)(ki & 31ull));
+    t += ki << (52 - 5);
+    const double sc = __builtin_bit_cast(double, t);
+    const double zz = 0x1.c6af84b912394p-5 * rr + 0x1.ebfce50fac4f3p-3;
+    const double rr2 = rr * rr;
+    double e = 0x1.62e42ff0c52d6p-1 * rr + 1.0;
+    e = zz * rr2 + e;
+    e = e * sc;
+    return square ? x * x : (float)e;
+}
+
+PV_HD inline float pvPowfNonNeg(float x, float y) { return pvPowfNonNegT(x, y, PvPowTabConst{}); }
 
 }  // namespace pva

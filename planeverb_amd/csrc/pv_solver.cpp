@@ -20,6 +20,7 @@
 #include "pv_launch.h"
 #include "pv_bands.h"
 #include "pv_decay.h"
+#include "pv_echo.h"
 #include "pv_echogram.h"
 #include "pv_lateral.h"
 #include "pv_metrics.h"
@@ -710,6 +711,9 @@ Solver::~Solver() {
     if (echo_) hipFree(echo_);
     for (auto& e : echoEv_)
         if (e) hipEventDestroy(e);
+    if (echoCrit_) hipFree(echoCrit_);
+    for (auto& e : echoCritEv_)
+        if (e) hipEventDestroy(e);
     for (float* p : {specTab_, specPow_, spectrum_})
         if (p) hipFree(p);
     for (auto& e : spectrumEv_)
@@ -791,7 +795,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     return id;
 }
 
@@ -802,7 +806,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     return true;
 }
 
@@ -813,7 +817,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     return true;
 }
 
@@ -885,14 +889,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -1039,7 +1043,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     return true;
 }
 
@@ -1079,7 +1083,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     return true;
 }
 
@@ -2143,7 +2147,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;       // (the history the records were made from is about to be overwritten)
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     if (!applyGeometry()) return false;
     PathRun r;
@@ -3097,6 +3101,79 @@ bool Solver::decayTimesAt(float ex, float ez, float out8[8]) {
         return true;
     }
     return copyDecayTimesBlock(cx, cy, 1, 1, out8);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// echo criterion (pv_echo.hip): everything as the decay times above, with ten planes; refused where the speech lag is below a step
+// ----------------------------------------------------------------------------------------------------------------
+
+bool Solver::computeEchoCriterion(float* ms) {
+    if (isSlab()) return fail("echo: not available on a slab");
+    if (opt_.streaming) return fail("echo: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("echo: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    if (!echoFsOk((int)g_.fs)) return fail("echo: the sampling rate gives a speech lag below one step ((int)(0.009f * (float)fs) < 1)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("echo: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("echo: the last run ended in error");
+    if (!echoCrit_ && !dalloc(&echoCrit_, (size_t)kEchoFloats * (size_t)histPlane_, false)) return false;
+    for (auto& e : echoCritEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    echoCritValid_ = false;
+    echoCritHostValid_ = false;
+    hipEventRecord(echoCritEv_[0], stream_);
+    launchEchoCriterion(analyzeArgs(lastLx_, lastLz_), echoCrit_, stream_);
+    hipEventRecord(echoCritEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "echo criterion launch") || !hipOk(hipStreamSynchronize(stream_), "echo criterion sync")) return false;
+    if (ms) hipEventElapsedTime(ms, echoCritEv_[0], echoCritEv_[1]);
+    echoCritDyn_ = dynCur_;
+    echoCritValid_ = true;
+    return true;
+}
+
+bool Solver::fetchEchoCriterion() {
+    if (!echoCritValid_) return fail("echo: not computed for the last run and the current geometry (PvAmdComputeEchoCriterion)");
+    if (echoCritHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    echoCritHost_.resize((size_t)kEchoFloats * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(echoCritHost_.data(), echoCrit_, echoCritHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "echo criterion copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "echo criterion sync"))
+        return false;
+    echoCritHostValid_ = true;
+    return true;
+}
+
+bool Solver::copyEchoCriterionBlock(int r0, int c0, int nr, int nc, float* out10) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("echo: block outside the map");
+    if (!fetchEchoCriterion()) return false;
+    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
+    const int wr0 = echoCritDyn_.histRow0 - geo_.G, wc0 = echoCritDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out10 + ((size_t)r * nc + c) * kEchoFloats;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < kEchoFloats; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * echoCritDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < kEchoFloats; ++k) o[k] = echoCritHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::echoCriterionAt(float ex, float ez, float out10[10]) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!echoCritValid_) return fetchEchoCriterion();
+        for (int k = 0; k < kEchoFloats; ++k) out10[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copyEchoCriterionBlock(cx, cy, 1, 1, out10);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

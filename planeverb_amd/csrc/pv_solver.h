@@ -159,11 +159,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -276,6 +276,13 @@ public:
     bool computeEchogram(float* ms);
     bool copyEchogramBlock(int r0, int c0, int nr, int nc, float* out);
     bool echogramAt(float ex, float ez, float* out);
+    // Echo criterion (pv_echo.hip; include/planeverb_amd.h PvAmdEchoCriterion) of the last completed run: speech and music
+    // variant from one forward pass over its history; stream, synchronisation, lifetime and refusals as the room metrics', and
+    // refused where the sampling rate gives a speech lag below one step.  out10: nr x nc records of ten floats, NaN where the
+    // cell has no onset in that run
+    bool computeEchoCriterion(float* ms);
+    bool copyEchoCriterionBlock(int r0, int c0, int nr, int nc, float* out10);
+    bool echoCriterionAt(float ex, float ez, float out10[10]);
     // Band metrics (pv_bands.hip; include/planeverb_amd.h PvAmdBandMetrics): decay times and clarity of the last completed run per
     // octave or third-octave band set here; lifetime and refusals as the decay times', and a change of bands invalidates the
     // records.  setBands: the caller has validated the centres (pv_bands.h bandsError); n = 0 clears and frees; waits for a run
@@ -540,6 +547,15 @@ private:
     bool echoHostValid_ = false;
     hipEvent_t echoEv_[2] = {nullptr, nullptr};
     bool fetchEchogram();
+    // echo criterion: ten planes of histPlane_ floats, kept exactly as the room metrics' ten (allocated by the first
+    // computeEchoCriterion); echoCritValid_ follows metricsValid_, and no computation touches another's flag
+    float* echoCrit_ = nullptr;
+    bool echoCritValid_ = false;
+    DynParams echoCritDyn_{};
+    std::vector<float> echoCritHost_;
+    bool echoCritHostValid_ = false;
+    hipEvent_t echoCritEv_[2] = {nullptr, nullptr};
+    bool fetchEchoCriterion();
     // band metrics (pv_bands.h): the centres, their fraction and the 10 float32 coefficients per band on the host (the kernel takes
     // them as arguments); 12 n planes of histPlane_ floats -- band j at planes 12 j .. 12 j + 11 -- allocated by the first
     // computeBandMetrics and again when n changes.  bandsValid_ follows metricsValid_ and is also cleared by a change of bands; no
