@@ -1058,22 +1058,51 @@ def test_resolution_presets_and_tiny_grids_vs_oracle(pvlib, oracle, size, res, s
 def test_non_square_grid_closed_room(pvlib):
     """Non-square grids are inconsistent in the reference and are implemented here with stride gy+1
     throughout.  Property: a closed room is decoupled from the outside, so the same room gives identical per-emitter
-    outputs on a 25 x 25 m and on a 25 x 14.6 m / 14.6 x 25 m grid."""
+    outputs on a 25 x 25 m and on a 25 x 14.6 m / 14.6 x 25 m grid -- at every emitter of the golden record that lies on the grid
+    (the third, at x = 20.5 m, is off the 14.6 m wide one: the sentinel), and in every cell of the room's interior: all eight
+    members and the onset map.  (tests/test_gpu_non_square.py compares non-square grids with an independent reference.)"""
     room = golden("g71_bigroom")  # 10 m closed room in the corner of the 25 m grid
-    outs = []
+    outs, maps = [], []
     for sx, sy in ((25.0, 25.0), (25.0, 14.6), (14.6, 25.0)):
         with pvlib.Solver(sx, sy, 275) as s:
             assert s.gx == int(np.float32(sx) * (np.float32(1) / np.float32(s.dx)))
+            assert s.gy == int(np.float32(sy) * (np.float32(1) / np.float32(s.dx)))
             for b in room["boxes"]:
                 s.add_geometry(b)
             s.run(room["listener"])
-            outs.append(np.stack([s.get_output(e).as_array() for e in room["emitters"][:1]]))
+            outs.append(np.stack([s.get_output(e).as_array() for e in room["emitters"]]))
             res, delay = s.results()
-            assert res.shape == (s.gx, s.gy, 8)
+            assert res.shape == (s.gx, s.gy, 8) and delay.shape == (s.gx, s.gy)
+            maps.append((res, delay))
+    assert len(room["emitters"]) == 3 and [o.shape for o in outs] == [(3, 8)] * 3
     compare_output_arrays = lambda a, b: [same_bits(a[:, k], b[:, k]).all() for k in (0, 1, 4, 5, 6, 7)]
-    assert all(compare_output_arrays(outs[0], outs[1])) and all(compare_output_arrays(outs[0], outs[2]))
-    assert rel_err(outs[0][:, 2], outs[1][:, 2]).max() <= RT60_TOL
-    compare_output(type("O", (), {"as_array": lambda self: outs[0][0]})(), room["emitter_out"][0], "square")
+    assert all(compare_output_arrays(outs[0], outs[1])) and all(compare_output_arrays(outs[0][:2], outs[2][:2]))
+    assert rel_err(outs[0][:, 2], outs[1][:, 2]).max() <= RT60_TOL and rel_err(outs[0][:2, 2], outs[2][:2, 2]).max() <= RT60_TOL
+    assert rel_err(outs[0][:, 3], outs[1][:, 3]).max() <= LOWPASS_TOL and rel_err(outs[0][:2, 3], outs[2][:2, 3]).max() <= LOWPASS_TOL
+    assert outs[2][2, 0] == -1 and not outs[2][2, 1:].any()  # (off the 14.6 m wide grid)
+    for k in range(3):
+        compare_output(type("O", (), {"as_array": lambda self: outs[0][k]})(), room["emitter_out"][k], "square, emitter %d" % k)
+    # every cell of the room's interior: the cells with an onset, the same cell indices on all three grids
+    res0, delay0 = maps[0]
+    inside = delay0 < 1e30
+    xs, ys = np.nonzero(inside)
+    assert inside.sum() > 500 and xs.max() < 40 and ys.max() < 40  # (14.6 m are 40 cells)
+    assert same_bits(delay0, room["delay"]).all()
+    for (res, delay), name in zip(maps[1:], ("25 x 14.6", "14.6 x 25")):
+        sub = inside[:delay.shape[0], :delay.shape[1]]
+        assert np.array_equal(delay < 1e30, sub), name + ": the cells with an onset"
+        assert same_bits(delay[sub], delay0[inside]).all(), name + ": onset map"
+        for k, nm in enumerate(NAMES):
+            a, b = res[sub][:, k], res0[inside][:, k]
+            if k == 2:
+                assert rel_err(a, b).max() <= RT60_TOL, name + " rt60"
+            elif k == 3:
+                assert rel_err(a, b).max() <= LOWPASS_TOL, name + " lowpass"
+            else:
+                assert same_bits(a, b).all(), "%s %s: %d cells differ" % (name, nm, int((~same_bits(a, b)).sum()))
+        # outside the room nothing has an onset, and the listener direction (recomputed for every cell) is the square grid's
+        for k in (4, 5):
+            assert same_bits(res[..., k], res0[:delay.shape[0], :delay.shape[1], k]).all(), name + " " + NAMES[k]
 
 
 def test_listener_outside_grid_and_api_misc(pvlib):
