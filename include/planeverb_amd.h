@@ -793,8 +793,8 @@ PVA_EXPORT int PvAmdHostEchogram(const float* p, const float* vx, const float* v
  * layer get records like any other cell.
  * Device storage: 10 x 4 bytes per cell of the history window, allocated by the first call, freed with the solver.  The records
  * stay valid until the next run, geometry, boundary or layer change on that solver: PvAmdCopyEchoCriterion* /
- * PvAmdGetEchoCriterion then return -1 until computed again.  The echo criterion and the six other record kinds (room metrics,
- * spectrum, decay times, lateral fraction, echogram, band metrics) do not invalidate each other.
+ * PvAmdGetEchoCriterion then return -1 until computed again.  The echo criterion and the seven other record kinds (room metrics,
+ * spectrum, decay times, lateral fraction, echogram, lobes, band metrics) do not invalidate each other.
  * Refused (-1, nothing changed, PvAmdLastError says why, "echo: ..."): what the room metrics refuse (NULL, no completed run, a
  * last run that ended in error, sparse-emitter solvers, PVA_OPT_SKIP_ANALYSIS, slab groups and slab ranks), and a sampling rate
  * whose speech lag is below one step, (int)(0.009f * (float)fs) < 1, i.e. fs < 112. */
@@ -817,6 +817,89 @@ PVA_EXPORT int PvAmdGetEchoCriterion(PvAmdSolver* s, float ex, float ey, float e
 /* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T and a sampling rate the criterion
  * accepts (fs >= 112); the restatement the tests hold the kernel to */
 PVA_EXPORT int PvAmdHostEchoCriterion(const float* p, int T, int fs, int onset, PvAmdEchoCriterion* out);
+/* ---- Directional energy lobes: the energy of every reached cell per time window, split over four axial travel directions ----
+ * In which directions does the energy of a response travel, and when?  sourceDirectivity is one vector from the first
+ * milliseconds, the lateral fraction one scalar for the first 80 ms, and the echogram's flux is a NET vector per slot: two
+ * reflections that cross a cell from opposite sides within one slot cancel in it, and a diffuse tail has a net flux near 0
+ * whatever its directional balance.  The lobes keep opposite directions apart: each sample's energy p^2 is split over the x and
+ * the y axis by the squared direction cosines of the particle velocity (cos^2 weights, which add up to 1), and goes to the lobe
+ * of the sign in which the sound travels along that axis.  Four lobes, +x, -x, +y, -y, per time window; a few windows of unequal
+ * lengths after each cell's onset (direct, early, late by default).  PvAmdComputeLobes reduces the history of the LAST COMPLETED
+ * run to 1 + 5 nW floats per cell on the device (pv_lobes.hip), with the velocity recurrence of the lateral-fraction pass carried
+ * through the whole response.  It touches no run and no result map.
+ * Windows: nEdges edges in seconds, 0 <= nEdges <= PVA_LOBES_MAX_EDGES, with step counts
+ *   n_i = (int)(edge_i * (float)fs)            in float32 -- the expression of n5 / n80 above.
+ * Refused with -1 and nothing changed unless every edge is finite, n_0 >= 1, every n_i <= (1 << 20) and the n_i are strictly
+ * increasing.  nW = nEdges + 1 windows; with k = t - onset, window 0 is k < n_0, window j is n_(j-1) <= k < n_j, and the last
+ * window is k >= n_last, up to T - 1.  A solver on which no windows were ever set uses the default edges {0.01f, 0.08f}
+ * (direct, early, late); nEdges = 0 (edgesSeconds is then not read and may be NULL) restores that default, also in
+ * PvAmdHostLobes.
+ * Definition, for result cell s = X * gy + Y, with delay the run's own onset map and p(t), vx(t), vy(t) exactly what
+ * PvAmdGetImpulseResponse returns for array cell (X, Y) -- the library's velocity, the UNDAMPED recurrence of the lateral-fraction
+ * section above, started from 0 at the cell's first recorded sample:
+ *   onset = (int)delay[s]                      (FLT_MAX: not reached)
+ *   for t = onset .. T - 1,  k = t - onset,  w = the window k lies in:
+ *      e = p * p;   a = vx * vx;   b = vy * vy;   q = a + b
+ *      E[w] = E[w] + e
+ *      if (q > 0.0f) {
+ *         ex = e * (a / q);   ey = e * (b / q)
+ *         if ((vx > 0.0f) == (p > 0.0f)) XP[w] = XP[w] + ex;  else XN[w] = XN[w] + ex;
+ *         if ((vy > 0.0f) == (p > 0.0f)) YP[w] = YP[w] + ey;  else YN[w] = YN[w] + ey;
+ *      }
+ *   record (1 + 5 nW floats): n = (float)(T - onset), then E, XP, XN, YP, YN of window 0, of window 1, ...
+ * Everything is float32; every product, sum and quotient is rounded on its own (no FMA); division is correctly rounded; every
+ * sum starts at +0.0f and is sequential in increasing t.  Nothing else is special-cased: a sample with q == 0 adds to E only
+ * (the caller sees it as E - (XP + XN + YP + YN)), a window the response does not reach holds five +0.0f, and a NaN or Inf
+ * input propagates as IEEE says.  The sign test uses the signs of p and v, not the product p * v, so an underflowing product
+ * cannot move energy to the wrong lobe.
+ * Meaning: XP is the energy of window w carried by sound that TRAVELS towards +x at the cell (array rows; away from the
+ * listener's side of the path); like dir of the lateral fraction and the echogram's flux it is not negated.  By reciprocity --
+ * the run's source is the listener, so the response recorded at a cell is the response at the listener to an emitter at that
+ * cell -- it is the energy an emitter at the cell sends to the listener by radiating towards -x.  PvAmdLobeGains below uses
+ * that reading to apply an emitter's directivity pattern to the reverberant path, per window.
+ * Per window of N steps the four lobes add up to E within  |(XP + XN + YP + YN) - E| <= (N + 8) * 2^-23 * E  wherever no sample
+ * has q == 0: all terms are non-negative, each sample's ex + ey differs from e by a few ulp, and a sequential float32 sum of N
+ * non-negative terms has a relative error of at most N * 2^-24.
+ * A cell WITHOUT an onset in that run holds 1 + 5 nW quiet NaNs (0x7fc00000); nothing is carried over from earlier runs.
+ * Cells inside an edge layer get records like any other cell.
+ * Device storage: (1 + 5 nW) x 4 bytes per cell of the history window, allocated by the first compute call (again when nW
+ * changes), freed with the solver.  The records stay valid until the next run, a geometry, boundary or layer change, or a
+ * window-setting call on that solver: the copy and point calls then return -1 until computed again.  The lobes and the seven
+ * other record kinds (room metrics, spectrum, decay times, lateral fraction, echogram, echo criterion, band metrics) do not
+ * invalidate each other.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "lobes: ..."): NULL, no completed run, a last run that ended in error,
+ * sparse-emitter solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks, a block outside the
+ * map, and the default windows at a sampling rate below 100 Hz. */
+#define PVA_LOBES_MAX_EDGES 7
+/* Set the window edges (nEdges > 0) or restore the default (nEdges = 0); waits for a run in flight */
+PVA_EXPORT int PvAmdSetLobeWindows(PvAmdSolver* s, const float* edgesSeconds, int nEdges);
+/* returns nEdges; the edges as set (or the default) and their step counts to edgesSeconds[nEdges] and edgeSteps[nEdges] (both
+ * optional; room for PVA_LOBES_MAX_EDGES is always enough) */
+PVA_EXPORT int PvAmdGetLobeWindows(PvAmdSolver* s, float* edgesSeconds, int* edgeSteps);
+/* Compute the lobe records of the LAST COMPLETED run of s (waits for a run in flight; works after every form of run, as
+ * PvAmdComputeEchogram).  Synchronous on the solver's own stream.  *ms (optional): device time of the pass. */
+PVA_EXPORT int PvAmdComputeLobes(PvAmdSolver* s, float* ms);
+/* gx*gy*(1+5nW) floats, AoS records, cell s = X*gy + Y */
+PVA_EXPORT int PvAmdCopyLobes(PvAmdSolver* s, float* out);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records, row-major */
+PVA_EXPORT int PvAmdCopyLobesBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out);
+/* the record (1+5nW floats) at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map
+ * gives NaNs and 0 */
+PVA_EXPORT int PvAmdGetLobes(PvAmdSolver* s, float ex, float ey, float ez, float* out);
+/* CPU only: the definition above applied to one impulse response p[T], vx[T], vy[T] with 0 <= onset < T, fs > 0 and edges that
+ * the window-setting call would accept at that fs (refused otherwise); out: 1 + 5 (nEdges + 1) floats (16 for nEdges = 0, the
+ * default edges); the restatement the tests hold the kernel to */
+PVA_EXPORT int PvAmdHostLobes(const float* p, const float* vx, const float* vy, int T, int fs, int onset,
+                              const float* edgesSeconds, int nEdges, float* out);
+/* CPU only: an emitter's directivity pattern applied to the reverberant path, per window of one lobe record (1 + 5 nWindows
+ * floats).  pattern 0 = omni, 1 = cardioid; (fwdX, fwdY) is the emitter's forward in the (x, z) plane, used as given (the caller
+ * normalises it).  In float32, each operation rounded on its own:
+ *   c(d)  = pattern == 0 ? 1.0f : max((1.0f + d) / 2.0f, 0.01f)
+ *   wXP = c(-fwdX),  wXN = c(fwdX),  wYP = c(-fwdY),  wYN = c(fwdY)         (emission direction = minus travel direction)
+ *   gains[w] = ((((XP * (wXP*wXP)) + (XN * (wXN*wXN))) + (YP * (wYP*wYP))) + (YN * (wYN*wYN))) / (((XP + XN) + YP) + YN)
+ * gains[w] is an ENERGY ratio; the amplitude factor is its square root and is left to the caller.  0 / 0 gives NaN as IEEE says
+ * (a window without directional energy).  Refused (-1) for NULL, nWindows outside 1 .. 8, or a pattern other than 0 / 1. */
+PVA_EXPORT int PvAmdLobeGains(const float* record, int nWindows, float fwdX, float fwdY, int pattern, float* gains);
 /* ---- Band metrics: decay times and clarity of every reached cell per octave or third-octave band ----
  * The records above are broadband: the decay of a cell is that of whichever part of the pulse's band decays slowest there.
  * PvAmdComputeBandMetrics filters each reached cell's recorded pressure into the bands set by PvAmdSetBands and reduces every

@@ -51,6 +51,11 @@ def main(argv=None):
     ap.add_argument("--echo-criterion", action="store_true",
                     help="add the echo criterion (Dietsch and Kraak: EK, its delay, the late EK, its delay and Ts, for speech "
                          "and for music) of each emitter's cell")
+    ap.add_argument("--lobes", metavar="SECONDS[,SECONDS...]", nargs="?", const=[], default=None,
+                    type=lambda v: [float(x) for x in v.split(",")],
+                    help="add the directional energy lobes of each emitter's cell: per time window after the onset the energy and "
+                         "its split over the travel directions +x, -x, +y, -y; the window edges in seconds, e.g. 0.005,0.02,0.08 "
+                         "(bare flag: 0.01,0.08)")
     ap.add_argument("--spectrum", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the transfer function (re, im, level in dB re the source) of each emitter's cell at these frequencies")
     ap.add_argument("--bands", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
@@ -88,6 +93,9 @@ def main(argv=None):
         if a.echogram:
             s.set_echogram(*a.echogram)
             s.compute_echogram()
+        if a.lobes is not None:
+            s.set_lobe_windows(a.lobes)
+            s.compute_lobes()
         if a.bands:
             s.set_bands(a.bands, a.band_fraction)
             s.compute_band_metrics()
@@ -118,6 +126,10 @@ def main(argv=None):
                 out["emitters"][-1]["echogram"] = {"slotSteps": s.echogram_slots()[2], "n": float(m[0]),
                                                    "e": [float(v) for v in m[1::3]], "ix": [float(v) for v in m[2::3]],
                                                    "iy": [float(v) for v in m[3::3]]}
+            if a.lobes is not None:
+                m = s.lobes_at(e)
+                out["emitters"][-1]["lobes"] = {"n": float(m[0]), "windows": [
+                    dict((n, float(v)) for n, v in zip(api.LOBE_NAMES, m[1 + 5 * w:6 + 5 * w])) for w in range((len(m) - 1) // 5)]}
             if a.bands:
                 m = s.band_metrics_at(e)
                 out["emitters"][-1]["bandMetrics"] = [

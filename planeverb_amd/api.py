@@ -297,6 +297,14 @@ SYMBOLS = {
     "PvAmdCopyEchogramBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "PvAmdGetEchogram": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
     "PvAmdHostEchogram": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _fp]),
+    "PvAmdSetLobeWindows": (C.c_int, [_vp, _fp, C.c_int]),
+    "PvAmdGetLobeWindows": (C.c_int, [_vp, _fp, C.POINTER(C.c_int)]),
+    "PvAmdComputeLobes": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyLobes": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyLobesBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetLobes": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
+    "PvAmdHostLobes": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
+    "PvAmdLobeGains": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, C.c_int, _fp]),
     "PvAmdSetBands": (C.c_int, [_vp, _fp, C.c_int, C.c_int]),
     "PvAmdGetBands": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(C.c_int)]),
     "PvAmdGetBandCoefs": (C.c_int, [_vp, _fp]),
@@ -787,6 +795,43 @@ def host_echogram(p, vx, vy, fs, onset, slot_seconds, n_slots):
     ptr = [_f(v) if v.size else None for v in (a, x, y)]
     _check(lib().PvAmdHostEchogram(ptr[0], ptr[1], ptr[2], int(a.size), int(fs), int(onset), float(slot_seconds), int(n_slots),
                                    _f(out)))
+    return out
+
+
+LOBES_MAX_EDGES = 7  # PVA_LOBES_MAX_EDGES
+LOBES_DEFAULT_EDGES = (0.01, 0.08)
+LOBE_NAMES = ("e", "xp", "xn", "yp", "yn")
+LOBE_PATTERN_OMNI, LOBE_PATTERN_CARDIOID = 0, 1
+
+
+def _lobe_edges(edges):
+    e = np.ascontiguousarray(() if edges is None else edges, np.float32).reshape(-1)
+    return e, (_f(e) if e.size else None)
+
+
+def host_lobes(p, vx, vy, fs, onset, edges=None):
+    """PvAmdHostLobes: float32 [1 + 5 nW] (n, then LOBE_NAMES per window) of one impulse response p[T] with its velocities vx[T],
+    vy[T] and its onset step, for the window edges given in seconds (None or empty: the default, 10 ms and 80 ms) -- the
+    definition of include/planeverb_amd.h (PvAmdSetLobeWindows) on the CPU"""
+    a, x, y = (np.ascontiguousarray(v, np.float32).reshape(-1) for v in (p, vx, vy))
+    if not (a.size == x.size == y.size):
+        raise ValueError("host_lobes: p, vx and vy must have the same length")
+    e, ep = _lobe_edges(edges)
+    out = np.empty(1 + 5 * ((e.size or 2) + 1), np.float32)
+    ptr = [_f(v) if v.size else None for v in (a, x, y)]
+    _check(lib().PvAmdHostLobes(ptr[0], ptr[1], ptr[2], int(a.size), int(fs), int(onset), ep, int(e.size), _f(out)))
+    return out
+
+
+def lobe_gains(record, forward, pattern=LOBE_PATTERN_CARDIOID):
+    """PvAmdLobeGains: float32 [nW], the energy ratio by which an emitter with the directivity `pattern` (0 omni, 1 cardioid)
+    facing `forward` = (x, z), used as given, changes each window of the lobe record [1 + 5 nW] of its cell"""
+    r = np.ascontiguousarray(record, np.float32).reshape(-1)
+    if r.size < 6 or (r.size - 1) % 5:
+        raise ValueError("lobe_gains: a record of 1 + 5 nW floats")
+    nw = (r.size - 1) // 5
+    out = np.empty(nw, np.float32)
+    _check(lib().PvAmdLobeGains(_f(r), nw, float(forward[0]), float(forward[1]), int(pattern), _f(out)))
     return out
 
 
@@ -1599,6 +1644,51 @@ class Solver:
         """float32 [1 + 3 n] at an emitter position (the cell get_output reads); NaNs off the map"""
         out = np.empty(1 + 3 * self.echogram_slots()[0], np.float32)
         _check(lib().PvAmdGetEchogram(self._h, *[float(v) for v in pos], _f(out)))
+        return out
+
+    def set_lobe_windows(self, edges=None):
+        """the time windows compute_lobes sums into, by their edges in seconds after every cell's own onset (at most
+        LOBES_MAX_EDGES, step counts (int)(edge * fs) strictly increasing from 1 on); None or empty restores the default,
+        10 ms and 80 ms: direct, early, late"""
+        e, ep = _lobe_edges(edges)
+        _check(lib().PvAmdSetLobeWindows(self._h, ep, int(e.size)))
+
+    def lobe_windows(self):
+        """(edges_seconds, edge_steps): the window edges in force, float32 [nE] and int32 [nE]; nW = nE + 1 windows"""
+        sec, steps = np.zeros(LOBES_MAX_EDGES, np.float32), np.zeros(LOBES_MAX_EDGES, np.int32)
+        n = lib().PvAmdGetLobeWindows(self._h, _f(sec), steps.ctypes.data_as(C.POINTER(C.c_int)))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return sec[:n].copy(), steps[:n].copy()
+
+    def _lobe_floats(self):
+        return 1 + 5 * (len(self.lobe_windows()[0]) + 1)
+
+    def compute_lobes(self):
+        """directional energy lobes of the last completed run for the windows of set_lobe_windows: the energy p^2 of every
+        reached cell per window and its split over the travel directions +x, -x, +y, -y, the velocity by the stencil's recurrence,
+        on the device; returns the pass's device time in milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeLobes(self._h, C.byref(ms)))
+        return ms.value
+
+    def lobes(self):
+        """float32 [gx, gy, 1 + 5 nW]: n = the steps of the response, then LOBE_NAMES (e, xp, xn, yp, yn) of each window; NaN
+        where the cell has no onset in the run they were computed for.  xp is the energy that travels towards +x at the cell"""
+        out = np.empty((self.gx, self.gy, self._lobe_floats()), np.float32)
+        _check(lib().PvAmdCopyLobes(self._h, _f(out)))
+        return out
+
+    def lobes_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, 1 + 5 nW] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, self._lobe_floats()), np.float32)
+        _check(lib().PvAmdCopyLobesBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def lobes_at(self, pos):
+        """float32 [1 + 5 nW] at an emitter position (the cell get_output reads); NaNs off the map"""
+        out = np.empty(self._lobe_floats(), np.float32)
+        _check(lib().PvAmdGetLobes(self._h, *[float(v) for v in pos], _f(out)))
         return out
 
     def set_bands(self, hz, fraction=1):

@@ -16,6 +16,7 @@
 #include "pv_echo.h"
 #include "pv_echogram.h"
 #include "pv_lateral.h"
+#include "pv_lobes.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
@@ -1332,6 +1333,66 @@ int PvAmdGetEchogram(PvAmdSolver* h, float ex, float ey, float ez, float* out) t
     return ret(h, h->s->echogramAt(ex, ez, out));
 } PV_API_CATCH(-1)
 
+// lobes (pv_lobes.hip): single whole-grid solvers only, as the echogram; every refusal says "lobes: ...".  The edges are checked
+// against the handle's own grid before anything else happens (pv_lobes.h lobesEdgeSteps, the rule PvAmdHostLobes applies too)
+static bool lobesHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "lobes: " + g_lastError;
+    return false;
+}
+
+int PvAmdSetLobeWindows(PvAmdSolver* h, const float* edgesSeconds, int nEdges) try {
+    if (!h) {
+        g_lastError = "lobes: null solver handle";
+        return -1;
+    }
+    LobeEdges ed;
+    if (nEdges != 0 && !lobesEdgeSteps(edgesSeconds, nEdges, (int)h->spec.fs, &ed)) {
+        g_lastError = kLobesEdgesError;
+        return -1;
+    }
+    if (!lobesHandle(h)) return -1;
+    return ret(h, h->s->setLobeWindows(edgesSeconds, nEdges));
+} PV_API_CATCH(-1)
+
+int PvAmdGetLobeWindows(PvAmdSolver* h, float* edgesSeconds, int* edgeSteps) try {
+    if (!lobesHandle(h)) return -1;
+    return h->s->lobeWindows(edgesSeconds, edgeSteps);
+} PV_API_CATCH(-1)
+
+int PvAmdComputeLobes(PvAmdSolver* h, float* ms) try {
+    if (!lobesHandle(h)) return -1;
+    return ret(h, h->s->computeLobes(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyLobes(PvAmdSolver* h, float* out) try {
+    if (!lobesHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "lobes: PvAmdCopyLobes: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyLobesBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyLobesBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out) try {
+    if (!lobesHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "lobes: PvAmdCopyLobesBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyLobesBlock(r0, c0, nr, nc, out));
+} PV_API_CATCH(-1)
+
+int PvAmdGetLobes(PvAmdSolver* h, float ex, float ey, float ez, float* out) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!lobesHandle(h)) return -1;
+    if (!out) {
+        g_lastError = "lobes: PvAmdGetLobes: null output";
+        return -1;
+    }
+    return ret(h, h->s->lobesAt(ex, ez, out));
+} PV_API_CATCH(-1)
+
 // band metrics (pv_bands.hip): single whole-grid solvers only, as the decay times; every refusal says "band metrics: ...".  The
 // bands are checked against the handle's own grid before anything else happens (pv_bands.h bandsError, the rule
 // PvAmdHostBandCoefs applies too)
@@ -1839,6 +1900,35 @@ int PvAmdHostEchogram(const float* p, const float* vx, const float* vy, int T, i
         return -1;
     }
     echogramOfIr(p, vx, vy, T, onset, echogramSlotSteps(slotSeconds, fs), nSlots, out);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostLobes(const float* p, const float* vx, const float* vy, int T, int fs, int onset, const float* edgesSeconds, int nEdges,
+                   float* out) try {
+    if (!p || !vx || !vy || !out || T <= 0 || onset < 0 || onset >= T || fs <= 0) {
+        g_lastError =
+            "lobes: PvAmdHostLobes: an impulse response p[T], vx[T], vy[T], T > 0, fs > 0, 0 <= onset < T and an output of 1 + 5 nW floats";
+        return -1;
+    }
+    if (nEdges == 0) {
+        edgesSeconds = kLobesDefaultEdges;
+        nEdges = 2;
+    }
+    LobeEdges ed;
+    if (!lobesEdgeSteps(edgesSeconds, nEdges, fs, &ed)) {
+        g_lastError = kLobesEdgesError;
+        return -1;
+    }
+    lobesOfIr(p, vx, vy, T, onset, ed, nEdges, out);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdLobeGains(const float* record, int nWindows, float fwdX, float fwdY, int pattern, float* gains) try {
+    if (!record || !gains || nWindows < 1 || nWindows > kLobesMaxWindows || (pattern != 0 && pattern != 1)) {
+        g_lastError = "lobes: PvAmdLobeGains: a record of 1 + 5 nWindows floats, 1 <= nWindows <= 8, pattern 0 (omni) or 1 (cardioid)";
+        return -1;
+    }
+    lobeGainsOfRecord(record, nWindows, fwdX, fwdY, pattern, gains);
     return 0;
 } PV_API_CATCH(-1)
 

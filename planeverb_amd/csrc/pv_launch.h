@@ -147,6 +147,14 @@ void launchLateralFraction(const AnalyzeArgs& a, float* out, hipStream_t stream)
 // offset inside a history plane; NaN where the cell has no onset in that run.  Whole-grid solvers only, as the lateral fraction
 void launchEchogram(const AnalyzeArgs& a, float* out, int ns, int nSlots, hipStream_t stream);
 
+// ---- pv_lobes.hip: per-cell directional energy lobes
+// lobe records of the last completed run (pv_lobes.hip) for nW windows (1 .. kLobesMaxWindows) whose nW - 1 edges in steps are
+// ed.n[0 .. nW - 2], strictly increasing, the other entries INT_MAX (pv_lobes.h lobesEdgeSteps): out = 1 + 5 nW planes of
+// a.histPlane floats (n, then E, XP, XN, YP, YN of window j at planes 1 + 5 j ..), indexed by the cell's offset inside a history
+// plane; NaN where the cell has no onset in that run.  Whole-grid solvers only, as the echogram
+struct LobeEdges;
+void launchLobes(const AnalyzeArgs& a, float* out, const LobeEdges& ed, int nW, hipStream_t stream);
+
 // ---- pv_bands.hip: per-cell, per-band decay times and clarity
 // band records of the last completed run (pv_bands.hip) for n bands: coefs = n x kBandCoefs floats on the HOST (they travel as
 // kernel arguments), out = n x kBandFloats planes of a.histPlane floats (band j, float k at plane j * kBandFloats + k), indexed by

@@ -23,6 +23,7 @@
 #include "pv_echo.h"
 #include "pv_echogram.h"
 #include "pv_lateral.h"
+#include "pv_lobes.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
 
@@ -711,6 +712,9 @@ Solver::~Solver() {
     if (echo_) hipFree(echo_);
     for (auto& e : echoEv_)
         if (e) hipEventDestroy(e);
+    if (lobes_) hipFree(lobes_);
+    for (auto& e : lobesEv_)
+        if (e) hipEventDestroy(e);
     if (echoCrit_) hipFree(echoCrit_);
     for (auto& e : echoCritEv_)
         if (e) hipEventDestroy(e);
@@ -795,7 +799,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     return id;
 }
 
@@ -806,7 +810,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     return true;
 }
 
@@ -817,7 +821,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     return true;
 }
 
@@ -889,14 +893,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -1043,7 +1047,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     return true;
 }
 
@@ -1083,7 +1087,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     return true;
 }
 
@@ -2147,7 +2151,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;       // (the history the records were made from is about to be overwritten)
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     if (!applyGeometry()) return false;
     PathRun r;
@@ -3358,6 +3362,118 @@ bool Solver::echogramAt(float ex, float ez, float* out) {
         return true;
     }
     return copyEchogramBlock(cx, cy, 1, 1, out);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// directional energy lobes (pv_lobes.hip): everything as the echogram above, with 1 + 5 nW planes; the windows are never unset,
+// a solver that was given none uses the default edges
+// ----------------------------------------------------------------------------------------------------------------
+
+bool Solver::setLobeWindows(const float* edgesSeconds, int nEdges) {
+    if (isSlab()) return fail("lobes: not available on a slab");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    lobesValid_ = false;
+    lobesHostValid_ = false;
+    if (nEdges == 0) {
+        edgesSeconds = kLobesDefaultEdges;
+        nEdges = 2;
+    }
+    for (int i = 0; i < kLobesMaxEdges; ++i) lobeEdges_[i] = i < nEdges ? edgesSeconds[i] : 0.f;
+    lobeEdgeCount_ = nEdges;
+    return true;
+}
+
+int Solver::lobeWindows(float* edgesSeconds, int* edgeSteps) const {
+    LobeEdges ed;
+    const bool ok = lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, (int)g_.fs, &ed);  // (false: the default at an fs below 100)
+    for (int i = 0; i < lobeEdgeCount_; ++i) {
+        if (edgesSeconds) edgesSeconds[i] = lobeEdges_[i];
+        if (edgeSteps) edgeSteps[i] = ok ? ed.n[i] : 0;
+    }
+    return lobeEdgeCount_;
+}
+
+bool Solver::computeLobes(float* ms) {
+    if (isSlab()) return fail("lobes: not available on a slab");
+    if (opt_.streaming) return fail("lobes: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("lobes: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    LobeEdges ed;
+    if (!lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, (int)g_.fs, &ed))
+        return fail("lobes: the default windows (10 ms, 80 ms) need a sampling rate of 100 Hz or more (PvAmdSetLobeWindows)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("lobes: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("lobes: the last run ended in error");
+    const int nW = lobeEdgeCount_ + 1, nf = lobesFloats(nW);
+    if (lobes_ && lobesPlanes_ != nf) {
+        hipFree(lobes_);
+        lobes_ = nullptr;
+    }
+    if (!lobes_) {
+        if (!dalloc(&lobes_, (size_t)nf * (size_t)histPlane_, false)) return false;
+        lobesPlanes_ = nf;
+    }
+    for (auto& e : lobesEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    lobesValid_ = false;
+    lobesHostValid_ = false;
+    hipEventRecord(lobesEv_[0], stream_);
+    launchLobes(analyzeArgs(lastLx_, lastLz_), lobes_, ed, nW, stream_);
+    hipEventRecord(lobesEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "lobes launch") || !hipOk(hipStreamSynchronize(stream_), "lobes sync")) return false;
+    if (ms) hipEventElapsedTime(ms, lobesEv_[0], lobesEv_[1]);
+    lobesDyn_ = dynCur_;
+    lobesValid_ = true;
+    return true;
+}
+
+bool Solver::fetchLobes() {
+    if (!lobesValid_)
+        return fail("lobes: not computed for the last run, the current geometry and the current windows (PvAmdComputeLobes)");
+    if (lobesHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    lobesHost_.resize((size_t)lobesPlanes_ * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(lobesHost_.data(), lobes_, lobesHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "lobes copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "lobes sync"))
+        return false;
+    lobesHostValid_ = true;
+    return true;
+}
+
+bool Solver::copyLobesBlock(int r0, int c0, int nr, int nc, float* out) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("lobes: block outside the map");
+    if (!fetchLobes()) return false;
+    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
+    const int wr0 = lobesDyn_.histRow0 - geo_.G, wc0 = lobesDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const int nf = lobesPlanes_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < nf; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * lobesDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < nf; ++k) o[k] = lobesHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::lobesAt(float ex, float ez, float* out) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!fetchLobes()) return false;
+        for (int k = 0; k < lobesPlanes_; ++k) out[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copyLobesBlock(cx, cy, 1, 1, out);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

@@ -159,11 +159,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -276,6 +276,16 @@ public:
     bool computeEchogram(float* ms);
     bool copyEchogramBlock(int r0, int c0, int nr, int nc, float* out);
     bool echogramAt(float ex, float ez, float* out);
+    // Directional energy lobes (pv_lobes.hip; include/planeverb_amd.h PvAmdSetLobeWindows): the energy of the last completed run
+    // per time window after each cell's onset, split over the travel directions +x, -x, +y, -y; lifetime and refusals as the
+    // echogram's, and a change of windows invalidates the records.  setLobeWindows: the caller has validated the edges
+    // (pv_lobes.h lobesEdgeSteps); nEdges = 0 restores the default; waits for a run in flight.  out: nr x nc records of
+    // 1 + 5 nW floats, NaN where the cell has no onset in that run
+    bool setLobeWindows(const float* edgesSeconds, int nEdges);
+    int lobeWindows(float* edgesSeconds, int* edgeSteps) const;
+    bool computeLobes(float* ms);
+    bool copyLobesBlock(int r0, int c0, int nr, int nc, float* out);
+    bool lobesAt(float ex, float ez, float* out);
     // Echo criterion (pv_echo.hip; include/planeverb_amd.h PvAmdEchoCriterion) of the last completed run: speech and music
     // variant from one forward pass over its history; stream, synchronisation, lifetime and refusals as the room metrics', and
     // refused where the sampling rate gives a speech lag below one step.  out10: nr x nc records of ten floats, NaN where the
@@ -556,6 +566,19 @@ private:
     bool echoCritHostValid_ = false;
     hipEvent_t echoCritEv_[2] = {nullptr, nullptr};
     bool fetchEchoCriterion();
+    // lobes (pv_lobes.h): the window edges as given (the default until some are set); 1 + 5 nW planes of histPlane_ floats -- n, then
+    // E, XP, XN, YP, YN of window j at planes 1 + 5 j .. -- allocated by the first computeLobes and again when nW changes.
+    // lobesValid_ follows metricsValid_ and is also cleared by a change of the windows; no computation touches another's flag
+    float lobeEdges_[7] = {0.01f, 0.08f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int lobeEdgeCount_ = 2;
+    float* lobes_ = nullptr;
+    int lobesPlanes_ = 0;  // 1 + 5 nW of the allocation
+    bool lobesValid_ = false;
+    DynParams lobesDyn_{};
+    std::vector<float> lobesHost_;
+    bool lobesHostValid_ = false;
+    hipEvent_t lobesEv_[2] = {nullptr, nullptr};
+    bool fetchLobes();
     // band metrics (pv_bands.h): the centres, their fraction and the 10 float32 coefficients per band on the host (the kernel takes
     // them as arguments); 12 n planes of histPlane_ floats -- band j at planes 12 j .. 12 j + 11 -- allocated by the first
     // computeBandMetrics and again when n changes.  bandsValid_ follows metricsValid_ and is also cleared by a change of bands; no
