@@ -526,6 +526,39 @@ PVA_EXPORT int PvAmdGetOutput(PvAmdSolver* s, float ex, float ey, float ez, Plan
  * reference's sentinel (occlusion = -1, the rest 0).  Setting queries waits for a run in flight. */
 PVA_EXPORT int PvAmdSetOutputQueries(PvAmdSolver* s, const float* xyz, int n);
 PVA_EXPORT int PvAmdGetQueriedOutputs(PvAmdSolver* s, PlaneverbOutput* out, int n);
+/* Query records: the per-cell analysis records further down (room metrics, decay times, lateral fraction, echogram, echo
+ * criterion, lobes) for the cells of the registered output queries, computed INSIDE the run.  `kinds` is a mask of PVA_QREC_*.
+ * Every FOLLOWING run of any form (PvAmdRun, PvAmdRunAsync, PvAmdRunAsyncAfter, a member of PvAmdRunBatch, a run that PvAmdSync
+ * repeats) computes the selected kinds for the queries' cells with ONE launch on the solver's stream, behind the run's analysis
+ * and in front of its last kernel, straight into pinned host memory: no pass over the history window, no per-cell device
+ * storage (the pinned block holds at most 64 x the sum of the kinds' floats x 4 bytes), no host synchronisation.
+ * PvAmdGetQueriedRecords waits for the run as PvAmdGetQueriedOutputs does and then copies ONE kind's records from pinned memory
+ * without GPU work: nQueries x PvAmdQueryRecordFloats(kind) floats, one record after the other in query order.
+ *   A record is bit for bit what PvAmdGet<Kind>(s, position) returns after PvAmdCompute<Kind> on the same run: the same
+ * definition, the same cell mapping.  A query off the map gives NaNs, and so does a query whose cell has no onset in that run;
+ * the call returns 0 for them, as PvAmdGet<Kind> does.  The echogram slots and lobe windows are those in force when the run was
+ * enqueued (PvAmdSetEchogram and PvAmdSetLobeWindows wait for a run in flight) and the record sizes follow them; selecting
+ * PVA_QREC_ECHOGRAM with no slots set is refused, and so is PvAmdSetEchogram(.., 0) while it is selected.  In-run records and
+ * the whole-map records (PvAmdCompute<Kind>) do not invalidate each other.
+ *   kinds = 0, the default, clears the selection and frees the pinned block: nothing is launched, recorded or allocated, and a
+ * run's launches are exactly those of a solver that never called this.  PvAmdSetQueryRecords and PvAmdSetOutputQueries wait
+ * for a run in flight (the launch reads the cell table).
+ *   Refused with -1 and nothing changed, PvAmdLastError "query records: ...": an unknown bit; sparse-emitter
+ * (PVA_OPT_STREAMING_ANALYSIS) solvers; PVA_OPT_SKIP_ANALYSIS; slab groups and slab ranks; PVA_QREC_ECHO_CRITERION at a
+ * sampling rate below 112 Hz; PVA_QREC_LOBES with the default windows at a sampling rate below 100 Hz.
+ * PvAmdGetQueriedRecords is refused when the kind is not selected (or is not exactly one bit), nQueries differs from the
+ * registered count, no run has completed since the kinds, the queries or the kind's settings changed, or the last run ended in
+ * error.  PvAmdQueryRecordFloats: floats per query of ONE kind under the current settings, -1 where it has none. */
+#define PVA_QREC_ROOM_METRICS   1u    /* PvAmdRoomMetrics      10 floats */
+#define PVA_QREC_DECAY_TIMES    2u    /* PvAmdDecayTimes        8 floats */
+#define PVA_QREC_LATERAL        4u    /* PvAmdLateralFraction  11 floats */
+#define PVA_QREC_ECHOGRAM       8u    /* 1 + 3 nSlots floats   (PvAmdSetEchogram) */
+#define PVA_QREC_ECHO_CRITERION 16u   /* PvAmdEchoCriterion    10 floats */
+#define PVA_QREC_LOBES          32u   /* 1 + 5 nWindows floats (PvAmdSetLobeWindows; default windows when never set) */
+PVA_EXPORT int PvAmdSetQueryRecords(PvAmdSolver* s, unsigned kinds);
+PVA_EXPORT unsigned PvAmdGetQueryRecordKinds(PvAmdSolver* s);
+PVA_EXPORT int PvAmdQueryRecordFloats(PvAmdSolver* s, unsigned kind);
+PVA_EXPORT int PvAmdGetQueriedRecords(PvAmdSolver* s, unsigned kind, float* out, int nQueries);
 /* Whole result map: res8 = gx*gy*8 floats in AnalyzerResult order (Analyzer.h:13-21), delay = gx*gy */
 PVA_EXPORT int PvAmdCopyResults(PvAmdSolver* s, float* res8, float* delay);
 /* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records / onsets, row-major (either may be NULL) */

@@ -62,6 +62,10 @@ def main(argv=None):
                     help="add the band metrics (decay times and clarity of the band-filtered response) of each emitter's cell for "
                          "the bands centred at these frequencies")
     ap.add_argument("--band-fraction", type=int, default=1, choices=(1, 3), help="octave (1, default) or third-octave (3) bands")
+    ap.add_argument("--in-run-records", action="store_true",
+                    help="take the room metrics, decay times, lateral fraction, echogram, echo criterion and lobes from records "
+                         "computed inside the run for the emitters' cells (at most 64 emitters) instead of from whole-map passes "
+                         "after it; the output is the same")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
@@ -75,25 +79,39 @@ def main(argv=None):
         dx = np.float32(343.21) / np.float32(a.res) / np.float32(3.5)
         size = float((a.cells + 0.5) * dx)
     emitters = a.emitter or [(5.0, 0.0, 6.0)]
+    if a.in_run_records and len(emitters) > 64:
+        ap.error("--in-run-records: at most 64 emitters (a run's output queries)")
     with api.Solver(size, size, a.res, device=a.device) as s:
         for b in boxes:
             s.add_geometry(b)
+        whole = not a.in_run_records  # the six record kinds from whole-map passes after the run, or from inside the run
+        if not whole:
+            kinds = ((api.QREC_ROOM_METRICS if a.room_metrics else 0) | (api.QREC_DECAY_TIMES if a.decay_times else 0) |
+                     (api.QREC_LATERAL if a.lateral_fraction else 0) | (api.QREC_ECHOGRAM if a.echogram else 0) |
+                     (api.QREC_ECHO_CRITERION if a.echo_criterion else 0) | (api.QREC_LOBES if a.lobes is not None else 0))
+            if a.echogram:
+                s.set_echogram(*a.echogram)
+            if a.lobes is not None:
+                s.set_lobe_windows(a.lobes)
+            s.set_output_queries(emitters)
+            s.set_query_records(kinds)
         s.run(a.listener)
+        qrec = {} if whole else dict((k, s.queried_records(k)) for k in (1, 2, 4, 8, 16, 32) if kinds & k)
         t = s.timings()
         out = {"scene": a.scene, "grid": [s.gx, s.gy], "T": s.T, "res": a.res, "dx": s.dx, "efree": s.efree,
                "listener": a.listener, "fdtd_ms": t.fdtdMs, "analysis_ms": t.analysisMs, "emitters": []}
-        if a.room_metrics:
+        if whole and a.room_metrics:
             s.compute_room_metrics()
-        if a.decay_times:
+        if whole and a.decay_times:
             s.compute_decay_times()
-        if a.echo_criterion:
+        if whole and a.echo_criterion:
             s.compute_echo_criterion()
-        if a.lateral_fraction:
+        if whole and a.lateral_fraction:
             s.compute_lateral_fraction()
-        if a.echogram:
+        if whole and a.echogram:
             s.set_echogram(*a.echogram)
             s.compute_echogram()
-        if a.lobes is not None:
+        if whole and a.lobes is not None:
             s.set_lobe_windows(a.lobes)
             s.compute_lobes()
         if a.bands:
@@ -102,7 +120,7 @@ def main(argv=None):
         if a.spectrum:
             s.set_spectrum_bins(a.spectrum)
             s.compute_spectrum()
-        for e in emitters:
+        for i, e in enumerate(emitters):
             o = s.get_output(e)
             ga, gb, gc = api.reverb_bus_gains(o.rt60, o.wetGain)
             out["emitters"].append({
@@ -110,24 +128,24 @@ def main(argv=None):
                 "direction": [o.directionX, o.directionY], "sourceDirectivity": [o.sourceDirectionX, o.sourceDirectionY],
                 "reverbBusGains": [ga, gb, gc]})
             if a.room_metrics:
-                m = s.room_metrics_at(e)
+                m = s.room_metrics_at(e) if whole else qrec[api.QREC_ROOM_METRICS][i]
                 out["emitters"][-1]["roomMetrics"] = dict((n, float(v)) for n, v in zip(api.ROOM_METRIC_NAMES, m))
             if a.decay_times:
-                m = s.decay_times_at(e)
+                m = s.decay_times_at(e) if whole else qrec[api.QREC_DECAY_TIMES][i]
                 out["emitters"][-1]["decayTimes"] = dict((n, float(v)) for n, v in zip(api.DECAY_TIME_NAMES, m))
             if a.echo_criterion:
-                m = s.echo_criterion_at(e)
+                m = s.echo_criterion_at(e) if whole else qrec[api.QREC_ECHO_CRITERION][i]
                 out["emitters"][-1]["echoCriterion"] = dict((n, float(v)) for n, v in zip(api.ECHO_CRITERION_NAMES, m))
             if a.lateral_fraction:
-                m = s.lateral_fraction_at(e)
+                m = s.lateral_fraction_at(e) if whole else qrec[api.QREC_LATERAL][i]
                 out["emitters"][-1]["lateralFraction"] = dict((n, float(v)) for n, v in zip(api.LATERAL_FRACTION_NAMES, m))
             if a.echogram:
-                m = s.echogram_at(e)
+                m = s.echogram_at(e) if whole else qrec[api.QREC_ECHOGRAM][i]
                 out["emitters"][-1]["echogram"] = {"slotSteps": s.echogram_slots()[2], "n": float(m[0]),
                                                    "e": [float(v) for v in m[1::3]], "ix": [float(v) for v in m[2::3]],
                                                    "iy": [float(v) for v in m[3::3]]}
             if a.lobes is not None:
-                m = s.lobes_at(e)
+                m = s.lobes_at(e) if whole else qrec[api.QREC_LOBES][i]
                 out["emitters"][-1]["lobes"] = {"n": float(m[0]), "windows": [
                     dict((n, float(v)) for n, v in zip(api.LOBE_NAMES, m[1 + 5 * w:6 + 5 * w])) for w in range((len(m) - 1) // 5)]}
             if a.bands:

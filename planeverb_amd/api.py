@@ -264,6 +264,10 @@ SYMBOLS = {
     "PvAmdGetOutput": (C.c_int, [_vp] + [C.c_float] * 3 + [C.POINTER(PlaneverbOutput)]),
     "PvAmdSetOutputQueries": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetQueriedOutputs": (C.c_int, [_vp, C.POINTER(PlaneverbOutput), C.c_int]),
+    "PvAmdSetQueryRecords": (C.c_int, [_vp, C.c_uint]),
+    "PvAmdGetQueryRecordKinds": (C.c_uint, [_vp]),
+    "PvAmdQueryRecordFloats": (C.c_int, [_vp, C.c_uint]),
+    "PvAmdGetQueriedRecords": (C.c_int, [_vp, C.c_uint, _fp, C.c_int]),
     "PvAmdCopyResults": (C.c_int, [_vp, _fp, _fp]),
     "PvAmdCopyResultsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "PvAmdGetImpulseResponse": (C.c_int, [_vp, C.c_int, C.c_int, _fp]),
@@ -799,6 +803,14 @@ def host_echogram(p, vx, vy, fs, onset, slot_seconds, n_slots):
 
 
 LOBES_MAX_EDGES = 7  # PVA_LOBES_MAX_EDGES
+# PVA_QREC_*: the record kinds Solver.set_query_records selects (a mask)
+QREC_ROOM_METRICS = 1
+QREC_DECAY_TIMES = 2
+QREC_LATERAL = 4
+QREC_ECHOGRAM = 8
+QREC_ECHO_CRITERION = 16
+QREC_LOBES = 32
+QREC_ALL = 63
 LOBES_DEFAULT_EDGES = (0.01, 0.08)
 LOBE_NAMES = ("e", "xp", "xn", "yp", "yn")
 LOBE_PATTERN_OMNI, LOBE_PATTERN_CARDIOID = 0, 1
@@ -1453,6 +1465,29 @@ class Solver:
         out = (PlaneverbOutput * max(n, 1))()
         _check(lib().PvAmdGetQueriedOutputs(self._h, out, n))
         return np.frombuffer(out, np.float32).reshape(-1, 8)[:n].copy()
+
+    def set_query_records(self, kinds):
+        """the per-cell record kinds (a mask of QREC_*) every following run computes for the cells of the output queries, in one
+        launch inside the run and straight into pinned host memory; 0 (the default) selects none and frees the block"""
+        _check(lib().PvAmdSetQueryRecords(self._h, int(kinds)))
+
+    def query_record_kinds(self):
+        return int(lib().PvAmdGetQueryRecordKinds(self._h))
+
+    def query_record_floats(self, kind):
+        """floats per query of ONE kind under the current settings (10, 8, 11, 1 + 3 nSlots, 10, 1 + 5 nW)"""
+        n = lib().PvAmdQueryRecordFloats(self._h, int(kind))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return n
+
+    def queried_records(self, kind):
+        """float32 [n_queries, floats] of ONE kind for the last run (waits for it; no GPU work): each row bit for bit what
+        <kind>_at(position) returns after compute_<kind>() on the same run; NaN rows off the map and where no sound arrived"""
+        n = getattr(self, "_nq", 0)
+        out = np.empty((n, self.query_record_floats(kind)), np.float32)
+        _check(lib().PvAmdGetQueriedRecords(self._h, int(kind), _f(out) if n else None, n))
+        return out
 
     def results(self):
         res = np.empty((self.gx, self.gy, 8), np.float32)

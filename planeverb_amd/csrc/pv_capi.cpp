@@ -1065,6 +1065,39 @@ int PvAmdGetQueriedOutputs(PvAmdSolver* h, PlaneverbOutput* out, int n) try {
     return 0;
 } PV_API_CATCH(-1)
 
+// in-run query records (pv_query_records.hip): single whole-grid solvers only; every refusal says "query records: ..."
+static bool queryRecordsHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "query records: " + g_lastError;
+    return false;
+}
+
+int PvAmdSetQueryRecords(PvAmdSolver* h, unsigned kinds) try {
+    if (!queryRecordsHandle(h)) return -1;
+    return ret(h, h->s->setQueryRecords(kinds));
+} PV_API_CATCH(-1)
+
+unsigned PvAmdGetQueryRecordKinds(PvAmdSolver* h) try {
+    if (!queryRecordsHandle(h)) return 0u;
+    return h->s->queryRecordKinds();
+} PV_API_CATCH(0u)
+
+int PvAmdQueryRecordFloats(PvAmdSolver* h, unsigned kind) try {
+    if (!queryRecordsHandle(h)) return -1;
+    const int n = h->s->queryRecordFloats(kind);
+    if (n < 0) ret(h, false);
+    return n;
+} PV_API_CATCH(-1)
+
+int PvAmdGetQueriedRecords(PvAmdSolver* h, unsigned kind, float* out, int nQueries) try {
+    if (!queryRecordsHandle(h)) return -1;
+    if (nQueries < 0 || nQueries > Solver::kMaxQueries || (nQueries > 0 && !out)) {
+        g_lastError = "query records: PvAmdGetQueriedRecords: 0 .. 64 queries and an output buffer";
+        return -1;
+    }
+    return ret(h, h->s->queriedRecords(kind, out, nQueries));
+} PV_API_CATCH(-1)
+
 int PvAmdCopyResults(PvAmdSolver* h, float* res8, float* delay) try {
     if (!wholeGrid(h) || !ensure(h, true)) return -1;
     return ret(h, h->g ? h->g->copyResults(res8, delay) : h->s->copyResults(res8, delay));

@@ -23,6 +23,10 @@
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): see profiles/echogram.txt; no scratch, no LDS.
 // The per-plane-descriptor form (!CHUNK: a plane of 2^31 / S bytes and more) is line for line the one of pv_lateral.hip and is
 // covered by that parallel only: no test can afford such a plane.
+//
+// The text of the pass is echogramBody (pv_echogram_dev.h): this file keeps the description, the whole-map kernel -- a wrapper that gives
+// the body the lane's consecutive offset and the out[k * plane + g] store -- and its launcher; pv_query_records.hip runs the
+// same body for the cells of a run's output queries.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -32,15 +36,9 @@
 #include "pv_analysis_dev.h"
 #include "pv_device.h"
 #include "pv_echogram.h"
+#include "pv_echogram_dev.h"
 #include "pv_launch.h"
 #include "pv_prims.h"
-
-#ifndef PV_ECHOGRAM_S
-#define PV_ECHOGRAM_S 8  // planes per chunk
-#endif
-#ifndef PV_ECHOGRAM_NB
-#define PV_ECHOGRAM_NB 2  // chunks of loads in flight per wave (three loads per plane)
-#endif
 
 namespace pva {
 
@@ -48,123 +46,11 @@ namespace {
 
 constexpr int kEchogramBlock = 256;
 
-// CHUNK: a chunk's S planes through ONE descriptor and S constant scalar offsets (S planes must stay below 2^31 bytes);
-// otherwise one descriptor per plane
 template <int S, int NB, bool CHUNK>
 __global__ __launch_bounds__(kEchogramBlock) void pv_echogram_kernel(const AnalyzeArgs a, float* __restrict__ out, int ns, int nSlots) {
     const DynParams dyn = *a.dyn;
-    const int T = a.T;
-    constexpr int kOut = 0x7fffffff;  // >= every descriptor's extent: the load returns 0
-    const long long plane = a.histPlane;
-    const int planeBytes = (int)(plane * 4);
-
     const long long g = ((long long)blockIdx.x * (kEchogramBlock / 64) + (threadIdx.x >> 6)) * 64 + (threadIdx.x & 63);
-    const PlaneCell pc = planeCell(a, dyn, g);  // (g >= histPlane: not in the grid)
-    const float delay = pc.inGrid ? a.delay[(long long)pc.X * a.gy + pc.Y] : FLT_MAX;
-    const bool live = delay != FLT_MAX;
-    if (g < plane && !live) {
-        const float qnan = echogramQuietNan();
-        float* q = out + g;
-        for (int k = 0; k < 1 + 3 * nSlots; ++k, q += plane) *q = qnan;
-    }
-    if (__ballot(live) == 0ull) return;
-
-    // the neighbours (X - 1, Y) and (X, Y - 1) as plane offsets, and the first recorded step of their tiles: encodeWave
-    const int tileCells = a.rxi * a.wi;
-    const bool hasX = pc.hti > 0 || pc.row > 0, hasY = pc.htj > 0 || pc.col > 0;
-    const int gX = pc.row > 0 ? pc.g - a.wi : pc.g - dyn.histTilesY * tileCells + (a.rxi - 1) * a.wi;
-    const int gY = pc.col > 0 ? pc.g - 1 : pc.g - tileCells + (a.wi - 1);
-    const int tileX = pc.row > 0 ? pc.tile : pc.tile - a.nty, tileY = pc.col > 0 ? pc.tile : pc.tile - 1;
-    int tFirst = T, tFx = INT_MAX, tFy = INT_MAX;
-    FaceCoef fc{0.f, 0.f, 0.f};
-    if (live) {
-        tFirst = a.tileFirst[pc.tile];
-        if (hasX) tFx = a.tileFirst[tileX];
-        if (hasY) tFy = a.tileFirst[tileY];
-        fc = a.coef[(size_t)(pc.X + a.G) * a.pitch + (pc.Y + a.G)];
-    }
-    const float kx = fc.kx, ky = fc.ky;
-    const bool airX = kx != kx, airY = ky != ky;
-    const float C = a.courant;
-
-    const int onset = live ? (int)delay : 0;
-    const int m = abs(pc.X - (dyn.lrow - a.G)) + abs(pc.Y - (dyn.lcol - a.G));
-    // a lane's ranges: the recurrence and the own loads over [tBegin, tEnd), a neighbour's loads from its tile's first step on,
-    // the sums over [onset, tEnd); a dead lane's are empty.  (ns * nSlots <= 2^25, onset < T: no overflow)
-    const int tEnd = live ? min(onset + ns * nSlots, T) : 0;
-    const int tBegin = live ? max(max(tFirst, m - 1), 0) : INT_MAX;
-    const int tLoX = (live && hasX) ? max(tBegin, tFx) : INT_MAX, tLoY = (live && hasY) ? max(tBegin, tFy) : INT_MAX;
-    // (wave-uniform by value; said so to the compiler by waveMin / waveMax: scalar loop counters and descriptors)
-    const int tLo = min(waveMin(tBegin), T), tHi = min(waveMax(tEnd), T);
-    const int vo = pc.g * 4, voX = gX * 4, voY = gY * 4;
-
-    float ring[NB][3][S];
-    // the 3 S loads of the chunk that begins at step tc >= 0 (issued whatever tc is: the counts are the same on every path)
-    auto loadChunk = [&](float (&dst)[3][S], int tc) {
-        const int tb = min(tc, T - 1);  // (a chunk past the end: every lane out of range, the base stays inside the history)
-        const rsrc_t rs = makeRsrc(a.hist + (long long)tb * plane, CHUNK ? (long long)S * planeBytes : (long long)planeBytes);
-#pragma unroll
-        for (int k = 0; k < S; ++k) {
-            const int t = tc + k;
-            const bool in = t < tEnd;  // (tEnd <= T)
-            const int o = (in && t >= tBegin) ? vo : kOut, oX = (in && t >= tLoX) ? voX : kOut, oY = (in && t >= tLoY) ? voY : kOut;
-            const rsrc_t r = CHUNK ? rs : makeRsrc(a.hist + (long long)min(t, T - 1) * plane, planeBytes);
-            const int so = CHUNK ? (int)((unsigned)k * (unsigned)planeBytes) : 0;
-            dst[0][k] = bufLoadF(r, o, so);
-            dst[1][k] = bufLoadF(r, oX, so);
-            dst[2][k] = bufLoadF(r, oY, so);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
-    // the current slot of the lane: its sums, the step at which it ends, where it goes (live lanes: g < plane, and the lane
-    // flushes at most nSlots times -- once per ns steps of [onset, tEnd), tEnd - onset <= ns nSlots -- so w stays inside plane 3 nSlots)
-    EchogramSums s{0.f, 0.f, 0.f};
-    int tNext = live ? min(onset + ns, tEnd) : INT_MAX;
-    float* w = out + plane + (live ? g : 0);
-    float vx = 0.f, vy = 0.f;
-    const int n = (tHi - tLo + S - 1) / S;  // chunks from the wave's smallest tBegin to its largest tEnd
-#pragma unroll
-    for (int b = 0; b < NB; ++b) loadChunk(ring[b], tLo + b * S);
-#pragma unroll 1
-    for (int c0 = 0; c0 < n; c0 += NB) {
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-            const int tc = tLo + (c0 + b) * S;
-            float p[S], px[S], py[S];
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                p[k] = ring[b][0][k];
-                px[k] = ring[b][1][k];
-                py[k] = ring[b][2][k];
-            }
-            loadChunk(ring[b], tc + NB * S);  // the slot's next occupant
-            if (tc >= tHi) continue;          // (past the last chunk: those loads returned 0)
-#pragma unroll
-            for (int k = 0; k < S; ++k) {
-                const int t = tc + k;
-                const bool mineV = t >= tBegin && t < tEnd, mine = t >= onset && t < tEnd;
-                const float ax = vx - C * (p[k] - px[k]), wx = kx * (p[k] + px[k]);
-                const float ay = vy - C * (p[k] - py[k]), wy = ky * (p[k] + py[k]);
-                vx = mineV ? (airX ? ax : wx) : vx;
-                vy = mineV ? (airY ? ay : wy) : vy;
-                echogramStep(s, mine, p[k], vx, vy);
-                if (mine && t + 1 == tNext) {  // the slot ends here, by its length or by tEnd
-                    w[0] = s.e;
-                    w[plane] = s.ix;
-                    w[2 * plane] = s.iy;
-                    w += 3 * plane;
-                    s = EchogramSums{0.f, 0.f, 0.f};
-                    tNext = min(tNext + ns, tEnd);
-                }
-            }
-        }
-    }
-    if (!live) return;
-    // (onset >= tBegin >= tLo and tEnd <= tHi: the lane's last slot has been written)
-    out[g] = (float)(tEnd - onset);
-    float* const wEnd = out + (1 + 3 * (long long)nSlots) * plane + g;
-    for (; w < wEnd; w += plane) *w = 0.f;  // the slots the record does not reach
+    echogramBody<S, NB, CHUNK>(a, dyn, recordLaneAt(a, dyn, g), PlaneStore{out, a.histPlane, g}, ns, nSlots);
 }
 
 }  // namespace

@@ -1,0 +1,132 @@
+// pv_lateral_dev.h -- the body of the lateral-fraction pass (pv_lateral.hip, which describes it), shared by the whole-map kernel and the in-run query
+// kernel (pv_query_records.hip): which cell the lane owns and where its record goes come from the caller (pv_record_lane.h),
+// everything else -- loads, ring, sums, order -- is this one text.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <climits>
+
+#include "pv_analysis.h"
+#include "pv_analysis_dev.h"
+#include "pv_device.h"
+#include "pv_lateral.h"
+#include "pv_prims.h"
+#include "pv_record_lane.h"
+
+#ifndef PV_LATERAL_S
+#define PV_LATERAL_S 8  // planes per chunk
+#endif
+#ifndef PV_LATERAL_NB
+#define PV_LATERAL_NB 2  // chunks of loads in flight per wave (three loads per plane)
+#endif
+
+namespace pva {
+
+// CHUNK: a chunk's S planes through ONE descriptor and S constant scalar offsets (S planes must stay below 2^31 bytes);
+// otherwise one descriptor per plane
+template <int S, int NB, bool CHUNK, class Store>
+__device__ __forceinline__ void lateralBody(const AnalyzeArgs& a, const DynParams& dyn, const RecordLane& ln, const Store& out, int n5, int n80) {
+    const int T = a.T;
+    constexpr int kOut = 0x7fffffff;  // >= every descriptor's extent: the load returns 0
+    const long long plane = a.histPlane;
+    const int planeBytes = (int)(plane * 4);
+
+    const PlaneCell& pc = ln.pc;
+    const float delay = ln.delay;
+    const bool live = ln.live;
+    if (ln.slot && !live) {
+        const float qnan = lateralQuietNan();
+#pragma unroll
+        for (int k = 0; k < kLateralFloats; ++k) out(k, qnan);
+    }
+    if (__ballot(live) == 0ull) return;
+
+    // the neighbours (X - 1, Y) and (X, Y - 1) as plane offsets, and the first recorded step of their tiles: encodeWave
+    const int tileCells = a.rxi * a.wi;
+    const bool hasX = pc.hti > 0 || pc.row > 0, hasY = pc.htj > 0 || pc.col > 0;
+    const int gX = pc.row > 0 ? pc.g - a.wi : pc.g - dyn.histTilesY * tileCells + (a.rxi - 1) * a.wi;
+    const int gY = pc.col > 0 ? pc.g - 1 : pc.g - tileCells + (a.wi - 1);
+    const int tileX = pc.row > 0 ? pc.tile : pc.tile - a.nty, tileY = pc.col > 0 ? pc.tile : pc.tile - 1;
+    int tFirst = T, tFx = INT_MAX, tFy = INT_MAX;
+    FaceCoef fc{0.f, 0.f, 0.f};
+    if (live) {
+        tFirst = a.tileFirst[pc.tile];
+        if (hasX) tFx = a.tileFirst[tileX];
+        if (hasY) tFy = a.tileFirst[tileY];
+        fc = a.coef[(size_t)(pc.X + a.G) * a.pitch + (pc.Y + a.G)];
+    }
+    const float kx = fc.kx, ky = fc.ky;
+    const bool airX = kx != kx, airY = ky != ky;
+    const float C = a.courant;
+
+    const int onset = live ? (int)delay : 0;
+    const int m = abs(pc.X - (dyn.lrow - a.G)) + abs(pc.Y - (dyn.lcol - a.G));
+    // a lane's ranges: the recurrence and the own loads over [tBegin, tEnd), a neighbour's loads from its tile's first step on,
+    // the sums over [onset, tEnd); a dead lane's are empty
+    const int tEnd = live ? min(onset + n80, T) : 0;
+    const int tBegin = live ? max(max(tFirst, m - 1), 0) : INT_MAX;
+    const int tLoX = (live && hasX) ? max(tBegin, tFx) : INT_MAX, tLoY = (live && hasY) ? max(tBegin, tFy) : INT_MAX;
+    // (wave-uniform by value; said so to the compiler by waveMin / waveMax: scalar loop counters and descriptors)
+    const int tLo = min(waveMin(tBegin), T), tHi = min(waveMax(tEnd), T);
+    const int vo = pc.g * 4, voX = gX * 4, voY = gY * 4;
+
+    float ring[NB][3][S];
+    // the 3 S loads of the chunk that begins at step tc >= 0 (issued whatever tc is: the counts are the same on every path)
+    auto loadChunk = [&](float (&dst)[3][S], int tc) {
+        const int tb = min(tc, T - 1);  // (a chunk past the end: every lane out of range, the base stays inside the history)
+        const rsrc_t rs = makeRsrc(a.hist + (long long)tb * plane, CHUNK ? (long long)S * planeBytes : (long long)planeBytes);
+#pragma unroll
+        for (int k = 0; k < S; ++k) {
+            const int t = tc + k;
+            const bool in = t < tEnd;  // (tEnd <= T)
+            const int o = (in && t >= tBegin) ? vo : kOut, oX = (in && t >= tLoX) ? voX : kOut, oY = (in && t >= tLoY) ? voY : kOut;
+            const rsrc_t r = CHUNK ? rs : makeRsrc(a.hist + (long long)min(t, T - 1) * plane, planeBytes);
+            const int so = CHUNK ? (int)((unsigned)k * (unsigned)planeBytes) : 0;
+            dst[0][k] = bufLoadF(r, o, so);
+            dst[1][k] = bufLoadF(r, oX, so);
+            dst[2][k] = bufLoadF(r, oY, so);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    LateralSums s{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float vx = 0.f, vy = 0.f;
+    const int n = (tHi - tLo + S - 1) / S;  // chunks from the wave's smallest tBegin to its largest tEnd
+#pragma unroll
+    for (int b = 0; b < NB; ++b) loadChunk(ring[b], tLo + b * S);
+#pragma unroll 1
+    for (int c0 = 0; c0 < n; c0 += NB) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int tc = tLo + (c0 + b) * S;
+            float p[S], px[S], py[S];
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                p[k] = ring[b][0][k];
+                px[k] = ring[b][1][k];
+                py[k] = ring[b][2][k];
+            }
+            loadChunk(ring[b], tc + NB * S);  // the slot's next occupant
+            if (tc >= tHi) continue;          // (past the last chunk: those loads returned 0)
+#pragma unroll
+            for (int k = 0; k < S; ++k) {
+                const int t = tc + k;
+                const bool mineV = t >= tBegin && t < tEnd, mine = t >= onset && t < tEnd;
+                const float ax = vx - C * (p[k] - px[k]), wx = kx * (p[k] + px[k]);
+                const float ay = vy - C * (p[k] - py[k]), wy = ky * (p[k] + py[k]);
+                vx = mineV ? (airX ? ax : wx) : vx;
+                vy = mineV ? (airY ? ay : wy) : vy;
+                lateralStep(s, mine, t - onset < n5, p[k], vx, vy);
+            }
+        }
+    }
+    if (!live) return;
+    float rec[kLateralFloats];
+    lateralDerive(s, tEnd - onset, rec);
+#pragma unroll
+    for (int k = 0; k < kLateralFloats; ++k) out(k, rec[k]);
+}
+
+}  // namespace pva

@@ -155,6 +155,12 @@ void launchEchogram(const AnalyzeArgs& a, float* out, int ns, int nSlots, hipStr
 struct LobeEdges;
 void launchLobes(const AnalyzeArgs& a, float* out, const LobeEdges& ed, int nW, hipStream_t stream);
 
+// ---- pv_query_records.hip: the record kinds above for the cells of the registered output queries, inside the run
+// one launch (one wave per selected kind, lane i = query i) that writes q.nq records per selected kind straight into pinned host
+// memory (pv_query_records.h); the records are bit for bit the whole-map passes' at the same cells
+struct QueryRecordArgs;
+void launchQueryRecords(const AnalyzeArgs& a, const QueryRecordArgs& q, hipStream_t stream);
+
 // ---- pv_bands.hip: per-cell, per-band decay times and clarity
 // band records of the last completed run (pv_bands.hip) for n bands: coefs = n x kBandCoefs floats on the HOST (they travel as
 // kernel arguments), out = n x kBandFloats planes of a.histPlane floats (band j, float k at plane j * kBandFloats + k), indexed by

@@ -1,0 +1,35 @@
+// pv_query_records.h -- the in-run per-query analysis records (PvAmdSetQueryRecords, pv_query_records.hip): the kinds, their record
+// sizes, and what travels to the kernel
+#pragma once
+
+#include "pv_decay.h"
+#include "pv_echo.h"
+#include "pv_echogram.h"
+#include "pv_lateral.h"
+#include "pv_lobes.h"
+#include "pv_metrics.h"
+
+namespace pva {
+
+// bit k of the kinds mask = PVA_QREC_* (include/planeverb_amd.h)
+constexpr int kQrecRoomMetrics = 0, kQrecDecay = 1, kQrecLateral = 2, kQrecEchogram = 3, kQrecEchoCriterion = 4, kQrecLobes = 5;
+constexpr int kQueryRecordKinds = 6;
+constexpr unsigned kQueryRecordMask = (1u << kQueryRecordKinds) - 1u;
+
+struct QueryRecordArgs {
+    const long long* cells;  // nq result-cell indices (-1: off the map), pinned host memory
+    float* out;              // pinned host memory
+    int nq;                  // <= 64
+    unsigned kinds;
+    int offset[kQueryRecordKinds];  // of a kind's nq x floats block inside out, in floats
+    int floats[kQueryRecordKinds];  // per query
+    int n50, n80;            // room metrics
+    int n5, latN80;          // lateral fraction
+    int tailN;               // decay times
+    int ns, nSlots;          // echogram
+    int nDs, nDm, nLs, nLm;  // echo criterion
+    LobeEdges ed;            // lobes
+    int nW;
+};
+
+}  // namespace pva

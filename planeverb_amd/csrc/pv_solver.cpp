@@ -25,6 +25,7 @@
 #include "pv_lateral.h"
 #include "pv_lobes.h"
 #include "pv_metrics.h"
+#include "pv_query_records.h"
 #include "pv_spectrum.h"
 
 namespace pva {
@@ -713,6 +714,7 @@ Solver::~Solver() {
     for (auto& e : echoEv_)
         if (e) hipEventDestroy(e);
     if (lobes_) hipFree(lobes_);
+    if (qrecHost_) hipHostFree(qrecHost_);
     for (auto& e : lobesEv_)
         if (e) hipEventDestroy(e);
     if (echoCrit_) hipFree(echoCrit_);
@@ -2153,6 +2155,7 @@ bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, floa
     if (pendingTimings_ && !sync()) return false;
     metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
+    qrecRun_ = QrecRun::None;    // (the pinned block is about to be overwritten, or this run leaves no records)
     if (!applyGeometry()) return false;
     PathRun r;
     r.kind = kind;
@@ -2219,6 +2222,7 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     if (!opt_.skipAnalysis) enqueueAnalysis(lx, lz);
     if (!stampTimed()) hipEventRecord(ev_[2], stream_);
     lastRunBatched_ = false;
+    enqueueQueryRecords();
     // last kernel of the run: the registered queries' outputs and the status words, both into pinned memory
     launchRunFinish(res_, (long long)g_.gx * g_.gy, qCellsHost_, opt_.skipAnalysis ? 0 : numQueries_, qOutHost_, farInfo(), errFlag_,
                     activeCount_, plan_.oneXcd ? resFlags_ + runTiles_ + 1 : nullptr, statusHost_, resFlags_,
@@ -2667,6 +2671,7 @@ bool Solver::sync() {
         }
         if (flag) return fail("pressure history window overflow (a tile outside the window became non-zero)");
         lastRun_ = plan_.kind == PathRun::Raw ? LastRun::None : LastRun::Ok;  // (raw stepping records no history)
+        if (qrecRun_ == QrecRun::Pending) qrecRun_ = QrecRun::Ok;
     }
     return true;
 }
@@ -2714,6 +2719,7 @@ bool Solver::setOutputQueries(const float* xyz, int n) {
         qCellsHost_[i] = resultCell(g_, xyz[3 * i], xyz[3 * i + 2], &cx, &cy) ? (long long)cx * g_.gy + cy : -1;
     }
     numQueries_ = n;
+    qrecRun_ = QrecRun::None;  // (the records in the pinned block belong to the queries of before)
     return true;
 }
 
@@ -2724,6 +2730,7 @@ void Solver::enqueueRunStatus() {
 }
 
 void Solver::enqueueQueries() {
+    enqueueQueryRecords();
     if (numQueries_ > 0 && !opt_.skipAnalysis)
         launchGatherQueries(res_, (long long)g_.gx * g_.gy, qCellsHost_, numQueries_, qOutHost_, farInfo(), stream_);
     enqueueTap();
@@ -2744,6 +2751,122 @@ bool Solver::queriedOutputs(float* out8n, unsigned char* valid, int n) {
         valid[i] = qCellsHost_[i] >= 0;
         for (int k = 0; k < 8; ++k) out8n[8 * i + k] = qOutHost_[8 * i + k];
     }
+    return true;
+}
+
+// ---- in-run query records (pv_query_records.hip)
+namespace {
+// floats per query of kind bit k under the given settings; -1 where the kind's setting is missing
+int qrecFloatsOf(int k, int echoSlots, int lobeWindows) {
+    switch (k) {
+        case kQrecRoomMetrics: return kRoomMetricFloats;
+        case kQrecDecay: return kDecayFloats;
+        case kQrecLateral: return kLateralFloats;
+        case kQrecEchogram: return echoSlots > 0 ? echogramFloats(echoSlots) : -1;
+        case kQrecEchoCriterion: return kEchoFloats;
+        case kQrecLobes: return lobesFloats(lobeWindows);
+    }
+    return -1;
+}
+int qrecBit(unsigned kind) {  // the bit of a mask that names ONE kind, or -1
+    for (int k = 0; k < kQueryRecordKinds; ++k)
+        if (kind == (1u << k)) return k;
+    return -1;
+}
+}  // namespace
+
+bool Solver::setQueryRecords(unsigned kinds) {
+    if (kinds & ~kQueryRecordMask) return fail("query records: unknown kind bit (PVA_QREC_*)");
+    if (kinds) {
+        if (isSlab()) return fail("query records: not available on a slab");
+        if (opt_.streaming) return fail("query records: the full pressure history is not kept in streaming-analysis mode");
+        if (opt_.skipAnalysis) return fail("query records: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+        if ((kinds & (1u << kQrecEchogram)) && !echoSlots_) return fail("query records: echogram: no slots set (PvAmdSetEchogram)");
+        if ((kinds & (1u << kQrecEchoCriterion)) && !echoFsOk((int)g_.fs))
+            return fail("query records: echo: the sampling rate gives a speech lag below one step ((int)(0.009f * (float)fs) < 1)");
+        LobeEdges ed;
+        if ((kinds & (1u << kQrecLobes)) && !lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, (int)g_.fs, &ed))
+            return fail("query records: lobes: the default windows (10 ms, 80 ms) need a sampling rate of 100 Hz or more (PvAmdSetLobeWindows)");
+    }
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // the launch of a run in flight still writes the pinned block
+    if (kinds == qrecKinds_) return true;
+    // the block holds every selected kind at its largest setting, so that a later change of slots or windows needs no allocation
+    size_t cap = 0;
+    for (int k = 0; k < kQueryRecordKinds; ++k)
+        if ((kinds >> k) & 1u) cap += (size_t)qrecFloatsOf(k, kEchogramMaxSlots, kLobesMaxWindows);
+    float* block = nullptr;
+    if (cap && !hipOk(hipHostMalloc((void**)&block, cap * kMaxQueries * sizeof(float)), "hipHostMalloc")) return false;
+    if (qrecHost_) hipHostFree(qrecHost_);
+    qrecHost_ = block;
+    qrecKinds_ = kinds;
+    qrecRun_ = QrecRun::None;
+    return true;
+}
+
+int Solver::queryRecordFloats(unsigned kind) {
+    const int k = qrecBit(kind);
+    if (k < 0) {
+        fail("query records: exactly one kind (PVA_QREC_*)");
+        return -1;
+    }
+    const int n = qrecFloatsOf(k, echoSlots_, lobeEdgeCount_ + 1);
+    if (n < 0) fail("query records: echogram: no slots set (PvAmdSetEchogram)");
+    return n;
+}
+
+// The settings are those of this moment: PvAmdSetEchogram / PvAmdSetLobeWindows wait for a run in flight, and the stamp keeps the
+// layout the run was enqueued with
+void Solver::enqueueQueryRecords() {
+    if (!qrecKinds_ || opt_.skipAnalysis) return;
+    QueryRecordArgs q{};
+    q.cells = qCellsHost_;
+    q.out = qrecHost_;
+    q.nq = numQueries_;
+    q.kinds = qrecKinds_;
+    const int fs = (int)g_.fs;
+    int off = 0;
+    for (int k = 0; k < kQueryRecordKinds; ++k) {
+        const bool on = (qrecKinds_ >> k) & 1u;
+        q.floats[k] = on ? qrecFloatsOf(k, echoSlots_, lobeEdgeCount_ + 1) : 0;
+        q.offset[k] = off;
+        off += q.floats[k] * numQueries_;
+        qrecRunFloats_[k] = q.floats[k];
+        qrecRunOffset_[k] = q.offset[k];
+    }
+    q.n50 = roomMetricsN50(fs);
+    q.n80 = roomMetricsN80(fs);
+    q.n5 = lateralN5(fs);
+    q.latN80 = lateralN80(fs);
+    q.tailN = decayTailN(fs);
+    q.ns = echoSteps_;
+    q.nSlots = echoSlots_;
+    q.nDs = echoSpeechLag(fs);
+    q.nDm = echoMusicLag(fs);
+    q.nLs = echoSpeechLimit(fs);
+    q.nLm = echoMusicLimit(fs);
+    lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, fs, &q.ed);  // (valid: checked where the kind was selected and where the windows are set)
+    q.nW = lobeEdgeCount_ + 1;
+    qrecRunKinds_ = qrecKinds_;
+    qrecRunQueries_ = numQueries_;
+    qrecRun_ = QrecRun::Pending;
+    if (numQueries_ > 0) launchQueryRecords(analyzeArgs(lastLx_, lastLz_), q, stream_);
+}
+
+// after the run has been waited for: the records of one kind, straight from pinned memory
+bool Solver::queriedRecords(unsigned kind, float* out, int n) {
+    const int k = qrecBit(kind);
+    if (k < 0) return fail("query records: exactly one kind (PVA_QREC_*)");
+    if (!(qrecKinds_ & kind)) return fail("query records: the kind is not selected (PvAmdSetQueryRecords)");
+    if (n != numQueries_) return fail("query records: count differs from the registered queries");
+    if (pendingTimings_ && !sync()) return false;
+    if (lastRun_ == LastRun::Failed) return fail("query records: the last run ended in error");
+    if (qrecRun_ != QrecRun::Ok || qrecRunKinds_ != qrecKinds_ || qrecRunQueries_ != numQueries_ ||
+        qrecRunFloats_[k] != qrecFloatsOf(k, echoSlots_, lobeEdgeCount_ + 1))
+        return fail("query records: no completed run since the kinds, the queries or the settings changed");
+    const float* src = qrecHost_ + qrecRunOffset_[k];
+    for (int i = 0; i < n * qrecRunFloats_[k]; ++i) out[i] = src[i];
     return true;
 }
 
@@ -3262,6 +3385,9 @@ bool Solver::setEchogram(float slotSeconds, int nSlots) {
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    if (nSlots == 0 && (qrecKinds_ & (1u << kQrecEchogram)))
+        return fail("query records: echogram: the slots cannot be cleared while PVA_QREC_ECHOGRAM is selected (PvAmdSetQueryRecords)");
+    if (qrecKinds_ & (1u << kQrecEchogram)) qrecRun_ = QrecRun::None;  // (the records in the pinned block are the old slots')
     echoValid_ = false;
     echoHostValid_ = false;
     if (nSlots == 0) {
@@ -3374,6 +3500,7 @@ bool Solver::setLobeWindows(const float* edgesSeconds, int nEdges) {
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    if (qrecKinds_ & (1u << kQrecLobes)) qrecRun_ = QrecRun::None;  // (the records in the pinned block are the old windows')
     lobesValid_ = false;
     lobesHostValid_ = false;
     if (nEdges == 0) {

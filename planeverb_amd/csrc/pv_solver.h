@@ -218,6 +218,17 @@ public:
     static constexpr int kMaxQueries = 64;
     bool setOutputQueries(const float* xyz, int n);
     bool queriedOutputs(float* out8n, unsigned char* valid, int n);
+    // In-run analysis records of the registered queries' cells (pv_query_records.hip; include/planeverb_amd.h
+    // PvAmdSetQueryRecords): every following run computes the selected kinds (a mask of bits kQrec*, pv_query_records.h) for the
+    // queries' cells in ONE launch behind its analysis and in front of its last kernel, straight into pinned host memory; the
+    // records are bit for bit the whole-map passes' at the same cells.  kinds = 0 (the default): nothing is launched and the
+    // pinned block is freed.  Both setters wait for a run in flight.  queriedRecords: n x queryRecordFloats(kind) floats of ONE
+    // kind, after the run has been waited for; refused until a run enqueued under the current kinds, queries and settings has
+    // completed without error
+    bool setQueryRecords(unsigned kinds);
+    unsigned queryRecordKinds() const { return qrecKinds_; }
+    int queryRecordFloats(unsigned kind);  // -1: not one kind, or its setting is missing
+    bool queriedRecords(unsigned kind, float* out, int n);
     bool copyResults(float* res8, float* delay);
     // the block [r0, r0 + nr) x [c0, c0 + nc) of the result map (AoS records) and of the onset map, row-major nr x nc
     bool copyResultsBlock(int r0, int c0, int nr, int nc, float* res8, float* delay);
@@ -626,6 +637,15 @@ private:
     float* qOutHost_ = nullptr;        // kMaxQueries x 8 floats
     int numQueries_ = 0;
     void enqueueQueries();
+    // in-run query records: the kinds, the pinned block (sized for the selected kinds' largest settings) and the stamp of the run
+    // whose records it holds -- the layout that run was enqueued with, pending until sync() has seen the run through
+    unsigned qrecKinds_ = 0;
+    float* qrecHost_ = nullptr;
+    enum class QrecRun { None, Pending, Ok } qrecRun_ = QrecRun::None;
+    unsigned qrecRunKinds_ = 0;
+    int qrecRunQueries_ = 0;
+    int qrecRunOffset_[6] = {0, 0, 0, 0, 0, 0}, qrecRunFloats_[6] = {0, 0, 0, 0, 0, 0};
+    void enqueueQueryRecords();  // behind a run's analysis, in front of its last kernel (nothing when no kind is selected)
     int* listHost_ = nullptr;
     int listCap_ = 0;
     // row-streaming air segments (pv_seg.h): rebuilt for every run (they avoid the tiles around the listener)
