@@ -995,6 +995,73 @@ PVA_EXPORT int PvAmdHostBandCoefs(int fs, const float* centreHz, int n, int frac
 /* CPU only: filter and record above applied to one impulse response p[T] with 0 <= onset < T and n (1 .. PVA_BANDS_MAX)
  * coefficient sets of 10 floats; the restatement the tests hold the kernel to */
 PVA_EXPORT int PvAmdHostBandMetrics(const float* p, int T, int fs, int onset, const float* coefs10n, int n, PvAmdBandMetrics* out12n);
+/* ---- Modulation: the modulation transfer function and modulation transfer index of every reached cell, per band ----
+ * How intelligible speech is at a cell: a room smears the slow intensity modulations (0.63 .. 12.5 Hz) that carry speech, and the
+ * modulation transfer function m(F) says by how much (Schroeder 1981; IEC 60268-16, indirect method: m(F) is the normalised
+ * Fourier transform of the squared, band-filtered impulse response).  PvAmdComputeModulation reduces the history of the LAST
+ * COMPLETED run to 15 floats per band and cell in one walk per band on the device (pv_modulation.hip).  It touches no run and no
+ * result map.
+ * Settings: the bands of PvAmdSetBands (n bands, their ten float32 coefficients, either fraction) and M = 14 modulation
+ * frequencies F[i] (Hz).  The default is the IEC third-octave series 0.63, 0.8, 1, 1.25, 1.6, 2, 2.5, 3.15, 4, 5, 6.3, 8, 10, 12.5.
+ * Table (T = the run's steps): built on the host in double with the host libm, row t = 0 .. T - 1, 28 floats per row:
+ *   ph = (2.0 * M_PI * (double)F[i] * (double)t) / (double)fs;   row[2 i] = (float)cos(ph),  row[2 i + 1] = (float)sin(ph)
+ *   t is the ABSOLUTE step, not t - t0: the magnitude does not depend on the time origin.  The device evaluates no trigonometric
+ *   function.
+ * For result cell s = X * gy + Y with onset t0 = (int)delay[s], per band:
+ *   y(t)   the band metrics' filtered sample: the same two sections, the same backward walk from T - 1 (state +0.0f) down to t0;
+ *          the walk STOPS at t0
+ *   e(t) = y(t) * y(t)
+ *   in DECREASING t from +0.0f, every product and sum rounded on its own (no FMA), denormals kept:
+ *      E += e;     re[i] += e * row_t[2 i];     im[i] += e * row_t[2 i + 1]
+ *   then per modulation frequency (division and sqrtf correctly rounded; log10f is glibc's):
+ *      a = re[i] / E;   b = im[i] / E;   m[i] = sqrtf((a * a) + (b * b))
+ *        (the ratios are taken first, so that re^2 + im^2 cannot underflow in a faint cell)
+ *      snr[i] = +15.0f where m[i] >= 1.0f, else v = 10.0f * log10f(m[i] / (1.0f - m[i])) clamped:
+ *               v < -15.0f ? -15.0f : (v > 15.0f ? 15.0f : v)                       (a NaN stays a NaN)
+ *      ti[i]  = (snr[i] + 15.0f) / 30.0f
+ *   mti = (the sequential sum of ti[0 .. 13] from +0.0f) / 14.0f
+ *   A band with E == 0 gives 15 quiet NaNs.  Nothing else is special-cased.
+ * Record per band (15 floats): m[0 .. 13], mti.  A cell WITHOUT an onset in that run holds 15 n quiet NaNs; nothing is carried
+ * over from earlier runs.
+ * What this is NOT: a full speech transmission index (STI) needs the seven octave bands from 125 Hz to 8 kHz.  A grid carries only
+ * the bands below its gridResolution, and PvAmdSetBands refuses a band at or above fs / 2 -- so what most solvers yield is the
+ * per-band MTI and, through PvAmdCombineMti, a PARTIAL index over the two or three bands they have.  No noise, masking or
+ * level-dependent correction of IEC 60268-16 is applied, and the library holds no table of band weights.
+ * Device storage: the table (28 x 4 bytes per step) and 15 n x 4 bytes per cell of the history window, allocated by the first
+ * PvAmdComputeModulation (again when n changes), freed by PvAmdSetBands(n = 0) and with the solver.  Lifetime and refusals are the
+ * band metrics', word for word, with the prefix "modulation: "; computing or reading with no bands set is refused ("no bands
+ * set"); PvAmdSetBands and PvAmdSetModulationFrequencies invalidate the records.  The other analysis kinds and this one do not
+ * invalidate each other. */
+#define PVA_MODULATION_FREQS 14
+typedef struct PvAmdModulation {
+    float m[PVA_MODULATION_FREQS], mti;
+} PvAmdModulation;
+/* Set the 14 modulation frequencies (copied); hz14 = NULL restores the default series.  Waits for a run in flight; invalidates the
+ * records.  -1 and nothing changed: a frequency that is not finite, negative or above fs / 2 */
+PVA_EXPORT int PvAmdSetModulationFrequencies(PvAmdSolver* s, const float* hz14);
+/* the 14 modulation frequencies in use */
+PVA_EXPORT int PvAmdGetModulationFrequencies(PvAmdSolver* s, float* hz14);
+/* Compute the modulation records of the LAST COMPLETED run of s (waits for a run in flight; works after every form of run, as
+ * PvAmdComputeBandMetrics).  Synchronous on the solver's own stream.  *ms (optional): device time of the passes. */
+PVA_EXPORT int PvAmdComputeModulation(PvAmdSolver* s, float* ms);
+/* gx*gy*n*15 floats: cell s = X*gy + Y, then band, then the 15 floats */
+PVA_EXPORT int PvAmdCopyModulation(PvAmdSolver* s, float* out15n);
+/* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc x n records, row-major */
+PVA_EXPORT int PvAmdCopyModulationBlock(PvAmdSolver* s, int r0, int c0, int nr, int nc, float* out15n);
+/* the n records at an emitter position, mapped to a cell exactly as PvAmdGetOutput does; a position off the map gives NaNs and 0 */
+PVA_EXPORT int PvAmdGetModulation(PvAmdSolver* s, float ex, float ey, float ez, PvAmdModulation* out15n);
+/* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T, n (1 .. PVA_BANDS_MAX) coefficient
+ * sets of 10 floats and the 14 modulation frequencies (NULL: the default); the restatement the tests hold the kernel to */
+PVA_EXPORT int PvAmdHostModulation(const float* p, int T, int fs, int onset, const float* coefs10n, int n, const float* hz14,
+                                   PvAmdModulation* out15n);
+/* CPU only: the table above, T rows of 28 floats (hz14 = NULL: the default) */
+PVA_EXPORT int PvAmdHostModulationTable(int T, int fs, const float* hz14, float* out28T);
+/* CPU only: combine the MTI of n (1 .. PVA_BANDS_MAX) adjacent bands into one index, in float32, sequentially from +0.0f:
+ *   *out = clamp((sum over k < n of (alpha[k] * mti[k])) - (sum over k < n - 1 of (beta[k] * sqrtf(mti[k] * mti[k + 1]))))
+ *   clamp(v) = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v)                              (a NaN stays a NaN)
+ * alpha: n weights, beta: n - 1 redundancy weights (may be NULL for n = 1) -- the caller supplies the IEC 60268-16 values for the
+ * bands it has.  Over fewer than the seven octaves 125 Hz .. 8 kHz the result is a partial index, not an STI. */
+PVA_EXPORT int PvAmdCombineMti(const float* mti, const float* alpha, const float* beta, int n, float* out);
 /* ---- Spectrum: the transfer function from the listener to every reached cell, at chosen frequencies ----
  * How loud the room is at ONE frequency at one position (room modes and their nodal lines, comb filtering behind an obstacle,
  * per-band gains): PvAmdComputeSpectrum reduces the history of the LAST COMPLETED run to three floats per bin and cell in one

@@ -62,6 +62,9 @@ def main(argv=None):
                     help="add the band metrics (decay times and clarity of the band-filtered response) of each emitter's cell for "
                          "the bands centred at these frequencies")
     ap.add_argument("--band-fraction", type=int, default=1, choices=(1, 3), help="octave (1, default) or third-octave (3) bands")
+    ap.add_argument("--modulation", action="store_true",
+                    help="with --bands: add the modulation transfer function (m at the 14 IEC modulation frequencies) and the "
+                         "modulation transfer index of each band at each emitter's cell")
     ap.add_argument("--in-run-records", action="store_true",
                     help="take the room metrics, decay times, lateral fraction, echogram, echo criterion and lobes from records "
                          "computed inside the run for the emitters' cells (at most 64 emitters) instead of from whole-map passes "
@@ -69,6 +72,8 @@ def main(argv=None):
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
+    if a.modulation and not a.bands:
+        ap.error("--modulation: needs --bands")
     boxes = api.load_pv(a.scene)
     if a.save:
         api.save_pv(a.save, boxes)
@@ -117,6 +122,8 @@ def main(argv=None):
         if a.bands:
             s.set_bands(a.bands, a.band_fraction)
             s.compute_band_metrics()
+        if a.modulation:
+            s.compute_modulation()
         if a.spectrum:
             s.set_spectrum_bins(a.spectrum)
             s.compute_spectrum()
@@ -153,6 +160,12 @@ def main(argv=None):
                 out["emitters"][-1]["bandMetrics"] = [
                     dict([("hz", float(hz)), ("fraction", a.band_fraction)] + [(n, float(v)) for n, v in zip(api.BAND_METRIC_NAMES, r)])
                     for hz, r in zip(a.bands, m)]
+            if a.modulation:
+                m = s.modulation_at(e)
+                out["emitters"][-1]["modulation"] = {
+                    "hz": [float(v) for v in s.modulation_frequencies()],
+                    "bands": [{"hz": float(hz), "fraction": a.band_fraction, "m": [float(v) for v in r[:-1]], "mti": float(r[-1])}
+                              for hz, r in zip(a.bands, m)]}
             if a.spectrum:
                 m = s.spectrum_at(e)
                 out["emitters"][-1]["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],

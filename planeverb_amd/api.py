@@ -318,6 +318,15 @@ SYMBOLS = {
     "PvAmdGetBandMetrics": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
     "PvAmdHostBandCoefs": (C.c_int, [C.c_int, _fp, C.c_int, C.c_int, _fp]),
     "PvAmdHostBandMetrics": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
+    "PvAmdSetModulationFrequencies": (C.c_int, [_vp, _fp]),
+    "PvAmdGetModulationFrequencies": (C.c_int, [_vp, _fp]),
+    "PvAmdComputeModulation": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyModulation": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyModulationBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdGetModulation": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
+    "PvAmdHostModulation": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
+    "PvAmdHostModulationTable": (C.c_int, [C.c_int, C.c_int, _fp, _fp]),
+    "PvAmdCombineMti": (C.c_int, [_fp, _fp, _fp, C.c_int, _fp]),
     "PvAmdSetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetSpectrumBins": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdGetSpectrumSource": (C.c_int, [_vp, _fp]),
@@ -870,6 +879,56 @@ def host_band_metrics(p, fs, onset, coefs):
     _check(lib().PvAmdHostBandMetrics(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(c) if c.size else None,
                                       int(c.shape[0]), _f(out)))
     return out
+
+
+MODULATION_FREQS = 14  # PVA_MODULATION_FREQS
+MODULATION_DEFAULT_HZ = (0.63, 0.8, 1.0, 1.25, 1.6, 2.0, 2.5, 3.15, 4.0, 5.0, 6.3, 8.0, 10.0, 12.5)  # IEC 60268-16
+
+
+def _hz14(hz):
+    if hz is None:
+        return None
+    h = np.ascontiguousarray(hz, np.float32).reshape(-1)
+    if h.size != MODULATION_FREQS:
+        raise ValueError("modulation: %d modulation frequencies, or None for the default" % MODULATION_FREQS)
+    return h
+
+
+def host_modulation_table(T, fs, hz=None):
+    """PvAmdHostModulationTable: float32 [T, 14, 2] -- (cos, sin) of every modulation frequency hz (None: the default series) at
+    every absolute step, computed in double on the CPU"""
+    h = _hz14(hz)
+    out = np.empty((max(int(T), 0), MODULATION_FREQS, 2), np.float32)
+    _check(lib().PvAmdHostModulationTable(int(T), int(fs), _f(h) if h is not None else None, _f(out)))
+    return out
+
+
+def host_modulation(p, fs, onset, coefs, hz=None):
+    """PvAmdHostModulation: float32 [n, 15] (m at the 14 modulation frequencies hz -- None: the default series -- then the band's
+    modulation transfer index) of one impulse response p[T] with its onset step, filtered backwards in time through the n
+    coefficient sets coefs[n, 10] -- the definition of include/planeverb_amd.h (PvAmdModulation) on the CPU"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    c = np.ascontiguousarray(coefs, np.float32).reshape(-1, 10)
+    h = _hz14(hz)
+    out = np.empty((c.shape[0], MODULATION_FREQS + 1), np.float32)
+    _check(lib().PvAmdHostModulation(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(c) if c.size else None,
+                                     int(c.shape[0]), _f(h) if h is not None else None, _f(out)))
+    return out
+
+
+def combine_mti(mti, alpha, beta=()):
+    """PvAmdCombineMti: sum(alpha[k] mti[k]) - sum(beta[k] sqrt(mti[k] mti[k + 1])) in float32, clamped to [0, 1]: the per-band
+    modulation transfer indices of n adjacent bands combined with the caller's IEC 60268-16 weights (n alpha, n - 1 beta).  Over
+    fewer than the seven octaves 125 Hz .. 8 kHz this is a partial index, not an STI"""
+    m = np.ascontiguousarray(mti, np.float32).reshape(-1)
+    a = np.ascontiguousarray(alpha, np.float32).reshape(-1)
+    b = np.ascontiguousarray(beta, np.float32).reshape(-1)
+    if a.size != m.size or b.size != max(m.size - 1, 0):
+        raise ValueError("combine_mti: n indices, n weights alpha and n - 1 weights beta")
+    out = C.c_float(0.0)
+    _check(lib().PvAmdCombineMti(_f(m) if m.size else None, _f(a) if a.size else None, _f(b) if b.size else None, int(m.size),
+                                 C.byref(out)))
+    return np.float32(out.value)
 
 
 SPECTRUM_MAX_BINS = 32  # PVA_SPECTRUM_MAX_BINS
@@ -1770,6 +1829,44 @@ class Solver:
         """float32 [n, 12] at an emitter position (the cell get_output reads); NaNs off the map"""
         out = np.empty((len(self.bands()[0]), 12), np.float32)
         _check(lib().PvAmdGetBandMetrics(self._h, *[float(v) for v in pos], _f(out)))
+        return out
+
+    def set_modulation_frequencies(self, hz=None):
+        """the 14 modulation frequencies (Hz, each in [0, fs / 2]) compute_modulation evaluates; None restores the default series
+        (MODULATION_DEFAULT_HZ)"""
+        h = _hz14(hz)
+        _check(lib().PvAmdSetModulationFrequencies(self._h, _f(h) if h is not None else None))
+
+    def modulation_frequencies(self):
+        """float32 [14]: the modulation frequencies in use"""
+        out = np.empty(MODULATION_FREQS, np.float32)
+        _check(lib().PvAmdGetModulationFrequencies(self._h, _f(out)))
+        return out
+
+    def compute_modulation(self):
+        """the modulation transfer function and index per band of set_bands of the last completed run, on the device; returns the
+        device time of the passes in milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeModulation(self._h, C.byref(ms)))
+        return ms.value
+
+    def modulation(self):
+        """float32 [gx, gy, n, 15] (m at the 14 modulation frequencies, then mti); NaN where the cell has no onset in the run they
+        were computed for"""
+        out = np.empty((self.gx, self.gy, len(self.bands()[0]), MODULATION_FREQS + 1), np.float32)
+        _check(lib().PvAmdCopyModulation(self._h, _f(out)))
+        return out
+
+    def modulation_block(self, r0, c0, nr, nc):
+        """the records [nr, nc, n, 15] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
+        out = np.empty((nr, nc, len(self.bands()[0]), MODULATION_FREQS + 1), np.float32)
+        _check(lib().PvAmdCopyModulationBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def modulation_at(self, pos):
+        """float32 [n, 15] at an emitter position (the cell get_output reads); NaNs off the map"""
+        out = np.empty((len(self.bands()[0]), MODULATION_FREQS + 1), np.float32)
+        _check(lib().PvAmdGetModulation(self._h, *[float(v) for v in pos], _f(out)))
         return out
 
     def set_spectrum_bins(self, hz):

@@ -12,6 +12,7 @@
 #include "pv_context.h"
 #include "pv_core.h"
 #include "pv_bands.h"
+#include "pv_modulation.h"
 #include "pv_decay.h"
 #include "pv_echo.h"
 #include "pv_echogram.h"
@@ -1501,6 +1502,73 @@ int PvAmdGetBandMetrics(PvAmdSolver* h, float ex, float ey, float ez, PvAmdBandM
     return ret(h, h->s->bandMetricsAt(ex, ez, reinterpret_cast<float*>(out12n)));
 } PV_API_CATCH(-1)
 
+// modulation (pv_modulation.hip): single whole-grid solvers only, as the band metrics; every refusal says "modulation: ...".  The
+// frequencies are checked against the handle's own grid before anything else happens (pv_modulation.h modulationFreqsError)
+static bool modulationHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "modulation: " + g_lastError;
+    return false;
+}
+
+int PvAmdSetModulationFrequencies(PvAmdSolver* h, const float* hz14) try {
+    if (!h) {
+        g_lastError = "modulation: null solver handle";
+        return -1;
+    }
+    if (hz14) {
+        if (const char* e = modulationFreqsError(hz14, (int)h->spec.fs)) {
+            g_lastError = e;
+            return -1;
+        }
+    }
+    if (!modulationHandle(h)) return -1;
+    return ret(h, h->s->setModulationFrequencies(hz14));
+} PV_API_CATCH(-1)
+
+int PvAmdGetModulationFrequencies(PvAmdSolver* h, float* hz14) try {
+    if (!modulationHandle(h)) return -1;
+    if (!hz14) {
+        g_lastError = "modulation: PvAmdGetModulationFrequencies: null output";
+        return -1;
+    }
+    h->s->modulationFrequencies(hz14);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdComputeModulation(PvAmdSolver* h, float* ms) try {
+    if (!modulationHandle(h)) return -1;
+    return ret(h, h->s->computeModulation(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyModulation(PvAmdSolver* h, float* out15n) try {
+    if (!modulationHandle(h)) return -1;
+    if (!out15n) {
+        g_lastError = "modulation: PvAmdCopyModulation: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyModulationBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out15n));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyModulationBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out15n) try {
+    if (!modulationHandle(h)) return -1;
+    if (!out15n) {
+        g_lastError = "modulation: PvAmdCopyModulationBlock: null output";
+        return -1;
+    }
+    return ret(h, h->s->copyModulationBlock(r0, c0, nr, nc, out15n));
+} PV_API_CATCH(-1)
+
+int PvAmdGetModulation(PvAmdSolver* h, float ex, float ey, float ez, PvAmdModulation* out15n) try {
+    (void)ey;  // world y is ignored, as everywhere
+    if (!modulationHandle(h)) return -1;
+    if (!out15n) {
+        g_lastError = "modulation: PvAmdGetModulation: null output";
+        return -1;
+    }
+    static_assert(sizeof(PvAmdModulation) == kModFloats * sizeof(float), "fifteen floats");
+    return ret(h, h->s->modulationAt(ex, ez, reinterpret_cast<float*>(out15n)));
+} PV_API_CATCH(-1)
+
 // spectrum (pv_spectrum.hip): single whole-grid solvers only, as the room metrics.  The bins are checked against the handle's
 // own grid before anything else happens (pv_spectrum.h spectrumBinsError, the rule the host calls apply too)
 int PvAmdSetSpectrumBins(PvAmdSolver* h, const float* hz, int n) try {
@@ -1987,6 +2055,49 @@ int PvAmdHostBandMetrics(const float* p, int T, int fs, int onset, const float* 
     }
     for (int j = 0; j < n; ++j)
         bandMetricsOfIr(p, T, fs, onset, coefs10n + (size_t)kBandCoefs * j, reinterpret_cast<float*>(out12n) + (size_t)kBandFloats * j);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostModulationTable(int T, int fs, const float* hz14, float* out28T) try {
+    if (T <= 0 || fs <= 0 || !out28T) {
+        g_lastError = "modulation: PvAmdHostModulationTable: T > 0, fs > 0 and a table of T * 28 floats";
+        return -1;
+    }
+    if (!hz14) hz14 = kModDefaultHz;
+    if (const char* e = modulationFreqsError(hz14, fs)) {
+        g_lastError = e;
+        return -1;
+    }
+    modulationTable(T, fs, hz14, out28T);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostModulation(const float* p, int T, int fs, int onset, const float* coefs10n, int n, const float* hz14,
+                        PvAmdModulation* out15n) try {
+    if (!p || !coefs10n || !out15n || T <= 0 || fs <= 0 || onset < 0 || onset >= T || n < 1 || n > kBandsMax) {
+        g_lastError =
+            "modulation: PvAmdHostModulation: an impulse response p[T], T > 0, fs > 0, 0 <= onset < T, 1 .. 8 coefficient sets and an "
+            "output of n records";
+        return -1;
+    }
+    if (!hz14) hz14 = kModDefaultHz;
+    if (const char* e = modulationFreqsError(hz14, fs)) {
+        g_lastError = e;
+        return -1;
+    }
+    std::vector<float> tab((size_t)T * kModRowFloats);
+    modulationTable(T, fs, hz14, tab.data());
+    for (int j = 0; j < n; ++j)
+        modulationOfIr(p, T, onset, coefs10n + (size_t)kBandCoefs * j, tab.data(), reinterpret_cast<float*>(out15n) + (size_t)kModFloats * j);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdCombineMti(const float* mti, const float* alpha, const float* beta, int n, float* out) try {
+    if (!mti || !alpha || !out || n < 1 || n > kBandsMax || (n > 1 && !beta)) {
+        g_lastError = "modulation: PvAmdCombineMti: n (1 .. 8) indices and weights alpha, n - 1 weights beta and an output";
+        return -1;
+    }
+    *out = combineMti(mti, alpha, beta, n);
     return 0;
 } PV_API_CATCH(-1)
 

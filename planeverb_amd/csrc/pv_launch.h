@@ -169,6 +169,13 @@ void launchQueryRecords(const AnalyzeArgs& a, const QueryRecordArgs& q, hipStrea
 void launchBandMetrics(const AnalyzeArgs& a, const float* coefs, int n, float* out, hipStream_t stream);
 int bandMetricsBlock();
 
+// ---- pv_modulation.hip: per-cell, per-band modulation transfer function and index
+// modulation records of the last completed run (pv_modulation.hip) for n bands: coefs as launchBandMetrics takes them; tab = row 0
+// of the twiddle table on the DEVICE (pv_modulation.h: kModRowStride floats from step to step, T rows, kModTablePad zero rows in front
+// of row 0); out = n x kModFloats planes of a.histPlane floats (band j, float k at plane j * kModFloats + k), indexed by the cell's
+// offset inside a history plane; NaN where the cell has no onset in that run.  One launch per band
+void launchModulation(const AnalyzeArgs& a, const float* coefs, int n, const float* tab, float* out, hipStream_t stream);
+
 // ---- pv_echo.hip: per-cell echo criterion (speech and music)
 // echo criterion of the last completed run (pv_echo.hip): out = kEchoFloats planes of a.histPlane floats, indexed by the cell's
 // offset inside a history plane; NaN where the cell has no onset in that run.  The caller has checked echoFsOk(a.fs)

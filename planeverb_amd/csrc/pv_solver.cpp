@@ -19,6 +19,7 @@
 
 #include "pv_launch.h"
 #include "pv_bands.h"
+#include "pv_modulation.h"
 #include "pv_decay.h"
 #include "pv_echo.h"
 #include "pv_echogram.h"
@@ -707,6 +708,10 @@ Solver::~Solver() {
     if (bands_) hipFree(bands_);
     for (auto& e : bandsEv_)
         if (e) hipEventDestroy(e);
+    for (float* p : {modTab_, modulation_})
+        if (p) hipFree(p);
+    for (auto& e : modulationEv_)
+        if (e) hipEventDestroy(e);
     if (lateral_) hipFree(lateral_);
     for (auto& e : lateralEv_)
         if (e) hipEventDestroy(e);
@@ -801,7 +806,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     return id;
 }
 
@@ -812,7 +817,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     return true;
 }
 
@@ -823,7 +828,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     return true;
 }
 
@@ -895,14 +900,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -1049,7 +1054,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     return true;
 }
 
@@ -1089,7 +1094,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     return true;
 }
 
@@ -2153,7 +2158,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;       // (the history the records were made from is about to be overwritten)
+    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     qrecRun_ = QrecRun::None;    // (the pinned block is about to be overwritten, or this run leaves no records)
     if (!applyGeometry()) return false;
@@ -3614,12 +3619,17 @@ bool Solver::setBands(const float* centreHz, int n, int fraction) {
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
     bandsValid_ = false;
     bandsHostValid_ = false;
+    modulationValid_ = false;  // (the modulation records are per band)
+    modulationHostValid_ = false;
     bandHz_.clear();
     bandCoefs_.clear();
     if (n == 0) {
         if (bands_) hipFree(bands_);
         bands_ = nullptr;
         bandsPlanes_ = 0;
+        if (modulation_) hipFree(modulation_);
+        modulation_ = nullptr;
+        modulationPlanes_ = 0;
         return true;
     }
     bandHz_.assign(centreHz, centreHz + n);
@@ -3720,6 +3730,121 @@ bool Solver::bandMetricsAt(float ex, float ez, float* out12n) {
         return true;
     }
     return copyBandMetricsBlock(cx, cy, 1, 1, out12n);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// modulation (pv_modulation.hip): everything as the band metrics above, with 15 planes per band; the modulation frequencies are
+// never unset, a solver that was given none uses the default series
+// ----------------------------------------------------------------------------------------------------------------
+
+bool Solver::setModulationFrequencies(const float* hz14) {
+    if (isSlab()) return fail("modulation: not available on a slab");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    modulationValid_ = false;
+    modulationHostValid_ = false;
+    modTabValid_ = false;
+    for (int i = 0; i < kModFreqs; ++i) modHz_[i] = hz14 ? hz14[i] : kModDefaultHz[i];
+    return true;
+}
+
+void Solver::modulationFrequencies(float* hz14) const {
+    for (int i = 0; i < kModFreqs; ++i) hz14[i] = modHz_[i];
+}
+
+bool Solver::computeModulation(float* ms) {
+    if (isSlab()) return fail("modulation: not available on a slab");
+    if (opt_.streaming) return fail("modulation: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("modulation: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    if (bandHz_.empty()) return fail("modulation: no bands set (PvAmdSetBands)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("modulation: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("modulation: the last run ended in error");
+    const int n = (int)bandHz_.size();
+    if (modulation_ && modulationPlanes_ != kModFloats * n) {
+        hipFree(modulation_);
+        modulation_ = nullptr;
+    }
+    if (!modulation_) {
+        if (!dalloc(&modulation_, (size_t)kModFloats * n * (size_t)histPlane_, false)) return false;
+        modulationPlanes_ = kModFloats * n;
+    }
+    const int T = T_;  // the run's steps (PVA_OPT_NUM_STEPS): the planes of the history
+    const size_t rows = (size_t)T + kModTablePad;
+    if (!modTab_ && !dalloc(&modTab_, rows * kModRowStride, false)) return false;
+    if (!modTabValid_) {  // rows -kModTablePad .. -1: zero; rows 0 .. T - 1: the table, 28 floats and four zeros each
+        std::vector<float> def((size_t)T * kModRowFloats), tab(rows * kModRowStride, 0.f);
+        modulationTable(T, (int)g_.fs, modHz_, def.data());
+        for (int t = 0; t < T; ++t)
+            std::memcpy(&tab[((size_t)t + kModTablePad) * kModRowStride], &def[(size_t)t * kModRowFloats], kModRowFloats * sizeof(float));
+        if (!hipOk(hipMemcpyAsync(modTab_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream_), "modulation table upload") ||
+            !hipOk(hipStreamSynchronize(stream_), "modulation table sync"))
+            return false;
+        modTabValid_ = true;
+    }
+    for (auto& e : modulationEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    modulationValid_ = false;
+    modulationHostValid_ = false;
+    hipEventRecord(modulationEv_[0], stream_);
+    launchModulation(analyzeArgs(lastLx_, lastLz_), bandCoefs_.data(), n, modTab_ + (size_t)kModTablePad * kModRowStride, modulation_, stream_);
+    hipEventRecord(modulationEv_[1], stream_);
+    if (!hipOk(hipGetLastError(), "modulation launch") || !hipOk(hipStreamSynchronize(stream_), "modulation sync")) return false;
+    if (ms) hipEventElapsedTime(ms, modulationEv_[0], modulationEv_[1]);
+    modulationDyn_ = dynCur_;
+    modulationValid_ = true;
+    return true;
+}
+
+bool Solver::fetchModulation() {
+    if (bandHz_.empty()) return fail("modulation: no bands set (PvAmdSetBands)");
+    if (!modulationValid_)
+        return fail("modulation: not computed for the last run, the current geometry, the current bands and the current modulation "
+                    "frequencies (PvAmdComputeModulation)");
+    if (modulationHostValid_) return true;
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    modulationHost_.resize((size_t)modulationPlanes_ * (size_t)histPlane_);
+    if (!hipOk(hipMemcpyAsync(modulationHost_.data(), modulation_, modulationHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "modulation copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "modulation sync"))
+        return false;
+    modulationHostValid_ = true;
+    return true;
+}
+
+bool Solver::copyModulationBlock(int r0, int c0, int nr, int nc, float* out) {
+    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("modulation: block outside the map");
+    if (!fetchModulation()) return false;
+    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
+    const int wr0 = modulationDyn_.histRow0 - geo_.G, wc0 = modulationDyn_.histCol0 - geo_.G;
+    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
+    const int nf = modulationPlanes_;
+    const float qnan = std::numeric_limits<float>::quiet_NaN();
+    for (int r = 0; r < nr; ++r)
+        for (int c = 0; c < nc; ++c) {
+            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
+            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
+            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
+                for (int k = 0; k < nf; ++k) o[k] = qnan;
+                continue;
+            }
+            const int ti = hr / rxi_, tj = hc / wi_;
+            const size_t g = ((size_t)(ti * modulationDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
+            for (int k = 0; k < nf; ++k) o[k] = modulationHost_[(size_t)k * histPlane_ + g];
+        }
+    return true;
+}
+
+bool Solver::modulationAt(float ex, float ez, float* out15n) {
+    int cx, cy;
+    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
+        if (!fetchModulation()) return false;
+        for (int k = 0; k < modulationPlanes_; ++k) out15n[k] = std::numeric_limits<float>::quiet_NaN();
+        return true;
+    }
+    return copyModulationBlock(cx, cy, 1, 1, out15n);
 }
 
 // ----------------------------------------------------------------------------------------------------------------

@@ -159,11 +159,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = false;
+        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -314,6 +314,16 @@ public:
     bool computeBandMetrics(float* ms);
     bool copyBandMetricsBlock(int r0, int c0, int nr, int nc, float* out);
     bool bandMetricsAt(float ex, float ez, float* out12n);
+    // Modulation (pv_modulation.hip; include/planeverb_amd.h PvAmdModulation): the modulation transfer function at 14 modulation
+    // frequencies and the modulation transfer index of the last completed run per band of setBands; lifetime and refusals as the
+    // band metrics', and a change of bands or of the modulation frequencies invalidates the records.  setModulationFrequencies:
+    // the caller has validated hz14 (pv_modulation.h modulationFreqsError); nullptr restores the default; waits for a run in
+    // flight.  out: nr x nc x n records of fifteen floats, NaN where the cell has no onset in that run
+    bool setModulationFrequencies(const float* hz14);
+    void modulationFrequencies(float* hz14) const;
+    bool computeModulation(float* ms);
+    bool copyModulationBlock(int r0, int c0, int nr, int nc, float* out);
+    bool modulationAt(float ex, float ez, float* out15n);
     // Spectrum (pv_spectrum.hip; include/planeverb_amd.h Spectrum): transfer functions of the last completed run at the bins set
     // here, lifetime and refusals as the room metrics'.  setSpectrumBins: the caller has validated hz (pv_spectrum.h
     // spectrumBinsError); n = 0 clears and frees; waits for a run in flight.  out: nr x nc x n records of three floats
@@ -604,6 +614,22 @@ private:
     bool bandsHostValid_ = false;
     hipEvent_t bandsEv_[2] = {nullptr, nullptr};
     bool fetchBandMetrics();
+    // modulation (pv_modulation.h): the 14 modulation frequencies (the default until some are set) and their twiddle table on the
+    // device (kModTablePad zero rows, then T rows of 28 floats padded to 32), uploaded by the first computeModulation after a change; 15 n planes
+    // of histPlane_ floats -- band j at planes 15 j .. 15 j + 14 -- allocated by the first computeModulation and again when n
+    // changes.  modulationValid_ follows metricsValid_ and is also cleared by a change of bands or frequencies; no computation
+    // touches another's flag
+    float modHz_[14] = {0.63f, 0.8f, 1.0f, 1.25f, 1.6f, 2.0f, 2.5f, 3.15f, 4.0f, 5.0f, 6.3f, 8.0f, 10.0f, 12.5f};
+    float* modTab_ = nullptr;
+    bool modTabValid_ = false;
+    float* modulation_ = nullptr;
+    int modulationPlanes_ = 0;  // 15 n of the allocation
+    bool modulationValid_ = false;
+    DynParams modulationDyn_{};
+    std::vector<float> modulationHost_;
+    bool modulationHostValid_ = false;
+    hipEvent_t modulationEv_[2] = {nullptr, nullptr};
+    bool fetchModulation();
     // spectrum (pv_spectrum.h): the bins, their tables c / s [T * n] and source values (sre, sim, spow per bin) on the host; the
     // passes the bins are dealt to (specPasses_: a slice of the bins, the register block that takes it, where its table slice
     // starts in specTab_); 3 n planes of histPlane_ floats -- re, im, level of bin j at planes 3 j .. 3 j + 2 -- allocated by the
