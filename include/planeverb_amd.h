@@ -130,9 +130,48 @@ typedef struct PlaneverbCell {
  * buffer), 0 for a position outside the cell array, -1 when the module is not initialised / on error.  Waits for the
  * iteration in flight (the reference reads the cube while the worker rewrites it); a debugging call, like upstream. */
 PVA_EXPORT int PlaneverbGetImpulseResponse(float x, float y, float z, PlaneverbCell* out, int capacity);
+
+/* Emission records: the per-cell analysis records of Part 2 (room metrics, decay times, lateral fraction, echogram, echo
+ * criterion, lobes -- PVA_QREC_*, PvAmdSetQueryRecords) for the cells of the LIVE EMITTERS, by emission id.  `kinds` is a mask of
+ * PVA_QREC_*.  While any kind is selected, the worker latches, at the start of every iteration, the cells of the emitters alive at
+ * that moment -- in ascending id, ended ids skipped, the first PVA_RECORD_QUERIES_MAX (1024) DISTINCT cells inside the result map,
+ * sorted -- and that iteration computes the selected kinds for them with ONE launch inside its run (64 cells per wave), straight
+ * into pinned host memory.  The records become readable in the same publish step as the iteration's outputs: a caller that reads
+ * PlaneverbGetOutput and a record between two publishes (an unchanged PlaneverbIterationCount) sees one iteration.
+ *   The three setters validate at the call -- PlaneverbSetEmissionEchogram by PvAmdSetEchogram's rules, PlaneverbSetEmissionLobeWindows
+ * by PvAmdSetLobeWindows' rules (nEdges = 0: the default windows), PlaneverbSetEmissionRecords by PvAmdSetQueryRecords' (an
+ * unknown bit; PVA_QREC_ECHOGRAM with no slots set; the sampling-rate floors of the echo criterion and the default lobe windows)
+ * -- and return 0, or -1 with nothing changed and PvAmdLastError "emission records: ...".  They are refused while the module is
+ * down and in sparse-emitter mode (PlaneverbIsStreaming: "the full pressure history is not kept").  An accepted change is queued
+ * with the geometry changes and takes effect at an iteration boundary, on both solvers of the pipelined loop at the same one; the
+ * readers below describe the PUBLISHED iteration, so a change shows there one to three iterations later.  kinds = 0, the default,
+ * switches the records off and frees the solvers' pinned blocks: nothing is launched, latched or copied, and an iteration's
+ * launches are exactly those of a module that never called this.
+ *   PlaneverbEmissionRecordKinds: the kinds the published iteration carries (0 when the module is down or nothing is published).
+ * PlaneverbEmissionRecordFloats: floats of ONE kind in the published iteration (10, 8, 11, 1 + 3 nSlots, 10, 1 + 5 nWindows), -1 if
+ * it does not carry the kind.  PlaneverbEmissionRecordCells: the distinct cells it served, -1 when the module is down.
+ *   PlaneverbGetEmissionRecord reads the emitter's CURRENT position, maps it to a result cell as PlaneverbGetOutput does and looks
+ * the cell up in the published iteration's table.  It is lock-free like PlaneverbGetOutput: no device access, no lock, and no
+ * allocation.  It returns
+ *    1: the record was written -- bit for bit what PvAmdGet<Kind> gives at that position after PvAmdCompute<Kind> on the same run;
+ *    0: PlaneverbEmissionRecordFloats(kind) quiet NaNs were written: an id that was never issued or has ended; a position off the
+ *       map; a cell that is not in the table (the emitter was added or moved to another cell since the latch -- it gets its record
+ *       one iteration later, the rule sparse-emitter mode has for wet gain and RT60 -- or the cell lies beyond the cap); a cell
+ *       without an onset in that run;
+ *   -1: nothing was written: the module is down; `kind` is not exactly one known bit; the published iteration does not carry the
+ *       kind (not selected, or not in effect yet); `out` is NULL; `capacity` is below PlaneverbEmissionRecordFloats(kind). */
+PVA_EXPORT int PlaneverbSetEmissionRecords(unsigned kinds);
+PVA_EXPORT int PlaneverbSetEmissionEchogram(float slotSeconds, int nSlots);
+PVA_EXPORT int PlaneverbSetEmissionLobeWindows(const float* edgesSeconds, int nEdges);
+PVA_EXPORT unsigned PlaneverbEmissionRecordKinds(void);
+PVA_EXPORT int PlaneverbEmissionRecordFloats(unsigned kind);
+PVA_EXPORT int PlaneverbEmissionRecordCells(void);
+PVA_EXPORT int PlaneverbGetEmissionRecord(int emissionID, unsigned kind, float* out, int capacity);
 /* Load a .pv scene (PlaneverbSandbox/src/Editor/Editor.cpp:245-281) into the live module; returns #boxes or <0 */
 PVA_EXPORT int PlaneverbLoadScene(const char* pvPath);
-/* Number of completed simulation iterations since Init (an iteration = FDTD + analysis, PvContext.cpp:74-93) */
+/* Number of completed (published) simulation iterations since Init (an iteration = FDTD + analysis, PvContext.cpp:74-93).  The
+ * count changes in the publish step itself: PlaneverbGetOutput and PlaneverbGetEmissionRecord calls made between two reads of the
+ * same count all answer from that one iteration. */
 PVA_EXPORT long long PlaneverbIterationCount(void);
 /* Block until at least `count` iterations have completed, or timeoutMs elapsed; returns the iteration count */
 PVA_EXPORT long long PlaneverbWaitIterations(long long count, int timeoutMs);
@@ -559,6 +598,17 @@ PVA_EXPORT int PvAmdSetQueryRecords(PvAmdSolver* s, unsigned kinds);
 PVA_EXPORT unsigned PvAmdGetQueryRecordKinds(PvAmdSolver* s);
 PVA_EXPORT int PvAmdQueryRecordFloats(PvAmdSolver* s, unsigned kind);
 PVA_EXPORT int PvAmdGetQueriedRecords(PvAmdSolver* s, unsigned kind, float* out, int nQueries);
+/* Record queries: up to PVA_RECORD_QUERIES_MAX positions (n x {x,y,z}) of their own for the in-run records, mapped to result cells
+ * in the given order exactly as PvAmdSetOutputQueries maps its positions.  While n > 0 every following run computes the selected
+ * kinds for THESE cells instead of the output queries' cells -- still one launch, 64 queries per wave and one more block row per
+ * 64 -- and PvAmdGetQueriedRecords takes this n; PvAmdGetQueriedOutputs keeps serving the (<= 64) output queries.  n = 0, the
+ * default, returns to the output queries.  The pinned cell table and record block grow to the registered count (at most
+ * 1024 x 177 floats with every kind selected).  The call waits for a run in flight, and a change of the table invalidates the
+ * records until the next run has completed.  A record's bits do not depend on the other queries of the table.
+ *   Refused with -1 and nothing changed, PvAmdLastError "query records: ...": n outside 0 .. PVA_RECORD_QUERIES_MAX; NULL with
+ * n > 0; slab groups and slab ranks; sparse-emitter (PVA_OPT_STREAMING_ANALYSIS) solvers. */
+#define PVA_RECORD_QUERIES_MAX 1024
+PVA_EXPORT int PvAmdSetRecordQueries(PvAmdSolver* s, const float* xyz, int n);
 /* Whole result map: res8 = gx*gy*8 floats in AnalyzerResult order (Analyzer.h:13-21), delay = gx*gy */
 PVA_EXPORT int PvAmdCopyResults(PvAmdSolver* s, float* res8, float* delay);
 /* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records / onsets, row-major (either may be NULL) */

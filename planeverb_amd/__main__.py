@@ -29,6 +29,43 @@ def echogram_setting(s):
     return float(v[0]), int(v[1])
 
 
+def record_object(kind, m, slot_steps=0):
+    """the JSON object of one record (the key names of RECORD_KEYS)"""
+    if kind == api.QREC_ECHOGRAM:
+        return {"slotSteps": slot_steps, "n": float(m[0]), "e": [float(v) for v in m[1::3]], "ix": [float(v) for v in m[2::3]],
+                "iy": [float(v) for v in m[3::3]]}
+    if kind == api.QREC_LOBES:
+        return {"n": float(m[0]), "windows": [dict((n, float(v)) for n, v in zip(api.LOBE_NAMES, m[1 + 5 * w:6 + 5 * w]))
+                                              for w in range((len(m) - 1) // 5)]}
+    names = {api.QREC_ROOM_METRICS: api.ROOM_METRIC_NAMES, api.QREC_DECAY_TIMES: api.DECAY_TIME_NAMES,
+             api.QREC_LATERAL: api.LATERAL_FRACTION_NAMES, api.QREC_ECHO_CRITERION: api.ECHO_CRITERION_NAMES}[kind]
+    return dict((n, float(v)) for n, v in zip(names, m))
+
+
+RECORD_KEYS = {api.QREC_ROOM_METRICS: "roomMetrics", api.QREC_DECAY_TIMES: "decayTimes", api.QREC_LATERAL: "lateralFraction",
+               api.QREC_ECHOGRAM: "echogram", api.QREC_ECHO_CRITERION: "echoCriterion", api.QREC_LOBES: "lobes"}
+
+
+def live_emission_records(size, res, boxes, listener, emitters, echogram, lobes, slot_steps):
+    """all six record kinds of each emitter from the LIVE module (PlaneverbSetEmissionRecords / PlaneverbGetEmissionRecord): the
+    scene and the emitters go in as a game would put them, three iterations later the records are read by emission id"""
+    api.Init(api.Config((size, size), res, 0, ".", 0, api.pv_GPU))
+    try:
+        api.SetListenerPosition(listener)
+        for b in boxes:
+            api.AddGeometry(b)
+        ids = [api.Emit(e) for e in emitters]
+        api.SetEmissionEchogram(*echogram)
+        api.SetEmissionLobeWindows(lobes)
+        api.SetEmissionRecords(api.QREC_ALL)
+        target = api.IterationCount() + 3
+        if api.WaitIterations(target, 120000) < target or api.EmissionRecordKinds() != api.QREC_ALL:
+            raise api.PlaneverbError("the live module did not publish the emission records: " + api.last_error())
+        return [dict((RECORD_KEYS[k], record_object(k, api.GetEmissionRecord(i, k)[1], slot_steps)) for k in RECORD_KEYS) for i in ids]
+    finally:
+        api.Exit()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m planeverb_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -69,6 +106,10 @@ def main(argv=None):
                     help="take the room metrics, decay times, lateral fraction, echogram, echo criterion and lobes from records "
                          "computed inside the run for the emitters' cells (at most 64 emitters) instead of from whole-map passes "
                          "after it; the output is the same")
+    ap.add_argument("--emission-records", action="store_true",
+                    help="add all six record kinds of each emitter as the LIVE module serves them by emission id "
+                         "(PlaneverbSetEmissionRecords; --echogram and --lobes give their settings, default 0.005,16 and "
+                         "0.01,0.08), under the key names of --in-run-records")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
@@ -170,6 +211,14 @@ def main(argv=None):
                 m = s.spectrum_at(e)
                 out["emitters"][-1]["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],
                                                    "im": [float(v) for v in m[:, 1]], "levelDb": [float(v) for v in m[:, 2]]}
+        if a.emission_records:
+            echogram = a.echogram or (0.005, 16)
+            s.set_echogram(*echogram)  # (for the slot length in steps)
+            slot_steps = s.echogram_slots()[2]
+    if a.emission_records:
+        live = live_emission_records(size, a.res, boxes, a.listener, emitters, echogram, a.lobes or None, slot_steps)
+        for e, r in zip(out["emitters"], live):
+            e.update(r)
     print(json.dumps(out, indent=1))
     return 0
 

@@ -183,6 +183,13 @@ SYMBOLS = {
     "PlaneverbWorkerError": (C.c_char_p, []),
     "PlaneverbIsStreaming": (C.c_int, []),
     "PlaneverbGetImpulseResponse": (C.c_int, [C.c_float] * 3 + [C.POINTER(PlaneverbCell), C.c_int]),
+    "PlaneverbSetEmissionRecords": (C.c_int, [C.c_uint]),
+    "PlaneverbSetEmissionEchogram": (C.c_int, [C.c_float, C.c_int]),
+    "PlaneverbSetEmissionLobeWindows": (C.c_int, [_fp, C.c_int]),
+    "PlaneverbEmissionRecordKinds": (C.c_uint, []),
+    "PlaneverbEmissionRecordFloats": (C.c_int, [C.c_uint]),
+    "PlaneverbEmissionRecordCells": (C.c_int, []),
+    "PlaneverbGetEmissionRecord": (C.c_int, [C.c_int, C.c_uint, _fp, C.c_int]),
     "PvAmdDeviceCount": (C.c_int, []),
     "PvAmdLastError": (C.c_char_p, []),
     "PvAmdVersion": (C.c_char_p, []),
@@ -268,6 +275,7 @@ SYMBOLS = {
     "PvAmdGetQueryRecordKinds": (C.c_uint, [_vp]),
     "PvAmdQueryRecordFloats": (C.c_int, [_vp, C.c_uint]),
     "PvAmdGetQueriedRecords": (C.c_int, [_vp, C.c_uint, _fp, C.c_int]),
+    "PvAmdSetRecordQueries": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdCopyResults": (C.c_int, [_vp, _fp, _fp]),
     "PvAmdCopyResultsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "PvAmdGetImpulseResponse": (C.c_int, [_vp, C.c_int, C.c_int, _fp]),
@@ -593,6 +601,46 @@ def GetImpulseResponse(pos):
     return out
 
 
+def SetEmissionRecords(kinds):
+    """the record kinds (a mask of QREC_*) every following iteration computes for the cells of the live emitters; 0 switches off"""
+    _check(lib().PlaneverbSetEmissionRecords(int(kinds)))
+
+
+def SetEmissionEchogram(slot_seconds, n_slots):
+    _check(lib().PlaneverbSetEmissionEchogram(float(slot_seconds), int(n_slots)))
+
+
+def SetEmissionLobeWindows(edges_seconds=None):
+    """the lobe windows' edges in seconds; None or empty: the default windows"""
+    e = np.ascontiguousarray([] if edges_seconds is None else edges_seconds, np.float32).reshape(-1)
+    _check(lib().PlaneverbSetEmissionLobeWindows(_f(e) if len(e) else None, len(e)))
+
+
+def EmissionRecordKinds():
+    """the kinds the PUBLISHED iteration carries"""
+    return int(lib().PlaneverbEmissionRecordKinds())
+
+
+def EmissionRecordFloats(kind):
+    """floats of ONE kind in the published iteration, -1 if it does not carry the kind"""
+    return int(lib().PlaneverbEmissionRecordFloats(int(kind)))
+
+
+def EmissionRecordCells():
+    """distinct cells the published iteration served, -1 when the module is down"""
+    return int(lib().PlaneverbEmissionRecordCells())
+
+
+def GetEmissionRecord(eid, kind, capacity=None):
+    """(ok, float32 array) of ONE kind for the emitter's current cell in the published iteration: ok = 1 the record, 0 quiet NaNs
+    (ended or unknown id, off the map, a cell not in the iteration's table or without an onset), -1 nothing written (the array
+    then keeps its fill of zeros; it is empty when the iteration does not carry the kind)"""
+    n = EmissionRecordFloats(kind) if capacity is None else int(capacity)
+    out = np.zeros(max(n, 0), np.float32)
+    ok = lib().PlaneverbGetEmissionRecord(int(eid), int(kind), _f(out) if len(out) else None, len(out))
+    return int(ok), out
+
+
 def IsRunning():
     return bool(lib().PlaneverbIsRunning())
 
@@ -820,6 +868,7 @@ QREC_ECHOGRAM = 8
 QREC_ECHO_CRITERION = 16
 QREC_LOBES = 32
 QREC_ALL = 63
+RECORD_QUERIES_MAX = 1024  # PVA_RECORD_QUERIES_MAX
 LOBES_DEFAULT_EDGES = (0.01, 0.08)
 LOBE_NAMES = ("e", "xp", "xn", "yp", "yn")
 LOBE_PATTERN_OMNI, LOBE_PATTERN_CARDIOID = 0, 1
@@ -1543,10 +1592,18 @@ class Solver:
     def queried_records(self, kind):
         """float32 [n_queries, floats] of ONE kind for the last run (waits for it; no GPU work): each row bit for bit what
         <kind>_at(position) returns after compute_<kind>() on the same run; NaN rows off the map and where no sound arrived"""
-        n = getattr(self, "_nq", 0)
+        n = getattr(self, "_nrq", 0) or getattr(self, "_nq", 0)
         out = np.empty((n, self.query_record_floats(kind)), np.float32)
         _check(lib().PvAmdGetQueriedRecords(self._h, int(kind), _f(out) if n else None, n))
         return out
+
+    def set_record_queries(self, positions):
+        """positions of their own (<= RECORD_QUERIES_MAX) for the in-run records: while there are any, every following run
+        computes the selected kinds for these cells instead of the output queries', and queried_records follows them;
+        queried_outputs keeps serving the output queries.  An empty list returns to the output queries"""
+        e = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
+        _check(lib().PvAmdSetRecordQueries(self._h, _f(e) if len(e) else None, len(e)))
+        self._nrq = len(e)
 
     def results(self):
         res = np.empty((self.gx, self.gy, 8), np.float32)

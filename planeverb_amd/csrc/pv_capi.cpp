@@ -19,6 +19,7 @@
 #include "pv_lateral.h"
 #include "pv_lobes.h"
 #include "pv_metrics.h"
+#include "pv_query_records.h"
 #include "pv_spectrum.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
 #include "pv_bake.h"
@@ -383,6 +384,51 @@ int PlaneverbGetImpulseResponse(float x, float y, float z, PlaneverbCell* out, i
     const int n = c->impulseResponse(x, y, z, out, capacity);
     if (n < 0) g_lastError = "impulse response not available (no completed iteration yet, or solver error)";
     return n;
+} PV_API_CATCH(-1)
+
+// emission records (pv_context.cpp): the setters answer 0, or -1 with PvAmdLastError "emission records: ..."
+static_assert(PVA_RECORD_QUERIES_MAX == kMaxRecordQueries, "planeverb_amd.h vs pv_query_records.h");
+static int emissionSetterDown() {
+    g_lastError = "emission records: the module is not initialised";
+    return -1;
+}
+
+int PlaneverbSetEmissionRecords(unsigned kinds) try {
+    Context::Ref c;
+    if (!c) return emissionSetterDown();
+    return c->setEmissionRecords(kinds, &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+
+int PlaneverbSetEmissionEchogram(float slotSeconds, int nSlots) try {
+    Context::Ref c;
+    if (!c) return emissionSetterDown();
+    return c->setEmissionEchogram(slotSeconds, nSlots, &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+
+int PlaneverbSetEmissionLobeWindows(const float* edgesSeconds, int nEdges) try {
+    Context::Ref c;
+    if (!c) return emissionSetterDown();
+    return c->setEmissionLobeWindows(edgesSeconds, nEdges, &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+
+unsigned PlaneverbEmissionRecordKinds(void) try {
+    Context::Ref c;
+    return c ? c->emissionRecordKinds() : 0u;
+} PV_API_CATCH(0u)
+
+int PlaneverbEmissionRecordFloats(unsigned kind) try {
+    Context::Ref c;
+    return c ? c->emissionRecordFloats(kind) : -1;
+} PV_API_CATCH(-1)
+
+int PlaneverbEmissionRecordCells(void) try {
+    Context::Ref c;
+    return c ? c->emissionRecordCells() : -1;
+} PV_API_CATCH(-1)
+
+int PlaneverbGetEmissionRecord(int emissionID, unsigned kind, float* out, int capacity) try {
+    Context::Ref c;
+    return c ? c->emissionRecord(emissionID, kind, out, capacity) : -1;
 } PV_API_CATCH(-1)
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1092,11 +1138,20 @@ int PvAmdQueryRecordFloats(PvAmdSolver* h, unsigned kind) try {
 
 int PvAmdGetQueriedRecords(PvAmdSolver* h, unsigned kind, float* out, int nQueries) try {
     if (!queryRecordsHandle(h)) return -1;
-    if (nQueries < 0 || nQueries > Solver::kMaxQueries || (nQueries > 0 && !out)) {
-        g_lastError = "query records: PvAmdGetQueriedRecords: 0 .. 64 queries and an output buffer";
+    if (nQueries < 0 || nQueries > kMaxRecordQueries || (nQueries > 0 && !out)) {
+        g_lastError = "query records: PvAmdGetQueriedRecords: 0 .. 1024 queries and an output buffer";
         return -1;
     }
     return ret(h, h->s->queriedRecords(kind, out, nQueries));
+} PV_API_CATCH(-1)
+
+int PvAmdSetRecordQueries(PvAmdSolver* h, const float* xyz, int n) try {
+    if (!queryRecordsHandle(h)) return -1;
+    if (n < 0 || n > kMaxRecordQueries || (n > 0 && !xyz)) {
+        g_lastError = "query records: PvAmdSetRecordQueries: 0 .. 1024 positions (NULL only with 0)";
+        return -1;
+    }
+    return ret(h, h->s->setRecordQueries(xyz, n));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyResults(PvAmdSolver* h, float* res8, float* delay) try {

@@ -10,6 +10,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
+#include <new>
 
 namespace pva {
 
@@ -160,6 +162,10 @@ Context::~Context() {
     delete solver_;
     for (Slot& s : slots_) Solver::hostFree(s.data);
     std::free(base_.load());
+    for (RecSlot& r : rec_) {
+        std::free(r.cells.load());
+        std::free(r.data.load());
+    }
     for (auto& c : chunks_) {
         Emitter* p = c.load();
         delete[] p;
@@ -244,8 +250,10 @@ void Context::workerLoop() {
         // DEVICE work of iteration i -- not for its copy, which overlaps the next iteration's first launches.
         // (sparse-emitter mode: enqueueing a run BLOCKS for the front phase of the run -- the host paces the fused forward sums
         // -- so the previous iteration is made visible first instead of ~100 ms late)
-        if (!((!streaming_ || (finishPublish() && registerEmitters())) && solver_->run(lx, ly, lz, /*wait=*/false) && finishPublish() &&
-              beginPublish() && solver_->sync())) {
+        // (emission records: the table is latched in front of the run -- the solver's previous run has been waited for -- and the
+        // records leave the solver's pinned block behind sync(), before the next run overwrites it)
+        if (!((!streaming_ || (finishPublish() && registerEmitters())) && latchRecords(0) && solver_->run(lx, ly, lz, /*wait=*/false) &&
+              finishPublish() && beginPublish() && solver_->sync() && collectRecords(0, pendBack_))) {
             stop();
             break;
         }
@@ -293,7 +301,7 @@ void Context::workerLoopPipelined() {
     auto complete = [&]() -> bool {
         const Flight f = flights.front();
         flights.pop_front();
-        if (!(sv[f.k]->sync() && sv[f.k]->waitPublish())) {
+        if (!(sv[f.k]->sync() && sv[f.k]->waitPublish() && collectRecords(f.k, f.slot))) {
             fail(sv[f.k]);
             return false;
         }
@@ -320,7 +328,8 @@ void Context::workerLoopPipelined() {
             if (!used) break;
         }
         Flight f{k, slot, {}};
-        if (!(sv[k]->run(lx, ly, lz, /*wait=*/false, prevK >= 0 ? sv[prevK] : nullptr) &&
+        rec_[slot].pendKinds = 0;  // (until collectRecords has seen the iteration through)
+        if (!(latchRecords(k) && sv[k]->run(lx, ly, lz, /*wait=*/false, prevK >= 0 ? sv[prevK] : nullptr) &&
               sv[k]->publishWindowAsync(slots_[slot].data, &f.win, false))) {
             // (the iteration still in flight on the other solver is valid: make it visible first, as the one-solver loop does)
             while (!flights.empty() && complete()) {
@@ -398,6 +407,7 @@ bool Context::beginPublish() {
     // their copy, measured 0.77 against 0.71 ms per iteration at 71^2)
     const bool overlap = solver_->windowCapacity() * 32 > (size_t)(1u << 20);
     if (!solver_->publishWindowAsync(slots_[pendBack_].data, &pendWin_, overlap)) return false;
+    rec_[pendBack_].pendKinds = 0;  // (until collectRecords has seen the iteration through)
     pendPublish_ = true;
     return true;
 }
@@ -453,6 +463,14 @@ void Context::publishSlot(const int back, const Solver::WindowBlock& w) {
     s.nc.store(w.nc, std::memory_order_relaxed);
     s.lx.store(w.lx, std::memory_order_relaxed);
     s.lz.store(w.lz, std::memory_order_relaxed);
+    // the iteration's emission records (collectRecords left them in the slot): readable from the same flip on
+    RecSlot& r = rec_[back];
+    r.kinds.store(r.pendKinds, std::memory_order_relaxed);
+    r.n.store(r.pendKinds ? r.pendN : 0, std::memory_order_relaxed);
+    for (int k = 0; k < kQueryRecordKinds; ++k) {
+        r.floats[k].store(r.pendFloats[k], std::memory_order_relaxed);
+        r.offset[k].store(r.pendOffset[k], std::memory_order_relaxed);
+    }
     front_.store(back, std::memory_order_relaxed);
     pubSeq_.fetch_add(1, std::memory_order_seq_cst);  // even
     {
@@ -523,6 +541,7 @@ int Context::emit(float x, float y, float z) {
     e->x.store(x);
     e->y.store(y);
     e->z.store(z);
+    e->live.store(1, std::memory_order_release);
     if (id == emitterCount_.load()) emitterCount_.store(id + 1, std::memory_order_release);
     return id;
 }
@@ -541,6 +560,7 @@ void Context::endEmission(int id) {
     if (id < 0 || id >= emitterCount_.load()) return;
     std::lock_guard<std::mutex> lock(emitMutex_);
     emitterFree_.push_back(id);
+    if (Emitter* e = emitterAt(id)) e->live.store(0, std::memory_order_release);
 }
 
 Out8 Context::getOutput(int id) {
@@ -588,6 +608,309 @@ void ensureRoom(V& v, size_t k) {
     if (v.capacity() - v.size() < k) v.reserve(std::max(v.capacity() * 2, v.size() + k));
 }
 }  // namespace
+
+// ----------------------------------------------------------------------------------------------------------------
+// emission records (pv_context.h): settings, the worker's latch and collect steps, the lock-free read
+// ----------------------------------------------------------------------------------------------------------------
+
+#if !defined(PVA_HOST_TEST) || defined(PVA_HOST_TEST_RECORDS)
+#define PVA_LIVE_RECORDS 1
+#endif
+
+namespace {
+const char kRecPrefix[] = "emission records: ";
+int recBit(unsigned kind) {  // the bit of a mask that names ONE kind, or -1
+    for (int k = 0; k < kQueryRecordKinds; ++k)
+        if (kind == (1u << k)) return k;
+    return -1;
+}
+inline long long loadCell(const long long* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+}  // namespace
+
+bool Context::setEmissionRecords(unsigned kinds, std::string* err) {
+#ifdef PVA_LIVE_RECORDS
+    const int fs = (int)spec().fs;
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    const char* why = nullptr;
+    LobeEdges ed;
+    if (kinds & ~kQueryRecordMask)
+        why = "unknown kind bit (PVA_QREC_*)";
+    else if (kinds && streaming_)
+        why = "the full pressure history is not kept in sparse-emitter mode";
+    else if ((kinds & (1u << kQrecEchogram)) && !wantSlots_)
+        why = "echogram: no slots set (PlaneverbSetEmissionEchogram)";
+    else if ((kinds & (1u << kQrecEchoCriterion)) && !echoFsOk(fs))
+        why = "echo: the sampling rate gives a speech lag below one step ((int)(0.009f * (float)fs) < 1)";
+    else if ((kinds & (1u << kQrecLobes)) &&
+             !lobesEdgeSteps(wantEdges_ ? wantEdge_ : kLobesDefaultEdges, wantEdges_ ? wantEdges_ : 2, fs, &ed))
+        why = "lobes: the default windows (10 ms, 80 ms) need a sampling rate of 100 Hz or more (PlaneverbSetEmissionLobeWindows)";
+    if (why) {
+        *err = std::string(kRecPrefix) + why;
+        return false;
+    }
+    ensureRoom(changes_, 1);
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.rec = 1;
+    c.recKinds = kinds;
+    changes_.push_back(c);
+    wantKinds_ = kinds;
+    return true;
+#else
+    (void)kinds;
+    *err = std::string(kRecPrefix) + "not in this build";
+    return false;
+#endif
+}
+
+bool Context::setEmissionEchogram(float slotSeconds, int nSlots, std::string* err) {
+#ifdef PVA_LIVE_RECORDS
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    const char* why = nullptr;
+    if (streaming_)
+        why = "the full pressure history is not kept in sparse-emitter mode";
+    else if (nSlots < 0 || nSlots > kEchogramMaxSlots)
+        why = "echogram: nSlots is 0 .. PVA_ECHOGRAM_MAX_SLOTS (32)";
+    else if (nSlots > 0 && !echogramSlotOk(slotSeconds, (int)spec().fs))
+        why = "echogram: slotSeconds must be finite and give 1 .. 2^20 steps per slot ((int)(slotSeconds * (float)fs))";
+    else if (nSlots == 0 && (wantKinds_ & (1u << kQrecEchogram)))
+        why = "echogram: the slots cannot be cleared while PVA_QREC_ECHOGRAM is selected (PlaneverbSetEmissionRecords)";
+    if (why) {
+        *err = std::string(kRecPrefix) + why;
+        return false;
+    }
+    ensureRoom(changes_, 1);
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.rec = 2;
+    c.recSeconds = slotSeconds;
+    c.recN = nSlots;
+    changes_.push_back(c);
+    wantSlots_ = nSlots;
+    return true;
+#else
+    (void)slotSeconds;
+    (void)nSlots;
+    *err = std::string(kRecPrefix) + "not in this build";
+    return false;
+#endif
+}
+
+bool Context::setEmissionLobeWindows(const float* edgesSeconds, int nEdges, std::string* err) {
+#ifdef PVA_LIVE_RECORDS
+    const int fs = (int)spec().fs;
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    std::string why;
+    LobeEdges ed;
+    if (streaming_)
+        why = "the full pressure history is not kept in sparse-emitter mode";
+    else if (nEdges != 0 && !lobesEdgeSteps(edgesSeconds, nEdges, fs, &ed))
+        why = kLobesEdgesError;
+    else if (nEdges == 0 && (wantKinds_ & (1u << kQrecLobes)) && !lobesEdgeSteps(kLobesDefaultEdges, 2, fs, &ed))
+        why = "lobes: the default windows (10 ms, 80 ms) need a sampling rate of 100 Hz or more";
+    if (!why.empty()) {
+        *err = kRecPrefix + why;
+        return false;
+    }
+    ensureRoom(changes_, 1);
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.rec = 3;
+    c.recN = nEdges;
+    for (int i = 0; i < nEdges; ++i) c.recEdges[i] = wantEdge_[i] = edgesSeconds[i];
+    changes_.push_back(c);
+    wantEdges_ = nEdges;
+    return true;
+#else
+    (void)edgesSeconds;
+    (void)nEdges;
+    *err = std::string(kRecPrefix) + "not in this build";
+    return false;
+#endif
+}
+
+// Start of an iteration on solver k: the cells of the live emitters, in ascending id as registerEmitters walks them, the first
+// kMaxRecordQueries distinct in-map ones, sorted, as that solver's record queries.  Nothing when no kind is selected.
+bool Context::latchRecords(const int k) {
+    Latch& L = latch_[k];
+    L.kinds = 0;
+    L.cells.clear();
+#ifdef PVA_LIVE_RECORDS
+    Solver* const s = k == 0 ? solver_ : solver2_;
+    L.kinds = s->queryRecordKinds();
+    if (!L.kinds) return true;
+    const GridSpec& g = s->spec();
+    auto& seen = latchScratch_;  // (cell, order of first appearance)
+    seen.clear();
+    {
+        std::lock_guard<std::mutex> lock(emitMutex_);
+        const int n = emitterCount_.load(std::memory_order_acquire);
+        for (int id = 0; id < n; ++id) {
+            Emitter* e = emitterAt(id);
+            if (!e || !e->live.load(std::memory_order_acquire)) continue;  // (ended)
+            int cx, cy;
+            if (resultCell(g, e->x.load(), e->z.load(), &cx, &cy)) seen.emplace_back((long long)cx * g.gy + cy, (int)seen.size());
+        }
+    }
+    // distinct cells, each with its first appearance; then the first kMaxRecordQueries of them by appearance; then by cell
+    std::sort(seen.begin(), seen.end());
+    seen.erase(std::unique(seen.begin(), seen.end(), [](const auto& a, const auto& b) { return a.first == b.first; }), seen.end());
+    if (seen.size() > (size_t)kMaxRecordQueries) {
+        std::nth_element(seen.begin(), seen.begin() + kMaxRecordQueries, seen.end(),
+                         [](const auto& a, const auto& b) { return a.second < b.second; });
+        seen.resize((size_t)kMaxRecordQueries);
+        std::sort(seen.begin(), seen.end());
+    }
+    // the solver takes positions: the cell centres ((c + 0.5) dx divided by dx lands within 2^-22 c of c + 0.5: the same cell)
+    latchXyz_.clear();
+    for (const auto& c : seen) {
+        L.cells.push_back(c.first);
+        latchXyz_.push_back((float)(((double)(c.first / g.gy) + 0.5) * (double)g.dx));
+        latchXyz_.push_back(0.f);
+        latchXyz_.push_back((float)(((double)(c.first % g.gy) + 0.5) * (double)g.dx));
+    }
+    return s->setRecordQueries(latchXyz_.data(), (int)L.cells.size());
+#else
+    return true;
+#endif
+}
+
+// Solver k's run has been waited for: its records leave the pinned block for record slot `slot` (not the readable one; relaxed
+// stores, because a late reader may still be looking at it -- it then discards what it read), to be made visible by publishSlot
+bool Context::collectRecords(const int k, const int slot) {
+    RecSlot& r = rec_[slot];
+    r.pendKinds = 0;
+    r.pendN = 0;
+#ifdef PVA_LIVE_RECORDS
+    const Latch& L = latch_[k];
+    if (!L.kinds) return true;
+    Solver* const s = k == 0 ? solver_ : solver2_;
+    long long* cells = r.cells.load(std::memory_order_relaxed);
+    float* data = r.data.load(std::memory_order_relaxed);
+    if (!cells) {
+        cells = static_cast<long long*>(std::calloc((size_t)kMaxRecordQueries, sizeof(long long)));
+        data = static_cast<float*>(std::calloc(kRecSlotFloats, sizeof(float)));
+        if (!cells || !data) {
+            std::free(cells);
+            std::free(data);
+            throw std::bad_alloc();  // (ends at the worker's barrier)
+        }
+        r.cells.store(cells, std::memory_order_release);
+        r.data.store(data, std::memory_order_release);
+    }
+    const int n = (int)L.cells.size();
+    int off = 0;
+    for (int b = 0; b < kQueryRecordKinds; ++b) {
+        r.pendFloats[b] = 0;
+        r.pendOffset[b] = off;
+        if (!((L.kinds >> b) & 1u)) continue;
+        const int f = s->queryRecordFloats(1u << b);
+        if (f < 0) return false;
+        r.pendFloats[b] = f;
+        if (n > 0) {
+            recStage_.resize((size_t)n * f);
+            if (!s->queriedRecords(1u << b, recStage_.data(), n)) return false;
+            storeRelaxed(data + off, recStage_.data(), (size_t)n * f);
+        }
+        off += n * f;
+    }
+    for (int i = 0; i < n; ++i) __atomic_store_n(cells + i, L.cells[(size_t)i], __ATOMIC_RELAXED);
+    r.pendKinds = L.kinds;
+    r.pendN = n;
+#else
+    (void)k;
+#endif
+    return true;
+}
+
+unsigned Context::emissionRecordKinds() {
+    for (;;) {
+        const uint64_t s1 = pubSeq_.load(std::memory_order_acquire);
+        if (s1 & 1) continue;
+        const int f = front_.load(std::memory_order_relaxed);
+        const unsigned kinds = f >= 0 ? rec_[f].kinds.load(std::memory_order_relaxed) : 0u;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if (pubSeq_.load(std::memory_order_relaxed) == s1) return kinds;
+    }
+}
+
+int Context::emissionRecordFloats(unsigned kind) {
+    const int b = recBit(kind);
+    if (b < 0) return -1;
+    for (;;) {
+        const uint64_t s1 = pubSeq_.load(std::memory_order_acquire);
+        if (s1 & 1) continue;
+        const int f = front_.load(std::memory_order_relaxed);
+        int n = -1;
+        if (f >= 0 && (rec_[f].kinds.load(std::memory_order_relaxed) & kind)) n = rec_[f].floats[b].load(std::memory_order_relaxed);
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if (pubSeq_.load(std::memory_order_relaxed) == s1) return n;
+    }
+}
+
+int Context::emissionRecordCells() {
+    for (;;) {
+        const uint64_t s1 = pubSeq_.load(std::memory_order_acquire);
+        if (s1 & 1) continue;
+        const int f = front_.load(std::memory_order_relaxed);
+        const int n = f >= 0 ? rec_[f].n.load(std::memory_order_relaxed) : 0;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if (pubSeq_.load(std::memory_order_relaxed) == s1) return n;
+    }
+}
+
+int Context::emissionRecord(int id, unsigned kind, float* out, int cap) {
+    const int b = recBit(kind);
+    if (b < 0 || !out) return -1;
+    const GridSpec& g = solver_->spec();
+    float rec[kRecMaxFloats];
+    for (;;) {
+        const uint64_t s1 = pubSeq_.load(std::memory_order_acquire);
+        if (s1 & 1) continue;  // the worker is between its two stores
+        int res = -1, nf = 0;
+        const int f = front_.load(std::memory_order_relaxed);
+        if (f >= 0 && (rec_[f].kinds.load(std::memory_order_relaxed) & kind)) {
+            const RecSlot& r = rec_[f];
+            nf = r.floats[b].load(std::memory_order_relaxed);
+            if (nf < 1 || nf > kRecMaxFloats) {
+                nf = 0;  // (a torn read: the check below repeats it)
+            } else if (cap >= nf) {
+                res = 0;
+                // the emitter's position NOW: a cell it moved to since the latch is not in the table (one iteration later it is)
+                Emitter* e = emitterAt(id);
+                int cx, cy;
+                if (e && e->live.load(std::memory_order_acquire) && resultCell(g, e->x.load(), e->z.load(), &cx, &cy)) {
+                    const long long cell = (long long)cx * g.gy + cy;
+                    const long long* cells = r.cells.load(std::memory_order_acquire);
+                    const float* data = r.data.load(std::memory_order_acquire);
+                    int lo = 0, hi = std::min(std::max(r.n.load(std::memory_order_relaxed), 0), kMaxRecordQueries);
+                    const int n = hi;
+                    while (cells && lo < hi) {
+                        const int mid = (lo + hi) / 2;
+                        if (loadCell(cells + mid) < cell)
+                            lo = mid + 1;
+                        else
+                            hi = mid;
+                    }
+                    const int off = r.offset[b].load(std::memory_order_relaxed);
+                    if (cells && data && lo < n && loadCell(cells + lo) == cell && off >= 0 &&
+                        (size_t)off + (size_t)n * nf <= kRecSlotFloats) {
+                        loadRelaxed(rec, data + off + (size_t)lo * nf, (size_t)nf);
+                        for (int i = 0; i < nf; ++i) res |= rec[i] == rec[i] ? 1 : 0;  // (all NaN: no onset in that run)
+                    }
+                }
+            }
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        if (pubSeq_.load(std::memory_order_relaxed) != s1) continue;
+        if (res == 1) {
+            std::memcpy(out, rec, (size_t)nf * sizeof(float));
+        } else if (res == 0) {
+            const float qnan = std::numeric_limits<float>::quiet_NaN();
+            for (int i = 0; i < nf; ++i) out[i] = qnan;
+        }
+        return res;
+    }
+}
+
+// ---- the geometry table
 
 int Context::addGeometry(const Box& b) {
     // (a non-finite absorption is refused: NaN marks air in the material and coefficient planes, pv_solver.cpp addBox)
@@ -700,6 +1023,21 @@ bool Context::setEdgeLayer(const int w4[4], std::string* err, bool split, double
 }
 
 void Context::applyChange(Solver* s, const Change& c) {
+    if (c.rec) {
+#ifdef PVA_LIVE_RECORDS
+        // (validated by the setters against the state these changes lead to, in queue order; a failure here -- the pinned block's
+        // allocation -- leaves the solver's kinds as they were, and the latch follows the solver's kinds)
+        if (c.rec == 1) {
+            s->setQueryRecords(c.recKinds);
+            if (!c.recKinds) s->setRecordQueries(nullptr, 0);
+        } else if (c.rec == 2) {
+            s->setEchogram(c.recSeconds, c.recN);
+        } else {
+            s->setLobeWindows(c.recN ? c.recEdges : nullptr, c.recN);
+        }
+#endif
+        return;
+    }
     if (c.layer) {
 #ifndef PVA_HOST_TEST
         s->setEdgeLayer(c.W4, c.split, c.r0);  // (validated by setEdgeLayer: the widths fit the grid and the configuration)

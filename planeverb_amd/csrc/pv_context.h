@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "pv_core.h"
+#include "pv_query_records.h"
 #ifdef PVA_HOST_TEST
 #include "fake_solver.h"  // tests/host/: same interface, no HIP
 #else
@@ -98,13 +99,34 @@ public:
     // (split, r0: the model, Solver::setEdgeLayer)
     bool setEdgeLayer(const int w4[4], std::string* err, bool split = false, double r0 = kEdgeLayerR0);
 
+    // Emission records: the in-run analysis records (Solver::setQueryRecords, pv_query_records.hip) of the live emitters' cells,
+    // published with every iteration.  The three setters validate at the call with the rules of the Solver calls (false + *err,
+    // "emission records: ..."; refused in sparse-emitter mode), then queue with the geometry changes and take effect on every
+    // solver at the same iteration boundary.  At the start of an iteration with kinds selected the worker latches the live
+    // emitters' cells (ascending id, ended ids skipped, the first kMaxRecordQueries DISTINCT in-map cells, sorted) into that
+    // iteration's solver; the iteration's records then become readable in the same publish step as its outputs.
+    bool setEmissionRecords(unsigned kinds, std::string* err);
+    bool setEmissionEchogram(float slotSeconds, int nSlots, std::string* err);
+    bool setEmissionLobeWindows(const float* edgesSeconds, int nEdges, std::string* err);
+    // of the PUBLISHED iteration: its kinds, the floats of one kind (-1: not carried), its distinct cells
+    unsigned emissionRecordKinds();
+    int emissionRecordFloats(unsigned kind);
+    int emissionRecordCells();
+    // The record of the emitter's CURRENT cell in the published iteration: 1 = written; 0 = quiet NaNs written (an id never issued
+    // or ended, a position off the map, a cell that is not in the iteration's table or has no onset in it); -1 = nothing written
+    // (not one kind, the iteration does not carry it, no buffer, cap too small).  Lock-free like getOutput: no device access, no
+    // lock, no allocation.
+    int emissionRecord(int id, unsigned kind, float* out, int cap);
+
     void setListener(float x, float y, float z);  // PvContext.cpp:50-56
     // Planeverb::GetImpulseResponse (FDTD.cpp:60-70): the IR of the last COMPLETED iteration at a world position as
     // reference Cells (16 B each).  Waits for the iteration in flight.  Returns the response length T (cells16 gets
     // min(cap, T) cells), 0 for a position outside the cell array, -1 on error.
     int impulseResponse(float x, float y, float z, void* cells16, int cap);
 
-    long long iterations() const { return iterations_.load(std::memory_order_acquire); }
+    // Published iterations, read off the publish step's sequence lock (two counts per publish): the count changes with the flip
+    // itself, so two reads -- GetOutput, an emission record -- between two equal counts are of ONE iteration
+    long long iterations() const { return (long long)(pubSeq_.load(std::memory_order_acquire) >> 1); }
     // a number no other context of this process has had (a new context can land on a retired one's address)
     unsigned long long generation() const { return generation_; }
     long long waitIterations(long long count, int timeoutMs);
@@ -138,6 +160,8 @@ private:
     Solver::WindowBlock pendWin_;
     void beginRetire();
     bool registerEmitters();
+    bool latchRecords(int k);
+    bool collectRecords(int k, int slot);
     friend void retireContext(Context*);
 
     unsigned long long generation_ = 0;
@@ -169,6 +193,7 @@ private:
     // emitters: fixed-capacity chunks so readers never race a reallocation
     struct Emitter {
         std::atomic<float> x{0.f}, y{0.f}, z{0.f};
+        std::atomic<int> live{0};  // 1 between Emit and EndEmission (what emissionRecord asks; GetOutput never did)
     };
     static constexpr int kChunk = 1024, kMaxChunks = 1024;
     std::atomic<Emitter*> chunks_[kMaxChunks] = {};
@@ -189,6 +214,12 @@ private:
         int W4[4] = {0, 0, 0, 0};
         bool split = false;  // ... and the model
         double r0 = kEdgeLayerR0;
+        // an emission-records change: 1 = the kinds, 2 = the echogram slots, 3 = the lobe windows (recN edges; 0 = the default)
+        int rec = 0;
+        unsigned recKinds = 0;
+        float recSeconds = 0.f;
+        int recN = 0;
+        float recEdges[kLobesMaxEdges] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     };
     static void applyChange(Solver* s, const Change& c);
     std::vector<Box> geometry_;
@@ -215,6 +246,39 @@ private:
     std::atomic<int> front_{-1};
     std::atomic<uint64_t> pubSeq_{0};
     std::atomic<float*> base_{nullptr};
+
+    // Emission records.  What the callers have asked for so far (the state the queued changes lead to: the setters validate against
+    // it), under geomMutex_:
+    unsigned wantKinds_ = 0;
+    int wantSlots_ = 0, wantEdges_ = 0;
+    float wantEdge_[kLobesMaxEdges] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    // the worker's: the table latched into solver k at the start of its iteration (sorted distinct cells), and its scratch
+    struct Latch {
+        unsigned kinds = 0;
+        std::vector<long long> cells;
+    };
+    Latch latch_[2];
+    std::vector<std::pair<long long, int>> latchScratch_;
+    std::vector<float> latchXyz_, recStage_;
+    // One record slot per result slot, selected by front_ and read under pubSeq_ like the result block: the iteration's sorted cell
+    // table, its kinds with their floats and offsets, and the floats (per kind n x floats[kind] from offset[kind] on).  The tables
+    // are allocated by the worker the first time an iteration carries records (kMaxRecordQueries cells, every kind at its largest
+    // setting) and live as long as the context: a reader may still be looking at them.  The pend* members are the worker's own: what
+    // collectRecords left in the slot, made visible by publishSlot.
+    static constexpr int kRecMaxFloats = 1 + 3 * kEchogramMaxSlots;  // the largest record of one kind
+    static constexpr size_t kRecSlotFloats =
+        (size_t)kMaxRecordQueries * (kRoomMetricFloats + kDecayFloats + kLateralFloats + (1 + 3 * kEchogramMaxSlots) + kEchoFloats +
+                                     (1 + 5 * kLobesMaxWindows));
+    struct RecSlot {
+        std::atomic<long long*> cells{nullptr};
+        std::atomic<float*> data{nullptr};
+        std::atomic<int> n{0};
+        std::atomic<unsigned> kinds{0};
+        std::atomic<int> floats[kQueryRecordKinds] = {}, offset[kQueryRecordKinds] = {};
+        unsigned pendKinds = 0;
+        int pendN = 0, pendFloats[kQueryRecordKinds] = {}, pendOffset[kQueryRecordKinds] = {};
+    };
+    RecSlot rec_[3];
 };
 
 }  // namespace pva

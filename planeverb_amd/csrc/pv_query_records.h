@@ -15,11 +15,13 @@ namespace pva {
 constexpr int kQrecRoomMetrics = 0, kQrecDecay = 1, kQrecLateral = 2, kQrecEchogram = 3, kQrecEchoCriterion = 4, kQrecLobes = 5;
 constexpr int kQueryRecordKinds = 6;
 constexpr unsigned kQueryRecordMask = (1u << kQueryRecordKinds) - 1u;
+// queries of one launch: groups of 64 on blockIdx.y (PVA_RECORD_QUERIES_MAX)
+constexpr int kMaxRecordQueries = 1024;
 
 struct QueryRecordArgs {
     const long long* cells;  // nq result-cell indices (-1: off the map), pinned host memory
     float* out;              // pinned host memory
-    int nq;                  // <= 64
+    int nq;                  // <= kMaxRecordQueries
     unsigned kinds;
     int offset[kQueryRecordKinds];  // of a kind's nq x floats block inside out, in floats
     int floats[kQueryRecordKinds];  // per query

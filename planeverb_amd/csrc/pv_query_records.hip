@@ -2,7 +2,8 @@
 // the run (PvAmdSetQueryRecords): one launch behind the run's analysis, in front of its last kernel, straight into pinned host
 // memory.  No pass over the history window, no per-cell device storage, no host synchronisation of its own.
 //
-// One wave per block, one block per selected kind (a wave-uniform switch on blockIdx.x), lane i = query i.  A lane's cell comes
+// One wave per block; blockIdx.x is the selected-kind ordinal (a wave-uniform switch), blockIdx.y the group of 64 queries: lane l
+// of group g serves query i = 64 g + l (up to kMaxRecordQueries; one group, the launch of before, up to 64).  A lane's cell comes
 // from the query table (recordLaneOfCell, pv_record_lane.h: the history offset g of the cell, where the cell lies inside the
 // run's history window), its record goes to the query's AoS slot.  Between the two runs the body of the kind's whole-map pass
 // (pv_metrics_dev.h ... pv_lobes_dev.h), the SAME text the whole-map kernel is made of: the same loads with the same
@@ -15,7 +16,8 @@
 // pv_gather_queries_kernel's are.
 //
 // Cost: a lone wave per kind walks its dependent chain once -- the launch takes what its slowest selected kind takes for one
-// wave, whatever the grid, the window or the number of queries.  The wave's 64 loads of a step hit up to 64 different lines.
+// wave, whatever the grid, the window or the number of queries (the groups are independent waves on other compute units).  The
+// wave's 64 loads of a step hit up to 64 different lines.
 #include <hip/hip_runtime.h>
 
 #include "pv_analysis.h"
@@ -60,10 +62,11 @@ __global__ __launch_bounds__(64) void pv_query_records_kernel(const AnalyzeArgs 
     __syncthreads();
 
     const DynParams dyn = *a.dyn;
-    const bool slot = lane < q.nq;
-    const RecordLane ln = recordLaneOfCell(a, dyn, slot ? q.cells[lane] : -1, slot);
+    const int i = 64 * (int)blockIdx.y + lane;  // the query (the group is wave-uniform)
+    const bool slot = i < q.nq;
+    const RecordLane ln = recordLaneOfCell(a, dyn, slot ? q.cells[i] : -1, slot);
     // (a lane without a slot never stores: it is not live, and the NaN fill asks for the slot)
-    const SlotStore out{q.out + q.offset[kind] + (long long)(slot ? lane : 0) * q.floats[kind]};
+    const SlotStore out{q.out + q.offset[kind] + (long long)(slot ? i : 0) * q.floats[kind]};
     switch (kind) {
         case kQrecRoomMetrics:
             roomMetricsBody<PV_METRICS_S, PV_METRICS_NB, CHUNK>(a, ln, out, q.n50, q.n80);
@@ -89,10 +92,10 @@ __global__ __launch_bounds__(64) void pv_query_records_kernel(const AnalyzeArgs 
 
 }  // namespace
 
-// q.kinds != 0; q.cells, q.out: device-visible pinned host memory (q.out holds, per selected kind, nq x floats[kind] floats from
+// q.kinds != 0, 0 < q.nq <= kMaxRecordQueries; q.cells, q.out: device-visible pinned host memory (q.out holds, per selected kind, nq x floats[kind] floats from
 // offset[kind] on); the settings of every selected kind filled in by the caller
 void launchQueryRecords(const AnalyzeArgs& a, const QueryRecordArgs& q, hipStream_t stream) {
-    const dim3 grid((unsigned)__builtin_popcount(q.kinds));
+    const dim3 grid((unsigned)__builtin_popcount(q.kinds), (unsigned)((q.nq + 63) / 64));
     // (the largest chunk of the six passes is 8 planes: one descriptor per chunk below 2^31 bytes, as in their own launchers)
     if (a.histPlane * 4 * 8 < (1ll << 31))
         hipLaunchKernelGGL((pv_query_records_kernel<true>), grid, dim3(64), 0, stream, a, q);

@@ -720,6 +720,7 @@ Solver::~Solver() {
         if (e) hipEventDestroy(e);
     if (lobes_) hipFree(lobes_);
     if (qrecHost_) hipHostFree(qrecHost_);
+    if (rqCellsHost_) hipHostFree(rqCellsHost_);
     for (auto& e : lobesEv_)
         if (e) hipEventDestroy(e);
     if (echoCrit_) hipFree(echoCrit_);
@@ -2724,7 +2725,32 @@ bool Solver::setOutputQueries(const float* xyz, int n) {
         qCellsHost_[i] = resultCell(g_, xyz[3 * i], xyz[3 * i + 2], &cx, &cy) ? (long long)cx * g_.gy + cy : -1;
     }
     numQueries_ = n;
-    qrecRun_ = QrecRun::None;  // (the records in the pinned block belong to the queries of before)
+    if (numRecQueries_ == 0) qrecRun_ = QrecRun::None;  // (the records in the pinned block belong to the queries of before)
+    return true;
+}
+
+bool Solver::setRecordQueries(const float* xyz, int n) {
+    if (n < 0 || n > kMaxRecordQueries) return fail("query records: at most 1024 record queries");
+    if (n > 0 && !xyz) return fail("query records: no positions");
+    if (n > 0 && isSlab()) return fail("query records: not available on a slab");
+    if (n > 0 && opt_.streaming) return fail("query records: the full pressure history is not kept in streaming-analysis mode");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // the launch of a run in flight still reads the cell table
+    if (n > rqCap_) {
+        long long* t = nullptr;
+        if (!hipOk(hipHostMalloc((void**)&t, (size_t)n * sizeof(long long)), "hipHostMalloc")) return false;
+        if (rqCellsHost_) hipHostFree(rqCellsHost_);
+        rqCellsHost_ = t;
+        rqCap_ = n;
+    }
+    if (!growQrecBlock(qrecKinds_, n)) return false;
+    for (int i = 0; i < n; ++i) {
+        int cx, cy;
+        rqCellsHost_[i] = resultCell(g_, xyz[3 * i], xyz[3 * i + 2], &cx, &cy) ? (long long)cx * g_.gy + cy : -1;
+    }
+    numRecQueries_ = n;
+    qrecRun_ = QrecRun::None;  // (the records in the pinned block belong to the table of before)
     return true;
 }
 
@@ -2773,6 +2799,14 @@ int qrecFloatsOf(int k, int echoSlots, int lobeWindows) {
     }
     return -1;
 }
+// floats per query of the pinned block: every selected kind at its largest setting, so that a later change of slots or windows
+// needs no allocation
+size_t qrecBlockFloats(unsigned kinds) {
+    size_t cap = 0;
+    for (int k = 0; k < kQueryRecordKinds; ++k)
+        if ((kinds >> k) & 1u) cap += (size_t)qrecFloatsOf(k, kEchogramMaxSlots, kLobesMaxWindows);
+    return cap;
+}
 int qrecBit(unsigned kind) {  // the bit of a mask that names ONE kind, or -1
     for (int k = 0; k < kQueryRecordKinds; ++k)
         if (kind == (1u << k)) return k;
@@ -2797,15 +2831,26 @@ bool Solver::setQueryRecords(unsigned kinds) {
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // the launch of a run in flight still writes the pinned block
     if (kinds == qrecKinds_) return true;
-    // the block holds every selected kind at its largest setting, so that a later change of slots or windows needs no allocation
-    size_t cap = 0;
-    for (int k = 0; k < kQueryRecordKinds; ++k)
-        if ((kinds >> k) & 1u) cap += (size_t)qrecFloatsOf(k, kEchogramMaxSlots, kLobesMaxWindows);
+    const size_t cap = qrecBlockFloats(kinds);
+    const int queries = numRecQueries_ > kMaxQueries ? numRecQueries_ : kMaxQueries;
     float* block = nullptr;
-    if (cap && !hipOk(hipHostMalloc((void**)&block, cap * kMaxQueries * sizeof(float)), "hipHostMalloc")) return false;
+    if (cap && !hipOk(hipHostMalloc((void**)&block, cap * queries * sizeof(float)), "hipHostMalloc")) return false;
     if (qrecHost_) hipHostFree(qrecHost_);
     qrecHost_ = block;
+    qrecBlockQueries_ = block ? queries : 0;
     qrecKinds_ = kinds;
+    qrecRun_ = QrecRun::None;
+    return true;
+}
+
+// the pinned block of the selected kinds with room for `queries` queries (no run in flight); nothing while no kind is selected
+bool Solver::growQrecBlock(unsigned kinds, int queries) {
+    if (!kinds || queries <= qrecBlockQueries_) return true;
+    float* block = nullptr;
+    if (!hipOk(hipHostMalloc((void**)&block, qrecBlockFloats(kinds) * queries * sizeof(float)), "hipHostMalloc")) return false;
+    if (qrecHost_) hipHostFree(qrecHost_);
+    qrecHost_ = block;
+    qrecBlockQueries_ = queries;
     qrecRun_ = QrecRun::None;
     return true;
 }
@@ -2826,9 +2871,10 @@ int Solver::queryRecordFloats(unsigned kind) {
 void Solver::enqueueQueryRecords() {
     if (!qrecKinds_ || opt_.skipAnalysis) return;
     QueryRecordArgs q{};
-    q.cells = qCellsHost_;
+    const int nq = qrecQueries();
+    q.cells = numRecQueries_ > 0 ? rqCellsHost_ : qCellsHost_;
     q.out = qrecHost_;
-    q.nq = numQueries_;
+    q.nq = nq;
     q.kinds = qrecKinds_;
     const int fs = (int)g_.fs;
     int off = 0;
@@ -2836,7 +2882,7 @@ void Solver::enqueueQueryRecords() {
         const bool on = (qrecKinds_ >> k) & 1u;
         q.floats[k] = on ? qrecFloatsOf(k, echoSlots_, lobeEdgeCount_ + 1) : 0;
         q.offset[k] = off;
-        off += q.floats[k] * numQueries_;
+        off += q.floats[k] * nq;
         qrecRunFloats_[k] = q.floats[k];
         qrecRunOffset_[k] = q.offset[k];
     }
@@ -2854,9 +2900,9 @@ void Solver::enqueueQueryRecords() {
     lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, fs, &q.ed);  // (valid: checked where the kind was selected and where the windows are set)
     q.nW = lobeEdgeCount_ + 1;
     qrecRunKinds_ = qrecKinds_;
-    qrecRunQueries_ = numQueries_;
+    qrecRunQueries_ = nq;
     qrecRun_ = QrecRun::Pending;
-    if (numQueries_ > 0) launchQueryRecords(analyzeArgs(lastLx_, lastLz_), q, stream_);
+    if (nq > 0) launchQueryRecords(analyzeArgs(lastLx_, lastLz_), q, stream_);
 }
 
 // after the run has been waited for: the records of one kind, straight from pinned memory
@@ -2864,10 +2910,10 @@ bool Solver::queriedRecords(unsigned kind, float* out, int n) {
     const int k = qrecBit(kind);
     if (k < 0) return fail("query records: exactly one kind (PVA_QREC_*)");
     if (!(qrecKinds_ & kind)) return fail("query records: the kind is not selected (PvAmdSetQueryRecords)");
-    if (n != numQueries_) return fail("query records: count differs from the registered queries");
+    if (n != qrecQueries()) return fail("query records: count differs from the registered queries");
     if (pendingTimings_ && !sync()) return false;
     if (lastRun_ == LastRun::Failed) return fail("query records: the last run ended in error");
-    if (qrecRun_ != QrecRun::Ok || qrecRunKinds_ != qrecKinds_ || qrecRunQueries_ != numQueries_ ||
+    if (qrecRun_ != QrecRun::Ok || qrecRunKinds_ != qrecKinds_ || qrecRunQueries_ != qrecQueries() ||
         qrecRunFloats_[k] != qrecFloatsOf(k, echoSlots_, lobeEdgeCount_ + 1))
         return fail("query records: no completed run since the kinds, the queries or the settings changed");
     const float* src = qrecHost_ + qrecRunOffset_[k];

@@ -229,6 +229,13 @@ public:
     unsigned queryRecordKinds() const { return qrecKinds_; }
     int queryRecordFloats(unsigned kind);  // -1: not one kind, or its setting is missing
     bool queriedRecords(unsigned kind, float* out, int n);
+    // Record queries: up to kMaxRecordQueries (pv_query_records.h) positions of their own, mapped in the given order as
+    // setOutputQueries maps them.  While n > 0 the in-run records are computed for THESE cells instead of the output queries'
+    // (64 queries per wave, one more block row per 64), and queriedRecords takes this n; the eight-output gather keeps serving
+    // the output queries.  n = 0, the default, returns to the output queries.  The pinned cell table and the record block grow to
+    // the registered count.  Waits for a run in flight; a change invalidates the records until the next run
+    bool setRecordQueries(const float* xyz, int n);
+    int recordQueries() const { return numRecQueries_; }
     bool copyResults(float* res8, float* delay);
     // the block [r0, r0 + nr) x [c0, c0 + nc) of the result map (AoS records) and of the onset map, row-major nr x nc
     bool copyResultsBlock(int r0, int c0, int nr, int nc, float* res8, float* delay);
@@ -670,6 +677,11 @@ private:
     enum class QrecRun { None, Pending, Ok } qrecRun_ = QrecRun::None;
     unsigned qrecRunKinds_ = 0;
     int qrecRunQueries_ = 0;
+    // the record queries' own pinned cell table (setRecordQueries) and the queries the pinned block has room for
+    long long* rqCellsHost_ = nullptr;
+    int rqCap_ = 0, numRecQueries_ = 0, qrecBlockQueries_ = 0;
+    int qrecQueries() const { return numRecQueries_ > 0 ? numRecQueries_ : numQueries_; }  // of the table the records follow
+    bool growQrecBlock(unsigned kinds, int queries);
     int qrecRunOffset_[6] = {0, 0, 0, 0, 0, 0}, qrecRunFloats_[6] = {0, 0, 0, 0, 0, 0};
     void enqueueQueryRecords();  // behind a run's analysis, in front of its last kernel (nothing when no kind is selected)
     int* listHost_ = nullptr;
