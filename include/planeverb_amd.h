@@ -609,6 +609,41 @@ PVA_EXPORT int PvAmdGetQueriedRecords(PvAmdSolver* s, unsigned kind, float* out,
  * n > 0; slab groups and slab ranks; sparse-emitter (PVA_OPT_STREAMING_ANALYSIS) solvers. */
 #define PVA_RECORD_QUERIES_MAX 1024
 PVA_EXPORT int PvAmdSetRecordQueries(PvAmdSolver* s, const float* xyz, int n);
+/* Spectral query records: the three frequency-resolved record kinds further down -- band metrics, modulation, spectrum -- for
+ * the same cells, computed INSIDE the run.  `kinds` is a mask of PVA_QSPEC_*, a selector of its own beside PVA_QREC_*: the two
+ * selections, their pinned blocks and their launches are independent, and neither invalidates the other.  Every FOLLOWING run of
+ * any form (PvAmdRun, PvAmdRunAsync, PvAmdRunAsyncAfter, a member of PvAmdRunBatch, a run that PvAmdSync repeats) computes the
+ * selected kinds with ONE more launch on the solver's stream, directly behind the launch of the PVA_QREC_* kinds and in front of
+ * the run's last kernel, straight into pinned host memory: one wave per 64 queries and per block of bands (band metrics), per
+ * band (modulation) and per slice of 8 or 16 bins (spectrum); no pass over the history window, no per-cell device storage, no
+ * host synchronisation.  The cells are those of the record queries (PvAmdSetRecordQueries) when there are any, else those of the
+ * output queries.  PvAmdGetQueriedSpectralRecords waits for the run and then copies ONE kind's records from pinned memory without
+ * GPU work: nQueries x PvAmdQuerySpectralFloats(kind) floats, one record after the other in query order, each record in the
+ * layout of the whole-map read-back at one position -- band after band of 12 floats (PvAmdBandMetrics), band after band of 15
+ * floats (PvAmdModulation), bin after bin of {re, im, level}.
+ *   A record is bit for bit what PvAmdGetBandMetrics / PvAmdGetModulation / PvAmdGetSpectrum return at the query's position
+ * after the whole-map pass on the same run.  A query off the map gives NaNs, and so does a query whose cell has no onset in that
+ * run; the call returns 0 for them.  The bands, modulation frequencies and bins are those in force when the run was enqueued and
+ * the record sizes follow them.  PvAmdSetBands, PvAmdSetModulationFrequencies and PvAmdSetSpectrumBins wait for a run in flight
+ * as before; while a kind that depends on them is selected they also invalidate the in-run records until the next run has
+ * completed, and clearing the bands or the bins (n = 0) is refused.  The device tables are uploaded by the selector and by these
+ * setters, never by a run.
+ *   kinds = 0, the default, clears the selection and frees the pinned block (at most 312 floats per query, for at least 64
+ * queries, growing with the record queries): nothing is launched, and a run's launches are exactly those of a solver that never
+ * called this.
+ *   Refused with -1 and nothing changed, PvAmdLastError "spectral records: ...": an unknown bit; sparse-emitter
+ * (PVA_OPT_STREAMING_ANALYSIS) solvers; PVA_OPT_SKIP_ANALYSIS; slab groups and slab ranks; a band kind with no bands set; the
+ * spectrum kind with no bins set.  PvAmdGetQueriedSpectralRecords is refused when the kind is not selected (or is not exactly one
+ * bit), nQueries differs from the registered count, no run has completed since the kinds, the queries or the kind's settings
+ * changed, or the last run ended in error.  PvAmdQuerySpectralFloats: floats per query of ONE kind under the current settings, -1
+ * where it has none. */
+#define PVA_QSPEC_BAND_METRICS 1u   /* 12 floats per band of PvAmdSetBands      (PvAmdBandMetrics) */
+#define PVA_QSPEC_MODULATION   2u   /* 15 floats per band of PvAmdSetBands      (PvAmdModulation)  */
+#define PVA_QSPEC_SPECTRUM     4u   /* 3 floats per bin of PvAmdSetSpectrumBins (re, im, level)    */
+PVA_EXPORT int PvAmdSetQuerySpectralRecords(PvAmdSolver* s, unsigned kinds);
+PVA_EXPORT unsigned PvAmdGetQuerySpectralKinds(PvAmdSolver* s);
+PVA_EXPORT int PvAmdQuerySpectralFloats(PvAmdSolver* s, unsigned kind);
+PVA_EXPORT int PvAmdGetQueriedSpectralRecords(PvAmdSolver* s, unsigned kind, float* out, int nQueries);
 /* Whole result map: res8 = gx*gy*8 floats in AnalyzerResult order (Analyzer.h:13-21), delay = gx*gy */
 PVA_EXPORT int PvAmdCopyResults(PvAmdSolver* s, float* res8, float* delay);
 /* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records / onsets, row-major (either may be NULL) */

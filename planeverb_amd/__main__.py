@@ -103,9 +103,10 @@ def main(argv=None):
                     help="with --bands: add the modulation transfer function (m at the 14 IEC modulation frequencies) and the "
                          "modulation transfer index of each band at each emitter's cell")
     ap.add_argument("--in-run-records", action="store_true",
-                    help="take the room metrics, decay times, lateral fraction, echogram, echo criterion and lobes from records "
-                         "computed inside the run for the emitters' cells (at most 64 emitters) instead of from whole-map passes "
-                         "after it; the output is the same")
+                    help="take the room metrics, decay times, lateral fraction, echogram, echo criterion and lobes -- and the band "
+                         "metrics, modulation and spectrum of --bands, --modulation and --spectrum -- from records computed inside "
+                         "the run for the emitters' cells (at most 64 emitters) instead of from whole-map passes after it; the "
+                         "output is the same")
     ap.add_argument("--emission-records", action="store_true",
                     help="add all six record kinds of each emitter as the LIVE module serves them by emission id "
                          "(PlaneverbSetEmissionRecords; --echogram and --lobes give their settings, default 0.005,16 and "
@@ -139,10 +140,18 @@ def main(argv=None):
                 s.set_echogram(*a.echogram)
             if a.lobes is not None:
                 s.set_lobe_windows(a.lobes)
+            spectral = ((api.QSPEC_BAND_METRICS if a.bands else 0) | (api.QSPEC_MODULATION if a.modulation else 0) |
+                        (api.QSPEC_SPECTRUM if a.spectrum else 0))
+            if a.bands:
+                s.set_bands(a.bands, a.band_fraction)
+            if a.spectrum:
+                s.set_spectrum_bins(a.spectrum)
             s.set_output_queries(emitters)
             s.set_query_records(kinds)
+            s.set_query_spectral_records(spectral)
         s.run(a.listener)
         qrec = {} if whole else dict((k, s.queried_records(k)) for k in (1, 2, 4, 8, 16, 32) if kinds & k)
+        qspec = {} if whole else dict((k, s.queried_spectral_records(k)) for k in (1, 2, 4) if spectral & k)
         t = s.timings()
         out = {"scene": a.scene, "grid": [s.gx, s.gy], "T": s.T, "res": a.res, "dx": s.dx, "efree": s.efree,
                "listener": a.listener, "fdtd_ms": t.fdtdMs, "analysis_ms": t.analysisMs, "emitters": []}
@@ -160,12 +169,12 @@ def main(argv=None):
         if whole and a.lobes is not None:
             s.set_lobe_windows(a.lobes)
             s.compute_lobes()
-        if a.bands:
+        if whole and a.bands:
             s.set_bands(a.bands, a.band_fraction)
             s.compute_band_metrics()
-        if a.modulation:
+        if whole and a.modulation:
             s.compute_modulation()
-        if a.spectrum:
+        if whole and a.spectrum:
             s.set_spectrum_bins(a.spectrum)
             s.compute_spectrum()
         for i, e in enumerate(emitters):
@@ -197,18 +206,18 @@ def main(argv=None):
                 out["emitters"][-1]["lobes"] = {"n": float(m[0]), "windows": [
                     dict((n, float(v)) for n, v in zip(api.LOBE_NAMES, m[1 + 5 * w:6 + 5 * w])) for w in range((len(m) - 1) // 5)]}
             if a.bands:
-                m = s.band_metrics_at(e)
+                m = s.band_metrics_at(e) if whole else qspec[api.QSPEC_BAND_METRICS][i]
                 out["emitters"][-1]["bandMetrics"] = [
                     dict([("hz", float(hz)), ("fraction", a.band_fraction)] + [(n, float(v)) for n, v in zip(api.BAND_METRIC_NAMES, r)])
                     for hz, r in zip(a.bands, m)]
             if a.modulation:
-                m = s.modulation_at(e)
+                m = s.modulation_at(e) if whole else qspec[api.QSPEC_MODULATION][i]
                 out["emitters"][-1]["modulation"] = {
                     "hz": [float(v) for v in s.modulation_frequencies()],
                     "bands": [{"hz": float(hz), "fraction": a.band_fraction, "m": [float(v) for v in r[:-1]], "mti": float(r[-1])}
                               for hz, r in zip(a.bands, m)]}
             if a.spectrum:
-                m = s.spectrum_at(e)
+                m = s.spectrum_at(e) if whole else qspec[api.QSPEC_SPECTRUM][i]
                 out["emitters"][-1]["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],
                                                    "im": [float(v) for v in m[:, 1]], "levelDb": [float(v) for v in m[:, 2]]}
         if a.emission_records:

@@ -276,6 +276,10 @@ SYMBOLS = {
     "PvAmdQueryRecordFloats": (C.c_int, [_vp, C.c_uint]),
     "PvAmdGetQueriedRecords": (C.c_int, [_vp, C.c_uint, _fp, C.c_int]),
     "PvAmdSetRecordQueries": (C.c_int, [_vp, _fp, C.c_int]),
+    "PvAmdSetQuerySpectralRecords": (C.c_int, [_vp, C.c_uint]),
+    "PvAmdGetQuerySpectralKinds": (C.c_uint, [_vp]),
+    "PvAmdQuerySpectralFloats": (C.c_int, [_vp, C.c_uint]),
+    "PvAmdGetQueriedSpectralRecords": (C.c_int, [_vp, C.c_uint, _fp, C.c_int]),
     "PvAmdCopyResults": (C.c_int, [_vp, _fp, _fp]),
     "PvAmdCopyResultsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "PvAmdGetImpulseResponse": (C.c_int, [_vp, C.c_int, C.c_int, _fp]),
@@ -869,6 +873,11 @@ QREC_ECHO_CRITERION = 16
 QREC_LOBES = 32
 QREC_ALL = 63
 RECORD_QUERIES_MAX = 1024  # PVA_RECORD_QUERIES_MAX
+# PVA_QSPEC_*: the in-run frequency-resolved record kinds (Solver.set_query_spectral_records), a selector of their own
+QSPEC_BAND_METRICS = 1
+QSPEC_MODULATION = 2
+QSPEC_SPECTRUM = 4
+QSPEC_ALL = 7
 LOBES_DEFAULT_EDGES = (0.01, 0.08)
 LOBE_NAMES = ("e", "xp", "xn", "yp", "yn")
 LOBE_PATTERN_OMNI, LOBE_PATTERN_CARDIOID = 0, 1
@@ -1604,6 +1613,32 @@ class Solver:
         e = np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))
         _check(lib().PvAmdSetRecordQueries(self._h, _f(e) if len(e) else None, len(e)))
         self._nrq = len(e)
+
+    def set_query_spectral_records(self, kinds):
+        """the frequency-resolved record kinds (a mask of QSPEC_*: band metrics, modulation, spectrum) every following run
+        computes for the cells the query records follow, in one launch of their own inside the run and straight into pinned
+        host memory; 0 (the default) selects none and frees the block.  Independent of set_query_records"""
+        _check(lib().PvAmdSetQuerySpectralRecords(self._h, int(kinds)))
+
+    def query_spectral_kinds(self):
+        return int(lib().PvAmdGetQuerySpectralKinds(self._h))
+
+    def query_spectral_floats(self, kind):
+        """floats per query of ONE kind under the current bands / bins (12 n, 15 n, 3 bins)"""
+        n = lib().PvAmdQuerySpectralFloats(self._h, int(kind))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return n
+
+    def queried_spectral_records(self, kind):
+        """float32 [n_queries, n, 12], [n_queries, n, 15] or [n_queries, bins, 3] of ONE kind for the last run (waits for it; no
+        GPU work): each row bit for bit what band_metrics_at / modulation_at / spectrum_at(position) return after the whole-map
+        pass on the same run; NaN rows off the map and where no sound arrived"""
+        n = getattr(self, "_nrq", 0) or getattr(self, "_nq", 0)
+        per = {QSPEC_BAND_METRICS: 12, QSPEC_MODULATION: 15, QSPEC_SPECTRUM: 3}.get(int(kind), 1)
+        out = np.empty((n, self.query_spectral_floats(kind) // per, per), np.float32)
+        _check(lib().PvAmdGetQueriedSpectralRecords(self._h, int(kind), _f(out) if n else None, n))
+        return out
 
     def results(self):
         res = np.empty((self.gx, self.gy, 8), np.float32)

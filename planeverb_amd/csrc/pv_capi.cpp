@@ -20,6 +20,7 @@
 #include "pv_lobes.h"
 #include "pv_metrics.h"
 #include "pv_query_records.h"
+#include "pv_query_spectral.h"
 #include "pv_spectrum.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
 #include "pv_bake.h"
@@ -1152,6 +1153,42 @@ int PvAmdSetRecordQueries(PvAmdSolver* h, const float* xyz, int n) try {
         return -1;
     }
     return ret(h, h->s->setRecordQueries(xyz, n));
+} PV_API_CATCH(-1)
+
+// in-run spectral records (pv_query_spectral.hip): single whole-grid solvers only; every refusal says "spectral records: ..."
+static_assert(PVA_QSPEC_BAND_METRICS == 1u << kQspecBandMetrics && PVA_QSPEC_MODULATION == 1u << kQspecModulation &&
+                  PVA_QSPEC_SPECTRUM == 1u << kQspecSpectrum,
+              "planeverb_amd.h vs pv_query_spectral.h");
+static bool spectralRecordsHandle(PvAmdSolver* h) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = "spectral records: " + g_lastError;
+    return false;
+}
+
+int PvAmdSetQuerySpectralRecords(PvAmdSolver* h, unsigned kinds) try {
+    if (!spectralRecordsHandle(h)) return -1;
+    return ret(h, h->s->setQuerySpectralRecords(kinds));
+} PV_API_CATCH(-1)
+
+unsigned PvAmdGetQuerySpectralKinds(PvAmdSolver* h) try {
+    if (!spectralRecordsHandle(h)) return 0u;
+    return h->s->querySpectralKinds();
+} PV_API_CATCH(0u)
+
+int PvAmdQuerySpectralFloats(PvAmdSolver* h, unsigned kind) try {
+    if (!spectralRecordsHandle(h)) return -1;
+    const int n = h->s->querySpectralFloats(kind);
+    if (n < 0) ret(h, false);
+    return n;
+} PV_API_CATCH(-1)
+
+int PvAmdGetQueriedSpectralRecords(PvAmdSolver* h, unsigned kind, float* out, int nQueries) try {
+    if (!spectralRecordsHandle(h)) return -1;
+    if (nQueries < 0 || nQueries > kMaxRecordQueries || (nQueries > 0 && !out)) {
+        g_lastError = "spectral records: PvAmdGetQueriedSpectralRecords: 0 .. 1024 queries and an output buffer";
+        return -1;
+    }
+    return ret(h, h->s->queriedSpectralRecords(kind, out, nQueries));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyResults(PvAmdSolver* h, float* res8, float* delay) try {

@@ -160,6 +160,10 @@ void launchLobes(const AnalyzeArgs& a, float* out, const LobeEdges& ed, int nW, 
 // memory (pv_query_records.h); the records are bit for bit the whole-map passes' at the same cells
 struct QueryRecordArgs;
 void launchQueryRecords(const AnalyzeArgs& a, const QueryRecordArgs& q, hipStream_t stream);
+// ---- pv_query_spectral.hip: band metrics, modulation and spectrum (below) for the same cells, inside the run, with a launch of
+// their own: one wave per work item (a block of bands, a band, a slice of bins) and per 64 queries (pv_query_spectral.h)
+struct QuerySpectralArgs;
+void launchQuerySpectral(const AnalyzeArgs& a, const QuerySpectralArgs& q, hipStream_t stream);
 
 // ---- pv_bands.hip: per-cell, per-band decay times and clarity
 // band records of the last completed run (pv_bands.hip) for n bands: coefs = n x kBandCoefs floats on the HOST (they travel as

@@ -27,6 +27,7 @@
 #include "pv_lobes.h"
 #include "pv_metrics.h"
 #include "pv_query_records.h"
+#include "pv_query_spectral.h"
 #include "pv_spectrum.h"
 
 namespace pva {
@@ -720,6 +721,7 @@ Solver::~Solver() {
         if (e) hipEventDestroy(e);
     if (lobes_) hipFree(lobes_);
     if (qrecHost_) hipHostFree(qrecHost_);
+    if (qspecHost_) hipHostFree(qspecHost_);
     if (rqCellsHost_) hipHostFree(rqCellsHost_);
     for (auto& e : lobesEv_)
         if (e) hipEventDestroy(e);
@@ -2162,6 +2164,7 @@ bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, floa
     metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;       // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     qrecRun_ = QrecRun::None;    // (the pinned block is about to be overwritten, or this run leaves no records)
+    qspecRun_ = QrecRun::None;
     if (!applyGeometry()) return false;
     PathRun r;
     r.kind = kind;
@@ -2229,6 +2232,7 @@ bool Solver::enqueueRun(int lcx, int lcy, float lx, float lz) {
     if (!stampTimed()) hipEventRecord(ev_[2], stream_);
     lastRunBatched_ = false;
     enqueueQueryRecords();
+    enqueueQuerySpectralRecords();
     // last kernel of the run: the registered queries' outputs and the status words, both into pinned memory
     launchRunFinish(res_, (long long)g_.gx * g_.gy, qCellsHost_, opt_.skipAnalysis ? 0 : numQueries_, qOutHost_, farInfo(), errFlag_,
                     activeCount_, plan_.oneXcd ? resFlags_ + runTiles_ + 1 : nullptr, statusHost_, resFlags_,
@@ -2678,6 +2682,7 @@ bool Solver::sync() {
         if (flag) return fail("pressure history window overflow (a tile outside the window became non-zero)");
         lastRun_ = plan_.kind == PathRun::Raw ? LastRun::None : LastRun::Ok;  // (raw stepping records no history)
         if (qrecRun_ == QrecRun::Pending) qrecRun_ = QrecRun::Ok;
+        if (qspecRun_ == QrecRun::Pending) qspecRun_ = QrecRun::Ok;
     }
     return true;
 }
@@ -2725,7 +2730,7 @@ bool Solver::setOutputQueries(const float* xyz, int n) {
         qCellsHost_[i] = resultCell(g_, xyz[3 * i], xyz[3 * i + 2], &cx, &cy) ? (long long)cx * g_.gy + cy : -1;
     }
     numQueries_ = n;
-    if (numRecQueries_ == 0) qrecRun_ = QrecRun::None;  // (the records in the pinned block belong to the queries of before)
+    if (numRecQueries_ == 0) qrecRun_ = qspecRun_ = QrecRun::None;  // (the records in the pinned blocks belong to the queries of before)
     return true;
 }
 
@@ -2744,13 +2749,13 @@ bool Solver::setRecordQueries(const float* xyz, int n) {
         rqCellsHost_ = t;
         rqCap_ = n;
     }
-    if (!growQrecBlock(qrecKinds_, n)) return false;
+    if (!growQrecBlock(qrecKinds_, n) || !growQspecBlock(qspecKinds_, n)) return false;
     for (int i = 0; i < n; ++i) {
         int cx, cy;
         rqCellsHost_[i] = resultCell(g_, xyz[3 * i], xyz[3 * i + 2], &cx, &cy) ? (long long)cx * g_.gy + cy : -1;
     }
     numRecQueries_ = n;
-    qrecRun_ = QrecRun::None;  // (the records in the pinned block belong to the table of before)
+    qrecRun_ = qspecRun_ = QrecRun::None;  // (the records in the pinned blocks belong to the table of before)
     return true;
 }
 
@@ -2762,6 +2767,7 @@ void Solver::enqueueRunStatus() {
 
 void Solver::enqueueQueries() {
     enqueueQueryRecords();
+    enqueueQuerySpectralRecords();
     if (numQueries_ > 0 && !opt_.skipAnalysis)
         launchGatherQueries(res_, (long long)g_.gx * g_.gy, qCellsHost_, numQueries_, qOutHost_, farInfo(), stream_);
     enqueueTap();
@@ -2918,6 +2924,147 @@ bool Solver::queriedRecords(unsigned kind, float* out, int n) {
         return fail("query records: no completed run since the kinds, the queries or the settings changed");
     const float* src = qrecHost_ + qrecRunOffset_[k];
     for (int i = 0; i < n * qrecRunFloats_[k]; ++i) out[i] = src[i];
+    return true;
+}
+
+// ---- in-run spectral records (pv_query_spectral.hip): the twins of the six kinds' functions above
+namespace {
+// floats per query of the pinned block: every selected kind at its largest setting (kBandsMax bands, kSpectrumMaxBins bins), so
+// that a later change of bands or bins needs no allocation
+size_t qspecBlockFloats(unsigned kinds) {
+    size_t cap = 0;
+    if (kinds & (1u << kQspecBandMetrics)) cap += (size_t)kBandFloats * kBandsMax;
+    if (kinds & (1u << kQspecModulation)) cap += (size_t)kModFloats * kBandsMax;
+    if (kinds & (1u << kQspecSpectrum)) cap += (size_t)kSpectrumFloats * kSpectrumMaxBins;
+    return cap;
+}
+int qspecBit(unsigned kind) {  // the bit of a mask that names ONE kind, or -1
+    for (int k = 0; k < kQuerySpectralKinds; ++k)
+        if (kind == (1u << k)) return k;
+    return -1;
+}
+constexpr unsigned kQspecBandKinds = (1u << kQspecBandMetrics) | (1u << kQspecModulation);
+}  // namespace
+
+int Solver::qspecFloatsOf(int k) const {
+    const int n = (int)bandHz_.size(), bins = (int)specHz_.size();
+    switch (k) {
+        case kQspecBandMetrics: return n > 0 ? kBandFloats * n : -1;
+        case kQspecModulation: return n > 0 ? kModFloats * n : -1;
+        case kQspecSpectrum: return bins > 0 ? kSpectrumFloats * bins : -1;
+    }
+    return -1;
+}
+
+bool Solver::setQuerySpectralRecords(unsigned kinds) {
+    if (kinds & ~kQuerySpectralMask) return fail("spectral records: unknown kind bit (PVA_QSPEC_*)");
+    if (kinds) {
+        if (isSlab()) return fail("spectral records: not available on a slab");
+        if (opt_.streaming) return fail("spectral records: the full pressure history is not kept in streaming-analysis mode");
+        if (opt_.skipAnalysis) return fail("spectral records: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+        if ((kinds & kQspecBandKinds) && bandHz_.empty()) return fail("spectral records: no bands set (PvAmdSetBands)");
+        if ((kinds & (1u << kQspecSpectrum)) && specHz_.empty()) return fail("spectral records: no bins set (PvAmdSetSpectrumBins)");
+    }
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // the launch of a run in flight still writes the pinned block
+    if (kinds == qspecKinds_) return true;
+    // (the spectrum's tables are on the device from PvAmdSetSpectrumBins on; the modulation's are made valid here)
+    if ((kinds & (1u << kQspecModulation)) && !ensureModTable()) return false;
+    const size_t cap = qspecBlockFloats(kinds);
+    const int queries = numRecQueries_ > kMaxQueries ? numRecQueries_ : kMaxQueries;
+    float* block = nullptr;
+    if (cap && !hipOk(hipHostMalloc((void**)&block, cap * queries * sizeof(float)), "hipHostMalloc")) return false;
+    if (qspecHost_) hipHostFree(qspecHost_);
+    qspecHost_ = block;
+    qspecBlockQueries_ = block ? queries : 0;
+    qspecKinds_ = kinds;
+    qspecRun_ = QrecRun::None;
+    return true;
+}
+
+// the pinned block of the selected kinds with room for `queries` queries (no run in flight); nothing while no kind is selected
+bool Solver::growQspecBlock(unsigned kinds, int queries) {
+    if (!kinds || queries <= qspecBlockQueries_) return true;
+    float* block = nullptr;
+    if (!hipOk(hipHostMalloc((void**)&block, qspecBlockFloats(kinds) * queries * sizeof(float)), "hipHostMalloc")) return false;
+    if (qspecHost_) hipHostFree(qspecHost_);
+    qspecHost_ = block;
+    qspecBlockQueries_ = queries;
+    qspecRun_ = QrecRun::None;
+    return true;
+}
+
+int Solver::querySpectralFloats(unsigned kind) {
+    const int k = qspecBit(kind);
+    if (k < 0) {
+        fail("spectral records: exactly one kind (PVA_QSPEC_*)");
+        return -1;
+    }
+    const int n = qspecFloatsOf(k);
+    if (n < 0) fail(k == kQspecSpectrum ? "spectral records: no bins set (PvAmdSetSpectrumBins)" : "spectral records: no bands set (PvAmdSetBands)");
+    return n;
+}
+
+// The settings are those of this moment: PvAmdSetBands, PvAmdSetModulationFrequencies and PvAmdSetSpectrumBins wait for a run in
+// flight and leave the device tables valid, and the stamp keeps the layout the run was enqueued with.  A kind whose tables are
+// missing (an upload that failed in a setter) is left out: its stamp then differs from the settings and its read-back is refused
+void Solver::enqueueQuerySpectralRecords() {
+    if (!qspecKinds_ || opt_.skipAnalysis) return;
+    QuerySpectralArgs q{};
+    const int nq = qrecQueries();
+    q.cells = numRecQueries_ > 0 ? rqCellsHost_ : qCellsHost_;
+    q.out = qspecHost_;
+    q.nq = nq;
+    const int n = (int)bandHz_.size(), B = bandMetricsBlock();
+    q.nBands = n;
+    for (int j = 0; j < n; ++j)
+        for (int k = 0; k < kBandCoefs; ++k) q.coefs[j][k] = bandCoefs_[(size_t)j * kBandCoefs + k];
+    const bool on[kQuerySpectralKinds] = {(qspecKinds_ & (1u << kQspecBandMetrics)) && n > 0,
+                                          (qspecKinds_ & (1u << kQspecModulation)) && n > 0 && modTab_ && modTabValid_,
+                                          (qspecKinds_ & (1u << kQspecSpectrum)) && !specPasses_.empty() && specTab_ && specPow_ &&
+                                              (int)specPasses_.size() <= kQspecMaxSlices};
+    q.items[kQspecBandMetrics] = on[kQspecBandMetrics] ? (n + B - 1) / B : 0;
+    q.items[kQspecModulation] = on[kQspecModulation] ? n : 0;
+    q.items[kQspecSpectrum] = on[kQspecSpectrum] ? (int)specPasses_.size() : 0;
+    int off = 0, items = 0;
+    for (int k = 0; k < kQuerySpectralKinds; ++k) {
+        q.floats[k] = on[k] ? qspecFloatsOf(k) : 0;
+        q.offset[k] = off;
+        off += q.floats[k] * nq;
+        items += q.items[k];
+        qspecRunFloats_[k] = q.floats[k];
+        qspecRunOffset_[k] = q.offset[k];
+    }
+    const int fs = (int)g_.fs;
+    q.tailN = decayTailN(fs);
+    q.n50 = roomMetricsN50(fs);
+    q.n80 = roomMetricsN80(fs);
+    q.modTab = modTab_ ? modTab_ + (size_t)kModTablePad * kModRowStride : nullptr;
+    q.specTab = specTab_;
+    q.specPow = specPow_;
+    for (int i = 0; i < q.items[kQspecSpectrum]; ++i) {
+        const SpecPass& ps = specPasses_[(size_t)i];
+        q.slice[i] = QuerySpectralSlice{ps.bin0, ps.bins, ps.block, (long long)ps.tabOff};
+    }
+    qspecRunKinds_ = qspecKinds_;
+    qspecRunQueries_ = nq;
+    qspecRun_ = QrecRun::Pending;
+    if (nq > 0 && items > 0) launchQuerySpectral(analyzeArgs(lastLx_, lastLz_), q, stream_);
+}
+
+// after the run has been waited for: the records of one kind, straight from pinned memory
+bool Solver::queriedSpectralRecords(unsigned kind, float* out, int n) {
+    const int k = qspecBit(kind);
+    if (k < 0) return fail("spectral records: exactly one kind (PVA_QSPEC_*)");
+    if (!(qspecKinds_ & kind)) return fail("spectral records: the kind is not selected (PvAmdSetQuerySpectralRecords)");
+    if (n != qrecQueries()) return fail("spectral records: count differs from the registered queries");
+    if (pendingTimings_ && !sync()) return false;
+    if (lastRun_ == LastRun::Failed) return fail("spectral records: the last run ended in error");
+    if (qspecRun_ != QrecRun::Ok || qspecRunKinds_ != qspecKinds_ || qspecRunQueries_ != qrecQueries() || qspecRunFloats_[k] != qspecFloatsOf(k))
+        return fail("spectral records: no completed run since the kinds, the queries or the settings changed");
+    const float* src = qspecHost_ + qspecRunOffset_[k];
+    for (int i = 0; i < n * qspecRunFloats_[k]; ++i) out[i] = src[i];
     return true;
 }
 
@@ -3660,6 +3807,8 @@ bool Solver::lobesAt(float ex, float ez, float* out) {
 
 bool Solver::setBands(const float* centreHz, int n, int fraction) {
     if (isSlab()) return fail("band metrics: not available on a slab");
+    if (n == 0 && (qspecKinds_ & kQspecBandKinds))
+        return fail("spectral records: the bands cannot be cleared while a band kind is selected (PvAmdSetQuerySpectralRecords)");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
@@ -3667,6 +3816,7 @@ bool Solver::setBands(const float* centreHz, int n, int fraction) {
     bandsHostValid_ = false;
     modulationValid_ = false;  // (the modulation records are per band)
     modulationHostValid_ = false;
+    if (qspecKinds_ & kQspecBandKinds) qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old bands')
     bandHz_.clear();
     bandCoefs_.clear();
     if (n == 0) {
@@ -3792,6 +3942,28 @@ bool Solver::setModulationFrequencies(const float* hz14) {
     modulationHostValid_ = false;
     modTabValid_ = false;
     for (int i = 0; i < kModFreqs; ++i) modHz_[i] = hz14 ? hz14[i] : kModDefaultHz[i];
+    if (qspecKinds_ & (1u << kQspecModulation)) {
+        qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old frequencies')
+        return ensureModTable();    // (the next run's launch reads the table: never uploaded from the enqueue path)
+    }
+    return true;
+}
+
+// the twiddle table of the current modulation frequencies on the device (no run in flight: the upload waits for the stream)
+bool Solver::ensureModTable() {
+    const int T = T_;  // the run's steps (PVA_OPT_NUM_STEPS): the planes of the history
+    const size_t rows = (size_t)T + kModTablePad;
+    if (!modTab_ && !dalloc(&modTab_, rows * kModRowStride, false)) return false;
+    if (!modTabValid_) {  // rows -kModTablePad .. -1: zero; rows 0 .. T - 1: the table, 28 floats and four zeros each
+        std::vector<float> def((size_t)T * kModRowFloats), tab(rows * kModRowStride, 0.f);
+        modulationTable(T, (int)g_.fs, modHz_, def.data());
+        for (int t = 0; t < T; ++t)
+            std::memcpy(&tab[((size_t)t + kModTablePad) * kModRowStride], &def[(size_t)t * kModRowFloats], kModRowFloats * sizeof(float));
+        if (!hipOk(hipMemcpyAsync(modTab_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream_), "modulation table upload") ||
+            !hipOk(hipStreamSynchronize(stream_), "modulation table sync"))
+            return false;
+        modTabValid_ = true;
+    }
     return true;
 }
 
@@ -3818,19 +3990,7 @@ bool Solver::computeModulation(float* ms) {
         if (!dalloc(&modulation_, (size_t)kModFloats * n * (size_t)histPlane_, false)) return false;
         modulationPlanes_ = kModFloats * n;
     }
-    const int T = T_;  // the run's steps (PVA_OPT_NUM_STEPS): the planes of the history
-    const size_t rows = (size_t)T + kModTablePad;
-    if (!modTab_ && !dalloc(&modTab_, rows * kModRowStride, false)) return false;
-    if (!modTabValid_) {  // rows -kModTablePad .. -1: zero; rows 0 .. T - 1: the table, 28 floats and four zeros each
-        std::vector<float> def((size_t)T * kModRowFloats), tab(rows * kModRowStride, 0.f);
-        modulationTable(T, (int)g_.fs, modHz_, def.data());
-        for (int t = 0; t < T; ++t)
-            std::memcpy(&tab[((size_t)t + kModTablePad) * kModRowStride], &def[(size_t)t * kModRowFloats], kModRowFloats * sizeof(float));
-        if (!hipOk(hipMemcpyAsync(modTab_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream_), "modulation table upload") ||
-            !hipOk(hipStreamSynchronize(stream_), "modulation table sync"))
-            return false;
-        modTabValid_ = true;
-    }
+    if (!ensureModTable()) return false;
     for (auto& e : modulationEv_)
         if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
     modulationValid_ = false;
@@ -3912,11 +4072,14 @@ static int spectrumBlockFor(int left) {
 
 bool Solver::setSpectrumBins(const float* hz, int n) {
     if (isSlab()) return fail("spectrum: not available on a slab");
+    if (n == 0 && (qspecKinds_ & (1u << kQspecSpectrum)))
+        return fail("spectral records: the bins cannot be cleared while PVA_QSPEC_SPECTRUM is selected (PvAmdSetQuerySpectralRecords)");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
     spectrumValid_ = false;
     spectrumHostValid_ = false;
+    if (qspecKinds_ & (1u << kQspecSpectrum)) qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old bins')
     for (float** p : {&specTab_, &specPow_})
         if (*p) {
             hipFree(*p);

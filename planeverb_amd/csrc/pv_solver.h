@@ -236,6 +236,15 @@ public:
     // the registered count.  Waits for a run in flight; a change invalidates the records until the next run
     bool setRecordQueries(const float* xyz, int n);
     int recordQueries() const { return numRecQueries_; }
+    // In-run FREQUENCY-RESOLVED records of the same cells (pv_query_spectral.hip; PvAmdSetQuerySpectralRecords): band metrics,
+    // modulation and spectrum, a mask of bits kQspec* (pv_query_spectral.h) with a selector, a pinned block and a launch of their
+    // own, directly behind the launch above.  Everything else as setQueryRecords ... queriedRecords; the records follow the bands,
+    // the modulation frequencies and the bins in force when the run was enqueued, and a change of those invalidates them until
+    // the next run has completed.  The device tables are made valid here and in the setters, never on the enqueue path
+    bool setQuerySpectralRecords(unsigned kinds);
+    unsigned querySpectralKinds() const { return qspecKinds_; }
+    int querySpectralFloats(unsigned kind);  // -1: not one kind, or its bands / bins are not set
+    bool queriedSpectralRecords(unsigned kind, float* out, int n);
     bool copyResults(float* res8, float* delay);
     // the block [r0, r0 + nr) x [c0, c0 + nc) of the result map (AoS records) and of the onset map, row-major nr x nc
     bool copyResultsBlock(int r0, int c0, int nr, int nc, float* res8, float* delay);
@@ -622,7 +631,7 @@ private:
     hipEvent_t bandsEv_[2] = {nullptr, nullptr};
     bool fetchBandMetrics();
     // modulation (pv_modulation.h): the 14 modulation frequencies (the default until some are set) and their twiddle table on the
-    // device (kModTablePad zero rows, then T rows of 28 floats padded to 32), uploaded by the first computeModulation after a change; 15 n planes
+    // device (kModTablePad zero rows, then T rows of 28 floats padded to 32), uploaded by ensureModTable after a change; 15 n planes
     // of histPlane_ floats -- band j at planes 15 j .. 15 j + 14 -- allocated by the first computeModulation and again when n
     // changes.  modulationValid_ follows metricsValid_ and is also cleared by a change of bands or frequencies; no computation
     // touches another's flag
@@ -684,6 +693,18 @@ private:
     bool growQrecBlock(unsigned kinds, int queries);
     int qrecRunOffset_[6] = {0, 0, 0, 0, 0, 0}, qrecRunFloats_[6] = {0, 0, 0, 0, 0, 0};
     void enqueueQueryRecords();  // behind a run's analysis, in front of its last kernel (nothing when no kind is selected)
+    // in-run spectral records (band metrics, modulation, spectrum): the twins of the members above, with a pinned block of their
+    // own that holds qspecBlockQueries_ queries at the selected kinds' largest settings (8 bands, 32 bins)
+    unsigned qspecKinds_ = 0;
+    float* qspecHost_ = nullptr;
+    QrecRun qspecRun_ = QrecRun::None;
+    unsigned qspecRunKinds_ = 0;
+    int qspecRunQueries_ = 0, qspecBlockQueries_ = 0;
+    int qspecRunOffset_[3] = {0, 0, 0}, qspecRunFloats_[3] = {0, 0, 0};
+    int qspecFloatsOf(int k) const;  // floats per query of kind bit k under the current settings, -1 where they are missing
+    bool growQspecBlock(unsigned kinds, int queries);
+    bool ensureModTable();               // the modulation twiddle table on the device (no run in flight)
+    void enqueueQuerySpectralRecords();  // directly behind enqueueQueryRecords (nothing when no kind is selected)
     int* listHost_ = nullptr;
     int listCap_ = 0;
     // row-streaming air segments (pv_seg.h): rebuilt for every run (they avoid the tiles around the listener)
