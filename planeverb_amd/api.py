@@ -1689,108 +1689,98 @@ class Solver:
         _check(lib().PvAmdCopyHistoryPlane(self._h, int(t), _f(out)))
         return out
 
+    # The nine per-cell analysis kinds share four call shapes: compute -> device milliseconds, the whole map, a block of it, the
+    # record at a position; `width` = the trailing dimensions of a record
+    def _map_ms(self, fn):
+        ms = C.c_float(0.0)
+        _check(fn(self._h, C.byref(ms)))
+        return ms.value
+
+    def _map_all(self, fn, *width):
+        out = np.empty((self.gx, self.gy) + width, np.float32)
+        _check(fn(self._h, _f(out)))
+        return out
+
+    def _map_block(self, fn, r0, c0, nr, nc, *width):
+        out = np.empty((nr, nc) + width, np.float32)
+        _check(fn(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
+        return out
+
+    def _map_at(self, fn, pos, *width, record=None):
+        out = record() if record else np.empty(width, np.float32)
+        _check(fn(self._h, *[float(v) for v in pos], out if record else _f(out)))
+        return out.as_array() if record else out
+
     def compute_room_metrics(self):
         """room metrics (C50, C80, D50, Ts: ROOM_METRIC_NAMES) of the last completed run, one pass on the device; returns
         the pass's device time in milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeRoomMetrics(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeRoomMetrics)
 
     def room_metrics(self):
         """float32 [gx, gy, 10] (ROOM_METRIC_NAMES); NaN where the cell has no onset in the run they were computed for"""
-        out = np.empty((self.gx, self.gy, 10), np.float32)
-        _check(lib().PvAmdCopyRoomMetrics(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopyRoomMetrics, 10)
 
     def room_metrics_block(self, r0, c0, nr, nc):
         """the records [nr, nc, 10] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, 10), np.float32)
-        _check(lib().PvAmdCopyRoomMetricsBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopyRoomMetricsBlock, r0, c0, nr, nc, 10)
 
     def room_metrics_at(self, pos):
         """float32 [10] at an emitter position (the cell get_output reads); ten NaNs off the map"""
-        out = PvAmdRoomMetrics()
-        _check(lib().PvAmdGetRoomMetrics(self._h, *[float(v) for v in pos], out))
-        return out.as_array()
+        return self._map_at(lib().PvAmdGetRoomMetrics, pos, record=PvAmdRoomMetrics)
 
     def compute_decay_times(self):
         """decay times (EDT, T20, T30: DECAY_TIME_NAMES) of the last completed run, two backward walks of its history on the
         device; returns the pass's device time in milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeDecayTimes(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeDecayTimes)
 
     def decay_times(self):
         """float32 [gx, gy, 8] (DECAY_TIME_NAMES); NaN where the cell has no onset in the run they were computed for, and in
         edt / t20 / t30 where the recorded curve does not fall through the range"""
-        out = np.empty((self.gx, self.gy, 8), np.float32)
-        _check(lib().PvAmdCopyDecayTimes(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopyDecayTimes, 8)
 
     def decay_times_block(self, r0, c0, nr, nc):
         """the records [nr, nc, 8] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, 8), np.float32)
-        _check(lib().PvAmdCopyDecayTimesBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopyDecayTimesBlock, r0, c0, nr, nc, 8)
 
     def decay_times_at(self, pos):
         """float32 [8] at an emitter position (the cell get_output reads); eight NaNs off the map"""
-        out = PvAmdDecayTimes()
-        _check(lib().PvAmdGetDecayTimes(self._h, *[float(v) for v in pos], out))
-        return out.as_array()
+        return self._map_at(lib().PvAmdGetDecayTimes, pos, record=PvAmdDecayTimes)
 
     def compute_echo_criterion(self):
         """echo criterion (Dietsch and Kraak, speech and music: ECHO_CRITERION_NAMES) of the last completed run, one forward
         pass over its history on the device; returns the pass's device time in milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeEchoCriterion(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeEchoCriterion)
 
     def echo_criterion(self):
         """float32 [gx, gy, 10] (ECHO_CRITERION_NAMES); NaN where the cell has no onset in the run they were computed for"""
-        out = np.empty((self.gx, self.gy, 10), np.float32)
-        _check(lib().PvAmdCopyEchoCriterion(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopyEchoCriterion, 10)
 
     def echo_criterion_block(self, r0, c0, nr, nc):
         """the records [nr, nc, 10] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, 10), np.float32)
-        _check(lib().PvAmdCopyEchoCriterionBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopyEchoCriterionBlock, r0, c0, nr, nc, 10)
 
     def echo_criterion_at(self, pos):
         """float32 [10] at an emitter position (the cell get_output reads); ten NaNs off the map"""
-        out = PvAmdEchoCriterion()
-        _check(lib().PvAmdGetEchoCriterion(self._h, *[float(v) for v in pos], out))
-        return out.as_array()
+        return self._map_at(lib().PvAmdGetEchoCriterion, pos, record=PvAmdEchoCriterion)
 
     def compute_lateral_fraction(self):
         """early lateral energy fraction and early-sound direction (LATERAL_FRACTION_NAMES) of the last completed run: the
         velocity recurrence through the 80 ms window of every reached cell, on the device; returns the pass's device time in
         milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeLateralFraction(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeLateralFraction)
 
     def lateral_fraction(self):
         """float32 [gx, gy, 11] (LATERAL_FRACTION_NAMES); NaN where the cell has no onset in the run they were computed for, and
         in lf / dir_x / dir_y where the early flux is zero"""
-        out = np.empty((self.gx, self.gy, 11), np.float32)
-        _check(lib().PvAmdCopyLateralFraction(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopyLateralFraction, 11)
 
     def lateral_fraction_block(self, r0, c0, nr, nc):
         """the records [nr, nc, 11] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, 11), np.float32)
-        _check(lib().PvAmdCopyLateralFractionBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopyLateralFractionBlock, r0, c0, nr, nc, 11)
 
     def lateral_fraction_at(self, pos):
         """float32 [11] at an emitter position (the cell get_output reads); eleven NaNs off the map"""
-        out = PvAmdLateralFraction()
-        _check(lib().PvAmdGetLateralFraction(self._h, *[float(v) for v in pos], out))
-        return out.as_array()
+        return self._map_at(lib().PvAmdGetLateralFraction, pos, record=PvAmdLateralFraction)
 
     def set_echogram(self, slot_seconds, n_slots):
         """the time slots compute_echogram sums into: n_slots (at most ECHOGRAM_MAX_SLOTS) of (int)(slot_seconds * fs) steps each,
@@ -1809,28 +1799,20 @@ class Solver:
         """directional echogram of the last completed run at the slots of set_echogram: energy p^2 and flux p vx, p vy of
         every reached cell per slot, the velocity by the stencil's recurrence, on the device; returns the pass's device time in
         milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeEchogram(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeEchogram)
 
     def echogram(self):
         """float32 [gx, gy, 1 + 3 n]: n = the steps summed, then e, ix, iy of each slot; NaN where the cell has no onset in the
         run they were computed for.  (ix, iy) is the direction slot j's sound travels in, neither normalised nor negated"""
-        out = np.empty((self.gx, self.gy, 1 + 3 * self.echogram_slots()[0]), np.float32)
-        _check(lib().PvAmdCopyEchogram(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopyEchogram, 1 + 3 * self.echogram_slots()[0])
 
     def echogram_block(self, r0, c0, nr, nc):
         """the records [nr, nc, 1 + 3 n] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, 1 + 3 * self.echogram_slots()[0]), np.float32)
-        _check(lib().PvAmdCopyEchogramBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopyEchogramBlock, r0, c0, nr, nc, 1 + 3 * self.echogram_slots()[0])
 
     def echogram_at(self, pos):
         """float32 [1 + 3 n] at an emitter position (the cell get_output reads); NaNs off the map"""
-        out = np.empty(1 + 3 * self.echogram_slots()[0], np.float32)
-        _check(lib().PvAmdGetEchogram(self._h, *[float(v) for v in pos], _f(out)))
-        return out
+        return self._map_at(lib().PvAmdGetEchogram, pos, 1 + 3 * self.echogram_slots()[0])
 
     def set_lobe_windows(self, edges=None):
         """the time windows compute_lobes sums into, by their edges in seconds after every cell's own onset (at most
@@ -1854,28 +1836,20 @@ class Solver:
         """directional energy lobes of the last completed run for the windows of set_lobe_windows: the energy p^2 of every
         reached cell per window and its split over the travel directions +x, -x, +y, -y, the velocity by the stencil's recurrence,
         on the device; returns the pass's device time in milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeLobes(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeLobes)
 
     def lobes(self):
         """float32 [gx, gy, 1 + 5 nW]: n = the steps of the response, then LOBE_NAMES (e, xp, xn, yp, yn) of each window; NaN
         where the cell has no onset in the run they were computed for.  xp is the energy that travels towards +x at the cell"""
-        out = np.empty((self.gx, self.gy, self._lobe_floats()), np.float32)
-        _check(lib().PvAmdCopyLobes(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopyLobes, self._lobe_floats())
 
     def lobes_block(self, r0, c0, nr, nc):
         """the records [nr, nc, 1 + 5 nW] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, self._lobe_floats()), np.float32)
-        _check(lib().PvAmdCopyLobesBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopyLobesBlock, r0, c0, nr, nc, self._lobe_floats())
 
     def lobes_at(self, pos):
         """float32 [1 + 5 nW] at an emitter position (the cell get_output reads); NaNs off the map"""
-        out = np.empty(self._lobe_floats(), np.float32)
-        _check(lib().PvAmdGetLobes(self._h, *[float(v) for v in pos], _f(out)))
-        return out
+        return self._map_at(lib().PvAmdGetLobes, pos, self._lobe_floats())
 
     def set_bands(self, hz, fraction=1):
         """the band centres (Hz, at most BANDS_MAX) compute_band_metrics filters into, octaves (fraction 1) or third octaves
@@ -1901,27 +1875,19 @@ class Solver:
     def compute_band_metrics(self):
         """decay times and clarity per band (BAND_METRIC_NAMES) of the last completed run at the bands of set_bands, on the
         device; returns the device time of the passes in milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeBandMetrics(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeBandMetrics)
 
     def band_metrics(self):
         """float32 [gx, gy, n, 12] (BAND_METRIC_NAMES); NaN where the cell has no onset in the run they were computed for"""
-        out = np.empty((self.gx, self.gy, len(self.bands()[0]), 12), np.float32)
-        _check(lib().PvAmdCopyBandMetrics(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopyBandMetrics, len(self.bands()[0]), 12)
 
     def band_metrics_block(self, r0, c0, nr, nc):
         """the records [nr, nc, n, 12] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, len(self.bands()[0]), 12), np.float32)
-        _check(lib().PvAmdCopyBandMetricsBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopyBandMetricsBlock, r0, c0, nr, nc, len(self.bands()[0]), 12)
 
     def band_metrics_at(self, pos):
         """float32 [n, 12] at an emitter position (the cell get_output reads); NaNs off the map"""
-        out = np.empty((len(self.bands()[0]), 12), np.float32)
-        _check(lib().PvAmdGetBandMetrics(self._h, *[float(v) for v in pos], _f(out)))
-        return out
+        return self._map_at(lib().PvAmdGetBandMetrics, pos, len(self.bands()[0]), 12)
 
     def set_modulation_frequencies(self, hz=None):
         """the 14 modulation frequencies (Hz, each in [0, fs / 2]) compute_modulation evaluates; None restores the default series
@@ -1938,28 +1904,20 @@ class Solver:
     def compute_modulation(self):
         """the modulation transfer function and index per band of set_bands of the last completed run, on the device; returns the
         device time of the passes in milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeModulation(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeModulation)
 
     def modulation(self):
         """float32 [gx, gy, n, 15] (m at the 14 modulation frequencies, then mti); NaN where the cell has no onset in the run they
         were computed for"""
-        out = np.empty((self.gx, self.gy, len(self.bands()[0]), MODULATION_FREQS + 1), np.float32)
-        _check(lib().PvAmdCopyModulation(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopyModulation, len(self.bands()[0]), MODULATION_FREQS + 1)
 
     def modulation_block(self, r0, c0, nr, nc):
         """the records [nr, nc, n, 15] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, len(self.bands()[0]), MODULATION_FREQS + 1), np.float32)
-        _check(lib().PvAmdCopyModulationBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopyModulationBlock, r0, c0, nr, nc, len(self.bands()[0]), MODULATION_FREQS + 1)
 
     def modulation_at(self, pos):
         """float32 [n, 15] at an emitter position (the cell get_output reads); NaNs off the map"""
-        out = np.empty((len(self.bands()[0]), MODULATION_FREQS + 1), np.float32)
-        _check(lib().PvAmdGetModulation(self._h, *[float(v) for v in pos], _f(out)))
-        return out
+        return self._map_at(lib().PvAmdGetModulation, pos, len(self.bands()[0]), MODULATION_FREQS + 1)
 
     def set_spectrum_bins(self, hz):
         """the frequencies (Hz, at most SPECTRUM_MAX_BINS, each in [0, fs / 2]) compute_spectrum evaluates; an empty list clears
@@ -1984,28 +1942,20 @@ class Solver:
     def compute_spectrum(self):
         """transfer functions of the last completed run at the bins of set_spectrum_bins, on the device; returns the device
         time of the passes in milliseconds"""
-        ms = C.c_float(0.0)
-        _check(lib().PvAmdComputeSpectrum(self._h, C.byref(ms)))
-        return ms.value
+        return self._map_ms(lib().PvAmdComputeSpectrum)
 
     def spectrum(self):
         """float32 [gx, gy, n, 3] (re, im, level in dB; X(f) = re - i im); NaN where the cell has no onset in the run they were
         computed for"""
-        out = np.empty((self.gx, self.gy, len(self.spectrum_bins()), 3), np.float32)
-        _check(lib().PvAmdCopySpectrum(self._h, _f(out)))
-        return out
+        return self._map_all(lib().PvAmdCopySpectrum, len(self.spectrum_bins()), 3)
 
     def spectrum_block(self, r0, c0, nr, nc):
         """the records [nr, nc, n, 3] of result cells [r0, r0 + nr) x [c0, c0 + nc)"""
-        out = np.empty((nr, nc, len(self.spectrum_bins()), 3), np.float32)
-        _check(lib().PvAmdCopySpectrumBlock(self._h, int(r0), int(c0), int(nr), int(nc), _f(out)))
-        return out
+        return self._map_block(lib().PvAmdCopySpectrumBlock, r0, c0, nr, nc, len(self.spectrum_bins()), 3)
 
     def spectrum_at(self, pos):
         """float32 [n, 3] at an emitter position (the cell get_output reads); NaNs off the map"""
-        out = np.empty((len(self.spectrum_bins()), 3), np.float32)
-        _check(lib().PvAmdGetSpectrum(self._h, *[float(v) for v in pos], _f(out)))
-        return out
+        return self._map_at(lib().PvAmdGetSpectrum, pos, len(self.spectrum_bins()), 3)
 
     def pulse(self):
         """float32 [T]: the pulse table of a run (T = the run's steps; zero past the grid's own table)"""

@@ -1222,185 +1222,117 @@ int PvAmdCopyHistoryPlane(PvAmdSolver* h, int t, float* pr) try {
     return ret(h, h->g ? h->g->copyHistoryPlane(t, pr) : h->s->copyHistoryPlane(t, pr));
 } PV_API_CATCH(-1)
 
-// room metrics (pv_metrics.hip): single whole-grid solvers only -- slab groups (ensure) and slab ranks (wholeGrid) are refused
+// The nine per-cell analysis kinds (pv_solver_maps.cpp): single whole-grid solvers only -- slab groups (ensure) and slab ranks
+// (wholeGrid) are refused.  `pre` is what every refusal of a kind's calls starts with ("decay times: "; none for the room
+// metrics and the spectrum); `fn` names the call in a null-output refusal.  Settings are checked against the handle's own grid
+// before anything else happens (the rules the PvAmdHost* calls apply too).  World y is ignored, as everywhere.
+static bool analysisHandle(PvAmdSolver* h, const char* pre) {
+    if (wholeGrid(h) && ensure(h)) return true;
+    g_lastError = pre + g_lastError;
+    return false;
+}
+
+static bool analysisCall(PvAmdSolver* h, const char* pre, const char* fn, const void* out) {
+    if (!analysisHandle(h, pre)) return false;
+    if (!out) g_lastError = std::string(pre) + fn + ": null output";
+    return out != nullptr;
+}
+
+static int analysisCopy(PvAmdSolver* h, AnalysisKind k, const char* pre, const char* fn, float* out) {
+    if (!analysisCall(h, pre, fn, out)) return -1;
+    return ret(h, h->s->copyAnalysisBlock(k, 0, 0, h->s->spec().gx, h->s->spec().gy, out));
+}
+
+static int analysisCopyBlock(PvAmdSolver* h, AnalysisKind k, const char* pre, const char* fn, int r0, int c0, int nr, int nc, float* out) {
+    if (!analysisCall(h, pre, fn, out)) return -1;
+    return ret(h, h->s->copyAnalysisBlock(k, r0, c0, nr, nc, out));
+}
+
+static int analysisGet(PvAmdSolver* h, AnalysisKind k, const char* pre, const char* fn, float ex, float ez, void* out) {
+    if (!analysisCall(h, pre, fn, out)) return -1;
+    return ret(h, h->s->analysisAt(k, ex, ez, static_cast<float*>(out)));  // (*out is written only where the call succeeds)
+}
+
+static_assert(sizeof(PvAmdRoomMetrics) == kRoomMetricFloats * sizeof(float), "ten floats");
+static_assert(sizeof(PvAmdDecayTimes) == kDecayFloats * sizeof(float), "eight floats");
+static_assert(sizeof(PvAmdLateralFraction) == kLateralFloats * sizeof(float), "eleven floats");
+static_assert(sizeof(PvAmdEchoCriterion) == kEchoFloats * sizeof(float), "ten floats");
+static_assert(sizeof(PvAmdBandMetrics) == kBandFloats * sizeof(float), "twelve floats");
+static_assert(sizeof(PvAmdModulation) == kModFloats * sizeof(float), "fifteen floats");
+
+// room metrics (pv_metrics.hip)
 int PvAmdComputeRoomMetrics(PvAmdSolver* h, float* ms) try {
-    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!analysisHandle(h, "")) return -1;
     return ret(h, h->s->computeRoomMetrics(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyRoomMetrics(PvAmdSolver* h, float* out10) try {
-    if (!wholeGrid(h) || !ensure(h)) return -1;
-    if (!out10) {
-        g_lastError = "PvAmdCopyRoomMetrics: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyRoomMetricsBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out10));
+    return analysisCopy(h, kMapRoomMetrics, "", __func__, out10);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyRoomMetricsBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out10) try {
-    if (!wholeGrid(h) || !ensure(h)) return -1;
-    if (!out10) {
-        g_lastError = "PvAmdCopyRoomMetricsBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyRoomMetricsBlock(r0, c0, nr, nc, out10));
+    return analysisCopyBlock(h, kMapRoomMetrics, "", __func__, r0, c0, nr, nc, out10);
 } PV_API_CATCH(-1)
 
 int PvAmdGetRoomMetrics(PvAmdSolver* h, float ex, float ey, float ez, PvAmdRoomMetrics* out) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!wholeGrid(h) || !ensure(h)) return -1;
-    if (!out) {
-        g_lastError = "PvAmdGetRoomMetrics: null output";
-        return -1;
-    }
-    static_assert(sizeof(PvAmdRoomMetrics) == kRoomMetricFloats * sizeof(float), "ten floats");
-    float v[kRoomMetricFloats];
-    if (!h->s->roomMetricsAt(ex, ez, v)) return ret(h, false);
-    std::memcpy(out, v, sizeof(*out));
-    return 0;
+    return analysisGet(h, kMapRoomMetrics, "", __func__, ex, ez, out);
 } PV_API_CATCH(-1)
 
-// decay times (pv_decay.hip): single whole-grid solvers only, as the room metrics; every refusal says "decay times: ..."
-static bool decayHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "decay times: " + g_lastError;
-    return false;
-}
-
+// decay times (pv_decay.hip)
 int PvAmdComputeDecayTimes(PvAmdSolver* h, float* ms) try {
-    if (!decayHandle(h)) return -1;
+    if (!analysisHandle(h, "decay times: ")) return -1;
     return ret(h, h->s->computeDecayTimes(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyDecayTimes(PvAmdSolver* h, float* out8) try {
-    if (!decayHandle(h)) return -1;
-    if (!out8) {
-        g_lastError = "decay times: PvAmdCopyDecayTimes: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyDecayTimesBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out8));
+    return analysisCopy(h, kMapDecayTimes, "decay times: ", __func__, out8);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyDecayTimesBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out8) try {
-    if (!decayHandle(h)) return -1;
-    if (!out8) {
-        g_lastError = "decay times: PvAmdCopyDecayTimesBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyDecayTimesBlock(r0, c0, nr, nc, out8));
+    return analysisCopyBlock(h, kMapDecayTimes, "decay times: ", __func__, r0, c0, nr, nc, out8);
 } PV_API_CATCH(-1)
 
 int PvAmdGetDecayTimes(PvAmdSolver* h, float ex, float ey, float ez, PvAmdDecayTimes* out) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!decayHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "decay times: PvAmdGetDecayTimes: null output";
-        return -1;
-    }
-    static_assert(sizeof(PvAmdDecayTimes) == kDecayFloats * sizeof(float), "eight floats");
-    float v[kDecayFloats];
-    if (!h->s->decayTimesAt(ex, ez, v)) return ret(h, false);
-    std::memcpy(out, v, sizeof(*out));
-    return 0;
+    return analysisGet(h, kMapDecayTimes, "decay times: ", __func__, ex, ez, out);
 } PV_API_CATCH(-1)
 
-// lateral fraction (pv_lateral.hip): single whole-grid solvers only, as the room metrics; every refusal says "lateral fraction: ..."
-static bool lateralHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "lateral fraction: " + g_lastError;
-    return false;
-}
-
+// lateral fraction (pv_lateral.hip)
 int PvAmdComputeLateralFraction(PvAmdSolver* h, float* ms) try {
-    if (!lateralHandle(h)) return -1;
+    if (!analysisHandle(h, "lateral fraction: ")) return -1;
     return ret(h, h->s->computeLateralFraction(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyLateralFraction(PvAmdSolver* h, float* out11) try {
-    if (!lateralHandle(h)) return -1;
-    if (!out11) {
-        g_lastError = "lateral fraction: PvAmdCopyLateralFraction: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyLateralFractionBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out11));
+    return analysisCopy(h, kMapLateralFraction, "lateral fraction: ", __func__, out11);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyLateralFractionBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out11) try {
-    if (!lateralHandle(h)) return -1;
-    if (!out11) {
-        g_lastError = "lateral fraction: PvAmdCopyLateralFractionBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyLateralFractionBlock(r0, c0, nr, nc, out11));
+    return analysisCopyBlock(h, kMapLateralFraction, "lateral fraction: ", __func__, r0, c0, nr, nc, out11);
 } PV_API_CATCH(-1)
 
 int PvAmdGetLateralFraction(PvAmdSolver* h, float ex, float ey, float ez, PvAmdLateralFraction* out) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!lateralHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "lateral fraction: PvAmdGetLateralFraction: null output";
-        return -1;
-    }
-    static_assert(sizeof(PvAmdLateralFraction) == kLateralFloats * sizeof(float), "eleven floats");
-    float v[kLateralFloats];
-    if (!h->s->lateralFractionAt(ex, ez, v)) return ret(h, false);
-    std::memcpy(out, v, sizeof(*out));
-    return 0;
+    return analysisGet(h, kMapLateralFraction, "lateral fraction: ", __func__, ex, ez, out);
 } PV_API_CATCH(-1)
 
-// echo criterion (pv_echo.hip): single whole-grid solvers only, as the room metrics; every refusal says "echo: ..."
-static bool echoCritHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "echo: " + g_lastError;
-    return false;
-}
-
+// echo criterion (pv_echo.hip)
 int PvAmdComputeEchoCriterion(PvAmdSolver* h, float* ms) try {
-    if (!echoCritHandle(h)) return -1;
+    if (!analysisHandle(h, "echo: ")) return -1;
     return ret(h, h->s->computeEchoCriterion(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyEchoCriterion(PvAmdSolver* h, float* out10) try {
-    if (!echoCritHandle(h)) return -1;
-    if (!out10) {
-        g_lastError = "echo: PvAmdCopyEchoCriterion: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyEchoCriterionBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out10));
+    return analysisCopy(h, kMapEchoCriterion, "echo: ", __func__, out10);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyEchoCriterionBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out10) try {
-    if (!echoCritHandle(h)) return -1;
-    if (!out10) {
-        g_lastError = "echo: PvAmdCopyEchoCriterionBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyEchoCriterionBlock(r0, c0, nr, nc, out10));
+    return analysisCopyBlock(h, kMapEchoCriterion, "echo: ", __func__, r0, c0, nr, nc, out10);
 } PV_API_CATCH(-1)
 
 int PvAmdGetEchoCriterion(PvAmdSolver* h, float ex, float ey, float ez, PvAmdEchoCriterion* out) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!echoCritHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "echo: PvAmdGetEchoCriterion: null output";
-        return -1;
-    }
-    static_assert(sizeof(PvAmdEchoCriterion) == kEchoFloats * sizeof(float), "ten floats");
-    float v[kEchoFloats];
-    if (!h->s->echoCriterionAt(ex, ez, v)) return ret(h, false);
-    std::memcpy(out, v, sizeof(*out));
-    return 0;
+    return analysisGet(h, kMapEchoCriterion, "echo: ", __func__, ex, ez, out);
 } PV_API_CATCH(-1)
 
-// echogram (pv_echogram.hip): single whole-grid solvers only, as the lateral fraction; every refusal says "echogram: ...".  The
-// setting is checked against the handle's own grid before anything else happens (pv_echogram.h echogramSlotOk, the rule
-// PvAmdHostEchogram applies too)
-static bool echogramHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "echogram: " + g_lastError;
-    return false;
-}
-
+// echogram (pv_echogram.hip; the setting: pv_echogram.h echogramSlotOk)
 static const char* echogramSettingError(float slotSeconds, int nSlots, int fs) {
     if (nSlots < 0 || nSlots > kEchogramMaxSlots) return "echogram: nSlots is 0 .. PVA_ECHOGRAM_MAX_SLOTS (32)";
     if (nSlots > 0 && !echogramSlotOk(slotSeconds, fs))
@@ -1417,56 +1349,33 @@ int PvAmdSetEchogram(PvAmdSolver* h, float slotSeconds, int nSlots) try {
         g_lastError = e;
         return -1;
     }
-    if (!echogramHandle(h)) return -1;
+    if (!analysisHandle(h, "echogram: ")) return -1;
     return ret(h, h->s->setEchogram(slotSeconds, nSlots));
 } PV_API_CATCH(-1)
 
 int PvAmdGetEchogramSlots(PvAmdSolver* h, float* slotSeconds, int* slotSteps) try {
-    if (!echogramHandle(h)) return -1;
+    if (!analysisHandle(h, "echogram: ")) return -1;
     return h->s->echogramSlots(slotSeconds, slotSteps);
 } PV_API_CATCH(-1)
 
 int PvAmdComputeEchogram(PvAmdSolver* h, float* ms) try {
-    if (!echogramHandle(h)) return -1;
+    if (!analysisHandle(h, "echogram: ")) return -1;
     return ret(h, h->s->computeEchogram(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyEchogram(PvAmdSolver* h, float* out) try {
-    if (!echogramHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "echogram: PvAmdCopyEchogram: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyEchogramBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out));
+    return analysisCopy(h, kMapEchogram, "echogram: ", __func__, out);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyEchogramBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out) try {
-    if (!echogramHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "echogram: PvAmdCopyEchogramBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyEchogramBlock(r0, c0, nr, nc, out));
+    return analysisCopyBlock(h, kMapEchogram, "echogram: ", __func__, r0, c0, nr, nc, out);
 } PV_API_CATCH(-1)
 
 int PvAmdGetEchogram(PvAmdSolver* h, float ex, float ey, float ez, float* out) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!echogramHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "echogram: PvAmdGetEchogram: null output";
-        return -1;
-    }
-    return ret(h, h->s->echogramAt(ex, ez, out));
+    return analysisGet(h, kMapEchogram, "echogram: ", __func__, ex, ez, out);
 } PV_API_CATCH(-1)
 
-// lobes (pv_lobes.hip): single whole-grid solvers only, as the echogram; every refusal says "lobes: ...".  The edges are checked
-// against the handle's own grid before anything else happens (pv_lobes.h lobesEdgeSteps, the rule PvAmdHostLobes applies too)
-static bool lobesHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "lobes: " + g_lastError;
-    return false;
-}
-
+// lobes (pv_lobes.hip; the setting: pv_lobes.h lobesEdgeSteps)
 int PvAmdSetLobeWindows(PvAmdSolver* h, const float* edgesSeconds, int nEdges) try {
     if (!h) {
         g_lastError = "lobes: null solver handle";
@@ -1477,57 +1386,33 @@ int PvAmdSetLobeWindows(PvAmdSolver* h, const float* edgesSeconds, int nEdges) t
         g_lastError = kLobesEdgesError;
         return -1;
     }
-    if (!lobesHandle(h)) return -1;
+    if (!analysisHandle(h, "lobes: ")) return -1;
     return ret(h, h->s->setLobeWindows(edgesSeconds, nEdges));
 } PV_API_CATCH(-1)
 
 int PvAmdGetLobeWindows(PvAmdSolver* h, float* edgesSeconds, int* edgeSteps) try {
-    if (!lobesHandle(h)) return -1;
+    if (!analysisHandle(h, "lobes: ")) return -1;
     return h->s->lobeWindows(edgesSeconds, edgeSteps);
 } PV_API_CATCH(-1)
 
 int PvAmdComputeLobes(PvAmdSolver* h, float* ms) try {
-    if (!lobesHandle(h)) return -1;
+    if (!analysisHandle(h, "lobes: ")) return -1;
     return ret(h, h->s->computeLobes(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyLobes(PvAmdSolver* h, float* out) try {
-    if (!lobesHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "lobes: PvAmdCopyLobes: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyLobesBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out));
+    return analysisCopy(h, kMapLobes, "lobes: ", __func__, out);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyLobesBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out) try {
-    if (!lobesHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "lobes: PvAmdCopyLobesBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyLobesBlock(r0, c0, nr, nc, out));
+    return analysisCopyBlock(h, kMapLobes, "lobes: ", __func__, r0, c0, nr, nc, out);
 } PV_API_CATCH(-1)
 
 int PvAmdGetLobes(PvAmdSolver* h, float ex, float ey, float ez, float* out) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!lobesHandle(h)) return -1;
-    if (!out) {
-        g_lastError = "lobes: PvAmdGetLobes: null output";
-        return -1;
-    }
-    return ret(h, h->s->lobesAt(ex, ez, out));
+    return analysisGet(h, kMapLobes, "lobes: ", __func__, ex, ez, out);
 } PV_API_CATCH(-1)
 
-// band metrics (pv_bands.hip): single whole-grid solvers only, as the decay times; every refusal says "band metrics: ...".  The
-// bands are checked against the handle's own grid before anything else happens (pv_bands.h bandsError, the rule
-// PvAmdHostBandCoefs applies too)
-static bool bandsHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "band metrics: " + g_lastError;
-    return false;
-}
-
+// band metrics (pv_bands.hip; the setting: pv_bands.h bandsError)
 int PvAmdSetBands(PvAmdSolver* h, const float* centreHz, int n, int fraction) try {
     if (!h) {
         g_lastError = "band metrics: null solver handle";
@@ -1542,66 +1427,38 @@ int PvAmdSetBands(PvAmdSolver* h, const float* centreHz, int n, int fraction) tr
         g_lastError = "band metrics: fraction is 1 (octave) or 3 (third octave)";
         return -1;
     }
-    if (!bandsHandle(h)) return -1;
+    if (!analysisHandle(h, "band metrics: ")) return -1;
     return ret(h, h->s->setBands(centreHz, n, fraction));
 } PV_API_CATCH(-1)
 
 int PvAmdGetBands(PvAmdSolver* h, float* centreHz, int cap, int* fraction) try {
-    if (!bandsHandle(h)) return -1;
+    if (!analysisHandle(h, "band metrics: ")) return -1;
     return h->s->bands(centreHz, cap, fraction);
 } PV_API_CATCH(-1)
 
 int PvAmdGetBandCoefs(PvAmdSolver* h, float* out10n) try {
-    if (!bandsHandle(h)) return -1;
-    if (!out10n) {
-        g_lastError = "band metrics: PvAmdGetBandCoefs: null output";
-        return -1;
-    }
+    if (!analysisCall(h, "band metrics: ", __func__, out10n)) return -1;
     return ret(h, h->s->bandCoefs(out10n));
 } PV_API_CATCH(-1)
 
 int PvAmdComputeBandMetrics(PvAmdSolver* h, float* ms) try {
-    if (!bandsHandle(h)) return -1;
+    if (!analysisHandle(h, "band metrics: ")) return -1;
     return ret(h, h->s->computeBandMetrics(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyBandMetrics(PvAmdSolver* h, float* out12n) try {
-    if (!bandsHandle(h)) return -1;
-    if (!out12n) {
-        g_lastError = "band metrics: PvAmdCopyBandMetrics: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyBandMetricsBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out12n));
+    return analysisCopy(h, kMapBandMetrics, "band metrics: ", __func__, out12n);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyBandMetricsBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out12n) try {
-    if (!bandsHandle(h)) return -1;
-    if (!out12n) {
-        g_lastError = "band metrics: PvAmdCopyBandMetricsBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyBandMetricsBlock(r0, c0, nr, nc, out12n));
+    return analysisCopyBlock(h, kMapBandMetrics, "band metrics: ", __func__, r0, c0, nr, nc, out12n);
 } PV_API_CATCH(-1)
 
 int PvAmdGetBandMetrics(PvAmdSolver* h, float ex, float ey, float ez, PvAmdBandMetrics* out12n) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!bandsHandle(h)) return -1;
-    if (!out12n) {
-        g_lastError = "band metrics: PvAmdGetBandMetrics: null output";
-        return -1;
-    }
-    static_assert(sizeof(PvAmdBandMetrics) == kBandFloats * sizeof(float), "twelve floats");
-    return ret(h, h->s->bandMetricsAt(ex, ez, reinterpret_cast<float*>(out12n)));
+    return analysisGet(h, kMapBandMetrics, "band metrics: ", __func__, ex, ez, out12n);
 } PV_API_CATCH(-1)
 
-// modulation (pv_modulation.hip): single whole-grid solvers only, as the band metrics; every refusal says "modulation: ...".  The
-// frequencies are checked against the handle's own grid before anything else happens (pv_modulation.h modulationFreqsError)
-static bool modulationHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "modulation: " + g_lastError;
-    return false;
-}
-
+// modulation (pv_modulation.hip; the setting: pv_modulation.h modulationFreqsError)
 int PvAmdSetModulationFrequencies(PvAmdSolver* h, const float* hz14) try {
     if (!h) {
         g_lastError = "modulation: null solver handle";
@@ -1613,56 +1470,34 @@ int PvAmdSetModulationFrequencies(PvAmdSolver* h, const float* hz14) try {
             return -1;
         }
     }
-    if (!modulationHandle(h)) return -1;
+    if (!analysisHandle(h, "modulation: ")) return -1;
     return ret(h, h->s->setModulationFrequencies(hz14));
 } PV_API_CATCH(-1)
 
 int PvAmdGetModulationFrequencies(PvAmdSolver* h, float* hz14) try {
-    if (!modulationHandle(h)) return -1;
-    if (!hz14) {
-        g_lastError = "modulation: PvAmdGetModulationFrequencies: null output";
-        return -1;
-    }
+    if (!analysisCall(h, "modulation: ", __func__, hz14)) return -1;
     h->s->modulationFrequencies(hz14);
     return 0;
 } PV_API_CATCH(-1)
 
 int PvAmdComputeModulation(PvAmdSolver* h, float* ms) try {
-    if (!modulationHandle(h)) return -1;
+    if (!analysisHandle(h, "modulation: ")) return -1;
     return ret(h, h->s->computeModulation(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyModulation(PvAmdSolver* h, float* out15n) try {
-    if (!modulationHandle(h)) return -1;
-    if (!out15n) {
-        g_lastError = "modulation: PvAmdCopyModulation: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyModulationBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out15n));
+    return analysisCopy(h, kMapModulation, "modulation: ", __func__, out15n);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyModulationBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out15n) try {
-    if (!modulationHandle(h)) return -1;
-    if (!out15n) {
-        g_lastError = "modulation: PvAmdCopyModulationBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copyModulationBlock(r0, c0, nr, nc, out15n));
+    return analysisCopyBlock(h, kMapModulation, "modulation: ", __func__, r0, c0, nr, nc, out15n);
 } PV_API_CATCH(-1)
 
 int PvAmdGetModulation(PvAmdSolver* h, float ex, float ey, float ez, PvAmdModulation* out15n) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!modulationHandle(h)) return -1;
-    if (!out15n) {
-        g_lastError = "modulation: PvAmdGetModulation: null output";
-        return -1;
-    }
-    static_assert(sizeof(PvAmdModulation) == kModFloats * sizeof(float), "fifteen floats");
-    return ret(h, h->s->modulationAt(ex, ez, reinterpret_cast<float*>(out15n)));
+    return analysisGet(h, kMapModulation, "modulation: ", __func__, ex, ez, out15n);
 } PV_API_CATCH(-1)
 
-// spectrum (pv_spectrum.hip): single whole-grid solvers only, as the room metrics.  The bins are checked against the handle's
-// own grid before anything else happens (pv_spectrum.h spectrumBinsError, the rule the host calls apply too)
+// spectrum (pv_spectrum.hip; the setting: pv_spectrum.h spectrumBinsError)
 int PvAmdSetSpectrumBins(PvAmdSolver* h, const float* hz, int n) try {
     if (!h) {
         g_lastError = "null solver handle";
@@ -1674,55 +1509,35 @@ int PvAmdSetSpectrumBins(PvAmdSolver* h, const float* hz, int n) try {
             return -1;
         }
     }
-    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!analysisHandle(h, "")) return -1;
     return ret(h, h->s->setSpectrumBins(hz, n));
 } PV_API_CATCH(-1)
 
 int PvAmdGetSpectrumBins(PvAmdSolver* h, float* hz, int cap) try {
-    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!analysisHandle(h, "")) return -1;
     return h->s->spectrumBins(hz, cap);
 } PV_API_CATCH(-1)
 
 int PvAmdGetSpectrumSource(PvAmdSolver* h, float* out3n) try {
-    if (!wholeGrid(h) || !ensure(h)) return -1;
-    if (!out3n) {
-        g_lastError = "PvAmdGetSpectrumSource: null output";
-        return -1;
-    }
+    if (!analysisCall(h, "", __func__, out3n)) return -1;
     return ret(h, h->s->spectrumSource(out3n));
 } PV_API_CATCH(-1)
 
 int PvAmdComputeSpectrum(PvAmdSolver* h, float* ms) try {
-    if (!wholeGrid(h) || !ensure(h)) return -1;
+    if (!analysisHandle(h, "")) return -1;
     return ret(h, h->s->computeSpectrum(ms));
 } PV_API_CATCH(-1)
 
 int PvAmdCopySpectrum(PvAmdSolver* h, float* out) try {
-    if (!wholeGrid(h) || !ensure(h)) return -1;
-    if (!out) {
-        g_lastError = "PvAmdCopySpectrum: null output";
-        return -1;
-    }
-    return ret(h, h->s->copySpectrumBlock(0, 0, h->s->spec().gx, h->s->spec().gy, out));
+    return analysisCopy(h, kMapSpectrum, "", __func__, out);
 } PV_API_CATCH(-1)
 
 int PvAmdCopySpectrumBlock(PvAmdSolver* h, int r0, int c0, int nr, int nc, float* out) try {
-    if (!wholeGrid(h) || !ensure(h)) return -1;
-    if (!out) {
-        g_lastError = "PvAmdCopySpectrumBlock: null output";
-        return -1;
-    }
-    return ret(h, h->s->copySpectrumBlock(r0, c0, nr, nc, out));
+    return analysisCopyBlock(h, kMapSpectrum, "", __func__, r0, c0, nr, nc, out);
 } PV_API_CATCH(-1)
 
 int PvAmdGetSpectrum(PvAmdSolver* h, float ex, float ey, float ez, float* out3n) try {
-    (void)ey;  // world y is ignored, as everywhere
-    if (!wholeGrid(h) || !ensure(h)) return -1;
-    if (!out3n) {
-        g_lastError = "PvAmdGetSpectrum: null output";
-        return -1;
-    }
-    return ret(h, h->s->spectrumAt(ex, ez, out3n));
+    return analysisGet(h, kMapSpectrum, "", __func__, ex, ez, out3n);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyPulse(PvAmdSolver* h, float* out) try {

@@ -14,6 +14,7 @@ namespace pva {
 constexpr int kQspecBandMetrics = 0, kQspecModulation = 1, kQspecSpectrum = 2;
 constexpr int kQuerySpectralKinds = 3;
 constexpr unsigned kQuerySpectralMask = (1u << kQuerySpectralKinds) - 1u;
+constexpr unsigned kQspecBandKinds = (1u << kQspecBandMetrics) | (1u << kQspecModulation);  // the kinds that follow setBands
 // coefficient sets that travel with a launch: kBandsMax, and room for the zero sets that pad the last block of the band metrics
 // (any register block up to 8 bands)
 constexpr int kQspecCoefSets = 2 * kBandsMax;

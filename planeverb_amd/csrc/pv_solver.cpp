@@ -81,15 +81,6 @@ bool Solver::hipOk(hipError_t e, const char* what) {
     return false;
 }
 
-template <typename Tp>
-bool Solver::dalloc(Tp** p, size_t count, bool zero) {
-    const size_t bytes = count * sizeof(Tp);
-    if (!hipOk(hipMalloc((void**)p, bytes), "hipMalloc")) return false;
-    deviceBytes_ += (long long)bytes;
-    if (zero && !hipOk(hipMemsetAsync(*p, 0, bytes, stream_), "hipMemsetAsync")) return false;
-    return true;
-}
-
 // claimed streams (the live solvers' main streams, slab groups' root streams), per device (QueueClaim)
 namespace {
 struct ClaimedStream {
@@ -700,38 +691,15 @@ Solver::~Solver() {
     if (caps_.useResident) residentDumpTrace();
 #endif
     if (resFlags_) hipFree(resFlags_);
-    if (metrics_) hipFree(metrics_);
-    for (auto& e : metricsEv_)
+    for (AnalysisMap& m : maps_)
+        if (m.dev) hipFree(m.dev);
+    for (auto& e : mapEv_)
         if (e) hipEventDestroy(e);
-    if (decay_) hipFree(decay_);
-    for (auto& e : decayEv_)
-        if (e) hipEventDestroy(e);
-    if (bands_) hipFree(bands_);
-    for (auto& e : bandsEv_)
-        if (e) hipEventDestroy(e);
-    for (float* p : {modTab_, modulation_})
+    for (float* p : {modTab_, specTab_, specPow_})
         if (p) hipFree(p);
-    for (auto& e : modulationEv_)
-        if (e) hipEventDestroy(e);
-    if (lateral_) hipFree(lateral_);
-    for (auto& e : lateralEv_)
-        if (e) hipEventDestroy(e);
-    if (echo_) hipFree(echo_);
-    for (auto& e : echoEv_)
-        if (e) hipEventDestroy(e);
-    if (lobes_) hipFree(lobes_);
     if (qrecHost_) hipHostFree(qrecHost_);
     if (qspecHost_) hipHostFree(qspecHost_);
     if (rqCellsHost_) hipHostFree(rqCellsHost_);
-    for (auto& e : lobesEv_)
-        if (e) hipEventDestroy(e);
-    if (echoCrit_) hipFree(echoCrit_);
-    for (auto& e : echoCritEv_)
-        if (e) hipEventDestroy(e);
-    for (float* p : {specTab_, specPow_, spectrum_})
-        if (p) hipFree(p);
-    for (auto& e : spectrumEv_)
-        if (e) hipEventDestroy(e);
     if (layerList_) hipFree(layerList_);
     if (layerTab_) hipFree(layerTab_);
     if (px_[0]) hipFree(px_[0]);  // (px_[1] lives in the same allocation)
@@ -809,7 +777,7 @@ int Solver::addBox(const Box& b) {
     }
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+    invalidateAnalysisMaps();
     return id;
 }
 
@@ -820,7 +788,7 @@ bool Solver::updateBox(int id, const Box& b) {
     boxTable_[(size_t)id] = b;
     mat_.add(b);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+    invalidateAnalysisMaps();
     return true;
 }
 
@@ -831,7 +799,7 @@ bool Solver::removeBox(int id) {
     boxUsed_[(size_t)id] = 0;
     boxFree_.push_back(id);
     geometryDirty_ = true;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+    invalidateAnalysisMaps();
     return true;
 }
 
@@ -903,14 +871,14 @@ bool Solver::shapeSet(int id, const Shape& sh) {
     shapeTable_[(size_t)id] = sh;
     shapeSeq_[(size_t)id] = shapeSeqNext_++;
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+    invalidateAnalysisMaps();
     return true;
 }
 
 bool Solver::shapeClear(int id) {
     if (id < 0 || id >= (int)shapeTable_.size() || shapeSeq_[(size_t)id] < 0) return fail("invalid shape id");
     markShapeDirty(id);
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+    invalidateAnalysisMaps();
     shapeSeq_[(size_t)id] = -1;
     shapeTable_[(size_t)id] = Shape{};
     return true;
@@ -1057,7 +1025,7 @@ bool Solver::setGridBoundary(const float R4[4]) {
         if (edgeR_[k] != R4[k] || std::signbit(edgeR_[k]) != std::signbit(R4[k])) boundaryDirty_ = true;
         edgeR_[k] = R4[k];
     }
-    if (boundaryDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+    if (boundaryDirty_) invalidateAnalysisMaps();
     return true;
 }
 
@@ -1097,7 +1065,7 @@ bool Solver::setEdgeLayer(const int w4[4], bool split, double r0) {
     if (layerSplit_ != split || layerR0_ != r0) layerDirty_ = true;
     layerSplit_ = split;
     layerR0_ = r0;
-    if (layerDirty_) metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+    if (layerDirty_) invalidateAnalysisMaps();
     return true;
 }
 
@@ -2161,7 +2129,7 @@ void Solver::enqueueAnalysis(float lx, float lz) {
 bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, float lx, float lz) {
     // one run in flight at a time: the pinned staging of the per-run parameters is reused
     if (pendingTimings_ && !sync()) return false;
-    metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;       // (the history the records were made from is about to be overwritten)
+    invalidateAnalysisMaps();  // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
     qrecRun_ = QrecRun::None;    // (the pinned block is about to be overwritten, or this run leaves no records)
     qspecRun_ = QrecRun::None;
@@ -2943,7 +2911,6 @@ int qspecBit(unsigned kind) {  // the bit of a mask that names ONE kind, or -1
         if (kind == (1u << k)) return k;
     return -1;
 }
-constexpr unsigned kQspecBandKinds = (1u << kQspecBandMetrics) | (1u << kQspecModulation);
 }  // namespace
 
 int Solver::qspecFloatsOf(int k) const {
@@ -3272,957 +3239,6 @@ bool Solver::copyHistoryPlane(int t, float* pr) {
     if (!hipOk(hipMemcpyAsync(pr, scratch_, (size_t)lNX_ * g_.NY * 4, hipMemcpyDeviceToHost, stream_), "plane copy"))
         return false;
     return hipOk(hipStreamSynchronize(stream_), "plane sync");
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// room metrics (pv_metrics.hip)
-// ----------------------------------------------------------------------------------------------------------------
-
-bool Solver::computeRoomMetrics(float* ms) {
-    if (isSlab()) return fail("room metrics: not available on a slab");
-    if (opt_.streaming) return fail("room metrics: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("room metrics: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("room metrics: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("room metrics: the last run ended in error");
-    if (!metrics_ && !dalloc(&metrics_, (size_t)kRoomMetricFloats * (size_t)histPlane_, false)) return false;
-    for (auto& e : metricsEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    metricsValid_ = false;
-    metricsHostValid_ = false;
-    hipEventRecord(metricsEv_[0], stream_);
-    launchRoomMetrics(analyzeArgs(lastLx_, lastLz_), metrics_, stream_);
-    hipEventRecord(metricsEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "room metrics launch") || !hipOk(hipStreamSynchronize(stream_), "room metrics sync")) return false;
-    if (ms) hipEventElapsedTime(ms, metricsEv_[0], metricsEv_[1]);
-    metricsDyn_ = dynCur_;
-    metricsValid_ = true;
-    return true;
-}
-
-bool Solver::fetchRoomMetrics() {
-    if (!metricsValid_) return fail("room metrics: not computed for the last run and the current geometry (PvAmdComputeRoomMetrics)");
-    if (metricsHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    metricsHost_.resize((size_t)kRoomMetricFloats * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(metricsHost_.data(), metrics_, metricsHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "room metrics copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "room metrics sync"))
-        return false;
-    metricsHostValid_ = true;
-    return true;
-}
-
-bool Solver::copyRoomMetricsBlock(int r0, int c0, int nr, int nc, float* out10) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("room metrics: block outside the map");
-    if (!fetchRoomMetrics()) return false;
-    // a cell outside the run's history window is unreached by construction; inside, its record sits at its offset in a history
-    // plane (tile-major: pv_prims.h histOffset)
-    const int wr0 = metricsDyn_.histRow0 - geo_.G, wc0 = metricsDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out10 + ((size_t)r * nc + c) * kRoomMetricFloats;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < kRoomMetricFloats; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * metricsDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < kRoomMetricFloats; ++k) o[k] = metricsHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::roomMetricsAt(float ex, float ez, float out10[10]) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!metricsValid_) return fetchRoomMetrics();
-        for (int k = 0; k < kRoomMetricFloats; ++k) out10[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copyRoomMetricsBlock(cx, cy, 1, 1, out10);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// decay times (pv_decay.hip): everything as the room metrics above, with eight planes
-// ----------------------------------------------------------------------------------------------------------------
-
-// PLANEVERB_AMD_DECAY_LAUNCHES = 2: the two walks of the curve as a launch each (measurement: profiles/decay_times.txt)
-static bool decayTwoLaunches() {
-    static const bool two = [] {
-        const char* e = std::getenv("PLANEVERB_AMD_DECAY_LAUNCHES");
-        return e && std::atoi(e) == 2;
-    }();
-    return two;
-}
-
-bool Solver::computeDecayTimes(float* ms) {
-    if (isSlab()) return fail("decay times: not available on a slab");
-    if (opt_.streaming) return fail("decay times: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("decay times: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("decay times: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("decay times: the last run ended in error");
-    if (!decay_ && !dalloc(&decay_, (size_t)kDecayFloats * (size_t)histPlane_, false)) return false;
-    for (auto& e : decayEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    decayValid_ = false;
-    decayHostValid_ = false;
-    hipEventRecord(decayEv_[0], stream_);
-    launchDecayTimes(analyzeArgs(lastLx_, lastLz_), decay_, decayTwoLaunches(), stream_);
-    hipEventRecord(decayEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "decay times launch") || !hipOk(hipStreamSynchronize(stream_), "decay times sync")) return false;
-    if (ms) hipEventElapsedTime(ms, decayEv_[0], decayEv_[1]);
-    decayDyn_ = dynCur_;
-    decayValid_ = true;
-    return true;
-}
-
-bool Solver::fetchDecayTimes() {
-    if (!decayValid_) return fail("decay times: not computed for the last run and the current geometry (PvAmdComputeDecayTimes)");
-    if (decayHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    decayHost_.resize((size_t)kDecayFloats * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(decayHost_.data(), decay_, decayHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "decay times copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "decay times sync"))
-        return false;
-    decayHostValid_ = true;
-    return true;
-}
-
-bool Solver::copyDecayTimesBlock(int r0, int c0, int nr, int nc, float* out8) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("decay times: block outside the map");
-    if (!fetchDecayTimes()) return false;
-    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
-    const int wr0 = decayDyn_.histRow0 - geo_.G, wc0 = decayDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out8 + ((size_t)r * nc + c) * kDecayFloats;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < kDecayFloats; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * decayDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < kDecayFloats; ++k) o[k] = decayHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::decayTimesAt(float ex, float ez, float out8[8]) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!decayValid_) return fetchDecayTimes();
-        for (int k = 0; k < kDecayFloats; ++k) out8[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copyDecayTimesBlock(cx, cy, 1, 1, out8);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// echo criterion (pv_echo.hip): everything as the decay times above, with ten planes; refused where the speech lag is below a step
-// ----------------------------------------------------------------------------------------------------------------
-
-bool Solver::computeEchoCriterion(float* ms) {
-    if (isSlab()) return fail("echo: not available on a slab");
-    if (opt_.streaming) return fail("echo: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("echo: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    if (!echoFsOk((int)g_.fs)) return fail("echo: the sampling rate gives a speech lag below one step ((int)(0.009f * (float)fs) < 1)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("echo: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("echo: the last run ended in error");
-    if (!echoCrit_ && !dalloc(&echoCrit_, (size_t)kEchoFloats * (size_t)histPlane_, false)) return false;
-    for (auto& e : echoCritEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    echoCritValid_ = false;
-    echoCritHostValid_ = false;
-    hipEventRecord(echoCritEv_[0], stream_);
-    launchEchoCriterion(analyzeArgs(lastLx_, lastLz_), echoCrit_, stream_);
-    hipEventRecord(echoCritEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "echo criterion launch") || !hipOk(hipStreamSynchronize(stream_), "echo criterion sync")) return false;
-    if (ms) hipEventElapsedTime(ms, echoCritEv_[0], echoCritEv_[1]);
-    echoCritDyn_ = dynCur_;
-    echoCritValid_ = true;
-    return true;
-}
-
-bool Solver::fetchEchoCriterion() {
-    if (!echoCritValid_) return fail("echo: not computed for the last run and the current geometry (PvAmdComputeEchoCriterion)");
-    if (echoCritHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    echoCritHost_.resize((size_t)kEchoFloats * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(echoCritHost_.data(), echoCrit_, echoCritHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "echo criterion copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "echo criterion sync"))
-        return false;
-    echoCritHostValid_ = true;
-    return true;
-}
-
-bool Solver::copyEchoCriterionBlock(int r0, int c0, int nr, int nc, float* out10) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("echo: block outside the map");
-    if (!fetchEchoCriterion()) return false;
-    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
-    const int wr0 = echoCritDyn_.histRow0 - geo_.G, wc0 = echoCritDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out10 + ((size_t)r * nc + c) * kEchoFloats;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < kEchoFloats; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * echoCritDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < kEchoFloats; ++k) o[k] = echoCritHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::echoCriterionAt(float ex, float ez, float out10[10]) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!echoCritValid_) return fetchEchoCriterion();
-        for (int k = 0; k < kEchoFloats; ++k) out10[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copyEchoCriterionBlock(cx, cy, 1, 1, out10);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// lateral energy fraction and early-sound direction (pv_lateral.hip): everything as the decay times above, with eleven planes
-// ----------------------------------------------------------------------------------------------------------------
-
-bool Solver::computeLateralFraction(float* ms) {
-    if (isSlab()) return fail("lateral fraction: not available on a slab");
-    if (opt_.streaming) return fail("lateral fraction: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("lateral fraction: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("lateral fraction: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("lateral fraction: the last run ended in error");
-    if (!lateral_ && !dalloc(&lateral_, (size_t)kLateralFloats * (size_t)histPlane_, false)) return false;
-    for (auto& e : lateralEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    lateralValid_ = false;
-    lateralHostValid_ = false;
-    hipEventRecord(lateralEv_[0], stream_);
-    launchLateralFraction(analyzeArgs(lastLx_, lastLz_), lateral_, stream_);
-    hipEventRecord(lateralEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "lateral fraction launch") || !hipOk(hipStreamSynchronize(stream_), "lateral fraction sync")) return false;
-    if (ms) hipEventElapsedTime(ms, lateralEv_[0], lateralEv_[1]);
-    lateralDyn_ = dynCur_;
-    lateralValid_ = true;
-    return true;
-}
-
-bool Solver::fetchLateralFraction() {
-    if (!lateralValid_) return fail("lateral fraction: not computed for the last run and the current geometry (PvAmdComputeLateralFraction)");
-    if (lateralHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    lateralHost_.resize((size_t)kLateralFloats * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(lateralHost_.data(), lateral_, lateralHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "lateral fraction copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "lateral fraction sync"))
-        return false;
-    lateralHostValid_ = true;
-    return true;
-}
-
-bool Solver::copyLateralFractionBlock(int r0, int c0, int nr, int nc, float* out11) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("lateral fraction: block outside the map");
-    if (!fetchLateralFraction()) return false;
-    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
-    const int wr0 = lateralDyn_.histRow0 - geo_.G, wc0 = lateralDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out11 + ((size_t)r * nc + c) * kLateralFloats;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < kLateralFloats; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * lateralDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < kLateralFloats; ++k) o[k] = lateralHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::lateralFractionAt(float ex, float ez, float out11[11]) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!lateralValid_) return fetchLateralFraction();
-        for (int k = 0; k < kLateralFloats; ++k) out11[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copyLateralFractionBlock(cx, cy, 1, 1, out11);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// directional echogram (pv_echogram.hip): everything as the lateral fraction above, with 1 + 3 nSlots planes and the slots as the
-// band metrics' bands
-// ----------------------------------------------------------------------------------------------------------------
-
-bool Solver::setEchogram(float slotSeconds, int nSlots) {
-    if (isSlab()) return fail("echogram: not available on a slab");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
-    if (nSlots == 0 && (qrecKinds_ & (1u << kQrecEchogram)))
-        return fail("query records: echogram: the slots cannot be cleared while PVA_QREC_ECHOGRAM is selected (PvAmdSetQueryRecords)");
-    if (qrecKinds_ & (1u << kQrecEchogram)) qrecRun_ = QrecRun::None;  // (the records in the pinned block are the old slots')
-    echoValid_ = false;
-    echoHostValid_ = false;
-    if (nSlots == 0) {
-        if (echo_) hipFree(echo_);
-        echo_ = nullptr;
-        echoPlanes_ = 0;
-        echoSeconds_ = 0.f;
-        echoSteps_ = echoSlots_ = 0;
-        return true;
-    }
-    echoSeconds_ = slotSeconds;
-    echoSteps_ = echogramSlotSteps(slotSeconds, (int)g_.fs);
-    echoSlots_ = nSlots;
-    return true;
-}
-
-int Solver::echogramSlots(float* slotSeconds, int* slotSteps) const {
-    if (slotSeconds && echoSlots_) *slotSeconds = echoSeconds_;
-    if (slotSteps && echoSlots_) *slotSteps = echoSteps_;
-    return echoSlots_;
-}
-
-bool Solver::computeEchogram(float* ms) {
-    if (isSlab()) return fail("echogram: not available on a slab");
-    if (opt_.streaming) return fail("echogram: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("echogram: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    if (!echoSlots_) return fail("echogram: no slots set (PvAmdSetEchogram)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("echogram: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("echogram: the last run ended in error");
-    const int nf = echogramFloats(echoSlots_);
-    if (echo_ && echoPlanes_ != nf) {
-        hipFree(echo_);
-        echo_ = nullptr;
-    }
-    if (!echo_) {
-        if (!dalloc(&echo_, (size_t)nf * (size_t)histPlane_, false)) return false;
-        echoPlanes_ = nf;
-    }
-    for (auto& e : echoEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    echoValid_ = false;
-    echoHostValid_ = false;
-    hipEventRecord(echoEv_[0], stream_);
-    launchEchogram(analyzeArgs(lastLx_, lastLz_), echo_, echoSteps_, echoSlots_, stream_);
-    hipEventRecord(echoEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "echogram launch") || !hipOk(hipStreamSynchronize(stream_), "echogram sync")) return false;
-    if (ms) hipEventElapsedTime(ms, echoEv_[0], echoEv_[1]);
-    echoDyn_ = dynCur_;
-    echoValid_ = true;
-    return true;
-}
-
-bool Solver::fetchEchogram() {
-    if (!echoSlots_) return fail("echogram: no slots set (PvAmdSetEchogram)");
-    if (!echoValid_)
-        return fail("echogram: not computed for the last run, the current geometry and the current slots (PvAmdComputeEchogram)");
-    if (echoHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    echoHost_.resize((size_t)echoPlanes_ * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(echoHost_.data(), echo_, echoHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "echogram copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "echogram sync"))
-        return false;
-    echoHostValid_ = true;
-    return true;
-}
-
-bool Solver::copyEchogramBlock(int r0, int c0, int nr, int nc, float* out) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("echogram: block outside the map");
-    if (!fetchEchogram()) return false;
-    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
-    const int wr0 = echoDyn_.histRow0 - geo_.G, wc0 = echoDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const int nf = echoPlanes_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < nf; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * echoDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < nf; ++k) o[k] = echoHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::echogramAt(float ex, float ez, float* out) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!fetchEchogram()) return false;
-        for (int k = 0; k < echoPlanes_; ++k) out[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copyEchogramBlock(cx, cy, 1, 1, out);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// directional energy lobes (pv_lobes.hip): everything as the echogram above, with 1 + 5 nW planes; the windows are never unset,
-// a solver that was given none uses the default edges
-// ----------------------------------------------------------------------------------------------------------------
-
-bool Solver::setLobeWindows(const float* edgesSeconds, int nEdges) {
-    if (isSlab()) return fail("lobes: not available on a slab");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
-    if (qrecKinds_ & (1u << kQrecLobes)) qrecRun_ = QrecRun::None;  // (the records in the pinned block are the old windows')
-    lobesValid_ = false;
-    lobesHostValid_ = false;
-    if (nEdges == 0) {
-        edgesSeconds = kLobesDefaultEdges;
-        nEdges = 2;
-    }
-    for (int i = 0; i < kLobesMaxEdges; ++i) lobeEdges_[i] = i < nEdges ? edgesSeconds[i] : 0.f;
-    lobeEdgeCount_ = nEdges;
-    return true;
-}
-
-int Solver::lobeWindows(float* edgesSeconds, int* edgeSteps) const {
-    LobeEdges ed;
-    const bool ok = lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, (int)g_.fs, &ed);  // (false: the default at an fs below 100)
-    for (int i = 0; i < lobeEdgeCount_; ++i) {
-        if (edgesSeconds) edgesSeconds[i] = lobeEdges_[i];
-        if (edgeSteps) edgeSteps[i] = ok ? ed.n[i] : 0;
-    }
-    return lobeEdgeCount_;
-}
-
-bool Solver::computeLobes(float* ms) {
-    if (isSlab()) return fail("lobes: not available on a slab");
-    if (opt_.streaming) return fail("lobes: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("lobes: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    LobeEdges ed;
-    if (!lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, (int)g_.fs, &ed))
-        return fail("lobes: the default windows (10 ms, 80 ms) need a sampling rate of 100 Hz or more (PvAmdSetLobeWindows)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("lobes: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("lobes: the last run ended in error");
-    const int nW = lobeEdgeCount_ + 1, nf = lobesFloats(nW);
-    if (lobes_ && lobesPlanes_ != nf) {
-        hipFree(lobes_);
-        lobes_ = nullptr;
-    }
-    if (!lobes_) {
-        if (!dalloc(&lobes_, (size_t)nf * (size_t)histPlane_, false)) return false;
-        lobesPlanes_ = nf;
-    }
-    for (auto& e : lobesEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    lobesValid_ = false;
-    lobesHostValid_ = false;
-    hipEventRecord(lobesEv_[0], stream_);
-    launchLobes(analyzeArgs(lastLx_, lastLz_), lobes_, ed, nW, stream_);
-    hipEventRecord(lobesEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "lobes launch") || !hipOk(hipStreamSynchronize(stream_), "lobes sync")) return false;
-    if (ms) hipEventElapsedTime(ms, lobesEv_[0], lobesEv_[1]);
-    lobesDyn_ = dynCur_;
-    lobesValid_ = true;
-    return true;
-}
-
-bool Solver::fetchLobes() {
-    if (!lobesValid_)
-        return fail("lobes: not computed for the last run, the current geometry and the current windows (PvAmdComputeLobes)");
-    if (lobesHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    lobesHost_.resize((size_t)lobesPlanes_ * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(lobesHost_.data(), lobes_, lobesHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "lobes copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "lobes sync"))
-        return false;
-    lobesHostValid_ = true;
-    return true;
-}
-
-bool Solver::copyLobesBlock(int r0, int c0, int nr, int nc, float* out) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("lobes: block outside the map");
-    if (!fetchLobes()) return false;
-    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
-    const int wr0 = lobesDyn_.histRow0 - geo_.G, wc0 = lobesDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const int nf = lobesPlanes_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < nf; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * lobesDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < nf; ++k) o[k] = lobesHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::lobesAt(float ex, float ez, float* out) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!fetchLobes()) return false;
-        for (int k = 0; k < lobesPlanes_; ++k) out[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copyLobesBlock(cx, cy, 1, 1, out);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// band metrics (pv_bands.hip): everything as the decay times above, with 12 planes per band and the bands as the spectrum's bins
-// ----------------------------------------------------------------------------------------------------------------
-
-bool Solver::setBands(const float* centreHz, int n, int fraction) {
-    if (isSlab()) return fail("band metrics: not available on a slab");
-    if (n == 0 && (qspecKinds_ & kQspecBandKinds))
-        return fail("spectral records: the bands cannot be cleared while a band kind is selected (PvAmdSetQuerySpectralRecords)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
-    bandsValid_ = false;
-    bandsHostValid_ = false;
-    modulationValid_ = false;  // (the modulation records are per band)
-    modulationHostValid_ = false;
-    if (qspecKinds_ & kQspecBandKinds) qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old bands')
-    bandHz_.clear();
-    bandCoefs_.clear();
-    if (n == 0) {
-        if (bands_) hipFree(bands_);
-        bands_ = nullptr;
-        bandsPlanes_ = 0;
-        if (modulation_) hipFree(modulation_);
-        modulation_ = nullptr;
-        modulationPlanes_ = 0;
-        return true;
-    }
-    bandHz_.assign(centreHz, centreHz + n);
-    bandFraction_ = fraction;
-    bandCoefs_.resize((size_t)kBandCoefs * n);
-    pva::bandCoefs((int)g_.fs, centreHz, n, fraction, bandCoefs_.data());
-    return true;
-}
-
-int Solver::bands(float* centreHz, int cap, int* fraction) const {
-    const int n = (int)bandHz_.size();
-    for (int j = 0; j < n && j < cap && centreHz; ++j) centreHz[j] = bandHz_[(size_t)j];
-    if (fraction && n) *fraction = bandFraction_;
-    return n;
-}
-
-bool Solver::bandCoefs(float* out10n) {
-    if (bandHz_.empty()) return fail("band metrics: no bands set (PvAmdSetBands)");
-    std::memcpy(out10n, bandCoefs_.data(), bandCoefs_.size() * 4);
-    return true;
-}
-
-bool Solver::computeBandMetrics(float* ms) {
-    if (isSlab()) return fail("band metrics: not available on a slab");
-    if (opt_.streaming) return fail("band metrics: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("band metrics: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    if (bandHz_.empty()) return fail("band metrics: no bands set (PvAmdSetBands)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("band metrics: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("band metrics: the last run ended in error");
-    const int n = (int)bandHz_.size();
-    if (bands_ && bandsPlanes_ != kBandFloats * n) {
-        hipFree(bands_);
-        bands_ = nullptr;
-    }
-    if (!bands_) {
-        if (!dalloc(&bands_, (size_t)kBandFloats * n * (size_t)histPlane_, false)) return false;
-        bandsPlanes_ = kBandFloats * n;
-    }
-    for (auto& e : bandsEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    bandsValid_ = false;
-    bandsHostValid_ = false;
-    hipEventRecord(bandsEv_[0], stream_);
-    launchBandMetrics(analyzeArgs(lastLx_, lastLz_), bandCoefs_.data(), n, bands_, stream_);
-    hipEventRecord(bandsEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "band metrics launch") || !hipOk(hipStreamSynchronize(stream_), "band metrics sync")) return false;
-    if (ms) hipEventElapsedTime(ms, bandsEv_[0], bandsEv_[1]);
-    bandsDyn_ = dynCur_;
-    bandsValid_ = true;
-    return true;
-}
-
-bool Solver::fetchBandMetrics() {
-    if (bandHz_.empty()) return fail("band metrics: no bands set (PvAmdSetBands)");
-    if (!bandsValid_)
-        return fail("band metrics: not computed for the last run, the current geometry and the current bands (PvAmdComputeBandMetrics)");
-    if (bandsHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    bandsHost_.resize((size_t)bandsPlanes_ * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(bandsHost_.data(), bands_, bandsHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "band metrics copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "band metrics sync"))
-        return false;
-    bandsHostValid_ = true;
-    return true;
-}
-
-bool Solver::copyBandMetricsBlock(int r0, int c0, int nr, int nc, float* out) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("band metrics: block outside the map");
-    if (!fetchBandMetrics()) return false;
-    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
-    const int wr0 = bandsDyn_.histRow0 - geo_.G, wc0 = bandsDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const int nf = bandsPlanes_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < nf; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * bandsDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < nf; ++k) o[k] = bandsHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::bandMetricsAt(float ex, float ez, float* out12n) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!fetchBandMetrics()) return false;
-        for (int k = 0; k < bandsPlanes_; ++k) out12n[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copyBandMetricsBlock(cx, cy, 1, 1, out12n);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// modulation (pv_modulation.hip): everything as the band metrics above, with 15 planes per band; the modulation frequencies are
-// never unset, a solver that was given none uses the default series
-// ----------------------------------------------------------------------------------------------------------------
-
-bool Solver::setModulationFrequencies(const float* hz14) {
-    if (isSlab()) return fail("modulation: not available on a slab");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
-    modulationValid_ = false;
-    modulationHostValid_ = false;
-    modTabValid_ = false;
-    for (int i = 0; i < kModFreqs; ++i) modHz_[i] = hz14 ? hz14[i] : kModDefaultHz[i];
-    if (qspecKinds_ & (1u << kQspecModulation)) {
-        qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old frequencies')
-        return ensureModTable();    // (the next run's launch reads the table: never uploaded from the enqueue path)
-    }
-    return true;
-}
-
-// the twiddle table of the current modulation frequencies on the device (no run in flight: the upload waits for the stream)
-bool Solver::ensureModTable() {
-    const int T = T_;  // the run's steps (PVA_OPT_NUM_STEPS): the planes of the history
-    const size_t rows = (size_t)T + kModTablePad;
-    if (!modTab_ && !dalloc(&modTab_, rows * kModRowStride, false)) return false;
-    if (!modTabValid_) {  // rows -kModTablePad .. -1: zero; rows 0 .. T - 1: the table, 28 floats and four zeros each
-        std::vector<float> def((size_t)T * kModRowFloats), tab(rows * kModRowStride, 0.f);
-        modulationTable(T, (int)g_.fs, modHz_, def.data());
-        for (int t = 0; t < T; ++t)
-            std::memcpy(&tab[((size_t)t + kModTablePad) * kModRowStride], &def[(size_t)t * kModRowFloats], kModRowFloats * sizeof(float));
-        if (!hipOk(hipMemcpyAsync(modTab_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream_), "modulation table upload") ||
-            !hipOk(hipStreamSynchronize(stream_), "modulation table sync"))
-            return false;
-        modTabValid_ = true;
-    }
-    return true;
-}
-
-void Solver::modulationFrequencies(float* hz14) const {
-    for (int i = 0; i < kModFreqs; ++i) hz14[i] = modHz_[i];
-}
-
-bool Solver::computeModulation(float* ms) {
-    if (isSlab()) return fail("modulation: not available on a slab");
-    if (opt_.streaming) return fail("modulation: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("modulation: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    if (bandHz_.empty()) return fail("modulation: no bands set (PvAmdSetBands)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("modulation: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("modulation: the last run ended in error");
-    const int n = (int)bandHz_.size();
-    if (modulation_ && modulationPlanes_ != kModFloats * n) {
-        hipFree(modulation_);
-        modulation_ = nullptr;
-    }
-    if (!modulation_) {
-        if (!dalloc(&modulation_, (size_t)kModFloats * n * (size_t)histPlane_, false)) return false;
-        modulationPlanes_ = kModFloats * n;
-    }
-    if (!ensureModTable()) return false;
-    for (auto& e : modulationEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    modulationValid_ = false;
-    modulationHostValid_ = false;
-    hipEventRecord(modulationEv_[0], stream_);
-    launchModulation(analyzeArgs(lastLx_, lastLz_), bandCoefs_.data(), n, modTab_ + (size_t)kModTablePad * kModRowStride, modulation_, stream_);
-    hipEventRecord(modulationEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "modulation launch") || !hipOk(hipStreamSynchronize(stream_), "modulation sync")) return false;
-    if (ms) hipEventElapsedTime(ms, modulationEv_[0], modulationEv_[1]);
-    modulationDyn_ = dynCur_;
-    modulationValid_ = true;
-    return true;
-}
-
-bool Solver::fetchModulation() {
-    if (bandHz_.empty()) return fail("modulation: no bands set (PvAmdSetBands)");
-    if (!modulationValid_)
-        return fail("modulation: not computed for the last run, the current geometry, the current bands and the current modulation "
-                    "frequencies (PvAmdComputeModulation)");
-    if (modulationHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    modulationHost_.resize((size_t)modulationPlanes_ * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(modulationHost_.data(), modulation_, modulationHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "modulation copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "modulation sync"))
-        return false;
-    modulationHostValid_ = true;
-    return true;
-}
-
-bool Solver::copyModulationBlock(int r0, int c0, int nr, int nc, float* out) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("modulation: block outside the map");
-    if (!fetchModulation()) return false;
-    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
-    const int wr0 = modulationDyn_.histRow0 - geo_.G, wc0 = modulationDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const int nf = modulationPlanes_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < nf; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * modulationDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < nf; ++k) o[k] = modulationHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::modulationAt(float ex, float ez, float* out15n) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!fetchModulation()) return false;
-        for (int k = 0; k < modulationPlanes_; ++k) out15n[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copyModulationBlock(cx, cy, 1, 1, out15n);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// spectrum (pv_spectrum.hip)
-// ----------------------------------------------------------------------------------------------------------------
-
-// The register block that takes the next of `left` bins: time goes with the bins a pass holds, padding included, and B = 16 was
-// the fastest form for 32 bins, B = 8 for 8 (docs/experiments/spectrum.md).  PLANEVERB_AMD_SPECTRUM_BLOCK = 8 / 16 forces one
-// form (measurement).
-static int spectrumBlockFor(int left) {
-    static const int forced = [] {
-        const char* e = std::getenv("PLANEVERB_AMD_SPECTRUM_BLOCK");
-        const int b = e ? std::atoi(e) : 0;
-        return spectrumBlockOk(b) ? b : 0;
-    }();
-    if (forced) return forced;
-    return left <= 8 ? 8 : 16;
-}
-
-bool Solver::setSpectrumBins(const float* hz, int n) {
-    if (isSlab()) return fail("spectrum: not available on a slab");
-    if (n == 0 && (qspecKinds_ & (1u << kQspecSpectrum)))
-        return fail("spectral records: the bins cannot be cleared while PVA_QSPEC_SPECTRUM is selected (PvAmdSetQuerySpectralRecords)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
-    spectrumValid_ = false;
-    spectrumHostValid_ = false;
-    if (qspecKinds_ & (1u << kQspecSpectrum)) qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old bins')
-    for (float** p : {&specTab_, &specPow_})
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    specHz_.clear();
-    specPasses_.clear();
-    if (n == 0) {
-        if (spectrum_) hipFree(spectrum_);
-        spectrum_ = nullptr;
-        spectrumPlanes_ = 0;
-        specCos_.clear();
-        specSin_.clear();
-        specSource_.clear();
-        return true;
-    }
-    const int T = T_;  // the run's steps (PVA_OPT_NUM_STEPS): the planes of the history; pulse_ holds at least as many
-    specHz_.assign(hz, hz + n);
-    specCos_.resize((size_t)T * n);
-    specSin_.resize((size_t)T * n);
-    spectrumTables(T, (int)g_.fs, hz, n, specCos_.data(), specSin_.data());
-    specSource_.resize((size_t)3 * n);
-    pva::spectrumSource(pulse_.data(), T, specCos_.data(), specSin_.data(), n, specSource_.data());
-    // the device tables: per pass, rows of {cos, sin} pairs of the pass's block (bins past the slice and rows past T - 1: zero)
-    const size_t rows = (size_t)T + kSpectrumTablePad;
-    size_t total = 0;
-    for (int b0 = 0; b0 < n;) {
-        const int block = spectrumBlockFor(n - b0), bins = std::min(block, n - b0);
-        specPasses_.push_back(SpecPass{b0, bins, block, total});
-        total += rows * 2 * (size_t)block;
-        b0 += bins;
-    }
-    std::vector<float> tab(total, 0.f), pw((size_t)n);
-    for (const SpecPass& ps : specPasses_)
-        for (int t = 0; t < T; ++t)
-            for (int j = 0; j < ps.bins; ++j) {
-                float* w = &tab[ps.tabOff + ((size_t)t * ps.block + j) * 2];
-                w[0] = specCos_[(size_t)t * n + ps.bin0 + j];
-                w[1] = specSin_[(size_t)t * n + ps.bin0 + j];
-            }
-    for (int j = 0; j < n; ++j) pw[(size_t)j] = specSource_[(size_t)3 * j + 2];
-    const bool ok = dalloc(&specTab_, total, false) && dalloc(&specPow_, (size_t)n, false) &&
-                    hipOk(hipMemcpyAsync(specTab_, tab.data(), total * 4, hipMemcpyHostToDevice, stream_), "spectrum table upload") &&
-                    hipOk(hipMemcpyAsync(specPow_, pw.data(), (size_t)n * 4, hipMemcpyHostToDevice, stream_), "spectrum table upload") &&
-                    hipOk(hipStreamSynchronize(stream_), "spectrum table sync");
-    if (!ok) {  // (nothing half-set: no bins)
-        specHz_.clear();
-        specPasses_.clear();
-    }
-    return ok;
-}
-
-int Solver::spectrumBins(float* hz, int cap) const {
-    const int n = (int)specHz_.size();
-    for (int j = 0; j < n && j < cap && hz; ++j) hz[j] = specHz_[(size_t)j];
-    return n;
-}
-
-bool Solver::spectrumSource(float* out3n) {
-    if (specHz_.empty()) return fail("spectrum: no bins set (PvAmdSetSpectrumBins)");
-    std::memcpy(out3n, specSource_.data(), specSource_.size() * 4);
-    return true;
-}
-
-bool Solver::computeSpectrum(float* ms) {
-    if (isSlab()) return fail("spectrum: not available on a slab");
-    if (opt_.streaming) return fail("spectrum: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("spectrum: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    if (specHz_.empty()) return fail("spectrum: no bins set (PvAmdSetSpectrumBins)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("spectrum: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("spectrum: the last run ended in error");
-    const int n = (int)specHz_.size();
-    if (spectrum_ && spectrumPlanes_ != 3 * n) {
-        hipFree(spectrum_);
-        spectrum_ = nullptr;
-    }
-    if (!spectrum_) {
-        if (!dalloc(&spectrum_, (size_t)3 * n * (size_t)histPlane_, false)) return false;
-        spectrumPlanes_ = 3 * n;
-    }
-    for (auto& e : spectrumEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    spectrumValid_ = false;
-    spectrumHostValid_ = false;
-    const AnalyzeArgs a = analyzeArgs(lastLx_, lastLz_);
-    hipEventRecord(spectrumEv_[0], stream_);
-    for (const SpecPass& ps : specPasses_)
-        launchSpectrum(a, ps.block, ps.bins, specTab_ + ps.tabOff, specPow_ + ps.bin0, spectrum_ + (size_t)3 * ps.bin0 * (size_t)histPlane_, stream_);
-    hipEventRecord(spectrumEv_[1], stream_);
-    if (!hipOk(hipGetLastError(), "spectrum launch") || !hipOk(hipStreamSynchronize(stream_), "spectrum sync")) return false;
-    if (ms) hipEventElapsedTime(ms, spectrumEv_[0], spectrumEv_[1]);
-    spectrumDyn_ = dynCur_;
-    spectrumValid_ = true;
-    return true;
-}
-
-bool Solver::fetchSpectrum() {
-    if (specHz_.empty()) return fail("spectrum: no bins set (PvAmdSetSpectrumBins)");
-    if (!spectrumValid_) return fail("spectrum: not computed for the last run, the current geometry and the current bins (PvAmdComputeSpectrum)");
-    if (spectrumHostValid_) return true;
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    spectrumHost_.resize((size_t)spectrumPlanes_ * (size_t)histPlane_);
-    if (!hipOk(hipMemcpyAsync(spectrumHost_.data(), spectrum_, spectrumHost_.size() * 4, hipMemcpyDeviceToHost, stream_), "spectrum copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "spectrum sync"))
-        return false;
-    spectrumHostValid_ = true;
-    return true;
-}
-
-bool Solver::copySpectrumBlock(int r0, int c0, int nr, int nc, float* out) {
-    if (r0 < 0 || c0 < 0 || nr < 1 || nc < 1 || r0 + nr > g_.gx || c0 + nc > g_.gy) return fail("spectrum: block outside the map");
-    if (!fetchSpectrum()) return false;
-    // (as copyRoomMetricsBlock: a cell outside the run's history window is unreached by construction)
-    const int wr0 = spectrumDyn_.histRow0 - geo_.G, wc0 = spectrumDyn_.histCol0 - geo_.G;
-    const int wnr = histTilesX_ * rxi_, wnc = histTilesY_ * wi_;
-    const int nf = spectrumPlanes_;
-    const float qnan = std::numeric_limits<float>::quiet_NaN();
-    for (int r = 0; r < nr; ++r)
-        for (int c = 0; c < nc; ++c) {
-            float* o = out + ((size_t)r * nc + c) * (size_t)nf;
-            const int hr = r0 + r - wr0, hc = c0 + c - wc0;
-            if (hr < 0 || hc < 0 || hr >= wnr || hc >= wnc) {
-                for (int k = 0; k < nf; ++k) o[k] = qnan;
-                continue;
-            }
-            const int ti = hr / rxi_, tj = hc / wi_;
-            const size_t g = ((size_t)(ti * spectrumDyn_.histTilesY + tj) * rxi_ + (hr - ti * rxi_)) * wi_ + (hc - tj * wi_);
-            for (int k = 0; k < nf; ++k) o[k] = spectrumHost_[(size_t)k * histPlane_ + g];
-        }
-    return true;
-}
-
-bool Solver::spectrumAt(float ex, float ez, float* out3n) {
-    int cx, cy;
-    if (!resultCell(g_, ex, ez, &cx, &cy)) {  // (a position off the map, as getOutput finds it)
-        if (!fetchSpectrum()) return false;
-        for (int k = 0; k < spectrumPlanes_; ++k) out3n[k] = std::numeric_limits<float>::quiet_NaN();
-        return true;
-    }
-    return copySpectrumBlock(cx, cy, 1, 1, out3n);
 }
 
 bool Solver::copyPulse(float* out) {

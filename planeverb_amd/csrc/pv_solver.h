@@ -85,6 +85,20 @@ struct SolverTimings {
     int silentCells = 0;   // air cells among them whose whole history stayed below the audible threshold
 };
 
+// the per-cell analysis maps a solver keeps (Solver::maps_; their messages: kAnalysisInfo, pv_solver_maps.cpp)
+enum AnalysisKind {
+    kMapRoomMetrics,
+    kMapDecayTimes,
+    kMapLateralFraction,
+    kMapEchoCriterion,
+    kMapEchogram,
+    kMapLobes,
+    kMapBandMetrics,
+    kMapModulation,
+    kMapSpectrum,
+    kAnalysisKinds
+};
+
 class SlabGroup;
 class SlabRoot;
 struct SlabRankOps;
@@ -159,11 +173,11 @@ public:
     // raw rasteriser access (Grid::AddAABB / RemoveAABB), used by the live context's change queue
     void rasterAdd(const Box& b) {
         mat_.add(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+        invalidateAnalysisMaps();
     }
     void rasterRemove(const Box& b) {
         mat_.remove(b);
-        metricsValid_ = spectrumValid_ = decayValid_ = lateralValid_ = bandsValid_ = echoValid_ = echoCritValid_ = lobesValid_ = modulationValid_ = false;
+        invalidateAnalysisMaps();
     }
 
     // Shape layer (pv_shapes.h): convex polygons, round shapes and simple polygons (pv_core.h Shape::kind) over the AABB layer,
@@ -275,80 +289,57 @@ public:
     bool copyFields(float* pr, float* vx, float* vy);
     bool setFields(const float* pr, const float* vx, const float* vy);
     bool copyHistoryPlane(int t, float* pr);
-    // Room metrics (pv_metrics.hip; include/planeverb_amd.h PvAmdRoomMetrics) of the last completed run: one pass over its history
-    // on stream_, synchronised before it returns; *ms (optional) = its device time.  The records stay valid until the next run,
-    // geometry, boundary or layer change.  out10: nr x nc records of ten floats, NaN where the cell has no onset in that run
+    // Per-cell analysis maps of the last completed run (pv_solver_maps.cpp; include/planeverb_amd.h names the records): nine
+    // kinds (AnalysisKind), each one pass over the run's history on stream_, synchronised before computeX returns; *ms
+    // (optional) = its device time.  A kind's records stay valid until the next run, geometry, boundary or layer change, or a
+    // change of the kind's own setting.  Refused on slabs, on sparse-emitter solvers, without an onset map and before a run has
+    // completed.  copyAnalysisBlock: nr x nc records of the kind's width, NaN where the cell has no onset in that run;
+    // analysisAt: the record of the cell getOutput reads, NaNs for a position off the map
+    bool copyAnalysisBlock(AnalysisKind k, int r0, int c0, int nr, int nc, float* out);
+    bool analysisAt(AnalysisKind k, float ex, float ez, float* out);
+    // Room metrics (pv_metrics.hip): records of ten floats
     bool computeRoomMetrics(float* ms);
-    bool copyRoomMetricsBlock(int r0, int c0, int nr, int nc, float* out10);
-    bool roomMetricsAt(float ex, float ez, float out10[10]);
-    // Decay times (pv_decay.hip; include/planeverb_amd.h PvAmdDecayTimes) of the last completed run: EDT, T20, T30 off the
-    // backward-integrated curve of its history; stream, synchronisation, lifetime and refusals as the room metrics'.  out8: nr x nc
-    // records of eight floats, NaN where the cell has no onset in that run
+    // Decay times (pv_decay.hip): EDT, T20, T30 off the backward-integrated curve of the history; records of eight floats
     bool computeDecayTimes(float* ms);
-    bool copyDecayTimesBlock(int r0, int c0, int nr, int nc, float* out8);
-    bool decayTimesAt(float ex, float ez, float out8[8]);
-    // Lateral energy fraction and early-sound direction (pv_lateral.hip; include/planeverb_amd.h PvAmdLateralFraction) of the last
-    // completed run: vx, vy of every reached cell re-derived from its history through the 80 ms window; stream, synchronisation,
-    // lifetime and refusals as the room metrics'.  out11: nr x nc records of eleven floats, NaN where the cell has no onset in that run
+    // Lateral energy fraction and early-sound direction (pv_lateral.hip): vx, vy of every reached cell re-derived from its
+    // history through the 80 ms window; records of eleven floats
     bool computeLateralFraction(float* ms);
-    bool copyLateralFractionBlock(int r0, int c0, int nr, int nc, float* out11);
-    bool lateralFractionAt(float ex, float ez, float out11[11]);
-    // Directional echogram (pv_echogram.hip; include/planeverb_amd.h PvAmdSetEchogram): energy and flux of the last completed run
-    // per time slot after each cell's onset, for the slots set here; lifetime and refusals as the lateral fraction's, and a
-    // change of slots invalidates the records.  setEchogram: the caller has validated the setting (pv_echogram.h echogramSlotOk,
-    // 0 <= nSlots <= kEchogramMaxSlots); nSlots = 0 clears and frees; waits for a run in flight.  out: nr x nc records of
-    // 1 + 3 nSlots floats, NaN where the cell has no onset in that run
+    // Directional echogram (pv_echogram.hip): energy and flux per time slot after each cell's onset, for the slots set here;
+    // records of 1 + 3 nSlots floats.  setEchogram: the caller has validated the setting (pv_echogram.h echogramSlotOk,
+    // 0 <= nSlots <= kEchogramMaxSlots); nSlots = 0 clears and frees; waits for a run in flight
     bool setEchogram(float slotSeconds, int nSlots);
     int echogramSlots(float* slotSeconds, int* slotSteps) const;
     bool computeEchogram(float* ms);
-    bool copyEchogramBlock(int r0, int c0, int nr, int nc, float* out);
-    bool echogramAt(float ex, float ez, float* out);
-    // Directional energy lobes (pv_lobes.hip; include/planeverb_amd.h PvAmdSetLobeWindows): the energy of the last completed run
-    // per time window after each cell's onset, split over the travel directions +x, -x, +y, -y; lifetime and refusals as the
-    // echogram's, and a change of windows invalidates the records.  setLobeWindows: the caller has validated the edges
-    // (pv_lobes.h lobesEdgeSteps); nEdges = 0 restores the default; waits for a run in flight.  out: nr x nc records of
-    // 1 + 5 nW floats, NaN where the cell has no onset in that run
+    // Directional energy lobes (pv_lobes.hip): the energy per time window after each cell's onset, split over the travel
+    // directions +x, -x, +y, -y; records of 1 + 5 nW floats.  setLobeWindows: the caller has validated the edges (pv_lobes.h
+    // lobesEdgeSteps); nEdges = 0 restores the default; waits for a run in flight
     bool setLobeWindows(const float* edgesSeconds, int nEdges);
     int lobeWindows(float* edgesSeconds, int* edgeSteps) const;
     bool computeLobes(float* ms);
-    bool copyLobesBlock(int r0, int c0, int nr, int nc, float* out);
-    bool lobesAt(float ex, float ez, float* out);
-    // Echo criterion (pv_echo.hip; include/planeverb_amd.h PvAmdEchoCriterion) of the last completed run: speech and music
-    // variant from one forward pass over its history; stream, synchronisation, lifetime and refusals as the room metrics', and
-    // refused where the sampling rate gives a speech lag below one step.  out10: nr x nc records of ten floats, NaN where the
-    // cell has no onset in that run
+    // Echo criterion (pv_echo.hip): speech and music variant from one forward pass over the history; records of ten floats;
+    // refused where the sampling rate gives a speech lag below one step
     bool computeEchoCriterion(float* ms);
-    bool copyEchoCriterionBlock(int r0, int c0, int nr, int nc, float* out10);
-    bool echoCriterionAt(float ex, float ez, float out10[10]);
-    // Band metrics (pv_bands.hip; include/planeverb_amd.h PvAmdBandMetrics): decay times and clarity of the last completed run per
-    // octave or third-octave band set here; lifetime and refusals as the decay times', and a change of bands invalidates the
-    // records.  setBands: the caller has validated the centres (pv_bands.h bandsError); n = 0 clears and frees; waits for a run
-    // in flight.  out: nr x nc x n records of twelve floats, NaN where the cell has no onset in that run
+    // Band metrics (pv_bands.hip): decay times and clarity per octave or third-octave band set here; n records of twelve floats
+    // per cell.  setBands: the caller has validated the centres (pv_bands.h bandsError); n = 0 clears and frees; waits for a run
+    // in flight
     bool setBands(const float* centreHz, int n, int fraction);
     int bands(float* centreHz, int cap, int* fraction) const;
     bool bandCoefs(float* out10n);
     bool computeBandMetrics(float* ms);
-    bool copyBandMetricsBlock(int r0, int c0, int nr, int nc, float* out);
-    bool bandMetricsAt(float ex, float ez, float* out12n);
-    // Modulation (pv_modulation.hip; include/planeverb_amd.h PvAmdModulation): the modulation transfer function at 14 modulation
-    // frequencies and the modulation transfer index of the last completed run per band of setBands; lifetime and refusals as the
-    // band metrics', and a change of bands or of the modulation frequencies invalidates the records.  setModulationFrequencies:
-    // the caller has validated hz14 (pv_modulation.h modulationFreqsError); nullptr restores the default; waits for a run in
-    // flight.  out: nr x nc x n records of fifteen floats, NaN where the cell has no onset in that run
+    // Modulation (pv_modulation.hip): the modulation transfer function at 14 modulation frequencies and the modulation transfer
+    // index per band of setBands; n records of fifteen floats per cell; a change of bands or of the modulation frequencies
+    // invalidates them.  setModulationFrequencies: the caller has validated hz14 (pv_modulation.h modulationFreqsError); nullptr
+    // restores the default; waits for a run in flight
     bool setModulationFrequencies(const float* hz14);
     void modulationFrequencies(float* hz14) const;
     bool computeModulation(float* ms);
-    bool copyModulationBlock(int r0, int c0, int nr, int nc, float* out);
-    bool modulationAt(float ex, float ez, float* out15n);
-    // Spectrum (pv_spectrum.hip; include/planeverb_amd.h Spectrum): transfer functions of the last completed run at the bins set
-    // here, lifetime and refusals as the room metrics'.  setSpectrumBins: the caller has validated hz (pv_spectrum.h
-    // spectrumBinsError); n = 0 clears and frees; waits for a run in flight.  out: nr x nc x n records of three floats
+    // Spectrum (pv_spectrum.hip): transfer functions at the bins set here; n records of three floats per cell.
+    // setSpectrumBins: the caller has validated hz (pv_spectrum.h spectrumBinsError); n = 0 clears and frees; waits for a run
+    // in flight
     bool setSpectrumBins(const float* hz, int n);
     int spectrumBins(float* hz, int cap) const;
     bool spectrumSource(float* out3n);
     bool computeSpectrum(float* ms);
-    bool copySpectrumBlock(int r0, int c0, int nr, int nc, float* out);
-    bool spectrumAt(float ex, float ez, float* out3n);
     bool copyPulse(float* out);
     bool copyMaterial(uint8_t* beta, float* R);
     bool freeFieldEnergyAt(int cellX, int cellY, int n, float r, float* out);
@@ -552,105 +543,62 @@ private:
     ResidentArgs residentArgs(const int* win) const;  // win = nullptr: the grid's own tiles
     void enqueueWindowRun(const int win[4]);
     float* scratch_ = nullptr;  // max(3T, NX*NY) floats
-    // room metrics: ten planes of histPlane_ floats, indexed by the cell's offset inside a history plane (allocated by the first
-    // computeRoomMetrics); metricsDyn_ = the window of the run they belong to; a host copy is fetched by the first read-back
-    float* metrics_ = nullptr;
-    bool metricsValid_ = false;
-    DynParams metricsDyn_{};
-    std::vector<float> metricsHost_;
-    bool metricsHostValid_ = false;
-    hipEvent_t metricsEv_[2] = {nullptr, nullptr};
     enum class LastRun { None, Failed, Ok };  // Failed: in flight, or ended in error (a run is Ok once sync() has seen it through)
     LastRun lastRun_ = LastRun::None;
-    bool fetchRoomMetrics();
-    // decay times: eight planes of histPlane_ floats, kept exactly as the room metrics' ten (allocated by the first
-    // computeDecayTimes); decayValid_ follows metricsValid_, and neither computation touches the other's flag
-    float* decay_ = nullptr;
-    bool decayValid_ = false;
-    DynParams decayDyn_{};
-    std::vector<float> decayHost_;
-    bool decayHostValid_ = false;
-    hipEvent_t decayEv_[2] = {nullptr, nullptr};
-    bool fetchDecayTimes();
-    // lateral fraction: eleven planes of histPlane_ floats, kept exactly as the decay times' eight (allocated by the first
-    // computeLateralFraction); lateralValid_ follows metricsValid_, and no computation touches another's flag
-    float* lateral_ = nullptr;
-    bool lateralValid_ = false;
-    DynParams lateralDyn_{};
-    std::vector<float> lateralHost_;
-    bool lateralHostValid_ = false;
-    hipEvent_t lateralEv_[2] = {nullptr, nullptr};
-    bool fetchLateralFraction();
-    // echogram (pv_echogram.h): the slot length as given and in steps, the slots; 1 + 3 nSlots planes of histPlane_ floats -- n,
-    // then e, ix, iy of slot j at planes 1 + 3 j .. -- allocated by the first computeEchogram and again when nSlots changes.
-    // echoValid_ follows metricsValid_ and is also cleared by a change of the setting; no computation touches another's flag
+    // The analysis maps (pv_solver_maps.cpp): one record per kind.  dev = `planes` planes of histPlane_ floats, a cell's record
+    // at its offset inside a history plane, (re)allocated by the kind's compute when the wanted plane count differs; dyn = the
+    // window of the run the records belong to; host = a copy fetched by the first read-back.  valid is cleared for every kind by
+    // invalidateAnalysisMaps (a new run, a geometry, boundary or layer change) and for one kind by a change of its setting; no
+    // computation touches another kind's record.  All passes are timed with the one event pair: each synchronises the stream and
+    // reads the time before it returns, under queue_.lockUse()
+    struct AnalysisMap {
+        float* dev = nullptr;
+        int planes = 0;
+        bool valid = false, hostValid = false;
+        DynParams dyn{};
+        std::vector<float> host;
+    };
+    AnalysisMap maps_[kAnalysisKinds];
+    hipEvent_t mapEv_[2] = {nullptr, nullptr};
+    void invalidateAnalysisMaps() {
+        for (AnalysisMap& m : maps_) m.valid = false;
+    }
+    void dropAnalysisMap(AnalysisKind k, bool freeDev);  // a changed setting: records invalid, the device storage freed on request
+    bool analysisSettingPresent(AnalysisKind k) const;
+    bool analysisReadable(AnalysisKind k);  // the missing-setting refusal, then the not-computed refusal
+    bool analysisHipOk(AnalysisKind k, hipError_t e, const char* step);
+    // A compute pass: begin = every refusal (`refusal`: the kind's own, nullptr where its precondition holds), the run in flight
+    // waited for, the storage at `planes` planes, `prepare` (stream work in front of the timed interval), the start event;
+    // the caller enqueues its launches on stream_; end = the stop event, the error check, the wait, *ms, the record valid
+    struct AnalysisPass {
+        AnalysisKind kind;
+        std::unique_lock<std::recursive_mutex> inUse;
+        AnalyzeArgs a;
+        float* dev;
+    };
+    bool beginAnalysisPass(AnalysisKind k, int planes, const char* refusal, AnalysisPass* p, bool (Solver::*prepare)() = nullptr);
+    bool endAnalysisPass(AnalysisPass& p, float* ms);
+    bool fetchAnalysisMap(AnalysisKind k);
+    // echogram (pv_echogram.h): the slot length as given and in steps, the slots; planes: n, then e, ix, iy of slot j at 1 + 3 j ..
     float echoSeconds_ = 0.f;
     int echoSteps_ = 0, echoSlots_ = 0;
-    float* echo_ = nullptr;
-    int echoPlanes_ = 0;  // 1 + 3 nSlots of the allocation
-    bool echoValid_ = false;
-    DynParams echoDyn_{};
-    std::vector<float> echoHost_;
-    bool echoHostValid_ = false;
-    hipEvent_t echoEv_[2] = {nullptr, nullptr};
-    bool fetchEchogram();
-    // echo criterion: ten planes of histPlane_ floats, kept exactly as the room metrics' ten (allocated by the first
-    // computeEchoCriterion); echoCritValid_ follows metricsValid_, and no computation touches another's flag
-    float* echoCrit_ = nullptr;
-    bool echoCritValid_ = false;
-    DynParams echoCritDyn_{};
-    std::vector<float> echoCritHost_;
-    bool echoCritHostValid_ = false;
-    hipEvent_t echoCritEv_[2] = {nullptr, nullptr};
-    bool fetchEchoCriterion();
-    // lobes (pv_lobes.h): the window edges as given (the default until some are set); 1 + 5 nW planes of histPlane_ floats -- n, then
-    // E, XP, XN, YP, YN of window j at planes 1 + 5 j .. -- allocated by the first computeLobes and again when nW changes.
-    // lobesValid_ follows metricsValid_ and is also cleared by a change of the windows; no computation touches another's flag
+    // lobes (pv_lobes.h): the window edges as given (the default until some are set); planes: n, then E, XP, XN, YP, YN of
+    // window j at 1 + 5 j ..
     float lobeEdges_[7] = {0.01f, 0.08f, 0.f, 0.f, 0.f, 0.f, 0.f};
     int lobeEdgeCount_ = 2;
-    float* lobes_ = nullptr;
-    int lobesPlanes_ = 0;  // 1 + 5 nW of the allocation
-    bool lobesValid_ = false;
-    DynParams lobesDyn_{};
-    std::vector<float> lobesHost_;
-    bool lobesHostValid_ = false;
-    hipEvent_t lobesEv_[2] = {nullptr, nullptr};
-    bool fetchLobes();
     // band metrics (pv_bands.h): the centres, their fraction and the 10 float32 coefficients per band on the host (the kernel takes
-    // them as arguments); 12 n planes of histPlane_ floats -- band j at planes 12 j .. 12 j + 11 -- allocated by the first
-    // computeBandMetrics and again when n changes.  bandsValid_ follows metricsValid_ and is also cleared by a change of bands; no
-    // computation touches another's flag
+    // them as arguments); planes: band j at 12 j .. 12 j + 11
     std::vector<float> bandHz_, bandCoefs_;
     int bandFraction_ = 1;
-    float* bands_ = nullptr;
-    int bandsPlanes_ = 0;  // 12 n of the allocation
-    bool bandsValid_ = false;
-    DynParams bandsDyn_{};
-    std::vector<float> bandsHost_;
-    bool bandsHostValid_ = false;
-    hipEvent_t bandsEv_[2] = {nullptr, nullptr};
-    bool fetchBandMetrics();
     // modulation (pv_modulation.h): the 14 modulation frequencies (the default until some are set) and their twiddle table on the
-    // device (kModTablePad zero rows, then T rows of 28 floats padded to 32), uploaded by ensureModTable after a change; 15 n planes
-    // of histPlane_ floats -- band j at planes 15 j .. 15 j + 14 -- allocated by the first computeModulation and again when n
-    // changes.  modulationValid_ follows metricsValid_ and is also cleared by a change of bands or frequencies; no computation
-    // touches another's flag
+    // device (kModTablePad zero rows, then T rows of 28 floats padded to 32), uploaded by ensureModTable after a change; planes:
+    // band j at 15 j .. 15 j + 14
     float modHz_[14] = {0.63f, 0.8f, 1.0f, 1.25f, 1.6f, 2.0f, 2.5f, 3.15f, 4.0f, 5.0f, 6.3f, 8.0f, 10.0f, 12.5f};
     float* modTab_ = nullptr;
     bool modTabValid_ = false;
-    float* modulation_ = nullptr;
-    int modulationPlanes_ = 0;  // 15 n of the allocation
-    bool modulationValid_ = false;
-    DynParams modulationDyn_{};
-    std::vector<float> modulationHost_;
-    bool modulationHostValid_ = false;
-    hipEvent_t modulationEv_[2] = {nullptr, nullptr};
-    bool fetchModulation();
     // spectrum (pv_spectrum.h): the bins, their tables c / s [T * n] and source values (sre, sim, spow per bin) on the host; the
     // passes the bins are dealt to (specPasses_: a slice of the bins, the register block that takes it, where its table slice
-    // starts in specTab_); 3 n planes of histPlane_ floats -- re, im, level of bin j at planes 3 j .. 3 j + 2 -- allocated by the
-    // first computeSpectrum and again when n changes.  spectrumValid_ follows metricsValid_ and is also cleared by a bin change;
-    // neither computation touches the other's flag.
+    // starts in specTab_); planes: re, im, level of bin j at 3 j .. 3 j + 2
     struct SpecPass {
         int bin0, bins, block;
         size_t tabOff;
@@ -659,14 +607,6 @@ private:
     std::vector<SpecPass> specPasses_;
     float* specTab_ = nullptr;
     float* specPow_ = nullptr;
-    float* spectrum_ = nullptr;
-    int spectrumPlanes_ = 0;  // 3 n of the allocation
-    bool spectrumValid_ = false;
-    DynParams spectrumDyn_{};
-    std::vector<float> spectrumHost_;
-    bool spectrumHostValid_ = false;
-    hipEvent_t spectrumEv_[2] = {nullptr, nullptr};
-    bool fetchSpectrum();
     size_t scratchCount_ = 0;
 
     // pinned host staging
@@ -783,5 +723,14 @@ private:
     bool pendingTimings_ = false;
     bool loopTimed() const { return plan_.path == StepPath::Launches && plan_.kind == PathRun::Run; }  // ev_[3] was recorded between the reset and the first step launch of this run
 };
+
+template <typename Tp>
+bool Solver::dalloc(Tp** p, size_t count, bool zero) {  // (here: pv_solver.cpp and pv_solver_maps.cpp both allocate)
+    const size_t bytes = count * sizeof(Tp);
+    if (!hipOk(hipMalloc((void**)p, bytes), "hipMalloc")) return false;
+    deviceBytes_ += (long long)bytes;
+    if (zero && !hipOk(hipMemsetAsync(*p, 0, bytes, stream_), "hipMemsetAsync")) return false;
+    return true;
+}
 
 }  // namespace pva
