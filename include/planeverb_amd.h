@@ -1201,6 +1201,78 @@ PVA_EXPORT int PvAmdHostSpectrumTables(int T, int fs, const float* hz, int n, fl
  * restatement the tests hold the kernel to.  The bins are checked by the rule of PvAmdSetSpectrumBins */
 PVA_EXPORT int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const float* hz, int n, const float* pulseT,
                                  float* out3n);
+
+/* ---- Zone statistics: spatial statistics of a computed map over receiver areas ----
+ * ISO 3382-1 reports its quantities as averages over receiver areas, with their spread.  A ZONE is a label per result cell;
+ * PvAmdComputeZoneStats reduces one computed map of the nine kinds above to one record per zone and plane ON THE DEVICE
+ * (pv_zones.hip) and only the records cross to the host -- no copy of the map is made.  Definition, for zone z and plane k:
+ *   members  the result cells s = X * gy + Y with labels[s] == z (label 0: no zone; labels 1 .. nZones, nZones <= PVA_ZONES_MAX;
+ *            zones do not overlap);
+ *   x(s)     exactly what PvAmdCopy<Kind> gives at cell s, float k of its record: cells without an onset, and cells outside
+ *            the run's history window, are NaN there and count as NaN here;
+ *   counts   every member is in exactly one class: finite (x - x == 0), NaN, +inf, -inf; the four counts add up to the zone's
+ *            size;
+ *   min, max over the FINITE members only; -0.0 and +0.0 compare equal; a tie goes to the smallest cell index s, and that
+ *            cell's bits are reported; argmin / argmax are cell indices s;
+ *   sum      double, in ONE order that depends on result coordinates alone (never on tiles, the history window or the launch
+ *            shape).  v(X, Y) = (double)x for a finite member, +0.0 for every other cell and for columns Y >= gy;
+ *              block  row X, block b: v(X, 64 b .. 64 b + 63) by a butterfly -- for st = 1, 2, 4, 8, 16, 32: v[i] = v[i] +
+ *                     v[i + st] for every i that is a multiple of 2 st; the block value is v[0];
+ *              row    the block values added sequentially in increasing b, from +0.0;
+ *              zone   the row sums added sequentially in increasing X over all rows 0 .. gx - 1, from +0.0;
+ *   mean     sum / (double)n_finite;
+ *   m2       the same three-level rule over d * d, d = (double)x - mean; the subtract, the product and every add are rounded
+ *            on their own (no fused multiply-add);
+ *   std      sqrt(m2 / (double)n_finite): the population form; divide and sqrt correctly rounded (std is computed on the host
+ *            from the device's m2);
+ *   empty    n_finite == 0: sum = +0.0; mean, m2, std, min, max quiet NaN; argmin = argmax = -1.
+ * PvAmdHostZoneStats applies the same rule on the CPU, bit for bit.
+ * Device storage: the labels (one byte per result cell) from PvAmdSetZones on; scratch of 48 bytes per zone, result row and
+ * plane in flight from the first PvAmdComputeZoneStats on -- the planes of a map are dealt in chunks that keep it within
+ * 32 MiB (one plane's nZones x gx x 48 bytes where that is more) -- plus the records.
+ * Out of scope: the eight-output result map (its far cells are kept lazily and carry values over between runs), histograms
+ * and percentiles, overlapping zones, in-run or live-module zone records, slab groups, slab ranks and sparse-emitter solvers. */
+#define PVA_MAP_ROOM_METRICS     0
+#define PVA_MAP_DECAY_TIMES      1
+#define PVA_MAP_LATERAL_FRACTION 2
+#define PVA_MAP_ECHO_CRITERION   3
+#define PVA_MAP_ECHOGRAM         4
+#define PVA_MAP_LOBES            5
+#define PVA_MAP_BAND_METRICS     6
+#define PVA_MAP_MODULATION       7
+#define PVA_MAP_SPECTRUM         8
+#define PVA_ZONES_MAX 64
+typedef struct PvAmdZoneStat {
+    double sum, mean, m2, std;
+    float min, max;
+    int argmin, argmax;
+    int n_finite, n_nan, n_posinf, n_neginf;
+} PvAmdZoneStat; /* 64 bytes */
+/* Set the zones: labels = gx*gy bytes, cell X*gy + Y, each 0 or 1 .. nZones (copied to the device; they survive runs and
+ * geometry changes).  labels = NULL with nZones = 0 clears them.  Waits for a run in flight.  Refused with -1 and nothing
+ * changed ("zone statistics: ..."): a label above nZones, nZones outside 1 .. PVA_ZONES_MAX, labels = NULL with nZones > 0,
+ * slab groups, slab ranks and sparse-emitter solvers */
+PVA_EXPORT int PvAmdSetZones(PvAmdSolver* s, const unsigned char* labels, int nZones);
+/* the labels as set (gx*gy bytes; labels may be NULL; untouched when no zones are set) and their count (0: none); returns 0 */
+PVA_EXPORT int PvAmdGetZones(PvAmdSolver* s, unsigned char* labels, int* nZones);
+/* the planes of a kind (PVA_MAP_*) under the current settings: 10, 8, 11, 10, 1 + 3 slots, 1 + 5 windows, 12 bands, 15 bands,
+ * 3 bins; -1 where the kind's setting is missing */
+PVA_EXPORT int PvAmdZoneStatPlanes(PvAmdSolver* s, int kind);
+/* The records of the computed map of `kind` for the current zones: nZones x planes records, zone-major -- zone z, plane k at
+ * out[(z - 1) * planes + k]; returns their number, or -1 with PvAmdLastError.  Refused: no zones set, cap below
+ * nZones x planes, a kind whose map is not valid (the kind's own "not computed ..." or missing-setting message behind
+ * "zone statistics: ").  Synchronous on the solver's own stream (waits for a run in flight); *ms (optional): device time of the
+ * passes.  Nothing is cached: the call neither changes the map nor invalidates any kind. */
+PVA_EXPORT int PvAmdComputeZoneStats(PvAmdSolver* s, int kind, PvAmdZoneStat* out, int cap, float* ms);
+/* CPU only: the definition above applied to a map as PvAmdCopy<Kind> returns it (gx*gy records of `planes` floats, cell-major);
+ * out = nZones x planes records, zone-major.  The restatement the tests hold the kernel to.  The labels are checked by the rule
+ * of PvAmdSetZones */
+PVA_EXPORT int PvAmdHostZoneStats(const float* map, int gx, int gy, int planes, const unsigned char* labels, int nZones,
+                                  PvAmdZoneStat* out);
+/* CPU only: labels from n <= PVA_ZONES_MAX rectangles rect4[4 j ..] = {xmin, zmin, xmax, zmax} in metres: cell (X, Y) gets j + 1
+ * where xmin <= (X + 0.5f) * dx < xmax and zmin <= (Y + 0.5f) * dx < zmax in float32; later rectangles overwrite earlier ones;
+ * cells in no rectangle get 0 */
+PVA_EXPORT int PvAmdHostZoneRects(float dx, int gx, int gy, const float* rect4, int n, unsigned char* labels);
 /* Gaussian pulse table (Grid.cpp:12-27), T floats */
 PVA_EXPORT int PvAmdCopyPulse(PvAmdSolver* s, float* out);
 /* Material planes after rasterisation: beta (uint8) and R (float), (gx+1)*(gy+1) each (with shapes: the composed material) */

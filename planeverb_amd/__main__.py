@@ -29,6 +29,51 @@ def echogram_setting(s):
     return float(v[0]), int(v[1])
 
 
+def rect4(s):
+    v = [float(x) for x in s.split(",")]
+    if len(v) != 4:
+        raise argparse.ArgumentTypeError("expected xmin,zmin,xmax,zmax")
+    return tuple(v)
+
+
+def zone_plane_names(s, a):
+    """(kind name, JSON key, the names of its planes) of every map the options asked for, in the maps' plane order"""
+    kinds = []
+    if a.room_metrics:
+        kinds.append(("room_metrics", "roomMetrics", list(api.ROOM_METRIC_NAMES)))
+    if a.decay_times:
+        kinds.append(("decay_times", "decayTimes", list(api.DECAY_TIME_NAMES)))
+    if a.lateral_fraction:
+        kinds.append(("lateral_fraction", "lateralFraction", list(api.LATERAL_FRACTION_NAMES)))
+    if a.echo_criterion:
+        kinds.append(("echo_criterion", "echoCriterion", list(api.ECHO_CRITERION_NAMES)))
+    if a.echogram:
+        kinds.append(("echogram", "echogram", ["n"] + ["%s[%d]" % (n, j) for j in range(s.echogram_slots()[0]) for n in ("e", "ix", "iy")]))
+    if a.lobes is not None:
+        kinds.append(("lobes", "lobes", ["n"] + ["%s[%d]" % (n, w) for w in range(len(s.lobe_windows()[0]) + 1) for n in api.LOBE_NAMES]))
+    if a.bands:
+        kinds.append(("band_metrics", "bandMetrics", ["%gHz.%s" % (hz, n) for hz in a.bands for n in api.BAND_METRIC_NAMES]))
+    if a.modulation:
+        kinds.append(("modulation", "modulation", ["%gHz.%s" % (hz, n) for hz in a.bands
+                                                   for n in ["m[%d]" % j for j in range(api.MODULATION_FREQS)] + ["mti"]]))
+    if a.spectrum:
+        kinds.append(("spectrum", "spectrum", ["%gHz.%s" % (hz, n) for hz in a.spectrum for n in ("re", "im", "levelDb")]))
+    return kinds
+
+
+def zone_tables(s, a):
+    """one table per --zone: for every plane of every computed map its n (finite members), mean, std, min and max over the zone"""
+    labels = api.zone_labels_from_rects(s.dx, s.gx, s.gy, a.zone)
+    s.set_zones(labels, len(a.zone))
+    tables = [{"rect": list(r), "cells": int((labels == j + 1).sum())} for j, r in enumerate(a.zone)]
+    for kind, key, names in zone_plane_names(s, a):
+        recs = s.zone_stats(kind).reshape(len(a.zone), -1)
+        for t, row in zip(tables, recs):
+            t[key] = dict((n, {"n": int(r["n_finite"]), "mean": float(r["mean"]), "std": float(r["std"]), "min": float(r["min"]),
+                               "max": float(r["max"])}) for n, r in zip(names, row))
+    return tables
+
+
 def record_object(kind, m, slot_steps=0):
     """the JSON object of one record (the key names of RECORD_KEYS)"""
     if kind == api.QREC_ECHOGRAM:
@@ -111,11 +156,19 @@ def main(argv=None):
                     help="add all six record kinds of each emitter as the LIVE module serves them by emission id "
                          "(PlaneverbSetEmissionRecords; --echogram and --lobes give their settings, default 0.005,16 and "
                          "0.01,0.08), under the key names of --in-run-records")
+    ap.add_argument("--zone", metavar="XMIN,ZMIN,XMAX,ZMAX", type=rect4, action="append", default=[],
+                    help="a receiver area in metres (repeatable, at most 64; a later one overwrites an earlier one where they "
+                         "overlap): with any of the map options above, add a table per zone with n, mean, std, min and max of "
+                         "every plane of those maps over the zone's cells, reduced on the GPU")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
     if a.modulation and not a.bands:
         ap.error("--modulation: needs --bands")
+    if a.zone and a.in_run_records:
+        ap.error("--zone: reduces the whole-map passes (not with --in-run-records)")
+    if len(a.zone) > api.ZONES_MAX:
+        ap.error("--zone: at most %d zones" % api.ZONES_MAX)
     boxes = api.load_pv(a.scene)
     if a.save:
         api.save_pv(a.save, boxes)
@@ -220,6 +273,8 @@ def main(argv=None):
                 m = s.spectrum_at(e) if whole else qspec[api.QSPEC_SPECTRUM][i]
                 out["emitters"][-1]["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],
                                                    "im": [float(v) for v in m[:, 1]], "levelDb": [float(v) for v in m[:, 2]]}
+        if a.zone:
+            out["zones"] = zone_tables(s, a)
         if a.emission_records:
             echogram = a.echogram or (0.005, 16)
             s.set_echogram(*echogram)  # (for the slot length in steps)

@@ -348,6 +348,12 @@ SYMBOLS = {
     "PvAmdGetSpectrum": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
     "PvAmdHostSpectrumTables": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
     "PvAmdHostSpectrum": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
+    "PvAmdSetZones": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int]),
+    "PvAmdGetZones": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
+    "PvAmdZoneStatPlanes": (C.c_int, [_vp, C.c_int]),
+    "PvAmdComputeZoneStats": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _fp]),
+    "PvAmdHostZoneStats": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, _vp]),
+    "PvAmdHostZoneRects": (C.c_int, [C.c_float, C.c_int, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
     "PvAmdCopyPulse": (C.c_int, [_vp, _fp]),
     "PvAmdCopyMaterial": (C.c_int, [_vp, C.POINTER(C.c_ubyte), _fp]),
     "PvAmdSetFields": (C.c_int, [_vp, _fp, _fp, _fp]),
@@ -1013,6 +1019,59 @@ def host_spectrum(p, fs, onset, hz, pulse):
     out = np.empty((h.size, 3), np.float32)
     _check(lib().PvAmdHostSpectrum(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(h) if h.size else None,
                                    int(h.size), _f(q) if q.size else None, _f(out)))
+    return out
+
+
+# PVA_MAP_*: the nine per-cell analysis kinds, as Solver.zone_stats names them (the stems of Solver.compute_<name> / <name>)
+PVA_MAP_ROOM_METRICS, PVA_MAP_DECAY_TIMES, PVA_MAP_LATERAL_FRACTION, PVA_MAP_ECHO_CRITERION, PVA_MAP_ECHOGRAM = 0, 1, 2, 3, 4
+PVA_MAP_LOBES, PVA_MAP_BAND_METRICS, PVA_MAP_MODULATION, PVA_MAP_SPECTRUM = 5, 6, 7, 8
+MAP_KIND_NAMES = ("room_metrics", "decay_times", "lateral_fraction", "echo_criterion", "echogram", "lobes", "band_metrics",
+                  "modulation", "spectrum")
+ZONES_MAX = 64  # PVA_ZONES_MAX
+# PvAmdZoneStat (64 bytes)
+ZONE_STAT_DTYPE = np.dtype([("sum", "<f8"), ("mean", "<f8"), ("m2", "<f8"), ("std", "<f8"), ("min", "<f4"), ("max", "<f4"),
+                            ("argmin", "<i4"), ("argmax", "<i4"), ("n_finite", "<i4"), ("n_nan", "<i4"), ("n_posinf", "<i4"),
+                            ("n_neginf", "<i4")])
+assert ZONE_STAT_DTYPE.itemsize == 64
+
+
+def _map_kind(kind):
+    if isinstance(kind, str):
+        if kind not in MAP_KIND_NAMES:
+            raise ValueError("zone statistics: kind is one of %s" % ", ".join(MAP_KIND_NAMES))
+        return MAP_KIND_NAMES.index(kind)
+    return int(kind)
+
+
+def _zone_labels(labels, n_zones):
+    lab = np.ascontiguousarray(labels, np.uint8)
+    n = int(lab.max()) if n_zones is None and lab.size else int(n_zones or 0)
+    return lab, n
+
+
+def host_zone_stats(map, labels, n_zones=None):
+    """PvAmdHostZoneStats: the zone statistics of include/planeverb_amd.h (PvAmdZoneStat) on the CPU -- map = float32
+    [gx, gy, *width] as Solver.<kind>() returns it, labels = uint8 [gx, gy] (0: no zone, 1 .. n_zones; n_zones None: the largest
+    label); a structured array (ZONE_STAT_DTYPE) of shape [n_zones, *width]"""
+    m = np.ascontiguousarray(map, np.float32)
+    lab, n = _zone_labels(labels, n_zones)
+    if m.ndim < 2 or lab.shape != m.shape[:2]:
+        raise ValueError("host_zone_stats: a map [gx, gy, ...] and labels [gx, gy]")
+    width = m.shape[2:]
+    planes = int(np.prod(width, dtype=np.int64))
+    out = np.zeros((max(n, 0), planes), ZONE_STAT_DTYPE)
+    _check(lib().PvAmdHostZoneStats(_f(m) if m.size else None, m.shape[0], m.shape[1], planes,
+                                    lab.ctypes.data_as(C.POINTER(C.c_ubyte)), n, out.ctypes.data_as(_vp)))
+    return out.reshape((n,) + width)
+
+
+def zone_labels_from_rects(dx, gx, gy, rects):
+    """PvAmdHostZoneRects: uint8 [gx, gy] -- cell (X, Y) gets j + 1 where rects[j] = (xmin, zmin, xmax, zmax) in metres holds
+    its centre ((X + 0.5) dx, (Y + 0.5) dx), float32, half-open; later rectangles overwrite earlier ones; 0 elsewhere"""
+    r = np.ascontiguousarray(rects, np.float32).reshape(-1, 4)
+    out = np.zeros((int(gx), int(gy)), np.uint8)
+    _check(lib().PvAmdHostZoneRects(float(dx), int(gx), int(gy), _f(r) if r.size else None, len(r),
+                                    out.ctypes.data_as(C.POINTER(C.c_ubyte))))
     return out
 
 
@@ -1956,6 +2015,48 @@ class Solver:
     def spectrum_at(self, pos):
         """float32 [n, 3] at an emitter position (the cell get_output reads); NaNs off the map"""
         return self._map_at(lib().PvAmdGetSpectrum, pos, len(self.spectrum_bins()), 3)
+
+    def set_zones(self, labels, n_zones=None):
+        """the zones zone_stats reduces over: labels = uint8 [gx, gy], 0 = no zone, 1 .. n_zones (at most ZONES_MAX; None: the
+        largest label), kept on the device across runs and geometry changes; labels = None clears them"""
+        if labels is None:
+            _check(lib().PvAmdSetZones(self._h, None, 0))
+            return
+        lab, n = _zone_labels(labels, n_zones)
+        if lab.shape != (self.gx, self.gy):
+            raise ValueError("set_zones: labels [gx, gy]")
+        _check(lib().PvAmdSetZones(self._h, lab.ctypes.data_as(C.POINTER(C.c_ubyte)), n))
+
+    def zones(self):
+        """(labels uint8 [gx, gy], n_zones) as set; (None, 0) when no zones are set"""
+        lab = np.zeros((self.gx, self.gy), np.uint8)
+        n = C.c_int(0)
+        _check(lib().PvAmdGetZones(self._h, lab.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(n)))
+        return (lab, n.value) if n.value else (None, 0)
+
+    def _zone_width(self, kind):
+        k = _map_kind(kind)
+        planes = lib().PvAmdZoneStatPlanes(self._h, k)
+        if planes < 0:
+            raise PlaneverbError(last_error())
+        per = {PVA_MAP_BAND_METRICS: 12, PVA_MAP_MODULATION: MODULATION_FREQS + 1, PVA_MAP_SPECTRUM: 3}.get(k)
+        return k, planes, ((planes // per, per) if per else (planes,))
+
+    def zone_stats(self, kind, with_ms=False):
+        """PvAmdComputeZoneStats: the statistics of the computed map of `kind` (a name of MAP_KIND_NAMES or a PVA_MAP_* constant)
+        over the zones of set_zones, reduced on the device -- a structured array (ZONE_STAT_DTYPE) of shape [n_zones, *width],
+        width as the kind's map has it; with_ms: (records, device milliseconds)"""
+        k, planes, width = self._zone_width(kind)
+        nz = C.c_int(0)
+        _check(lib().PvAmdGetZones(self._h, None, C.byref(nz)))
+        n = nz.value
+        out = np.zeros((max(n, 1), planes), ZONE_STAT_DTYPE)
+        ms = C.c_float(0.0)
+        got = lib().PvAmdComputeZoneStats(self._h, k, out.ctypes.data_as(_vp), out.size, C.byref(ms))
+        if got < 0:
+            raise PlaneverbError(last_error())
+        out = out[:n].reshape((n,) + width)
+        return (out, ms.value) if with_ms else out
 
     def pulse(self):
         """float32 [T]: the pulse table of a run (T = the run's steps; zero past the grid's own table)"""

@@ -22,6 +22,7 @@
 #include "pv_query_records.h"
 #include "pv_query_spectral.h"
 #include "pv_spectrum.h"
+#include "pv_zones.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
 #include "pv_bake.h"
 #include "pv_shard.h"
@@ -1540,6 +1541,54 @@ int PvAmdGetSpectrum(PvAmdSolver* h, float ex, float ey, float ez, float* out3n)
     return analysisGet(h, kMapSpectrum, "", __func__, ex, ez, out3n);
 } PV_API_CATCH(-1)
 
+// zone statistics (pv_zones.hip; the labels: pv_zones.h zoneLabelsError)
+static_assert(sizeof(PvAmdZoneStat) == sizeof(ZoneStat), "64 bytes");
+static_assert(PVA_MAP_ROOM_METRICS == kMapRoomMetrics && PVA_MAP_SPECTRUM == kMapSpectrum && PVA_MAP_SPECTRUM + 1 == kAnalysisKinds,
+              "the order of AnalysisKind");
+static_assert(PVA_ZONES_MAX == kZonesMax, "a lane per zone");
+
+static bool zoneKind(int kind) {
+    if (kind >= 0 && kind < kAnalysisKinds) return true;
+    g_lastError = "zone statistics: kind is one of PVA_MAP_*";
+    return false;
+}
+
+int PvAmdSetZones(PvAmdSolver* h, const unsigned char* labels, int nZones) try {
+    if (!h) {
+        g_lastError = "zone statistics: null solver handle";
+        return -1;
+    }
+    if (labels || nZones != 0) {
+        if (const char* e = zoneLabelsError(labels, (long long)h->spec.gx * h->spec.gy, nZones)) {
+            g_lastError = e;
+            return -1;
+        }
+    }
+    if (!analysisHandle(h, "zone statistics: ")) return -1;
+    return ret(h, h->s->setZones(labels, nZones));
+} PV_API_CATCH(-1)
+
+int PvAmdGetZones(PvAmdSolver* h, unsigned char* labels, int* nZones) try {
+    if (!analysisHandle(h, "zone statistics: ")) return -1;
+    const int n = h->s->zones(labels);
+    if (nZones) *nZones = n;
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdZoneStatPlanes(PvAmdSolver* h, int kind) try {
+    if (!zoneKind(kind) || !analysisHandle(h, "zone statistics: ")) return -1;
+    const int n = h->s->zoneStatPlanes((AnalysisKind)kind);
+    if (n < 0) g_lastError = "zone statistics: the kind's setting is missing (slots, bands or bins)";
+    return n;
+} PV_API_CATCH(-1)
+
+int PvAmdComputeZoneStats(PvAmdSolver* h, int kind, PvAmdZoneStat* out, int cap, float* ms) try {
+    if (!zoneKind(kind) || !analysisCall(h, "zone statistics: ", __func__, out)) return -1;
+    int count = 0;
+    if (!h->s->computeZoneStats((AnalysisKind)kind, out, cap, ms, &count)) return ret(h, false);
+    return count;
+} PV_API_CATCH(-1)
+
 int PvAmdCopyPulse(PvAmdSolver* h, float* out) try {
     if (!out || !ensure(h, true)) return -1;
     return ret(h, h->g ? h->g->copyPulse(out) : h->s->copyPulse(out));
@@ -2034,6 +2083,29 @@ int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const float* hz,
     spectrumTables(T, fs, hz, n, c.data(), s.data());
     spectrumSource(pulseT, T, c.data(), s.data(), n, src.data());
     spectrumOfIr(p, T, onset, c.data(), s.data(), n, src.data(), out3n);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostZoneStats(const float* map, int gx, int gy, int planes, const unsigned char* labels, int nZones, PvAmdZoneStat* out) try {
+    if (!map || !out || gx < 1 || gy < 1 || planes < 1 || (long long)gx * gy > INT_MAX) {
+        g_lastError = "zone statistics: PvAmdHostZoneStats: a map of gx x gy records of `planes` floats, gx, gy, planes >= 1, and an output of nZones x planes records";
+        return -1;
+    }
+    if (const char* e = zoneLabelsError(labels, (long long)gx * gy, nZones)) {
+        g_lastError = e;
+        return -1;
+    }
+    static_assert(sizeof(PvAmdZoneStat) == sizeof(ZoneStat), "64 bytes");
+    zoneStatsOfMap(map, gx, gy, planes, labels, nZones, reinterpret_cast<ZoneStat*>(out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostZoneRects(float dx, int gx, int gy, const float* rect4, int n, unsigned char* labels) try {
+    if (!labels || gx < 1 || gy < 1 || n < 0 || n > kZonesMax || (n > 0 && !rect4)) {
+        g_lastError = "zone statistics: PvAmdHostZoneRects: gx, gy >= 1, 0 .. 64 rectangles and gx x gy labels";
+        return -1;
+    }
+    zoneLabelsFromRects(dx, gx, gy, rect4, n, labels);
     return 0;
 } PV_API_CATCH(-1)
 

@@ -129,6 +129,12 @@ void launchRunFinish(const float* res, long long n, const long long* cellsHost, 
 // cell's offset inside a history plane; NaN where the cell has no onset in that run
 void launchRoomMetrics(const AnalyzeArgs& a, float* out, hipStream_t stream);
 
+// ---- pv_zones.hip: per-zone statistics of a computed map
+// the records (pv_zones.h ZoneStat, without std and the empty-zone values: zoneStatFinish) of one chunk of a map's planes for the
+// zones of a.labels: four launches, a.rows / a.rowM2 are scratch
+struct ZoneArgs;
+void launchZoneStats(const ZoneArgs& a, hipStream_t stream);
+
 // ---- pv_decay.hip: per-cell decay times
 // decay times (EDT, T20, T30) of the last completed run (pv_decay.hip): out = kDecayFloats planes of a.histPlane floats, indexed
 // by the cell's offset inside a history plane; NaN where the cell has no onset in that run.  twoLaunches: the two walks of the

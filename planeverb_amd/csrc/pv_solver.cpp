@@ -697,6 +697,8 @@ Solver::~Solver() {
         if (e) hipEventDestroy(e);
     for (float* p : {modTab_, specTab_, specPow_})
         if (p) hipFree(p);
+    for (unsigned char* p : {zoneLabels_, zoneScratch_})
+        if (p) hipFree(p);
     if (qrecHost_) hipHostFree(qrecHost_);
     if (qspecHost_) hipHostFree(qspecHost_);
     if (rqCellsHost_) hipHostFree(rqCellsHost_);

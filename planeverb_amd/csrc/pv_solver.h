@@ -340,6 +340,15 @@ public:
     int spectrumBins(float* hz, int cap) const;
     bool spectrumSource(float* out3n);
     bool computeSpectrum(float* ms);
+    // Zone statistics (pv_zones.hip; include/planeverb_amd.h PvAmdZoneStat): a label per result cell, 0 = no zone, 1 .. nZones;
+    // computeZoneStats reduces the valid map of one kind to nZones x planes records on the device -- no host copy of the map,
+    // nothing cached, no kind touched.  setZones: the caller has validated the labels (pv_zones.h zoneLabelsError); nullptr / 0
+    // clears; waits for a run in flight; the labels survive runs and geometry changes.  zoneStatPlanes: the planes of a kind under
+    // the current settings, -1 where its setting is missing
+    bool setZones(const unsigned char* labels, int nZones);
+    int zones(unsigned char* labels) const;
+    int zoneStatPlanes(AnalysisKind k) const;
+    bool computeZoneStats(AnalysisKind k, void* out, int cap, float* ms, int* count);
     bool copyPulse(float* out);
     bool copyMaterial(uint8_t* beta, float* R);
     bool freeFieldEnergyAt(int cellX, int cellY, int n, float r, float* out);
@@ -607,6 +616,15 @@ private:
     std::vector<SpecPass> specPasses_;
     float* specTab_ = nullptr;
     float* specPow_ = nullptr;
+    // zone statistics (pv_zones.h): the labels on the device and as given, and the pass's scratch -- per plane in flight, zone and
+    // result row one ZoneRow and one double (48 bytes), the planes dealt in chunks that keep it within kZoneScratchBytes (one
+    // plane's where that is more), then the nZones x planes records; grown on demand, kept
+    static constexpr size_t kZoneScratchBytes = 32u << 20;
+    unsigned char* zoneLabels_ = nullptr;
+    std::vector<unsigned char> zoneHost_;
+    int zoneCount_ = 0;
+    unsigned char* zoneScratch_ = nullptr;
+    size_t zoneScratchBytes_ = 0;
     size_t scratchCount_ = 0;
 
     // pinned host staging

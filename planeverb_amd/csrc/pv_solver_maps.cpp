@@ -21,6 +21,7 @@
 #include "pv_query_records.h"
 #include "pv_query_spectral.h"
 #include "pv_spectrum.h"
+#include "pv_zones.h"
 
 namespace pva {
 
@@ -208,6 +209,120 @@ bool Solver::analysisAt(AnalysisKind k, float ex, float ez, float* out) {
         return true;
     }
     return copyAnalysisBlock(k, cx, cy, 1, 1, out);
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// zone statistics (pv_zones.hip): one reduction for every kind, straight off the kind's device planes
+// ----------------------------------------------------------------------------------------------------------------
+
+bool Solver::setZones(const unsigned char* labels, int nZones) {
+    if (isSlab()) return fail("zone statistics: not available on a slab");
+    if (opt_.streaming) return fail("zone statistics: the full pressure history is not kept in streaming-analysis mode");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    if (nZones == 0) {
+        zoneCount_ = 0;
+        zoneHost_.clear();
+        return true;
+    }
+    const size_t cells = (size_t)g_.gx * (size_t)g_.gy;
+    if (!zoneLabels_ && !dalloc(&zoneLabels_, cells, false)) return false;
+    if (!hipOk(hipMemcpyAsync(zoneLabels_, labels, cells, hipMemcpyHostToDevice, stream_), "zone labels upload") ||
+        !hipOk(hipStreamSynchronize(stream_), "zone labels sync")) {
+        zoneCount_ = 0;  // (the device labels are neither the old nor the new ones)
+        zoneHost_.clear();
+        return false;
+    }
+    zoneHost_.assign(labels, labels + cells);
+    zoneCount_ = nZones;
+    return true;
+}
+
+int Solver::zones(unsigned char* labels) const {
+    const auto inUse = queue_.lockUse();  // (setZones changes both under it)
+    if (labels && zoneCount_) std::memcpy(labels, zoneHost_.data(), zoneHost_.size());
+    return zoneCount_;
+}
+
+int Solver::zoneStatPlanes(AnalysisKind k) const {
+    if (!analysisSettingPresent(k)) return -1;
+    switch (k) {
+        case kMapRoomMetrics: return kRoomMetricFloats;
+        case kMapDecayTimes: return kDecayFloats;
+        case kMapLateralFraction: return kLateralFloats;
+        case kMapEchoCriterion: return kEchoFloats;
+        case kMapEchogram: return echogramFloats(echoSlots_);
+        case kMapLobes: return lobesFloats(lobeEdgeCount_ + 1);
+        case kMapBandMetrics: return kBandFloats * (int)bandHz_.size();
+        case kMapModulation: return kModFloats * (int)bandHz_.size();
+        case kMapSpectrum: return kSpectrumFloats * (int)specHz_.size();
+        default: return -1;
+    }
+}
+
+bool Solver::computeZoneStats(AnalysisKind k, void* out, int cap, float* ms, int* count) {
+    if (isSlab()) return fail("zone statistics: not available on a slab");
+    if (opt_.streaming) return fail("zone statistics: the full pressure history is not kept in streaming-analysis mode");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight: it leaves no kind valid)
+    if (!zoneCount_) return fail("zone statistics: no zones set (PvAmdSetZones)");
+    if (!analysisReadable(k)) return fail("zone statistics: " + err_);
+    const AnalysisMap& m = maps_[k];
+    const int records = zoneCount_ * m.planes;
+    if (cap < records) return fail("zone statistics: PvAmdComputeZoneStats: the output holds fewer than nZones x planes records");
+    // scratch: the rows' records and m2 sums of one chunk of planes, then the zones' records
+    const size_t perPlane = (size_t)zoneCount_ * (size_t)g_.gx * (sizeof(ZoneRow) + sizeof(double));
+    const int chunk = (int)std::min<size_t>((size_t)m.planes, std::max<size_t>(1, kZoneScratchBytes / perPlane));
+    const size_t rowsBytes = (size_t)chunk * (size_t)zoneCount_ * (size_t)g_.gx * sizeof(ZoneRow), m2Bytes = perPlane * chunk - rowsBytes;
+    const size_t need = rowsBytes + m2Bytes + (size_t)records * sizeof(ZoneStat);
+    if (zoneScratchBytes_ < need) {
+        if (zoneScratch_) {
+            hipFree(zoneScratch_);
+            deviceBytes_ -= (long long)zoneScratchBytes_;
+            zoneScratch_ = nullptr;
+            zoneScratchBytes_ = 0;
+        }
+        if (!dalloc(&zoneScratch_, need, false)) return false;
+        zoneScratchBytes_ = need;
+    }
+    for (auto& e : mapEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    ZoneArgs a{};
+    a.histPlane = histPlane_;
+    a.labels = zoneLabels_;
+    a.gx = g_.gx;
+    a.gy = g_.gy;
+    a.nZones = zoneCount_;
+    a.wr0 = m.dyn.histRow0 - geo_.G;  // (the window as copyAnalysisBlock reads it)
+    a.wc0 = m.dyn.histCol0 - geo_.G;
+    a.wnr = histTilesX_ * rxi_;
+    a.wnc = histTilesY_ * wi_;
+    a.rxi = rxi_;
+    a.wi = wi_;
+    a.tilesY = m.dyn.histTilesY;
+    a.totalPlanes = m.planes;
+    a.rows = reinterpret_cast<ZoneRow*>(zoneScratch_);
+    a.rowM2 = reinterpret_cast<double*>(zoneScratch_ + rowsBytes);
+    a.out = reinterpret_cast<ZoneStat*>(zoneScratch_ + rowsBytes + m2Bytes);
+    hipEventRecord(mapEv_[0], stream_);
+    for (int p0 = 0; p0 < m.planes; p0 += chunk) {
+        a.map = m.dev + (size_t)p0 * (size_t)histPlane_;
+        a.plane0 = p0;
+        a.planes = std::min(chunk, m.planes - p0);
+        launchZoneStats(a, stream_);
+    }
+    hipEventRecord(mapEv_[1], stream_);
+    ZoneStat* recs = static_cast<ZoneStat*>(out);
+    if (!hipOk(hipGetLastError(), "zone statistics launch") ||
+        !hipOk(hipMemcpyAsync(recs, a.out, (size_t)records * sizeof(ZoneStat), hipMemcpyDeviceToHost, stream_), "zone statistics copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "zone statistics sync"))
+        return false;
+    if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
+    for (int i = 0; i < records; ++i) zoneStatFinish(&recs[i]);
+    *count = records;
+    return true;
 }
 
 // ----------------------------------------------------------------------------------------------------------------
