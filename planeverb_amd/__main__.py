@@ -203,8 +203,9 @@ def main(argv=None):
             s.set_query_records(kinds)
             s.set_query_spectral_records(spectral)
         s.run(a.listener)
-        qrec = {} if whole else dict((k, s.queried_records(k)) for k in (1, 2, 4, 8, 16, 32) if kinds & k)
-        qspec = {} if whole else dict((k, s.queried_spectral_records(k)) for k in (1, 2, 4) if spectral & k)
+        qrec = {} if whole else dict((k, s.queried_records(k)) for k in RECORD_KEYS if kinds & k)
+        qspec = {} if whole else dict((k, s.queried_spectral_records(k))
+                                      for k in (api.QSPEC_BAND_METRICS, api.QSPEC_MODULATION, api.QSPEC_SPECTRUM) if spectral & k)
         t = s.timings()
         out = {"scene": a.scene, "grid": [s.gx, s.gy], "T": s.T, "res": a.res, "dx": s.dx, "efree": s.efree,
                "listener": a.listener, "fdtd_ms": t.fdtdMs, "analysis_ms": t.analysisMs, "emitters": []}

@@ -1647,23 +1647,30 @@ class Solver:
         launch inside the run and straight into pinned host memory; 0 (the default) selects none and frees the block"""
         _check(lib().PvAmdSetQueryRecords(self._h, int(kinds)))
 
+    def _record_floats(self, floats, kind):
+        n = floats(self._h, int(kind))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return n
+
+    def _read_records(self, read, kind, shape):
+        """float32 [n_queries] + shape of ONE kind of either family, for the table the records follow"""
+        n = getattr(self, "_nrq", 0) or getattr(self, "_nq", 0)
+        out = np.empty((n,) + shape, np.float32)
+        _check(read(self._h, int(kind), _f(out) if n else None, n))
+        return out
+
     def query_record_kinds(self):
         return int(lib().PvAmdGetQueryRecordKinds(self._h))
 
     def query_record_floats(self, kind):
         """floats per query of ONE kind under the current settings (10, 8, 11, 1 + 3 nSlots, 10, 1 + 5 nW)"""
-        n = lib().PvAmdQueryRecordFloats(self._h, int(kind))
-        if n < 0:
-            raise PlaneverbError(last_error())
-        return n
+        return self._record_floats(lib().PvAmdQueryRecordFloats, kind)
 
     def queried_records(self, kind):
         """float32 [n_queries, floats] of ONE kind for the last run (waits for it; no GPU work): each row bit for bit what
         <kind>_at(position) returns after compute_<kind>() on the same run; NaN rows off the map and where no sound arrived"""
-        n = getattr(self, "_nrq", 0) or getattr(self, "_nq", 0)
-        out = np.empty((n, self.query_record_floats(kind)), np.float32)
-        _check(lib().PvAmdGetQueriedRecords(self._h, int(kind), _f(out) if n else None, n))
-        return out
+        return self._read_records(lib().PvAmdGetQueriedRecords, kind, (self.query_record_floats(kind),))
 
     def set_record_queries(self, positions):
         """positions of their own (<= RECORD_QUERIES_MAX) for the in-run records: while there are any, every following run
@@ -1684,20 +1691,14 @@ class Solver:
 
     def query_spectral_floats(self, kind):
         """floats per query of ONE kind under the current bands / bins (12 n, 15 n, 3 bins)"""
-        n = lib().PvAmdQuerySpectralFloats(self._h, int(kind))
-        if n < 0:
-            raise PlaneverbError(last_error())
-        return n
+        return self._record_floats(lib().PvAmdQuerySpectralFloats, kind)
 
     def queried_spectral_records(self, kind):
         """float32 [n_queries, n, 12], [n_queries, n, 15] or [n_queries, bins, 3] of ONE kind for the last run (waits for it; no
         GPU work): each row bit for bit what band_metrics_at / modulation_at / spectrum_at(position) return after the whole-map
         pass on the same run; NaN rows off the map and where no sound arrived"""
-        n = getattr(self, "_nrq", 0) or getattr(self, "_nq", 0)
         per = {QSPEC_BAND_METRICS: 12, QSPEC_MODULATION: 15, QSPEC_SPECTRUM: 3}.get(int(kind), 1)
-        out = np.empty((n, self.query_spectral_floats(kind) // per, per), np.float32)
-        _check(lib().PvAmdGetQueriedSpectralRecords(self._h, int(kind), _f(out) if n else None, n))
-        return out
+        return self._read_records(lib().PvAmdGetQueriedSpectralRecords, kind, (self.query_spectral_floats(kind) // per, per))
 
     def results(self):
         res = np.empty((self.gx, self.gy, 8), np.float32)

@@ -1114,41 +1114,59 @@ int PvAmdGetQueriedOutputs(PvAmdSolver* h, PlaneverbOutput* out, int n) try {
     return 0;
 } PV_API_CATCH(-1)
 
-// in-run query records (pv_query_records.hip): single whole-grid solvers only; every refusal says "query records: ..."
-static bool queryRecordsHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "query records: " + g_lastError;
-    return false;
+// In-run records of the registered queries, two families (pv_solver_records.cpp): single whole-grid solvers only.  `pre` is what
+// every refusal of a family's calls starts with, the member what serves the call for that family
+static bool analysisHandle(PvAmdSolver* h, const char* pre);
+static const char kQrecPre[] = "query records: ", kQspecPre[] = "spectral records: ";
+static_assert(PVA_QSPEC_BAND_METRICS == 1u << kQspecBandMetrics && PVA_QSPEC_MODULATION == 1u << kQspecModulation &&
+                  PVA_QSPEC_SPECTRUM == 1u << kQspecSpectrum,
+              "planeverb_amd.h vs pv_query_spectral.h");
+
+static int recordsSelect(PvAmdSolver* h, const char* pre, bool (Solver::*select)(unsigned), unsigned kinds) {
+    if (!analysisHandle(h, pre)) return -1;
+    return ret(h, (h->s->*select)(kinds));
+}
+
+static unsigned recordsKinds(PvAmdSolver* h, const char* pre, unsigned (Solver::*kinds)() const) {
+    if (!analysisHandle(h, pre)) return 0u;
+    return (h->s->*kinds)();
+}
+
+static int recordsFloats(PvAmdSolver* h, const char* pre, int (Solver::*floats)(unsigned), unsigned kind) {
+    if (!analysisHandle(h, pre)) return -1;
+    const int n = (h->s->*floats)(kind);
+    if (n < 0) ret(h, false);
+    return n;
+}
+
+static int recordsRead(PvAmdSolver* h, const char* pre, const char* fn, bool (Solver::*read)(unsigned, float*, int), unsigned kind,
+                       float* out, int nQueries) {
+    if (!analysisHandle(h, pre)) return -1;
+    if (nQueries < 0 || nQueries > kMaxRecordQueries || (nQueries > 0 && !out)) {
+        g_lastError = std::string(pre) + fn + ": 0 .. 1024 queries and an output buffer";
+        return -1;
+    }
+    return ret(h, (h->s->*read)(kind, out, nQueries));
 }
 
 int PvAmdSetQueryRecords(PvAmdSolver* h, unsigned kinds) try {
-    if (!queryRecordsHandle(h)) return -1;
-    return ret(h, h->s->setQueryRecords(kinds));
+    return recordsSelect(h, kQrecPre, &Solver::setQueryRecords, kinds);
 } PV_API_CATCH(-1)
 
 unsigned PvAmdGetQueryRecordKinds(PvAmdSolver* h) try {
-    if (!queryRecordsHandle(h)) return 0u;
-    return h->s->queryRecordKinds();
+    return recordsKinds(h, kQrecPre, &Solver::queryRecordKinds);
 } PV_API_CATCH(0u)
 
 int PvAmdQueryRecordFloats(PvAmdSolver* h, unsigned kind) try {
-    if (!queryRecordsHandle(h)) return -1;
-    const int n = h->s->queryRecordFloats(kind);
-    if (n < 0) ret(h, false);
-    return n;
+    return recordsFloats(h, kQrecPre, &Solver::queryRecordFloats, kind);
 } PV_API_CATCH(-1)
 
 int PvAmdGetQueriedRecords(PvAmdSolver* h, unsigned kind, float* out, int nQueries) try {
-    if (!queryRecordsHandle(h)) return -1;
-    if (nQueries < 0 || nQueries > kMaxRecordQueries || (nQueries > 0 && !out)) {
-        g_lastError = "query records: PvAmdGetQueriedRecords: 0 .. 1024 queries and an output buffer";
-        return -1;
-    }
-    return ret(h, h->s->queriedRecords(kind, out, nQueries));
+    return recordsRead(h, kQrecPre, __func__, &Solver::queriedRecords, kind, out, nQueries);
 } PV_API_CATCH(-1)
 
 int PvAmdSetRecordQueries(PvAmdSolver* h, const float* xyz, int n) try {
-    if (!queryRecordsHandle(h)) return -1;
+    if (!analysisHandle(h, kQrecPre)) return -1;
     if (n < 0 || n > kMaxRecordQueries || (n > 0 && !xyz)) {
         g_lastError = "query records: PvAmdSetRecordQueries: 0 .. 1024 positions (NULL only with 0)";
         return -1;
@@ -1156,40 +1174,20 @@ int PvAmdSetRecordQueries(PvAmdSolver* h, const float* xyz, int n) try {
     return ret(h, h->s->setRecordQueries(xyz, n));
 } PV_API_CATCH(-1)
 
-// in-run spectral records (pv_query_spectral.hip): single whole-grid solvers only; every refusal says "spectral records: ..."
-static_assert(PVA_QSPEC_BAND_METRICS == 1u << kQspecBandMetrics && PVA_QSPEC_MODULATION == 1u << kQspecModulation &&
-                  PVA_QSPEC_SPECTRUM == 1u << kQspecSpectrum,
-              "planeverb_amd.h vs pv_query_spectral.h");
-static bool spectralRecordsHandle(PvAmdSolver* h) {
-    if (wholeGrid(h) && ensure(h)) return true;
-    g_lastError = "spectral records: " + g_lastError;
-    return false;
-}
-
 int PvAmdSetQuerySpectralRecords(PvAmdSolver* h, unsigned kinds) try {
-    if (!spectralRecordsHandle(h)) return -1;
-    return ret(h, h->s->setQuerySpectralRecords(kinds));
+    return recordsSelect(h, kQspecPre, &Solver::setQuerySpectralRecords, kinds);
 } PV_API_CATCH(-1)
 
 unsigned PvAmdGetQuerySpectralKinds(PvAmdSolver* h) try {
-    if (!spectralRecordsHandle(h)) return 0u;
-    return h->s->querySpectralKinds();
+    return recordsKinds(h, kQspecPre, &Solver::querySpectralKinds);
 } PV_API_CATCH(0u)
 
 int PvAmdQuerySpectralFloats(PvAmdSolver* h, unsigned kind) try {
-    if (!spectralRecordsHandle(h)) return -1;
-    const int n = h->s->querySpectralFloats(kind);
-    if (n < 0) ret(h, false);
-    return n;
+    return recordsFloats(h, kQspecPre, &Solver::querySpectralFloats, kind);
 } PV_API_CATCH(-1)
 
 int PvAmdGetQueriedSpectralRecords(PvAmdSolver* h, unsigned kind, float* out, int nQueries) try {
-    if (!spectralRecordsHandle(h)) return -1;
-    if (nQueries < 0 || nQueries > kMaxRecordQueries || (nQueries > 0 && !out)) {
-        g_lastError = "spectral records: PvAmdGetQueriedSpectralRecords: 0 .. 1024 queries and an output buffer";
-        return -1;
-    }
-    return ret(h, h->s->queriedSpectralRecords(kind, out, nQueries));
+    return recordsRead(h, kQspecPre, __func__, &Solver::queriedSpectralRecords, kind, out, nQueries);
 } PV_API_CATCH(-1)
 
 int PvAmdCopyResults(PvAmdSolver* h, float* res8, float* delay) try {

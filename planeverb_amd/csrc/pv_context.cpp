@@ -619,11 +619,6 @@ void ensureRoom(V& v, size_t k) {
 
 namespace {
 const char kRecPrefix[] = "emission records: ";
-int recBit(unsigned kind) {  // the bit of a mask that names ONE kind, or -1
-    for (int k = 0; k < kQueryRecordKinds; ++k)
-        if (kind == (1u << k)) return k;
-    return -1;
-}
 inline long long loadCell(const long long* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 }  // namespace
 
@@ -832,7 +827,7 @@ unsigned Context::emissionRecordKinds() {
 }
 
 int Context::emissionRecordFloats(unsigned kind) {
-    const int b = recBit(kind);
+    const int b = oneKindBit(kind, kQueryRecordKinds);
     if (b < 0) return -1;
     for (;;) {
         const uint64_t s1 = pubSeq_.load(std::memory_order_acquire);
@@ -857,7 +852,7 @@ int Context::emissionRecordCells() {
 }
 
 int Context::emissionRecord(int id, unsigned kind, float* out, int cap) {
-    const int b = recBit(kind);
+    const int b = oneKindBit(kind, kQueryRecordKinds);
     if (b < 0 || !out) return -1;
     const GridSpec& g = solver_->spec();
     float rec[kRecMaxFloats];

@@ -18,6 +18,13 @@ constexpr unsigned kQueryRecordMask = (1u << kQueryRecordKinds) - 1u;
 // queries of one launch: groups of 64 on blockIdx.y (PVA_RECORD_QUERIES_MAX)
 constexpr int kMaxRecordQueries = 1024;
 
+// the bit of a mask that names ONE of a family's `kinds` kinds, or -1
+inline int oneKindBit(unsigned kind, int kinds) {
+    for (int k = 0; k < kinds; ++k)
+        if (kind == (1u << k)) return k;
+    return -1;
+}
+
 struct QueryRecordArgs {
     const long long* cells;  // nq result-cell indices (-1: off the map), pinned host memory
     float* out;              // pinned host memory

@@ -26,8 +26,6 @@
 #include "pv_lateral.h"
 #include "pv_lobes.h"
 #include "pv_metrics.h"
-#include "pv_query_records.h"
-#include "pv_query_spectral.h"
 #include "pv_spectrum.h"
 
 namespace pva {
@@ -699,8 +697,8 @@ Solver::~Solver() {
         if (p) hipFree(p);
     for (unsigned char* p : {zoneLabels_, zoneScratch_})
         if (p) hipFree(p);
-    if (qrecHost_) hipHostFree(qrecHost_);
-    if (qspecHost_) hipHostFree(qspecHost_);
+    for (RecordSet& r : recs_)
+        if (r.host) hipHostFree(r.host);
     if (rqCellsHost_) hipHostFree(rqCellsHost_);
     if (layerList_) hipFree(layerList_);
     if (layerTab_) hipFree(layerTab_);
@@ -2133,8 +2131,7 @@ bool Solver::beginRun(PathRun::Kind kind, int lcx, int lcy, bool withPulse, floa
     if (pendingTimings_ && !sync()) return false;
     invalidateAnalysisMaps();  // (the history the records were made from is about to be overwritten)
     lastRun_ = LastRun::Failed;  // (until sync() has seen this run through)
-    qrecRun_ = QrecRun::None;    // (the pinned block is about to be overwritten, or this run leaves no records)
-    qspecRun_ = QrecRun::None;
+    for (RecordSet& r : recs_) r.run = RecordSet::Run::None;  // (the pinned block is about to be overwritten, or this run leaves no records)
     if (!applyGeometry()) return false;
     PathRun r;
     r.kind = kind;
@@ -2651,8 +2648,8 @@ bool Solver::sync() {
         }
         if (flag) return fail("pressure history window overflow (a tile outside the window became non-zero)");
         lastRun_ = plan_.kind == PathRun::Raw ? LastRun::None : LastRun::Ok;  // (raw stepping records no history)
-        if (qrecRun_ == QrecRun::Pending) qrecRun_ = QrecRun::Ok;
-        if (qspecRun_ == QrecRun::Pending) qspecRun_ = QrecRun::Ok;
+        for (RecordSet& r : recs_)
+            if (r.run == RecordSet::Run::Pending) r.run = RecordSet::Run::Ok;
     }
     return true;
 }
@@ -2689,351 +2686,6 @@ bool Solver::getOutput(float ex, float ey, float ez, float out8[8], bool* valid)
     launchGatherOutput(res_, (long long)g_.gx * g_.gy, (long long)idx, outHost_, farInfo(), stream_);
     if (!hipOk(hipStreamSynchronize(stream_), "output sync")) return false;
     for (int k = 0; k < 8; ++k) out8[k] = outHost_[k];
-    return true;
-}
-
-bool Solver::setOutputQueries(const float* xyz, int n) {
-    if (n < 0 || n > kMaxQueries) return fail("at most 64 output queries");
-    if (pendingTimings_ && !sync()) return false;  // the gather of a run in flight still reads the cell table
-    for (int i = 0; i < n; ++i) {
-        int cx, cy;
-        qCellsHost_[i] = resultCell(g_, xyz[3 * i], xyz[3 * i + 2], &cx, &cy) ? (long long)cx * g_.gy + cy : -1;
-    }
-    numQueries_ = n;
-    if (numRecQueries_ == 0) qrecRun_ = qspecRun_ = QrecRun::None;  // (the records in the pinned blocks belong to the queries of before)
-    return true;
-}
-
-bool Solver::setRecordQueries(const float* xyz, int n) {
-    if (n < 0 || n > kMaxRecordQueries) return fail("query records: at most 1024 record queries");
-    if (n > 0 && !xyz) return fail("query records: no positions");
-    if (n > 0 && isSlab()) return fail("query records: not available on a slab");
-    if (n > 0 && opt_.streaming) return fail("query records: the full pressure history is not kept in streaming-analysis mode");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // the launch of a run in flight still reads the cell table
-    if (n > rqCap_) {
-        long long* t = nullptr;
-        if (!hipOk(hipHostMalloc((void**)&t, (size_t)n * sizeof(long long)), "hipHostMalloc")) return false;
-        if (rqCellsHost_) hipHostFree(rqCellsHost_);
-        rqCellsHost_ = t;
-        rqCap_ = n;
-    }
-    if (!growQrecBlock(qrecKinds_, n) || !growQspecBlock(qspecKinds_, n)) return false;
-    for (int i = 0; i < n; ++i) {
-        int cx, cy;
-        rqCellsHost_[i] = resultCell(g_, xyz[3 * i], xyz[3 * i + 2], &cx, &cy) ? (long long)cx * g_.gy + cy : -1;
-    }
-    numRecQueries_ = n;
-    qrecRun_ = qspecRun_ = QrecRun::None;  // (the records in the pinned blocks belong to the table of before)
-    return true;
-}
-
-// last kernel of a run: its status words into pinned memory (sync() then needs no copy and no second synchronisation)
-void Solver::enqueueRunStatus() {
-    launchRunStatus(errFlag_, activeCount_, plan_.oneXcd ? resFlags_ + runTiles_ + 1 : nullptr, statusHost_, stream_);
-    statusQueued_ = true;
-}
-
-void Solver::enqueueQueries() {
-    enqueueQueryRecords();
-    enqueueQuerySpectralRecords();
-    if (numQueries_ > 0 && !opt_.skipAnalysis)
-        launchGatherQueries(res_, (long long)g_.gx * g_.gy, qCellsHost_, numQueries_, qOutHost_, farInfo(), stream_);
-    enqueueTap();
-}
-
-void Solver::enqueueTap() {
-    if (tap_ && !opt_.skipAnalysis) {
-        const Block b = curWindow();
-        tap_->afterRun(res_, delay_, (long long)g_.gx * g_.gy, g_.gy, b.r0, b.c0, b.nr, b.nc, stream_);
-    }
-}
-
-// after sync(): the registered queries' outputs of the last run, straight from pinned memory
-bool Solver::queriedOutputs(float* out8n, unsigned char* valid, int n) {
-    if (n != numQueries_) return fail("queriedOutputs: count differs from the registered queries");
-    if (pendingTimings_ && !sync()) return false;
-    for (int i = 0; i < n; ++i) {
-        valid[i] = qCellsHost_[i] >= 0;
-        for (int k = 0; k < 8; ++k) out8n[8 * i + k] = qOutHost_[8 * i + k];
-    }
-    return true;
-}
-
-// ---- in-run query records (pv_query_records.hip)
-namespace {
-// floats per query of kind bit k under the given settings; -1 where the kind's setting is missing
-int qrecFloatsOf(int k, int echoSlots, int lobeWindows) {
-    switch (k) {
-        case kQrecRoomMetrics: return kRoomMetricFloats;
-        case kQrecDecay: return kDecayFloats;
-        case kQrecLateral: return kLateralFloats;
-        case kQrecEchogram: return echoSlots > 0 ? echogramFloats(echoSlots) : -1;
-        case kQrecEchoCriterion: return kEchoFloats;
-        case kQrecLobes: return lobesFloats(lobeWindows);
-    }
-    return -1;
-}
-// floats per query of the pinned block: every selected kind at its largest setting, so that a later change of slots or windows
-// needs no allocation
-size_t qrecBlockFloats(unsigned kinds) {
-    size_t cap = 0;
-    for (int k = 0; k < kQueryRecordKinds; ++k)
-        if ((kinds >> k) & 1u) cap += (size_t)qrecFloatsOf(k, kEchogramMaxSlots, kLobesMaxWindows);
-    return cap;
-}
-int qrecBit(unsigned kind) {  // the bit of a mask that names ONE kind, or -1
-    for (int k = 0; k < kQueryRecordKinds; ++k)
-        if (kind == (1u << k)) return k;
-    return -1;
-}
-}  // namespace
-
-bool Solver::setQueryRecords(unsigned kinds) {
-    if (kinds & ~kQueryRecordMask) return fail("query records: unknown kind bit (PVA_QREC_*)");
-    if (kinds) {
-        if (isSlab()) return fail("query records: not available on a slab");
-        if (opt_.streaming) return fail("query records: the full pressure history is not kept in streaming-analysis mode");
-        if (opt_.skipAnalysis) return fail("query records: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-        if ((kinds & (1u << kQrecEchogram)) && !echoSlots_) return fail("query records: echogram: no slots set (PvAmdSetEchogram)");
-        if ((kinds & (1u << kQrecEchoCriterion)) && !echoFsOk((int)g_.fs))
-            return fail("query records: echo: the sampling rate gives a speech lag below one step ((int)(0.009f * (float)fs) < 1)");
-        LobeEdges ed;
-        if ((kinds & (1u << kQrecLobes)) && !lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, (int)g_.fs, &ed))
-            return fail("query records: lobes: the default windows (10 ms, 80 ms) need a sampling rate of 100 Hz or more (PvAmdSetLobeWindows)");
-    }
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // the launch of a run in flight still writes the pinned block
-    if (kinds == qrecKinds_) return true;
-    const size_t cap = qrecBlockFloats(kinds);
-    const int queries = numRecQueries_ > kMaxQueries ? numRecQueries_ : kMaxQueries;
-    float* block = nullptr;
-    if (cap && !hipOk(hipHostMalloc((void**)&block, cap * queries * sizeof(float)), "hipHostMalloc")) return false;
-    if (qrecHost_) hipHostFree(qrecHost_);
-    qrecHost_ = block;
-    qrecBlockQueries_ = block ? queries : 0;
-    qrecKinds_ = kinds;
-    qrecRun_ = QrecRun::None;
-    return true;
-}
-
-// the pinned block of the selected kinds with room for `queries` queries (no run in flight); nothing while no kind is selected
-bool Solver::growQrecBlock(unsigned kinds, int queries) {
-    if (!kinds || queries <= qrecBlockQueries_) return true;
-    float* block = nullptr;
-    if (!hipOk(hipHostMalloc((void**)&block, qrecBlockFloats(kinds) * queries * sizeof(float)), "hipHostMalloc")) return false;
-    if (qrecHost_) hipHostFree(qrecHost_);
-    qrecHost_ = block;
-    qrecBlockQueries_ = queries;
-    qrecRun_ = QrecRun::None;
-    return true;
-}
-
-int Solver::queryRecordFloats(unsigned kind) {
-    const int k = qrecBit(kind);
-    if (k < 0) {
-        fail("query records: exactly one kind (PVA_QREC_*)");
-        return -1;
-    }
-    const int n = qrecFloatsOf(k, echoSlots_, lobeEdgeCount_ + 1);
-    if (n < 0) fail("query records: echogram: no slots set (PvAmdSetEchogram)");
-    return n;
-}
-
-// The settings are those of this moment: PvAmdSetEchogram / PvAmdSetLobeWindows wait for a run in flight, and the stamp keeps the
-// layout the run was enqueued with
-void Solver::enqueueQueryRecords() {
-    if (!qrecKinds_ || opt_.skipAnalysis) return;
-    QueryRecordArgs q{};
-    const int nq = qrecQueries();
-    q.cells = numRecQueries_ > 0 ? rqCellsHost_ : qCellsHost_;
-    q.out = qrecHost_;
-    q.nq = nq;
-    q.kinds = qrecKinds_;
-    const int fs = (int)g_.fs;
-    int off = 0;
-    for (int k = 0; k < kQueryRecordKinds; ++k) {
-        const bool on = (qrecKinds_ >> k) & 1u;
-        q.floats[k] = on ? qrecFloatsOf(k, echoSlots_, lobeEdgeCount_ + 1) : 0;
-        q.offset[k] = off;
-        off += q.floats[k] * nq;
-        qrecRunFloats_[k] = q.floats[k];
-        qrecRunOffset_[k] = q.offset[k];
-    }
-    q.n50 = roomMetricsN50(fs);
-    q.n80 = roomMetricsN80(fs);
-    q.n5 = lateralN5(fs);
-    q.latN80 = lateralN80(fs);
-    q.tailN = decayTailN(fs);
-    q.ns = echoSteps_;
-    q.nSlots = echoSlots_;
-    q.nDs = echoSpeechLag(fs);
-    q.nDm = echoMusicLag(fs);
-    q.nLs = echoSpeechLimit(fs);
-    q.nLm = echoMusicLimit(fs);
-    lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, fs, &q.ed);  // (valid: checked where the kind was selected and where the windows are set)
-    q.nW = lobeEdgeCount_ + 1;
-    qrecRunKinds_ = qrecKinds_;
-    qrecRunQueries_ = nq;
-    qrecRun_ = QrecRun::Pending;
-    if (nq > 0) launchQueryRecords(analyzeArgs(lastLx_, lastLz_), q, stream_);
-}
-
-// after the run has been waited for: the records of one kind, straight from pinned memory
-bool Solver::queriedRecords(unsigned kind, float* out, int n) {
-    const int k = qrecBit(kind);
-    if (k < 0) return fail("query records: exactly one kind (PVA_QREC_*)");
-    if (!(qrecKinds_ & kind)) return fail("query records: the kind is not selected (PvAmdSetQueryRecords)");
-    if (n != qrecQueries()) return fail("query records: count differs from the registered queries");
-    if (pendingTimings_ && !sync()) return false;
-    if (lastRun_ == LastRun::Failed) return fail("query records: the last run ended in error");
-    if (qrecRun_ != QrecRun::Ok || qrecRunKinds_ != qrecKinds_ || qrecRunQueries_ != qrecQueries() ||
-        qrecRunFloats_[k] != qrecFloatsOf(k, echoSlots_, lobeEdgeCount_ + 1))
-        return fail("query records: no completed run since the kinds, the queries or the settings changed");
-    const float* src = qrecHost_ + qrecRunOffset_[k];
-    for (int i = 0; i < n * qrecRunFloats_[k]; ++i) out[i] = src[i];
-    return true;
-}
-
-// ---- in-run spectral records (pv_query_spectral.hip): the twins of the six kinds' functions above
-namespace {
-// floats per query of the pinned block: every selected kind at its largest setting (kBandsMax bands, kSpectrumMaxBins bins), so
-// that a later change of bands or bins needs no allocation
-size_t qspecBlockFloats(unsigned kinds) {
-    size_t cap = 0;
-    if (kinds & (1u << kQspecBandMetrics)) cap += (size_t)kBandFloats * kBandsMax;
-    if (kinds & (1u << kQspecModulation)) cap += (size_t)kModFloats * kBandsMax;
-    if (kinds & (1u << kQspecSpectrum)) cap += (size_t)kSpectrumFloats * kSpectrumMaxBins;
-    return cap;
-}
-int qspecBit(unsigned kind) {  // the bit of a mask that names ONE kind, or -1
-    for (int k = 0; k < kQuerySpectralKinds; ++k)
-        if (kind == (1u << k)) return k;
-    return -1;
-}
-}  // namespace
-
-int Solver::qspecFloatsOf(int k) const {
-    const int n = (int)bandHz_.size(), bins = (int)specHz_.size();
-    switch (k) {
-        case kQspecBandMetrics: return n > 0 ? kBandFloats * n : -1;
-        case kQspecModulation: return n > 0 ? kModFloats * n : -1;
-        case kQspecSpectrum: return bins > 0 ? kSpectrumFloats * bins : -1;
-    }
-    return -1;
-}
-
-bool Solver::setQuerySpectralRecords(unsigned kinds) {
-    if (kinds & ~kQuerySpectralMask) return fail("spectral records: unknown kind bit (PVA_QSPEC_*)");
-    if (kinds) {
-        if (isSlab()) return fail("spectral records: not available on a slab");
-        if (opt_.streaming) return fail("spectral records: the full pressure history is not kept in streaming-analysis mode");
-        if (opt_.skipAnalysis) return fail("spectral records: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-        if ((kinds & kQspecBandKinds) && bandHz_.empty()) return fail("spectral records: no bands set (PvAmdSetBands)");
-        if ((kinds & (1u << kQspecSpectrum)) && specHz_.empty()) return fail("spectral records: no bins set (PvAmdSetSpectrumBins)");
-    }
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // the launch of a run in flight still writes the pinned block
-    if (kinds == qspecKinds_) return true;
-    // (the spectrum's tables are on the device from PvAmdSetSpectrumBins on; the modulation's are made valid here)
-    if ((kinds & (1u << kQspecModulation)) && !ensureModTable()) return false;
-    const size_t cap = qspecBlockFloats(kinds);
-    const int queries = numRecQueries_ > kMaxQueries ? numRecQueries_ : kMaxQueries;
-    float* block = nullptr;
-    if (cap && !hipOk(hipHostMalloc((void**)&block, cap * queries * sizeof(float)), "hipHostMalloc")) return false;
-    if (qspecHost_) hipHostFree(qspecHost_);
-    qspecHost_ = block;
-    qspecBlockQueries_ = block ? queries : 0;
-    qspecKinds_ = kinds;
-    qspecRun_ = QrecRun::None;
-    return true;
-}
-
-// the pinned block of the selected kinds with room for `queries` queries (no run in flight); nothing while no kind is selected
-bool Solver::growQspecBlock(unsigned kinds, int queries) {
-    if (!kinds || queries <= qspecBlockQueries_) return true;
-    float* block = nullptr;
-    if (!hipOk(hipHostMalloc((void**)&block, qspecBlockFloats(kinds) * queries * sizeof(float)), "hipHostMalloc")) return false;
-    if (qspecHost_) hipHostFree(qspecHost_);
-    qspecHost_ = block;
-    qspecBlockQueries_ = queries;
-    qspecRun_ = QrecRun::None;
-    return true;
-}
-
-int Solver::querySpectralFloats(unsigned kind) {
-    const int k = qspecBit(kind);
-    if (k < 0) {
-        fail("spectral records: exactly one kind (PVA_QSPEC_*)");
-        return -1;
-    }
-    const int n = qspecFloatsOf(k);
-    if (n < 0) fail(k == kQspecSpectrum ? "spectral records: no bins set (PvAmdSetSpectrumBins)" : "spectral records: no bands set (PvAmdSetBands)");
-    return n;
-}
-
-// The settings are those of this moment: PvAmdSetBands, PvAmdSetModulationFrequencies and PvAmdSetSpectrumBins wait for a run in
-// flight and leave the device tables valid, and the stamp keeps the layout the run was enqueued with.  A kind whose tables are
-// missing (an upload that failed in a setter) is left out: its stamp then differs from the settings and its read-back is refused
-void Solver::enqueueQuerySpectralRecords() {
-    if (!qspecKinds_ || opt_.skipAnalysis) return;
-    QuerySpectralArgs q{};
-    const int nq = qrecQueries();
-    q.cells = numRecQueries_ > 0 ? rqCellsHost_ : qCellsHost_;
-    q.out = qspecHost_;
-    q.nq = nq;
-    const int n = (int)bandHz_.size(), B = bandMetricsBlock();
-    q.nBands = n;
-    for (int j = 0; j < n; ++j)
-        for (int k = 0; k < kBandCoefs; ++k) q.coefs[j][k] = bandCoefs_[(size_t)j * kBandCoefs + k];
-    const bool on[kQuerySpectralKinds] = {(qspecKinds_ & (1u << kQspecBandMetrics)) && n > 0,
-                                          (qspecKinds_ & (1u << kQspecModulation)) && n > 0 && modTab_ && modTabValid_,
-                                          (qspecKinds_ & (1u << kQspecSpectrum)) && !specPasses_.empty() && specTab_ && specPow_ &&
-                                              (int)specPasses_.size() <= kQspecMaxSlices};
-    q.items[kQspecBandMetrics] = on[kQspecBandMetrics] ? (n + B - 1) / B : 0;
-    q.items[kQspecModulation] = on[kQspecModulation] ? n : 0;
-    q.items[kQspecSpectrum] = on[kQspecSpectrum] ? (int)specPasses_.size() : 0;
-    int off = 0, items = 0;
-    for (int k = 0; k < kQuerySpectralKinds; ++k) {
-        q.floats[k] = on[k] ? qspecFloatsOf(k) : 0;
-        q.offset[k] = off;
-        off += q.floats[k] * nq;
-        items += q.items[k];
-        qspecRunFloats_[k] = q.floats[k];
-        qspecRunOffset_[k] = q.offset[k];
-    }
-    const int fs = (int)g_.fs;
-    q.tailN = decayTailN(fs);
-    q.n50 = roomMetricsN50(fs);
-    q.n80 = roomMetricsN80(fs);
-    q.modTab = modTab_ ? modTab_ + (size_t)kModTablePad * kModRowStride : nullptr;
-    q.specTab = specTab_;
-    q.specPow = specPow_;
-    for (int i = 0; i < q.items[kQspecSpectrum]; ++i) {
-        const SpecPass& ps = specPasses_[(size_t)i];
-        q.slice[i] = QuerySpectralSlice{ps.bin0, ps.bins, ps.block, (long long)ps.tabOff};
-    }
-    qspecRunKinds_ = qspecKinds_;
-    qspecRunQueries_ = nq;
-    qspecRun_ = QrecRun::Pending;
-    if (nq > 0 && items > 0) launchQuerySpectral(analyzeArgs(lastLx_, lastLz_), q, stream_);
-}
-
-// after the run has been waited for: the records of one kind, straight from pinned memory
-bool Solver::queriedSpectralRecords(unsigned kind, float* out, int n) {
-    const int k = qspecBit(kind);
-    if (k < 0) return fail("spectral records: exactly one kind (PVA_QSPEC_*)");
-    if (!(qspecKinds_ & kind)) return fail("spectral records: the kind is not selected (PvAmdSetQuerySpectralRecords)");
-    if (n != qrecQueries()) return fail("spectral records: count differs from the registered queries");
-    if (pendingTimings_ && !sync()) return false;
-    if (lastRun_ == LastRun::Failed) return fail("spectral records: the last run ended in error");
-    if (qspecRun_ != QrecRun::Ok || qspecRunKinds_ != qspecKinds_ || qspecRunQueries_ != qrecQueries() || qspecRunFloats_[k] != qspecFloatsOf(k))
-        return fail("spectral records: no completed run since the kinds, the queries or the settings changed");
-    const float* src = qspecHost_ + qspecRunOffset_[k];
-    for (int i = 0; i < n * qspecRunFloats_[k]; ++i) out[i] = src[i];
     return true;
 }
 

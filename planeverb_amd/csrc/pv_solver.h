@@ -16,6 +16,7 @@
 
 #include "pv_core.h"
 #include "pv_device.h"
+#include "pv_query_spectral.h"
 
 namespace pva {
 
@@ -232,33 +233,31 @@ public:
     static constexpr int kMaxQueries = 64;
     bool setOutputQueries(const float* xyz, int n);
     bool queriedOutputs(float* out8n, unsigned char* valid, int n);
-    // In-run analysis records of the registered queries' cells (pv_query_records.hip; include/planeverb_amd.h
-    // PvAmdSetQueryRecords): every following run computes the selected kinds (a mask of bits kQrec*, pv_query_records.h) for the
-    // queries' cells in ONE launch behind its analysis and in front of its last kernel, straight into pinned host memory; the
-    // records are bit for bit the whole-map passes' at the same cells.  kinds = 0 (the default): nothing is launched and the
-    // pinned block is freed.  Both setters wait for a run in flight.  queriedRecords: n x queryRecordFloats(kind) floats of ONE
-    // kind, after the run has been waited for; refused until a run enqueued under the current kinds, queries and settings has
-    // completed without error
-    bool setQueryRecords(unsigned kinds);
-    unsigned queryRecordKinds() const { return qrecKinds_; }
-    int queryRecordFloats(unsigned kind);  // -1: not one kind, or its setting is missing
-    bool queriedRecords(unsigned kind, float* out, int n);
+    // In-run analysis records of the registered queries' cells, in two families with a selector, a pinned block, a launch and a
+    // stamp each (pv_solver_records.cpp): the six time-domain kinds (bits kQrec*, pv_query_records.h / .hip; PvAmdSetQueryRecords)
+    // and, directly behind them, the three frequency-resolved ones (bits kQspec*, pv_query_spectral.h / .hip;
+    // PvAmdSetQuerySpectralRecords).  Every following run computes a family's selected kinds for the queries' cells in ONE launch
+    // behind its analysis and in front of its last kernel, straight into pinned host memory; the records are bit for bit the
+    // whole-map passes' at the same cells, under the settings in force when the run was enqueued.  kinds = 0 (the default): nothing
+    // is launched and the block is freed.  Every setter waits for a run in flight.  queried...Records: n x ...Floats(kind) floats of
+    // ONE kind, after the run has been waited for; refused until a run enqueued under the current kinds, queries and settings has
+    // completed without error.  The spectral kinds' device tables are made valid in the setters, never on the enqueue path
+    enum RecordFamily { kRecTime = 0, kRecSpectral = 1, kRecordFamilies = 2 };
+    bool setQueryRecords(unsigned kinds) { return selectRecords(kRecTime, kinds); }
+    unsigned queryRecordKinds() const { return recs_[kRecTime].kinds; }
+    int queryRecordFloats(unsigned kind) { return recordFloats(kRecTime, kind); }  // -1: not one kind, or its setting is missing
+    bool queriedRecords(unsigned kind, float* out, int n) { return readRecords(kRecTime, kind, out, n); }
+    bool setQuerySpectralRecords(unsigned kinds) { return selectRecords(kRecSpectral, kinds); }
+    unsigned querySpectralKinds() const { return recs_[kRecSpectral].kinds; }
+    int querySpectralFloats(unsigned kind) { return recordFloats(kRecSpectral, kind); }
+    bool queriedSpectralRecords(unsigned kind, float* out, int n) { return readRecords(kRecSpectral, kind, out, n); }
     // Record queries: up to kMaxRecordQueries (pv_query_records.h) positions of their own, mapped in the given order as
     // setOutputQueries maps them.  While n > 0 the in-run records are computed for THESE cells instead of the output queries'
-    // (64 queries per wave, one more block row per 64), and queriedRecords takes this n; the eight-output gather keeps serving
-    // the output queries.  n = 0, the default, returns to the output queries.  The pinned cell table and the record block grow to
+    // (64 queries per wave, one more block row per 64), and queried...Records take this n; the eight-output gather keeps serving
+    // the output queries.  n = 0, the default, returns to the output queries.  The pinned cell table and the record blocks grow to
     // the registered count.  Waits for a run in flight; a change invalidates the records until the next run
     bool setRecordQueries(const float* xyz, int n);
     int recordQueries() const { return numRecQueries_; }
-    // In-run FREQUENCY-RESOLVED records of the same cells (pv_query_spectral.hip; PvAmdSetQuerySpectralRecords): band metrics,
-    // modulation and spectrum, a mask of bits kQspec* (pv_query_spectral.h) with a selector, a pinned block and a launch of their
-    // own, directly behind the launch above.  Everything else as setQueryRecords ... queriedRecords; the records follow the bands,
-    // the modulation frequencies and the bins in force when the run was enqueued, and a change of those invalidates them until
-    // the next run has completed.  The device tables are made valid here and in the setters, never on the enqueue path
-    bool setQuerySpectralRecords(unsigned kinds);
-    unsigned querySpectralKinds() const { return qspecKinds_; }
-    int querySpectralFloats(unsigned kind);  // -1: not one kind, or its bands / bins are not set
-    bool queriedSpectralRecords(unsigned kind, float* out, int n);
     bool copyResults(float* res8, float* delay);
     // the block [r0, r0 + nr) x [c0, c0 + nc) of the result map (AoS records) and of the onset map, row-major nr x nc
     bool copyResultsBlock(int r0, int c0, int nr, int nc, float* res8, float* delay);
@@ -637,31 +636,41 @@ private:
     float* qOutHost_ = nullptr;        // kMaxQueries x 8 floats
     int numQueries_ = 0;
     void enqueueQueries();
-    // in-run query records: the kinds, the pinned block (sized for the selected kinds' largest settings) and the stamp of the run
-    // whose records it holds -- the layout that run was enqueued with, pending until sync() has seen the run through
-    unsigned qrecKinds_ = 0;
-    float* qrecHost_ = nullptr;
-    enum class QrecRun { None, Pending, Ok } qrecRun_ = QrecRun::None;
-    unsigned qrecRunKinds_ = 0;
-    int qrecRunQueries_ = 0;
-    // the record queries' own pinned cell table (setRecordQueries) and the queries the pinned block has room for
+    // In-run query records, one RecordSet per family: what differs between the families as data (how its refusals start, how they
+    // name the kind bits and the selector, the number of kinds), the selected kinds, the pinned block -- blockQueries queries at the
+    // selected kinds' largest settings -- and the stamp of the run whose records it holds: the layout that run was enqueued with,
+    // pending until sync() has seen the run through
+    static constexpr int kRecordKindsMax = kQueryRecordKinds > kQuerySpectralKinds ? kQueryRecordKinds : kQuerySpectralKinds;
+    struct RecordSet {
+        const char *prefix, *bits, *selector;
+        int nKinds;
+        unsigned kinds = 0;
+        float* host = nullptr;
+        int blockQueries = 0;
+        enum class Run { None, Pending, Ok } run = Run::None;
+        unsigned runKinds = 0;
+        int runQueries = 0;
+        int runOffset[kRecordKindsMax] = {}, runFloats[kRecordKindsMax] = {};
+    };
+    RecordSet recs_[kRecordFamilies] = {{"query records: ", "PVA_QREC_*", "PvAmdSetQueryRecords", kQueryRecordKinds},
+                                        {"spectral records: ", "PVA_QSPEC_*", "PvAmdSetQuerySpectralRecords", kQuerySpectralKinds}};
+    // the record queries' own pinned cell table (setRecordQueries)
     long long* rqCellsHost_ = nullptr;
-    int rqCap_ = 0, numRecQueries_ = 0, qrecBlockQueries_ = 0;
-    int qrecQueries() const { return numRecQueries_ > 0 ? numRecQueries_ : numQueries_; }  // of the table the records follow
-    bool growQrecBlock(unsigned kinds, int queries);
-    int qrecRunOffset_[6] = {0, 0, 0, 0, 0, 0}, qrecRunFloats_[6] = {0, 0, 0, 0, 0, 0};
-    void enqueueQueryRecords();  // behind a run's analysis, in front of its last kernel (nothing when no kind is selected)
-    // in-run spectral records (band metrics, modulation, spectrum): the twins of the members above, with a pinned block of their
-    // own that holds qspecBlockQueries_ queries at the selected kinds' largest settings (8 bands, 32 bins)
-    unsigned qspecKinds_ = 0;
-    float* qspecHost_ = nullptr;
-    QrecRun qspecRun_ = QrecRun::None;
-    unsigned qspecRunKinds_ = 0;
-    int qspecRunQueries_ = 0, qspecBlockQueries_ = 0;
-    int qspecRunOffset_[3] = {0, 0, 0}, qspecRunFloats_[3] = {0, 0, 0};
-    int qspecFloatsOf(int k) const;  // floats per query of kind bit k under the current settings, -1 where they are missing
-    bool growQspecBlock(unsigned kinds, int queries);
+    int rqCap_ = 0, numRecQueries_ = 0;
+    int recordQueryCount() const { return numRecQueries_ > 0 ? numRecQueries_ : numQueries_; }  // of the table the records follow
+    int recordFloatsOf(RecordFamily f, int k, bool largest = false) const;  // per query of kind bit k; -1: its setting is missing
+    const char* recordKindsRefusal(RecordFamily f, unsigned kinds) const;  // of the kinds' settings, nullptr where none
+    bool selectRecords(RecordFamily f, unsigned kinds);
+    bool swapRecordBlock(RecordFamily f, unsigned kinds, int queries);
+    bool growRecordBlock(RecordFamily f, int queries);
+    int recordFloats(RecordFamily f, unsigned kind);
+    void stampRecords(RecordFamily f, int nq, const bool* on, int* offset, int* floats);
+    bool readRecords(RecordFamily f, unsigned kind, float* out, int n);
+    void invalidateRecords(RecordFamily f, unsigned kinds = ~0u) {  // the block's records are those of other queries or settings
+        if (recs_[f].kinds & kinds) recs_[f].run = RecordSet::Run::None;
+    }
     bool ensureModTable();               // the modulation twiddle table on the device (no run in flight)
+    void enqueueQueryRecords();          // behind a run's analysis, in front of its last kernel (nothing when no kind is selected)
     void enqueueQuerySpectralRecords();  // directly behind enqueueQueryRecords (nothing when no kind is selected)
     int* listHost_ = nullptr;
     int listCap_ = 0;

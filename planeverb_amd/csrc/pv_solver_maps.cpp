@@ -18,8 +18,6 @@
 #include "pv_lateral.h"
 #include "pv_lobes.h"
 #include "pv_metrics.h"
-#include "pv_query_records.h"
-#include "pv_query_spectral.h"
 #include "pv_spectrum.h"
 #include "pv_zones.h"
 
@@ -368,9 +366,9 @@ bool Solver::setEchogram(float slotSeconds, int nSlots) {
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
-    if (nSlots == 0 && (qrecKinds_ & (1u << kQrecEchogram)))
+    if (nSlots == 0 && (recs_[kRecTime].kinds & (1u << kQrecEchogram)))
         return fail("query records: echogram: the slots cannot be cleared while PVA_QREC_ECHOGRAM is selected (PvAmdSetQueryRecords)");
-    if (qrecKinds_ & (1u << kQrecEchogram)) qrecRun_ = QrecRun::None;  // (the records in the pinned block are the old slots')
+    invalidateRecords(kRecTime, 1u << kQrecEchogram);  // (the records in the pinned block are the old slots')
     dropAnalysisMap(kMapEchogram, nSlots == 0);
     if (nSlots == 0) {
         echoSeconds_ = 0.f;
@@ -406,7 +404,7 @@ bool Solver::setLobeWindows(const float* edgesSeconds, int nEdges) {
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
-    if (qrecKinds_ & (1u << kQrecLobes)) qrecRun_ = QrecRun::None;  // (the records in the pinned block are the old windows')
+    invalidateRecords(kRecTime, 1u << kQrecLobes);  // (the records in the pinned block are the old windows')
     dropAnalysisMap(kMapLobes, false);
     if (nEdges == 0) {
         edgesSeconds = kLobesDefaultEdges;
@@ -445,14 +443,14 @@ bool Solver::computeLobes(float* ms) {
 
 bool Solver::setBands(const float* centreHz, int n, int fraction) {
     if (isSlab()) return fail("band metrics: not available on a slab");
-    if (n == 0 && (qspecKinds_ & kQspecBandKinds))
+    if (n == 0 && (recs_[kRecSpectral].kinds & kQspecBandKinds))
         return fail("spectral records: the bands cannot be cleared while a band kind is selected (PvAmdSetQuerySpectralRecords)");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
     dropAnalysisMap(kMapBandMetrics, n == 0);
     dropAnalysisMap(kMapModulation, n == 0);  // (the modulation records are per band)
-    if (qspecKinds_ & kQspecBandKinds) qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old bands')
+    invalidateRecords(kRecSpectral, kQspecBandKinds);  // (the records in the pinned block are the old bands')
     bandHz_.clear();
     bandCoefs_.clear();
     if (n == 0) return true;
@@ -497,11 +495,9 @@ bool Solver::setModulationFrequencies(const float* hz14) {
     dropAnalysisMap(kMapModulation, false);
     modTabValid_ = false;
     for (int i = 0; i < kModFreqs; ++i) modHz_[i] = hz14 ? hz14[i] : kModDefaultHz[i];
-    if (qspecKinds_ & (1u << kQspecModulation)) {
-        qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old frequencies')
-        return ensureModTable();    // (the next run's launch reads the table: never uploaded from the enqueue path)
-    }
-    return true;
+    invalidateRecords(kRecSpectral, 1u << kQspecModulation);  // (the records in the pinned block are the old frequencies')
+    // (the next run's launch reads the table: never uploaded from the enqueue path)
+    return !(recs_[kRecSpectral].kinds & (1u << kQspecModulation)) || ensureModTable();
 }
 
 // the twiddle table of the current modulation frequencies on the device (no run in flight: the upload waits for the stream)
@@ -540,13 +536,13 @@ bool Solver::computeModulation(float* ms) {
 
 bool Solver::setSpectrumBins(const float* hz, int n) {
     if (isSlab()) return fail("spectrum: not available on a slab");
-    if (n == 0 && (qspecKinds_ & (1u << kQspecSpectrum)))
+    if (n == 0 && (recs_[kRecSpectral].kinds & (1u << kQspecSpectrum)))
         return fail("spectral records: the bins cannot be cleared while PVA_QSPEC_SPECTRUM is selected (PvAmdSetQuerySpectralRecords)");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
     dropAnalysisMap(kMapSpectrum, n == 0);
-    if (qspecKinds_ & (1u << kQspecSpectrum)) qspecRun_ = QrecRun::None;  // (the records in the pinned block are the old bins')
+    invalidateRecords(kRecSpectral, 1u << kQspecSpectrum);  // (the records in the pinned block are the old bins')
     for (float** p : {&specTab_, &specPow_})
         if (*p) {
             hipFree(*p);

@@ -4,11 +4,13 @@ profiles/query_spectral_records.txt quotes.
 Per scene, 64 queries (random reached cells of a first run); every figure the median of 20 after 3 warm-ups, with the smallest
 and largest sample next to it:
   (a) wall time of run_async + sync with NO kind selected -- with this build, and with the build PLANEVERB_AMD_BASELINE_LIB names
-      (the parent commit's library, which has no such call at all).  The launch chain is the same, so the two medians should
-      agree within the same-GPU repeatability;
+      (the parent commit's library).  The launch chain is the same, so the two medians should agree within the same-GPU
+      repeatability.  A baseline from before the feature has no such call at all and gets (a) alone; one that has the calls
+      gets every figure, for a comparison of the host side of two builds;
   (b) the same wall time with each kind alone and with all three (reading the records back from pinned memory included): band
       kinds with two octaves (63, 125 Hz), the spectrum with 8 and with 32 bins.  A launch is expected to cost what its slowest
-      work item costs as a lone wave, whatever the number of queries;
+      work item costs as a lone wave, whatever the number of queries; and all NINE in-run kinds, the six time-domain ones of
+      PvAmdSetQueryRecords (4 echogram slots, the default lobe windows) beside the three;
   (c) the comparison: the same run followed by the three whole-map passes (compute_band_metrics, compute_modulation,
       compute_spectrum with 8 bins, each with its own synchronisation), as wall time, and the passes' own device times.
 
@@ -58,11 +60,13 @@ def timed(f, runs, warm):
 
 def one(name, baseline, runs=20, warm=3):
     from planeverb_amd import api
+    full = True
     if baseline:  # a build from before the feature: bind what it has
         have = ctypes.CDLL(api.LIB_PATH)
         for n in NEW_CALLS:
             if not hasattr(have, n):
                 api.SYMBOLS.pop(n, None)
+                full = False
     scene, size, res, _ = GRIDS[name]
     if api.device_count() < 1:
         raise RuntimeError("needs a HIP device")
@@ -82,7 +86,7 @@ def one(name, baseline, runs=20, warm=3):
 
         rec = dict(scene=name, lib=os.path.basename(api.LIB_PATH), cells=[s.gx, s.gy], T=s.T, queries=64,
                    run_no_kinds_wall_ms=stats(timed(run, runs, warm)))
-        if not baseline:
+        if full:
             bins8 = [float(v) for v in np.linspace(20.0, s.fs / 4.0, 8)]
             bins32 = [float(v) for v in np.linspace(20.0, s.fs / 4.0, 32)]
             s.set_bands(BANDS)
@@ -97,14 +101,18 @@ def one(name, baseline, runs=20, warm=3):
             rec["run_then_three_whole_map_passes_wall_ms"] = stats(timed(run_whole, runs, warm))
             rec["each_whole_map_pass_own_ms_median"] = [round(float(v), 5) for v in np.median(np.array(own[warm:]), axis=0)]
 
-            def case(kinds):
+            def case(kinds, six=0):
                 s.set_query_spectral_records(kinds)
+                s.set_query_records(six)
 
                 def f():
                     run()
                     for k in (1, 2, 4):
                         if kinds & k:
                             s.queried_spectral_records(k)
+                    for k in (1, 2, 4, 8, 16, 32):
+                        if six & k:
+                            s.queried_records(k)
 
                 return stats(timed(f, runs, warm))
 
@@ -112,10 +120,13 @@ def one(name, baseline, runs=20, warm=3):
             rec["run_modulation_wall_ms"] = case(api.QSPEC_MODULATION)
             rec["run_spectrum_8_bins_wall_ms"] = case(api.QSPEC_SPECTRUM)
             rec["run_all_three_8_bins_wall_ms"] = case(api.QSPEC_ALL)
+            s.set_echogram(0.01, 4)
+            rec["run_all_nine_8_bins_wall_ms"] = case(api.QSPEC_ALL, api.QREC_ALL)
             s.set_spectrum_bins(bins32)
             rec["run_spectrum_32_bins_wall_ms"] = case(api.QSPEC_SPECTRUM)
             rec["run_all_three_32_bins_wall_ms"] = case(api.QSPEC_ALL)
             s.set_query_spectral_records(0)
+            s.set_query_records(0)
             rec["run_no_kinds_again_wall_ms"] = stats(timed(run, runs, warm))
     print(json.dumps(rec), flush=True)
     return rec
