@@ -1273,6 +1273,59 @@ PVA_EXPORT int PvAmdHostZoneStats(const float* map, int gx, int gy, int planes, 
  * where xmin <= (X + 0.5f) * dx < xmax and zmin <= (Y + 0.5f) * dx < zmax in float32; later rectangles overwrite earlier ones;
  * cells in no rectangle get 0 */
 PVA_EXPORT int PvAmdHostZoneRects(float dx, int gx, int gy, const float* rect4, int n, unsigned char* labels);
+
+/* ---- Zone decay: the ensemble decay curve of a receiver area and the decay times read off it ----
+ * ISO 3382-2 states the reverberation time of a room or an area either as the average of the positions' decay times (the zone
+ * statistics of PVA_MAP_DECAY_TIMES above) or from ONE ensemble decay curve: the squared impulse responses of all positions summed,
+ * integrated backwards, and EDT, T20 and T30 read off that curve.  PvAmdComputeZoneDecay reduces the recorded history itself,
+ * [T][cells] -> [zones][T], ON THE DEVICE (pv_zone_decay.hip); only nZones x T doubles and the records cross to the host.
+ * Inputs: the last completed run, the labels of PvAmdSetZones, and align.  Definition, for zone z:
+ *   members  the result cells s = X * gy + Y with labels[s] == z that have an onset in that run (delay[s] != FLT_MAX; cells
+ *            outside the run's history window have none); t0(s) = (int)delay[s]; n_cells = their number, t_first / t_last the
+ *            smallest / largest t0, both -1 for a zone without a member;
+ *   p_s(t)   exactly what PvAmdCopyHistoryPlane(t) gives at array cell (X, Y); only the samples t0(s) <= t < T are used;
+ *   slot     of a sample: PVA_ZONE_DECAY_ABSOLUTE j = t (time since emission); PVA_ZONE_DECAY_ONSET j = t - t0(s) (the
+ *            beginnings synchronised);
+ *   etc[j]   the energy-time curve, j = 0 .. T - 1: the three-level sum of the zone statistics above, unchanged -- butterfly over
+ *            blocks of 64 consecutive Y, the blocks of a row sequentially, the rows sequentially in X, each from +0.0 -- applied
+ *            to v(X, Y) = (double)p * (double)p (exact in double) for a member whose sample for slot j exists (ABSOLUTE:
+ *            j >= t0; ONSET: t0 + j < T) and +0.0 for every other cell; blocks and rows without such a member are skipped;
+ *   edc[j]   the Schroeder curve: edc[T] = +0.0, edc[j] = edc[j + 1] + etc[j] for j = T - 1 .. 0, in double; slots before the
+ *            first member sample add +0.0, so edc[0] holds E0 bit for bit;
+ *   fits     tailN as for PvAmdDecayTimes; j0 = ABSOLUTE ? t_first : 0; jEnd = ABSOLUTE ? T - tailN : T - tailN - t_last (in
+ *            ONSET mode the slots past jEnd no longer hold every cell); e0 = edc[j0]; r(j) = edc[j] / e0; L(j) = 10.0 *
+ *            log10(r(j)) in double with the host libm's log10; the three ranges of PvAmdDecayTimes with the same float limits
+ *            widened to double; membership r <= hi && r >= lo for j in [j0, jEnd), k = j - j0; n, kmin, kmax, Sy, Sky, kbar and
+ *            slope as there, all in double, the steps taken in decreasing j, nothing fused; value = (-60.0 / slope) /
+ *            (double)fs.  A range is complete iff j0 < jEnd && r(jEnd - 1) < lo; value is quiet NaN unless the range is complete
+ *            and n >= 2; depth = j0 < jEnd ? L(jEnd - 1) : NaN;
+ *   empty    a zone without a member: e0 = +0.0, the five doubles quiet NaN, the three n zero.
+ * The device computes etc and the three integers (order-independent); edc and the fits are finished on the host by the function
+ * PvAmdHostZoneDecay ends with.  PvAmdHostZoneDecay applies the whole rule on the CPU, bit for bit.
+ * Device storage: the zone scratch of the zone statistics, grown on demand -- 8 bytes per zone, result row and time slot in
+ * flight, the slots dealt in chunks that keep it within 32 MiB, plus nZones x T doubles and 12 bytes per zone and result row.
+ * Out of scope: normalising each cell by its own E0, per-band curves, clarity and centre time of a zone, in-run or live-module
+ * records, overlapping zones, slab groups, slab ranks and sparse-emitter solvers. */
+#define PVA_ZONE_DECAY_ABSOLUTE 0
+#define PVA_ZONE_DECAY_ONSET    1
+typedef struct PvAmdZoneDecay {
+    double edt, t20, t30, e0, depth;
+    int n_edt, n_t20, n_t30, n_cells, t_first, t_last;
+} PvAmdZoneDecay; /* 64 bytes */
+/* The records of the current zones for the last completed run: out[z - 1] for zone z; returns nZones, or -1 with PvAmdLastError.
+ * etc / edc (optional): nZones x T doubles each, zone-major.  *ms (optional): device time of the passes.  Synchronous on the
+ * solver's own stream (waits for a run in flight).  Nothing is cached and nothing invalidated: no map, plan or run chain is
+ * touched.  Refused ("zone decay: ..."): NULL solver or out, a bad align, no zones set, cap < nZones, no completed run or a last
+ * run that ended in error, sparse-emitter (streaming) solvers, PVA_OPT_SKIP_ANALYSIS, slab groups and slab ranks */
+PVA_EXPORT int PvAmdComputeZoneDecay(PvAmdSolver* s, int align, PvAmdZoneDecay* out, int cap, double* etc, double* edc, float* ms);
+/* the time slots PvAmdComputeZoneDecay deals per pair of launches under the current zones (the scratch bound above); T and more:
+ * all at once */
+PVA_EXPORT int PvAmdZoneDecayChunkSlots(PvAmdSolver* s);
+/* CPU only: the definition above applied to a history p[t * gx * gy + X * gy + Y] of T planes and an onset map delay[X * gy + Y]
+ * (FLT_MAX: none); out = nZones records, etc / edc (optional) = nZones x T doubles.  The restatement the tests hold the kernel to.
+ * The labels are checked by the rule of PvAmdSetZones; an onset of a labelled cell outside 0 .. T - 1 is refused */
+PVA_EXPORT int PvAmdHostZoneDecay(const float* p, const float* delay, int gx, int gy, int T, int fs, const unsigned char* labels,
+                                  int nZones, int align, PvAmdZoneDecay* out, double* etc, double* edc);
 /* Gaussian pulse table (Grid.cpp:12-27), T floats */
 PVA_EXPORT int PvAmdCopyPulse(PvAmdSolver* s, float* out);
 /* Material planes after rasterisation: beta (uint8) and R (float), (gx+1)*(gy+1) each (with shapes: the composed material) */

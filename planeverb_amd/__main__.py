@@ -71,6 +71,15 @@ def zone_tables(s, a):
         for t, row in zip(tables, recs):
             t[key] = dict((n, {"n": int(r["n_finite"]), "mean": float(r["mean"]), "std": float(r["std"]), "min": float(r["min"]),
                                "max": float(r["max"])}) for n, r in zip(names, row))
+    if a.zone_decay:
+        recs, etc, edc = s.zone_decay(a.zone_decay, curves=True)
+        for t, r, e, d in zip(tables, recs, etc, edc):
+            t["zoneDecay"] = {"align": a.zone_decay, "nCells": int(r["n_cells"]), "tFirst": int(r["t_first"]), "tLast": int(r["t_last"]),
+                              "edt": float(r["edt"]), "t20": float(r["t20"]), "t30": float(r["t30"]), "depth": float(r["depth"]),
+                              "nEdt": int(r["n_edt"]), "nT20": int(r["n_t20"]), "nT30": int(r["n_t30"])}
+            if a.zone_decay_curves:
+                t["zoneDecay"]["etc"] = [float(v) for v in e]
+                t["zoneDecay"]["edc"] = [float(v) for v in d]
     return tables
 
 
@@ -159,7 +168,14 @@ def main(argv=None):
     ap.add_argument("--zone", metavar="XMIN,ZMIN,XMAX,ZMAX", type=rect4, action="append", default=[],
                     help="a receiver area in metres (repeatable, at most 64; a later one overwrites an earlier one where they "
                          "overlap): with any of the map options above, add a table per zone with n, mean, std, min and max of "
-                         "every plane of those maps over the zone's cells, reduced on the GPU")
+                         "every plane of those maps over the zone's cells, reduced on the GPU; with --zone-decay, the zone's "
+                         "ensemble decay curve and its decay times")
+    ap.add_argument("--zone-decay", choices=api.ZONE_DECAY_ALIGN_NAMES,
+                    help="with --zone (it counts as one of the options --zone needs): add per zone the ensemble decay curve's table "
+                         "-- the squared responses of the zone's reached cells summed on the GPU, by time since emission (absolute) "
+                         "or since each cell's onset (onset) --: nCells, tFirst, tLast, EDT, T20, T30, depth and the point counts")
+    ap.add_argument("--zone-decay-curves", action="store_true",
+                    help="with --zone-decay: add the curves themselves, etc (energy per step) and edc (its backward sum)")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
@@ -167,6 +183,10 @@ def main(argv=None):
         ap.error("--modulation: needs --bands")
     if a.zone and a.in_run_records:
         ap.error("--zone: reduces the whole-map passes (not with --in-run-records)")
+    if a.zone_decay and not a.zone:
+        ap.error("--zone-decay: needs --zone")
+    if a.zone_decay_curves and not a.zone_decay:
+        ap.error("--zone-decay-curves: needs --zone-decay")
     if len(a.zone) > api.ZONES_MAX:
         ap.error("--zone: at most %d zones" % api.ZONES_MAX)
     boxes = api.load_pv(a.scene)

@@ -354,6 +354,10 @@ SYMBOLS = {
     "PvAmdComputeZoneStats": (C.c_int, [_vp, C.c_int, _vp, C.c_int, _fp]),
     "PvAmdHostZoneStats": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ubyte), C.c_int, _vp]),
     "PvAmdHostZoneRects": (C.c_int, [C.c_float, C.c_int, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
+    "PvAmdComputeZoneDecay": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _fp]),
+    "PvAmdZoneDecayChunkSlots": (C.c_int, [_vp]),
+    "PvAmdHostZoneDecay": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.POINTER(C.c_ubyte), C.c_int, C.c_int, _vp, C.POINTER(C.c_double),
+                                                                   C.POINTER(C.c_double)]),
     "PvAmdCopyPulse": (C.c_int, [_vp, _fp]),
     "PvAmdCopyMaterial": (C.c_int, [_vp, C.POINTER(C.c_ubyte), _fp]),
     "PvAmdSetFields": (C.c_int, [_vp, _fp, _fp, _fp]),
@@ -1073,6 +1077,43 @@ def zone_labels_from_rects(dx, gx, gy, rects):
     _check(lib().PvAmdHostZoneRects(float(dx), int(gx), int(gy), _f(r) if r.size else None, len(r),
                                     out.ctypes.data_as(C.POINTER(C.c_ubyte))))
     return out
+
+
+# PVA_ZONE_DECAY_*: how the cells' samples are put into the time slots of a zone's ensemble decay curve
+PVA_ZONE_DECAY_ABSOLUTE, PVA_ZONE_DECAY_ONSET = 0, 1
+ZONE_DECAY_ALIGN_NAMES = ("absolute", "onset")
+# PvAmdZoneDecay (64 bytes)
+ZONE_DECAY_DTYPE = np.dtype([("edt", "<f8"), ("t20", "<f8"), ("t30", "<f8"), ("e0", "<f8"), ("depth", "<f8"), ("n_edt", "<i4"),
+                             ("n_t20", "<i4"), ("n_t30", "<i4"), ("n_cells", "<i4"), ("t_first", "<i4"), ("t_last", "<i4")])
+assert ZONE_DECAY_DTYPE.itemsize == 64
+_dp = C.POINTER(C.c_double)
+
+
+def _zone_decay_align(align):
+    if isinstance(align, str):
+        if align not in ZONE_DECAY_ALIGN_NAMES:
+            raise ValueError("zone decay: align is one of %s" % ", ".join(ZONE_DECAY_ALIGN_NAMES))
+        return ZONE_DECAY_ALIGN_NAMES.index(align)
+    return int(align)
+
+
+def host_zone_decay(p, delay, fs, labels, n_zones=None, align="absolute"):
+    """PvAmdHostZoneDecay: the zone decay of include/planeverb_amd.h (PvAmdZoneDecay) on the CPU -- p = float32 [T, gx, gy]
+    (plane t as Solver.history_plane(t)[:gx, :gy]), delay = float32 [gx, gy] (the onset map, FLT_MAX: none), labels = uint8
+    [gx, gy] (0: no zone, 1 .. n_zones; None: the largest label), align "absolute" or "onset"; (records [n_zones] of
+    ZONE_DECAY_DTYPE, etc float64 [n_zones, T], edc float64 [n_zones, T])"""
+    h = np.ascontiguousarray(p, np.float32)
+    d = np.ascontiguousarray(delay, np.float32)
+    lab, n = _zone_labels(labels, n_zones)
+    if h.ndim != 3 or d.shape != h.shape[1:] or lab.shape != h.shape[1:]:
+        raise ValueError("host_zone_decay: a history [T, gx, gy], onsets [gx, gy] and labels [gx, gy]")
+    T = h.shape[0]
+    out = np.zeros(max(n, 0), ZONE_DECAY_DTYPE)
+    etc, edc = np.zeros((max(n, 0), T)), np.zeros((max(n, 0), T))
+    _check(lib().PvAmdHostZoneDecay(_f(h) if h.size else None, _f(d) if d.size else None, h.shape[1], h.shape[2], T, int(fs),
+                                    lab.ctypes.data_as(C.POINTER(C.c_ubyte)), n, _zone_decay_align(align), out.ctypes.data_as(_vp),
+                                    etc.ctypes.data_as(_dp), edc.ctypes.data_as(_dp)))
+    return out, etc, edc
 
 
 def host_cells(size_x, size_y, res, x, z):
@@ -2058,6 +2099,33 @@ class Solver:
             raise PlaneverbError(last_error())
         out = out[:n].reshape((n,) + width)
         return (out, ms.value) if with_ms else out
+
+    def zone_decay(self, align="absolute", curves=False, with_ms=False):
+        """PvAmdComputeZoneDecay: the ensemble decay curve of every zone of set_zones over the last completed run -- the squared
+        histories of the zone's reached cells summed on the device, slot j = t ("absolute") or t - onset ("onset") -- and EDT, T20
+        and T30 read off it: records [n_zones] of ZONE_DECAY_DTYPE; curves: (records, etc, edc), float64 [n_zones, T] each;
+        with_ms: the device milliseconds appended"""
+        nz = C.c_int(0)
+        lib().PvAmdGetZones(self._h, None, C.byref(nz))  # (a handle it refuses has no zones: the call below says why, in its own words)
+        n = nz.value
+        out = np.zeros(max(n, 1), ZONE_DECAY_DTYPE)
+        etc = np.zeros((max(n, 1), self.T)) if curves else None
+        edc = np.zeros((max(n, 1), self.T)) if curves else None
+        ms = C.c_float(0.0)
+        got = lib().PvAmdComputeZoneDecay(self._h, _zone_decay_align(align), out.ctypes.data_as(_vp), out.size,
+                                          etc.ctypes.data_as(_dp) if curves else None, edc.ctypes.data_as(_dp) if curves else None,
+                                          C.byref(ms))
+        if got < 0:
+            raise PlaneverbError(last_error())
+        res = (out[:n],) + ((etc[:n], edc[:n]) if curves else ()) + ((ms.value,) if with_ms else ())
+        return res[0] if len(res) == 1 else res
+
+    def zone_decay_chunk_slots(self):
+        """PvAmdZoneDecayChunkSlots: the time slots zone_decay deals per pair of launches under the current zones"""
+        n = lib().PvAmdZoneDecayChunkSlots(self._h)
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return n
 
     def pulse(self):
         """float32 [T]: the pulse table of a run (T = the run's steps; zero past the grid's own table)"""

@@ -22,6 +22,7 @@
 #include "pv_query_records.h"
 #include "pv_query_spectral.h"
 #include "pv_spectrum.h"
+#include "pv_zone_decay.h"
 #include "pv_zones.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
 #include "pv_bake.h"
@@ -458,6 +459,13 @@ const char* PlaneverbWorkerError(void) try {
     return w.c_str();
 } PV_API_CATCH("")
 const char* PvAmdVersion(void) try { return "planeverb_amd 0.4.1 (gfx950)"; } PV_API_CATCH("")
+
+// (PvAmdComputeZoneDecay and PvAmdHostZoneDecay)
+static bool zoneDecayAlign(int align) {
+    if (align == kZoneDecayAbsolute || align == kZoneDecayOnset) return true;
+    g_lastError = "zone decay: align is PVA_ZONE_DECAY_ABSOLUTE or PVA_ZONE_DECAY_ONSET";
+    return false;
+}
 
 #ifndef PVA_HOST_TEST
 int PvAmdDeviceCount(void) try {
@@ -1587,6 +1595,22 @@ int PvAmdComputeZoneStats(PvAmdSolver* h, int kind, PvAmdZoneStat* out, int cap,
     return count;
 } PV_API_CATCH(-1)
 
+// zone decay (pv_zone_decay.hip)
+static_assert(sizeof(PvAmdZoneDecay) == sizeof(ZoneDecay), "64 bytes");
+static_assert(PVA_ZONE_DECAY_ABSOLUTE == kZoneDecayAbsolute && PVA_ZONE_DECAY_ONSET == kZoneDecayOnset, "the alignments");
+
+int PvAmdComputeZoneDecay(PvAmdSolver* h, int align, PvAmdZoneDecay* out, int cap, double* etc, double* edc, float* ms) try {
+    if (!analysisCall(h, "zone decay: ", __func__, out) || !zoneDecayAlign(align)) return -1;
+    int count = 0;
+    if (!h->s->computeZoneDecay(align, out, cap, etc, edc, ms, &count)) return ret(h, false);
+    return count;
+} PV_API_CATCH(-1)
+
+int PvAmdZoneDecayChunkSlots(PvAmdSolver* h) try {
+    if (!analysisHandle(h, "zone decay: ")) return -1;
+    return h->s->zoneDecayChunkSlots();
+} PV_API_CATCH(-1)
+
 int PvAmdCopyPulse(PvAmdSolver* h, float* out) try {
     if (!out || !ensure(h, true)) return -1;
     return ret(h, h->g ? h->g->copyPulse(out) : h->s->copyPulse(out));
@@ -2095,6 +2119,25 @@ int PvAmdHostZoneStats(const float* map, int gx, int gy, int planes, const unsig
     }
     static_assert(sizeof(PvAmdZoneStat) == sizeof(ZoneStat), "64 bytes");
     zoneStatsOfMap(map, gx, gy, planes, labels, nZones, reinterpret_cast<ZoneStat*>(out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostZoneDecay(const float* p, const float* delay, int gx, int gy, int T, int fs, const unsigned char* labels, int nZones,
+                       int align, PvAmdZoneDecay* out, double* etc, double* edc) try {
+    if (!p || !delay || !out || gx < 1 || gy < 1 || T < 1 || fs < 1 || (long long)gx * gy > INT_MAX) {
+        g_lastError = "zone decay: PvAmdHostZoneDecay: a history of T planes of gx x gy floats, gx x gy onsets, gx, gy, T, fs >= 1, and an output of nZones records";
+        return -1;
+    }
+    if (!zoneDecayAlign(align)) return -1;
+    if (const char* e = zoneLabelsError(labels, (long long)gx * gy, nZones)) {
+        g_lastError = std::string("zone decay: ") + (e + sizeof("zone statistics: ") - 1);
+        return -1;
+    }
+    if (const char* e = zoneDecayOnsetsError(delay, labels, (long long)gx * gy, T)) {
+        g_lastError = e;
+        return -1;
+    }
+    zoneDecayOfHistory(p, delay, gx, gy, T, fs, labels, nZones, align, reinterpret_cast<ZoneDecay*>(out), etc, edc);
     return 0;
 } PV_API_CATCH(-1)
 

@@ -135,6 +135,14 @@ void launchRoomMetrics(const AnalyzeArgs& a, float* out, hipStream_t stream);
 struct ZoneArgs;
 void launchZoneStats(const ZoneArgs& a, hipStream_t stream);
 
+// ---- pv_zone_decay.hip: per-zone ensemble decay curves
+// launchZoneMembers: members, smallest and largest onset of every zone into a.members (a.memberRows is scratch; a.slot0 / a.slots /
+// a.rows / a.etc are not used).  launchZoneCurves: etc of the chunk of slots a.slot0 .. a.slot0 + a.slots - 1 of every zone into
+// a.etc (pv_zone_decay.h; a.rows is scratch), slot j = t (onset false) or t - t0 (true)
+struct ZoneCurveArgs;
+void launchZoneMembers(const ZoneCurveArgs& a, hipStream_t stream);
+void launchZoneCurves(const ZoneCurveArgs& a, bool onset, hipStream_t stream);
+
 // ---- pv_decay.hip: per-cell decay times
 // decay times (EDT, T20, T30) of the last completed run (pv_decay.hip): out = kDecayFloats planes of a.histPlane floats, indexed
 // by the cell's offset inside a history plane; NaN where the cell has no onset in that run.  twoLaunches: the two walks of the

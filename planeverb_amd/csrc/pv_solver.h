@@ -348,6 +348,12 @@ public:
     int zones(unsigned char* labels) const;
     int zoneStatPlanes(AnalysisKind k) const;
     bool computeZoneStats(AnalysisKind k, void* out, int cap, float* ms, int* count);
+    // Zone decay (pv_zone_decay.hip; include/planeverb_amd.h PvAmdZoneDecay): the ensemble decay curve of every zone of setZones
+    // from the last completed run's history and onset map, and the decay times read off it -- out = nZones records, etc / edc
+    // (either may be nullptr) = nZones x T doubles.  Nothing cached, no map, plan or run chain touched; waits for a run in flight.
+    // zoneDecayChunkSlots: the time slots one pair of launches covers under the current zones (T and more: all of them at once)
+    bool computeZoneDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count);
+    int zoneDecayChunkSlots() const;
     bool copyPulse(float* out);
     bool copyMaterial(uint8_t* beta, float* R);
     bool freeFieldEnergyAt(int cellX, int cellY, int n, float r, float* out);
@@ -617,7 +623,10 @@ private:
     float* specPow_ = nullptr;
     // zone statistics (pv_zones.h): the labels on the device and as given, and the pass's scratch -- per plane in flight, zone and
     // result row one ZoneRow and one double (48 bytes), the planes dealt in chunks that keep it within kZoneScratchBytes (one
-    // plane's where that is more), then the nZones x planes records; grown on demand, kept
+    // plane's where that is more), then the nZones x planes records; grown on demand, kept.  The zone-decay pass uses the same
+    // scratch: per time slot in flight, zone and result row one double, the slots dealt in chunks within the same bound, then
+    // nZones x T doubles of curves and the zones' member rows and records
+    bool growZoneScratch(size_t need);
     static constexpr size_t kZoneScratchBytes = 32u << 20;
     unsigned char* zoneLabels_ = nullptr;
     std::vector<unsigned char> zoneHost_;

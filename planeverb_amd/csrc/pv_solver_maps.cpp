@@ -19,6 +19,7 @@
 #include "pv_lobes.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
+#include "pv_zone_decay.h"
 #include "pv_zones.h"
 
 namespace pva {
@@ -259,6 +260,19 @@ int Solver::zoneStatPlanes(AnalysisKind k) const {
     }
 }
 
+bool Solver::growZoneScratch(size_t need) {
+    if (zoneScratchBytes_ >= need) return true;
+    if (zoneScratch_) {
+        hipFree(zoneScratch_);
+        deviceBytes_ -= (long long)zoneScratchBytes_;
+        zoneScratch_ = nullptr;
+        zoneScratchBytes_ = 0;
+    }
+    if (!dalloc(&zoneScratch_, need, false)) return false;
+    zoneScratchBytes_ = need;
+    return true;
+}
+
 bool Solver::computeZoneStats(AnalysisKind k, void* out, int cap, float* ms, int* count) {
     if (isSlab()) return fail("zone statistics: not available on a slab");
     if (opt_.streaming) return fail("zone statistics: the full pressure history is not kept in streaming-analysis mode");
@@ -275,16 +289,7 @@ bool Solver::computeZoneStats(AnalysisKind k, void* out, int cap, float* ms, int
     const int chunk = (int)std::min<size_t>((size_t)m.planes, std::max<size_t>(1, kZoneScratchBytes / perPlane));
     const size_t rowsBytes = (size_t)chunk * (size_t)zoneCount_ * (size_t)g_.gx * sizeof(ZoneRow), m2Bytes = perPlane * chunk - rowsBytes;
     const size_t need = rowsBytes + m2Bytes + (size_t)records * sizeof(ZoneStat);
-    if (zoneScratchBytes_ < need) {
-        if (zoneScratch_) {
-            hipFree(zoneScratch_);
-            deviceBytes_ -= (long long)zoneScratchBytes_;
-            zoneScratch_ = nullptr;
-            zoneScratchBytes_ = 0;
-        }
-        if (!dalloc(&zoneScratch_, need, false)) return false;
-        zoneScratchBytes_ = need;
-    }
+    if (!growZoneScratch(need)) return false;
     for (auto& e : mapEv_)
         if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
     ZoneArgs a{};
@@ -320,6 +325,84 @@ bool Solver::computeZoneStats(AnalysisKind k, void* out, int cap, float* ms, int
     if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
     for (int i = 0; i < records; ++i) zoneStatFinish(&recs[i]);
     *count = records;
+    return true;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// zone decay (pv_zone_decay.hip): the ensemble decay curve of every zone, straight off the history planes and the onset map
+// ----------------------------------------------------------------------------------------------------------------
+
+int Solver::zoneDecayChunkSlots() const {
+    const size_t perSlot = (size_t)std::max(zoneCount_, 1) * (size_t)g_.gx * sizeof(double);
+    const size_t fit = kZoneScratchBytes / perSlot / kZoneCurveSlots * kZoneCurveSlots;
+    return (int)std::min<size_t>(std::max<size_t>(fit, kZoneCurveSlots), kZoneCurveMaxChunk);
+}
+
+bool Solver::computeZoneDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count) {
+    if (isSlab()) return fail("zone decay: not available on a slab");
+    if (opt_.streaming) return fail("zone decay: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("zone decay: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (!zoneCount_) return fail("zone decay: no zones set (PvAmdSetZones)");
+    if (cap < zoneCount_) return fail("zone decay: PvAmdComputeZoneDecay: the output holds fewer than nZones records");
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("zone decay: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("zone decay: the last run ended in error");
+    const int T = T_, nz = zoneCount_;
+    // scratch: the row sums of one chunk of slots, the curves, the zones' member rows and records
+    const int chunk = std::min(zoneDecayChunkSlots(), T);
+    const size_t rowsBytes = (size_t)chunk * (size_t)nz * (size_t)g_.gx * sizeof(double), etcBytes = (size_t)nz * (size_t)T * sizeof(double);
+    const size_t memberRowsBytes = ((size_t)nz * (size_t)g_.gx * sizeof(ZoneMembers) + 7) / 8 * 8;
+    if (!growZoneScratch(rowsBytes + etcBytes + memberRowsBytes + (size_t)nz * sizeof(ZoneMembers))) return false;
+    for (auto& e : mapEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    ZoneCurveArgs a{};
+    a.hist = hist_;
+    a.histPlane = histPlane_;
+    a.delay = delay_;
+    a.labels = zoneLabels_;
+    a.gx = g_.gx;
+    a.gy = g_.gy;
+    a.nZones = nz;
+    a.T = T;
+    a.wr0 = dynCur_.histRow0 - geo_.G;  // (the window as the last run recorded it)
+    a.wc0 = dynCur_.histCol0 - geo_.G;
+    a.wnr = std::min(dynCur_.histTilesX, histTilesX_) * rxi_;
+    a.wnc = std::min(dynCur_.histTilesY, histTilesY_) * wi_;
+    a.rxi = rxi_;
+    a.wi = wi_;
+    a.tilesY = dynCur_.histTilesY;
+    a.rows = reinterpret_cast<double*>(zoneScratch_);
+    a.etc = reinterpret_cast<double*>(zoneScratch_ + rowsBytes);
+    a.memberRows = reinterpret_cast<ZoneMembers*>(zoneScratch_ + rowsBytes + etcBytes);
+    a.members = reinterpret_cast<ZoneMembers*>(zoneScratch_ + rowsBytes + etcBytes + memberRowsBytes);
+    hipEventRecord(mapEv_[0], stream_);
+    launchZoneMembers(a, stream_);
+    for (int j0 = 0; j0 < T; j0 += chunk) {
+        a.slot0 = j0;
+        a.slots = std::min(chunk, T - j0);
+        launchZoneCurves(a, align == kZoneDecayOnset, stream_);
+    }
+    hipEventRecord(mapEv_[1], stream_);
+    std::vector<double> etcHost, edcHost;
+    if (!etc) etcHost.resize((size_t)nz * T), etc = etcHost.data();
+    std::vector<ZoneMembers> members((size_t)nz);
+    if (!hipOk(hipGetLastError(), "zone decay launch") ||
+        !hipOk(hipMemcpyAsync(etc, a.etc, etcBytes, hipMemcpyDeviceToHost, stream_), "zone decay copy") ||
+        !hipOk(hipMemcpyAsync(members.data(), a.members, (size_t)nz * sizeof(ZoneMembers), hipMemcpyDeviceToHost, stream_), "zone decay copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "zone decay sync"))
+        return false;
+    if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
+    if (!edc) edcHost.resize((size_t)T);
+    ZoneDecay* recs = static_cast<ZoneDecay*>(out);
+    for (int z = 0; z < nz; ++z) {
+        recs[z].n_cells = members[(size_t)z].n_cells;
+        recs[z].t_first = members[(size_t)z].t_first;
+        recs[z].t_last = members[(size_t)z].t_last;
+        zoneDecayFinish(etc + (size_t)z * T, edc ? edc + (size_t)z * T : edcHost.data(), T, (int)g_.fs, align, &recs[z]);
+    }
+    *count = nz;
     return true;
 }
 

@@ -1,0 +1,247 @@
+// pv_zone_decay.hip -- per-zone ensemble decay curves (pv_zone_decay.h has the definition): the reduction of the recorded pressure
+// history itself, [T][cells] -> [zones][T], by the summation order of pv_zones.h applied per time slot.
+//
+// The history is T planes in the tile-major layout; labels and onsets are row-major over the result map.  Per chunk of slots:
+//   pv_zone_curve_rows_kernel<ONSET>  a wave owns one result row X and a group of kZoneCurveSlots consecutive slots, and walks the
+//                                     row in blocks of 64 consecutive Y, one per lane.  Label, onset and the cell's offset inside
+//                                     a plane are found ONCE per block and serve all slots of the group -- the zone-statistics
+//                                     pass pays them per plane.  The group's loads of a block are issued together: plane j of
+//                                     every lane in ABSOLUTE mode (a block touches at most three tile rows' pieces of a plane,
+//                                     each contiguous), plane t0 + j of the lane's own onset t0 in ONSET mode (lanes with one
+//                                     onset share their lines).  A lane loads only where t0 <= t < T and the cell lies in the
+//                                     history window: a tile's history is stored only from the launch in which it first became
+//                                     non-zero, so nothing below an onset may be read; every other lane contributes +0.0.
+//                                     Per label present the wave runs the butterflies of zoneWaveBlockSum over (double)p *
+//                                     (double)p for the group's sixteen slots TOGETHER (zoneWaveBlockSums16: the lanes a
+//                                     butterfly step leaves idle carry another slot); lane z - 1 keeps zone z's row
+//                                     accumulators of the group in registers and writes them to rows[slot][zone][X].
+//                                     Skipped wave-uniformly, because they could only add +0.0 to sums that start at +0.0:
+//                                     lanes that have no sample in any slot of the group (ABSOLUTE: onset after the group;
+//                                     ONSET: t0 + first slot >= T), and with them whole blocks and whole groups;
+//   pv_zone_curve_merge_kernel        a wave per (zone, slot) adds the row sums in increasing X, as pv_zone_merge_kernel does.
+// Once per call, before the chunks:
+//   pv_zone_members_rows_kernel, pv_zone_members_merge_kernel: members, smallest and largest onset of every zone (integers:
+//                                     the order does not matter).
+// A block is reduced while the samples of the next block and the label and onset of the one after are in flight.  edc, the fits and the empty-zone values are
+// the host's (zoneDecayFinish).  Plane offsets are 64-bit throughout.  Only vector stores; nothing is atomic.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <climits>
+
+#include "pv_launch.h"
+#include "pv_zone_decay.h"
+#include "pv_zones_dev.h"
+
+namespace pva {
+
+namespace {
+
+constexpr int kZoneCurveBlock = 256;  // four waves: four consecutive rows of one slot group (they share the lines of a tile's rows)
+
+// a lane's cell of a block: label 0 where the cell is no member (no label, past gy, no onset, outside the window)
+struct ZoneCurveCell {
+    int label;
+    int t0;
+    long long g;  // offset inside a history plane
+};
+__device__ __forceinline__ ZoneCurveCell zoneCurveCellAt(const ZoneCurveArgs& a, int X, int Y) {
+    ZoneCurveCell c{0, 0, 0};
+    if (Y >= a.gy) return c;
+    const long long s = (long long)X * a.gy + Y;
+    const int label = (int)a.labels[s];
+    if (label == 0) return c;
+    const float d = a.delay[s];
+    const int hr = X - a.wr0, hc = Y - a.wc0;
+    if (d == FLT_MAX || !(d >= 0.0f && d < (float)a.T) || hr < 0 || hc < 0 || hr >= a.wnr || hc >= a.wnc) return c;
+    const int ti = hr / a.rxi, tj = hc / a.wi;
+    const long long g = ((long long)(ti * a.tilesY + tj) * a.rxi + (hr - ti * a.rxi)) * a.wi + (hc - tj * a.wi);
+    if (g >= a.histPlane) return c;
+    c.label = label;
+    c.t0 = (int)d;
+    c.g = g;
+    return c;
+}
+
+// The butterflies of zoneWaveBlockSum for SIXTEEN slots at once: v[k] = the lane's value of slot k; lane k (< 16) returns the block
+// value of slot k.  After the step s of one butterfly only the lanes that are multiples of 2 s hold values anybody reads, so the
+// other lanes carry another slot's: at step s = 1, 2, 4, 8 the lanes whose bit s is clear keep the even slot of a pair and the
+// others the odd one, and each hands the partner lane (lane ^ s) the value IT needs -- 8 + 4 + 2 + 1 adds instead of 16 x 4.  Every
+// add has the operands of the definition's v[i] = v[i] + v[i + s], for the odd slot with the two sides exchanged (IEEE addition is
+// commutative).  Lane i then holds, for slot i & 15, the value of its row of 16 lanes; s = 16 and 32 add the rows as before.
+// Exchanges: quad_perm [1, 0, 3, 2] and [2, 3, 0, 1], row_shl:4 / row_shr:4 by the side of the lane, row_ror:8
+__device__ __forceinline__ double zoneWaveBlockSums16(const double (&v)[kZoneCurveSlots], int lane) {
+    static_assert(kZoneCurveSlots == 16, "four halvings");
+    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
+    double y[8], z[4], w[2];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) y[m] = (b0 ? v[2 * m + 1] : v[2 * m]) + zoneDpp<0xB1>(b0 ? v[2 * m] : v[2 * m + 1]);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) z[m] = (b1 ? y[2 * m + 1] : y[2 * m]) + zoneDpp<0x4E>(b1 ? y[2 * m] : y[2 * m + 1]);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const double send = b2 ? z[2 * m] : z[2 * m + 1];
+        const double up = zoneDpp<0x104>(send), down = zoneDpp<0x114>(send);  // lane + 4, lane - 4 (0 outside the row: not selected)
+        w[m] = (b2 ? z[2 * m + 1] : z[2 * m]) + (b2 ? down : up);
+    }
+    double u = (b3 ? w[1] : w[0]) + zoneDpp<0x128>(b3 ? w[0] : w[1]);
+    u = u + __shfl_down(u, 16);
+    u = u + __shfl_down(u, 32);
+    return u;
+}
+
+template <bool ONSET>
+__global__ __launch_bounds__(kZoneCurveBlock) void pv_zone_curve_rows_kernel(const ZoneCurveArgs a) {
+    constexpr int TC = kZoneCurveSlots;
+    const int lane = threadIdx.x & 63;
+    const int X = blockIdx.x * (kZoneCurveBlock / 64) + (threadIdx.x >> 6);
+    if (X >= a.gx) return;  // (wave-uniform)
+    const int jl0 = blockIdx.y * TC;                           // the group's first slot inside the chunk
+    const int j0 = a.slot0 + jl0;                              // ... and in the curve
+    const int nj = a.slots - jl0 < TC ? a.slots - jl0 : TC;   // its slots (the chunk's last group may be short)
+    double acc[TC];
+#pragma unroll
+    for (int k = 0; k < TC; ++k) acc[k] = 0.0;
+    const int nb = (a.gy + kZoneBlock - 1) / kZoneBlock;
+    // a member with a sample in some slot of the group
+    const auto liveIn = [&](const ZoneCurveCell& c) { return c.label != 0 && (ONSET ? c.t0 + j0 < a.T : c.t0 <= j0 + nj - 1); };
+    // the group's samples of a block's cell (+0.0f where the cell has none)
+    const auto loadGroup = [&](const ZoneCurveCell& c, bool live, float (&p)[TC]) {
+        const float* __restrict__ h = a.hist + c.g;
+#pragma unroll
+        for (int k = 0; k < TC; ++k) {
+            const int t = ONSET ? c.t0 + j0 + k : j0 + k;
+            const bool has = live && k < nj && t >= c.t0 && t < a.T;
+            p[k] = has ? h[(long long)t * a.histPlane] : 0.0f;
+        }
+    };
+    // two blocks ahead: block b is reduced while the samples of block b + 1 and the label and onset of block b + 2 are in flight
+    ZoneCurveCell c = zoneCurveCellAt(a, X, lane);
+    bool live = liveIn(c);
+    float p[TC];
+    loadGroup(c, live, p);
+    ZoneCurveCell c1 = nb > 1 ? zoneCurveCellAt(a, X, kZoneBlock + lane) : ZoneCurveCell{0, 0, 0};
+    for (int b = 0; b < nb; ++b) {
+        const bool live1 = liveIn(c1);  // (label 0 past the last block)
+        float p1[TC];
+        loadGroup(c1, live1, p1);
+        const ZoneCurveCell c2 = b + 2 < nb ? zoneCurveCellAt(a, X, (b + 2) * kZoneBlock + lane) : ZoneCurveCell{0, 0, 0};
+        unsigned long long left = __ballot(live);
+        while (left) {  // (wave-uniform)
+            const int z = __builtin_amdgcn_readlane(c.label, __ffsll((long long)left) - 1);
+            const bool mine = live && c.label == z;
+            left &= ~__ballot(mine);
+            double v[TC];
+#pragma unroll
+            for (int k = 0; k < TC; ++k) {
+                const double x = mine ? (double)p[k] : 0.0;
+                v[k] = x * x;
+            }
+            const double sums = zoneWaveBlockSums16(v, lane);  // lane k: slot k's block value
+#pragma unroll
+            for (int k = 0; k < TC; ++k) {
+                const double bv = zoneReadLane(sums, k);
+                if (lane == z - 1) acc[k] = acc[k] + bv;
+            }
+        }
+        c = c1;
+        live = live1;
+#pragma unroll
+        for (int k = 0; k < TC; ++k) p[k] = p1[k];
+        c1 = c2;
+    }
+    if (lane >= a.nZones) return;
+#pragma unroll
+    for (int k = 0; k < TC; ++k)
+        if (k < nj) a.rows[((long long)(jl0 + k) * a.nZones + lane) * a.gx + X] = acc[k];
+}
+
+// slot slot0 + blockIdx.y of zone blockIdx.x: the row sums in increasing X
+__global__ __launch_bounds__(64) void pv_zone_curve_merge_kernel(const ZoneCurveArgs a) {
+    const int lane = threadIdx.x;
+    const int z = blockIdx.x, sl = blockIdx.y;
+    const double* __restrict__ rows = a.rows + ((long long)sl * a.nZones + z) * a.gx;
+    double total = 0.0;
+    for (int X0 = 0; X0 < a.gx; X0 += 64) {
+        const int X = X0 + lane;
+        const double r = X < a.gx ? rows[X] : 0.0;
+        // increasing X, wave-uniform (pv_zone_merge_kernel); the rows past gx add +0.0, which changes no bit
+#pragma unroll
+        for (int i = 0; i < 64; ++i) total = total + zoneReadLane(r, i);
+    }
+    if (lane == 0) a.etc[(long long)z * a.T + a.slot0 + sl] = total;
+}
+
+__device__ __forceinline__ int zoneWaveMin(int v) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v = min(v, __shfl_xor(v, s));
+    return v;
+}
+__device__ __forceinline__ int zoneWaveMax(int v) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v = max(v, __shfl_xor(v, s));
+    return v;
+}
+
+// members, smallest and largest onset of every zone in one result row
+__global__ __launch_bounds__(kZoneCurveBlock) void pv_zone_members_rows_kernel(const ZoneCurveArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int X = blockIdx.x * (kZoneCurveBlock / 64) + (threadIdx.x >> 6);
+    if (X >= a.gx) return;  // (wave-uniform)
+    ZoneMembers m{0, INT_MAX, -1};
+    const int nb = (a.gy + kZoneBlock - 1) / kZoneBlock;
+    for (int b = 0; b < nb; ++b) {
+        const ZoneCurveCell c = zoneCurveCellAt(a, X, b * kZoneBlock + lane);
+        unsigned long long left = __ballot(c.label != 0);
+        while (left) {
+            const int z = __builtin_amdgcn_readlane(c.label, __ffsll((long long)left) - 1);
+            const bool mine = c.label == z;
+            const unsigned long long who = __ballot(mine);
+            left &= ~who;
+            const int lo = zoneWaveMin(mine ? c.t0 : INT_MAX), hi = zoneWaveMax(mine ? c.t0 : -1);
+            if (lane == z - 1) {
+                m.n_cells += __popcll(who);
+                m.t_first = min(m.t_first, lo);
+                m.t_last = max(m.t_last, hi);
+            }
+        }
+    }
+    if (lane < a.nZones) a.memberRows[(long long)lane * a.gx + X] = m;
+}
+
+__global__ __launch_bounds__(64) void pv_zone_members_merge_kernel(const ZoneCurveArgs a) {
+    const int lane = threadIdx.x, z = blockIdx.x;
+    int n = 0, lo = INT_MAX, hi = -1;
+    for (int X = lane; X < a.gx; X += 64) {
+        const ZoneMembers m = a.memberRows[(long long)z * a.gx + X];
+        n += m.n_cells;
+        lo = min(lo, m.t_first);
+        hi = max(hi, m.t_last);
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) n += __shfl_xor(n, s);
+    lo = zoneWaveMin(lo);
+    hi = zoneWaveMax(hi);
+    if (lane == 0) a.members[z] = ZoneMembers{n, lo, hi};
+}
+
+}  // namespace
+
+void launchZoneMembers(const ZoneCurveArgs& a, hipStream_t stream) {
+    const dim3 rowsGrid((unsigned)((a.gx + kZoneCurveBlock / 64 - 1) / (kZoneCurveBlock / 64)));
+    hipLaunchKernelGGL(pv_zone_members_rows_kernel, rowsGrid, dim3(kZoneCurveBlock), 0, stream, a);
+    hipLaunchKernelGGL(pv_zone_members_merge_kernel, dim3((unsigned)a.nZones), dim3(64), 0, stream, a);
+}
+
+// slots a.slot0 .. a.slot0 + a.slots - 1 of every zone's etc
+void launchZoneCurves(const ZoneCurveArgs& a, bool onset, hipStream_t stream) {
+    const dim3 rowsGrid((unsigned)((a.gx + kZoneCurveBlock / 64 - 1) / (kZoneCurveBlock / 64)),
+                        (unsigned)((a.slots + kZoneCurveSlots - 1) / kZoneCurveSlots));
+    if (onset)
+        hipLaunchKernelGGL(pv_zone_curve_rows_kernel<true>, rowsGrid, dim3(kZoneCurveBlock), 0, stream, a);
+    else
+        hipLaunchKernelGGL(pv_zone_curve_rows_kernel<false>, rowsGrid, dim3(kZoneCurveBlock), 0, stream, a);
+    hipLaunchKernelGGL(pv_zone_curve_merge_kernel, dim3((unsigned)a.nZones, (unsigned)a.slots), dim3(64), 0, stream, a);
+}
+
+}  // namespace pva
