@@ -541,6 +541,23 @@ PVA_EXPORT float PvAmdClockProbe(int device, float* byMemtimeMHz);
  * pattern).  1 GiB per buffer (2 GiB of device memory while it runs), best of five launches each, ~60 ms, on a stream of its
  * own; call it on an idle device.  0, or -1 on failure.  bench.py's roofline record. */
 PVA_EXPORT int PvAmdBandwidthProbe(int device, float* gbPerS4);
+/* The library's own log10f / powf (the restatement of glibc's that every analysis pass evaluates), one form per call:
+ * out[i] = form(in[i]), i < n, computed on the current device (onDevice != 0: the device compile, with the logarithm's and the
+ * power's tables in LDS exactly as the analysis kernels fill them) or by the same source on the host (onDevice = 0).  A test
+ * seam: the two must agree bit for bit for every float.  PVA_LIBM_LOG10_NORMAL_TAB and _NORMAL_BATCH are defined for positive
+ * normal finite inputs only; the batch form evaluates eight inputs that lie ceil(n / 8) apart together.  0, or -1 on failure. */
+#define PVA_LIBM_LOG10               0  /* log10f, the branching form                              */
+#define PVA_LIBM_LOG10_NONNEG        1  /* branch-free, x >= +0, constant table                    */
+#define PVA_LIBM_LOG10_NONNEG_TAB    2  /* the same with the table in LDS                          */
+#define PVA_LIBM_LOG10_NORMAL_TAB    3  /* normal-only form, table in LDS                          */
+#define PVA_LIBM_LOG10_NORMAL_BATCH  4  /* eight of them stage by stage (the decay-time kernel's)  */
+#define PVA_LIBM_POW_08              5  /* powf(x, 0.8f), the branching form                       */
+#define PVA_LIBM_POW_23              6  /* powf(x, (float)(2.0 / 3.0))                             */
+#define PVA_LIBM_POW_NONNEG_08       7  /* branch-free, constant tables                            */
+#define PVA_LIBM_POW_NONNEG_23       8
+#define PVA_LIBM_POW_NONNEG_TAB_08   9  /* the same with the tables in LDS                         */
+#define PVA_LIBM_POW_NONNEG_TAB_23  10
+PVA_EXPORT int PvAmdLibmProbe(int form, const float* in, float* out, long long n, int onDevice);
 PVA_EXPORT int PvAmdGetTimings(PvAmdSolver* s, PvAmdTimings* out);
 /* 1: the last run (PvAmdRun / PvAmdRunAsync + PvAmdSync) went out as one resident-kernel launch over the tile window around the
  * listener's walled-in air component (PVA_OPT_RESIDENT_WINDOW), 0: by any other path, -1: error.  Results do not depend on it. */
@@ -656,6 +673,21 @@ PVA_EXPORT int PvAmdGetImpulseResponseCells(PvAmdSolver* s, int cx, int cy, Plan
 PVA_EXPORT int PvAmdCopyFields(PvAmdSolver* s, float* pr, float* vx, float* vy);
 /* Recorded pressure plane of step t (zeros where the history was provably zero and not stored) */
 PVA_EXPORT int PvAmdCopyHistoryPlane(PvAmdSolver* s, int t, float* pr);
+/* The inverse, a test seam like PvAmdSetFields / PvAmdRunSteps: pr = one float per cell in exactly the order and extent
+ * PvAmdCopyHistoryPlane(t) returns them (the array cells, x * (gy + 1) + y), written into the recorded plane of step t of the
+ * LAST COMPLETED run, so that the analysis passes below can be fed histories the stencil never produces.  A cell that is not
+ * stored at step t -- outside the run's history window, or in a tile the pulse had not reached by step t -- is ignored and
+ * still reads back as 0.  Waits for a run in flight; marks all nine analysis maps "not computed", as a geometry change does;
+ * leaves the run's result map, onset map, first-step table and in-run query records as they are; the next run overwrites the
+ * history as always.
+ *   One structural rule the passes rely on, and the caller keeps: A CELL'S SAMPLES BEFORE ITS OWN FIRST NON-ZERO RECORDED SAMPLE
+ * STAY ZERO.  The velocity passes (lateral fraction, echogram, lobes) start a cell's recurrence at the step the light cone allows,
+ * PvAmdGetImpulseResponse at the tile's first stored step; the two agree only where nothing sounds ahead of the wave front.
+ *   Records of cells whose own samples (for the velocity kinds: or those of the (X - 1, Y) / (X, Y - 1) neighbours) are not all
+ * finite are whatever the definitions below give in IEEE arithmetic; no other cell's record depends on them.
+ *   Refused with -1, PvAmdLastError "set history plane: ...": a null handle or plane, t outside [0, T), no completed run, sparse-
+ * emitter (PVA_OPT_STREAMING_ANALYSIS) solvers, slab groups and slab ranks. */
+PVA_EXPORT int PvAmdSetHistoryPlane(PvAmdSolver* s, int t, const float* pr);
 /* ---- Room metrics: clarity C50 / C80, definition D50 and centre time Ts (ISO 3382) of every reached cell ----
  * The recorded pressure of a reached cell is the impulse response from the listener to that cell; PvAmdComputeRoomMetrics
  * reduces the history of the LAST COMPLETED run to one record per cell in one pass on the device (pv_metrics.hip).

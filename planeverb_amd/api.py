@@ -286,6 +286,8 @@ SYMBOLS = {
     "PvAmdGetImpulseResponseCells": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(PlaneverbCell)]),
     "PvAmdCopyFields": (C.c_int, [_vp, _fp, _fp, _fp]),
     "PvAmdCopyHistoryPlane": (C.c_int, [_vp, C.c_int, _fp]),
+    "PvAmdSetHistoryPlane": (C.c_int, [_vp, C.c_int, _fp]),
+    "PvAmdLibmProbe": (C.c_int, [C.c_int, _fp, _fp, C.c_longlong, C.c_int]),
     "PvAmdComputeRoomMetrics": (C.c_int, [_vp, _fp]),
     "PvAmdCopyRoomMetrics": (C.c_int, [_vp, _fp]),
     "PvAmdCopyRoomMetricsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
@@ -1137,6 +1139,22 @@ def bandwidth_probe(device=0):
     return {"copy_x4": float(v[0]), "copy_dword": float(v[1]), "read_dword": float(v[2]), "write_dword": float(v[3])}
 
 
+# PVA_LIBM_*: the forms of csrc/pv_libm.h that libm_probe evaluates
+LIBM_FORMS = ("log10", "log10_nonneg", "log10_nonneg_tab", "log10_normal_tab", "log10_normal_batch", "pow_08", "pow_23",
+              "pow_nonneg_08", "pow_nonneg_23", "pow_nonneg_tab_08", "pow_nonneg_tab_23")
+LIBM_NORMAL_ONLY = ("log10_normal_tab", "log10_normal_batch")  # defined for positive normal finite inputs only
+
+
+def libm_probe(form, x, on_device=True):
+    """PvAmdLibmProbe: float32, the shape of x -- the library's own log10f / powf in the form named (LIBM_FORMS, or its index) of
+    every x, evaluated by the device compile on the current device (the tables in LDS) or by the same source on the host"""
+    f = LIBM_FORMS.index(form) if isinstance(form, str) else int(form)
+    a = np.ascontiguousarray(x, np.float32)
+    out = np.empty_like(a)
+    _check(lib().PvAmdLibmProbe(f, _f(a) if a.size else None, _f(out) if a.size else None, int(a.size), 1 if on_device else 0))
+    return out
+
+
 def device_count():
     return lib().PvAmdDeviceCount()
 
@@ -1789,6 +1807,14 @@ class Solver:
         out = np.empty((self.gx + 1, self.gy + 1), np.float32)
         _check(lib().PvAmdCopyHistoryPlane(self._h, int(t), _f(out)))
         return out
+
+    def set_history_plane(self, t, plane):
+        """PvAmdSetHistoryPlane, the inverse of history_plane (a test seam): plane = float32 [gx + 1, gy + 1] into the stored cells
+        of step t of the last completed run; every analysis map becomes "not computed" """
+        a = np.ascontiguousarray(plane, np.float32)
+        if a.shape != (self.gx + 1, self.gy + 1):
+            raise ValueError("set_history_plane: a plane [gx + 1, gy + 1], as history_plane returns it")
+        _check(lib().PvAmdSetHistoryPlane(self._h, int(t), _f(a)))
 
     # The nine per-cell analysis kinds share four call shapes: compute -> device milliseconds, the whole map, a block of it, the
     # record at a position; `width` = the trailing dimensions of a record

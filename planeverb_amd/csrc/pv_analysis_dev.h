@@ -250,6 +250,9 @@ __device__ __forceinline__ void rowScan2(float& accA, const float aA, float& acc
 #ifndef PV_RT60_AHEAD
 #define PV_RT60_AHEAD 4
 #endif
+#ifndef PV_RT60_TILE_S
+#define PV_RT60_TILE_S 8  // samples per chunk of the lane-per-cell form (pv_rt60.hip): the N of its pvLog10fNormalBatch
+#endif
 constexpr int kRt60Ahead = PV_RT60_AHEAD;  // chunks of history loads in flight per wave in the sixteen- and four-lane decay-time forms
 
 // every lane of the wave must call; live / s / hc / startingPointIn are the values of the lane's cell (the same in the 16

@@ -1053,6 +1053,10 @@ int PvAmdBandwidthProbe(int device, float* gbPerS4) try {
     return -1;
 } PV_API_CATCH(-1)
 
+int PvAmdLibmProbe(int form, const float* in, float* out, long long n, int onDevice) try {
+    return libmProbe(form, in, out, n, onDevice != 0, &g_lastError) ? 0 : -1;
+} PV_API_CATCH(-1)
+
 int PvAmdGetTimings(PvAmdSolver* h, PvAmdTimings* out) try {
     if (!out || !ensure(h, true)) return -1;
     const SolverTimings& t = h->g ? h->g->timings() : h->s->timings();
@@ -1244,6 +1248,12 @@ static bool analysisCall(PvAmdSolver* h, const char* pre, const char* fn, const 
     if (!out) g_lastError = std::string(pre) + fn + ": null output";
     return out != nullptr;
 }
+
+// the inverse of PvAmdCopyHistoryPlane, with the analysis passes' refusals (what it feeds)
+int PvAmdSetHistoryPlane(PvAmdSolver* h, int t, const float* pr) try {
+    if (!analysisCall(h, "set history plane: ", __func__, pr)) return -1;
+    return ret(h, h->s->setHistoryPlane(t, pr));
+} PV_API_CATCH(-1)
 
 static int analysisCopy(PvAmdSolver* h, AnalysisKind k, const char* pre, const char* fn, float* out) {
     if (!analysisCall(h, pre, fn, out)) return -1;

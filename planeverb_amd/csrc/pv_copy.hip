@@ -293,6 +293,20 @@ __global__ void pv_histplane_kernel(const AnalyzeArgs a, int t, float* dense, in
     }
     dense[(size_t)x * NY + y] = v;
 }
+// the inverse (PvAmdSetHistoryPlane, a test seam): dense order -> recorded pressure plane t, through the same window, tile and
+// tileFirst tests; a cell that is not stored at step t is left out, so that the read-back gives 0 there as before
+__global__ void pv_set_histplane_kernel(const AnalyzeArgs a, int t, const float* dense, int NX, int NY, int histRows,
+                                        float* hist) {
+    const int y = blockIdx.x * blockDim.x + threadIdx.x;
+    const int x = blockIdx.y;
+    if (y >= NY || x >= NX) return;
+    const DynParams dyn = *a.dyn;
+    const int hr = x + a.G - dyn.histRow0, hcn = y + a.G - dyn.histCol0;
+    if (hr >= 0 && hr < histRows && hcn >= 0 && hcn < dyn.histTilesY * a.wi) {
+        const int tF = a.tileFirst[(x / a.rxi) * a.nty + (y / a.wi)];
+        if (t >= tF) hist[(long long)t * a.histPlane + histOffset(hr, hcn, a.rxi, a.wi, dyn.histTilesY)] = dense[(size_t)x * NY + y];
+    }
+}
 
 void launchUnpad(const float* padded, float* dense, const Geometry& g, hipStream_t stream) {
     dim3 grid((g.NY + 255) / 256, g.NX);
@@ -306,6 +320,11 @@ void launchHistPlane(const AnalyzeArgs& a, int t, float* dense, int NX, int NY, 
                      hipStream_t stream) {
     dim3 grid((NY + 255) / 256, NX);
     hipLaunchKernelGGL(pv_histplane_kernel, grid, dim3(256), 0, stream, a, t, dense, NX, NY, histRows);
+}
+void launchSetHistPlane(const AnalyzeArgs& a, int t, const float* dense, int NX, int NY, int histRows, float* hist,
+                        hipStream_t stream) {
+    dim3 grid((NY + 255) / 256, NX);
+    hipLaunchKernelGGL(pv_set_histplane_kernel, grid, dim3(256), 0, stream, a, t, dense, NX, NY, histRows, hist);
 }
 
 }  // namespace pva

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 
 #include "pv_device.h"
 
@@ -71,6 +72,23 @@ bool streamsShareQueue(hipStream_t a, hipStream_t b, unsigned long long* stamps)
 float clockProbeMHz(int device, float* byMemtime);
 // the device's own streaming bandwidth in GB/s: {copy 16 B per lane, copy 4 B per lane, read only, write only} (pv_probe.hip)
 bool bandwidthProbeGBs(int device, float out[4]);
+// one form of pv_libm.h per input (pv_probe.hip; PVA_LIBM_* of include/planeverb_amd.h): on the current device with the analysis
+// kernels' LDS tables, or the same header on the host
+enum LibmForm {
+    kLibmLog10 = 0,         // pvLog10f
+    kLibmLog10NonNeg,       // pvLog10fNonNeg
+    kLibmLog10NonNegTab,    // pvLog10fNonNegT<LogTabLds>
+    kLibmLog10NormalTab,    // pvLog10fNormalT<LogTabLds>      (normal positive inputs only)
+    kLibmLog10NormalBatch,  // pvLog10fNormalBatch<LogTabLds>  (likewise)
+    kLibmPow08,             // pvPowf(x, 0.8f)
+    kLibmPow23,             // pvPowf(x, (float)(2.0 / 3.0))
+    kLibmPowNonNeg08,       // pvPowfNonNeg(x, 0.8f)
+    kLibmPowNonNeg23,
+    kLibmPowNonNegTab08,    // pvPowfNonNegT<PowTabLds>(x, 0.8f)
+    kLibmPowNonNegTab23,
+    kLibmForms
+};
+bool libmProbe(int form, const float* in, float* out, long long n, bool onDevice, std::string* err);
 // error flag, {cells of non-zero tiles, cells with an onset}, resident claim counter (or NULL) -> 4 ints of pinned host memory
 void launchRunStatus(int* err, int* counts, const unsigned* claims, int* outHost, hipStream_t stream);
 
@@ -230,5 +248,7 @@ void launchUnpad(const float* padded, float* dense, const Geometry& g, hipStream
 void launchPad(const float* dense, float* padded, const Geometry& g, hipStream_t stream);
 void launchHistPlane(const AnalyzeArgs& a, int t, float* dense, int NX, int NY, int histRows,
                      hipStream_t stream);
+void launchSetHistPlane(const AnalyzeArgs& a, int t, const float* dense, int NX, int NY, int histRows, float* hist,
+                        hipStream_t stream);
 
 }  // namespace pva

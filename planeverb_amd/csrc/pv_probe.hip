@@ -1,13 +1,20 @@
-// pv_probe.hip -- the shader clock the chip sustains right now, for bench.py's device record.
+// pv_probe.hip -- probes: the shader clock the chip sustains right now and the streaming bandwidth, for bench.py's device record;
+// the device's own evaluation of pv_libm.h, for the tests (libmProbe, at the end).
 // One wave sleeps 100 x s_sleep 127 = 812 800 shader-clock cycles and times that with s_memrealtime (constant 100 MHz): the
 // clock of the moment it runs in, whatever else the chip is doing (tools/clock_probe.hip, made callable).  Launched on a
 // stream of its own so that it can sit beside the solvers' launches.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
+#include "pv_analysis_dev.h"
+#include "pv_echo_dev.h"
 #include "pv_launch.h"
+#include "pv_libm.h"
 
 namespace pva {
 
@@ -164,6 +171,98 @@ bool bandwidthProbeGBs(int device, float out[4]) {
     if (st) hipStreamDestroy(st);
     for (float* p : {a, b, sink})
         if (p) hipFree(p);
+    return ok;
+}
+
+// The device's own libm (PvAmdLibmProbe): one form of pv_libm.h per input, as the amdgcn compile of this library evaluates it --
+// fused pairs, the staged batch with its scheduling barriers, and the tables in LDS, filled by the analysis kernels' own
+// fillLogTab / fillPowTab -- or, onDevice = 0, the same header on the host (the table functors are then the constant ones).
+// The batch form takes the N = PV_RT60_TILE_S arguments of an evaluation from N places of the input that lie ceil(n / N) apart
+// (1.0f past the end); the normal-only forms (3, 4) are for pvIsNormalPositive inputs.
+namespace {
+constexpr int kLibmBatch = PV_RT60_TILE_S;
+constexpr float kPow23 = (float)(2.0 / 3.0);
+
+template <class LogTab, class PowTab>
+PV_HD inline float libmForm(int form, float x, const LogTab& lt, const PowTab& pt) {
+    switch (form) {
+        case kLibmLog10: return pvLog10f(x);
+        case kLibmLog10NonNeg: return pvLog10fNonNeg(x);
+        case kLibmLog10NonNegTab: return pvLog10fNonNegT(x, lt);
+        case kLibmLog10NormalTab: return pvLog10fNormalT(x, lt);
+        case kLibmPow08: return pvPowf(x, 0.8f);
+        case kLibmPow23: return pvPowf(x, kPow23);
+        case kLibmPowNonNeg08: return pvPowfNonNeg(x, 0.8f);
+        case kLibmPowNonNeg23: return pvPowfNonNeg(x, kPow23);
+        case kLibmPowNonNegTab08: return pvPowfNonNegT(x, 0.8f, pt);
+        default: return pvPowfNonNegT(x, kPow23, pt);  // kLibmPowNonNegTab23
+    }
+}
+
+template <class LogTab>
+PV_HD inline void libmBatch(const float* in, float* out, long long n, long long nb, long long b, const LogTab& lt) {
+    float x[kLibmBatch], y[kLibmBatch];
+#pragma unroll
+    for (int k = 0; k < kLibmBatch; ++k) {
+        const long long i = b + (long long)k * nb;
+        x[k] = i < n ? in[i] : 1.0f;
+    }
+    pvLog10fNormalBatch(x, y, lt);
+#pragma unroll
+    for (int k = 0; k < kLibmBatch; ++k) {
+        const long long i = b + (long long)k * nb;
+        if (i < n) out[i] = y[k];
+    }
+}
+
+__global__ __launch_bounds__(256) void pv_libm_probe_kernel(int form, const float* __restrict__ in, float* __restrict__ out,
+                                                             long long n) {
+    __shared__ double logTab[96];
+    __shared__ double powLt[32];
+    __shared__ uint64_t powEt[32];
+    fillLogTab(logTab, threadIdx.x, 256);
+    fillPowTab(powLt, powEt, (int)threadIdx.x);
+    __syncthreads();
+    const LogTabLds lt{logTab};
+    const PowTabLds pt{powLt, powEt};
+    const long long stride = (long long)gridDim.x * blockDim.x, first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (form == kLibmLog10NormalBatch) {
+        const long long nb = (n + kLibmBatch - 1) / kLibmBatch;
+        for (long long b = first; b < nb; b += stride) libmBatch(in, out, n, nb, b, lt);
+        return;
+    }
+    for (long long i = first; i < n; i += stride) out[i] = libmForm(form, in[i], lt, pt);
+}
+}  // namespace
+
+bool libmProbe(int form, const float* in, float* out, long long n, bool onDevice, std::string* err) {
+    if (form < 0 || form >= kLibmForms) return *err = "libm probe: unknown form", false;
+    if (n < 0 || (n > 0 && (!in || !out))) return *err = "libm probe: null input or output", false;
+    if (n == 0) return true;
+    if (!onDevice) {
+        const PvLogTabConst lt{};
+        const PvPowTabConst pt{};
+        if (form == kLibmLog10NormalBatch) {
+            const long long nb = (n + kLibmBatch - 1) / kLibmBatch;
+            for (long long b = 0; b < nb; ++b) libmBatch(in, out, n, nb, b, lt);
+        } else {
+            for (long long i = 0; i < n; ++i) out[i] = libmForm(form, in[i], lt, pt);
+        }
+        return true;
+    }
+    float *dIn = nullptr, *dOut = nullptr;
+    const size_t bytes = (size_t)n * 4;
+    bool ok = hipMalloc((void**)&dIn, bytes) == hipSuccess && hipMalloc((void**)&dOut, bytes) == hipSuccess &&
+              hipMemcpy(dIn, in, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        const unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(pv_libm_probe_kernel, dim3(blocks), dim3(256), 0, nullptr, form, dIn, dOut, n);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(out, dOut, bytes, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (dIn) hipFree(dIn);
+    if (dOut) hipFree(dOut);
+    if (!ok) *err = "libm probe: allocation, copy or launch failed";
     return ok;
 }
 

@@ -31,9 +31,7 @@
 #include "pv_libm.h"
 #include "pv_prims.h"
 
-#ifndef PV_RT60_TILE_S
-#define PV_RT60_TILE_S 8  // samples per chunk of the lane-per-cell form
-#endif
+// (PV_RT60_TILE_S, samples per chunk of the lane-per-cell form: pv_analysis_dev.h -- the libm probe of pv_probe.hip batches as many)
 #ifndef PV_RT60_TILE_NB
 #define PV_RT60_TILE_NB 4  // chunks of loads in flight per wave
 #endif

@@ -2895,6 +2895,23 @@ bool Solver::copyHistoryPlane(int t, float* pr) {
     return hipOk(hipStreamSynchronize(stream_), "plane sync");
 }
 
+// the inverse of copyHistoryPlane (a test seam: histories the stencil never produces in front of the analysis passes)
+bool Solver::setHistoryPlane(int t, const float* pr) {
+    if (isSlab()) return fail("set history plane: not available on a slab");
+    if (opt_.streaming) return fail("set history plane: the full pressure history is not kept in streaming-analysis mode");
+    if (t < 0 || t >= T_) return fail("set history plane: step outside the recorded range");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("set history plane: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("set history plane: the last run ended in error");
+    invalidateAnalysisMaps();  // (the history the records were made from changes)
+    if (!hipOk(hipMemcpyAsync(scratch_, pr, (size_t)g_.NX * g_.NY * 4, hipMemcpyHostToDevice, stream_), "set history plane upload"))
+        return false;
+    launchSetHistPlane(analyzeArgs(lastLx_, lastLz_), t, scratch_, g_.NX, g_.NY, histRows_, hist_, stream_);
+    return hipOk(hipGetLastError(), "set history plane launch") && hipOk(hipStreamSynchronize(stream_), "set history plane sync");
+}
+
 bool Solver::copyPulse(float* out) {
     std::memcpy(out, pulse_.data(), (size_t)g_.T * 4);
     return true;

@@ -288,6 +288,9 @@ public:
     bool copyFields(float* pr, float* vx, float* vy);
     bool setFields(const float* pr, const float* vx, const float* vy);
     bool copyHistoryPlane(int t, float* pr);
+    // the inverse (a test seam): NX x NY floats into the stored cells of plane t; waits for a run in flight, leaves every
+    // analysis map "not computed" and the run's results, onsets, tileFirst and query records alone
+    bool setHistoryPlane(int t, const float* pr);
     // Per-cell analysis maps of the last completed run (pv_solver_maps.cpp; include/planeverb_amd.h names the records): nine
     // kinds (AnalysisKind), each one pass over the run's history on stream_, synchronised before computeX returns; *ms
     // (optional) = its device time.  A kind's records stay valid until the next run, geometry, boundary or layer change, or a
