@@ -1336,8 +1336,9 @@ PVA_EXPORT int PvAmdHostZoneRects(float dx, int gx, int gy, const float* rect4, 
  * PvAmdHostZoneDecay ends with.  PvAmdHostZoneDecay applies the whole rule on the CPU, bit for bit.
  * Device storage: the zone scratch of the zone statistics, grown on demand -- 8 bytes per zone, result row and time slot in
  * flight, the slots dealt in chunks that keep it within 32 MiB, plus nZones x T doubles and 12 bytes per zone and result row.
- * Out of scope: normalising each cell by its own E0, per-band curves, clarity and centre time of a zone, in-run or live-module
- * records, overlapping zones, slab groups, slab ranks and sparse-emitter solvers. */
+ * Per-band curves and the clarity and centre time of a zone's curve: the zone band decay below.
+ * Out of scope: normalising each cell by its own E0, in-run or live-module records, overlapping zones, slab groups, slab ranks
+ * and sparse-emitter solvers. */
 #define PVA_ZONE_DECAY_ABSOLUTE 0
 #define PVA_ZONE_DECAY_ONSET    1
 typedef struct PvAmdZoneDecay {
@@ -1358,6 +1359,64 @@ PVA_EXPORT int PvAmdZoneDecayChunkSlots(PvAmdSolver* s);
  * The labels are checked by the rule of PvAmdSetZones; an onset of a labelled cell outside 0 .. T - 1 is refused */
 PVA_EXPORT int PvAmdHostZoneDecay(const float* p, const float* delay, int gx, int gy, int T, int fs, const unsigned char* labels,
                                   int nZones, int align, PvAmdZoneDecay* out, double* etc, double* edc);
+/* ---- Zone band decay: the ensemble decay curve of a receiver area PER OCTAVE OR THIRD-OCTAVE BAND, and the clarity of a curve ----
+ * ISO 3382-2 reports an area's reverberation time per band.  The average of the positions' band decay times is the zone
+ * statistics of PVA_MAP_BAND_METRICS; this is the other method, one ensemble curve per zone AND band: the band-filtered histories
+ * squared, summed, integrated backwards.  PvAmdComputeZoneBandDecay reduces the FILTERED history, [T][cells] -> [zones][bands][T],
+ * ON THE DEVICE (pv_zone_band_decay.hip); only nZones x nBands x T doubles and the records cross to the host.
+ * Inputs: the last completed run, the labels of PvAmdSetZones, the bands of PvAmdSetBands (nBands >= 1) and align.  Definition,
+ * for zone z and band b:
+ *   members, t0(s), n_cells, t_first, t_last   PvAmdZoneDecay's, word for word; they do not depend on the band;
+ *   y_{s,b}(t)  the band-metrics filter, word for word: the ten float32 coefficients PvAmdGetBandCoefs returns for band b, two
+ *            sections in transposed direct form II, float32, every product and sum rounded on its own (no FMA), denormals kept;
+ *            state +0.0f at t = T - 1, walking t = T - 1 DOWN TO t0(s) and stopping there; x(t) is exactly what
+ *            PvAmdCopyHistoryPlane(t) gives at array cell (X, Y); nothing below t0(s) is read;
+ *   slot     of a sample: PVA_ZONE_DECAY_ABSOLUTE j = t; PVA_ZONE_DECAY_ONSET j = t - t0(s);
+ *   etc[z][b][j]  j = 0 .. T - 1: the three-level sum of the zone statistics, unchanged -- butterfly over blocks of 64 consecutive
+ *            Y, the blocks of a row sequentially, the rows sequentially in X, each from +0.0 -- applied to v(X, Y) = (double)y *
+ *            (double)y (exact in double) for a member whose sample for slot j exists and +0.0 for every other cell.  Blocks and
+ *            rows without such a member are skipped, which changes no bit: no sum here is ever -0.0 (every term is a square or
+ *            +0.0), so adding +0.0 to it returns it;
+ *   edc, edt, t20, t30, e0, depth, n_*   the finish of PvAmdZoneDecay applied to etc[z][b], unchanged and shared (one function);
+ *   clarity  of the curve (double throughout, the host libm's log10, nothing fused): j0 and tailN as in the fits (an empty zone:
+ *            j0 = 0); n50 = (int)(0.05f * (float)fs), n80 = (int)(0.08f * (float)fs); m50 = min(j0 + n50, T); l50 = edc[m50] with
+ *            edc[T] = +0.0; e50 = the sum of etc[j] for j = j0 .. m50 - 1 in increasing j from +0.0; e80, l80 likewise; moment =
+ *            the sum of (double)(j - j0) * etc[j] for j = j0 .. T - 1 in increasing j; c50 = 10 * log10(e50 / l50), c80 likewise;
+ *            d50 = e50 / (e50 + l50); ts = (moment / e0) / (double)fs.  Nothing is special-cased: an empty zone has quiet NaNs.
+ *            These are the ISO 3382-1 quantities in ONSET alignment.  In ABSOLUTE alignment they are measured from the zone's FIRST
+ *            onset and mix the cells' travel times.
+ * The device computes etc and the three integers; the rest is finished on the host by the function PvAmdHostZoneBandDecay ends
+ * with.  Time is not cut into chunks (the filter state crosses them): the pass deals its work in chunks of (zone, band) pairs.
+ * Device storage: the zone scratch, grown on demand -- per (zone, band) pair in flight gx rows of T doubles; all bands of as many
+ * whole zones as stay within 32 MiB, or one zone and as many bands as stay within it; where ONE pair's rows exceed 32 MiB, one
+ * pair's rows are what it takes -- plus nZones x nBands x T doubles and 12 bytes per zone and result row.
+ * Out of scope: in-run or live-module zone records, overlapping zones, normalising each cell by its own E0, slab groups, slab
+ * ranks and sparse-emitter solvers (refused). */
+typedef struct PvAmdZoneBandDecay {
+    double edt, t20, t30, e0, depth, c50, c80, d50, ts;
+    int n_edt, n_t20, n_t30, n_cells, t_first, t_last;
+} PvAmdZoneBandDecay; /* 96 bytes */
+/* The records of the current zones and bands for the last completed run: out[(z - 1) * nBands + b]; returns nZones x nBands, or
+ * -1 with PvAmdLastError.  etc / edc (optional): nZones x nBands x T doubles each, zone-major then band.  *ms (optional): device
+ * time of the passes.  Synchronous on the solver's own stream (waits for a run in flight).  Nothing is cached and nothing
+ * invalidated: no map, plan or run chain is touched, and every call reads the bands as set at that moment.  Refused ("zone band
+ * decay: ..."): what PvAmdComputeZoneDecay refuses, no bands set, cap < nZones x nBands */
+PVA_EXPORT int PvAmdComputeZoneBandDecay(PvAmdSolver* s, int align, PvAmdZoneBandDecay* out, int cap, double* etc, double* edc,
+                                         float* ms);
+/* how PvAmdComputeZoneBandDecay deals its work under the current zones and bands: returns the number of chunks of (zone, band)
+ * pairs (0: no zones or no bands set); *slots (optional) = the time slots of a chunk (T: time is never cut), *bands (optional) =
+ * the bands of a chunk */
+PVA_EXPORT int PvAmdZoneBandDecayChunk(PvAmdSolver* s, int* slots, int* bands);
+/* CPU only: the whole rule applied to a history p[t * gx * gy + X * gy + Y] of T planes, an onset map delay[X * gy + Y]
+ * (FLT_MAX: none) and nBands (1 .. PVA_BANDS_MAX) coefficient sets of ten floats (PvAmdHostBandCoefs / PvAmdGetBandCoefs); out =
+ * nZones x nBands records, etc / edc (optional) = nZones x nBands x T doubles.  The restatement the kernels are held to.  Labels
+ * and onsets are checked as by PvAmdHostZoneDecay */
+PVA_EXPORT int PvAmdHostZoneBandDecay(const float* p, const float* delay, int gx, int gy, int T, int fs, const unsigned char* labels,
+                                      int nZones, const float* coefs10n, int nBands, int align, PvAmdZoneBandDecay* out, double* etc,
+                                      double* edc);
+/* CPU only: the clarity rule above applied to ANY energy-time curve etc[T] whose beginning is slot j0 (0 <= j0 < T): out4 = c50,
+ * c80, d50, ts.  With the etc of PvAmdComputeZoneDecay it gives the broadband curve its clarity and centre time */
+PVA_EXPORT int PvAmdHostZoneCurveClarity(const double* etc, int T, int fs, int j0, double out4[4]);
 /* Gaussian pulse table (Grid.cpp:12-27), T floats */
 PVA_EXPORT int PvAmdCopyPulse(PvAmdSolver* s, float* out);
 /* Material planes after rasterisation: beta (uint8) and R (float), (gx+1)*(gy+1) each (with shapes: the composed material) */

@@ -80,6 +80,18 @@ def zone_tables(s, a):
             if a.zone_decay_curves:
                 t["zoneDecay"]["etc"] = [float(v) for v in e]
                 t["zoneDecay"]["edc"] = [float(v) for v in d]
+    if a.zone_band_decay:
+        recs, etc, edc = s.zone_band_decay(a.zone_decay, curves=True)
+        for t, rz, ez, dz in zip(tables, recs, etc, edc):
+            t["zoneBandDecay"] = []
+            for hz, r, e, d in zip(a.bands, rz, ez, dz):
+                b = {"hz": hz, "align": a.zone_decay, "edt": float(r["edt"]), "t20": float(r["t20"]), "t30": float(r["t30"]),
+                     "depth": float(r["depth"]), "nEdt": int(r["n_edt"]), "nT20": int(r["n_t20"]), "nT30": int(r["n_t30"]),
+                     "c50": float(r["c50"]), "c80": float(r["c80"]), "d50": float(r["d50"]), "ts": float(r["ts"])}
+                if a.zone_decay_curves:
+                    b["etc"] = [float(v) for v in e]
+                    b["edc"] = [float(v) for v in d]
+                t["zoneBandDecay"].append(b)
     return tables
 
 
@@ -176,6 +188,10 @@ def main(argv=None):
                          "or since each cell's onset (onset) --: nCells, tFirst, tLast, EDT, T20, T30, depth and the point counts")
     ap.add_argument("--zone-decay-curves", action="store_true",
                     help="with --zone-decay: add the curves themselves, etc (energy per step) and edc (its backward sum)")
+    ap.add_argument("--zone-band-decay", action="store_true",
+                    help="with --zone-decay and --bands: add per zone a zoneBandDecay list, one entry per band -- the ensemble decay "
+                         "curve of the band-filtered responses, reduced on the GPU in the alignment of --zone-decay: EDT, T20, T30, "
+                         "depth, the point counts and the curve's C50, C80, D50 and Ts (with --zone-decay-curves: etc and edc too)")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
@@ -187,6 +203,8 @@ def main(argv=None):
         ap.error("--zone-decay: needs --zone")
     if a.zone_decay_curves and not a.zone_decay:
         ap.error("--zone-decay-curves: needs --zone-decay")
+    if a.zone_band_decay and not (a.zone_decay and a.bands):
+        ap.error("--zone-band-decay: needs --zone-decay and --bands")
     if len(a.zone) > api.ZONES_MAX:
         ap.error("--zone: at most %d zones" % api.ZONES_MAX)
     boxes = api.load_pv(a.scene)

@@ -358,6 +358,11 @@ SYMBOLS = {
     "PvAmdHostZoneRects": (C.c_int, [C.c_float, C.c_int, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
     "PvAmdComputeZoneDecay": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _fp]),
     "PvAmdZoneDecayChunkSlots": (C.c_int, [_vp]),
+    "PvAmdComputeZoneBandDecay": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _fp]),
+    "PvAmdZoneBandDecayChunk": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "PvAmdHostZoneBandDecay": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.POINTER(C.c_ubyte), C.c_int, _fp, C.c_int, C.c_int, _vp,
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "PvAmdHostZoneCurveClarity": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "PvAmdHostZoneDecay": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.POINTER(C.c_ubyte), C.c_int, C.c_int, _vp, C.POINTER(C.c_double),
                                                                    C.POINTER(C.c_double)]),
     "PvAmdCopyPulse": (C.c_int, [_vp, _fp]),
@@ -1116,6 +1121,43 @@ def host_zone_decay(p, delay, fs, labels, n_zones=None, align="absolute"):
                                     lab.ctypes.data_as(C.POINTER(C.c_ubyte)), n, _zone_decay_align(align), out.ctypes.data_as(_vp),
                                     etc.ctypes.data_as(_dp), edc.ctypes.data_as(_dp)))
     return out, etc, edc
+
+
+# PvAmdZoneBandDecay (96 bytes): PvAmdZoneDecay with the clarity of the curve behind depth
+ZONE_BAND_DECAY_DTYPE = np.dtype([("edt", "<f8"), ("t20", "<f8"), ("t30", "<f8"), ("e0", "<f8"), ("depth", "<f8"), ("c50", "<f8"),
+                                  ("c80", "<f8"), ("d50", "<f8"), ("ts", "<f8"), ("n_edt", "<i4"), ("n_t20", "<i4"), ("n_t30", "<i4"),
+                                  ("n_cells", "<i4"), ("t_first", "<i4"), ("t_last", "<i4")])
+assert ZONE_BAND_DECAY_DTYPE.itemsize == 96
+
+
+def host_zone_band_decay(p, delay, fs, labels, coefs, n_zones=None, align="absolute"):
+    """PvAmdHostZoneBandDecay: the zone band decay of include/planeverb_amd.h (PvAmdZoneBandDecay) on the CPU -- p, delay, labels,
+    n_zones and align as for host_zone_decay, coefs = float32 [n_bands, 10] (host_band_coefs / Solver.band_coefs); (records
+    [n_zones, n_bands] of ZONE_BAND_DECAY_DTYPE, etc float64 [n_zones, n_bands, T], edc float64 [n_zones, n_bands, T])"""
+    h = np.ascontiguousarray(p, np.float32)
+    d = np.ascontiguousarray(delay, np.float32)
+    c = np.ascontiguousarray(coefs, np.float32).reshape(-1, 10)
+    lab, n = _zone_labels(labels, n_zones)
+    if h.ndim != 3 or d.shape != h.shape[1:] or lab.shape != h.shape[1:]:
+        raise ValueError("host_zone_band_decay: a history [T, gx, gy], onsets [gx, gy] and labels [gx, gy]")
+    T, nb = h.shape[0], c.shape[0]
+    out = np.zeros((max(n, 0), nb), ZONE_BAND_DECAY_DTYPE)
+    etc, edc = np.zeros((max(n, 0), nb, T)), np.zeros((max(n, 0), nb, T))
+    _check(lib().PvAmdHostZoneBandDecay(_f(h) if h.size else None, _f(d) if d.size else None, h.shape[1], h.shape[2], T, int(fs),
+                                        lab.ctypes.data_as(C.POINTER(C.c_ubyte)), n, _f(c) if c.size else None, nb,
+                                        _zone_decay_align(align), out.ctypes.data_as(_vp), etc.ctypes.data_as(_dp),
+                                        edc.ctypes.data_as(_dp)))
+    return out, etc, edc
+
+
+def host_zone_curve_clarity(etc, fs, j0):
+    """PvAmdHostZoneCurveClarity: float64 [4] = c50, c80, d50, ts of the energy-time curve etc[T] whose beginning is slot j0 -- the
+    clarity rule of include/planeverb_amd.h (PvAmdZoneBandDecay); with the etc of Solver.zone_decay: the broadband curve's"""
+    e = np.ascontiguousarray(etc, np.float64).reshape(-1)
+    out = np.zeros(4)
+    _check(lib().PvAmdHostZoneCurveClarity(e.ctypes.data_as(_dp) if e.size else None, int(e.size), int(fs), int(j0),
+                                           out.ctypes.data_as(_dp)))
+    return out
 
 
 def host_cells(size_x, size_y, res, x, z):
@@ -2152,6 +2194,36 @@ class Solver:
         if n < 0:
             raise PlaneverbError(last_error())
         return n
+
+    def zone_band_decay(self, align="absolute", curves=False, with_ms=False):
+        """PvAmdComputeZoneBandDecay: the ensemble decay curve of every zone of set_zones PER BAND of set_bands over the last
+        completed run -- the band-filtered histories of the zone's reached cells squared and summed on the device -- with EDT, T20,
+        T30 and the clarity (c50, c80, d50, ts) read off it: records [n_zones, n_bands] of ZONE_BAND_DECAY_DTYPE; curves: (records,
+        etc, edc), float64 [n_zones, n_bands, T] each; with_ms: the device milliseconds appended"""
+        nz, fr = C.c_int(0), C.c_int(1)
+        lib().PvAmdGetZones(self._h, None, C.byref(nz))  # (a handle it refuses has no zones: the call below says why, in its own words)
+        hz = np.empty(BANDS_MAX, np.float32)
+        n, nb = nz.value, max(lib().PvAmdGetBands(self._h, _f(hz), BANDS_MAX, C.byref(fr)), 0)
+        out = np.zeros((max(n, 1), max(nb, 1)), ZONE_BAND_DECAY_DTYPE)
+        etc = np.zeros((max(n, 1), max(nb, 1), self.T)) if curves else None
+        edc = np.zeros((max(n, 1), max(nb, 1), self.T)) if curves else None
+        ms = C.c_float(0.0)
+        got = lib().PvAmdComputeZoneBandDecay(self._h, _zone_decay_align(align), out.ctypes.data_as(_vp), n * nb,
+                                              etc.ctypes.data_as(_dp) if curves else None,
+                                              edc.ctypes.data_as(_dp) if curves else None, C.byref(ms))
+        if got < 0:
+            raise PlaneverbError(last_error())
+        res = (out[:n, :nb],) + ((etc[:n, :nb], edc[:n, :nb]) if curves else ()) + ((ms.value,) if with_ms else ())
+        return res[0] if len(res) == 1 else res
+
+    def zone_band_decay_chunk(self):
+        """PvAmdZoneBandDecayChunk: (chunks, slots, bands) -- the chunks of (zone, band) pairs zone_band_decay takes under the
+        current zones and bands, the time slots of a chunk (T: time is never cut) and the bands of a chunk"""
+        sl, bd = C.c_int(0), C.c_int(0)
+        n = lib().PvAmdZoneBandDecayChunk(self._h, C.byref(sl), C.byref(bd))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return n, sl.value, bd.value
 
     def pulse(self):
         """float32 [T]: the pulse table of a run (T = the run's steps; zero past the grid's own table)"""

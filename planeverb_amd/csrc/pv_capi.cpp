@@ -22,6 +22,7 @@
 #include "pv_query_records.h"
 #include "pv_query_spectral.h"
 #include "pv_spectrum.h"
+#include "pv_zone_band_decay.h"
 #include "pv_zone_decay.h"
 #include "pv_zones.h"
 #ifndef PVA_HOST_TEST  // (tests/host/: HIP-less sanitizer build of the live module against a fake Solver)
@@ -461,9 +462,9 @@ const char* PlaneverbWorkerError(void) try {
 const char* PvAmdVersion(void) try { return "planeverb_amd 0.4.1 (gfx950)"; } PV_API_CATCH("")
 
 // (PvAmdComputeZoneDecay and PvAmdHostZoneDecay)
-static bool zoneDecayAlign(int align) {
+static bool zoneDecayAlign(int align, const char* pre = "zone decay: ") {
     if (align == kZoneDecayAbsolute || align == kZoneDecayOnset) return true;
-    g_lastError = "zone decay: align is PVA_ZONE_DECAY_ABSOLUTE or PVA_ZONE_DECAY_ONSET";
+    g_lastError = std::string(pre) + "align is PVA_ZONE_DECAY_ABSOLUTE or PVA_ZONE_DECAY_ONSET";
     return false;
 }
 
@@ -1621,6 +1622,21 @@ int PvAmdZoneDecayChunkSlots(PvAmdSolver* h) try {
     return h->s->zoneDecayChunkSlots();
 } PV_API_CATCH(-1)
 
+// zone band decay (pv_zone_band_decay.hip)
+static_assert(sizeof(PvAmdZoneBandDecay) == sizeof(ZoneBandDecay), "96 bytes");
+
+int PvAmdComputeZoneBandDecay(PvAmdSolver* h, int align, PvAmdZoneBandDecay* out, int cap, double* etc, double* edc, float* ms) try {
+    if (!analysisCall(h, "zone band decay: ", __func__, out) || !zoneDecayAlign(align, "zone band decay: ")) return -1;
+    int count = 0;
+    if (!h->s->computeZoneBandDecay(align, out, cap, etc, edc, ms, &count)) return ret(h, false);
+    return count;
+} PV_API_CATCH(-1)
+
+int PvAmdZoneBandDecayChunk(PvAmdSolver* h, int* slots, int* bands) try {
+    if (!analysisHandle(h, "zone band decay: ")) return -1;
+    return h->s->zoneBandDecayChunks(slots, bands);
+} PV_API_CATCH(-1)
+
 int PvAmdCopyPulse(PvAmdSolver* h, float* out) try {
     if (!out || !ensure(h, true)) return -1;
     return ret(h, h->g ? h->g->copyPulse(out) : h->s->copyPulse(out));
@@ -2148,6 +2164,37 @@ int PvAmdHostZoneDecay(const float* p, const float* delay, int gx, int gy, int T
         return -1;
     }
     zoneDecayOfHistory(p, delay, gx, gy, T, fs, labels, nZones, align, reinterpret_cast<ZoneDecay*>(out), etc, edc);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostZoneBandDecay(const float* p, const float* delay, int gx, int gy, int T, int fs, const unsigned char* labels, int nZones,
+                           const float* coefs10n, int nBands, int align, PvAmdZoneBandDecay* out, double* etc, double* edc) try {
+    if (!p || !delay || !coefs10n || !out || gx < 1 || gy < 1 || T < 1 || fs < 1 || (long long)gx * gy > INT_MAX || nBands < 1 ||
+        nBands > kBandsMax) {
+        g_lastError =
+            "zone band decay: PvAmdHostZoneBandDecay: a history of T planes of gx x gy floats, gx x gy onsets, gx, gy, T, fs >= 1, 1 .. 8 "
+            "coefficient sets (PVA_BANDS_MAX), and an output of nZones x nBands records";
+        return -1;
+    }
+    if (!zoneDecayAlign(align, "zone band decay: ")) return -1;
+    if (const char* e = zoneLabelsError(labels, (long long)gx * gy, nZones)) {
+        g_lastError = std::string("zone band decay: ") + (e + sizeof("zone statistics: ") - 1);
+        return -1;
+    }
+    if (const char* e = zoneDecayOnsetsError(delay, labels, (long long)gx * gy, T)) {
+        g_lastError = std::string("zone band decay: ") + (e + sizeof("zone decay: ") - 1);
+        return -1;
+    }
+    zoneBandDecayOfHistory(p, delay, gx, gy, T, fs, labels, nZones, coefs10n, nBands, align, reinterpret_cast<ZoneBandDecay*>(out), etc, edc);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostZoneCurveClarity(const double* etc, int T, int fs, int j0, double out4[4]) try {
+    if (!etc || !out4 || T < 1 || fs < 1 || j0 < 0 || j0 >= T) {
+        g_lastError = "zone band decay: PvAmdHostZoneCurveClarity: a curve etc[T], T, fs >= 1, 0 <= j0 < T and an output of four doubles";
+        return -1;
+    }
+    zoneCurveClarity(etc, T, fs, j0, out4);
     return 0;
 } PV_API_CATCH(-1)
 

@@ -161,6 +161,13 @@ struct ZoneCurveArgs;
 void launchZoneMembers(const ZoneCurveArgs& a, hipStream_t stream);
 void launchZoneCurves(const ZoneCurveArgs& a, bool onset, hipStream_t stream);
 
+// ---- pv_zone_band_decay.hip: per-zone ensemble decay curves per band
+// etc of one chunk of (zone, band) pairs -- zones a.zone0 + 1 .. a.zone0 + a.zones, bands a.band0 .. a.band0 + a.bands - 1 -- into
+// a.c.etc (nZones x nBands x T; pv_zone_band_decay.h); a.c.rows = a.zones x a.bands x gx x T doubles of scratch the caller has
+// cleared to +0.0; slot j = t (onset false) or t - t0 (true).  The members are launchZoneMembers'
+struct ZoneBandCurveArgs;
+void launchZoneBandCurves(const ZoneBandCurveArgs& a, bool onset, hipStream_t stream);
+
 // ---- pv_decay.hip: per-cell decay times
 // decay times (EDT, T20, T30) of the last completed run (pv_decay.hip): out = kDecayFloats planes of a.histPlane floats, indexed
 // by the cell's offset inside a history plane; NaN where the cell has no onset in that run.  twoLaunches: the two walks of the

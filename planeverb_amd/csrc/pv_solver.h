@@ -357,6 +357,13 @@ public:
     // zoneDecayChunkSlots: the time slots one pair of launches covers under the current zones (T and more: all of them at once)
     bool computeZoneDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count);
     int zoneDecayChunkSlots() const;
+    // Zone band decay (pv_zone_band_decay.hip; include/planeverb_amd.h PvAmdZoneBandDecay): the same curve per band of setBands,
+    // off the band-filtered history -- out = nZones x nBands records, etc / edc (either may be nullptr) = nZones x nBands x T
+    // doubles.  Nothing cached, no map, plan or run chain touched; the bands are read at the call; waits for a run in flight.
+    // zoneBandDecayChunks: the chunks of (zone, band) pairs the pass takes under the current zones and bands (0: none set), the
+    // slots (T: time is never cut) and the bands of one chunk
+    bool computeZoneBandDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count);
+    int zoneBandDecayChunks(int* slots, int* bands) const;
     bool copyPulse(float* out);
     bool copyMaterial(uint8_t* beta, float* R);
     bool freeFieldEnergyAt(int cellX, int cellY, int n, float r, float* out);
@@ -628,7 +635,9 @@ private:
     // result row one ZoneRow and one double (48 bytes), the planes dealt in chunks that keep it within kZoneScratchBytes (one
     // plane's where that is more), then the nZones x planes records; grown on demand, kept.  The zone-decay pass uses the same
     // scratch: per time slot in flight, zone and result row one double, the slots dealt in chunks within the same bound, then
-    // nZones x T doubles of curves and the zones' member rows and records
+    // nZones x T doubles of curves and the zones' member rows and records.  The zone-band-decay pass too: per (zone, band) pair in
+    // flight and result row T doubles, the pairs dealt in chunks within the same bound (one pair's where that is more), then nZones x
+    // nBands x T doubles of curves and the member rows and records
     bool growZoneScratch(size_t need);
     static constexpr size_t kZoneScratchBytes = 32u << 20;
     unsigned char* zoneLabels_ = nullptr;

@@ -19,6 +19,7 @@
 #include "pv_lobes.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
+#include "pv_zone_band_decay.h"
 #include "pv_zone_decay.h"
 #include "pv_zones.h"
 
@@ -403,6 +404,98 @@ bool Solver::computeZoneDecay(int align, void* out, int cap, double* etc, double
         zoneDecayFinish(etc + (size_t)z * T, edc ? edc + (size_t)z * T : edcHost.data(), T, (int)g_.fs, align, &recs[z]);
     }
     *count = nz;
+    return true;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// zone band decay (pv_zone_band_decay.hip): the same curve per band of setBands, off the band-filtered history
+// ----------------------------------------------------------------------------------------------------------------
+
+int Solver::zoneBandDecayChunks(int* slots, int* bands) const {
+    const auto inUse = queue_.lockUse();  // (setZones and setBands change what is read here under it)
+    const int nb = (int)bandHz_.size();
+    if (slots) *slots = T_;
+    if (bands) *bands = 0;
+    if (!zoneCount_ || !nb) return 0;
+    return pva::zoneBandDecayChunks(g_.gx, T_, zoneCount_, nb, kZoneScratchBytes, nullptr, bands);
+}
+
+bool Solver::computeZoneBandDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count) {
+    if (isSlab()) return fail("zone band decay: not available on a slab");
+    if (opt_.streaming) return fail("zone band decay: the full pressure history is not kept in streaming-analysis mode");
+    if (opt_.skipAnalysis) return fail("zone band decay: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (!zoneCount_) return fail("zone band decay: no zones set (PvAmdSetZones)");
+    const int T = T_, nz = zoneCount_, nBands = (int)bandHz_.size();
+    if (!nBands) return fail("zone band decay: no bands set (PvAmdSetBands)");
+    const int records = nz * nBands;
+    if (cap < records) return fail("zone band decay: PvAmdComputeZoneBandDecay: the output holds fewer than nZones x nBands records");
+    if (lastRun_ == LastRun::None || !dynValid_) return fail("zone band decay: no completed run");
+    if (lastRun_ != LastRun::Ok) return fail("zone band decay: the last run ended in error");
+    // scratch: the rows of one chunk of pairs, the curves, the zones' member rows and records
+    int zonesPer = 0, bandsPer = 0;
+    pva::zoneBandDecayChunks(g_.gx, T, nz, nBands, kZoneScratchBytes, &zonesPer, &bandsPer);
+    const size_t pairBytes = (size_t)g_.gx * (size_t)T * sizeof(double);
+    const size_t rowsBytes = (size_t)zonesPer * (size_t)bandsPer * pairBytes, etcBytes = (size_t)records * (size_t)T * sizeof(double);
+    const size_t memberRowsBytes = ((size_t)nz * (size_t)g_.gx * sizeof(ZoneMembers) + 7) / 8 * 8;
+    if (!growZoneScratch(rowsBytes + etcBytes + memberRowsBytes + (size_t)nz * sizeof(ZoneMembers))) return false;
+    for (auto& e : mapEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    ZoneBandCurveArgs a{};
+    ZoneCurveArgs& c = a.c;
+    c.hist = hist_;
+    c.histPlane = histPlane_;
+    c.delay = delay_;
+    c.labels = zoneLabels_;
+    c.gx = g_.gx;
+    c.gy = g_.gy;
+    c.nZones = nz;
+    c.T = T;
+    c.wr0 = dynCur_.histRow0 - geo_.G;  // (the window as the last run recorded it)
+    c.wc0 = dynCur_.histCol0 - geo_.G;
+    c.wnr = std::min(dynCur_.histTilesX, histTilesX_) * rxi_;
+    c.wnc = std::min(dynCur_.histTilesY, histTilesY_) * wi_;
+    c.rxi = rxi_;
+    c.wi = wi_;
+    c.tilesY = dynCur_.histTilesY;
+    c.rows = reinterpret_cast<double*>(zoneScratch_);
+    c.etc = reinterpret_cast<double*>(zoneScratch_ + rowsBytes);
+    c.memberRows = reinterpret_cast<ZoneMembers*>(zoneScratch_ + rowsBytes + etcBytes);
+    c.members = reinterpret_cast<ZoneMembers*>(zoneScratch_ + rowsBytes + etcBytes + memberRowsBytes);
+    a.nBands = nBands;
+    std::copy(bandCoefs_.begin(), bandCoefs_.begin() + (size_t)nBands * kBandCoefs, a.coefs);
+    hipEventRecord(mapEv_[0], stream_);
+    launchZoneMembers(c, stream_);
+    for (int z0 = 0; z0 < nz; z0 += zonesPer)
+        for (int b0 = 0; b0 < nBands; b0 += bandsPer) {
+            a.zone0 = z0;
+            a.zones = std::min(zonesPer, nz - z0);
+            a.band0 = b0;
+            a.bands = std::min(bandsPer, nBands - b0);
+            if (!hipOk(hipMemsetAsync(c.rows, 0, (size_t)a.zones * (size_t)a.bands * pairBytes, stream_), "zone band decay clear")) return false;
+            launchZoneBandCurves(a, align == kZoneDecayOnset, stream_);
+        }
+    hipEventRecord(mapEv_[1], stream_);
+    std::vector<double> etcHost, edcHost;
+    if (!etc) etcHost.resize((size_t)records * T), etc = etcHost.data();
+    std::vector<ZoneMembers> members((size_t)nz);
+    if (!hipOk(hipGetLastError(), "zone band decay launch") ||
+        !hipOk(hipMemcpyAsync(etc, c.etc, etcBytes, hipMemcpyDeviceToHost, stream_), "zone band decay copy") ||
+        !hipOk(hipMemcpyAsync(members.data(), c.members, (size_t)nz * sizeof(ZoneMembers), hipMemcpyDeviceToHost, stream_), "zone band decay copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "zone band decay sync"))
+        return false;
+    if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
+    if (!edc) edcHost.resize((size_t)T);
+    ZoneBandDecay* recs = static_cast<ZoneBandDecay*>(out);
+    for (int z = 0; z < nz; ++z)
+        for (int b = 0; b < nBands; ++b) {
+            const size_t r = (size_t)z * nBands + b;
+            const ZoneMembers& m = members[(size_t)z];
+            zoneBandDecayFinish(etc + r * T, edc ? edc + r * T : edcHost.data(), T, (int)g_.fs, align, m.n_cells, m.t_first, m.t_last, &recs[r]);
+        }
+    *count = records;
     return true;
 }
 

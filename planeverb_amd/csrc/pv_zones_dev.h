@@ -1,8 +1,13 @@
-// pv_zones_dev.h -- the cross-lane pieces the zone passes share (pv_zones.hip, pv_zone_decay.hip): DPP moves and the wave form of
-// the block butterfly of pv_zones.h.  Device code only.
+// pv_zones_dev.h -- the cross-lane pieces the zone passes share (pv_zones.hip, pv_zone_decay.hip, pv_zone_band_decay.hip): DPP
+// moves, the wave form of the block butterfly of pv_zones.h, its sixteen-slot form and the member rule of the two zone-decay
+// passes.  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <cfloat>
+
+#include "pv_zone_decay.h"
 
 namespace pva {
 
@@ -35,6 +40,70 @@ __device__ __forceinline__ double zoneWaveBlockSum(double v) {
     v = v + __shfl_down(v, 16);
     v = v + __shfl_down(v, 32);
     return zoneReadLane(v, 0);
+}
+
+// ---- the pieces the two zone-decay passes share (pv_zone_decay.hip, pv_zone_band_decay.hip)
+
+// a lane's cell of a block: label 0 where the cell is no member (no label, past gy, no onset, outside the window)
+struct ZoneCurveCell {
+    int label;
+    int t0;
+    long long g;  // offset inside a history plane
+};
+__device__ __forceinline__ ZoneCurveCell zoneCurveCellAt(const ZoneCurveArgs& a, int X, int Y) {
+    ZoneCurveCell c{0, 0, 0};
+    if (Y >= a.gy) return c;
+    const long long s = (long long)X * a.gy + Y;
+    const int label = (int)a.labels[s];
+    if (label == 0) return c;
+    const float d = a.delay[s];
+    const int hr = X - a.wr0, hc = Y - a.wc0;
+    if (d == FLT_MAX || !(d >= 0.0f && d < (float)a.T) || hr < 0 || hc < 0 || hr >= a.wnr || hc >= a.wnc) return c;
+    const int ti = hr / a.rxi, tj = hc / a.wi;
+    const long long g = ((long long)(ti * a.tilesY + tj) * a.rxi + (hr - ti * a.rxi)) * a.wi + (hc - tj * a.wi);
+    if (g >= a.histPlane) return c;
+    c.label = label;
+    c.t0 = (int)d;
+    c.g = g;
+    return c;
+}
+
+// The butterflies of zoneWaveBlockSum for SIXTEEN slots at once: v[k] = the lane's value of slot k; lane k (< 16) returns the block
+// value of slot k.  After the step s of one butterfly only the lanes that are multiples of 2 s hold values anybody reads, so the
+// other lanes carry another slot's: at step s = 1, 2, 4, 8 the lanes whose bit s is clear keep the even slot of a pair and the
+// others the odd one, and each hands the partner lane (lane ^ s) the value IT needs -- 8 + 4 + 2 + 1 adds instead of 16 x 4.  Every
+// add has the operands of the definition's v[i] = v[i] + v[i + s], for the odd slot with the two sides exchanged (IEEE addition is
+// commutative).  Lane i then holds, for slot i & 15, the value of its row of 16 lanes; s = 16 and 32 add the rows as before.
+// Exchanges: quad_perm [1, 0, 3, 2] and [2, 3, 0, 1], row_shl:4 / row_shr:4 by the side of the lane, row_ror:8
+__device__ __forceinline__ double zoneWaveBlockSums16(const double (&v)[kZoneCurveSlots], int lane) {
+    static_assert(kZoneCurveSlots == 16, "four halvings");
+    const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4, b3 = lane & 8;
+    double y[8], z[4], w[2];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) y[m] = (b0 ? v[2 * m + 1] : v[2 * m]) + zoneDpp<0xB1>(b0 ? v[2 * m] : v[2 * m + 1]);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) z[m] = (b1 ? y[2 * m + 1] : y[2 * m]) + zoneDpp<0x4E>(b1 ? y[2 * m] : y[2 * m + 1]);
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const double send = b2 ? z[2 * m] : z[2 * m + 1];
+        const double up = zoneDpp<0x104>(send), down = zoneDpp<0x114>(send);  // lane + 4, lane - 4 (0 outside the row: not selected)
+        w[m] = (b2 ? z[2 * m + 1] : z[2 * m]) + (b2 ? down : up);
+    }
+    double u = (b3 ? w[1] : w[0]) + zoneDpp<0x128>(b3 ? w[0] : w[1]);
+    u = u + __shfl_down(u, 16);
+    u = u + __shfl_down(u, 32);
+    return u;
+}
+
+__device__ __forceinline__ int zoneWaveMin(int v) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v = min(v, __shfl_xor(v, s));
+    return v;
+}
+__device__ __forceinline__ int zoneWaveMax(int v) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v = max(v, __shfl_xor(v, s));
+    return v;
 }
 
 }  // namespace pva
