@@ -661,6 +661,38 @@ PVA_EXPORT int PvAmdSetQuerySpectralRecords(PvAmdSolver* s, unsigned kinds);
 PVA_EXPORT unsigned PvAmdGetQuerySpectralKinds(PvAmdSolver* s);
 PVA_EXPORT int PvAmdQuerySpectralFloats(PvAmdSolver* s, unsigned kind);
 PVA_EXPORT int PvAmdGetQueriedSpectralRecords(PvAmdSolver* s, unsigned kind, float* out, int nQueries);
+/* Emitter records: the same nine record kinds for the registered emitters (PvAmdSetEmitters) of a sparse-emitter
+ * (PVA_OPT_STREAMING_ANALYSIS) solver, the mode the selectors above refuse because it keeps a ring of pressure planes instead of
+ * the history.  `timeKinds` is a mask of PVA_QREC_*, `spectralKinds` one of PVA_QSPEC_*; both are set by the one call, and both 0
+ * (the default) clears the selection.  While a kind is selected every accumulate pass of a run also copies the emitters' cells
+ * -- and, for PVA_QREC_LATERAL, PVA_QREC_ECHOGRAM and PVA_QREC_LOBES, their neighbours (X - 1, Y) and (X, Y - 1) -- from the ring
+ * into record traces on the device, laid out as history planes: T x P floats, P = the emitters rounded up to a multiple of 64,
+ * times 3 with the neighbour columns (104 MB at T = 25 432 and 1024 emitters, 312 MB with the neighbours; allocated only while
+ * a kind is selected, growing with the emitter table).  Behind the run's finalize pass the launches of PvAmdSetQueryRecords and
+ * PvAmdSetQuerySpectralRecords -- the same kernels, one wave per kind (or work item) and 64 emitters -- walk the traces and write
+ * the records straight into pinned host memory.
+ *   Record i belongs to the i-th emitter that PvAmdSetEmitters KEPT (it drops positions off the map: PvAmdGetEmitterCells says
+ * which cell became which index), and is bit for bit what PvAmdGet<Kind> returns at that cell after PvAmdCompute<Kind> on a
+ * solver that keeps its history, for the same scene and listener.  An emitter in a wall or without an onset gives NaNs.  The
+ * settings (echogram slots, lobe windows, bands, modulation frequencies, bins) are those in force when the run was enqueued.
+ * PvAmdGetEmitterRecords waits for the run and copies ONE kind of ONE family (0: PVA_QREC_*, 1: PVA_QSPEC_*) from pinned memory:
+ * nEmitters x PvAmdEmitterRecordFloats(family, kind) floats.  With no kind selected a run enqueues exactly what it enqueued
+ * before these calls existed; with kinds selected the result map, the onset map and PvAmdGetOutput keep every bit.
+ *   Refused with -1 and nothing changed, PvAmdLastError "emitter records: ...": a solver that is not in sparse-emitter mode (use
+ * PvAmdSetQueryRecords there); slab groups and slab ranks; PVA_OPT_SKIP_ANALYSIS; an unknown bit; a kind whose setting is
+ * missing (echogram slots, bands, bins) or whose sampling rate is too low, as for the selectors above; more than
+ * PVA_RECORD_QUERIES_MAX registered emitters -- and PvAmdSetEmitters with more than that many while a kind is selected.
+ * PvAmdGetEmitterRecords is refused when the kind is not selected (or is not exactly one bit), nEmitters differs from the kept
+ * count, no run has completed since the kinds, the emitters or the kind's settings changed, or the last run ended in error.
+ *   PvAmdGetEmitterCells: returns the kept emitters' count and writes the first min(count, cap) result cells as {cx, cy} pairs.
+ *   PvAmdCopyEmitterTrace: the pressure of kept emitter `emitter` at every step of the last run (T floats, PvAmdGetInfo), the
+ * impulse response PvAmdGetImpulseResponse cannot give in this mode; it needs no kind selected. */
+PVA_EXPORT int PvAmdSetEmitterRecords(PvAmdSolver* s, unsigned timeKinds, unsigned spectralKinds);
+PVA_EXPORT int PvAmdGetEmitterRecordKinds(PvAmdSolver* s, unsigned* timeKinds, unsigned* spectralKinds);
+PVA_EXPORT int PvAmdEmitterRecordFloats(PvAmdSolver* s, int family, unsigned kind);
+PVA_EXPORT int PvAmdGetEmitterRecords(PvAmdSolver* s, int family, unsigned kind, float* out, int nEmitters);
+PVA_EXPORT int PvAmdGetEmitterCells(PvAmdSolver* s, int* cxcy, int cap);
+PVA_EXPORT int PvAmdCopyEmitterTrace(PvAmdSolver* s, int emitter, float* outT);
 /* Whole result map: res8 = gx*gy*8 floats in AnalyzerResult order (Analyzer.h:13-21), delay = gx*gy */
 PVA_EXPORT int PvAmdCopyResults(PvAmdSolver* s, float* res8, float* delay);
 /* the same for the block of result cells [r0, r0 + nr) x [c0, c0 + nc): nr x nc records / onsets, row-major (either may be NULL) */

@@ -173,6 +173,11 @@ def main(argv=None):
                          "metrics, modulation and spectrum of --bands, --modulation and --spectrum -- from records computed inside "
                          "the run for the emitters' cells (at most 64 emitters) instead of from whole-map passes after it; the "
                          "output is the same")
+    ap.add_argument("--sparse-emitters", action="store_true",
+                    help="run in sparse-emitter mode (streaming_analysis = 1: a ring of pressure planes instead of the history, the "
+                         "mode of the large grids) with the emitters registered, and take the same records as --in-run-records "
+                         "from the emitter records computed inside the run from per-emitter traces (at most 1024 emitters); the "
+                         "output is the same")
     ap.add_argument("--emission-records", action="store_true",
                     help="add all six record kinds of each emitter as the LIVE module serves them by emission id "
                          "(PlaneverbSetEmissionRecords; --echogram and --lobes give their settings, default 0.005,16 and "
@@ -197,8 +202,10 @@ def main(argv=None):
 
     if a.modulation and not a.bands:
         ap.error("--modulation: needs --bands")
-    if a.zone and a.in_run_records:
-        ap.error("--zone: reduces the whole-map passes (not with --in-run-records)")
+    if a.zone and (a.in_run_records or a.sparse_emitters):
+        ap.error("--zone: reduces the whole-map passes (not with --in-run-records or --sparse-emitters)")
+    if a.in_run_records and a.sparse_emitters:
+        ap.error("--sparse-emitters: not with --in-run-records (the output queries' records need the history)")
     if a.zone_decay and not a.zone:
         ap.error("--zone-decay: needs --zone")
     if a.zone_decay_curves and not a.zone_decay:
@@ -219,10 +226,13 @@ def main(argv=None):
     emitters = a.emitter or [(5.0, 0.0, 6.0)]
     if a.in_run_records and len(emitters) > 64:
         ap.error("--in-run-records: at most 64 emitters (a run's output queries)")
-    with api.Solver(size, size, a.res, device=a.device) as s:
+    if a.sparse_emitters and len(emitters) > api.RECORD_QUERIES_MAX:
+        ap.error("--sparse-emitters: at most %d emitters" % api.RECORD_QUERIES_MAX)
+    with api.Solver(size, size, a.res, device=a.device, **(dict(streaming_analysis=1) if a.sparse_emitters else {})) as s:
         for b in boxes:
             s.add_geometry(b)
-        whole = not a.in_run_records  # the six record kinds from whole-map passes after the run, or from inside the run
+        # the record kinds from whole-map passes after the run, or from inside the run
+        whole = not (a.in_run_records or a.sparse_emitters)
         if not whole:
             kinds = ((api.QREC_ROOM_METRICS if a.room_metrics else 0) | (api.QREC_DECAY_TIMES if a.decay_times else 0) |
                      (api.QREC_LATERAL if a.lateral_fraction else 0) | (api.QREC_ECHOGRAM if a.echogram else 0) |
@@ -237,13 +247,31 @@ def main(argv=None):
                 s.set_bands(a.bands, a.band_fraction)
             if a.spectrum:
                 s.set_spectrum_bins(a.spectrum)
-            s.set_output_queries(emitters)
-            s.set_query_records(kinds)
-            s.set_query_spectral_records(spectral)
+            if a.sparse_emitters:
+                s.set_emitters(emitters)
+                s.set_emitter_records(kinds, spectral)
+            else:
+                s.set_output_queries(emitters)
+                s.set_query_records(kinds)
+                s.set_query_spectral_records(spectral)
         s.run(a.listener)
-        qrec = {} if whole else dict((k, s.queried_records(k)) for k in RECORD_KEYS if kinds & k)
-        qspec = {} if whole else dict((k, s.queried_spectral_records(k))
-                                      for k in (api.QSPEC_BAND_METRICS, api.QSPEC_MODULATION, api.QSPEC_SPECTRUM) if spectral & k)
+        spec_per = {api.QSPEC_BAND_METRICS: 12, api.QSPEC_MODULATION: 15, api.QSPEC_SPECTRUM: 3}
+        if a.sparse_emitters:
+            # set_emitters keeps the positions on the map, in order: row i of the output is the kept emitter's record, or NaNs
+            on_map = [api.host_cells(size, size, a.res, e[0], e[2])[1] is not None for e in emitters]
+            row = np.cumsum(on_map) - 1
+
+            def per_position(r):
+                full = np.full((len(emitters),) + r.shape[1:], np.nan, np.float32)
+                full[np.flatnonzero(on_map)] = r[row[np.flatnonzero(on_map)]]
+                return full
+
+            qrec = dict((k, per_position(s.emitter_records(k))) for k in RECORD_KEYS if kinds & k)
+            qspec = dict((k, per_position(s.emitter_records(k, spectral=True).reshape(s.emitter_cells().shape[0], -1, spec_per[k])))
+                         for k in spec_per if spectral & k)
+        else:
+            qrec = {} if whole else dict((k, s.queried_records(k)) for k in RECORD_KEYS if kinds & k)
+            qspec = {} if whole else dict((k, s.queried_spectral_records(k)) for k in spec_per if spectral & k)
         t = s.timings()
         out = {"scene": a.scene, "grid": [s.gx, s.gy], "T": s.T, "res": a.res, "dx": s.dx, "efree": s.efree,
                "listener": a.listener, "fdtd_ms": t.fdtdMs, "analysis_ms": t.analysisMs, "emitters": []}

@@ -280,6 +280,12 @@ SYMBOLS = {
     "PvAmdGetQuerySpectralKinds": (C.c_uint, [_vp]),
     "PvAmdQuerySpectralFloats": (C.c_int, [_vp, C.c_uint]),
     "PvAmdGetQueriedSpectralRecords": (C.c_int, [_vp, C.c_uint, _fp, C.c_int]),
+    "PvAmdSetEmitterRecords": (C.c_int, [_vp, C.c_uint, C.c_uint]),
+    "PvAmdGetEmitterRecordKinds": (C.c_int, [_vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "PvAmdEmitterRecordFloats": (C.c_int, [_vp, C.c_int, C.c_uint]),
+    "PvAmdGetEmitterRecords": (C.c_int, [_vp, C.c_int, C.c_uint, _fp, C.c_int]),
+    "PvAmdGetEmitterCells": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int]),
+    "PvAmdCopyEmitterTrace": (C.c_int, [_vp, C.c_int, _fp]),
     "PvAmdCopyResults": (C.c_int, [_vp, _fp, _fp]),
     "PvAmdCopyResultsBlock": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "PvAmdGetImpulseResponse": (C.c_int, [_vp, C.c_int, C.c_int, _fp]),
@@ -1800,6 +1806,47 @@ class Solver:
         pass on the same run; NaN rows off the map and where no sound arrived"""
         per = {QSPEC_BAND_METRICS: 12, QSPEC_MODULATION: 15, QSPEC_SPECTRUM: 3}.get(int(kind), 1)
         return self._read_records(lib().PvAmdGetQueriedSpectralRecords, kind, (self.query_spectral_floats(kind) // per, per))
+
+    def set_emitter_records(self, time_kinds, spectral_kinds=0):
+        """sparse-emitter mode: the record kinds (masks of QREC_* and of QSPEC_*) every following run computes for the registered
+        emitters (set_emitters), inside the run and straight into pinned host memory; both 0 (the default) selects none"""
+        _check(lib().PvAmdSetEmitterRecords(self._h, int(time_kinds), int(spectral_kinds)))
+
+    def emitter_record_kinds(self):
+        """(time kinds, spectral kinds)"""
+        t, f = C.c_uint(0), C.c_uint(0)
+        _check(lib().PvAmdGetEmitterRecordKinds(self._h, C.byref(t), C.byref(f)))
+        return int(t.value), int(f.value)
+
+    def emitter_cells(self):
+        """int32 [n, 2]: the result cells (cx, cy) of the emitters set_emitters kept (it drops positions off the map), in the order
+        of the emitter records"""
+        n = lib().PvAmdGetEmitterCells(self._h, None, 0)
+        if n < 0:
+            raise PlaneverbError(last_error())
+        out = np.zeros((n, 2), np.int32)
+        if n and lib().PvAmdGetEmitterCells(self._h, out.ctypes.data_as(C.POINTER(C.c_int)), n) < 0:
+            raise PlaneverbError(last_error())
+        return out
+
+    def emitter_records(self, kind, spectral=False):
+        """float32 [n_emitters, floats] of ONE kind (QSPEC_* with spectral=True) for the last run (waits for it; no GPU work): row i
+        bit for bit what <kind>_at returns at emitter_cells()[i] on a solver that keeps its history; NaN rows where no sound
+        arrived.  The spectral kinds' rows are band after band (12 or 15 floats) or bin after bin (3 floats)"""
+        fam = 1 if spectral else 0
+        floats = lib().PvAmdEmitterRecordFloats(self._h, fam, int(kind))
+        if floats < 0:
+            raise PlaneverbError(last_error())
+        n = len(self.emitter_cells())
+        out = np.empty((n, floats), np.float32)
+        _check(lib().PvAmdGetEmitterRecords(self._h, fam, int(kind), _f(out) if n else None, n))
+        return out
+
+    def emitter_trace(self, i):
+        """float32 [T]: the pressure at kept emitter i at every step of the last sparse-emitter run"""
+        out = np.empty(self.T, np.float32)
+        _check(lib().PvAmdCopyEmitterTrace(self._h, int(i), _f(out)))
+        return out
 
     def results(self):
         res = np.empty((self.gx, self.gy, 8), np.float32)

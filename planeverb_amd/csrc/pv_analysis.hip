@@ -17,6 +17,8 @@
 #include "pv_launch.h"
 #include "pv_libm.h"
 #include "pv_prims.h"
+#include "pv_record_lane.h"
+
 namespace pva {
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -613,6 +615,33 @@ __global__ void pv_stream_trace_kernel(const AnalyzeArgs a) {
     a.emTrace[(size_t)e * a.T + t] = v;
 }
 
+// The same pass for the record traces (AnalyzeArgs::recTrace): plane t of recCols x (1 or 3) columns, lanes along the columns so
+// that a step's stores are consecutive.  Column part 0 = the emitters' own cells, parts 1 / 2 = their neighbours (X - 1, Y) /
+// (X, Y - 1), each zero before its own tile's first step; a neighbour outside the window (traceNeighbours) and a column without
+// an emitter stay zero
+__global__ __launch_bounds__(256) void pv_stream_rectrace_kernel(const AnalyzeArgs a) {
+    const int plane = a.recCols * (a.recVel ? 3 : 1);
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    const int t = a.tA + (int)blockIdx.y;
+    if (c >= plane || t >= a.tB || t >= a.T) return;
+    const int part = c / a.recCols, e = c - part * a.recCols;
+    float v = 0.f;
+    if (e < a.numEmitters) {
+        const DynParams dyn = *a.dyn;
+        const int cell = a.emCells[e];
+        int X = cell / a.gy, Y = cell - X * a.gy;
+        bool hasX, hasY;
+        traceNeighbours(a, dyn, X, Y, &hasX, &hasY);
+        const bool has = part == 0 || (part == 1 ? hasX : hasY);
+        if (part == 1) --X;
+        if (part == 2) --Y;
+        if (has && t >= a.tileFirst[(X / a.rxi) * a.nty + (Y / a.wi)])
+            v = a.hist[(long long)(t % a.ring) * a.histPlane +
+                       histOffset(X + a.G - dyn.histRow0, Y + a.G - dyn.histCol0, a.rxi, a.wi, dyn.histTilesY)];
+    }
+    a.recTrace[(long long)t * plane + c] = v;
+}
+
 // end of run: onset map + the outputs that come from the forward sums (Analyzer.cpp:197-230), every cell
 __global__ __launch_bounds__(256) void pv_stream_finalize_kernel(const AnalyzeArgs a) {
     const int Y = blockIdx.x * blockDim.x + threadIdx.x;
@@ -693,6 +722,9 @@ void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t*
                        hasEmitter, a.tileFirst, a.tB, tileOpen, ntiles);
     const int n = a.numEmitters * (a.tB - a.tA);
     if (n > 0) hipLaunchKernelGGL(pv_stream_trace_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, a);
+    if (n > 0 && a.recTrace)
+        hipLaunchKernelGGL(pv_stream_rectrace_kernel, dim3((unsigned)((a.recCols * (a.recVel ? 3 : 1) + 255) / 256), (unsigned)(a.tB - a.tA)),
+                           dim3(256), 0, stream, a);
 }
 
 void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream) {

@@ -1130,6 +1130,7 @@ int PvAmdGetQueriedOutputs(PvAmdSolver* h, PlaneverbOutput* out, int n) try {
 // In-run records of the registered queries, two families (pv_solver_records.cpp): single whole-grid solvers only.  `pre` is what
 // every refusal of a family's calls starts with, the member what serves the call for that family
 static bool analysisHandle(PvAmdSolver* h, const char* pre);
+static bool analysisCall(PvAmdSolver* h, const char* pre, const char* fn, const void* out);
 static const char kQrecPre[] = "query records: ", kQspecPre[] = "spectral records: ";
 static_assert(PVA_QSPEC_BAND_METRICS == 1u << kQspecBandMetrics && PVA_QSPEC_MODULATION == 1u << kQspecModulation &&
                   PVA_QSPEC_SPECTRUM == 1u << kQspecSpectrum,
@@ -1201,6 +1202,61 @@ int PvAmdQuerySpectralFloats(PvAmdSolver* h, unsigned kind) try {
 
 int PvAmdGetQueriedSpectralRecords(PvAmdSolver* h, unsigned kind, float* out, int nQueries) try {
     return recordsRead(h, kQspecPre, __func__, &Solver::queriedSpectralRecords, kind, out, nQueries);
+} PV_API_CATCH(-1)
+
+// Emitter records of sparse-emitter mode: the same two families with the registered emitters as the cell source
+static const char kEmitterPre[] = "emitter records: ";
+static bool emitterFamily(int family, Solver::RecordFamily* f) {
+    if (family == 0 || family == 1) {
+        *f = family ? Solver::kRecSpectral : Solver::kRecTime;
+        return true;
+    }
+    g_lastError = std::string(kEmitterPre) + "family: 0 (PVA_QREC_*) or 1 (PVA_QSPEC_*)";
+    return false;
+}
+
+int PvAmdSetEmitterRecords(PvAmdSolver* h, unsigned timeKinds, unsigned spectralKinds) try {
+    if (!analysisHandle(h, kEmitterPre)) return -1;
+    return ret(h, h->s->setEmitterRecords(timeKinds, spectralKinds));
+} PV_API_CATCH(-1)
+
+int PvAmdGetEmitterRecordKinds(PvAmdSolver* h, unsigned* timeKinds, unsigned* spectralKinds) try {
+    if (!analysisHandle(h, kEmitterPre)) return -1;
+    if (timeKinds) *timeKinds = h->s->emitterRecordKinds(Solver::kRecTime);
+    if (spectralKinds) *spectralKinds = h->s->emitterRecordKinds(Solver::kRecSpectral);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdEmitterRecordFloats(PvAmdSolver* h, int family, unsigned kind) try {
+    Solver::RecordFamily f;
+    if (!analysisHandle(h, kEmitterPre) || !emitterFamily(family, &f)) return -1;
+    const int n = h->s->emitterRecordFloats(f, kind);
+    if (n < 0) ret(h, false);
+    return n;
+} PV_API_CATCH(-1)
+
+int PvAmdGetEmitterRecords(PvAmdSolver* h, int family, unsigned kind, float* out, int nEmitters) try {
+    Solver::RecordFamily f;
+    if (!analysisHandle(h, kEmitterPre) || !emitterFamily(family, &f)) return -1;
+    if (nEmitters < 0 || nEmitters > kMaxRecordQueries || (nEmitters > 0 && !out)) {
+        g_lastError = std::string(kEmitterPre) + __func__ + ": 0 .. 1024 emitters and an output buffer";
+        return -1;
+    }
+    return ret(h, h->s->emitterRecords(f, kind, out, nEmitters));
+} PV_API_CATCH(-1)
+
+int PvAmdGetEmitterCells(PvAmdSolver* h, int* cxcy, int cap) try {
+    if (!analysisHandle(h, "emitter cells: ")) return -1;
+    if (cap < 0 || (cap > 0 && !cxcy)) {
+        g_lastError = std::string("emitter cells: ") + __func__ + ": a capacity of 0 or more, and a buffer with it";
+        return -1;
+    }
+    return h->s->emitterCells(cxcy, cap);
+} PV_API_CATCH(-1)
+
+int PvAmdCopyEmitterTrace(PvAmdSolver* h, int emitter, float* outT) try {
+    if (!analysisCall(h, "emitter trace: ", __func__, outT)) return -1;
+    return ret(h, h->s->copyEmitterTrace(emitter, outT));
 } PV_API_CATCH(-1)
 
 int PvAmdCopyResults(PvAmdSolver* h, float* res8, float* delay) try {

@@ -384,6 +384,13 @@ struct AnalyzeArgs {
     const int* emCells;  // registered emitter cells: X*gy + Y
     float* emTrace;      // numEmitters x T pressure traces
     int numEmitters;
+    // Record traces of the registered emitters (PvAmdSetEmitterRecords; NULL while no kind is selected): [T][recPlane] floats laid
+    // out as history planes, so that the record bodies walk them as they walk the history (recordLaneOfTrace, pv_record_lane.h).
+    // Column e = emitter e; with recVel, column recCols + e = its neighbour (X - 1, Y) and 2 recCols + e = (X, Y - 1).
+    // recPlane = recCols x (recVel ? 3 : 1), recCols a multiple of 64.  At T = 25 432 and 1024 emitters: 312 MB with the
+    // neighbour columns, 104 MB without
+    float* recTrace;
+    int recCols, recVel;
 };
 
 // fused analysis of the small grids (pv_fused.hip)

@@ -43,18 +43,12 @@ __device__ __forceinline__ void lateralBody(const AnalyzeArgs& a, const DynParam
     }
     if (__ballot(live) == 0ull) return;
 
-    // the neighbours (X - 1, Y) and (X, Y - 1) as plane offsets, and the first recorded step of their tiles: encodeWave
-    const int tileCells = a.rxi * a.wi;
-    const bool hasX = pc.hti > 0 || pc.row > 0, hasY = pc.htj > 0 || pc.col > 0;
-    const int gX = pc.row > 0 ? pc.g - a.wi : pc.g - dyn.histTilesY * tileCells + (a.rxi - 1) * a.wi;
-    const int gY = pc.col > 0 ? pc.g - 1 : pc.g - tileCells + (a.wi - 1);
-    const int tileX = pc.row > 0 ? pc.tile : pc.tile - a.nty, tileY = pc.col > 0 ? pc.tile : pc.tile - 1;
-    int tFirst = T, tFx = INT_MAX, tFy = INT_MAX;
+    // the neighbours (X - 1, Y) and (X, Y - 1) as plane offsets, and the first recorded step of their tiles: the lane's (pv_record_lane.h)
+    const bool hasX = ln.hasX, hasY = ln.hasY;
+    const int gX = ln.gX, gY = ln.gY;
+    const int tFirst = ln.tFirst, tFx = ln.tFx, tFy = ln.tFy;
     FaceCoef fc{0.f, 0.f, 0.f};
     if (live) {
-        tFirst = a.tileFirst[pc.tile];
-        if (hasX) tFx = a.tileFirst[tileX];
-        if (hasY) tFy = a.tileFirst[tileY];
         fc = a.coef[(size_t)(pc.X + a.G) * a.pitch + (pc.Y + a.G)];
     }
     const float kx = fc.kx, ky = fc.ky;

@@ -11,6 +11,9 @@
 // decided by selects on its own ranges, so a record's bits do not depend on the other lanes of the wave: record i is bit for bit
 // what PvAmdGet<Kind> returns at the query's position after PvAmdCompute<Kind> on the same run.
 //
+// In sparse-emitter mode (PvAmdSetEmitterRecords) the same kernel serves the registered emitters: the history planes are the
+// emitters' record traces and a lane's offsets are its columns there (recordLaneOfTrace); the bodies do not know the difference.
+//
 // Lanes at or above nq have no slot and no cell; a query off the map, outside the window or without an onset gets quiet NaNs.
 // The stores are plain vector stores to host-coherent memory; they are visible to the host when the stream has drained, as
 // pv_gather_queries_kernel's are.
@@ -40,7 +43,8 @@ namespace {
 static_assert(PV_METRICS_S <= 8 && PV_DECAY_S <= 8 && PV_LATERAL_S <= 8 && PV_ECHOGRAM_S <= 8 && PV_ECHO_S <= 8 && PV_LOBES_S <= 8,
               "launchQueryRecords chooses the one-descriptor-per-chunk form for chunks of at most 8 planes");
 
-template <bool CHUNK>
+// TRACE: the lanes are the registered emitters of sparse-emitter mode and the history is their record traces (recordLaneOfTrace)
+template <bool CHUNK, bool TRACE>
 __global__ __launch_bounds__(64) void pv_query_records_kernel(const AnalyzeArgs a, const QueryRecordArgs q) {
     __shared__ double logTab[96];
     __shared__ double powLt[32];
@@ -64,7 +68,8 @@ __global__ __launch_bounds__(64) void pv_query_records_kernel(const AnalyzeArgs 
     const DynParams dyn = *a.dyn;
     const int i = 64 * (int)blockIdx.y + lane;  // the query (the group is wave-uniform)
     const bool slot = i < q.nq;
-    const RecordLane ln = recordLaneOfCell(a, dyn, slot ? q.cells[i] : -1, slot);
+    const long long cell = slot ? q.cells[i] : -1;
+    const RecordLane ln = TRACE ? recordLaneOfTrace(a, dyn, cell, i, slot) : recordLaneOfCell(a, dyn, cell, slot);
     // (a lane without a slot never stores: it is not live, and the NaN fill asks for the slot)
     const SlotStore out{q.out + q.offset[kind] + (long long)(slot ? i : 0) * q.floats[kind]};
     switch (kind) {
@@ -97,10 +102,13 @@ __global__ __launch_bounds__(64) void pv_query_records_kernel(const AnalyzeArgs 
 void launchQueryRecords(const AnalyzeArgs& a, const QueryRecordArgs& q, hipStream_t stream) {
     const dim3 grid((unsigned)__builtin_popcount(q.kinds), (unsigned)((q.nq + 63) / 64));
     // (the largest chunk of the six passes is 8 planes: one descriptor per chunk below 2^31 bytes, as in their own launchers)
-    if (a.histPlane * 4 * 8 < (1ll << 31))
-        hipLaunchKernelGGL((pv_query_records_kernel<true>), grid, dim3(64), 0, stream, a, q);
+    // (record traces -- a.hist = a.recTrace, planes of at most 3 x 1024 floats -- always take the chunk form)
+    if (a.recTrace)
+        hipLaunchKernelGGL((pv_query_records_kernel<true, true>), grid, dim3(64), 0, stream, a, q);
+    else if (a.histPlane * 4 * 8 < (1ll << 31))
+        hipLaunchKernelGGL((pv_query_records_kernel<true, false>), grid, dim3(64), 0, stream, a, q);
     else
-        hipLaunchKernelGGL((pv_query_records_kernel<false>), grid, dim3(64), 0, stream, a, q);
+        hipLaunchKernelGGL((pv_query_records_kernel<false, false>), grid, dim3(64), 0, stream, a, q);
 }
 
 }  // namespace pva

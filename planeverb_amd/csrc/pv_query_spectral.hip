@@ -25,6 +25,9 @@
 //                  chunk boundaries differ from the whole-map wave's, but a lane's sums take the steps in ascending order either way.
 // The tables are indexed by ABSOLUTE step, so a row address is wave-uniform whatever cells the lanes own: scalar loads, as before.
 //
+// In sparse-emitter mode (PvAmdSetEmitterRecords) the same kernel serves the registered emitters from their record traces
+// (recordLaneOfTrace), as pv_query_records.hip does.
+//
 // Lanes at or above nq have no slot and no cell; a query off the map, outside the window or without an onset gets quiet NaNs.
 // The stores are plain vector stores to host-coherent memory, all behind the loops; they are visible to the host when the stream
 // has drained.  The device tables are uploaded where the kinds are selected and where the settings change (both wait for a run in
@@ -52,7 +55,8 @@ static_assert(PV_BANDS_S <= 8 && PV_MODULATION_S <= 8 && PV_SPECTRUM_S <= 8,
               "launchQuerySpectral chooses the one-descriptor-per-chunk form for chunks of at most 8 planes");
 static_assert(PV_BANDS_B <= kBandsMax && kBandsMax + PV_BANDS_B - 1 <= kQspecCoefSets, "the padded last block of bands reads zero sets");
 
-template <bool CHUNK>
+// TRACE: the lanes are the registered emitters of sparse-emitter mode and the history is their record traces (recordLaneOfTrace)
+template <bool CHUNK, bool TRACE>
 __global__ __launch_bounds__(64) void pv_query_spectral_kernel(const AnalyzeArgs a, const QuerySpectralArgs q) {
     __shared__ double logTab[96];
     // the work item (wave-uniform): kind and ordinal inside the kind
@@ -66,7 +70,8 @@ __global__ __launch_bounds__(64) void pv_query_spectral_kernel(const AnalyzeArgs
     const DynParams dyn = *a.dyn;
     const int i = 64 * (int)blockIdx.y + lane;  // the query (the group is wave-uniform)
     const bool slot = i < q.nq;
-    const RecordLane ln = recordLaneOfCell(a, dyn, slot ? q.cells[i] : -1, slot);
+    const long long cell = slot ? q.cells[i] : -1;
+    const RecordLane ln = TRACE ? recordLaneOfTrace(a, dyn, cell, i, slot) : recordLaneOfCell(a, dyn, cell, slot);
     // (a lane without a slot never stores: it is not live, and the NaN fill asks for the slot)
     float* rec = q.out + q.offset[kind] + (long long)(slot ? i : 0) * q.floats[kind];
     switch (kind) {
@@ -110,10 +115,13 @@ __global__ __launch_bounds__(64) void pv_query_spectral_kernel(const AnalyzeArgs
 void launchQuerySpectral(const AnalyzeArgs& a, const QuerySpectralArgs& q, hipStream_t stream) {
     const dim3 grid((unsigned)(q.items[0] + q.items[1] + q.items[2]), (unsigned)((q.nq + 63) / 64));
     // (the largest chunk of the three passes is 8 planes: one descriptor per chunk below 2^31 bytes, as in their own launchers)
-    if (a.histPlane * 4 * 8 < (1ll << 31))
-        hipLaunchKernelGGL((pv_query_spectral_kernel<true>), grid, dim3(64), 0, stream, a, q);
+    // (record traces -- a.hist = a.recTrace, planes of at most 3 x 1024 floats -- always take the chunk form)
+    if (a.recTrace)
+        hipLaunchKernelGGL((pv_query_spectral_kernel<true, true>), grid, dim3(64), 0, stream, a, q);
+    else if (a.histPlane * 4 * 8 < (1ll << 31))
+        hipLaunchKernelGGL((pv_query_spectral_kernel<true, false>), grid, dim3(64), 0, stream, a, q);
     else
-        hipLaunchKernelGGL((pv_query_spectral_kernel<false>), grid, dim3(64), 0, stream, a, q);
+        hipLaunchKernelGGL((pv_query_spectral_kernel<false, false>), grid, dim3(64), 0, stream, a, q);
 }
 
 }  // namespace pva

@@ -705,6 +705,8 @@ Solver::~Solver() {
     if (px_[0]) hipFree(px_[0]);  // (px_[1] lives in the same allocation)
     if (emCells_) hipFree(emCells_);
     if (emTrace_) hipFree(emTrace_);
+    if (recTrace_) hipFree(recTrace_);
+    if (emRecCells_) hipHostFree(emRecCells_);
     void* ptrs[] = {coef_,      matDev_, pulseDev_, hist_,  tileFirst_, tileClass_, generalList_,
                     generalCount_, dynDev_, errFlag_, res8_,     delay_, scratch_, res_, activeCount_, win8_, unitList_, fusedCtl_, labelDev_, nearBox_,
                     histAbove_, histEdge_, tileDead_, deadCount_, matBaseDev_, shapeDev_};
@@ -2034,6 +2036,9 @@ AnalyzeArgs Solver::analyzeArgs(float lx, float lz) const {
     a.emCells = emCells_;
     a.emTrace = emTrace_;
     a.numEmitters = numEmitters_;
+    a.recTrace = recTrace_;  // (while an emitter-record kind is selected)
+    a.recCols = recCols_;
+    a.recVel = recVel_ ? 1 : 0;
     a.tileOpenOut = tileMarks_;
     return a;
 }
@@ -2285,6 +2290,9 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
     launchStreamFinalize(aa, stream_);
     hipEventRecord(ev_[2], stream_);
     lastRunBatched_ = false;
+    streamedOnce_ = true;
+    // (the emitter records' two launches come first in here: behind the finalize pass, whose delay map they read, and -- by the
+    // waits on accDone above -- behind the last accumulate passes' trace writes on stream2_)
     enqueueQueries();
     pendingTimings_ = true;
     return hipOk(hipGetLastError(), "run launch");
@@ -2801,15 +2809,34 @@ bool Solver::setEmitters(const float* xyz, int n) {
         int cx, cy;
         if (resultCell(g_, xyz[3 * i], xyz[3 * i + 2], &cx, &cy)) cells.push_back(cx * g_.gy + cy);
     }
+    const bool records = (recs_[kRecTime].kinds | recs_[kRecSpectral].kinds) != 0;
+    if (records && (int)cells.size() > kMaxRecordQueries) return fail("emitter records: at most 1024 registered emitters while a kind is selected");
+    // (the record launches of a run in flight read the cell table and write the pinned blocks, whose stamps sync() settles)
+    if (records && pendingTimings_ && !sync()) return false;
     if (!hipOk(hipStreamSynchronize(stream_), "sync")) return false;
     if ((int)cells.size() > emCap_) {
+        long long* t = nullptr;
+        if (!hipOk(hipHostMalloc((void**)&t, cells.size() * sizeof(long long)), "hipHostMalloc")) return false;
+        if (emRecCells_) hipHostFree(emRecCells_);
+        emRecCells_ = t;
         if (emCells_) hipFree(emCells_);
         if (emTrace_) hipFree(emTrace_);
         emCells_ = nullptr;
         emTrace_ = nullptr;
+        emCap_ = 0;
+        if (!dalloc(&emCells_, cells.size(), true) || !dalloc(&emTrace_, cells.size() * T_, true)) {
+            numEmitters_ = 0;
+            return false;
+        }
         emCap_ = (int)cells.size();
-        if (!dalloc(&emCells_, (size_t)emCap_, true) || !dalloc(&emTrace_, (size_t)emCap_ * T_, true)) return false;
     }
+    // the emitter records follow the table: their pinned blocks and traces grow with it, their records are the old table's
+    for (int f = 0; f < kRecordFamilies; ++f)
+        if (!growRecordBlock((RecordFamily)f, (int)cells.size())) return false;
+    if (records && !fitRecTrace((int)cells.size(), recs_[kRecTime].kinds, recs_[kRecSpectral].kinds)) return false;
+    for (int f = 0; f < kRecordFamilies; ++f) invalidateRecords((RecordFamily)f);
+    for (size_t i = 0; i < cells.size(); ++i) emRecCells_[i] = cells[i];
+    streamedOnce_ = false;  // (emTrace_'s rows are the old table's)
     numEmitters_ = (int)cells.size();
     // The uploads go through stream_, behind the zero fill dalloc() queued there (a synchronous hipMemcpy is not ordered with
     // a non-blocking stream: the fill could land AFTER it and leave every emitter at cell 0 -- seen as wet gain / RT60 = 0 in

@@ -244,11 +244,11 @@ public:
     // completed without error.  The spectral kinds' device tables are made valid in the setters, never on the enqueue path
     enum RecordFamily { kRecTime = 0, kRecSpectral = 1, kRecordFamilies = 2 };
     bool setQueryRecords(unsigned kinds) { return selectRecords(kRecTime, kinds); }
-    unsigned queryRecordKinds() const { return recs_[kRecTime].kinds; }
+    unsigned queryRecordKinds() const { return opt_.streaming ? 0u : recs_[kRecTime].kinds; }
     int queryRecordFloats(unsigned kind) { return recordFloats(kRecTime, kind); }  // -1: not one kind, or its setting is missing
     bool queriedRecords(unsigned kind, float* out, int n) { return readRecords(kRecTime, kind, out, n); }
     bool setQuerySpectralRecords(unsigned kinds) { return selectRecords(kRecSpectral, kinds); }
-    unsigned querySpectralKinds() const { return recs_[kRecSpectral].kinds; }
+    unsigned querySpectralKinds() const { return opt_.streaming ? 0u : recs_[kRecSpectral].kinds; }
     int querySpectralFloats(unsigned kind) { return recordFloats(kRecSpectral, kind); }
     bool queriedSpectralRecords(unsigned kind, float* out, int n) { return readRecords(kRecSpectral, kind, out, n); }
     // Record queries: up to kMaxRecordQueries (pv_query_records.h) positions of their own, mapped in the given order as
@@ -258,6 +258,21 @@ public:
     // the registered count.  Waits for a run in flight; a change invalidates the records until the next run
     bool setRecordQueries(const float* xyz, int n);
     int recordQueries() const { return numRecQueries_; }
+    // Emitter records (sparse-emitter mode only, PvAmdSetEmitterRecords): the same two families, selectors, pinned blocks, launches
+    // and stamps with the registered emitters (setEmitters) as the cell source -- record i belongs to the i-th emitter setEmitters
+    // kept.  The mode keeps a ring of pressure planes, not the history, so while a kind is selected every accumulate pass also
+    // copies the emitters' cells -- and, for the velocity kinds, their neighbours (X - 1, Y) and (X, Y - 1) -- from the ring into
+    // record traces laid out as history planes ([T][P] floats, AnalyzeArgs::recTrace: 104 MB at T = 25 432 and 1024 emitters, 312 MB
+    // with the neighbour columns), and the two record launches behind the run's finalize pass walk those.  The records are bit for
+    // bit what a full-history solver's whole-map passes give at the emitters' cells.  At most kMaxRecordQueries emitters while a kind
+    // is selected.  The selectors of the output queries' records keep refusing in this mode
+    bool setEmitterRecords(unsigned timeKinds, unsigned spectralKinds);
+    unsigned emitterRecordKinds(RecordFamily f) const { return opt_.streaming ? recs_[f].kinds : 0u; }
+    int emitterRecordFloats(RecordFamily f, unsigned kind);
+    bool emitterRecords(RecordFamily f, unsigned kind, float* out, int n) { return readRecords(f, kind, out, n, true); }
+    int emitters() const { return numEmitters_; }
+    int emitterCells(int* cxcy, int cap) const;  // the kept emitters' count; the first min(count, cap) result cells (cx, cy) into cxcy
+    bool copyEmitterTrace(int emitter, float* outT);  // the emitter's pressure at every step of the last run
     bool copyResults(float* res8, float* delay);
     // the block [r0, r0 + nr) x [c0, c0 + nc) of the result map (AoS records) and of the onset map, row-major nr x nc
     bool copyResultsBlock(int r0, int c0, int nr, int nc, float* res8, float* delay);
@@ -540,6 +555,15 @@ private:
     int* emCells_ = nullptr;
     float* emTrace_ = nullptr;
     int numEmitters_ = 0, emCap_ = 0;
+    // emitter records: the emitters' result cells as the record launches read them (pinned, emCap_ entries), the record traces
+    // (allocated while a kind is selected; recTraceCap_ floats) and their layout under the current emitters and kinds
+    long long* emRecCells_ = nullptr;
+    float* recTrace_ = nullptr;
+    size_t recTraceCap_ = 0;
+    int recCols_ = 0;
+    bool recVel_ = false;
+    bool streamedOnce_ = false;  // a sparse-emitter run has been enqueued: emTrace_ holds a run's traces
+    bool fitRecTrace(int emitters, unsigned timeKinds, unsigned spectralKinds);  // (no run in flight)
     // resident kernel (pv_resident.hip)
     unsigned* resFlags_ = nullptr;     // ntiles epoch counters + 1 abort word
     int residentHeld_ = 0;             // blocks of the device's resident budget held by the run in flight
@@ -678,15 +702,21 @@ private:
     // the record queries' own pinned cell table (setRecordQueries)
     long long* rqCellsHost_ = nullptr;
     int rqCap_ = 0, numRecQueries_ = 0;
-    int recordQueryCount() const { return numRecQueries_ > 0 ? numRecQueries_ : numQueries_; }  // of the table the records follow
+    int recordQueryCount() const {  // of the table the records follow
+        return opt_.streaming ? numEmitters_ : numRecQueries_ > 0 ? numRecQueries_ : numQueries_;
+    }
+    const long long* recordCells() const { return opt_.streaming ? emRecCells_ : numRecQueries_ > 0 ? rqCellsHost_ : qCellsHost_; }
+    AnalyzeArgs recordArgs() const;  // of the record launches: the history, or the record traces in its place
     int recordFloatsOf(RecordFamily f, int k, bool largest = false) const;  // per query of kind bit k; -1: its setting is missing
     const char* recordKindsRefusal(RecordFamily f, unsigned kinds) const;  // of the kinds' settings, nullptr where none
-    bool selectRecords(RecordFamily f, unsigned kinds);
+    // (emitters: the call came through the emitter records' entry points, which serve sparse-emitter solvers and those alone)
+    std::string selectRefusal(RecordFamily f, unsigned kinds, bool emitters) const;  // what needs no device; empty: none
+    bool selectRecords(RecordFamily f, unsigned kinds, bool emitters = false);
     bool swapRecordBlock(RecordFamily f, unsigned kinds, int queries);
     bool growRecordBlock(RecordFamily f, int queries);
     int recordFloats(RecordFamily f, unsigned kind);
     void stampRecords(RecordFamily f, int nq, const bool* on, int* offset, int* floats);
-    bool readRecords(RecordFamily f, unsigned kind, float* out, int n);
+    bool readRecords(RecordFamily f, unsigned kind, float* out, int n, bool emitters = false);
     void invalidateRecords(RecordFamily f, unsigned kinds = ~0u) {  // the block's records are those of other queries or settings
         if (recs_[f].kinds & kinds) recs_[f].run = RecordSet::Run::None;
     }

@@ -543,7 +543,8 @@ bool Solver::setEchogram(float slotSeconds, int nSlots) {
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
     if (nSlots == 0 && (recs_[kRecTime].kinds & (1u << kQrecEchogram)))
-        return fail("query records: echogram: the slots cannot be cleared while PVA_QREC_ECHOGRAM is selected (PvAmdSetQueryRecords)");
+        return fail(opt_.streaming ? "emitter records: echogram: the slots cannot be cleared while PVA_QREC_ECHOGRAM is selected (PvAmdSetEmitterRecords)"
+                                   : "query records: echogram: the slots cannot be cleared while PVA_QREC_ECHOGRAM is selected (PvAmdSetQueryRecords)");
     invalidateRecords(kRecTime, 1u << kQrecEchogram);  // (the records in the pinned block are the old slots')
     dropAnalysisMap(kMapEchogram, nSlots == 0);
     if (nSlots == 0) {
@@ -620,7 +621,8 @@ bool Solver::computeLobes(float* ms) {
 bool Solver::setBands(const float* centreHz, int n, int fraction) {
     if (isSlab()) return fail("band metrics: not available on a slab");
     if (n == 0 && (recs_[kRecSpectral].kinds & kQspecBandKinds))
-        return fail("spectral records: the bands cannot be cleared while a band kind is selected (PvAmdSetQuerySpectralRecords)");
+        return fail(opt_.streaming ? "emitter records: the bands cannot be cleared while a band kind is selected (PvAmdSetEmitterRecords)"
+                                   : "spectral records: the bands cannot be cleared while a band kind is selected (PvAmdSetQuerySpectralRecords)");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
@@ -713,7 +715,8 @@ bool Solver::computeModulation(float* ms) {
 bool Solver::setSpectrumBins(const float* hz, int n) {
     if (isSlab()) return fail("spectrum: not available on a slab");
     if (n == 0 && (recs_[kRecSpectral].kinds & (1u << kQspecSpectrum)))
-        return fail("spectral records: the bins cannot be cleared while PVA_QSPEC_SPECTRUM is selected (PvAmdSetQuerySpectralRecords)");
+        return fail(opt_.streaming ? "emitter records: the bins cannot be cleared while PVA_QSPEC_SPECTRUM is selected (PvAmdSetEmitterRecords)"
+                                   : "spectral records: the bins cannot be cleared while PVA_QSPEC_SPECTRUM is selected (PvAmdSetQuerySpectralRecords)");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)

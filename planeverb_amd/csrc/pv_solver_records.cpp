@@ -1,8 +1,12 @@
 // pv_solver_records.cpp -- what a run leaves in pinned host memory for the registered queries of a Solver (pv_solver.h): the eight
 // outputs of the output queries, and the in-run analysis records in their two families (pv_query_records.hip, six time-domain
 // kinds; pv_query_spectral.hip, three frequency-resolved ones).  A family's selector, pinned block and stamp are written once, for
-// a RecordSet; what is a family's own: its record sizes, the preconditions of its kinds, and its launch with the arguments.
+// a RecordSet; what is a family's own: its record sizes, the preconditions of its kinds, and its launch with the arguments.  In
+// sparse-emitter mode the same path serves the registered emitters (PvAmdSetEmitterRecords): the cell table is theirs, the history
+// planes are their record traces.
 #include "pv_solver.h"
+
+#include <algorithm>
 
 #include "pv_launch.h"
 #include "pv_bands.h"
@@ -150,7 +154,7 @@ void Solver::enqueueQueryRecords() {
     const RecordSet& r = recs_[kRecTime];
     if (!r.kinds || opt_.skipAnalysis) return;
     QueryRecordArgs q{};
-    q.cells = numRecQueries_ > 0 ? rqCellsHost_ : qCellsHost_;
+    q.cells = recordCells();
     q.out = r.host;
     q.nq = recordQueryCount();
     q.kinds = r.kinds;
@@ -171,7 +175,7 @@ void Solver::enqueueQueryRecords() {
     q.nLm = echoMusicLimit(fs);
     lobesEdgeSteps(lobeEdges_, lobeEdgeCount_, fs, &q.ed);  // (valid: checked where the kind was selected and where the windows are set)
     q.nW = lobeEdgeCount_ + 1;
-    if (q.nq > 0) launchQueryRecords(analyzeArgs(lastLx_, lastLz_), q, stream_);
+    if (q.nq > 0) launchQueryRecords(recordArgs(), q, stream_);
 }
 
 // The settings are those of this moment: PvAmdSetBands, PvAmdSetModulationFrequencies and PvAmdSetSpectrumBins wait for a run in
@@ -181,7 +185,7 @@ void Solver::enqueueQuerySpectralRecords() {
     const RecordSet& r = recs_[kRecSpectral];
     if (!r.kinds || opt_.skipAnalysis) return;
     QuerySpectralArgs q{};
-    q.cells = numRecQueries_ > 0 ? rqCellsHost_ : qCellsHost_;
+    q.cells = recordCells();
     q.out = r.host;
     q.nq = recordQueryCount();
     const int n = (int)bandHz_.size(), B = bandMetricsBlock();
@@ -208,29 +212,135 @@ void Solver::enqueueQuerySpectralRecords() {
         q.slice[i] = QuerySpectralSlice{ps.bin0, ps.bins, ps.block, (long long)ps.tabOff};
     }
     if (q.nq > 0 && q.items[kQspecBandMetrics] + q.items[kQspecModulation] + q.items[kQspecSpectrum] > 0)
-        launchQuerySpectral(analyzeArgs(lastLx_, lastLz_), q, stream_);
+        launchQuerySpectral(recordArgs(), q, stream_);
+}
+
+// The record launches' arguments.  A sparse-emitter run's history is a ring: its record launches get the record traces as their
+// history planes (a.recTrace set: the launchers take the trace lane, recordLaneOfTrace)
+AnalyzeArgs Solver::recordArgs() const {
+    AnalyzeArgs a = analyzeArgs(lastLx_, lastLz_);
+    if (opt_.streaming) {
+        a.hist = a.recTrace;
+        a.histPlane = (long long)a.recCols * (a.recVel ? 3 : 1);
+        a.ring = 0;
+    }
+    return a;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// emitter records: the two families with the registered emitters of sparse-emitter mode as the cell source
+// ----------------------------------------------------------------------------------------------------------------
+
+namespace {
+const char kEmitterPre[] = "emitter records: ";
+const char kEmitterMode[] = "the solver is not in sparse-emitter mode (PvAmdSetQueryRecords serves the output queries of a solver that keeps its history)";
+const char kEmitterMax[] = "at most 1024 registered emitters while a kind is selected";
+constexpr unsigned kVelocityKinds = (1u << kQrecLateral) | (1u << kQrecEchogram) | (1u << kQrecLobes);
+}  // namespace
+
+// The record traces for `emitters` emitters under the two families' kinds: none while no kind is selected, else [T][P] floats, P
+// = the emitters rounded up to whole waves, times three where a velocity kind asks for the neighbours' columns
+bool Solver::fitRecTrace(int emitters, unsigned timeKinds, unsigned spectralKinds) {
+    if (!(timeKinds | spectralKinds)) {
+        if (recTrace_) hipFree(recTrace_);
+        recTrace_ = nullptr;
+        recTraceCap_ = 0;
+        recCols_ = 0;
+        recVel_ = false;
+        return true;
+    }
+    const int cols = (std::max(emitters, 1) + 63) / 64 * 64;
+    const bool vel = (timeKinds & kVelocityKinds) != 0;
+    const size_t need = (size_t)T_ * cols * (vel ? 3 : 1);
+    if (need > recTraceCap_) {
+        float* t = nullptr;
+        if (!hipOk(hipMalloc((void**)&t, need * sizeof(float)), "hipMalloc (record traces)")) return false;
+        if (recTrace_) hipFree(recTrace_);
+        recTrace_ = t;
+        recTraceCap_ = need;
+    }
+    recCols_ = cols;
+    recVel_ = vel;
+    return true;
+}
+
+bool Solver::setEmitterRecords(unsigned timeKinds, unsigned spectralKinds) {
+    const unsigned kinds[kRecordFamilies] = {timeKinds, spectralKinds};
+    for (int f = 0; f < kRecordFamilies; ++f) {  // (both families' refusals in front of either family's change)
+        const std::string why = selectRefusal((RecordFamily)f, kinds[f], true);
+        if (!why.empty()) return fail(why);
+    }
+    for (int f = 0; f < kRecordFamilies; ++f)
+        if (!selectRecords((RecordFamily)f, kinds[f], true)) return false;
+    // (no run in flight: selectRecords waited.  Every pass of a run writes every column of its steps: nothing to clear)
+    if (!fitRecTrace(numEmitters_, timeKinds, spectralKinds)) return false;
+    for (int f = 0; f < kRecordFamilies; ++f) invalidateRecords((RecordFamily)f);  // (the traces' layout may have changed)
+    return true;
+}
+
+int Solver::emitterRecordFloats(RecordFamily f, unsigned kind) {
+    if (!opt_.streaming) {
+        fail(std::string(kEmitterPre) + kEmitterMode);
+        return -1;
+    }
+    const int n = recordFloats(f, kind);
+    if (n < 0 && err_.compare(0, std::char_traits<char>::length(recs_[f].prefix), recs_[f].prefix) == 0)
+        err_ = kEmitterPre + err_.substr(std::char_traits<char>::length(recs_[f].prefix));
+    return n;
+}
+
+int Solver::emitterCells(int* cxcy, int cap) const {
+    for (int i = 0; i < numEmitters_ && i < cap; ++i) {
+        cxcy[2 * i] = (int)(emRecCells_[i] / g_.gy);
+        cxcy[2 * i + 1] = (int)(emRecCells_[i] % g_.gy);
+    }
+    return numEmitters_;
+}
+
+bool Solver::copyEmitterTrace(int emitter, float* outT) {
+    if (!opt_.streaming) return fail("emitter trace: the solver is not in sparse-emitter mode (PvAmdGetImpulseResponse serves a solver that keeps its history)");
+    if (emitter < 0 || emitter >= numEmitters_) return fail("emitter trace: no such registered emitter");
+    if (pendingTimings_ && !sync()) return false;
+    if (!streamedOnce_) return fail("emitter trace: no simulation has run yet");
+    if (lastRun_ == LastRun::Failed) return fail("emitter trace: the last run ended in error");
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (!hipOk(hipMemcpyAsync(outT, emTrace_ + (size_t)emitter * T_, (size_t)T_ * 4, hipMemcpyDeviceToHost, stream_), "trace copy")) return false;
+    return hipOk(hipStreamSynchronize(stream_), "trace sync");
 }
 
 // ----------------------------------------------------------------------------------------------------------------
 // in-run records: the selector, the pinned block and the stamp, for either family
 // ----------------------------------------------------------------------------------------------------------------
 
-bool Solver::selectRecords(RecordFamily f, unsigned kinds) {
-    RecordSet& r = recs_[f];
-    if (kinds & ~((1u << r.nKinds) - 1u)) return fail(std::string(r.prefix) + "unknown kind bit (" + r.bits + ")");
+std::string Solver::selectRefusal(RecordFamily f, unsigned kinds, bool emitters) const {
+    const RecordSet& r = recs_[f];
+    const std::string pre = emitters ? kEmitterPre : r.prefix;
+    if (emitters && !opt_.streaming) return pre + kEmitterMode;
+    if (kinds & ~((1u << r.nKinds) - 1u)) return pre + "unknown kind bit (" + r.bits + ")";
     if (kinds) {
-        if (isSlab()) return fail(std::string(r.prefix) + "not available on a slab");
-        if (opt_.streaming) return fail(std::string(r.prefix) + "the full pressure history is not kept in streaming-analysis mode");
-        if (opt_.skipAnalysis) return fail(std::string(r.prefix) + "the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+        if (isSlab()) return pre + "not available on a slab";
+        if (opt_.streaming && !emitters) return pre + "the full pressure history is not kept in streaming-analysis mode";
+        if (opt_.skipAnalysis) return pre + "the run has no onset map (PVA_OPT_SKIP_ANALYSIS)";
     }
-    if (const char* why = recordKindsRefusal(f, kinds)) return fail(why);
+    if (const char* why = recordKindsRefusal(f, kinds))  // (said with the family's own prefix)
+        return emitters ? pre + (why + std::char_traits<char>::length(r.prefix)) : std::string(why);
+    if (emitters && kinds && numEmitters_ > kMaxRecordQueries) return pre + kEmitterMax;
+    return std::string();
+}
+
+bool Solver::selectRecords(RecordFamily f, unsigned kinds, bool emitters) {
+    RecordSet& r = recs_[f];
+    const std::string why = selectRefusal(f, kinds, emitters);
+    if (!why.empty()) return fail(why);
+    if (opt_.streaming && !emitters) return true;  // (kinds = 0: nothing of the output queries' is selected in this mode)
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // the launch of a run in flight still writes the pinned block
     if (kinds == r.kinds) return true;
     // (the spectrum's tables are on the device from PvAmdSetSpectrumBins on; the modulation's are made valid here)
     if (f == kRecSpectral && (kinds & (1u << kQspecModulation)) && !ensureModTable()) return false;
-    if (!swapRecordBlock(f, kinds, numRecQueries_ > kMaxQueries ? numRecQueries_ : kMaxQueries)) return false;
+    const int table = opt_.streaming ? numEmitters_ : numRecQueries_;
+    if (!swapRecordBlock(f, kinds, table > kMaxQueries ? table : kMaxQueries)) return false;
     r.kinds = kinds;
     return true;
 }
@@ -285,16 +395,19 @@ void Solver::stampRecords(RecordFamily f, int nq, const bool* on, int* offset, i
 }
 
 // after the run has been waited for: the records of one kind, straight from pinned memory
-bool Solver::readRecords(RecordFamily f, unsigned kind, float* out, int n) {
+bool Solver::readRecords(RecordFamily f, unsigned kind, float* out, int n, bool emitters) {
     const RecordSet& r = recs_[f];
+    const std::string pre = emitters ? kEmitterPre : r.prefix, selector = emitters ? "PvAmdSetEmitterRecords" : r.selector;
+    if (emitters && !opt_.streaming) return fail(pre + kEmitterMode);
     const int k = oneKindBit(kind, r.nKinds);
-    if (k < 0) return fail(std::string(r.prefix) + "exactly one kind (" + r.bits + ")");
-    if (!(r.kinds & kind)) return fail(std::string(r.prefix) + "the kind is not selected (" + r.selector + ")");
-    if (n != recordQueryCount()) return fail(std::string(r.prefix) + "count differs from the registered queries");
+    if (k < 0) return fail(pre + "exactly one kind (" + r.bits + ")");
+    if (!(r.kinds & kind) || emitters != opt_.streaming) return fail(pre + "the kind is not selected (" + selector + ")");
+    if (n != recordQueryCount()) return fail(pre + (emitters ? "count differs from the registered emitters" : "count differs from the registered queries"));
     if (pendingTimings_ && !sync()) return false;
-    if (lastRun_ == LastRun::Failed) return fail(std::string(r.prefix) + "the last run ended in error");
+    if (lastRun_ == LastRun::Failed) return fail(pre + "the last run ended in error");
     if (r.run != RecordSet::Run::Ok || r.runKinds != r.kinds || r.runQueries != recordQueryCount() || r.runFloats[k] != recordFloatsOf(f, k))
-        return fail(std::string(r.prefix) + "no completed run since the kinds, the queries or the settings changed");
+        return fail(pre + (emitters ? "no completed run since the kinds, the emitters or the settings changed"
+                                    : "no completed run since the kinds, the queries or the settings changed"));
     const float* src = r.host + r.runOffset[k];
     for (int i = 0; i < n * r.runFloats[k]; ++i) out[i] = src[i];
     return true;
