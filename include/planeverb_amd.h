@@ -1295,7 +1295,8 @@ PVA_EXPORT int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const
  * plane in flight from the first PvAmdComputeZoneStats on -- the planes of a map are dealt in chunks that keep it within
  * 32 MiB (one plane's nZones x gx x 48 bytes where that is more) -- plus the records.
  * Out of scope: the eight-output result map (its far cells are kept lazily and carry values over between runs), histograms
- * and percentiles, overlapping zones, in-run or live-module zone records, slab groups, slab ranks and sparse-emitter solvers. */
+ * and percentiles, overlapping zones, in-run or live-module zone records, slab groups and slab ranks.  Sparse-emitter solvers
+ * take the labels (PvAmdSetZones, for the in-run zone curves below) but keep no history: PvAmdComputeZoneStats is refused there. */
 #define PVA_MAP_ROOM_METRICS     0
 #define PVA_MAP_DECAY_TIMES      1
 #define PVA_MAP_LATERAL_FRACTION 2
@@ -1315,7 +1316,9 @@ typedef struct PvAmdZoneStat {
 /* Set the zones: labels = gx*gy bytes, cell X*gy + Y, each 0 or 1 .. nZones (copied to the device; they survive runs and
  * geometry changes).  labels = NULL with nZones = 0 clears them.  Waits for a run in flight.  Refused with -1 and nothing
  * changed ("zone statistics: ..."): a label above nZones, nZones outside 1 .. PVA_ZONES_MAX, labels = NULL with nZones > 0,
- * slab groups, slab ranks and sparse-emitter solvers */
+ * slab groups and slab ranks; on a sparse-emitter solver also clearing the zones while PvAmdSetZoneCurves is enabled.  Labels
+ * alone change nothing about a sparse-emitter run; with the curves enabled, new labels re-derive the tiles, the launch box and
+ * the buffers, and the curves of the run before are refused */
 PVA_EXPORT int PvAmdSetZones(PvAmdSolver* s, const unsigned char* labels, int nZones);
 /* the labels as set (gx*gy bytes; labels may be NULL; untouched when no zones are set) and their count (0: none); returns 0 */
 PVA_EXPORT int PvAmdGetZones(PvAmdSolver* s, unsigned char* labels, int* nZones);
@@ -1369,8 +1372,18 @@ PVA_EXPORT int PvAmdHostZoneRects(float dx, int gx, int gy, const float* rect4, 
  * Device storage: the zone scratch of the zone statistics, grown on demand -- 8 bytes per zone, result row and time slot in
  * flight, the slots dealt in chunks that keep it within 32 MiB, plus nZones x T doubles and 12 bytes per zone and result row.
  * Per-band curves and the clarity and centre time of a zone's curve: the zone band decay below.
- * Out of scope: normalising each cell by its own E0, in-run or live-module records, overlapping zones, slab groups, slab ranks
- * and sparse-emitter solvers. */
+ * Sparse-emitter (PVA_OPT_STREAMING_ANALYSIS) solvers keep a ring of planes instead of the history.  There the ABSOLUTE curve
+ * is a streaming reduction -- etc[j] needs plane j and the onsets <= j only -- and is accumulated INSIDE every run that follows
+ * PvAmdSetZoneCurves(s, 1), per accumulate pass off the ring, by the definition above word for word (the launch covers the
+ * labels' bounding box: the rows and blocks it leaves out hold no member).  PvAmdComputeZoneDecay(ABSOLUTE) then runs the members
+ * pass over the run's onset map, copies nZones x T doubles and finishes on the host: the same records and curves, bit for bit,
+ * as a solver that keeps its history gives for the same scene, listener and labels.  While enabled, a tile that holds a
+ * labelled cell stays in the ring and records for the whole run, as a registered emitter's tile does; device storage:
+ * nZones x T doubles plus the row sums of one chunk of steps (8 bytes per zone, row of the box and step, within 32 MiB).
+ * PvAmdHostZoneCurveClarity gives such a curve its clarity and centre time.
+ * Out of scope: normalising each cell by its own E0, live-module records, overlapping zones, slab groups and slab ranks; in
+ * sparse-emitter mode also PVA_ZONE_DECAY_ONSET (every member's sample of a slot is needed at once, and they arrive at different
+ * steps), the band curves (the filter walks backwards in time) and the zone statistics. */
 #define PVA_ZONE_DECAY_ABSOLUTE 0
 #define PVA_ZONE_DECAY_ONSET    1
 typedef struct PvAmdZoneDecay {
@@ -1381,8 +1394,28 @@ typedef struct PvAmdZoneDecay {
  * etc / edc (optional): nZones x T doubles each, zone-major.  *ms (optional): device time of the passes.  Synchronous on the
  * solver's own stream (waits for a run in flight).  Nothing is cached and nothing invalidated: no map, plan or run chain is
  * touched.  Refused ("zone decay: ..."): NULL solver or out, a bad align, no zones set, cap < nZones, no completed run or a last
- * run that ended in error, sparse-emitter (streaming) solvers, PVA_OPT_SKIP_ANALYSIS, slab groups and slab ranks */
+ * run that ended in error, PVA_OPT_SKIP_ANALYSIS, slab groups and slab ranks; on a sparse-emitter (streaming) solver: curves not
+ * enabled ("... history is not kept ..."), align = ONSET, and a last run that was enqueued before the curves were enabled or
+ * before the current labels were set.  There the call launches the members pass only (*ms is its time) */
 PVA_EXPORT int PvAmdComputeZoneDecay(PvAmdSolver* s, int align, PvAmdZoneDecay* out, int cap, double* etc, double* edc, float* ms);
+/* Sparse-emitter solvers only: accumulate the ABSOLUTE zone curves inside every following run (enable != 0), or stop (0).  Needs
+ * zones (PvAmdSetZones); waits for a run in flight; allocates on enable and frees on disable; enabling twice changes nothing.
+ * Returns 0, or -1 with PvAmdLastError "zone curves: ...": NULL, a solver that keeps its history (it needs none of this), slab
+ * groups and slab ranks, no zones set.  With the curves disabled a run is launch for launch what it was before */
+PVA_EXPORT int PvAmdSetZoneCurves(PvAmdSolver* s, int enable);
+/* *enabled = 1 while PvAmdSetZoneCurves holds, else 0 (a solver that keeps its history: 0); returns 0 */
+PVA_EXPORT int PvAmdGetZoneCurves(PvAmdSolver* s, int* enabled);
+/* CPU only: what labels mean for a sparse-emitter run with the curves enabled -- flags = ceil(gx / tileRows) x ceil(gy / tileCols)
+ * bytes, 1 for every tile that holds a labelled cell (it stays in the ring), box4 = the first and last labelled row and the
+ * first and last labelled block of 64 Y (0, -1, 0, -1 for no labelled cell): the extent of the curve launches */
+PVA_EXPORT int PvAmdHostZoneTiles(const unsigned char* labels, int gx, int gy, int tileRows, int tileCols, unsigned char* flags,
+                                  int box4[4]);
+/* CPU only: out[t] = 1 where emitterFlags[t] or zoneFlags[t] is set (either may be NULL: none): the tile plane of a run */
+PVA_EXPORT int PvAmdHostZoneTileUnion(const unsigned char* emitterFlags, const unsigned char* zoneFlags, int ntiles,
+                                      unsigned char* out);
+/* CPU only: the steps of an accumulate pass one pair of curve launches takes for nZones zones and a box of `rows` rows under a
+ * scratch bound: a multiple of 16 whose row sums fit the bound, 16 where even that is more */
+PVA_EXPORT int PvAmdHostZoneCurveChunk(int nZones, int rows, long long scratchBytes);
 /* the time slots PvAmdComputeZoneDecay deals per pair of launches under the current zones (the scratch bound above); T and more:
  * all at once */
 PVA_EXPORT int PvAmdZoneDecayChunkSlots(PvAmdSolver* s);

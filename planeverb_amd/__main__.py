@@ -64,9 +64,10 @@ def zone_plane_names(s, a):
 def zone_tables(s, a):
     """one table per --zone: for every plane of every computed map its n (finite members), mean, std, min and max over the zone"""
     labels = api.zone_labels_from_rects(s.dx, s.gx, s.gy, a.zone)
-    s.set_zones(labels, len(a.zone))
+    if not a.sparse_emitters:  # (there the labels were set in front of the run, which accumulated the curves; no maps to reduce)
+        s.set_zones(labels, len(a.zone))
     tables = [{"rect": list(r), "cells": int((labels == j + 1).sum())} for j, r in enumerate(a.zone)]
-    for kind, key, names in zone_plane_names(s, a):
+    for kind, key, names in ([] if a.sparse_emitters else zone_plane_names(s, a)):
         recs = s.zone_stats(kind).reshape(len(a.zone), -1)
         for t, row in zip(tables, recs):
             t[key] = dict((n, {"n": int(r["n_finite"]), "mean": float(r["mean"]), "std": float(r["std"]), "min": float(r["min"]),
@@ -186,7 +187,8 @@ def main(argv=None):
                     help="a receiver area in metres (repeatable, at most 64; a later one overwrites an earlier one where they "
                          "overlap): with any of the map options above, add a table per zone with n, mean, std, min and max of "
                          "every plane of those maps over the zone's cells, reduced on the GPU; with --zone-decay, the zone's "
-                         "ensemble decay curve and its decay times")
+                         "ensemble decay curve and its decay times; with --sparse-emitters only --zone-decay absolute, whose "
+                         "curves are accumulated inside the run (no tables of the maps: that mode keeps no history)")
     ap.add_argument("--zone-decay", choices=api.ZONE_DECAY_ALIGN_NAMES,
                     help="with --zone (it counts as one of the options --zone needs): add per zone the ensemble decay curve's table "
                          "-- the squared responses of the zone's reached cells summed on the GPU, by time since emission (absolute) "
@@ -202,8 +204,11 @@ def main(argv=None):
 
     if a.modulation and not a.bands:
         ap.error("--modulation: needs --bands")
-    if a.zone and (a.in_run_records or a.sparse_emitters):
-        ap.error("--zone: reduces the whole-map passes (not with --in-run-records or --sparse-emitters)")
+    if a.zone and a.in_run_records:
+        ap.error("--zone: reduces the whole-map passes (not with --in-run-records)")
+    if a.zone and a.sparse_emitters and (a.zone_decay != "absolute" or a.zone_band_decay):
+        ap.error("--zone: with --sparse-emitters only --zone-decay absolute (the curves are accumulated inside the run; the "
+                 "onset-synchronised and the band curves need the history)")
     if a.in_run_records and a.sparse_emitters:
         ap.error("--sparse-emitters: not with --in-run-records (the output queries' records need the history)")
     if a.zone_decay and not a.zone:
@@ -250,6 +255,9 @@ def main(argv=None):
             if a.sparse_emitters:
                 s.set_emitters(emitters)
                 s.set_emitter_records(kinds, spectral)
+                if a.zone:  # (the curves of --zone-decay absolute are accumulated inside the run)
+                    s.set_zones(api.zone_labels_from_rects(s.dx, s.gx, s.gy, a.zone), len(a.zone))
+                    s.set_zone_curves(True)
             else:
                 s.set_output_queries(emitters)
                 s.set_query_records(kinds)

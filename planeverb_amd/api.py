@@ -364,6 +364,11 @@ SYMBOLS = {
     "PvAmdHostZoneRects": (C.c_int, [C.c_float, C.c_int, C.c_int, _fp, C.c_int, C.POINTER(C.c_ubyte)]),
     "PvAmdComputeZoneDecay": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _fp]),
     "PvAmdZoneDecayChunkSlots": (C.c_int, [_vp]),
+    "PvAmdSetZoneCurves": (C.c_int, [_vp, C.c_int]),
+    "PvAmdGetZoneCurves": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "PvAmdHostZoneTiles": (C.c_int, [C.POINTER(C.c_ubyte)] + [C.c_int] * 4 + [C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
+    "PvAmdHostZoneTileUnion": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.c_int, C.POINTER(C.c_ubyte)]),
+    "PvAmdHostZoneCurveChunk": (C.c_int, [C.c_int, C.c_int, C.c_longlong]),
     "PvAmdComputeZoneBandDecay": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _fp]),
     "PvAmdZoneBandDecayChunk": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "PvAmdHostZoneBandDecay": (C.c_int, [_fp, _fp] + [C.c_int] * 4 + [C.POINTER(C.c_ubyte), C.c_int, _fp, C.c_int, C.c_int, _vp,
@@ -1090,6 +1095,40 @@ def zone_labels_from_rects(dx, gx, gy, rects):
     _check(lib().PvAmdHostZoneRects(float(dx), int(gx), int(gy), _f(r) if r.size else None, len(r),
                                     out.ctypes.data_as(C.POINTER(C.c_ubyte))))
     return out
+
+
+def host_zone_tiles(labels, tile_rows, tile_cols):
+    """PvAmdHostZoneTiles: (flags uint8 [ceil(gx / tile_rows), ceil(gy / tile_cols)], (row0, row1, blk0, blk1)) -- the tiles that
+    hold a labelled cell and the labels' bounding box in result rows and blocks of 64 Y ((0, -1, 0, -1): nothing labelled); what
+    Solver.set_zone_curves derives from the labels"""
+    lab = np.ascontiguousarray(labels, np.uint8)
+    if lab.ndim != 2 or not lab.size:
+        raise ValueError("host_zone_tiles: labels [gx, gy]")
+    gx, gy = lab.shape
+    flags = np.zeros((-(-gx // int(tile_rows)), -(-gy // int(tile_cols))), np.uint8)
+    box = (C.c_int * 4)()
+    _check(lib().PvAmdHostZoneTiles(lab.ctypes.data_as(C.POINTER(C.c_ubyte)), gx, gy, int(tile_rows), int(tile_cols),
+                                    flags.ctypes.data_as(C.POINTER(C.c_ubyte)), box))
+    return flags, tuple(box)
+
+
+def host_zone_tile_union(emitter_flags, zone_flags, n_tiles):
+    """PvAmdHostZoneTileUnion: uint8 [n_tiles], 1 where either side (uint8 [n_tiles], or None) is set"""
+    sides = [None if f is None else np.ascontiguousarray(f, np.uint8).reshape(-1) for f in (emitter_flags, zone_flags)]
+    if any(f is not None and f.size != int(n_tiles) for f in sides):
+        raise ValueError("host_zone_tile_union: flags of n_tiles bytes")
+    out = np.zeros(int(n_tiles), np.uint8)
+    _check(lib().PvAmdHostZoneTileUnion(*[None if f is None else f.ctypes.data_as(C.POINTER(C.c_ubyte)) for f in sides], int(n_tiles),
+                                        out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return out
+
+
+def host_zone_curve_chunk(n_zones, rows, scratch_bytes=32 << 20):
+    """PvAmdHostZoneCurveChunk: the steps of an accumulate pass one pair of in-run curve launches takes"""
+    n = lib().PvAmdHostZoneCurveChunk(int(n_zones), int(rows), int(scratch_bytes))
+    if n < 0:
+        raise PlaneverbError(last_error())
+    return n
 
 
 # PVA_ZONE_DECAY_*: how the cells' samples are put into the time slots of a zone's ensemble decay curve
@@ -2234,6 +2273,17 @@ class Solver:
             raise PlaneverbError(last_error())
         res = (out[:n],) + ((etc[:n], edc[:n]) if curves else ()) + ((ms.value,) if with_ms else ())
         return res[0] if len(res) == 1 else res
+
+    def set_zone_curves(self, on):
+        """PvAmdSetZoneCurves (sparse-emitter solvers, zones set): every following run accumulates the "absolute" curves of the
+        zones on the device, off the ring, and zone_decay("absolute") reads them; False stops it and frees the buffers"""
+        _check(lib().PvAmdSetZoneCurves(self._h, 1 if on else 0))
+
+    def zone_curves(self):
+        """PvAmdGetZoneCurves: True while set_zone_curves(True) holds"""
+        on = C.c_int(0)
+        _check(lib().PvAmdGetZoneCurves(self._h, C.byref(on)))
+        return bool(on.value)
 
     def zone_decay_chunk_slots(self):
         """PvAmdZoneDecayChunkSlots: the time slots zone_decay deals per pair of launches under the current zones"""

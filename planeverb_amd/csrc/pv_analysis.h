@@ -100,8 +100,9 @@ __device__ __forceinline__ float efreePerR(float efree, float dx, int lX, int lY
     return efree / r;
 }
 
-// is `tile` one whose forward sums live in the stencil?  (air class, no registered emitter, not the listener's tile -- that
-// one is on the general list for the run)
+// is `tile` one whose forward sums live in the stencil?  (air class, no registered emitter and -- while the zone curves are enabled
+// -- no labelled cell: tileEmit is the union of both, Solver::uploadTileEmit; not the listener's tile -- that one is on the general
+// list for the run)
 __device__ __forceinline__ bool fusedTile(const uint8_t* tileClass, const uint8_t* tileEmit, const DynParams& dyn, int ti,
                                           int tj, int nty, int G, int K, int rxi, int wi, int rows, int withPulse) {
     const int t = ti * nty + tj;

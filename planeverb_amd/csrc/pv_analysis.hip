@@ -705,7 +705,7 @@ __global__ void pv_stream_emitter_kernel(const AnalyzeArgs a) {
 }
 
 // tileOpen[tile] for the next launches: some cell marked it open in this pass, or the wave has not reached it yet,
-// or it holds a registered emitter (its whole trace is needed)
+// or it holds a registered emitter (its whole trace is needed) or a cell of a zone whose curve is accumulated (every step of it is)
 __global__ void pv_stream_tilegate_kernel(const uint8_t* marks, const uint8_t* hasEmitter, const int* tileFirst, int tB,
                                           uint8_t* tileOpen, int ntiles) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -713,7 +713,7 @@ __global__ void pv_stream_tilegate_kernel(const uint8_t* marks, const uint8_t* h
 }
 
 void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
-                       hipStream_t stream) {
+                       hipStream_t stream, const StreamZoneCurveArgs* zc, double* zcEtc, int zcChunk) {
     dim3 grid((a.gy + 255) / 256, a.gx);
     if (a.ringList) grid = dim3((unsigned)((a.rxi * a.wi + 255) / 256) * (unsigned)(a.numRing > 0 ? a.numRing : 1), 1);
     hipMemsetAsync(a.tileOpenOut, 0, (size_t)ntiles, stream);
@@ -725,6 +725,9 @@ void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t*
     if (n > 0 && a.recTrace)
         hipLaunchKernelGGL(pv_stream_rectrace_kernel, dim3((unsigned)((a.recCols * (a.recVel ? 3 : 1) + 255) / 256), (unsigned)(a.tB - a.tA)),
                            dim3(256), 0, stream, a);
+    // the zones' curves of this pass's steps: behind the accumulate kernel, whose onsets decide the members, and -- as everything
+    // in here -- in front of the event that hands the half ring back to the step kernels
+    if (zc) launchStreamZoneCurves(*zc, zcEtc, a.tA, a.tB, zcChunk, stream);
 }
 
 void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream) {

@@ -1678,6 +1678,18 @@ int PvAmdZoneDecayChunkSlots(PvAmdSolver* h) try {
     return h->s->zoneDecayChunkSlots();
 } PV_API_CATCH(-1)
 
+// the ABSOLUTE curves inside a sparse-emitter run (pv_zone_decay.hip pv_stream_zone_curve_rows_kernel)
+int PvAmdSetZoneCurves(PvAmdSolver* h, int enable) try {
+    if (!analysisHandle(h, "zone curves: ")) return -1;
+    return ret(h, h->s->setZoneCurves(enable != 0));
+} PV_API_CATCH(-1)
+
+int PvAmdGetZoneCurves(PvAmdSolver* h, int* enabled) try {
+    if (!analysisHandle(h, "zone curves: ")) return -1;
+    if (enabled) *enabled = h->s->zoneCurves() ? 1 : 0;
+    return 0;
+} PV_API_CATCH(-1)
+
 // zone band decay (pv_zone_band_decay.hip)
 static_assert(sizeof(PvAmdZoneBandDecay) == sizeof(ZoneBandDecay), "96 bytes");
 
@@ -2252,6 +2264,33 @@ int PvAmdHostZoneCurveClarity(const double* etc, int T, int fs, int j0, double o
     }
     zoneCurveClarity(etc, T, fs, j0, out4);
     return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostZoneTiles(const unsigned char* labels, int gx, int gy, int tileRows, int tileCols, unsigned char* flags, int box4[4]) try {
+    if (!labels || !flags || !box4 || gx < 1 || gy < 1 || tileRows < 1 || tileCols < 1) {
+        g_lastError = "zone curves: PvAmdHostZoneTiles: gx x gy labels, gx, gy, tileRows, tileCols >= 1, ceil(gx / tileRows) x ceil(gy / tileCols) flags and four ints";
+        return -1;
+    }
+    const ZoneTileBox b = zoneTileFlags(labels, gx, gy, tileRows, tileCols, flags);
+    box4[0] = b.row0, box4[1] = b.row1, box4[2] = b.blk0, box4[3] = b.blk1;
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostZoneTileUnion(const unsigned char* emitterFlags, const unsigned char* zoneFlags, int ntiles, unsigned char* out) try {
+    if (!out || ntiles < 0) {
+        g_lastError = "zone curves: PvAmdHostZoneTileUnion: ntiles >= 0 and an output of ntiles bytes";
+        return -1;
+    }
+    zoneTileUnion(emitterFlags, zoneFlags, ntiles, out);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostZoneCurveChunk(int nZones, int rows, long long scratchBytes) try {
+    if (nZones < 1 || nZones > kZonesMax || rows < 1 || scratchBytes < 0) {
+        g_lastError = "zone curves: PvAmdHostZoneCurveChunk: nZones 1 .. 64, rows >= 1, scratchBytes >= 0";
+        return -1;
+    }
+    return streamZoneCurveChunk(nZones, rows, (size_t)scratchBytes);
 } PV_API_CATCH(-1)
 
 int PvAmdHostZoneRects(float dx, int gx, int gy, const float* rect4, int n, unsigned char* labels) try {

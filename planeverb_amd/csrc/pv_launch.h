@@ -118,8 +118,10 @@ void launchAnalysisDirection(const AnalyzeArgs& a, hipStream_t stream);
 // direction planes of the far cells, for whole-map read-backs; delay plane = "no onset" everywhere (solver creation)
 void launchFarDirections(float* res, long long n, const FarInfo& far, hipStream_t stream);
 void launchFillDelay(float* delay, long long n, hipStream_t stream);
+// (zc: the zones' curves of the pass's steps behind its onsets -- launchStreamZoneCurves below --, nullptr: none)
+struct StreamZoneCurveArgs;
 void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
-                       hipStream_t stream);
+                       hipStream_t stream, const StreamZoneCurveArgs* zc = nullptr, double* zcEtc = nullptr, int zcChunk = 0);
 void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream);
 
 // ---- pv_rt60.hip: wet gain and decay time; results carried over from another solver
@@ -160,6 +162,9 @@ void launchZoneStats(const ZoneArgs& a, hipStream_t stream);
 struct ZoneCurveArgs;
 void launchZoneMembers(const ZoneCurveArgs& a, hipStream_t stream);
 void launchZoneCurves(const ZoneCurveArgs& a, bool onset, hipStream_t stream);
+// sparse-emitter mode: steps [tA, min(tB, a.T)) of every zone's ABSOLUTE curve into etc (nZones x T), off the ring, in chunks of
+// `chunk` steps (pv_zone_decay.h streamZoneCurveChunk; a.slot0 / a.slots are the launcher's; a.rowSums is scratch)
+void launchStreamZoneCurves(const StreamZoneCurveArgs& a, double* etc, int tA, int tB, int chunk, hipStream_t stream);
 
 // ---- pv_zone_band_decay.hip: per-zone ensemble decay curves per band
 // etc of one chunk of (zone, band) pairs -- zones a.zone0 + 1 .. a.zone0 + a.zones, bands a.band0 .. a.band0 + a.bands - 1 -- into

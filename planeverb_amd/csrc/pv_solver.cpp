@@ -27,6 +27,7 @@
 #include "pv_lobes.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
+#include "pv_zone_decay.h"
 
 namespace pva {
 
@@ -697,6 +698,7 @@ Solver::~Solver() {
         if (p) hipFree(p);
     for (unsigned char* p : {zoneLabels_, zoneScratch_})
         if (p) hipFree(p);
+    freeZoneCurves();
     for (RecordSet& r : recs_)
         if (r.host) hipHostFree(r.host);
     if (rqCellsHost_) hipHostFree(rqCellsHost_);
@@ -2254,6 +2256,30 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
             return false;
     }
     AnalyzeArgs aa = analyzeArgs(lx, lz);
+    // the zones' curves (setZoneCurves): every accumulate pass reduces its own steps.  A box without a labelled cell is launched
+    // as one row and one block, which find no member and leave +0.0 in every slot
+    StreamZoneCurveArgs zc{};
+    if (zoneCurvesOn_) {
+        zc.hist = aa.hist;
+        zc.histPlane = aa.histPlane;
+        zc.ring = aa.ring;
+        zc.onset = sOnset_;
+        zc.labels = zoneLabels_;
+        zc.dyn = aa.dyn;
+        zc.gx = g_.gx;
+        zc.gy = g_.gy;
+        zc.nZones = zoneCount_;
+        zc.T = T_;
+        zc.G = geo_.G;
+        zc.rxi = rxi_;
+        zc.wi = wi_;
+        zc.row0 = zoneBox_[0];
+        zc.rows = std::max(zoneBox_[1] - zoneBox_[0] + 1, 1);
+        zc.blk0 = zoneBox_[2];
+        zc.blks = std::max(zoneBox_[3] - zoneBox_[2] + 1, 1);
+        zc.rowSums = zoneCurveRows_;
+    }
+    zoneCurveRun_ = zoneCurvesOn_ ? zoneCurveSetting_ : 0;
     if (streamEv_[0] == nullptr)
         for (auto& e : streamEv_)
             if (!hipOk(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) return false;
@@ -2280,7 +2306,7 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
         hipStreamWaitEvent(stream2_, streamEv_[h], 0);
         aa.tA = tA;
         aa.tB = tA + n;
-        launchStreamAccum(aa, tileEmit_, tileOpen_, ntiles, stream2_);
+        launchStreamAccum(aa, tileEmit_, tileOpen_, ntiles, stream2_, zoneCurvesOn_ ? &zc : nullptr, zoneCurveEtc_, zoneCurveChunk_);
         if (streamFuse_ && !fuseIdle_) launchStreamIdle(classifyArgs(baseStepArgs(true, true), 0, true), idleHost_ + h, stream2_);
         hipEventRecord(streamEv_[2 + h], stream2_);
     }
@@ -2843,12 +2869,22 @@ bool Solver::setEmitters(const float* xyz, int n) {
     // about one process out of four).
     std::vector<uint8_t> te((size_t)geo_.ntx * geo_.nty, 0);
     for (int c : cells) te[(size_t)((c / g_.gy) / rxi_) * geo_.nty + (c % g_.gy) / wi_] = 1;
-    emTilesHost_ = te;
-    if (!hipOk(hipMemcpyAsync(tileEmit_, te.data(), te.size(), hipMemcpyHostToDevice, stream_), "emitter tiles")) return false;
+    emitterTilesHost_ = te;
+    if (!uploadTileEmit()) return false;
     if (numEmitters_ > 0 &&
         !hipOk(hipMemcpyAsync(emCells_, cells.data(), cells.size() * 4, hipMemcpyHostToDevice, stream_), "emitters"))
         return false;
     return hipOk(hipStreamSynchronize(stream_), "emitter upload");
+}
+
+// the tile plane fusedTile() and the tile gate read, and its host copy (enqueueStreamingRun's ring list): the emitters' tiles,
+// united with the zones' while the curves are enabled (pv_zone_decay.h zoneTileUnion).  The caller syncs stream_
+bool Solver::uploadTileEmit() {
+    const int ntiles = geo_.ntx * geo_.nty;
+    emTilesHost_.assign((size_t)ntiles, 0);
+    zoneTileUnion(emitterTilesHost_.empty() ? nullptr : emitterTilesHost_.data(), zoneTilesHost_.empty() ? nullptr : zoneTilesHost_.data(),
+                  ntiles, emTilesHost_.data());
+    return hipOk(hipMemcpyAsync(tileEmit_, emTilesHost_.data(), emTilesHost_.size(), hipMemcpyHostToDevice, stream_), "emitter tiles");
 }
 
 bool Solver::impulseResponse(int cx, int cy, float* out3T) {

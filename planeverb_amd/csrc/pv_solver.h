@@ -372,6 +372,15 @@ public:
     // zoneDecayChunkSlots: the time slots one pair of launches covers under the current zones (T and more: all of them at once)
     bool computeZoneDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count);
     int zoneDecayChunkSlots() const;
+    // Sparse-emitter solvers keep a ring, not the history: there the ABSOLUTE curves are accumulated INSIDE every run enqueued
+    // while setZoneCurves(true) holds (pv_zone_decay.hip pv_stream_zone_curve_rows_kernel, per accumulate pass), and
+    // computeZoneDecay(ABSOLUTE) reads them -- members pass, one copy, the host finish.  Needs zones; waits for a run in flight;
+    // allocates on enable (nZones x T doubles and the row sums of one chunk of steps), frees on disable; while enabled the tiles
+    // that hold a labelled cell stay in the ring and record for the whole run, as the emitters' tiles do, and the zones cannot be
+    // cleared.  The curves carry the stamp of the run they were enqueued with: a call after setZones / setZoneCurves and before
+    // the next run is refused
+    bool setZoneCurves(bool on);
+    bool zoneCurves() const;
     // Zone band decay (pv_zone_band_decay.hip; include/planeverb_amd.h PvAmdZoneBandDecay): the same curve per band of setBands,
     // off the band-filtered history -- out = nZones x nBands records, etc / edc (either may be nullptr) = nZones x nBands x T
     // doubles.  Nothing cached, no map, plan or run chain touched; the bands are read at the call; waits for a run in flight.
@@ -537,7 +546,7 @@ private:
     float* sState_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // Edry, fluxX, fluxY, vx, vy
     uint8_t* tileOpen_ = nullptr;   // per tile: history still wanted (streaming mode)
     uint8_t* tileMarks_ = nullptr;  // scratch of one accumulate pass
-    uint8_t* tileEmit_ = nullptr;   // per tile: holds a registered emitter
+    uint8_t* tileEmit_ = nullptr;   // per tile: holds a registered emitter or, while the zone curves are enabled, a labelled cell
     // forward sums inside the stencil (pv_stream.h)
     bool streamFuse_ = false;
     uint8_t* classStream_ = nullptr;   // per-launch tile classes (open air tiles masked out of the merged launch)
@@ -551,6 +560,7 @@ private:
     int* ringHost_ = nullptr;          // pinned staging of it
     int numRing_ = 0;
     std::vector<uint8_t> emTilesHost_; // host copy of tileEmit_
+    std::vector<uint8_t> emitterTilesHost_;  // the registered emitters' part of it (setEmitters; uploadTileEmit adds the zones')
     int* openCount_ = nullptr;         // two counters, alternating from launch to launch
     int* emCells_ = nullptr;
     float* emTrace_ = nullptr;
@@ -669,6 +679,23 @@ private:
     int zoneCount_ = 0;
     unsigned char* zoneScratch_ = nullptr;
     size_t zoneScratchBytes_ = 0;
+    // sparse-emitter mode, curves enabled (setZoneCurves): the curves of the last run enqueued with them (nZones x T), the row sums
+    // of one chunk of an accumulate pass's steps -- a scratch of their own: the pass runs on stream2_, the calls above on stream_
+    // --, the tiles that hold a labelled cell, the labels' bounding box, and two stamps: zoneCurveSetting_ counts the changes of
+    // labels or switch, zoneCurveRun_ is its value when the last run was enqueued (0: that run accumulated no curves)
+    bool deriveZoneCurves();  // (everything below from zoneHost_ / zoneCount_; uploads the tile plane)
+    bool disableZoneCurves();
+    bool streamZoneDecay(void* out, double* etc, double* edc, float* ms, int* count);
+    void freeZoneCurves();
+    bool uploadTileEmit();    // tileEmit_ = the emitters' tiles, united with the zones' while the curves are enabled
+    bool zoneCurvesOn_ = false;
+    double* zoneCurveEtc_ = nullptr;
+    double* zoneCurveRows_ = nullptr;
+    size_t zoneCurveEtcBytes_ = 0, zoneCurveRowsBytes_ = 0;
+    std::vector<uint8_t> zoneTilesHost_;  // per tile of the grid (geo_.ntx x geo_.nty); empty while disabled
+    int zoneBox_[4] = {0, -1, 0, -1};     // first / last labelled row, first / last labelled 64-block
+    int zoneCurveChunk_ = 0;
+    unsigned long long zoneCurveSetting_ = 0, zoneCurveRun_ = 0;
     size_t scratchCount_ = 0;
 
     // pinned host staging

@@ -217,11 +217,11 @@ bool Solver::analysisAt(AnalysisKind k, float ex, float ez, float* out) {
 
 bool Solver::setZones(const unsigned char* labels, int nZones) {
     if (isSlab()) return fail("zone statistics: not available on a slab");
-    if (opt_.streaming) return fail("zone statistics: the full pressure history is not kept in streaming-analysis mode");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
     if (nZones == 0) {
+        if (zoneCurvesOn_) return fail("zone statistics: the zones cannot be cleared while the zone curves are enabled (PvAmdSetZoneCurves)");
         zoneCount_ = 0;
         zoneHost_.clear();
         return true;
@@ -232,11 +232,88 @@ bool Solver::setZones(const unsigned char* labels, int nZones) {
         !hipOk(hipStreamSynchronize(stream_), "zone labels sync")) {
         zoneCount_ = 0;  // (the device labels are neither the old nor the new ones)
         zoneHost_.clear();
+        if (zoneCurvesOn_) disableZoneCurves();
         return false;
     }
     zoneHost_.assign(labels, labels + cells);
     zoneCount_ = nZones;
+    // (sparse-emitter mode with the curves enabled: the tiles, the box and the buffers follow the labels; the curves of the last run
+    // are the old labels' and are refused until the next one)
+    if (zoneCurvesOn_ && !deriveZoneCurves()) {
+        const std::string why = err_;
+        disableZoneCurves();
+        return fail(why);
+    }
     return true;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// zone curves inside a sparse-emitter run (pv_zone_decay.hip pv_stream_zone_curve_rows_kernel)
+// ----------------------------------------------------------------------------------------------------------------
+
+void Solver::freeZoneCurves() {
+    if (zoneCurveEtc_) hipFree(zoneCurveEtc_), deviceBytes_ -= (long long)zoneCurveEtcBytes_;
+    if (zoneCurveRows_) hipFree(zoneCurveRows_), deviceBytes_ -= (long long)zoneCurveRowsBytes_;
+    zoneCurveEtc_ = zoneCurveRows_ = nullptr;
+    zoneCurveEtcBytes_ = zoneCurveRowsBytes_ = 0;
+}
+
+// (no run in flight) back to the emitters' tile plane; the buffers go
+bool Solver::disableZoneCurves() {
+    zoneCurvesOn_ = false;
+    ++zoneCurveSetting_;
+    zoneTilesHost_.clear();
+    freeZoneCurves();
+    return uploadTileEmit() && hipOk(hipStreamSynchronize(stream_), "tile plane upload");
+}
+
+bool Solver::deriveZoneCurves() {
+    ++zoneCurveSetting_;
+    const int ntx = (g_.gx + rxi_ - 1) / rxi_, nty = (g_.gy + wi_ - 1) / wi_;
+    if (ntx > geo_.ntx || nty > geo_.nty) return fail("the result map reaches past the tile grid");
+    std::vector<unsigned char> flags((size_t)ntx * nty);
+    const ZoneTileBox b = zoneTileFlags(zoneHost_.data(), g_.gx, g_.gy, rxi_, wi_, flags.data());
+    zoneTilesHost_.assign((size_t)geo_.ntx * geo_.nty, 0);
+    for (int ti = 0; ti < ntx; ++ti)
+        for (int tj = 0; tj < nty; ++tj) zoneTilesHost_[(size_t)ti * geo_.nty + tj] = flags[(size_t)ti * nty + tj];
+    zoneBox_[0] = b.row0, zoneBox_[1] = b.row1, zoneBox_[2] = b.blk0, zoneBox_[3] = b.blk1;
+    const int rows = std::max(b.row1 - b.row0 + 1, 1);
+    // the steps of a pass per pair of launches; a pass has halfRing_ of them at the most
+    zoneCurveChunk_ = std::min(streamZoneCurveChunk(zoneCount_, rows, kZoneScratchBytes),
+                               (halfRing_ + kZoneCurveSlots - 1) / kZoneCurveSlots * kZoneCurveSlots);
+    const size_t etcBytes = (size_t)zoneCount_ * (size_t)T_ * sizeof(double);
+    const size_t rowsBytes = (size_t)zoneCurveChunk_ * (size_t)zoneCount_ * (size_t)rows * sizeof(double);
+    if (etcBytes != zoneCurveEtcBytes_ || rowsBytes > zoneCurveRowsBytes_) {
+        freeZoneCurves();
+        if (!dalloc(&zoneCurveEtc_, etcBytes / sizeof(double), false)) return false;
+        zoneCurveEtcBytes_ = etcBytes;
+        if (!dalloc(&zoneCurveRows_, rowsBytes / sizeof(double), false)) return false;
+        zoneCurveRowsBytes_ = rowsBytes;
+    }
+    return uploadTileEmit() && hipOk(hipStreamSynchronize(stream_), "tile plane upload");
+}
+
+bool Solver::setZoneCurves(bool on) {
+    if (isSlab()) return fail("zone curves: not available on a slab");
+    if (!opt_.streaming) return fail("zone curves: sparse-emitter solvers only (PVA_OPT_STREAMING_ANALYSIS): a solver that keeps its history computes the curves after the run");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight reads the tile plane and writes the curves)
+    if (!on) return zoneCurvesOn_ ? disableZoneCurves() : true;
+    if (!zoneCount_) return fail("zone curves: no zones set (PvAmdSetZones)");
+    if (zoneCurvesOn_) return true;
+    zoneCurvesOn_ = true;
+    if (!deriveZoneCurves()) {
+        const std::string why = err_;
+        disableZoneCurves();
+        return fail("zone curves: " + why);
+    }
+    return true;
+}
+
+bool Solver::zoneCurves() const {
+    const auto inUse = queue_.lockUse();
+    return zoneCurvesOn_;
 }
 
 int Solver::zones(unsigned char* labels) const {
@@ -341,15 +418,23 @@ int Solver::zoneDecayChunkSlots() const {
 
 bool Solver::computeZoneDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count) {
     if (isSlab()) return fail("zone decay: not available on a slab");
-    if (opt_.streaming) return fail("zone decay: the full pressure history is not kept in streaming-analysis mode");
     if (opt_.skipAnalysis) return fail("zone decay: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    if (opt_.streaming) {
+        if (!zoneCurvesOn_)
+            return fail("zone decay: the full pressure history is not kept in streaming-analysis mode: the ABSOLUTE curves are accumulated "
+                        "inside the runs that follow PvAmdSetZoneCurves");
+        if (align != kZoneDecayAbsolute)
+            return fail("zone decay: onset-synchronised curves need the full pressure history, which streaming-analysis mode does not keep "
+                        "(PVA_ZONE_DECAY_ABSOLUTE only)");
+    }
     if (!zoneCount_) return fail("zone decay: no zones set (PvAmdSetZones)");
     if (cap < zoneCount_) return fail("zone decay: PvAmdComputeZoneDecay: the output holds fewer than nZones records");
     if (lastRun_ == LastRun::None || !dynValid_) return fail("zone decay: no completed run");
     if (lastRun_ != LastRun::Ok) return fail("zone decay: the last run ended in error");
+    if (opt_.streaming) return streamZoneDecay(out, etc, edc, ms, count);
     const int T = T_, nz = zoneCount_;
     // scratch: the row sums of one chunk of slots, the curves, the zones' member rows and records
     const int chunk = std::min(zoneDecayChunkSlots(), T);
@@ -402,6 +487,59 @@ bool Solver::computeZoneDecay(int align, void* out, int cap, double* etc, double
         recs[z].t_first = members[(size_t)z].t_first;
         recs[z].t_last = members[(size_t)z].t_last;
         zoneDecayFinish(etc + (size_t)z * T, edc ? edc + (size_t)z * T : edcHost.data(), T, (int)g_.fs, align, &recs[z]);
+    }
+    *count = nz;
+    return true;
+}
+
+// computeZoneDecay(ABSOLUTE) of a sparse-emitter solver (the caller holds the lock and has checked zones, output and run): the
+// curves are the last run's own (enqueueStreamingRun), so what is left is the members pass over the finalize pass's delay map,
+// one copy and the host finish.  No curve kernel is launched here: *ms is the members pass
+bool Solver::streamZoneDecay(void* out, double* etc, double* edc, float* ms, int* count) {
+    if (zoneCurveRun_ != zoneCurveSetting_)
+        return fail("zone decay: the last run was enqueued before the zone curves were enabled or before the current zones were set");
+    const int T = T_, nz = zoneCount_;
+    const size_t etcBytes = (size_t)nz * (size_t)T * sizeof(double);
+    const size_t memberRowsBytes = ((size_t)nz * (size_t)g_.gx * sizeof(ZoneMembers) + 7) / 8 * 8;
+    if (!growZoneScratch(memberRowsBytes + (size_t)nz * sizeof(ZoneMembers))) return false;
+    for (auto& e : mapEv_)
+        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
+    ZoneCurveArgs a{};
+    a.histPlane = histPlane_;
+    a.delay = delay_;
+    a.labels = zoneLabels_;
+    a.gx = g_.gx;
+    a.gy = g_.gy;
+    a.nZones = nz;
+    a.T = T;
+    a.wr0 = dynCur_.histRow0 - geo_.G;  // (the window as the last run recorded it: the whole tile grid in this mode)
+    a.wc0 = dynCur_.histCol0 - geo_.G;
+    a.wnr = std::min(dynCur_.histTilesX, histTilesX_) * rxi_;
+    a.wnc = std::min(dynCur_.histTilesY, histTilesY_) * wi_;
+    a.rxi = rxi_;
+    a.wi = wi_;
+    a.tilesY = dynCur_.histTilesY;
+    a.memberRows = reinterpret_cast<ZoneMembers*>(zoneScratch_);
+    a.members = reinterpret_cast<ZoneMembers*>(zoneScratch_ + memberRowsBytes);
+    hipEventRecord(mapEv_[0], stream_);
+    launchZoneMembers(a, stream_);
+    hipEventRecord(mapEv_[1], stream_);
+    std::vector<double> etcHost, edcHost;
+    if (!etc) etcHost.resize((size_t)nz * T), etc = etcHost.data();
+    std::vector<ZoneMembers> members((size_t)nz);
+    if (!hipOk(hipGetLastError(), "zone decay launch") ||
+        !hipOk(hipMemcpyAsync(etc, zoneCurveEtc_, etcBytes, hipMemcpyDeviceToHost, stream_), "zone decay copy") ||
+        !hipOk(hipMemcpyAsync(members.data(), a.members, (size_t)nz * sizeof(ZoneMembers), hipMemcpyDeviceToHost, stream_), "zone decay copy") ||
+        !hipOk(hipStreamSynchronize(stream_), "zone decay sync"))
+        return false;
+    if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
+    if (!edc) edcHost.resize((size_t)T);
+    ZoneDecay* recs = static_cast<ZoneDecay*>(out);
+    for (int z = 0; z < nz; ++z) {
+        recs[z].n_cells = members[(size_t)z].n_cells;
+        recs[z].t_first = members[(size_t)z].t_first;
+        recs[z].t_last = members[(size_t)z].t_last;
+        zoneDecayFinish(etc + (size_t)z * T, edc ? edc + (size_t)z * T : edcHost.data(), T, (int)g_.fs, kZoneDecayAbsolute, &recs[z]);
     }
     *count = nz;
     return true;

@@ -55,6 +55,66 @@ struct ZoneCurveArgs {
     ZoneMembers* members;         // nZones
 };
 
+// ---- sparse-emitter mode: the ABSOLUTE curve inside the run (pv_zone_decay.hip pv_stream_zone_curve_rows_kernel).  The history is
+// a ring of planes there, so the reduction runs per accumulate pass over the pass's steps, with the onsets that pass has just
+// settled (slot t needs plane t and the onsets <= t only).  The launch covers the labels' bounding box: a row or a 64-block
+// without a labelled cell is skipped by the definition itself
+struct DynParams;  // (pv_device.h)
+struct StreamZoneCurveArgs {
+    const float* hist;            // plane 0 of the ring: `ring` planes of histPlane floats, step t in plane t % ring
+    long long histPlane;
+    int ring;
+    const int* onset;             // gx * gy: the accumulate pass's onsets, -1 = none yet
+    const unsigned char* labels;  // gx * gy
+    const DynParams* dyn;         // the run's history window (device)
+    int gx, gy, nZones, T, G;
+    int rxi, wi;                  // tile interior (pv_prims.h histOffset)
+    int row0, rows;               // the result rows of the launch: row0 .. row0 + rows - 1
+    int blk0, blks;               // ... and its blocks of 64 Y, aligned at Y = 0: blk0 .. blk0 + blks - 1
+    int slot0, slots;             // the chunk: steps slot0 .. slot0 + slots - 1, all below T
+    double* rowSums;              // slots x nZones x rows: the row sums of the chunk
+};
+
+// What a zone's labels mean for the tiles and for the launch above (Solver::setZones): flags[ti * nty + tj] = 1 for every tile of
+// rxi x wi result cells that holds a labelled cell -- ntx = ceil(gx / rxi) rows of nty = ceil(gy / wi) tiles --, the first and
+// last labelled result row and the first and last labelled block of 64 Y.  Nothing labelled: no flag, rows 0 .. -1, blocks 0 .. -1
+struct ZoneTileBox {
+    int row0, row1, blk0, blk1;
+};
+inline ZoneTileBox zoneTileFlags(const unsigned char* labels, int gx, int gy, int rxi, int wi, unsigned char* flags) {
+    const int ntx = (gx + rxi - 1) / rxi, nty = (gy + wi - 1) / wi;
+    for (int t = 0; t < ntx * nty; ++t) flags[t] = 0;
+    ZoneTileBox b{0, -1, 0, -1};
+    bool any = false;
+    for (int X = 0; X < gx; ++X)
+        for (int Y = 0; Y < gy; ++Y) {
+            if (!labels[(size_t)X * gy + Y]) continue;
+            flags[(X / rxi) * nty + Y / wi] = 1;
+            const int blk = Y / kZoneBlock;
+            if (!any) b = ZoneTileBox{X, X, blk, blk};
+            any = true;
+            b.row1 = X;  // (X only grows)
+            if (blk < b.blk0) b.blk0 = blk;
+            if (blk > b.blk1) b.blk1 = blk;
+        }
+    return b;
+}
+
+// the tile plane of a sparse-emitter run: a tile stays in the ring and records for the whole run where it holds a registered
+// emitter or -- while the curves are enabled -- a labelled cell.  Either side may be nullptr (none)
+inline void zoneTileUnion(const unsigned char* emitterFlags, const unsigned char* zoneFlags, int ntiles, unsigned char* out) {
+    for (int t = 0; t < ntiles; ++t) out[t] = ((emitterFlags && emitterFlags[t]) || (zoneFlags && zoneFlags[t])) ? 1 : 0;
+}
+
+// the steps of an accumulate pass that one pair of launches takes: whole groups of kZoneCurveSlots whose row sums (a double per
+// step, zone and row of the box) stay within scratchBytes -- one group where even that is more
+inline int streamZoneCurveChunk(int nZones, int rows, size_t scratchBytes) {
+    const size_t perSlot = (size_t)(nZones > 1 ? nZones : 1) * (size_t)(rows > 1 ? rows : 1) * sizeof(double);
+    const size_t fit = scratchBytes / perSlot / kZoneCurveSlots * kZoneCurveSlots;
+    if (fit < (size_t)kZoneCurveSlots) return kZoneCurveSlots;
+    return (int)(fit < (size_t)kZoneCurveMaxChunk ? fit : (size_t)kZoneCurveMaxChunk);
+}
+
 // the refusals of PvAmdHostZoneDecay beyond the labels' (nullptr: fine): every labelled cell with an onset has it inside the run
 inline const char* zoneDecayOnsetsError(const float* delay, const unsigned char* labels, long long cells, int T) {
     for (long long s = 0; s < cells; ++s)

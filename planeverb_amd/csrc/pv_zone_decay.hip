@@ -22,6 +22,12 @@
 // Once per call, before the chunks:
 //   pv_zone_members_rows_kernel, pv_zone_members_merge_kernel: members, smallest and largest onset of every zone (integers:
 //                                     the order does not matter).
+// Sparse-emitter mode keeps a ring of planes instead of the history; there the ABSOLUTE curve is reduced inside the run, per
+// accumulate pass (launchStreamZoneCurves, from launchStreamAccum):
+//   pv_stream_zone_curve_rows_kernel  the ABSOLUTE rows kernel over the ring: plane t % ring, the onsets of the accumulate pass
+//                                     (int, -1 = none yet), loads only where onset <= t < T, and a launch over the rows and
+//                                     64-blocks of the labels' bounding box alone; merged by pv_zone_curve_merge_kernel over the
+//                                     box's rows.
 // A block is reduced while the samples of the next block and the label and onset of the one after are in flight.  edc, the fits and the empty-zone values are
 // the host's (zoneDecayFinish).  Plane offsets are 64-bit throughout.  Only vector stores; nothing is atomic.
 #include <hip/hip_runtime.h>
@@ -30,6 +36,7 @@
 #include <climits>
 
 #include "pv_launch.h"
+#include "pv_prims.h"
 #include "pv_zone_decay.h"
 #include "pv_zones_dev.h"
 
@@ -121,6 +128,97 @@ __global__ __launch_bounds__(64) void pv_zone_curve_merge_kernel(const ZoneCurve
     if (lane == 0) a.etc[(long long)z * a.T + a.slot0 + sl] = total;
 }
 
+// a lane's cell of a block in sparse-emitter mode: the onset is the accumulate pass's (int, -1 = none yet), the plane offset the
+// run's window's (the whole tile grid in this mode; checked all the same)
+__device__ __forceinline__ ZoneCurveCell streamZoneCurveCellAt(const StreamZoneCurveArgs& a, const DynParams& dyn, int X, int Y) {
+    ZoneCurveCell c{0, 0, 0};
+    if (Y >= a.gy) return c;
+    const long long s = (long long)X * a.gy + Y;
+    const int label = (int)a.labels[s];
+    if (label == 0) return c;
+    const int on = a.onset[s];
+    const int hr = X + a.G - dyn.histRow0, hc = Y + a.G - dyn.histCol0;
+    if (on < 0 || on >= a.T || hr < 0 || hc < 0 || hr >= dyn.histTilesX * a.rxi || hc >= dyn.histTilesY * a.wi) return c;
+    const long long g = histOffset(hr, hc, a.rxi, a.wi, dyn.histTilesY);
+    if (g >= a.histPlane) return c;
+    c.label = label;
+    c.t0 = on;
+    c.g = g;
+    return c;
+}
+
+// pv_zone_curve_rows_kernel<false> over the ring of a sparse-emitter run, for the steps of one accumulate pass: a wave owns result
+// row a.row0 + x of the labels' bounding box and a group of sixteen steps, and walks the box's blocks of 64 Y.  Step t lies in
+// plane t % ring; a lane loads only where onset <= t < T with an onset this pass or an earlier one has found -- before a tile's
+// first step the ring holds another step's data, and no member's sample lies there.  Everything else is the kernel above
+__global__ __launch_bounds__(kZoneCurveBlock) void pv_stream_zone_curve_rows_kernel(const StreamZoneCurveArgs a) {
+    constexpr int TC = kZoneCurveSlots;
+    const int lane = threadIdx.x & 63;
+    const int xr = blockIdx.x * (kZoneCurveBlock / 64) + (threadIdx.x >> 6);
+    if (xr >= a.rows) return;  // (wave-uniform)
+    const int X = a.row0 + xr;
+    const int jl0 = blockIdx.y * TC;                           // the group's first step inside the chunk
+    const int j0 = a.slot0 + jl0;                              // ... and in the run
+    const int nj = a.slots - jl0 < TC ? a.slots - jl0 : TC;   // its steps (the chunk's last group may be short)
+    const int r0 = j0 % a.ring;                                // the plane of its first step
+    const DynParams dyn = *a.dyn;
+    double acc[TC];
+#pragma unroll
+    for (int k = 0; k < TC; ++k) acc[k] = 0.0;
+    // a member with a sample in some step of the group
+    const auto liveIn = [&](const ZoneCurveCell& c) { return c.label != 0 && c.t0 <= j0 + nj - 1; };
+    // the group's samples of a block's cell (+0.0f where the cell has none)
+    const auto loadGroup = [&](const ZoneCurveCell& c, bool live, float (&p)[TC]) {
+        const float* __restrict__ h = a.hist + c.g;
+#pragma unroll
+        for (int k = 0; k < TC; ++k) {
+            const int t = j0 + k;
+            const int r = (r0 + k) % a.ring;  // (wave-uniform)
+            const bool has = live && k < nj && t >= c.t0 && t < a.T;
+            p[k] = has ? h[(long long)r * a.histPlane] : 0.0f;
+        }
+    };
+    const int bEnd = a.blk0 + a.blks;
+    ZoneCurveCell c = streamZoneCurveCellAt(a, dyn, X, a.blk0 * kZoneBlock + lane);
+    bool live = liveIn(c);
+    float p[TC];
+    loadGroup(c, live, p);
+    ZoneCurveCell c1 = a.blks > 1 ? streamZoneCurveCellAt(a, dyn, X, (a.blk0 + 1) * kZoneBlock + lane) : ZoneCurveCell{0, 0, 0};
+    for (int b = a.blk0; b < bEnd; ++b) {
+        const bool live1 = liveIn(c1);  // (label 0 past the last block)
+        float p1[TC];
+        loadGroup(c1, live1, p1);
+        const ZoneCurveCell c2 = b + 2 < bEnd ? streamZoneCurveCellAt(a, dyn, X, (b + 2) * kZoneBlock + lane) : ZoneCurveCell{0, 0, 0};
+        unsigned long long left = __ballot(live);
+        while (left) {  // (wave-uniform)
+            const int z = __builtin_amdgcn_readlane(c.label, __ffsll((long long)left) - 1);
+            const bool mine = live && c.label == z;
+            left &= ~__ballot(mine);
+            double v[TC];
+#pragma unroll
+            for (int k = 0; k < TC; ++k) {
+                const double x = mine ? (double)p[k] : 0.0;
+                v[k] = x * x;
+            }
+            const double sums = zoneWaveBlockSums16(v, lane);  // lane k: step k's block value
+#pragma unroll
+            for (int k = 0; k < TC; ++k) {
+                const double bv = zoneReadLane(sums, k);
+                if (lane == z - 1) acc[k] = acc[k] + bv;
+            }
+        }
+        c = c1;
+        live = live1;
+#pragma unroll
+        for (int k = 0; k < TC; ++k) p[k] = p1[k];
+        c1 = c2;
+    }
+    if (lane >= a.nZones) return;
+#pragma unroll
+    for (int k = 0; k < TC; ++k)
+        if (k < nj) a.rowSums[((long long)(jl0 + k) * a.nZones + lane) * a.rows + xr] = acc[k];
+}
+
 // members, smallest and largest onset of every zone in one result row
 __global__ __launch_bounds__(kZoneCurveBlock) void pv_zone_members_rows_kernel(const ZoneCurveArgs a) {
     const int lane = threadIdx.x & 63;
@@ -180,6 +278,27 @@ void launchZoneCurves(const ZoneCurveArgs& a, bool onset, hipStream_t stream) {
     else
         hipLaunchKernelGGL(pv_zone_curve_rows_kernel<false>, rowsGrid, dim3(kZoneCurveBlock), 0, stream, a);
     hipLaunchKernelGGL(pv_zone_curve_merge_kernel, dim3((unsigned)a.nZones, (unsigned)a.slots), dim3(64), 0, stream, a);
+}
+
+// steps [tA, min(tB, T)) of every zone's etc, off the ring: per chunk the rows kernel over the box and the merge kernel above, whose
+// "gx" is the box's rows (the rows outside the box could only add +0.0)
+void launchStreamZoneCurves(const StreamZoneCurveArgs& a, double* etc, int tA, int tB, int chunk, hipStream_t stream) {
+    const int tEnd = tB < a.T ? tB : a.T;
+    StreamZoneCurveArgs s = a;
+    ZoneCurveArgs m{};
+    m.rows = a.rowSums;
+    m.nZones = a.nZones;
+    m.gx = a.rows;
+    m.T = a.T;
+    m.etc = etc;
+    for (int t0 = tA; t0 < tEnd; t0 += chunk) {
+        s.slot0 = m.slot0 = t0;
+        s.slots = m.slots = tEnd - t0 < chunk ? tEnd - t0 : chunk;
+        const dim3 rowsGrid((unsigned)((a.rows + kZoneCurveBlock / 64 - 1) / (kZoneCurveBlock / 64)),
+                            (unsigned)((s.slots + kZoneCurveSlots - 1) / kZoneCurveSlots));
+        hipLaunchKernelGGL(pv_stream_zone_curve_rows_kernel, rowsGrid, dim3(kZoneCurveBlock), 0, stream, s);
+        hipLaunchKernelGGL(pv_zone_curve_merge_kernel, dim3((unsigned)a.nZones, (unsigned)s.slots), dim3(64), 0, stream, m);
+    }
 }
 
 }  // namespace pva
