@@ -713,7 +713,7 @@ __global__ void pv_stream_tilegate_kernel(const uint8_t* marks, const uint8_t* h
 }
 
 void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
-                       hipStream_t stream, const StreamZoneCurveArgs* zc, double* zcEtc, int zcChunk) {
+                       hipStream_t stream, const ZoneRingCurveArgs* zc, int zcChunk) {
     dim3 grid((a.gy + 255) / 256, a.gx);
     if (a.ringList) grid = dim3((unsigned)((a.rxi * a.wi + 255) / 256) * (unsigned)(a.numRing > 0 ? a.numRing : 1), 1);
     hipMemsetAsync(a.tileOpenOut, 0, (size_t)ntiles, stream);
@@ -727,7 +727,7 @@ void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t*
                            dim3(256), 0, stream, a);
     // the zones' curves of this pass's steps: behind the accumulate kernel, whose onsets decide the members, and -- as everything
     // in here -- in front of the event that hands the half ring back to the step kernels
-    if (zc) launchStreamZoneCurves(*zc, zcEtc, a.tA, a.tB, zcChunk, stream);
+    if (zc) launchStreamZoneCurves(*zc, a.tA, a.tB, zcChunk, stream);
 }
 
 void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream) {

@@ -1678,7 +1678,7 @@ int PvAmdZoneDecayChunkSlots(PvAmdSolver* h) try {
     return h->s->zoneDecayChunkSlots();
 } PV_API_CATCH(-1)
 
-// the ABSOLUTE curves inside a sparse-emitter run (pv_zone_decay.hip pv_stream_zone_curve_rows_kernel)
+// the ABSOLUTE curves inside a sparse-emitter run (pv_zone_decay.hip: the rows kernel over the ring source)
 int PvAmdSetZoneCurves(PvAmdSolver* h, int enable) try {
     if (!analysisHandle(h, "zone curves: ")) return -1;
     return ret(h, h->s->setZoneCurves(enable != 0));

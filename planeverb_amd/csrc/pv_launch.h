@@ -119,9 +119,9 @@ void launchAnalysisDirection(const AnalyzeArgs& a, hipStream_t stream);
 void launchFarDirections(float* res, long long n, const FarInfo& far, hipStream_t stream);
 void launchFillDelay(float* delay, long long n, hipStream_t stream);
 // (zc: the zones' curves of the pass's steps behind its onsets -- launchStreamZoneCurves below --, nullptr: none)
-struct StreamZoneCurveArgs;
+struct ZoneRingCurveArgs;
 void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
-                       hipStream_t stream, const StreamZoneCurveArgs* zc = nullptr, double* zcEtc = nullptr, int zcChunk = 0);
+                       hipStream_t stream, const ZoneRingCurveArgs* zc = nullptr, int zcChunk = 0);
 void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream);
 
 // ---- pv_rt60.hip: wet gain and decay time; results carried over from another solver
@@ -156,15 +156,15 @@ struct ZoneArgs;
 void launchZoneStats(const ZoneArgs& a, hipStream_t stream);
 
 // ---- pv_zone_decay.hip: per-zone ensemble decay curves
-// launchZoneMembers: members, smallest and largest onset of every zone into a.members (a.memberRows is scratch; a.slot0 / a.slots /
-// a.rows / a.etc are not used).  launchZoneCurves: etc of the chunk of slots a.slot0 .. a.slot0 + a.slots - 1 of every zone into
-// a.etc (pv_zone_decay.h; a.rows is scratch), slot j = t (onset false) or t - t0 (true)
+// launchZoneMembers: members, smallest and largest onset of every zone into a.members (a.memberRows is scratch; of the window, the
+// onset map and the labels alone).  launchZoneCurves: etc of the chunk of slots a.slot0 .. a.slot0 + a.slots - 1 of every zone into
+// a.etc off the kept history (pv_zone_decay.h; a.rows is scratch), slot j = t (onset false) or t - t0 (true)
 struct ZoneCurveArgs;
 void launchZoneMembers(const ZoneCurveArgs& a, hipStream_t stream);
 void launchZoneCurves(const ZoneCurveArgs& a, bool onset, hipStream_t stream);
-// sparse-emitter mode: steps [tA, min(tB, a.T)) of every zone's ABSOLUTE curve into etc (nZones x T), off the ring, in chunks of
-// `chunk` steps (pv_zone_decay.h streamZoneCurveChunk; a.slot0 / a.slots are the launcher's; a.rowSums is scratch)
-void launchStreamZoneCurves(const StreamZoneCurveArgs& a, double* etc, int tA, int tB, int chunk, hipStream_t stream);
+// sparse-emitter mode: steps [tA, min(tB, T)) of every zone's ABSOLUTE curve into a.c.etc (nZones x T), off the ring, in chunks of
+// `chunk` steps (pv_zone_decay.h streamZoneCurveChunk; a.c.slot0 / a.c.slots are the launcher's; a.c.rows is scratch)
+void launchStreamZoneCurves(const ZoneRingCurveArgs& a, int tA, int tB, int chunk, hipStream_t stream);
 
 // ---- pv_zone_band_decay.hip: per-zone ensemble decay curves per band
 // etc of one chunk of (zone, band) pairs -- zones a.zone0 + 1 .. a.zone0 + a.zones, bands a.band0 .. a.band0 + a.bands - 1 -- into

@@ -2258,26 +2258,19 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
     AnalyzeArgs aa = analyzeArgs(lx, lz);
     // the zones' curves (setZoneCurves): every accumulate pass reduces its own steps.  A box without a labelled cell is launched
     // as one row and one block, which find no member and leave +0.0 in every slot
-    StreamZoneCurveArgs zc{};
+    ZoneRingCurveArgs zc{};
     if (zoneCurvesOn_) {
-        zc.hist = aa.hist;
-        zc.histPlane = aa.histPlane;
-        zc.ring = aa.ring;
+        zc.c = zoneCurveArgs();  // (of its window only rxi and wi are read: the ring's source builds its own from them and *dyn)
+        zc.c.rows = zoneCurveRows_;
+        zc.c.etc = zoneCurveEtc_;
         zc.onset = sOnset_;
-        zc.labels = zoneLabels_;
         zc.dyn = aa.dyn;
-        zc.gx = g_.gx;
-        zc.gy = g_.gy;
-        zc.nZones = zoneCount_;
-        zc.T = T_;
+        zc.ring = aa.ring;
         zc.G = geo_.G;
-        zc.rxi = rxi_;
-        zc.wi = wi_;
         zc.row0 = zoneBox_[0];
-        zc.rows = std::max(zoneBox_[1] - zoneBox_[0] + 1, 1);
+        zc.nRows = std::max(zoneBox_[1] - zoneBox_[0] + 1, 1);
         zc.blk0 = zoneBox_[2];
-        zc.blks = std::max(zoneBox_[3] - zoneBox_[2] + 1, 1);
-        zc.rowSums = zoneCurveRows_;
+        zc.nBlks = std::max(zoneBox_[3] - zoneBox_[2] + 1, 1);
     }
     zoneCurveRun_ = zoneCurvesOn_ ? zoneCurveSetting_ : 0;
     if (streamEv_[0] == nullptr)
@@ -2306,7 +2299,7 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
         hipStreamWaitEvent(stream2_, streamEv_[h], 0);
         aa.tA = tA;
         aa.tB = tA + n;
-        launchStreamAccum(aa, tileEmit_, tileOpen_, ntiles, stream2_, zoneCurvesOn_ ? &zc : nullptr, zoneCurveEtc_, zoneCurveChunk_);
+        launchStreamAccum(aa, tileEmit_, tileOpen_, ntiles, stream2_, zoneCurvesOn_ ? &zc : nullptr, zoneCurveChunk_);
         if (streamFuse_ && !fuseIdle_) launchStreamIdle(classifyArgs(baseStepArgs(true, true), 0, true), idleHost_ + h, stream2_);
         hipEventRecord(streamEv_[2 + h], stream2_);
     }

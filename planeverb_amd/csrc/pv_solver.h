@@ -17,6 +17,7 @@
 #include "pv_core.h"
 #include "pv_device.h"
 #include "pv_query_spectral.h"
+#include "pv_zone_decay.h"
 
 namespace pva {
 
@@ -357,6 +358,7 @@ public:
     int spectrumBins(float* hz, int cap) const;
     bool spectrumSource(float* out3n);
     bool computeSpectrum(float* ms);
+    // The reductions over zones: pv_solver_zones.cpp.
     // Zone statistics (pv_zones.hip; include/planeverb_amd.h PvAmdZoneStat): a label per result cell, 0 = no zone, 1 .. nZones;
     // computeZoneStats reduces the valid map of one kind to nZones x planes records on the device -- no host copy of the map,
     // nothing cached, no kind touched.  setZones: the caller has validated the labels (pv_zones.h zoneLabelsError); nullptr / 0
@@ -373,7 +375,7 @@ public:
     bool computeZoneDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count);
     int zoneDecayChunkSlots() const;
     // Sparse-emitter solvers keep a ring, not the history: there the ABSOLUTE curves are accumulated INSIDE every run enqueued
-    // while setZoneCurves(true) holds (pv_zone_decay.hip pv_stream_zone_curve_rows_kernel, per accumulate pass), and
+    // while setZoneCurves(true) holds (pv_zone_decay.hip, the rows kernel over the ring source, per accumulate pass), and
     // computeZoneDecay(ABSOLUTE) reads them -- members pass, one copy, the host finish.  Needs zones; waits for a run in flight;
     // allocates on enable (nZones x T doubles and the row sums of one chunk of steps), frees on disable; while enabled the tiles
     // that hold a labelled cell stay in the ring and record for the whole run, as the emitters' tiles do, and the zones cannot be
@@ -673,6 +675,29 @@ private:
     // flight and result row T doubles, the pairs dealt in chunks within the same bound (one pair's where that is more), then nZones x
     // nBands x T doubles of curves and the member rows and records
     bool growZoneScratch(size_t need);
+    // A zone pass (pv_solver_zones.cpp), after the pattern of AnalysisPass.  beginZonePass = the refusals every call makes ahead of
+    // the lock (a slab; by flag: a sparse-emitter solver, a solver without onset map), the lock, the run in flight waited for.  The
+    // call then lists its remaining refusals in its own order (zoneRefuse; zoneRunRefusal: the two about the last run).  A curve pass
+    // goes on with beginZoneCurves = the scratch carved, the arguments (zoneCurveArgs: window and common fields from the last run),
+    // the first event, the members pass; the caller enqueues its launches with p.c; endZoneCurves = the second event, the error
+    // check, curves and members copied, the wait, *ms.  Zone statistics keep their own scratch and tail
+    enum : unsigned { kZoneNeedsHistory = 1, kZoneNeedsOnsets = 2 };
+    struct ZonePass {
+        const char* name;  // the prefix of the refusals, the label of a failed HIP call
+        std::unique_lock<std::recursive_mutex> inUse;
+        ZoneCurveArgs c;
+        std::vector<double> etcHost;  // the curves where the caller takes none
+        std::vector<ZoneMembers> members;
+    };
+    bool beginZonePass(ZonePass* p, const char* name, unsigned flags);
+    bool zoneRefuse(const ZonePass& p, const std::string& what);
+    const char* zoneRunRefusal() const;
+    bool beginZoneCurves(ZonePass* p, size_t rowsBytes, size_t etcBytes, double* runCurves = nullptr);
+    bool endZoneCurves(ZonePass& p, size_t curves, double** etc, float* ms);
+    bool startZoneTimer();
+    bool zoneHipOk(const ZonePass& p, hipError_t e, const char* step);
+    ZoneWindow zoneWindow(const DynParams& dyn, int tilesX, int tilesY) const;
+    ZoneCurveArgs zoneCurveArgs() const;
     static constexpr size_t kZoneScratchBytes = 32u << 20;
     unsigned char* zoneLabels_ = nullptr;
     std::vector<unsigned char> zoneHost_;
@@ -685,7 +710,6 @@ private:
     // labels or switch, zoneCurveRun_ is its value when the last run was enqueued (0: that run accumulated no curves)
     bool deriveZoneCurves();  // (everything below from zoneHost_ / zoneCount_; uploads the tile plane)
     bool disableZoneCurves();
-    bool streamZoneDecay(void* out, double* etc, double* edc, float* ms, int* count);
     void freeZoneCurves();
     bool uploadTileEmit();    // tileEmit_ = the emitters' tiles, united with the zones' while the curves are enabled
     bool zoneCurvesOn_ = false;
@@ -830,7 +854,7 @@ private:
 };
 
 template <typename Tp>
-bool Solver::dalloc(Tp** p, size_t count, bool zero) {  // (here: pv_solver.cpp and pv_solver_maps.cpp both allocate)
+bool Solver::dalloc(Tp** p, size_t count, bool zero) {  // (here: pv_solver.cpp, pv_solver_maps.cpp and pv_solver_zones.cpp all allocate)
     const size_t bytes = count * sizeof(Tp);
     if (!hipOk(hipMalloc((void**)p, bytes), "hipMalloc")) return false;
     deviceBytes_ += (long long)bytes;

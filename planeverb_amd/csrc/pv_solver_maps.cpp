@@ -19,9 +19,6 @@
 #include "pv_lobes.h"
 #include "pv_metrics.h"
 #include "pv_spectrum.h"
-#include "pv_zone_band_decay.h"
-#include "pv_zone_decay.h"
-#include "pv_zones.h"
 
 namespace pva {
 
@@ -97,6 +94,23 @@ bool Solver::analysisSettingPresent(AnalysisKind k) const {
         case kMapModulation: return !bandHz_.empty();
         case kMapSpectrum: return !specHz_.empty();
         default: return true;  // (no setting, or one that is never unset: the lobes' windows)
+    }
+}
+
+// the planes of a kind under the current settings, -1 where a setting is missing (the zone statistics' width: pv_solver_zones.cpp)
+int Solver::zoneStatPlanes(AnalysisKind k) const {
+    if (!analysisSettingPresent(k)) return -1;
+    switch (k) {
+        case kMapRoomMetrics: return kRoomMetricFloats;
+        case kMapDecayTimes: return kDecayFloats;
+        case kMapLateralFraction: return kLateralFloats;
+        case kMapEchoCriterion: return kEchoFloats;
+        case kMapEchogram: return echogramFloats(echoSlots_);
+        case kMapLobes: return lobesFloats(lobeEdgeCount_ + 1);
+        case kMapBandMetrics: return kBandFloats * (int)bandHz_.size();
+        case kMapModulation: return kModFloats * (int)bandHz_.size();
+        case kMapSpectrum: return kSpectrumFloats * (int)specHz_.size();
+        default: return -1;
     }
 }
 
@@ -209,432 +223,6 @@ bool Solver::analysisAt(AnalysisKind k, float ex, float ez, float* out) {
         return true;
     }
     return copyAnalysisBlock(k, cx, cy, 1, 1, out);
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// zone statistics (pv_zones.hip): one reduction for every kind, straight off the kind's device planes
-// ----------------------------------------------------------------------------------------------------------------
-
-bool Solver::setZones(const unsigned char* labels, int nZones) {
-    if (isSlab()) return fail("zone statistics: not available on a slab");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight)
-    if (nZones == 0) {
-        if (zoneCurvesOn_) return fail("zone statistics: the zones cannot be cleared while the zone curves are enabled (PvAmdSetZoneCurves)");
-        zoneCount_ = 0;
-        zoneHost_.clear();
-        return true;
-    }
-    const size_t cells = (size_t)g_.gx * (size_t)g_.gy;
-    if (!zoneLabels_ && !dalloc(&zoneLabels_, cells, false)) return false;
-    if (!hipOk(hipMemcpyAsync(zoneLabels_, labels, cells, hipMemcpyHostToDevice, stream_), "zone labels upload") ||
-        !hipOk(hipStreamSynchronize(stream_), "zone labels sync")) {
-        zoneCount_ = 0;  // (the device labels are neither the old nor the new ones)
-        zoneHost_.clear();
-        if (zoneCurvesOn_) disableZoneCurves();
-        return false;
-    }
-    zoneHost_.assign(labels, labels + cells);
-    zoneCount_ = nZones;
-    // (sparse-emitter mode with the curves enabled: the tiles, the box and the buffers follow the labels; the curves of the last run
-    // are the old labels' and are refused until the next one)
-    if (zoneCurvesOn_ && !deriveZoneCurves()) {
-        const std::string why = err_;
-        disableZoneCurves();
-        return fail(why);
-    }
-    return true;
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// zone curves inside a sparse-emitter run (pv_zone_decay.hip pv_stream_zone_curve_rows_kernel)
-// ----------------------------------------------------------------------------------------------------------------
-
-void Solver::freeZoneCurves() {
-    if (zoneCurveEtc_) hipFree(zoneCurveEtc_), deviceBytes_ -= (long long)zoneCurveEtcBytes_;
-    if (zoneCurveRows_) hipFree(zoneCurveRows_), deviceBytes_ -= (long long)zoneCurveRowsBytes_;
-    zoneCurveEtc_ = zoneCurveRows_ = nullptr;
-    zoneCurveEtcBytes_ = zoneCurveRowsBytes_ = 0;
-}
-
-// (no run in flight) back to the emitters' tile plane; the buffers go
-bool Solver::disableZoneCurves() {
-    zoneCurvesOn_ = false;
-    ++zoneCurveSetting_;
-    zoneTilesHost_.clear();
-    freeZoneCurves();
-    return uploadTileEmit() && hipOk(hipStreamSynchronize(stream_), "tile plane upload");
-}
-
-bool Solver::deriveZoneCurves() {
-    ++zoneCurveSetting_;
-    const int ntx = (g_.gx + rxi_ - 1) / rxi_, nty = (g_.gy + wi_ - 1) / wi_;
-    if (ntx > geo_.ntx || nty > geo_.nty) return fail("the result map reaches past the tile grid");
-    std::vector<unsigned char> flags((size_t)ntx * nty);
-    const ZoneTileBox b = zoneTileFlags(zoneHost_.data(), g_.gx, g_.gy, rxi_, wi_, flags.data());
-    zoneTilesHost_.assign((size_t)geo_.ntx * geo_.nty, 0);
-    for (int ti = 0; ti < ntx; ++ti)
-        for (int tj = 0; tj < nty; ++tj) zoneTilesHost_[(size_t)ti * geo_.nty + tj] = flags[(size_t)ti * nty + tj];
-    zoneBox_[0] = b.row0, zoneBox_[1] = b.row1, zoneBox_[2] = b.blk0, zoneBox_[3] = b.blk1;
-    const int rows = std::max(b.row1 - b.row0 + 1, 1);
-    // the steps of a pass per pair of launches; a pass has halfRing_ of them at the most
-    zoneCurveChunk_ = std::min(streamZoneCurveChunk(zoneCount_, rows, kZoneScratchBytes),
-                               (halfRing_ + kZoneCurveSlots - 1) / kZoneCurveSlots * kZoneCurveSlots);
-    const size_t etcBytes = (size_t)zoneCount_ * (size_t)T_ * sizeof(double);
-    const size_t rowsBytes = (size_t)zoneCurveChunk_ * (size_t)zoneCount_ * (size_t)rows * sizeof(double);
-    if (etcBytes != zoneCurveEtcBytes_ || rowsBytes > zoneCurveRowsBytes_) {
-        freeZoneCurves();
-        if (!dalloc(&zoneCurveEtc_, etcBytes / sizeof(double), false)) return false;
-        zoneCurveEtcBytes_ = etcBytes;
-        if (!dalloc(&zoneCurveRows_, rowsBytes / sizeof(double), false)) return false;
-        zoneCurveRowsBytes_ = rowsBytes;
-    }
-    return uploadTileEmit() && hipOk(hipStreamSynchronize(stream_), "tile plane upload");
-}
-
-bool Solver::setZoneCurves(bool on) {
-    if (isSlab()) return fail("zone curves: not available on a slab");
-    if (!opt_.streaming) return fail("zone curves: sparse-emitter solvers only (PVA_OPT_STREAMING_ANALYSIS): a solver that keeps its history computes the curves after the run");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight reads the tile plane and writes the curves)
-    if (!on) return zoneCurvesOn_ ? disableZoneCurves() : true;
-    if (!zoneCount_) return fail("zone curves: no zones set (PvAmdSetZones)");
-    if (zoneCurvesOn_) return true;
-    zoneCurvesOn_ = true;
-    if (!deriveZoneCurves()) {
-        const std::string why = err_;
-        disableZoneCurves();
-        return fail("zone curves: " + why);
-    }
-    return true;
-}
-
-bool Solver::zoneCurves() const {
-    const auto inUse = queue_.lockUse();
-    return zoneCurvesOn_;
-}
-
-int Solver::zones(unsigned char* labels) const {
-    const auto inUse = queue_.lockUse();  // (setZones changes both under it)
-    if (labels && zoneCount_) std::memcpy(labels, zoneHost_.data(), zoneHost_.size());
-    return zoneCount_;
-}
-
-int Solver::zoneStatPlanes(AnalysisKind k) const {
-    if (!analysisSettingPresent(k)) return -1;
-    switch (k) {
-        case kMapRoomMetrics: return kRoomMetricFloats;
-        case kMapDecayTimes: return kDecayFloats;
-        case kMapLateralFraction: return kLateralFloats;
-        case kMapEchoCriterion: return kEchoFloats;
-        case kMapEchogram: return echogramFloats(echoSlots_);
-        case kMapLobes: return lobesFloats(lobeEdgeCount_ + 1);
-        case kMapBandMetrics: return kBandFloats * (int)bandHz_.size();
-        case kMapModulation: return kModFloats * (int)bandHz_.size();
-        case kMapSpectrum: return kSpectrumFloats * (int)specHz_.size();
-        default: return -1;
-    }
-}
-
-bool Solver::growZoneScratch(size_t need) {
-    if (zoneScratchBytes_ >= need) return true;
-    if (zoneScratch_) {
-        hipFree(zoneScratch_);
-        deviceBytes_ -= (long long)zoneScratchBytes_;
-        zoneScratch_ = nullptr;
-        zoneScratchBytes_ = 0;
-    }
-    if (!dalloc(&zoneScratch_, need, false)) return false;
-    zoneScratchBytes_ = need;
-    return true;
-}
-
-bool Solver::computeZoneStats(AnalysisKind k, void* out, int cap, float* ms, int* count) {
-    if (isSlab()) return fail("zone statistics: not available on a slab");
-    if (opt_.streaming) return fail("zone statistics: the full pressure history is not kept in streaming-analysis mode");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight: it leaves no kind valid)
-    if (!zoneCount_) return fail("zone statistics: no zones set (PvAmdSetZones)");
-    if (!analysisReadable(k)) return fail("zone statistics: " + err_);
-    const AnalysisMap& m = maps_[k];
-    const int records = zoneCount_ * m.planes;
-    if (cap < records) return fail("zone statistics: PvAmdComputeZoneStats: the output holds fewer than nZones x planes records");
-    // scratch: the rows' records and m2 sums of one chunk of planes, then the zones' records
-    const size_t perPlane = (size_t)zoneCount_ * (size_t)g_.gx * (sizeof(ZoneRow) + sizeof(double));
-    const int chunk = (int)std::min<size_t>((size_t)m.planes, std::max<size_t>(1, kZoneScratchBytes / perPlane));
-    const size_t rowsBytes = (size_t)chunk * (size_t)zoneCount_ * (size_t)g_.gx * sizeof(ZoneRow), m2Bytes = perPlane * chunk - rowsBytes;
-    const size_t need = rowsBytes + m2Bytes + (size_t)records * sizeof(ZoneStat);
-    if (!growZoneScratch(need)) return false;
-    for (auto& e : mapEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    ZoneArgs a{};
-    a.histPlane = histPlane_;
-    a.labels = zoneLabels_;
-    a.gx = g_.gx;
-    a.gy = g_.gy;
-    a.nZones = zoneCount_;
-    a.wr0 = m.dyn.histRow0 - geo_.G;  // (the window as copyAnalysisBlock reads it)
-    a.wc0 = m.dyn.histCol0 - geo_.G;
-    a.wnr = histTilesX_ * rxi_;
-    a.wnc = histTilesY_ * wi_;
-    a.rxi = rxi_;
-    a.wi = wi_;
-    a.tilesY = m.dyn.histTilesY;
-    a.totalPlanes = m.planes;
-    a.rows = reinterpret_cast<ZoneRow*>(zoneScratch_);
-    a.rowM2 = reinterpret_cast<double*>(zoneScratch_ + rowsBytes);
-    a.out = reinterpret_cast<ZoneStat*>(zoneScratch_ + rowsBytes + m2Bytes);
-    hipEventRecord(mapEv_[0], stream_);
-    for (int p0 = 0; p0 < m.planes; p0 += chunk) {
-        a.map = m.dev + (size_t)p0 * (size_t)histPlane_;
-        a.plane0 = p0;
-        a.planes = std::min(chunk, m.planes - p0);
-        launchZoneStats(a, stream_);
-    }
-    hipEventRecord(mapEv_[1], stream_);
-    ZoneStat* recs = static_cast<ZoneStat*>(out);
-    if (!hipOk(hipGetLastError(), "zone statistics launch") ||
-        !hipOk(hipMemcpyAsync(recs, a.out, (size_t)records * sizeof(ZoneStat), hipMemcpyDeviceToHost, stream_), "zone statistics copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "zone statistics sync"))
-        return false;
-    if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
-    for (int i = 0; i < records; ++i) zoneStatFinish(&recs[i]);
-    *count = records;
-    return true;
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// zone decay (pv_zone_decay.hip): the ensemble decay curve of every zone, straight off the history planes and the onset map
-// ----------------------------------------------------------------------------------------------------------------
-
-int Solver::zoneDecayChunkSlots() const {
-    const size_t perSlot = (size_t)std::max(zoneCount_, 1) * (size_t)g_.gx * sizeof(double);
-    const size_t fit = kZoneScratchBytes / perSlot / kZoneCurveSlots * kZoneCurveSlots;
-    return (int)std::min<size_t>(std::max<size_t>(fit, kZoneCurveSlots), kZoneCurveMaxChunk);
-}
-
-bool Solver::computeZoneDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count) {
-    if (isSlab()) return fail("zone decay: not available on a slab");
-    if (opt_.skipAnalysis) return fail("zone decay: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (opt_.streaming) {
-        if (!zoneCurvesOn_)
-            return fail("zone decay: the full pressure history is not kept in streaming-analysis mode: the ABSOLUTE curves are accumulated "
-                        "inside the runs that follow PvAmdSetZoneCurves");
-        if (align != kZoneDecayAbsolute)
-            return fail("zone decay: onset-synchronised curves need the full pressure history, which streaming-analysis mode does not keep "
-                        "(PVA_ZONE_DECAY_ABSOLUTE only)");
-    }
-    if (!zoneCount_) return fail("zone decay: no zones set (PvAmdSetZones)");
-    if (cap < zoneCount_) return fail("zone decay: PvAmdComputeZoneDecay: the output holds fewer than nZones records");
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("zone decay: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("zone decay: the last run ended in error");
-    if (opt_.streaming) return streamZoneDecay(out, etc, edc, ms, count);
-    const int T = T_, nz = zoneCount_;
-    // scratch: the row sums of one chunk of slots, the curves, the zones' member rows and records
-    const int chunk = std::min(zoneDecayChunkSlots(), T);
-    const size_t rowsBytes = (size_t)chunk * (size_t)nz * (size_t)g_.gx * sizeof(double), etcBytes = (size_t)nz * (size_t)T * sizeof(double);
-    const size_t memberRowsBytes = ((size_t)nz * (size_t)g_.gx * sizeof(ZoneMembers) + 7) / 8 * 8;
-    if (!growZoneScratch(rowsBytes + etcBytes + memberRowsBytes + (size_t)nz * sizeof(ZoneMembers))) return false;
-    for (auto& e : mapEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    ZoneCurveArgs a{};
-    a.hist = hist_;
-    a.histPlane = histPlane_;
-    a.delay = delay_;
-    a.labels = zoneLabels_;
-    a.gx = g_.gx;
-    a.gy = g_.gy;
-    a.nZones = nz;
-    a.T = T;
-    a.wr0 = dynCur_.histRow0 - geo_.G;  // (the window as the last run recorded it)
-    a.wc0 = dynCur_.histCol0 - geo_.G;
-    a.wnr = std::min(dynCur_.histTilesX, histTilesX_) * rxi_;
-    a.wnc = std::min(dynCur_.histTilesY, histTilesY_) * wi_;
-    a.rxi = rxi_;
-    a.wi = wi_;
-    a.tilesY = dynCur_.histTilesY;
-    a.rows = reinterpret_cast<double*>(zoneScratch_);
-    a.etc = reinterpret_cast<double*>(zoneScratch_ + rowsBytes);
-    a.memberRows = reinterpret_cast<ZoneMembers*>(zoneScratch_ + rowsBytes + etcBytes);
-    a.members = reinterpret_cast<ZoneMembers*>(zoneScratch_ + rowsBytes + etcBytes + memberRowsBytes);
-    hipEventRecord(mapEv_[0], stream_);
-    launchZoneMembers(a, stream_);
-    for (int j0 = 0; j0 < T; j0 += chunk) {
-        a.slot0 = j0;
-        a.slots = std::min(chunk, T - j0);
-        launchZoneCurves(a, align == kZoneDecayOnset, stream_);
-    }
-    hipEventRecord(mapEv_[1], stream_);
-    std::vector<double> etcHost, edcHost;
-    if (!etc) etcHost.resize((size_t)nz * T), etc = etcHost.data();
-    std::vector<ZoneMembers> members((size_t)nz);
-    if (!hipOk(hipGetLastError(), "zone decay launch") ||
-        !hipOk(hipMemcpyAsync(etc, a.etc, etcBytes, hipMemcpyDeviceToHost, stream_), "zone decay copy") ||
-        !hipOk(hipMemcpyAsync(members.data(), a.members, (size_t)nz * sizeof(ZoneMembers), hipMemcpyDeviceToHost, stream_), "zone decay copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "zone decay sync"))
-        return false;
-    if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
-    if (!edc) edcHost.resize((size_t)T);
-    ZoneDecay* recs = static_cast<ZoneDecay*>(out);
-    for (int z = 0; z < nz; ++z) {
-        recs[z].n_cells = members[(size_t)z].n_cells;
-        recs[z].t_first = members[(size_t)z].t_first;
-        recs[z].t_last = members[(size_t)z].t_last;
-        zoneDecayFinish(etc + (size_t)z * T, edc ? edc + (size_t)z * T : edcHost.data(), T, (int)g_.fs, align, &recs[z]);
-    }
-    *count = nz;
-    return true;
-}
-
-// computeZoneDecay(ABSOLUTE) of a sparse-emitter solver (the caller holds the lock and has checked zones, output and run): the
-// curves are the last run's own (enqueueStreamingRun), so what is left is the members pass over the finalize pass's delay map,
-// one copy and the host finish.  No curve kernel is launched here: *ms is the members pass
-bool Solver::streamZoneDecay(void* out, double* etc, double* edc, float* ms, int* count) {
-    if (zoneCurveRun_ != zoneCurveSetting_)
-        return fail("zone decay: the last run was enqueued before the zone curves were enabled or before the current zones were set");
-    const int T = T_, nz = zoneCount_;
-    const size_t etcBytes = (size_t)nz * (size_t)T * sizeof(double);
-    const size_t memberRowsBytes = ((size_t)nz * (size_t)g_.gx * sizeof(ZoneMembers) + 7) / 8 * 8;
-    if (!growZoneScratch(memberRowsBytes + (size_t)nz * sizeof(ZoneMembers))) return false;
-    for (auto& e : mapEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    ZoneCurveArgs a{};
-    a.histPlane = histPlane_;
-    a.delay = delay_;
-    a.labels = zoneLabels_;
-    a.gx = g_.gx;
-    a.gy = g_.gy;
-    a.nZones = nz;
-    a.T = T;
-    a.wr0 = dynCur_.histRow0 - geo_.G;  // (the window as the last run recorded it: the whole tile grid in this mode)
-    a.wc0 = dynCur_.histCol0 - geo_.G;
-    a.wnr = std::min(dynCur_.histTilesX, histTilesX_) * rxi_;
-    a.wnc = std::min(dynCur_.histTilesY, histTilesY_) * wi_;
-    a.rxi = rxi_;
-    a.wi = wi_;
-    a.tilesY = dynCur_.histTilesY;
-    a.memberRows = reinterpret_cast<ZoneMembers*>(zoneScratch_);
-    a.members = reinterpret_cast<ZoneMembers*>(zoneScratch_ + memberRowsBytes);
-    hipEventRecord(mapEv_[0], stream_);
-    launchZoneMembers(a, stream_);
-    hipEventRecord(mapEv_[1], stream_);
-    std::vector<double> etcHost, edcHost;
-    if (!etc) etcHost.resize((size_t)nz * T), etc = etcHost.data();
-    std::vector<ZoneMembers> members((size_t)nz);
-    if (!hipOk(hipGetLastError(), "zone decay launch") ||
-        !hipOk(hipMemcpyAsync(etc, zoneCurveEtc_, etcBytes, hipMemcpyDeviceToHost, stream_), "zone decay copy") ||
-        !hipOk(hipMemcpyAsync(members.data(), a.members, (size_t)nz * sizeof(ZoneMembers), hipMemcpyDeviceToHost, stream_), "zone decay copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "zone decay sync"))
-        return false;
-    if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
-    if (!edc) edcHost.resize((size_t)T);
-    ZoneDecay* recs = static_cast<ZoneDecay*>(out);
-    for (int z = 0; z < nz; ++z) {
-        recs[z].n_cells = members[(size_t)z].n_cells;
-        recs[z].t_first = members[(size_t)z].t_first;
-        recs[z].t_last = members[(size_t)z].t_last;
-        zoneDecayFinish(etc + (size_t)z * T, edc ? edc + (size_t)z * T : edcHost.data(), T, (int)g_.fs, kZoneDecayAbsolute, &recs[z]);
-    }
-    *count = nz;
-    return true;
-}
-
-// ----------------------------------------------------------------------------------------------------------------
-// zone band decay (pv_zone_band_decay.hip): the same curve per band of setBands, off the band-filtered history
-// ----------------------------------------------------------------------------------------------------------------
-
-int Solver::zoneBandDecayChunks(int* slots, int* bands) const {
-    const auto inUse = queue_.lockUse();  // (setZones and setBands change what is read here under it)
-    const int nb = (int)bandHz_.size();
-    if (slots) *slots = T_;
-    if (bands) *bands = 0;
-    if (!zoneCount_ || !nb) return 0;
-    return pva::zoneBandDecayChunks(g_.gx, T_, zoneCount_, nb, kZoneScratchBytes, nullptr, bands);
-}
-
-bool Solver::computeZoneBandDecay(int align, void* out, int cap, double* etc, double* edc, float* ms, int* count) {
-    if (isSlab()) return fail("zone band decay: not available on a slab");
-    if (opt_.streaming) return fail("zone band decay: the full pressure history is not kept in streaming-analysis mode");
-    if (opt_.skipAnalysis) return fail("zone band decay: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
-    const auto inUse = queue_.lockUse();
-    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
-    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
-    if (!zoneCount_) return fail("zone band decay: no zones set (PvAmdSetZones)");
-    const int T = T_, nz = zoneCount_, nBands = (int)bandHz_.size();
-    if (!nBands) return fail("zone band decay: no bands set (PvAmdSetBands)");
-    const int records = nz * nBands;
-    if (cap < records) return fail("zone band decay: PvAmdComputeZoneBandDecay: the output holds fewer than nZones x nBands records");
-    if (lastRun_ == LastRun::None || !dynValid_) return fail("zone band decay: no completed run");
-    if (lastRun_ != LastRun::Ok) return fail("zone band decay: the last run ended in error");
-    // scratch: the rows of one chunk of pairs, the curves, the zones' member rows and records
-    int zonesPer = 0, bandsPer = 0;
-    pva::zoneBandDecayChunks(g_.gx, T, nz, nBands, kZoneScratchBytes, &zonesPer, &bandsPer);
-    const size_t pairBytes = (size_t)g_.gx * (size_t)T * sizeof(double);
-    const size_t rowsBytes = (size_t)zonesPer * (size_t)bandsPer * pairBytes, etcBytes = (size_t)records * (size_t)T * sizeof(double);
-    const size_t memberRowsBytes = ((size_t)nz * (size_t)g_.gx * sizeof(ZoneMembers) + 7) / 8 * 8;
-    if (!growZoneScratch(rowsBytes + etcBytes + memberRowsBytes + (size_t)nz * sizeof(ZoneMembers))) return false;
-    for (auto& e : mapEv_)
-        if (!e && !hipOk(hipEventCreate(&e), "hipEventCreate")) return false;
-    ZoneBandCurveArgs a{};
-    ZoneCurveArgs& c = a.c;
-    c.hist = hist_;
-    c.histPlane = histPlane_;
-    c.delay = delay_;
-    c.labels = zoneLabels_;
-    c.gx = g_.gx;
-    c.gy = g_.gy;
-    c.nZones = nz;
-    c.T = T;
-    c.wr0 = dynCur_.histRow0 - geo_.G;  // (the window as the last run recorded it)
-    c.wc0 = dynCur_.histCol0 - geo_.G;
-    c.wnr = std::min(dynCur_.histTilesX, histTilesX_) * rxi_;
-    c.wnc = std::min(dynCur_.histTilesY, histTilesY_) * wi_;
-    c.rxi = rxi_;
-    c.wi = wi_;
-    c.tilesY = dynCur_.histTilesY;
-    c.rows = reinterpret_cast<double*>(zoneScratch_);
-    c.etc = reinterpret_cast<double*>(zoneScratch_ + rowsBytes);
-    c.memberRows = reinterpret_cast<ZoneMembers*>(zoneScratch_ + rowsBytes + etcBytes);
-    c.members = reinterpret_cast<ZoneMembers*>(zoneScratch_ + rowsBytes + etcBytes + memberRowsBytes);
-    a.nBands = nBands;
-    std::copy(bandCoefs_.begin(), bandCoefs_.begin() + (size_t)nBands * kBandCoefs, a.coefs);
-    hipEventRecord(mapEv_[0], stream_);
-    launchZoneMembers(c, stream_);
-    for (int z0 = 0; z0 < nz; z0 += zonesPer)
-        for (int b0 = 0; b0 < nBands; b0 += bandsPer) {
-            a.zone0 = z0;
-            a.zones = std::min(zonesPer, nz - z0);
-            a.band0 = b0;
-            a.bands = std::min(bandsPer, nBands - b0);
-            if (!hipOk(hipMemsetAsync(c.rows, 0, (size_t)a.zones * (size_t)a.bands * pairBytes, stream_), "zone band decay clear")) return false;
-            launchZoneBandCurves(a, align == kZoneDecayOnset, stream_);
-        }
-    hipEventRecord(mapEv_[1], stream_);
-    std::vector<double> etcHost, edcHost;
-    if (!etc) etcHost.resize((size_t)records * T), etc = etcHost.data();
-    std::vector<ZoneMembers> members((size_t)nz);
-    if (!hipOk(hipGetLastError(), "zone band decay launch") ||
-        !hipOk(hipMemcpyAsync(etc, c.etc, etcBytes, hipMemcpyDeviceToHost, stream_), "zone band decay copy") ||
-        !hipOk(hipMemcpyAsync(members.data(), c.members, (size_t)nz * sizeof(ZoneMembers), hipMemcpyDeviceToHost, stream_), "zone band decay copy") ||
-        !hipOk(hipStreamSynchronize(stream_), "zone band decay sync"))
-        return false;
-    if (ms) hipEventElapsedTime(ms, mapEv_[0], mapEv_[1]);
-    if (!edc) edcHost.resize((size_t)T);
-    ZoneBandDecay* recs = static_cast<ZoneBandDecay*>(out);
-    for (int z = 0; z < nz; ++z)
-        for (int b = 0; b < nBands; ++b) {
-            const size_t r = (size_t)z * nBands + b;
-            const ZoneMembers& m = members[(size_t)z];
-            zoneBandDecayFinish(etc + r * T, edc ? edc + r * T : edcHost.data(), T, (int)g_.fs, align, m.n_cells, m.t_first, m.t_last, &recs[r]);
-        }
-    *count = records;
-    return true;
 }
 
 // ----------------------------------------------------------------------------------------------------------------

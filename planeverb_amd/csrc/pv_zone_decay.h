@@ -38,42 +38,53 @@ struct ZoneMembers {
 };
 static_assert(sizeof(ZoneMembers) == 12, "the scratch bound counts on it");
 
-// One chunk of time slots for launchZoneCurves (pv_launch.h).  The history window in RESULT coordinates is rows [wr0, wr0 + wnr) x
-// columns [wc0, wc0 + wnc); a cell outside it has no sample recorded and is no member
+// One chunk of time slots for launchZoneCurves and what launchZoneMembers reads (pv_launch.h): the kept history of a run, step t
+// in plane t, the run's onset map, the window as the run recorded it.  A cell outside the window has no sample recorded and is no
+// member.  The band pass embeds this struct (pv_zone_band_decay.h), and so does the ring's below
 struct ZoneCurveArgs {
-    const float* hist;            // plane 0 of the history: T planes of histPlane floats
+    const float* hist;            // plane 0: planes of histPlane floats
     long long histPlane;
     const float* delay;           // gx * gy: the onset map, FLT_MAX = none
     const unsigned char* labels;  // gx * gy
     int gx, gy, nZones, T;
-    int wr0, wc0, wnr, wnc;
-    int rxi, wi, tilesY;          // tile interior and tile columns of the window (pv_prims.h histOffset)
+    ZoneWindow w;
     int slot0, slots;             // the chunk: slots slot0 .. slot0 + slots - 1
-    double* rows;                 // slots x nZones x gx: the row sums of the chunk
+    double* rows;                 // slots x nZones x (rows walked): the row sums of the chunk
     double* etc;                  // nZones x T, zone-major
     ZoneMembers* memberRows;      // nZones x gx
     ZoneMembers* members;         // nZones
 };
 
-// ---- sparse-emitter mode: the ABSOLUTE curve inside the run (pv_zone_decay.hip pv_stream_zone_curve_rows_kernel).  The history is
-// a ring of planes there, so the reduction runs per accumulate pass over the pass's steps, with the onsets that pass has just
-// settled (slot t needs plane t and the onsets <= t only).  The launch covers the labels' bounding box: a row or a 64-block
-// without a labelled cell is skipped by the definition itself
+// ---- sparse-emitter mode: the ABSOLUTE curve inside the run (launchStreamZoneCurves).  c.hist is a ring of planes there, step t
+// in plane t % ring, so the reduction runs per accumulate pass over the pass's steps, with the onsets that pass has just settled
+// (slot t needs plane t and the onsets <= t only); origin and extent of the window are read from *dyn on the device (c.w gives rxi
+// and wi; c.delay is not used).  The launch covers the labels' bounding box: a row or a 64-block without a labelled cell is
+// skipped by the definition itself
 struct DynParams;  // (pv_device.h)
-struct StreamZoneCurveArgs {
-    const float* hist;            // plane 0 of the ring: `ring` planes of histPlane floats, step t in plane t % ring
-    long long histPlane;
-    int ring;
+struct ZoneRingCurveArgs {
+    ZoneCurveArgs c;
     const int* onset;             // gx * gy: the accumulate pass's onsets, -1 = none yet
-    const unsigned char* labels;  // gx * gy
     const DynParams* dyn;         // the run's history window (device)
-    int gx, gy, nZones, T, G;
-    int rxi, wi;                  // tile interior (pv_prims.h histOffset)
-    int row0, rows;               // the result rows of the launch: row0 .. row0 + rows - 1
-    int blk0, blks;               // ... and its blocks of 64 Y, aligned at Y = 0: blk0 .. blk0 + blks - 1
-    int slot0, slots;             // the chunk: steps slot0 .. slot0 + slots - 1, all below T
-    double* rowSums;              // slots x nZones x rows: the row sums of the chunk
+    int ring, G;
+    int row0, nRows;              // the result rows of the launch: row0 .. row0 + nRows - 1
+    int blk0, nBlks;              // ... and its blocks of 64 Y, aligned at Y = 0: blk0 .. blk0 + nBlks - 1
 };
+
+// The scratch of a curve pass: the row sums of one chunk | the curves | the zones' member rows, rounded up to 8 bytes | the
+// zones' members.  Offsets in bytes, every one a multiple of 8 (a pass without row sums or curves gives 0 bytes for them)
+struct ZoneCurveScratch {
+    size_t rows, etc, memberRows, members, total;
+};
+inline ZoneCurveScratch zoneCurveScratch(size_t rowsBytes, size_t etcBytes, int nZones, int gx) {
+    const size_t memberRowsBytes = ((size_t)nZones * (size_t)gx * sizeof(ZoneMembers) + 7) / 8 * 8;
+    ZoneCurveScratch s;
+    s.rows = 0;
+    s.etc = rowsBytes;
+    s.memberRows = s.etc + etcBytes;
+    s.members = s.memberRows + memberRowsBytes;
+    s.total = s.members + (size_t)nZones * sizeof(ZoneMembers);
+    return s;
+}
 
 // What a zone's labels mean for the tiles and for the launch above (Solver::setZones): flags[ti * nty + tj] = 1 for every tile of
 // rxi x wi result cells that holds a labelled cell -- ntx = ceil(gx / rxi) rows of nty = ceil(gy / wi) tiles --, the first and
@@ -106,8 +117,8 @@ inline void zoneTileUnion(const unsigned char* emitterFlags, const unsigned char
     for (int t = 0; t < ntiles; ++t) out[t] = ((emitterFlags && emitterFlags[t]) || (zoneFlags && zoneFlags[t])) ? 1 : 0;
 }
 
-// the steps of an accumulate pass that one pair of launches takes: whole groups of kZoneCurveSlots whose row sums (a double per
-// step, zone and row of the box) stay within scratchBytes -- one group where even that is more
+// the slots that one pair of launches takes: whole groups of kZoneCurveSlots whose row sums (a double per slot, zone and row
+// walked -- the map's rows, or the box's in an accumulate pass) stay within scratchBytes -- one group where even that is more
 inline int streamZoneCurveChunk(int nZones, int rows, size_t scratchBytes) {
     const size_t perSlot = (size_t)(nZones > 1 ? nZones : 1) * (size_t)(rows > 1 ? rows : 1) * sizeof(double);
     const size_t fit = scratchBytes / perSlot / kZoneCurveSlots * kZoneCurveSlots;

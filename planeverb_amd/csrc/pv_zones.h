@@ -44,15 +44,23 @@ struct ZoneRow {
 };
 static_assert(sizeof(ZoneRow) == 40, "the scratch bound counts on it");
 
-// One chunk of planes of a map for launchZoneStats (pv_launch.h).  The history window of the map in RESULT coordinates is rows
-// [wr0, wr0 + wnr) x columns [wc0, wc0 + wnc); a cell outside it is NaN, as the read-backs give it
+// The history window of a run in RESULT coordinates, rows [r0, r0 + nr) x columns [c0, c0 + nc), and what places a cell of it
+// inside a tile-major plane (pv_zones_dev.h zoneWindowOffset).  Every zone pass carries one.  The plane's size stays a field of
+// the pass's own arguments, beside the pointer it goes with: seven ints keep every kernel's argument block as it was, and the
+// kernels of these passes sit at the scalar-register limit, where a moved argument is a measurable change
+struct ZoneWindow {
+    int r0, c0, nr, nc;
+    int rxi, wi, tilesY;  // tile interior and tile columns of the window (pv_prims.h histOffset)
+};
+
+// One chunk of planes of a map for launchZoneStats (pv_launch.h).  A cell outside the map's window w is NaN, as the read-backs
+// give it
 struct ZoneArgs {
     const float* map;             // plane 0 of the chunk: `planes` planes of histPlane floats
     long long histPlane;
     const unsigned char* labels;  // gx * gy
     int gx, gy, nZones;
-    int wr0, wc0, wnr, wnc;
-    int rxi, wi, tilesY;          // tile interior and tile columns of the window (pv_prims.h histOffset)
+    ZoneWindow w;
     int planes;                   // of the chunk
     int plane0, totalPlanes;      // the chunk's first plane in the map, the map's planes
     ZoneRow* rows;                // planes x nZones x gx

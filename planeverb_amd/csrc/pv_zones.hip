@@ -88,10 +88,8 @@ __device__ __forceinline__ ZoneCell zoneCellAt(const ZoneArgs& a, const float* _
     ZoneCell c;
     c.label = Y < a.gy ? (int)a.labels[(long long)X * a.gy + Y] : 0;
     c.x = __builtin_nanf("");
-    const int hr = X - a.wr0, hc = Y - a.wc0;
-    if (c.label != 0 && hr >= 0 && hc >= 0 && hr < a.wnr && hc < a.wnc) {
-        const int ti = hr / a.rxi, tj = hc / a.wi;
-        const long long g = ((long long)(ti * a.tilesY + tj) * a.rxi + (hr - ti * a.rxi)) * a.wi + (hc - tj * a.wi);
+    if (c.label != 0 && zoneWindowHas(a.w, X, Y)) {
+        const long long g = zoneWindowOffset(a.w, X, Y);
         if (g < a.histPlane) c.x = plane[g];
     }
     return c;

@@ -1,12 +1,13 @@
 // pv_zones_dev.h -- the cross-lane pieces the zone passes share (pv_zones.hip, pv_zone_decay.hip, pv_zone_band_decay.hip): DPP
-// moves, the wave form of the block butterfly of pv_zones.h, its sixteen-slot form and the member rule of the two zone-decay
-// passes.  Device code only.
+// moves, the wave form of the block butterfly of pv_zones.h, its sixteen-slot form, a cell's offset inside a plane of the history
+// window and the member rule of the two zone-decay passes.  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
 
+#include "pv_prims.h"
 #include "pv_zone_decay.h"
 
 namespace pva {
@@ -42,6 +43,18 @@ __device__ __forceinline__ double zoneWaveBlockSum(double v) {
     return zoneReadLane(v, 0);
 }
 
+// The one place a zone kernel finds result cell (X, Y) in a tile-major plane of the window: is it inside, and at which offset
+// (floats; the caller still holds it against the plane's size).  Two functions and not one with an "outside" value: a kernel
+// tests the window in one condition with its own refusals of the cell, and these kernels sit at the scalar-register limit, where
+// another shape of that condition compiles to other code (profiles/zone_passes_refactor.txt)
+__device__ __forceinline__ bool zoneWindowHas(const ZoneWindow& w, int X, int Y) {
+    const int hr = X - w.r0, hc = Y - w.c0;
+    return hr >= 0 && hc >= 0 && hr < w.nr && hc < w.nc;
+}
+__device__ __forceinline__ long long zoneWindowOffset(const ZoneWindow& w, int X, int Y) {
+    return histOffset(X - w.r0, Y - w.c0, w.rxi, w.wi, w.tilesY);
+}
+
 // ---- the pieces the two zone-decay passes share (pv_zone_decay.hip, pv_zone_band_decay.hip)
 
 // a lane's cell of a block: label 0 where the cell is no member (no label, past gy, no onset, outside the window)
@@ -50,6 +63,7 @@ struct ZoneCurveCell {
     int t0;
     long long g;  // offset inside a history plane
 };
+// the kept history's: the onset map of the run (float, FLT_MAX = none) and the window of the args
 __device__ __forceinline__ ZoneCurveCell zoneCurveCellAt(const ZoneCurveArgs& a, int X, int Y) {
     ZoneCurveCell c{0, 0, 0};
     if (Y >= a.gy) return c;
@@ -57,10 +71,8 @@ __device__ __forceinline__ ZoneCurveCell zoneCurveCellAt(const ZoneCurveArgs& a,
     const int label = (int)a.labels[s];
     if (label == 0) return c;
     const float d = a.delay[s];
-    const int hr = X - a.wr0, hc = Y - a.wc0;
-    if (d == FLT_MAX || !(d >= 0.0f && d < (float)a.T) || hr < 0 || hc < 0 || hr >= a.wnr || hc >= a.wnc) return c;
-    const int ti = hr / a.rxi, tj = hc / a.wi;
-    const long long g = ((long long)(ti * a.tilesY + tj) * a.rxi + (hr - ti * a.rxi)) * a.wi + (hc - tj * a.wi);
+    if (d == FLT_MAX || !(d >= 0.0f && d < (float)a.T) || !zoneWindowHas(a.w, X, Y)) return c;
+    const long long g = zoneWindowOffset(a.w, X, Y);
     if (g >= a.histPlane) return c;
     c.label = label;
     c.t0 = (int)d;

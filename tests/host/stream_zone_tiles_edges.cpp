@@ -1,13 +1,15 @@
 // stream_zone_tiles_edges.cpp -- the edge cases of what a sparse-emitter run derives from the zones' labels (csrc/pv_zone_decay.h:
-// zoneTileFlags, zoneTileUnion, streamZoneCurveChunk) in a program of their own, to be compiled with -fsanitize=address,undefined
-// and run on the CPU (tests/test_host_stream_zone_decay.py): every array is sized exactly, so a flag written past the tile plane
-// or a label read past the map is an ASan report.
+// zoneTileFlags, zoneTileUnion, streamZoneCurveChunk) and the scratch layout of the curve passes (zoneCurveScratch) in a program
+// of their own, to be compiled with -fsanitize=address,undefined and run on the CPU (tests/test_host_stream_zone_decay.py): every
+// array is sized exactly, so a flag written past the tile plane or a label read past the map is an ASan report.
 //   1  no labelled cell: no flag, the empty box;
 //   2  one labelled cell in each corner of the grid, on grids that are no multiple of the tile or of 64;
 //   3  labels on the last row / column of a tile and on Y = 63 / 64;
 //   4  a grid smaller than one tile and smaller than one block;
 //   5  the union with either side missing, and with no tile at all;
-//   6  the chunk: whole groups within the bound, one group where the bound is below one.
+//   6  the chunk: whole groups within the bound, one group where the bound is below one;
+//   7  the scratch of a curve pass: increasing offsets, every region 8-byte aligned (a member record is 12 bytes, so an odd
+//      nZones x gx needs the padding), and the total the passes have always asked for.
 #include <cstdio>
 #include <vector>
 
@@ -116,6 +118,28 @@ int main() {
         CHECK(streamZoneCurveChunk(64, 16384, bound) == 16);  // (one group is more than the bound: one group all the same)
         CHECK(streamZoneCurveChunk(1, 1, 0) == 16);
         CHECK(streamZoneCurveChunk(0, 0, bound) == kZoneCurveMaxChunk);
+    }
+    {  // 7
+        static_assert(sizeof(ZoneMembers) == 12, "the padding below counts on it");
+        const int T = 435;
+        for (int nz : {1, 5, 64})
+            for (int gx : {1, 70, 401}) {
+                const size_t curve = (size_t)nz * T * sizeof(double), group = (size_t)kZoneCurveSlots * nz * gx * sizeof(double);
+                // zone decay (a chunk of slots), zone band decay with three bands (a chunk of pairs), a sparse-emitter solver (members only)
+                const size_t sizes[][2] = {{group, curve}, {(size_t)nz * 3 * gx * T * sizeof(double), 3 * curve}, {0, 0}};
+                for (const auto& b : sizes) {
+                    const ZoneCurveScratch s = zoneCurveScratch(b[0], b[1], nz, gx);
+                    CHECK(s.rows == 0 && s.etc == s.rows + b[0] && s.memberRows == s.etc + b[1]);
+                    CHECK(s.rows <= s.etc && s.etc <= s.memberRows && s.memberRows < s.members && s.members < s.total);
+                    CHECK(s.rows % 8 == 0 && s.etc % 8 == 0 && s.memberRows % 8 == 0 && s.members % 8 == 0);
+                    CHECK(s.members - s.memberRows >= (size_t)nz * gx * sizeof(ZoneMembers));
+                    CHECK(s.members - s.memberRows < (size_t)nz * gx * sizeof(ZoneMembers) + 8);
+                    const size_t memberRowsBytes = ((size_t)nz * (size_t)gx * sizeof(ZoneMembers) + 7) / 8 * 8;
+                    CHECK(s.total == b[0] + b[1] + memberRowsBytes + (size_t)nz * sizeof(ZoneMembers));
+                }
+            }
+        CHECK(zoneCurveScratch(0, 0, 1, 1).members == 16);  // (12 bytes of member rows, padded)
+        CHECK(zoneCurveScratch(0, 0, 5, 401).members == 24064);  // (24060, padded)
     }
     std::printf("stream_zone_tiles_edges: %d failure(s)\n", failures);
     return failures ? 1 : 0;

@@ -1,5 +1,6 @@
 """GPU (-m gpu): the contract the nine per-cell analysis kinds share (csrc/pv_solver_maps.cpp: one record per kind in the solver,
-one set of compute / fetch / block / at routines).  What the numbers are is each kind's own test file's business; here it is the
+one set of compute / fetch / block / at routines; the reductions of these maps over zones are csrc/pv_solver_zones.cpp's and have
+their own test files).  What the numbers are is each kind's own test file's business; here it is the
 plumbing: a kind's device buffer, host copy and validity must not leak into another kind's.  Everything is compared bit for bit,
 NaNs by position.  One 25 m x 25 m solver at 275 Hz, 160 steps, one box (its cells have no onset: NaN records)."""
 import numpy as np

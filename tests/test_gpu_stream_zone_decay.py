@@ -1,5 +1,5 @@
 """GPU (-m gpu): the zones' ABSOLUTE ensemble decay curves of a sparse-emitter solver (PvAmdSetZoneCurves), accumulated inside the
-run off the ring of pressure planes (csrc/pv_zone_decay.hip pv_stream_zone_curve_rows_kernel).
+run off the ring of pressure planes (csrc/pv_zone_decay.hip: the rows kernel over the ring source).
 
 The reference is always a SECOND solver that keeps its history -- the same scene, listener and labels, zone_decay("absolute",
 curves=True) -- never the sparse-emitter solver itself.  Tolerance 0: all 64 bytes of every record, etc and edc bit for bit,

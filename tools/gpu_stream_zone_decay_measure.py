@@ -33,7 +33,7 @@ ZONES = {"off": [],
          "one": [(8.0, 8.0, 13.0, 13.0)],
          "five": [(8.0, 8.0, 13.0, 13.0), (1.0, 1.0, 4.0, 7.0), (15.0, 2.0, 23.0, 6.0), (2.0, 16.0, 9.0, 23.0), (16.0, 15.0, 22.0, 22.0)],
          "whole": [(0.0, 0.0, 26.0, 26.0)]}
-KERNELS = ("pv_stream_zone_curve_rows_kernel", "pv_zone_curve_merge_kernel", "pv_stream_accum_kernel")
+KERNELS = ("pv_zone_curve_rows_kernel", "pv_zone_curve_merge_kernel", "pv_stream_accum_kernel")
 
 
 def load_api():
