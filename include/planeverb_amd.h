@@ -741,7 +741,9 @@ PVA_EXPORT int PvAmdSetHistoryPlane(PvAmdSolver* s, int t, const float* pr);
  * solver; cells outside the window are unreached by construction.  The records stay valid until the next run, geometry,
  * boundary or layer change on that solver: PvAmdCopyRoomMetrics* / PvAmdGetRoomMetrics then return -1 until computed again.
  * Refused (-1, nothing changed, PvAmdLastError says why): NULL, no completed run, a last run that ended in error, sparse-emitter
- * solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks. */
+ * solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks.
+ * On a sparse-emitter solver PvAmdComputeRoomMetrics stays refused (there is no history), but the records of the LABELLED cells
+ * can be accumulated inside the run: PvAmdSetZoneMaps(PVA_ZMAP_ROOM_METRICS) below; the three read-backs then serve that map. */
 typedef struct PvAmdRoomMetrics {
     float c50, c80, d50, ts, e50, l50, e80, l80, total, moment;
 } PvAmdRoomMetrics;
@@ -1240,7 +1242,10 @@ PVA_EXPORT int PvAmdCombineMti(const float* mti, const float* alpha, const float
  * invalidate each other.  Options (PVA_OPT_NUM_STEPS among them) are fixed before the first call, so T cannot change under
  * the tables.
  * Refused (-1, nothing changed, PvAmdLastError says why, "spectrum: ..."): no bins set, no completed run, a last run that ended
- * in error, sparse-emitter solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks. */
+ * in error, sparse-emitter solvers (no history), PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks.
+ * On a sparse-emitter solver PvAmdComputeSpectrum stays refused (there is no history), but the records of the LABELLED cells can
+ * be accumulated inside the run: PvAmdSetZoneMaps(PVA_ZMAP_SPECTRUM) below; the three read-backs then serve that map, and the
+ * bins cannot be cleared while it is selected (changing them is allowed: the map of the run before is then refused). */
 #define PVA_SPECTRUM_MAX_BINS 32
 /* Set the bins (copied).  n = 0 clears them and frees the device storage; waits for a run in flight.  Refused with -1 and nothing
  * changed: hz = NULL with n > 0, n outside 0 .. PVA_SPECTRUM_MAX_BINS, a frequency that is not finite, negative or above fs / 2 */
@@ -1296,7 +1301,9 @@ PVA_EXPORT int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const
  * 32 MiB (one plane's nZones x gx x 48 bytes where that is more) -- plus the records.
  * Out of scope: the eight-output result map (its far cells are kept lazily and carry values over between runs), histograms
  * and percentiles, overlapping zones, in-run or live-module zone records, slab groups and slab ranks.  Sparse-emitter solvers
- * take the labels (PvAmdSetZones, for the in-run zone curves below) but keep no history: PvAmdComputeZoneStats is refused there. */
+ * take the labels (PvAmdSetZones, for the in-run zone curves and zone maps below) but keep no history: PvAmdComputeZoneStats is
+ * refused there, except for PVA_MAP_ROOM_METRICS and PVA_MAP_SPECTRUM while PvAmdSetZoneMaps has the kind selected -- the map is
+ * then the last run's own, and the records are those of a solver that keeps its history, byte for byte. */
 #define PVA_MAP_ROOM_METRICS     0
 #define PVA_MAP_DECAY_TIMES      1
 #define PVA_MAP_LATERAL_FRACTION 2
@@ -1316,9 +1323,10 @@ typedef struct PvAmdZoneStat {
 /* Set the zones: labels = gx*gy bytes, cell X*gy + Y, each 0 or 1 .. nZones (copied to the device; they survive runs and
  * geometry changes).  labels = NULL with nZones = 0 clears them.  Waits for a run in flight.  Refused with -1 and nothing
  * changed ("zone statistics: ..."): a label above nZones, nZones outside 1 .. PVA_ZONES_MAX, labels = NULL with nZones > 0,
- * slab groups and slab ranks; on a sparse-emitter solver also clearing the zones while PvAmdSetZoneCurves is enabled.  Labels
- * alone change nothing about a sparse-emitter run; with the curves enabled, new labels re-derive the tiles, the launch box and
- * the buffers, and the curves of the run before are refused */
+ * slab groups and slab ranks; on a sparse-emitter solver also clearing the zones while PvAmdSetZoneCurves is enabled or a kind of
+ * PvAmdSetZoneMaps is selected.  Labels alone change nothing about a sparse-emitter run; with the curves enabled (a map kind
+ * selected), new labels re-derive the tiles, the launch box and the buffers (the tile list and the NaN fill), and the curves
+ * (the maps) of the run before are refused */
 PVA_EXPORT int PvAmdSetZones(PvAmdSolver* s, const unsigned char* labels, int nZones);
 /* the labels as set (gx*gy bytes; labels may be NULL; untouched when no zones are set) and their count (0: none); returns 0 */
 PVA_EXPORT int PvAmdGetZones(PvAmdSolver* s, unsigned char* labels, int* nZones);
@@ -1383,7 +1391,9 @@ PVA_EXPORT int PvAmdHostZoneRects(float dx, int gx, int gy, const float* rect4, 
  * PvAmdHostZoneCurveClarity gives such a curve its clarity and centre time.
  * Out of scope: normalising each cell by its own E0, live-module records, overlapping zones, slab groups and slab ranks; in
  * sparse-emitter mode also PVA_ZONE_DECAY_ONSET (every member's sample of a slot is needed at once, and they arrive at different
- * steps), the band curves (the filter walks backwards in time) and the zone statistics. */
+ * steps) and the band curves (the filter walks backwards in time).  The zone statistics of the room metrics and the spectrum are
+ * available there through PvAmdSetZoneMaps; those of the seven other kinds are not (decay times, band metrics and modulation walk
+ * backwards in time, the echo criterion needs c(k - nD), the three velocity kinds need the neighbours from the light cone on). */
 #define PVA_ZONE_DECAY_ABSOLUTE 0
 #define PVA_ZONE_DECAY_ONSET    1
 typedef struct PvAmdZoneDecay {
@@ -1405,6 +1415,45 @@ PVA_EXPORT int PvAmdComputeZoneDecay(PvAmdSolver* s, int align, PvAmdZoneDecay* 
 PVA_EXPORT int PvAmdSetZoneCurves(PvAmdSolver* s, int enable);
 /* *enabled = 1 while PvAmdSetZoneCurves holds, else 0 (a solver that keeps its history: 0); returns 0 */
 PVA_EXPORT int PvAmdGetZoneCurves(PvAmdSolver* s, int* enabled);
+/* ---- Zone maps: room-metrics and spectrum records of every labelled cell, accumulated inside a sparse-emitter run ----
+ * Sparse-emitter solvers only.  Both kinds are forward sums from the cell's onset -- six float32 sums for the room metrics, re
+ * and im per bin for the spectrum, each sequential in increasing t from +0.0f -- so they are advanced per accumulate pass off the
+ * ring, in the pass that follows the one that settles the onset, and end with the same bits a walk over a kept history gives.
+ * Definition: the record of a LABELLED cell (PvAmdSetZones, label != 0) is the kind's own definition above (PvAmdRoomMetrics,
+ * spectrum) word for word -- ten quiet NaNs / 3 n quiet NaNs where the cell has no onset in that run (wall cells among them;
+ * nothing is carried over from earlier runs); every UNLABELLED cell holds quiet NaN in every float.  Every record matches, bit for
+ * bit, what PvAmdComputeRoomMetrics / PvAmdComputeSpectrum give at that cell on a second solver that keeps its history (same
+ * scene, listener, labels and bins), and PvAmdComputeZoneStats of the two kinds matches byte for byte.
+ * PvAmdSetZoneMaps(kinds) selects PVA_ZMAP_ROOM_METRICS and / or PVA_ZMAP_SPECTRUM for every following run; kinds = 0 deselects.
+ * It waits for a run in flight, allocates on select and frees on deselect.  Device storage: the kind's own map over the whole
+ * grid (tile-rounded) -- 10 x 4 bytes per cell for the room metrics (about 0.67 GB at 4096^2), 3 n x 4 bytes per cell for the
+ * spectrum -- plus 4 bytes per labelled tile; storage over the labelled tiles only is out of scope.  While a kind is selected a
+ * tile that holds a labelled cell stays in the ring and records for the whole run, as with PvAmdSetZoneCurves (neither selector
+ * drops the other's tiles), PvAmdSetZones(NULL, 0) is refused, and PvAmdSetSpectrumBins(.., 0) is refused while PVA_ZMAP_SPECTRUM
+ * is selected.  Changing labels or bins is allowed and re-derives the storage.
+ * After a run that accumulated a kind, PvAmdCopyRoomMetrics / ..Block / PvAmdGetRoomMetrics, PvAmdCopySpectrum / ..Block /
+ * PvAmdGetSpectrum and PvAmdComputeZoneStats(PVA_MAP_ROOM_METRICS / PVA_MAP_SPECTRUM) work on that map (they wait for a run in
+ * flight).  Refused there ("room metrics: ..." / "spectrum: ..."): no completed run, a last run that ended in error, and a last run
+ * that was enqueued before the kind was selected, before the current labels were set or before the current bins were set.  With no
+ * kind selected every call refuses as it did.  With nothing selected a run is launch for launch what it was before.
+ * Returns 0, or -1 with PvAmdLastError "zone maps: ..." and nothing changed: NULL, unknown bits, a solver that keeps its history
+ * (it has PvAmdCompute*), slab groups and slab ranks, PVA_OPT_SKIP_ANALYSIS, no zones set, PVA_ZMAP_SPECTRUM with no bins set.
+ * Out of scope: the seven other map kinds, ONSET and band curves, the live module, slab groups and slab ranks. */
+#define PVA_ZMAP_ROOM_METRICS 1u
+#define PVA_ZMAP_SPECTRUM     2u
+PVA_EXPORT int PvAmdSetZoneMaps(PvAmdSolver* s, unsigned kinds);
+/* *kinds = the kinds PvAmdSetZoneMaps holds (a solver that keeps its history: 0); returns 0 */
+PVA_EXPORT int PvAmdGetZoneMaps(PvAmdSolver* s, unsigned* kinds);
+/* CPU only: one accumulate pass [tA, tB) of the room metrics restated -- the six sums (e50, l50, e80, l80, total, moment) advanced
+ * over t = max(tA, onset) .. min(tB, T) - 1 by the per-sample update of the definition; a cell whose onset lies in the pass
+ * (onset >= tA) starts from +0.0f and never reads sums6; onset >= min(tB, T) changes nothing */
+PVA_EXPORT int PvAmdHostRoomSumsAdvance(const float* p, int T, int fs, int onset, int tA, int tB, float sums6[6]);
+/* CPU only: the record of six such sums: c50, c80, d50, ts derived as the definition says, then the sums themselves */
+PVA_EXPORT int PvAmdHostRoomMetricsFromSums(const float sums6[6], int fs, PvAmdRoomMetrics* out);
+/* CPU only: the same pass for the spectrum -- re, im of bin j at reim2n[2 j], [2 j + 1], the tables of PvAmdHostSpectrumTables
+ * (T x n floats each, indexed by absolute step) */
+PVA_EXPORT int PvAmdHostSpectrumAdvance(const float* p, int T, int onset, int tA, int tB, const float* cosTn, const float* sinTn,
+                                        int n, float* reim2n);
 /* CPU only: what labels mean for a sparse-emitter run with the curves enabled -- flags = ceil(gx / tileRows) x ceil(gy / tileCols)
  * bytes, 1 for every tile that holds a labelled cell (it stays in the ring), box4 = the first and last labelled row and the
  * first and last labelled block of 64 Y (0, -1, 0, -1 for no labelled cell): the extent of the curve launches */

@@ -64,10 +64,12 @@ def zone_plane_names(s, a):
 def zone_tables(s, a):
     """one table per --zone: for every plane of every computed map its n (finite members), mean, std, min and max over the zone"""
     labels = api.zone_labels_from_rects(s.dx, s.gx, s.gy, a.zone)
-    if not a.sparse_emitters:  # (there the labels were set in front of the run, which accumulated the curves; no maps to reduce)
+    if not a.sparse_emitters:  # (there the labels were set in front of the run, which accumulated the curves and the zone maps)
         s.set_zones(labels, len(a.zone))
     tables = [{"rect": list(r), "cells": int((labels == j + 1).sum())} for j, r in enumerate(a.zone)]
-    for kind, key, names in ([] if a.sparse_emitters else zone_plane_names(s, a)):
+    # (sparse-emitter mode: the two kinds a run can accumulate -- Solver.set_zone_maps --, the same tables from the run's own maps)
+    streamed = ("room_metrics", "spectrum")
+    for kind, key, names in [k for k in zone_plane_names(s, a) if not a.sparse_emitters or k[0] in streamed]:
         recs = s.zone_stats(kind).reshape(len(a.zone), -1)
         for t, row in zip(tables, recs):
             t[key] = dict((n, {"n": int(r["n_finite"]), "mean": float(r["mean"]), "std": float(r["std"]), "min": float(r["min"]),
@@ -188,7 +190,8 @@ def main(argv=None):
                          "overlap): with any of the map options above, add a table per zone with n, mean, std, min and max of "
                          "every plane of those maps over the zone's cells, reduced on the GPU; with --zone-decay, the zone's "
                          "ensemble decay curve and its decay times; with --sparse-emitters only --zone-decay absolute, whose "
-                         "curves are accumulated inside the run (no tables of the maps: that mode keeps no history)")
+                         "curves are accumulated inside the run, and the tables of --room-metrics and --spectrum, whose records "
+                         "of the zones' cells are too (no tables of the other maps: that mode keeps no history)")
     ap.add_argument("--zone-decay", choices=api.ZONE_DECAY_ALIGN_NAMES,
                     help="with --zone (it counts as one of the options --zone needs): add per zone the ensemble decay curve's table "
                          "-- the squared responses of the zone's reached cells summed on the GPU, by time since emission (absolute) "
@@ -206,9 +209,10 @@ def main(argv=None):
         ap.error("--modulation: needs --bands")
     if a.zone and a.in_run_records:
         ap.error("--zone: reduces the whole-map passes (not with --in-run-records)")
-    if a.zone and a.sparse_emitters and (a.zone_decay != "absolute" or a.zone_band_decay):
-        ap.error("--zone: with --sparse-emitters only --zone-decay absolute (the curves are accumulated inside the run; the "
-                 "onset-synchronised and the band curves need the history)")
+    if a.zone and a.sparse_emitters and (a.zone_band_decay or a.zone_decay == "onset" or
+                                         not (a.zone_decay or a.room_metrics or a.spectrum)):
+        ap.error("--zone: with --sparse-emitters only --zone-decay absolute, --room-metrics and --spectrum (the curves and those two "
+                 "maps are accumulated inside the run; the onset-synchronised and the band curves and the other maps need the history)")
     if a.in_run_records and a.sparse_emitters:
         ap.error("--sparse-emitters: not with --in-run-records (the output queries' records need the history)")
     if a.zone_decay and not a.zone:
@@ -257,7 +261,10 @@ def main(argv=None):
                 s.set_emitter_records(kinds, spectral)
                 if a.zone:  # (the curves of --zone-decay absolute are accumulated inside the run)
                     s.set_zones(api.zone_labels_from_rects(s.dx, s.gx, s.gy, a.zone), len(a.zone))
-                    s.set_zone_curves(True)
+                    if a.zone_decay:
+                        s.set_zone_curves(True)
+                    # (... and so are the room-metrics and spectrum records of the zones' cells)
+                    s.set_zone_maps((api.ZMAP_ROOM_METRICS if a.room_metrics else 0) | (api.ZMAP_SPECTRUM if a.spectrum else 0))
             else:
                 s.set_output_queries(emitters)
                 s.set_query_records(kinds)

@@ -366,6 +366,11 @@ SYMBOLS = {
     "PvAmdZoneDecayChunkSlots": (C.c_int, [_vp]),
     "PvAmdSetZoneCurves": (C.c_int, [_vp, C.c_int]),
     "PvAmdGetZoneCurves": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "PvAmdSetZoneMaps": (C.c_int, [_vp, C.c_uint]),
+    "PvAmdGetZoneMaps": (C.c_int, [_vp, C.POINTER(C.c_uint)]),
+    "PvAmdHostRoomSumsAdvance": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "PvAmdHostRoomMetricsFromSums": (C.c_int, [_fp, C.c_int, C.POINTER(PvAmdRoomMetrics)]),
+    "PvAmdHostSpectrumAdvance": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp]),
     "PvAmdHostZoneTiles": (C.c_int, [C.POINTER(C.c_ubyte)] + [C.c_int] * 4 + [C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "PvAmdHostZoneTileUnion": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.c_int, C.POINTER(C.c_ubyte)]),
     "PvAmdHostZoneCurveChunk": (C.c_int, [C.c_int, C.c_int, C.c_longlong]),
@@ -1042,6 +1047,40 @@ def host_spectrum(p, fs, onset, hz, pulse):
     _check(lib().PvAmdHostSpectrum(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(h) if h.size else None,
                                    int(h.size), _f(q) if q.size else None, _f(out)))
     return out
+
+
+ZMAP_ROOM_METRICS, ZMAP_SPECTRUM = 1, 2  # PVA_ZMAP_*: the map kinds of Solver.set_zone_maps
+
+
+def host_room_sums_advance(p, fs, onset, tA, tB, sums6=None):
+    """PvAmdHostRoomSumsAdvance: the six room-metric sums (e50, l50, e80, l80, total, moment) of p[T] advanced over the accumulate
+    pass [tA, tB) -- from +0.0 where the onset lies in the pass, else from sums6; float32 [6]"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    s = np.zeros(6, np.float32) if sums6 is None else np.array(sums6, np.float32).reshape(6)
+    _check(lib().PvAmdHostRoomSumsAdvance(_f(a) if a.size else None, int(a.size), int(fs), int(onset), int(tA), int(tB), _f(s)))
+    return s
+
+
+def host_room_metrics_from_sums(sums6, fs):
+    """PvAmdHostRoomMetricsFromSums: float32 [10] (ROOM_METRIC_NAMES) of six such sums"""
+    s = np.ascontiguousarray(sums6, np.float32).reshape(6)
+    out = PvAmdRoomMetrics()
+    _check(lib().PvAmdHostRoomMetricsFromSums(_f(s), int(fs), out))
+    return out.as_array()
+
+
+def host_spectrum_advance(p, onset, tA, tB, cos_tn, sin_tn, reim=None):
+    """PvAmdHostSpectrumAdvance: re, im of every bin (float32 [n, 2]) of p[T] advanced over the accumulate pass [tA, tB) with the
+    tables of host_spectrum_tables -- from +0.0 where the onset lies in the pass, else from reim"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    c = np.ascontiguousarray(cos_tn, np.float32)
+    s = np.ascontiguousarray(sin_tn, np.float32)
+    if c.ndim != 2 or c.shape != s.shape or c.shape[0] != a.size:
+        raise ValueError("host_spectrum_advance: tables [T, n]")
+    n = c.shape[1]
+    r = np.zeros((n, 2), np.float32) if reim is None else np.array(reim, np.float32).reshape(n, 2)
+    _check(lib().PvAmdHostSpectrumAdvance(_f(a) if a.size else None, int(a.size), int(onset), int(tA), int(tB), _f(c), _f(s), int(n), _f(r)))
+    return r
 
 
 # PVA_MAP_*: the nine per-cell analysis kinds, as Solver.zone_stats names them (the stems of Solver.compute_<name> / <name>)
@@ -2284,6 +2323,18 @@ class Solver:
         on = C.c_int(0)
         _check(lib().PvAmdGetZoneCurves(self._h, C.byref(on)))
         return bool(on.value)
+
+    def set_zone_maps(self, kinds):
+        """PvAmdSetZoneMaps (sparse-emitter solvers, zones set): every following run accumulates the room-metrics (ZMAP_ROOM_METRICS)
+        and / or spectrum (ZMAP_SPECTRUM; bins set) records of every labelled cell on the device, off the ring; room_metrics*,
+        spectrum* and zone_stats of the two kinds then read that map (unlabelled cells: NaN).  0 deselects and frees"""
+        _check(lib().PvAmdSetZoneMaps(self._h, int(kinds)))
+
+    def zone_maps(self):
+        """PvAmdGetZoneMaps: the kinds set_zone_maps holds"""
+        k = C.c_uint(0)
+        _check(lib().PvAmdGetZoneMaps(self._h, C.byref(k)))
+        return int(k.value)
 
     def zone_decay_chunk_slots(self):
         """PvAmdZoneDecayChunkSlots: the time slots zone_decay deals per pair of launches under the current zones"""

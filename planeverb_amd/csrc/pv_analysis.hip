@@ -18,6 +18,7 @@
 #include "pv_libm.h"
 #include "pv_prims.h"
 #include "pv_record_lane.h"
+#include "pv_zone_maps.h"
 
 namespace pva {
 
@@ -713,7 +714,8 @@ __global__ void pv_stream_tilegate_kernel(const uint8_t* marks, const uint8_t* h
 }
 
 void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
-                       hipStream_t stream, const ZoneRingCurveArgs* zc, int zcChunk) {
+                       hipStream_t stream, const ZoneRingCurveArgs* zc, int zcChunk, const ZoneMapArgs* zm,
+                       const ZoneMapSpecSlice* zmSlices, int zmSliceCount) {
     dim3 grid((a.gy + 255) / 256, a.gx);
     if (a.ringList) grid = dim3((unsigned)((a.rxi * a.wi + 255) / 256) * (unsigned)(a.numRing > 0 ? a.numRing : 1), 1);
     hipMemsetAsync(a.tileOpenOut, 0, (size_t)ntiles, stream);
@@ -728,6 +730,13 @@ void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t*
     // the zones' curves of this pass's steps: behind the accumulate kernel, whose onsets decide the members, and -- as everything
     // in here -- in front of the event that hands the half ring back to the step kernels
     if (zc) launchStreamZoneCurves(*zc, a.tA, a.tB, zcChunk, stream);
+    // the labelled cells' map sums of this pass's steps: the same two conditions
+    if (zm) {
+        ZoneMapArgs m = *zm;
+        m.tA = a.tA;
+        m.tB = a.tB;
+        launchStreamZoneMaps(m, zmSlices, zmSliceCount, stream);
+    }
 }
 
 void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream) {

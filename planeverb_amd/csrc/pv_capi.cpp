@@ -1690,6 +1690,20 @@ int PvAmdGetZoneCurves(PvAmdSolver* h, int* enabled) try {
     return 0;
 } PV_API_CATCH(-1)
 
+// the room-metrics and spectrum maps of the labelled cells inside a sparse-emitter run (pv_zone_maps.hip)
+static_assert(PVA_ZMAP_ROOM_METRICS == kZoneMapRoomMetrics && PVA_ZMAP_SPECTRUM == kZoneMapSpectrum, "the map kinds");
+
+int PvAmdSetZoneMaps(PvAmdSolver* h, unsigned kinds) try {
+    if (!analysisHandle(h, "zone maps: ")) return -1;
+    return ret(h, h->s->setZoneMaps(kinds));
+} PV_API_CATCH(-1)
+
+int PvAmdGetZoneMaps(PvAmdSolver* h, unsigned* kinds) try {
+    if (!analysisHandle(h, "zone maps: ")) return -1;
+    if (kinds) *kinds = h->s->zoneMaps();
+    return 0;
+} PV_API_CATCH(-1)
+
 // zone band decay (pv_zone_band_decay.hip)
 static_assert(sizeof(PvAmdZoneBandDecay) == sizeof(ZoneBandDecay), "96 bytes");
 
@@ -2199,6 +2213,44 @@ int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const float* hz,
     spectrumTables(T, fs, hz, n, c.data(), s.data());
     spectrumSource(pulseT, T, c.data(), s.data(), n, src.data());
     spectrumOfIr(p, T, onset, c.data(), s.data(), n, src.data(), out3n);
+    return 0;
+} PV_API_CATCH(-1)
+
+// the accumulate passes of PvAmdSetZoneMaps restated: the step functions of pv_metrics.h / pv_spectrum.h the kernel applies
+int PvAmdHostRoomSumsAdvance(const float* p, int T, int fs, int onset, int tA, int tB, float sums6[6]) try {
+    if (!p || !sums6 || T <= 0 || onset < 0 || onset >= T || tA < 0 || tB < tA) {
+        g_lastError = "zone maps: PvAmdHostRoomSumsAdvance: an impulse response p[T], T > 0, 0 <= onset < T, a pass 0 <= tA <= tB and six sums";
+        return -1;
+    }
+    static_assert(sizeof(RoomSums) == 6 * sizeof(float), "six floats");
+    RoomSums s;
+    std::memcpy(&s, sums6, sizeof(s));
+    roomSumsAdvance(p, T, fs, onset, tA, tB, &s);
+    std::memcpy(sums6, &s, sizeof(s));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostRoomMetricsFromSums(const float sums6[6], int fs, PvAmdRoomMetrics* out) try {
+    if (!sums6 || !out) {
+        g_lastError = "zone maps: PvAmdHostRoomMetricsFromSums: six sums and an output record";
+        return -1;
+    }
+    RoomSums s;
+    std::memcpy(&s, sums6, sizeof(s));
+    float v[kRoomMetricFloats];
+    roomMetricsDerive(s, fs, &v[0], &v[1], &v[2], &v[3]);
+    std::memcpy(v + 4, sums6, 6 * sizeof(float));
+    std::memcpy(out, v, sizeof(*out));
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostSpectrumAdvance(const float* p, int T, int onset, int tA, int tB, const float* cosTn, const float* sinTn, int n, float* reim2n) try {
+    if (!p || !cosTn || !sinTn || !reim2n || T <= 0 || onset < 0 || onset >= T || tA < 0 || tB < tA || n < 1 || n > kSpectrumMaxBins) {
+        g_lastError = "zone maps: PvAmdHostSpectrumAdvance: an impulse response p[T], tables of T x n floats, T > 0, 0 <= onset < T, a pass 0 <= tA <= tB, "
+                      "1 .. 32 bins and 2 n sums";
+        return -1;
+    }
+    spectrumAdvance(p, T, onset, tA, tB, cosTn, sinTn, n, reim2n);
     return 0;
 } PV_API_CATCH(-1)
 

@@ -119,9 +119,14 @@ void launchAnalysisDirection(const AnalyzeArgs& a, hipStream_t stream);
 void launchFarDirections(float* res, long long n, const FarInfo& far, hipStream_t stream);
 void launchFillDelay(float* delay, long long n, hipStream_t stream);
 // (zc: the zones' curves of the pass's steps behind its onsets -- launchStreamZoneCurves below --, nullptr: none)
+// (zm: the labelled cells' room-metrics / spectrum sums of the pass's steps, likewise behind its onsets -- launchStreamZoneMaps
+// below, with the pass's tA / tB --, nullptr: no map kind selected)
 struct ZoneRingCurveArgs;
+struct ZoneMapArgs;
+struct ZoneMapSpecSlice;
 void launchStreamAccum(const AnalyzeArgs& a, const uint8_t* hasEmitter, uint8_t* tileOpen, int ntiles,
-                       hipStream_t stream, const ZoneRingCurveArgs* zc = nullptr, int zcChunk = 0);
+                       hipStream_t stream, const ZoneRingCurveArgs* zc = nullptr, int zcChunk = 0, const ZoneMapArgs* zm = nullptr,
+                       const ZoneMapSpecSlice* zmSlices = nullptr, int zmSliceCount = 0);
 void launchStreamFinalize(const AnalyzeArgs& a, hipStream_t stream);
 
 // ---- pv_rt60.hip: wet gain and decay time; results carried over from another solver
@@ -165,6 +170,13 @@ void launchZoneCurves(const ZoneCurveArgs& a, bool onset, hipStream_t stream);
 // sparse-emitter mode: steps [tA, min(tB, T)) of every zone's ABSOLUTE curve into a.c.etc (nZones x T), off the ring, in chunks of
 // `chunk` steps (pv_zone_decay.h streamZoneCurveChunk; a.c.slot0 / a.c.slots are the launcher's; a.c.rows is scratch)
 void launchStreamZoneCurves(const ZoneRingCurveArgs& a, int tA, int tB, int chunk, hipStream_t stream);
+
+// ---- pv_zone_maps.hip: sparse-emitter mode, the room-metrics and spectrum records of the labelled cells inside the run
+// launchStreamZoneMaps: the sums of the steps [a.tA, min(a.tB, a.T)) into the records' own planes (pv_zone_maps.h), one launch for
+// the room metrics and one per slice of the bins; launchStreamZoneMapsFinish: the derived planes, NaN where a labelled cell has no
+// onset -- behind the finalize pass.  Neither launches anything without a labelled tile
+void launchStreamZoneMaps(const ZoneMapArgs& a, const ZoneMapSpecSlice* slices, int nSlices, hipStream_t stream);
+void launchStreamZoneMapsFinish(const ZoneMapArgs& a, hipStream_t stream);
 
 // ---- pv_zone_band_decay.hip: per-zone ensemble decay curves per band
 // etc of one chunk of (zone, band) pairs -- zones a.zone0 + 1 .. a.zone0 + a.zones, bands a.band0 .. a.band0 + a.bands - 1 -- into

@@ -699,6 +699,7 @@ Solver::~Solver() {
     for (unsigned char* p : {zoneLabels_, zoneScratch_})
         if (p) hipFree(p);
     freeZoneCurves();
+    if (zoneMapTiles_) hipFree(zoneMapTiles_);
     for (RecordSet& r : recs_)
         if (r.host) hipHostFree(r.host);
     if (rqCellsHost_) hipHostFree(rqCellsHost_);
@@ -2273,6 +2274,17 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
         zc.nBlks = std::max(zoneBox_[3] - zoneBox_[2] + 1, 1);
     }
     zoneCurveRun_ = zoneCurvesOn_ ? zoneCurveSetting_ : 0;
+    // the zones' maps (setZoneMaps): every accumulate pass advances the labelled cells' sums in the kinds' own planes, the finish
+    // pass below derives the rest.  The bins are dealt as the spectrum's own passes deal them
+    ZoneMapArgs zm{};
+    std::vector<ZoneMapSpecSlice> zmSlices;
+    if (zoneMapKinds_) {
+        zm = zoneMapArgs(aa);
+        if (zm.spec)
+            for (const SpecPass& ps : specPasses_) zmSlices.push_back(ZoneMapSpecSlice{ps.bin0, ps.bins, ps.block, specTab_ + ps.tabOff});
+    }
+    zoneMapRun_[0] = (zoneMapKinds_ & kZoneMapRoomMetrics) ? zoneMapSetting_[0] : 0;
+    zoneMapRun_[1] = (zoneMapKinds_ & kZoneMapSpectrum) ? zoneMapSetting_[1] : 0;
     if (streamEv_[0] == nullptr)
         for (auto& e : streamEv_)
             if (!hipOk(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate")) return false;
@@ -2299,7 +2311,8 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
         hipStreamWaitEvent(stream2_, streamEv_[h], 0);
         aa.tA = tA;
         aa.tB = tA + n;
-        launchStreamAccum(aa, tileEmit_, tileOpen_, ntiles, stream2_, zoneCurvesOn_ ? &zc : nullptr, zoneCurveChunk_);
+        launchStreamAccum(aa, tileEmit_, tileOpen_, ntiles, stream2_, zoneCurvesOn_ ? &zc : nullptr, zoneCurveChunk_,
+                          zoneMapKinds_ ? &zm : nullptr, zmSlices.data(), (int)zmSlices.size());
         if (streamFuse_ && !fuseIdle_) launchStreamIdle(classifyArgs(baseStepArgs(true, true), 0, true), idleHost_ + h, stream2_);
         hipEventRecord(streamEv_[2 + h], stream2_);
     }
@@ -2307,6 +2320,17 @@ bool Solver::enqueueStreamingRun(float lx, float lz) {
     if (pass >= 2) hipStreamWaitEvent(stream_, streamEv_[3], 0);
     hipEventRecord(ev_[1], stream_);
     launchStreamFinalize(aa, stream_);
+    if (zoneMapKinds_) {
+        // (behind the two waits on accDone above, i.e. behind the last passes of either parity; the maps are this run's from here
+        // on -- zoneMapReadable tests the stamps and the run's end)
+        launchStreamZoneMapsFinish(zm, stream_);
+        for (AnalysisKind k : {kMapRoomMetrics, kMapSpectrum})
+            if (zoneMapKinds_ & (k == kMapRoomMetrics ? kZoneMapRoomMetrics : kZoneMapSpectrum)) {
+                maps_[k].dyn = dynCur_;
+                maps_[k].valid = true;
+                maps_[k].hostValid = false;
+            }
+    }
     hipEventRecord(ev_[2], stream_);
     lastRunBatched_ = false;
     streamedOnce_ = true;

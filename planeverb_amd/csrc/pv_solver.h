@@ -18,6 +18,7 @@
 #include "pv_device.h"
 #include "pv_query_spectral.h"
 #include "pv_zone_decay.h"
+#include "pv_zone_maps.h"
 
 namespace pva {
 
@@ -383,6 +384,16 @@ public:
     // the next run is refused
     bool setZoneCurves(bool on);
     bool zoneCurves() const;
+    // Sparse-emitter solvers, the per-cell maps of the zones (pv_zone_maps.hip): while a kind of setZoneMaps (kZoneMapRoomMetrics |
+    // kZoneMapSpectrum) is selected, every run accumulates that kind's record of every LABELLED cell inside the run, off the ring, in
+    // the kind's own map (maps_: planes x histPlane_ floats, 10 resp. 3 n planes; unlabelled cells quiet NaN) -- bit for bit what
+    // computeRoomMetrics / computeSpectrum give on a solver that keeps its history.  The read-backs of the two kinds and
+    // computeZoneStats of them then work on that map.  Needs zones (and bins for the spectrum); waits for a run in flight; allocates
+    // on select, frees on deselect; while a kind is selected the tiles that hold a labelled cell stay in the ring, as with the curves,
+    // and the zones (the bins) cannot be cleared.  A map carries the stamp of the run it was enqueued with: a read after
+    // setZoneMaps / setZones / setSpectrumBins and before the next run is refused
+    bool setZoneMaps(unsigned kinds);
+    unsigned zoneMaps() const;
     // Zone band decay (pv_zone_band_decay.hip; include/planeverb_amd.h PvAmdZoneBandDecay): the same curve per band of setBands,
     // off the band-filtered history -- out = nZones x nBands records, etc / edc (either may be nullptr) = nZones x nBands x T
     // doubles.  Nothing cached, no map, plan or run chain touched; the bands are read at the call; waits for a run in flight.
@@ -711,7 +722,21 @@ private:
     bool deriveZoneCurves();  // (everything below from zoneHost_ / zoneCount_; uploads the tile plane)
     bool disableZoneCurves();
     void freeZoneCurves();
-    bool uploadTileEmit();    // tileEmit_ = the emitters' tiles, united with the zones' while the curves are enabled
+    bool uploadTileEmit();    // tileEmit_ = the emitters' tiles, united with the zones' while the curves or a map kind are enabled
+    // the zones' tiles and box for whoever is enabled -- the curves or a map kind; cleared where neither is -- and the tile plane
+    // uploaded: setZones, setZoneCurves and setZoneMaps all come through here, so none drops another's tiles
+    bool rebuildZoneTiles();
+    // the map kinds (setZoneMaps): the storage is maps_[kMapRoomMetrics / kMapSpectrum].dev; the list of labelled tiles on the
+    // device; per kind (0: room metrics, 1: spectrum) a stamp as the curves': zoneMapSetting_ counts the changes of selection, labels
+    // or bins, zoneMapRun_ is its value when the last run was enqueued (0: that run accumulated no such map)
+    bool deriveZoneMaps(unsigned kinds);  // storage at the current plane counts, NaN everywhere, the tile list; bumps the stamps
+    void dropZoneMaps(unsigned kinds);    // the kinds' storage freed and their selection cleared
+    bool zoneMapReadable(AnalysisKind k);
+    ZoneMapArgs zoneMapArgs(const AnalyzeArgs& a) const;
+    unsigned zoneMapKinds_ = 0;
+    int* zoneMapTiles_ = nullptr;
+    int zoneMapTileCount_ = 0, zoneMapTileCap_ = 0;
+    unsigned long long zoneMapSetting_[2] = {0, 0}, zoneMapRun_[2] = {0, 0};
     bool zoneCurvesOn_ = false;
     double* zoneCurveEtc_ = nullptr;
     double* zoneCurveRows_ = nullptr;

@@ -116,6 +116,9 @@ int Solver::zoneStatPlanes(AnalysisKind k) const {
 
 bool Solver::analysisReadable(AnalysisKind k) {
     if (!analysisSettingPresent(k)) return fail(kAnalysisInfo[k].noSetting);
+    // (a sparse-emitter solver with the kind selected by setZoneMaps: the map is the last run's own, pv_solver_zones.cpp)
+    if (opt_.streaming && (zoneMapKinds_ & (k == kMapRoomMetrics ? kZoneMapRoomMetrics : k == kMapSpectrum ? kZoneMapSpectrum : 0u)))
+        return zoneMapReadable(k);
     if (!maps_[k].valid) return fail(kAnalysisInfo[k].notComputed);
     return true;
 }
@@ -446,6 +449,8 @@ bool Solver::setSpectrumBins(const float* hz, int n) {
     const auto inUse = queue_.lockUse();
     if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
+    if (n == 0 && (zoneMapKinds_ & kZoneMapSpectrum))
+        return fail("spectrum: the bins cannot be cleared while PVA_ZMAP_SPECTRUM is selected (PvAmdSetZoneMaps)");
     dropAnalysisMap(kMapSpectrum, n == 0);
     invalidateRecords(kRecSpectral, 1u << kQspecSpectrum);  // (the records in the pinned block are the old bins')
     for (float** p : {&specTab_, &specPow_})
@@ -493,6 +498,16 @@ bool Solver::setSpectrumBins(const float* hz, int n) {
     if (!ok) {  // (nothing half-set: no bins)
         specHz_.clear();
         specPasses_.clear();
+        if (zoneMapKinds_ & kZoneMapSpectrum) dropZoneMaps(kZoneMapSpectrum), rebuildZoneTiles();
+        return false;
+    }
+    // (sparse-emitter mode, the spectrum selected by setZoneMaps: the storage follows the bins, every record goes back to NaN, and the
+    // map of the last run is the old bins' and is refused until the next one)
+    if ((zoneMapKinds_ & kZoneMapSpectrum) && !deriveZoneMaps(kZoneMapSpectrum)) {
+        const std::string why = err_;
+        dropZoneMaps(kZoneMapSpectrum);
+        rebuildZoneTiles();
+        return fail(why);
     }
     return ok;
 }

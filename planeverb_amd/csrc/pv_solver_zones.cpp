@@ -27,6 +27,7 @@ bool Solver::setZones(const unsigned char* labels, int nZones) {
     if (pendingTimings_ && !sync()) return false;  // (a run in flight)
     if (nZones == 0) {
         if (zoneCurvesOn_) return fail("zone statistics: the zones cannot be cleared while the zone curves are enabled (PvAmdSetZoneCurves)");
+        if (zoneMapKinds_) return fail("zone statistics: the zones cannot be cleared while a zone map kind is selected (PvAmdSetZoneMaps)");
         zoneCount_ = 0;
         zoneHost_.clear();
         return true;
@@ -37,7 +38,9 @@ bool Solver::setZones(const unsigned char* labels, int nZones) {
         !hipOk(hipStreamSynchronize(stream_), "zone labels sync")) {
         zoneCount_ = 0;  // (the device labels are neither the old nor the new ones)
         zoneHost_.clear();
+        if (zoneMapKinds_) dropZoneMaps(zoneMapKinds_);
         if (zoneCurvesOn_) disableZoneCurves();
+        else rebuildZoneTiles();
         return false;
     }
     zoneHost_.assign(labels, labels + cells);
@@ -46,7 +49,16 @@ bool Solver::setZones(const unsigned char* labels, int nZones) {
     // are the old labels' and are refused until the next one)
     if (zoneCurvesOn_ && !deriveZoneCurves()) {
         const std::string why = err_;
+        if (zoneMapKinds_) dropZoneMaps(zoneMapKinds_);  // (nothing half-derived stays selected)
         disableZoneCurves();
+        return fail(why);
+    }
+    // (a selected map kind: the tiles and the tile list follow the labels too, every record goes back to NaN, and the maps of the last
+    // run are the old labels' and are refused until the next one)
+    if (zoneMapKinds_ && !(rebuildZoneTiles() && deriveZoneMaps(zoneMapKinds_))) {
+        const std::string why = err_;
+        dropZoneMaps(zoneMapKinds_);
+        rebuildZoneTiles();
         return fail(why);
     }
     return true;
@@ -63,22 +75,50 @@ void Solver::freeZoneCurves() {
 bool Solver::disableZoneCurves() {
     zoneCurvesOn_ = false;
     ++zoneCurveSetting_;
-    zoneTilesHost_.clear();
     freeZoneCurves();
-    return uploadTileEmit() && hipOk(hipStreamSynchronize(stream_), "tile plane upload");
+    return rebuildZoneTiles();
+}
+
+// (no run in flight) the tiles that hold a labelled cell, for the curves or a map kind -- whoever is enabled -- and the tile plane
+bool Solver::rebuildZoneTiles() {
+    zoneTilesHost_.clear();
+    zoneBox_[0] = 0, zoneBox_[1] = -1, zoneBox_[2] = 0, zoneBox_[3] = -1;
+    std::vector<int> list;
+    if ((zoneCurvesOn_ || zoneMapKinds_) && zoneCount_) {
+        const int ntx = (g_.gx + rxi_ - 1) / rxi_, nty = (g_.gy + wi_ - 1) / wi_;
+        if (ntx > geo_.ntx || nty > geo_.nty) return fail("the result map reaches past the tile grid");
+        std::vector<unsigned char> flags((size_t)ntx * nty);
+        const ZoneTileBox b = zoneTileFlags(zoneHost_.data(), g_.gx, g_.gy, rxi_, wi_, flags.data());
+        zoneTilesHost_.assign((size_t)geo_.ntx * geo_.nty, 0);
+        for (int ti = 0; ti < ntx; ++ti)
+            for (int tj = 0; tj < nty; ++tj)
+                if ((zoneTilesHost_[(size_t)ti * geo_.nty + tj] = flags[(size_t)ti * nty + tj]) != 0) list.push_back(ti * geo_.nty + tj);
+        zoneBox_[0] = b.row0, zoneBox_[1] = b.row1, zoneBox_[2] = b.blk0, zoneBox_[3] = b.blk1;
+    }
+    // the map kinds walk the list of those tiles on the device
+    zoneMapTileCount_ = 0;
+    if (zoneMapKinds_ && !list.empty()) {
+        if ((int)list.size() > zoneMapTileCap_) {
+            if (zoneMapTiles_) hipFree(zoneMapTiles_), deviceBytes_ -= (long long)zoneMapTileCap_ * (long long)sizeof(int);
+            zoneMapTiles_ = nullptr;
+            zoneMapTileCap_ = 0;
+            if (!dalloc(&zoneMapTiles_, list.size(), false)) return false;
+            zoneMapTileCap_ = (int)list.size();
+        }
+        if (!hipOk(hipMemcpyAsync(zoneMapTiles_, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice, stream_), "zone tile list")) return false;
+        zoneMapTileCount_ = (int)list.size();
+    } else if (!zoneMapKinds_ && zoneMapTiles_) {
+        hipFree(zoneMapTiles_), deviceBytes_ -= (long long)zoneMapTileCap_ * (long long)sizeof(int);
+        zoneMapTiles_ = nullptr;
+        zoneMapTileCap_ = 0;
+    }
+    return uploadTileEmit() && hipOk(hipStreamSynchronize(stream_), "tile plane upload");  // (the list above is a local: copied by now)
 }
 
 bool Solver::deriveZoneCurves() {
     ++zoneCurveSetting_;
-    const int ntx = (g_.gx + rxi_ - 1) / rxi_, nty = (g_.gy + wi_ - 1) / wi_;
-    if (ntx > geo_.ntx || nty > geo_.nty) return fail("the result map reaches past the tile grid");
-    std::vector<unsigned char> flags((size_t)ntx * nty);
-    const ZoneTileBox b = zoneTileFlags(zoneHost_.data(), g_.gx, g_.gy, rxi_, wi_, flags.data());
-    zoneTilesHost_.assign((size_t)geo_.ntx * geo_.nty, 0);
-    for (int ti = 0; ti < ntx; ++ti)
-        for (int tj = 0; tj < nty; ++tj) zoneTilesHost_[(size_t)ti * geo_.nty + tj] = flags[(size_t)ti * nty + tj];
-    zoneBox_[0] = b.row0, zoneBox_[1] = b.row1, zoneBox_[2] = b.blk0, zoneBox_[3] = b.blk1;
-    const int rows = std::max(b.row1 - b.row0 + 1, 1);
+    if (!rebuildZoneTiles()) return false;
+    const int rows = std::max(zoneBox_[1] - zoneBox_[0] + 1, 1);
     // the steps of a pass per pair of launches; a pass has halfRing_ of them at the most
     zoneCurveChunk_ = std::min(streamZoneCurveChunk(zoneCount_, rows, kZoneScratchBytes),
                                (halfRing_ + kZoneCurveSlots - 1) / kZoneCurveSlots * kZoneCurveSlots);
@@ -91,7 +131,7 @@ bool Solver::deriveZoneCurves() {
         if (!dalloc(&zoneCurveRows_, rowsBytes / sizeof(double), false)) return false;
         zoneCurveRowsBytes_ = rowsBytes;
     }
-    return uploadTileEmit() && hipOk(hipStreamSynchronize(stream_), "tile plane upload");
+    return true;
 }
 
 bool Solver::setZoneCurves(bool on) {
@@ -115,6 +155,124 @@ bool Solver::setZoneCurves(bool on) {
 bool Solver::zoneCurves() const {
     const auto inUse = queue_.lockUse();
     return zoneCurvesOn_;
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// the zones' per-cell maps inside a sparse-emitter run (pv_zone_maps.hip)
+// ----------------------------------------------------------------------------------------------------------------
+
+namespace {
+constexpr AnalysisKind kZoneMapKindOf[2] = {kMapRoomMetrics, kMapSpectrum};
+}
+
+// (no run in flight) the storage of `kinds` at the current plane counts and quiet NaN in every plane of it: a run writes the labelled
+// cells only, and writes every one of them.  The maps of the last run are no longer the current setting's
+bool Solver::deriveZoneMaps(unsigned kinds) {
+    for (int i = 0; i < 2; ++i) {
+        if (!(kinds & (1u << i))) continue;
+        const AnalysisKind k = kZoneMapKindOf[i];
+        const int planes = zoneStatPlanes(k);
+        if (planes < 1) return fail(std::string("zone maps: ") + (i ? "no bins set (PvAmdSetSpectrumBins)" : "no planes"));
+        ++zoneMapSetting_[i];
+        AnalysisMap& m = maps_[k];
+        m.valid = m.hostValid = false;
+        if (m.dev && m.planes != planes) {
+            hipFree(m.dev);
+            deviceBytes_ -= (long long)m.planes * histPlane_ * 4;
+            m.dev = nullptr;
+            m.planes = 0;
+        }
+        if (!m.dev) {
+            if (!dalloc(&m.dev, (size_t)planes * (size_t)histPlane_, false)) return false;
+            m.planes = planes;
+        }
+        if (!hipOk(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(m.dev), 0x7fc00000, (size_t)planes * (size_t)histPlane_, stream_), "zone map fill"))
+            return false;
+    }
+    return hipOk(hipStreamSynchronize(stream_), "zone map fill");
+}
+
+void Solver::dropZoneMaps(unsigned kinds) {
+    for (int i = 0; i < 2; ++i) {
+        if (!(kinds & zoneMapKinds_ & (1u << i))) continue;
+        AnalysisMap& m = maps_[kZoneMapKindOf[i]];
+        if (m.dev) hipFree(m.dev), deviceBytes_ -= (long long)m.planes * histPlane_ * 4;
+        m.dev = nullptr;
+        m.planes = 0;
+        m.valid = m.hostValid = false;
+        std::vector<float>().swap(m.host);
+        ++zoneMapSetting_[i];
+    }
+    zoneMapKinds_ &= ~kinds;
+}
+
+bool Solver::setZoneMaps(unsigned kinds) {
+    if (kinds & ~(kZoneMapRoomMetrics | kZoneMapSpectrum)) return fail("zone maps: kinds is a combination of PVA_ZMAP_ROOM_METRICS and PVA_ZMAP_SPECTRUM");
+    if (!opt_.streaming)
+        return fail("zone maps: sparse-emitter solvers only (PVA_OPT_STREAMING_ANALYSIS): a solver that keeps its history computes the maps after the run "
+                    "(PvAmdComputeRoomMetrics, PvAmdComputeSpectrum)");
+    if (isSlab()) return fail("zone maps: not available on a slab");
+    if (opt_.skipAnalysis) return fail("zone maps: the run has no onset map (PVA_OPT_SKIP_ANALYSIS)");
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight reads the tile plane and writes the maps)
+    if (kinds && !zoneCount_) return fail("zone maps: no zones set (PvAmdSetZones)");
+    if ((kinds & kZoneMapSpectrum) && specHz_.empty()) return fail("zone maps: PVA_ZMAP_SPECTRUM: no bins set (PvAmdSetSpectrumBins)");
+    if (kinds == zoneMapKinds_) return true;
+    const unsigned fresh = kinds & ~zoneMapKinds_;
+    dropZoneMaps(zoneMapKinds_ & ~kinds);
+    zoneMapKinds_ = kinds;
+    if (!(rebuildZoneTiles() && deriveZoneMaps(fresh))) {
+        const std::string why = err_;
+        dropZoneMaps(fresh);
+        rebuildZoneTiles();
+        return fail(why.rfind("zone maps: ", 0) == 0 ? why : "zone maps: " + why);
+    }
+    return true;
+}
+
+unsigned Solver::zoneMaps() const {
+    const auto inUse = queue_.lockUse();
+    return zoneMapKinds_;
+}
+
+// a read of kind k's map on a sparse-emitter solver that has the kind selected: the run in flight waited for, then the refusals
+bool Solver::zoneMapReadable(AnalysisKind k) {
+    const int i = k == kMapSpectrum ? 1 : 0;
+    const auto inUse = queue_.lockUse();
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    if (pendingTimings_ && !sync()) return false;  // (a run in flight; one that ends in error leaves its message)
+    std::string pre(k == kMapSpectrum ? "spectrum: " : "room metrics: ");
+    if (const char* why = zoneRunRefusal()) return fail(pre + why);
+    if (zoneMapRun_[i] != zoneMapSetting_[i])
+        return fail(pre + "the last run was enqueued before the kind was selected (PvAmdSetZoneMaps) or before the current zones or bins were set");
+    if (!maps_[k].valid) return fail(pre + "not accumulated for the last run and the current geometry");
+    return true;
+}
+
+ZoneMapArgs Solver::zoneMapArgs(const AnalyzeArgs& a) const {
+    ZoneMapArgs z{};
+    z.hist = a.hist;
+    z.histPlane = a.histPlane;
+    z.onset = sOnset_;
+    z.labels = zoneLabels_;
+    z.dyn = a.dyn;
+    z.tiles = zoneMapTiles_;
+    z.nTiles = zoneMapTileCount_;
+    z.gx = g_.gx;
+    z.gy = g_.gy;
+    z.G = geo_.G;
+    z.rxi = rxi_;
+    z.wi = wi_;
+    z.nty = geo_.nty;
+    z.ring = ring_;
+    z.T = T_;
+    z.fs = (int)g_.fs;
+    z.room = (zoneMapKinds_ & kZoneMapRoomMetrics) ? maps_[kMapRoomMetrics].dev : nullptr;
+    z.spec = (zoneMapKinds_ & kZoneMapSpectrum) ? maps_[kMapSpectrum].dev : nullptr;
+    z.nBins = (int)specHz_.size();
+    z.specPow = specPow_;
+    return z;
 }
 
 int Solver::zones(unsigned char* labels) const {
@@ -253,7 +411,10 @@ bool Solver::endZoneCurves(ZonePass& p, size_t curves, double** etc, float* ms) 
 
 bool Solver::computeZoneStats(AnalysisKind k, void* out, int cap, float* ms, int* count) {
     ZonePass p;
-    if (!beginZonePass(&p, "zone statistics", kZoneNeedsHistory)) return false;
+    // (a sparse-emitter solver has a map of the two kinds of setZoneMaps while they are selected, and no other)
+    const auto pre = queue_.lockUse();
+    const unsigned bit = k == kMapRoomMetrics ? kZoneMapRoomMetrics : k == kMapSpectrum ? kZoneMapSpectrum : 0u;
+    if (!beginZonePass(&p, "zone statistics", (opt_.streaming && (zoneMapKinds_ & bit)) ? 0u : kZoneNeedsHistory)) return false;
     const AnalysisMap& m = maps_[k];
     // (neither the run nor the onset map is tested here: analysisReadable refuses where the kind has no valid map)
     if (!zoneCount_) return zoneRefuse(p, "no zones set (PvAmdSetZones)");

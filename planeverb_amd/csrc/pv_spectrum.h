@@ -46,17 +46,34 @@ inline void spectrumTables(int T, int fs, const float* hz, int n, float* c, floa
         }
 }
 
+// one sample of the definition: what p = p(t) adds to a bin's two sums, c and s the bin's table values at the same step t.  The
+// walk below and the in-run accumulate pass of sparse-emitter mode (pv_zone_maps.hip) are both this text
+PV_HD inline void spectrumStep(float p, float c, float s, float& re, float& im) {
+    const float pc = p * c;
+    const float ps = p * s;
+    re = re + pc;
+    im = im + ps;
+}
+
 // the two sums of bin j over p[onset .. T - 1]
 inline void spectrumSums(const float* p, int T, int onset, const float* c, const float* s, int n, int j, float* re, float* im) {
     float r = 0.f, i = 0.f;
-    for (int t = onset; t < T; ++t) {
-        const float pc = p[t] * c[(size_t)t * n + j];
-        const float ps = p[t] * s[(size_t)t * n + j];
-        r = r + pc;
-        i = i + ps;
-    }
+    for (int t = onset; t < T; ++t) spectrumStep(p[t], c[(size_t)t * n + j], s[(size_t)t * n + j], r, i);
     *re = r;
     *im = i;
+}
+
+// The sums of all n bins carried over the steps [max(tA, onset), min(tB, T)) of one accumulate pass [tA, tB) -- reim2n = re, im of
+// bin j at 2 j, 2 j + 1: a cell whose onset lies in the pass (onset >= tA) starts from +0.0f and never reads them
+inline void spectrumAdvance(const float* p, int T, int onset, int tA, int tB, const float* c, const float* s, int n, float* reim2n) {
+    const int tEnd = tB < T ? tB : T;
+    if (onset < 0 || onset >= tEnd) return;
+    for (int j = 0; j < n; ++j) {
+        float r = onset >= tA ? 0.f : reim2n[2 * j], i = onset >= tA ? 0.f : reim2n[2 * j + 1];
+        for (int t = onset > tA ? onset : tA; t < tEnd; ++t) spectrumStep(p[t], c[(size_t)t * n + j], s[(size_t)t * n + j], r, i);
+        reim2n[2 * j] = r;
+        reim2n[2 * j + 1] = i;
+    }
 }
 
 PV_HD inline float spectrumPower(float re, float im) { return (re * re) + (im * im); }
