@@ -105,6 +105,16 @@ PVA_EXPORT void PlaneverbRemoveWallPathGeometry(int id);
 PVA_EXPORT int PlaneverbAddConcavePolygonGeometry(const float* xy, int n, float absorption);
 PVA_EXPORT void PlaneverbUpdateConcavePolygonGeometry(int id, const float* xy, int n, float absorption);
 PVA_EXPORT void PlaneverbRemoveConcavePolygonGeometry(int id);
+/* Triangle meshes, the model of PvAmdAddMesh below (slice, coverage, composition, refusals), in an id table of their own.  The
+ * vertex data is copied into a store the module owns at the Add call, which may fail cleanly with -1 (PvAmdLastError); the
+ * changes are queued with the others and applied at the iteration boundary in call order, to both live solvers.
+ * PlaneverbSetSliceHeight sets the world height of the slice (0 at Init): a Unity caller passes the listener's y; the module does
+ * not follow the listener by itself.  A non-finite height or transform entry is ignored (PvAmdLastError says so). */
+PVA_EXPORT int PlaneverbAddMeshGeometry(const float* verts, int nv, const int* tris, int nt, float absorption, int mode,
+                                        float radius);
+PVA_EXPORT void PlaneverbSetMeshGeometryTransform(int id, const float m12[12]);
+PVA_EXPORT void PlaneverbRemoveMeshGeometry(int id);
+PVA_EXPORT void PlaneverbSetSliceHeight(float h);
 /* Extension: the absorption of the four grid edges (PvAmdSetGridBoundary: xMin = side 0, xMax = 1, zMin = 2, zMax = 3), queued
  * like the geometry calls and applied to both live solvers at the same iteration boundary.  A non-finite value is refused
  * (nothing changes; PvAmdLastError says why). */
@@ -407,6 +417,65 @@ PVA_EXPORT int PvAmdAddWallPath(PvAmdSolver* s, const float* xy, int n, float ra
 PVA_EXPORT int PvAmdUpdateWallPath(PvAmdSolver* s, int id, const float* xy, int n, float radius, float absorption);
 PVA_EXPORT int PvAmdAddPolygon(PvAmdSolver* s, const float* xy, int n, float absorption);
 PVA_EXPORT int PvAmdUpdatePolygon(PvAmdSolver* s, int id, const float* xy, int n, float absorption);
+/* Triangle meshes (no reference counterpart: the reference adds a collider's bounding box while the listener's height lies
+ * inside it).  The grid is a horizontal slice of a 3-D world; a mesh stays on the device and is sliced at the solver's slice
+ * height h, and the section is rasterised there, in a layer of its own BETWEEN the AABB layer and the shape layer.  Everything
+ * below is float32 without contraction, in the order the brackets give.
+ *
+ * Mesh: nv vertices (x, y, z) in world units, y = height, grid x = world x and grid y = world z as for the AABBs; nt triangles
+ *   of three int32 indices; an absorption value, taken as PvAmdAddGeometry takes it; a mode, PVA_MESH_SOLID or PVA_MESH_SHELL;
+ *   in shell mode a radius r, half the wall's thickness (ignored in solid mode).  An optional affine transform m[12],
+ *   row-major 3 x 4: world = ((m0*x + m1*y) + m2*z) + m3 per row.  A mesh without a transform call has none: its vertices are
+ *   used as they are, bit for bit.  At most PVA_MESH_MAX live meshes, PVA_MESH_MAX_TRIS triangles per mesh and
+ *   PVA_MESH_MAX_TRIS_TOTAL over all meshes of a solver.
+ * Slice: one height h per solver, 0 by default (PvAmdSetSliceHeight).  A vertex is ABOVE when v.y > h, strictly: a vertex on
+ *   the plane is not above.  A triangle whose three vertices agree gives no segment.  Otherwise exactly two of its edges, in
+ *   the order (v0,v1), (v1,v2), (v2,v0), have ends that disagree; for each, p = the end that is not above and q = the end
+ *   above, whichever way the triangle lists them (so two triangles that share an edge compute the same bits):
+ *   t = (h - p.y) / (q.y - p.y), X = p.x + (t * (q.x - p.x)), Z = p.z + (t * (q.z - p.z)).  The triangle's segment is a -> b,
+ *   a from the first such edge and b from the second, in grid coordinates (X, Z).  A face lying exactly in the plane yields no
+ *   segment in either mode: its neighbours' sections outline it.
+ * Coverage (P = the cell centre of the rules above; the ghost row and column are never covered):
+ *   Solid: even-odd crossings over the mesh's segments by the edge rule of PvAmdAddPolygon, word for word: a segment toggles
+ *   the cell when (a.y > P.y) != (b.y > P.y) and P.x < (((b.x - a.x) * (P.y - a.y)) / (b.y - a.y)) + a.x; covered after an odd
+ *   number of toggles.  A section with a hole is an annulus: the one kind here that expresses holes.
+ *   Shell: covered when the capsule rule of PvAmdAddCapsule with radius r covers the cell for any segment (ee == 0, a disc,
+ *   included: a segment with a == b can arise).
+ * Composition: the AABB layer, overwritten by the mesh layer -- among meshes the one added or updated most recently wins, and
+ *   PvAmdSetMeshTransform counts as an update -- overwritten by the shape layer.  Each layer is a pure function of its current
+ *   set and h.  Mesh ids are a table of their own, recycled last-in first-out.  A solver that never has a mesh runs exactly
+ *   as before.
+ * Refused (-1, PvAmdLastError, the tables unchanged): a non-finite vertex, transform entry, h, absorption or (shell) radius; in
+ *   shell mode r <= 0 or an r whose float32 square is 0 or infinite; an index outside [0, nv); nt < 1 or a count over the
+ *   limits; a triangle with two equal indices; in solid mode a mesh in which some undirected edge is not shared by exactly two
+ *   triangles (checked on the host when the mesh is added: it is what makes the parity fill well defined; the same open mesh
+ *   is accepted in shell mode).  Slab groups and slab ranks refuse meshes.  The .pv scene format holds boxes only.
+ * PvAmdCopyMeshSection: the segments as the device sliced them at the current h and transform, out4nt[4 i ..] = (a.x, a.z,
+ *   b.x, b.z) and valid_nt[i] = 1, or zeros and 0 for a triangle without one; slot i belongs to triangle i (no compaction), so
+ *   the result is deterministic.  Either array may be NULL. */
+#define PVA_MESH_SOLID 0
+#define PVA_MESH_SHELL 1
+#define PVA_MESH_MAX 64
+#define PVA_MESH_MAX_TRIS (1 << 20)
+#define PVA_MESH_MAX_TRIS_TOTAL (1 << 22)
+PVA_EXPORT int PvAmdAddMesh(PvAmdSolver* s, const float* verts, int nv, const int* tris, int nt, float absorption, int mode,
+                            float radius);
+PVA_EXPORT int PvAmdUpdateMesh(PvAmdSolver* s, int id, const float* verts, int nv, const int* tris, int nt, float absorption,
+                               int mode, float radius);
+PVA_EXPORT int PvAmdSetMeshTransform(PvAmdSolver* s, int id, const float m12[12]);
+PVA_EXPORT int PvAmdRemoveMesh(PvAmdSolver* s, int id);
+PVA_EXPORT int PvAmdSetSliceHeight(PvAmdSolver* s, float h);
+PVA_EXPORT float PvAmdGetSliceHeight(PvAmdSolver* s);
+PVA_EXPORT int PvAmdMeshTriangles(PvAmdSolver* s, int id); /* nt of a live mesh, -1 otherwise */
+PVA_EXPORT int PvAmdCopyMeshSection(PvAmdSolver* s, int id, float* out4nt, uint8_t* valid_nt);
+/* The same rules on the CPU, without a device.  PvAmdHostMeshSection: the section of triangles that need not form a valid
+ * mesh (indices inside [0, nv) and finite inputs are still required); m12_or_null = NULL: no transform.
+ * PvAmdHostMeshCoverage: cover[NX * NY], index x * NY + y, 0 / 1, of one mesh (validated as PvAmdAddMesh validates it). */
+PVA_EXPORT int PvAmdHostMeshSection(const float* verts, int nv, const int* tris, int nt, const float* m12_or_null, float h,
+                                    float* out4nt, uint8_t* valid_nt);
+PVA_EXPORT int PvAmdHostMeshCoverage(float gridSizeX, float gridSizeY, int gridResolution, const float* verts, int nv,
+                                     const int* tris, int nt, const float* m12_or_null, float h, int mode, float radius,
+                                     uint8_t* cover);
 /* Grid edges.  absorption4 = R of the sides 0: faces at x = 0 (world x = 0), 1: faces at x = gx, 2: faces at y = 0 (world
  * z = 0), 3: faces at y = gy, taken as PvAmdAddGeometry takes absorption (any finite value); the admittance of side k is
  * Y = (1 - R) / (1 + R) in float32.  The edge faces are the reference's absorbing edges (FDTD.cpp:201-223) with Y in place of

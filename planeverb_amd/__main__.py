@@ -135,6 +135,21 @@ def live_emission_records(size, res, boxes, listener, emitters, echogram, lobes,
         api.Exit()
 
 
+def mesh_setting(v):
+    """FILE.npz[,absorption[,shell:r]] -> (path, absorption, mode, radius)"""
+    parts = v.split(",")
+    try:
+        absorption = float(parts[1]) if len(parts) > 1 else 0.5
+        mode, radius = api.MESH_SOLID, 0.0
+        if len(parts) > 2:
+            if not parts[2].startswith("shell:") or len(parts) > 3:
+                raise ValueError
+            mode, radius = api.MESH_SHELL, float(parts[2][6:])
+    except ValueError:
+        raise argparse.ArgumentTypeError("expected FILE.npz[,absorption[,shell:r]]")
+    return parts[0], absorption, mode, radius
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m planeverb_amd", description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -202,6 +217,12 @@ def main(argv=None):
                     help="with --zone-decay and --bands: add per zone a zoneBandDecay list, one entry per band -- the ensemble decay "
                          "curve of the band-filtered responses, reduced on the GPU in the alignment of --zone-decay: EDT, T20, T30, "
                          "depth, the point counts and the curve's C50, C80, D50 and Ts (with --zone-decay-curves: etc and edc too)")
+    ap.add_argument("--mesh", metavar="FILE.npz[,ABSORPTION[,shell:R]]", type=mesh_setting, action="append", default=[],
+                    help="a triangle mesh on top of the scene's boxes, repeatable: an .npz with `vertices` (nv x 3 world x, y, z; y is "
+                         "the height) and `triangles` (nt x 3 indices), sliced at --slice-height and rasterised on the GPU; solid "
+                         "(the section is filled, holes included; the mesh must be closed) unless shell:R is given (cells within "
+                         "R metres of the section).  Absorption as in a .pv box, default 0.5")
+    ap.add_argument("--slice-height", type=float, default=0.0, help="world height at which the meshes are sliced, default 0")
     ap.add_argument("--save", help="write the loaded boxes back as a .pv file and exit (no GPU needed)")
     a = ap.parse_args(argv)
 
@@ -240,6 +261,10 @@ def main(argv=None):
     with api.Solver(size, size, a.res, device=a.device, **(dict(streaming_analysis=1) if a.sparse_emitters else {})) as s:
         for b in boxes:
             s.add_geometry(b)
+        s.set_slice_height(a.slice_height)
+        for path, absorption, mode, radius in a.mesh:
+            with np.load(path) as f:
+                s.add_mesh(f["vertices"], f["triangles"], absorption, mode, radius)
         # the record kinds from whole-map passes after the run, or from inside the run
         whole = not (a.in_run_records or a.sparse_emitters)
         if not whole:

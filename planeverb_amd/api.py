@@ -176,6 +176,10 @@ SYMBOLS = {
     "PlaneverbAddConcavePolygonGeometry": (C.c_int, [_fp, C.c_int, C.c_float]),
     "PlaneverbUpdateConcavePolygonGeometry": (None, [C.c_int, _fp, C.c_int, C.c_float]),
     "PlaneverbRemoveConcavePolygonGeometry": (None, [C.c_int]),
+    "PlaneverbAddMeshGeometry": (C.c_int, [_fp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_float]),
+    "PlaneverbSetMeshGeometryTransform": (None, [C.c_int, _fp]),
+    "PlaneverbRemoveMeshGeometry": (None, [C.c_int]),
+    "PlaneverbSetSliceHeight": (None, [C.c_float]),
     "PlaneverbLoadScene": (C.c_int, [C.c_char_p]),
     "PlaneverbIterationCount": (C.c_longlong, []),
     "PlaneverbWaitIterations": (C.c_longlong, [C.c_longlong, C.c_int]),
@@ -239,6 +243,17 @@ SYMBOLS = {
     "PvAmdUpdateWallPath": (C.c_int, [_vp, C.c_int, _fp, C.c_int, C.c_float, C.c_float]),
     "PvAmdAddPolygon": (C.c_int, [_vp, _fp, C.c_int, C.c_float]),
     "PvAmdUpdatePolygon": (C.c_int, [_vp, C.c_int, _fp, C.c_int, C.c_float]),
+    "PvAmdAddMesh": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_float]),
+    "PvAmdUpdateMesh": (C.c_int, [_vp, C.c_int, _fp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_float, C.c_int, C.c_float]),
+    "PvAmdSetMeshTransform": (C.c_int, [_vp, C.c_int, _fp]),
+    "PvAmdRemoveMesh": (C.c_int, [_vp, C.c_int]),
+    "PvAmdSetSliceHeight": (C.c_int, [_vp, C.c_float]),
+    "PvAmdGetSliceHeight": (C.c_float, [_vp]),
+    "PvAmdMeshTriangles": (C.c_int, [_vp, C.c_int]),
+    "PvAmdCopyMeshSection": (C.c_int, [_vp, C.c_int, _fp, C.POINTER(C.c_ubyte)]),
+    "PvAmdHostMeshSection": (C.c_int, [_fp, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, C.c_float, _fp, C.POINTER(C.c_ubyte)]),
+    "PvAmdHostMeshCoverage": (C.c_int, [C.c_float, C.c_float, C.c_int, _fp, C.c_int, C.POINTER(C.c_int), C.c_int, _fp, C.c_float,
+                                        C.c_int, C.c_float, C.POINTER(C.c_ubyte)]),
     "PvAmdSetGridBoundary": (C.c_int, [_vp, _fp]),
     "PvAmdGetGridBoundary": (C.c_int, [_vp, _fp]),
     "PlaneverbSetGridBoundary": (None, [C.c_float] * 4),
@@ -602,6 +617,26 @@ def RemoveConcavePolygonGeometry(sid):
     lib().PlaneverbRemoveConcavePolygonGeometry(int(sid))
 
 
+def AddMeshGeometry(vertices, triangles, absorption, mode=0, radius=0.0):
+    """a triangle mesh (Solver.add_mesh), copied into the module's store at this call (mesh ids); -1 if refused"""
+    v, t, tp = _mesh(vertices, triangles)
+    return lib().PlaneverbAddMeshGeometry(_f(v), v.shape[0], tp, t.shape[0], float(absorption), int(mode), float(radius))
+
+
+def SetMeshGeometryTransform(mid, transform):
+    m, mp = _m12(transform)
+    lib().PlaneverbSetMeshGeometryTransform(int(mid), mp)
+
+
+def RemoveMeshGeometry(mid):
+    lib().PlaneverbRemoveMeshGeometry(int(mid))
+
+
+def SetSliceHeight(h):
+    """the world height at which the meshes are sliced, applied at the next iteration boundary (pass the listener's y)"""
+    lib().PlaneverbSetSliceHeight(float(h))
+
+
 def SetGridBoundary(xmin, xmax, zmin, zmax):
     """absorption of the four grid edges (Solver.set_grid_boundary), applied at the next iteration boundary"""
     lib().PlaneverbSetGridBoundary(float(xmin), float(xmax), float(zmin), float(zmax))
@@ -757,6 +792,51 @@ def host_coverage(size_x, size_y, res, kind, points, radius=0.0):
     cover = np.empty((g.gx + 1, g.gy + 1), np.uint8)
     _check(lib().PvAmdHostRoundShapeCoverage(float(size_x), float(size_y), int(res), int(kind), _f(a), n, float(radius),
                                              cover.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return cover
+
+
+MESH_SOLID, MESH_SHELL = 0, 1
+MESH_MAX, MESH_MAX_TRIS, MESH_MAX_TRIS_TOTAL = 64, 1 << 20, 1 << 22
+
+
+def _mesh(vertices, triangles):
+    v = np.ascontiguousarray(vertices, np.float32)
+    t = np.ascontiguousarray(triangles, np.int32)
+    if v.ndim != 2 or v.shape[1] != 3 or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("a mesh is nv x 3 vertices (x, y, z) and nt x 3 triangle indices")
+    return v, t, t.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _m12(transform):
+    if transform is None:
+        return None, None
+    m = np.ascontiguousarray(transform, np.float32).reshape(-1)
+    if m.size != 12:
+        raise ValueError("a mesh transform is 3 x 4, row-major")
+    return m, _f(m)
+
+
+def host_mesh_section(vertices, triangles, h=0.0, transform=None):
+    """the section of every triangle at height h, as the library slices it: (segments nt x 4 float32 (a.x, a.z, b.x, b.z),
+    valid nt uint8); transform: 3 x 4 row-major or None"""
+    v, t, tp = _mesh(vertices, triangles)
+    m, mp = _m12(transform)
+    seg = np.empty((t.shape[0], 4), np.float32)
+    valid = np.empty(t.shape[0], np.uint8)
+    _check(lib().PvAmdHostMeshSection(_f(v), v.shape[0], tp, t.shape[0], mp, float(h), _f(seg),
+                                      valid.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return seg, valid
+
+
+def host_mesh_coverage(size_x, size_y, res, vertices, triangles, h=0.0, mode=MESH_SOLID, radius=0.0, transform=None):
+    """the cells (gx+1) x (gy+1) a mesh covers at slice height h on a grid of that configuration (uint8), on the CPU;
+    PlaneverbError if the mesh is refused"""
+    v, t, tp = _mesh(vertices, triangles)
+    m, mp = _m12(transform)
+    g = host_grid_info(size_x, size_y, res)
+    cover = np.empty((g.gx + 1, g.gy + 1), np.uint8)
+    _check(lib().PvAmdHostMeshCoverage(float(size_x), float(size_y), int(res), _f(v), v.shape[0], tp, t.shape[0], mp, float(h),
+                                       int(mode), float(radius), cover.ctypes.data_as(C.POINTER(C.c_ubyte))))
     return cover
 
 
@@ -1728,6 +1808,45 @@ class Solver:
 
     def remove_shape(self, sid):
         _check(lib().PvAmdRemoveShape(self._h, int(sid)))
+
+    def add_mesh(self, vertices, triangles, absorption, mode=MESH_SOLID, radius=0.0):
+        """a triangle mesh (nv x 3 world (x, y, z), y = height; nt x 3 indices), kept on the device and sliced at the solver's
+        slice height: MESH_SOLID fills the section (even-odd, holes included), MESH_SHELL covers within radius of it.  Returns
+        the mesh id (a table of its own; PlaneverbError if refused)"""
+        v, t, tp = _mesh(vertices, triangles)
+        return self._added(lib().PvAmdAddMesh(self._h, _f(v), v.shape[0], tp, t.shape[0], float(absorption), int(mode),
+                                              float(radius)))
+
+    def update_mesh(self, mid, vertices, triangles, absorption, mode=MESH_SOLID, radius=0.0):
+        v, t, tp = _mesh(vertices, triangles)
+        _check(lib().PvAmdUpdateMesh(self._h, int(mid), _f(v), v.shape[0], tp, t.shape[0], float(absorption), int(mode),
+                                     float(radius)))
+
+    def set_mesh_transform(self, mid, transform):
+        """3 x 4 row-major affine transform of the mesh's vertices; counts as an update (the mesh becomes the most recent)"""
+        m, mp = _m12(np.eye(3, 4) if transform is None else transform)
+        _check(lib().PvAmdSetMeshTransform(self._h, int(mid), mp))
+
+    def remove_mesh(self, mid):
+        _check(lib().PvAmdRemoveMesh(self._h, int(mid)))
+
+    def set_slice_height(self, h):
+        """the world height at which every mesh is sliced (0 by default); a change re-slices them at the next run"""
+        _check(lib().PvAmdSetSliceHeight(self._h, float(h)))
+
+    @property
+    def slice_height(self):
+        return float(lib().PvAmdGetSliceHeight(self._h))
+
+    def mesh_section(self, mid):
+        """the mesh's section as the device sliced it: (segments nt x 4 float32 (a.x, a.z, b.x, b.z), valid nt uint8)"""
+        nt = lib().PvAmdMeshTriangles(self._h, int(mid))
+        if nt < 0:
+            raise PlaneverbError("invalid mesh id")
+        seg = np.empty((nt, 4), np.float32)
+        valid = np.empty(nt, np.uint8)
+        _check(lib().PvAmdCopyMeshSection(self._h, int(mid), _f(seg), valid.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return seg, valid
 
     def set_grid_boundary(self, r4):
         """absorption R of the grid edges x = 0, x = gx, y = 0 (world z = 0), y = gy, as add_geometry takes it: 0 = absorbing

@@ -2,6 +2,7 @@
 // No C++ exception leaves this file; the reference's sentinels are kept (-1 ids, occlusion = -1).
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -345,6 +346,32 @@ void PlaneverbUpdateConcavePolygonGeometry(int id, const float* xy, int n, float
 void PlaneverbRemoveConcavePolygonGeometry(int id) try {
     Context::Ref c;
     if (c) c->removeShape(id);
+} PV_API_CATCH_VOID
+
+// triangle meshes (pv_context.h): validated here, the vertex data copied into the context's store at the Add call
+int PlaneverbAddMeshGeometry(const float* verts, int nv, const int* tris, int nt, float absorption, int mode, float radius) try {
+    Context::Ref c;
+    if (!c || !validateMesh(verts, nv, tris, nt, absorption, mode, radius, &g_lastError)) return -1;
+    return c->addMesh(verts, nv, tris, nt, absorption, mode, radius, &g_lastError);
+} PV_API_CATCH(-1)
+
+void PlaneverbSetMeshGeometryTransform(int id, const float* m12) try {
+    Context::Ref c;
+    if (c && validateMeshTransform(m12, &g_lastError)) c->setMeshTransform(id, m12);
+} PV_API_CATCH_VOID
+
+void PlaneverbRemoveMeshGeometry(int id) try {
+    Context::Ref c;
+    if (c) c->removeMesh(id);
+} PV_API_CATCH_VOID
+
+void PlaneverbSetSliceHeight(float h) try {
+    Context::Ref c;
+    if (!(h - h == 0.f)) {
+        g_lastError = "PlaneverbSetSliceHeight: the height is not finite";
+        return;
+    }
+    if (c) c->setSliceHeight(h);
 } PV_API_CATCH_VOID
 
 void PlaneverbSetListenerPosition(float x, float y, float z) try {
@@ -907,6 +934,56 @@ int PvAmdUpdatePolygon(PvAmdSolver* h, int id, const float* xy, int n, float abs
     Shape sh;
     if (!shapesOk(h) || !makePolygon(xy, n, absorption, &sh, &g_lastError)) return -1;
     return updateShape(h, id, sh);
+} PV_API_CATCH(-1)
+
+// triangle meshes (pv_core.h validateMesh; Solver::addMesh).  One solver only: slab groups and slab ranks refuse them.
+static bool meshesOk(PvAmdSolver* h) {
+    if (h && (h->opt.slabCount > 1 || !h->slabDevices.empty())) {
+        g_lastError = "meshes are not available on slabs (PvAmdCreateSlabs, PvAmdCreateSlabRank)";
+        return false;
+    }
+    return ensure(h);
+}
+
+int PvAmdAddMesh(PvAmdSolver* h, const float* verts, int nv, const int* tris, int nt, float absorption, int mode, float radius) try {
+    if (!meshesOk(h) || !validateMesh(verts, nv, tris, nt, absorption, mode, radius, &g_lastError)) return -1;
+    const int id = h->s->addMesh(verts, nv, tris, nt, absorption, mode, radius);
+    if (id < 0) ret(h, false);
+    return id;
+} PV_API_CATCH(-1)
+
+int PvAmdUpdateMesh(PvAmdSolver* h, int id, const float* verts, int nv, const int* tris, int nt, float absorption, int mode,
+                    float radius) try {
+    if (!meshesOk(h) || !validateMesh(verts, nv, tris, nt, absorption, mode, radius, &g_lastError)) return -1;
+    return ret(h, h->s->updateMesh(id, verts, nv, tris, nt, absorption, mode, radius));
+} PV_API_CATCH(-1)
+
+int PvAmdSetMeshTransform(PvAmdSolver* h, int id, const float* m12) try {
+    if (!meshesOk(h) || !validateMeshTransform(m12, &g_lastError)) return -1;
+    return ret(h, h->s->setMeshTransform(id, m12));
+} PV_API_CATCH(-1)
+
+int PvAmdRemoveMesh(PvAmdSolver* h, int id) try {
+    if (!meshesOk(h)) return -1;
+    return ret(h, h->s->removeMesh(id));
+} PV_API_CATCH(-1)
+
+int PvAmdSetSliceHeight(PvAmdSolver* h, float height) try {
+    if (!(height - height == 0.f)) {
+        g_lastError = "PvAmdSetSliceHeight: the height is not finite";
+        return -1;
+    }
+    if (!meshesOk(h)) return -1;
+    return ret(h, h->s->setSliceHeight(height));
+} PV_API_CATCH(-1)
+
+float PvAmdGetSliceHeight(PvAmdSolver* h) try { return meshesOk(h) ? h->s->sliceHeight() : 0.f; } PV_API_CATCH(0.f)
+
+int PvAmdMeshTriangles(PvAmdSolver* h, int id) try { return meshesOk(h) ? h->s->meshTriangles(id) : -1; } PV_API_CATCH(-1)
+
+int PvAmdCopyMeshSection(PvAmdSolver* h, int id, float* out4nt, uint8_t* valid_nt) try {
+    if (!meshesOk(h)) return -1;
+    return ret(h, h->s->copyMeshSection(id, out4nt, valid_nt));
 } PV_API_CATCH(-1)
 
 int PvAmdSetGridBoundary(PvAmdSolver* h, const float* absorption4) try {
@@ -1945,6 +2022,49 @@ int PvAmdHostRoundShapeCoverage(float sx, float sy, int res, int kind, const flo
     shapeCellBounds(sh, g, &x0, &x1, &y0, &y1);
     for (int x = x0; x < x1; ++x)
         for (int y = y0; y < y1; ++y) cover[(size_t)x * g.NY + y] = shapeCovers(sh, g.dx, x, y) ? 1 : 0;
+    return 0;
+} PV_API_CATCH(-1)
+
+// indices and finite inputs only: what the section needs (a mesh's other rules are validateMesh's)
+static bool sectionInputsOk(const float* verts, int nv, const int* tris, int nt, const float* m12, float h, const char* name) {
+    bool ok = verts && tris && nv >= 1 && nt >= 1 && nt <= kMeshMaxTris && h - h == 0.f;
+    for (size_t i = 0; ok && i < (size_t)3 * nv; ++i) ok = std::isfinite(verts[i]);
+    for (size_t i = 0; ok && i < (size_t)3 * nt; ++i) ok = tris[i] >= 0 && tris[i] < nv;
+    if (!ok) {
+        g_lastError = std::string(name) + ": a null array, a count out of range, a non-finite input or an index outside [0, nv)";
+        return false;
+    }
+    return !m12 || validateMeshTransform(m12, &g_lastError);
+}
+
+int PvAmdHostMeshSection(const float* verts, int nv, const int* tris, int nt, const float* m12, float h, float* out4nt,
+                         uint8_t* valid_nt) try {
+    if (!out4nt || !valid_nt) {
+        g_lastError = "PvAmdHostMeshSection: a null array";
+        return -1;
+    }
+    if (!sectionInputsOk(verts, nv, tris, nt, m12, h, "PvAmdHostMeshSection")) return -1;
+    meshSection(verts, tris, nt, m12, h, out4nt, valid_nt);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostMeshCoverage(float sx, float sy, int res, const float* verts, int nv, const int* tris, int nt, const float* m12, float h,
+                          int mode, float radius, uint8_t* cover) try {
+    if (res < kLowResolution || !cover) {
+        g_lastError = "PvAmdHostMeshCoverage: resolution below 275 or a null array";
+        return -1;
+    }
+    if (!(h - h == 0.f)) {
+        g_lastError = "PvAmdHostMeshCoverage: the height is not finite";
+        return -1;
+    }
+    if (!validateMesh(verts, nv, tris, nt, 0.f, mode, radius, &g_lastError) || (m12 && !validateMeshTransform(m12, &g_lastError)))
+        return -1;
+    const GridSpec g = makeGridSpec(sx, sy, res);
+    std::vector<float> seg((size_t)4 * nt);
+    std::vector<uint8_t> valid((size_t)nt);
+    meshSection(verts, tris, nt, m12, h, seg.data(), valid.data());
+    meshCoverage(g, seg.data(), valid.data(), nt, mode, radius, cover);
     return 0;
 } PV_API_CATCH(-1)
 

@@ -979,6 +979,121 @@ void Context::removeShape(int id) {
     shapeFree_.push_back(id);
 }
 
+int Context::addMesh(const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius, std::string* err) {
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    int live = 0;
+    long long total = nt;
+    for (int n : meshTris_) {
+        live += n > 0;
+        total += n;
+    }
+    if (live >= kMeshMax) {
+        *err = "PlaneverbAddMeshGeometry: 64 meshes are live already";
+        return -1;
+    }
+    if (total > kMeshMaxTrisTotal) {
+        *err = "PlaneverbAddMeshGeometry: more than 1 << 22 triangles over all meshes";
+        return -1;
+    }
+    // everything that can fail first (the copies among it): the tables are still what they were
+    ensureRoom(changes_, 1);
+    ensureRoom(meshStore_, 1);
+    ensureRoom(meshTris_, 1);
+    std::unique_ptr<MeshEntry> e(new MeshEntry);
+    e->verts.assign(verts, verts + (size_t)3 * nv);
+    e->tris.assign(tris, tris + (size_t)3 * nt);
+    e->serial = meshSerialNext_++;
+    e->uploadsLeft = solver2_ ? 2 : 1;
+    e->nv = nv;
+    e->nt = nt;
+    e->mode = mode;
+    e->R = R;
+    e->r = radius;
+    int id;
+    if (meshFree_.empty()) {
+        id = (int)meshTris_.size();
+        meshTris_.push_back(nt);
+    } else {
+        id = meshFree_.back();
+        meshFree_.pop_back();
+        meshTris_[(size_t)id] = nt;
+    }
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.mesh = 1;
+    c.meshId = id;
+    c.meshSerial = e->serial;
+    meshStore_.push_back(std::move(e));
+    changes_.push_back(c);
+    return id;
+}
+
+void Context::setMeshTransform(int id, const float* m12) {
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    if (id < 0 || id >= (int)meshTris_.size() || !meshTris_[(size_t)id]) return;
+    ensureRoom(changes_, 1);
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.mesh = 2;
+    c.meshId = id;
+    for (int k = 0; k < 12; ++k) c.m12[k] = m12[k];
+    changes_.push_back(c);
+}
+
+void Context::removeMesh(int id) {
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    if (id < 0 || id >= (int)meshTris_.size() || !meshTris_[(size_t)id]) return;
+    ensureRoom(changes_, 1);
+    ensureRoom(meshFree_, 1);
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.mesh = 3;
+    c.meshId = id;
+    changes_.push_back(c);
+    meshTris_[(size_t)id] = 0;
+    meshFree_.push_back(id);
+}
+
+void Context::setSliceHeight(float h) {
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    ensureRoom(changes_, 1);
+    Change c{false, Box{0, 0, 0, 0, 0}, -1, Shape{}};
+    c.mesh = 4;
+    c.h = h;
+    changes_.push_back(c);
+}
+
+// (the worker's thread.  A failure of a solver call here -- a device allocation -- surfaces as the solver's error at its next run.)
+void Context::applyMeshChange(Solver* s, const Change& c) {
+#ifndef PVA_HOST_TEST  // (the HIP-less fake has no mesh layer)
+    if (c.mesh == 2) {
+        s->setMeshTransform(c.meshId, c.m12);
+    } else if (c.mesh == 3) {
+        s->meshClear(c.meshId);
+    } else if (c.mesh == 4) {
+        s->setSliceHeight(c.h);
+    }
+#endif
+    if (c.mesh != 1) return;
+    MeshEntry* e = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(geomMutex_);
+        for (auto& p : meshStore_)
+            if (p->serial == c.meshSerial) e = p.get();
+    }
+    if (!e) return;
+#ifndef PVA_HOST_TEST
+    // (only this thread erases entries, so e stays valid without the lock; meshSet returns with the data on the device)
+    s->meshSet(c.meshId, e->verts.data(), e->nv, e->tris.data(), e->nt, e->R, e->mode, e->r);
+#else
+    (void)s;
+#endif
+    std::lock_guard<std::mutex> lock(geomMutex_);
+    if (--e->uploadsLeft <= 0)
+        for (size_t i = 0; i < meshStore_.size(); ++i)
+            if (meshStore_[i].get() == e) {
+                meshStore_.erase(meshStore_.begin() + (long)i);
+                break;
+            }
+}
+
 void Context::setGridBoundary(const float R4[4]) {
     std::lock_guard<std::mutex> lock(geomMutex_);
     ensureRoom(changes_, 1);
@@ -1071,12 +1186,22 @@ void Context::pushGeometryChanges() {
         for (auto& pend : pending_) pend.insert(pend.end(), q.begin(), q.end());
         return;
     }
-    for (const Change& c : q) applyChange(solver_, c);  // GeometryManager.cpp:123-152, applied in queue order
+    for (const Change& c : q) {  // GeometryManager.cpp:123-152, applied in queue order
+        if (c.mesh)
+            applyMeshChange(solver_, c);
+        else
+            applyChange(solver_, c);
+    }
 }
 
 void Context::applyPending(const int k) {
     Solver* s = k == 0 ? solver_ : solver2_;
-    for (const Change& c : pending_[k]) applyChange(s, c);
+    for (const Change& c : pending_[k]) {
+        if (c.mesh)
+            applyMeshChange(s, c);
+        else
+            applyChange(s, c);
+    }
     pending_[k].clear();
 }
 

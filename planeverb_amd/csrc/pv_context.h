@@ -24,6 +24,7 @@
 #include <condition_variable>
 #include <deque>
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -91,6 +92,14 @@ public:
     int addShape(const Shape& sh);
     void updateShape(int id, const Shape& sh);
     void removeShape(int id);
+    // Triangle meshes (Solver::meshSet, already validated by pv_core.h validateMesh): ids of their own, recycled LIFO.  The
+    // vertex data is copied into a store the context owns AT THE CALL -- the one step that can fail: -1 + *err, nothing changed --
+    // and the queued change carries only the id, the operation, twelve floats and h, so it stays a fixed-size record.  An entry
+    // of the store lives until every solver has taken it to the device.
+    int addMesh(const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius, std::string* err);
+    void setMeshTransform(int id, const float* m12);
+    void removeMesh(int id);
+    void setSliceHeight(float h);
     // grid edges (Solver::setGridBoundary, finite values already checked): queued with the geometry changes, applied to every
     // solver at the same iteration boundary
     void setGridBoundary(const float R4[4]);
@@ -220,8 +229,26 @@ private:
         float recSeconds = 0.f;
         int recN = 0;
         float recEdges[kLobesMaxEdges] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        // a mesh change: 1 = slot meshId takes the store's entry meshSerial, 2 = its transform, 3 = it is emptied, 4 = the slice height
+        int mesh = 0;
+        int meshId = -1;
+        int meshSerial = 0;
+        float m12[12] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        float h = 0.f;
     };
     static void applyChange(Solver* s, const Change& c);
+    void applyMeshChange(Solver* s, const Change& c);
+    struct MeshEntry {
+        int serial = 0, uploadsLeft = 0;  // (one upload per solver)
+        int nv = 0, nt = 0, mode = 0;
+        float R = 0.f, r = 0.f;
+        std::vector<float> verts;
+        std::vector<int> tris;
+    };
+    std::vector<std::unique_ptr<MeshEntry>> meshStore_;
+    std::vector<int> meshTris_;  // per id: the live mesh's triangle count, 0 = empty slot
+    std::vector<int> meshFree_;
+    int meshSerialNext_ = 1;
     std::vector<Box> geometry_;
     std::vector<int> geometryFree_;
     std::vector<uint8_t> shapeUsed_;

@@ -530,6 +530,156 @@ std::vector<SegRect> planSegments(const uint8_t* air, int ntx, int nty, int rxi,
     return out;
 }
 
+// ----------------------------------------------------------------------------------------------------------------
+// triangle meshes (pv_core.h; the device side is pv_mesh.hip)
+// ----------------------------------------------------------------------------------------------------------------
+
+bool validateMeshTransform(const float* m12, std::string* err) {
+    if (!m12) {
+        if (err) *err = "mesh: no transform";
+        return false;
+    }
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(m12[i])) {
+            if (err) *err = "mesh with a non-finite transform entry";
+            return false;
+        }
+    return true;
+}
+
+bool validateMesh(const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius, std::string* err) {
+    auto refuse = [&](const char* why) {
+        if (err) *err = why;
+        return false;
+    };
+    if (!verts || !tris) return refuse("mesh: no vertex or triangle list");
+    if (mode != kMeshSolid && mode != kMeshShell) return refuse("mesh: unknown mode");
+    if (nv < 1) return refuse("mesh: no vertices");
+    if (nt < 1) return refuse("mesh: at least one triangle");
+    if (nt > kMeshMaxTris) return refuse("mesh: more than 1 << 20 triangles");
+    if (!std::isfinite(R)) return refuse("mesh with a non-finite absorption");
+    if (mode == kMeshShell) {
+        if (!std::isfinite(radius)) return refuse("mesh with a non-finite radius");
+        if (!(radius > 0.f) || !(radius * radius > 0.f)) return refuse("mesh: the shell radius must be positive");
+        if (!std::isfinite(radius * radius)) return refuse("mesh: the shell radius is too large");
+    }
+    for (size_t i = 0; i < (size_t)3 * nv; ++i)
+        if (!std::isfinite(verts[i])) return refuse("mesh with a non-finite vertex");
+    for (int i = 0; i < nt; ++i) {
+        const int a = tris[3 * i], b = tris[3 * i + 1], c = tris[3 * i + 2];
+        if (a < 0 || a >= nv || b < 0 || b >= nv || c < 0 || c >= nv) return refuse("mesh: a vertex index outside [0, nv)");
+        if (a == b || b == c || c == a) return refuse("mesh: a triangle with two equal indices");
+    }
+    if (mode != kMeshSolid) return true;
+    // closedness: every undirected edge in exactly two triangles (open addressing over (min, max) keys)
+    size_t cap = 16;
+    while (cap < (size_t)6 * nt) cap <<= 1;
+    std::vector<uint64_t> keys(cap, ~(uint64_t)0);
+    std::vector<uint8_t> count(cap, 0);
+    for (int i = 0; i < nt; ++i)
+        for (int e = 0; e < 3; ++e) {
+            const unsigned a = (unsigned)tris[3 * i + e], b = (unsigned)tris[3 * i + (e + 1) % 3];
+            const uint64_t key = ((uint64_t)std::min(a, b) << 32) | std::max(a, b);
+            size_t slot = (size_t)((key * 0x9E3779B97F4A7C15ull) >> 20) & (cap - 1);
+            while (keys[slot] != key && keys[slot] != ~(uint64_t)0) slot = (slot + 1) & (cap - 1);
+            keys[slot] = key;
+            if (++count[slot] > 2) return refuse("mesh: a solid mesh's edge is shared by more than two triangles");
+        }
+    for (size_t s = 0; s < cap; ++s)
+        if (count[s] == 1) return refuse("mesh: a solid mesh must be closed (an edge belongs to one triangle only)");
+    return true;
+}
+
+void meshSection(const float* verts, const int* tris, int nt, const float* m12, float h, float* out4, uint8_t* valid) {
+    for (int i = 0; i < nt; ++i) {
+        float p[3][3];
+        for (int k = 0; k < 3; ++k) {
+            const float* v = verts + (size_t)3 * tris[3 * i + k];
+            for (int r = 0; r < 3; ++r)
+                p[k][r] = m12 ? ((m12[4 * r] * v[0] + m12[4 * r + 1] * v[1]) + m12[4 * r + 2] * v[2]) + m12[4 * r + 3] : v[r];
+        }
+        const bool up[3] = {p[0][1] > h, p[1][1] > h, p[2][1] > h};
+        float* o = out4 + (size_t)4 * i;
+        o[0] = o[1] = o[2] = o[3] = 0.f;
+        valid[i] = 0;
+        if (up[0] == up[1] && up[1] == up[2]) continue;
+        int n = 0;
+        for (int e = 0; e < 3; ++e) {
+            const int e2 = e == 2 ? 0 : e + 1;
+            if (up[e] == up[e2]) continue;
+            const float* lo = up[e] ? p[e2] : p[e];
+            const float* hi = up[e] ? p[e] : p[e2];
+            const float t = (h - lo[1]) / (hi[1] - lo[1]);
+            o[2 * n] = lo[0] + (t * (hi[0] - lo[0]));
+            o[2 * n + 1] = lo[2] + (t * (hi[2] - lo[2]));
+            ++n;
+        }
+        valid[i] = 1;
+    }
+}
+
+int meshCrossingPrefix(float xi, float dx, int gx) {
+    const float kf = std::ceil(xi / dx - 0.5f);
+    if (!(kf >= 0.f)) return 0;  // (left of the grid, or NaN)
+    int k = kf >= (float)gx ? gx : (int)kf;
+    while (k > 0 && !(((float)(k - 1) + 0.5f) * dx < xi)) --k;
+    while (k < gx && ((float)k + 0.5f) * dx < xi) ++k;
+    return k;
+}
+
+void meshCoverage(const GridSpec& g, const float* seg4, const uint8_t* valid, int nt, int mode, float radius, uint8_t* cover) {
+    const int NY = g.NY, gx = g.gx, gy = g.gy;
+    const float dx = g.dx;
+    std::memset(cover, 0, (size_t)g.NX * NY);
+    // rows (or columns) n of 0 .. cells whose centre can lie in [lo - pad, hi + pad]; everything when a bound is not finite
+    auto range = [&](float lo, float hi, double pad, int cells, int* c0, int* c1) {
+        *c0 = 0;
+        *c1 = cells;
+        if (!std::isfinite(lo) || !std::isfinite(hi)) return;
+        const double a = std::floor((double)lo / dx - 0.5 - pad), b = std::ceil((double)hi / dx - 0.5 + pad) + 1;
+        *c0 = (int)std::max(0.0, std::min((double)cells, a));
+        *c1 = (int)std::max(0.0, std::min((double)cells, b));
+    };
+    const float rr = radius * radius;
+    for (int i = 0; i < nt; ++i) {
+        if (!valid[i]) continue;
+        const float ax = seg4[4 * (size_t)i], ay = seg4[4 * (size_t)i + 1], bx = seg4[4 * (size_t)i + 2], by = seg4[4 * (size_t)i + 3];
+        int x0, x1, y0, y1;
+        if (mode == kMeshSolid) {
+            range(std::min(ay, by), std::max(ay, by), 1.0, gy, &y0, &y1);
+            for (int y = y0; y < y1; ++y) {
+                const float py = ((float)y + 0.5f) * dx;
+                if ((ay > py) == (by > py)) continue;
+                const int k = meshCrossingPrefix((((bx - ax) * (py - ay)) / (by - ay)) + ax, dx, gx);
+                if (k > 0) cover[(size_t)(k - 1) * NY + y] ^= 1;  // a mark: the suffix XOR below turns marks into coverage
+            }
+            continue;
+        }
+        double m = std::max(g.gsx, g.gsy) * (double)dx;
+        for (float c : {ax, ay, bx, by}) m = std::max(m, std::fabs((double)c));
+        const double pad = 2.0 + std::ceil((m + radius) * 4e-6 / dx);  // (as shapeCellBounds for a round shape)
+        range(std::min(ax, bx) - radius, std::max(ax, bx) + radius, pad, gx, &x0, &x1);
+        range(std::min(ay, by) - radius, std::max(ay, by) + radius, pad, gy, &y0, &y1);
+        const float ex = bx - ax, ey = by - ay, ee = (ex * ex) + (ey * ey);
+        for (int x = x0; x < x1; ++x) {
+            const float wx = ((float)x + 0.5f) * dx - ax;
+            for (int y = y0; y < y1; ++y) {
+                const float wy = ((float)y + 0.5f) * dx - ay;
+                float t = 0.f;
+                if (ee != 0.f) {
+                    t = ((wx * ex) + (wy * ey)) / ee;
+                    t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+                }
+                const float qx = wx - (t * ex), qy = wy - (t * ey);
+                if ((qx * qx) + (qy * qy) <= rr) cover[(size_t)x * NY + y] = 1;
+            }
+        }
+    }
+    if (mode == kMeshSolid)
+        for (int x = gx - 2; x >= 0; --x)
+            for (int y = 0; y < gy; ++y) cover[(size_t)x * NY + y] ^= cover[(size_t)(x + 1) * NY + y];
+}
+
 const char* edgeLayerRefusal(int gx, int gy, const int w4[4]) {
     for (int k = 0; k < 4; ++k)
         if (w4[k] < 0 || w4[k] > kEdgeLayerMaxWidth) return "edge layer widths run from 0 to 64 cells";

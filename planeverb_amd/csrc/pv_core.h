@@ -128,6 +128,26 @@ bool shapeCovers(const Shape& s, float dx, int x, int y);
 // function), clipped to the grid's cells 0 <= x < gx, 0 <= y < gy (never the ghost row / column); empty when x0 >= x1 or y0 >= y1
 void shapeCellBounds(const Shape& s, const GridSpec& g, int* x0, int* x1, int* y0, int* y1);
 
+// Triangle meshes (include/planeverb_amd.h, "Triangle meshes"; no reference counterpart): sliced at the solver's height and
+// rasterised on the device (pv_mesh.h) between the AABB layer and the shape layer.  These are the host's parts: validation, the
+// closedness check of a solid mesh and the CPU restatement of slice and coverage -- float32 without contraction, as the kernels.
+constexpr int kMeshMax = 64;
+constexpr int kMeshMaxTris = 1 << 20;
+constexpr int kMeshMaxTrisTotal = 1 << 22;
+enum MeshMode : int { kMeshSolid = 0, kMeshShell = 1 };
+// finite vertices, absorption and (shell) radius with a finite non-zero float32 square; 1 <= nt <= kMeshMaxTris; indices inside
+// [0, nv) and distinct within a triangle; solid: every undirected edge shared by exactly two triangles (a hash over the edges)
+bool validateMesh(const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius, std::string* err);
+bool validateMeshTransform(const float* m12, std::string* err);
+// the section of every triangle at height h: out4[4 i ..] = (a.x, a.z, b.x, b.z) and valid[i] = 1, or valid[i] = 0 and zeros.
+// m12 = nullptr: no transform.
+void meshSection(const float* verts, const int* tris, int nt, const float* m12, float h, float* out4, uint8_t* valid);
+// coverage of the section's segments over the grid's cells (cover[x * NY + y] = 0 / 1, the ghost row and column never): solid by
+// the marks-and-suffix-XOR form of the even-odd rule, shell by the capsule rule over each segment's cell bounds
+void meshCoverage(const GridSpec& g, const float* seg4, const uint8_t* valid, int nt, int mode, float radius, uint8_t* cover);
+// how many cells x in [0, gx) have ((float)x + 0.5f) * dx < xi: the cells one crossing toggles are the prefix [0, k)
+int meshCrossingPrefix(float xi, float dx, int gx);
+
 // Graded absorbing layers at the grid edges (pv_layer.h: the model and the layer kernel)
 constexpr int kEdgeLayerMaxWidth = 64;
 constexpr int kEdgeLayerMinInterior = 8;  // cells between two opposite layers (or a layer and the far edge)

@@ -3,6 +3,7 @@
 #include "pv_boundary.h"
 #include "pv_layer.h"
 #include "pv_shapes.h"
+#include "pv_mesh.h"
 
 #include <unistd.h>
 
@@ -710,9 +711,12 @@ Solver::~Solver() {
     if (emTrace_) hipFree(emTrace_);
     if (recTrace_) hipFree(recTrace_);
     if (emRecCells_) hipHostFree(emRecCells_);
+    for (MeshSlot& m : meshTable_)
+        if (m.dev) hipFree(m.dev);
     void* ptrs[] = {coef_,      matDev_, pulseDev_, hist_,  tileFirst_, tileClass_, generalList_,
                     generalCount_, dynDev_, errFlag_, res8_,     delay_, scratch_, res_, activeCount_, win8_, unitList_, fusedCtl_, labelDev_, nearBox_,
-                    histAbove_, histEdge_, tileDead_, deadCount_, matBaseDev_, shapeDev_};
+                    histAbove_, histEdge_, tileDead_, deadCount_, matBaseDev_, shapeDev_,
+                    matMeshDev_, meshOwnerDev_, meshBoundsDev_};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (size_t b = 1; b < bandStream_.size(); ++b)
@@ -890,9 +894,10 @@ bool Solver::shapeClear(int id) {
 }
 
 // Recompose the dirty bins: the bins of the changed shapes' old and new cell bounds and of the AABB rows [aabbLo, aabbHi).
-// The device writes matDev_ from matBaseDev_ and the table (pv_shape_compose_kernel); the host mirrors -- betaHost_ / byHost_
-// (air components, IR cells) and compBeta_ / compR_ (copyMaterial) -- restate the same rule (shapeCovers) over the same bins
-// and bin lists, cell by cell, so the two agree by construction.  A slab recomposes on the device only the bins that reach
+// The device writes matDev_ from matBaseDev_ (with meshes: matMeshDev_) and the table (pv_shape_compose_kernel); the host
+// mirrors -- betaHost_ / byHost_ (air components, IR cells) and compBeta_ / compR_ (copyMaterial) -- restate the same rule
+// (shapeCovers) over the same bins and bin lists, cell by cell, so the two agree by construction: composeMirrors, which
+// applyGeometry calls behind its geometry sync with what this function leaves in mirror_.  A slab recomposes on the device only the bins that reach
 // the rows its coefficient pass reads (whole-grid coordinates, as pv_coef_kernel with x0).
 bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
     const int NX = g_.NX, NY = g_.NY;
@@ -975,7 +980,7 @@ bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
     unsigned char* base = static_cast<unsigned char*>(shapeDev_);
     if (!hipOk(hipMemcpyAsync(base, shapeStage_.data(), bytes, hipMemcpyHostToDevice, stream_), "shape table upload")) return false;
     ShapeArgs a;
-    a.base = matBaseDev_;
+    a.base = meshActive_ ? matMeshDev_ : matBaseDev_;
     a.mat = matDev_;
     a.shapes = reinterpret_cast<const DevShape*>(base + oTab);
     a.pool = pool.empty() ? nullptr : reinterpret_cast<const float*>(base + oPool);
@@ -989,13 +994,39 @@ bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
     a.dx = g_.dx;
     launchShapeCompose(a, stream_);
     if (!hipOk(hipGetLastError(), "shape compose launch")) return false;
-    // host mirrors over every dirty bin
+    // what composeMirrors needs, behind the geometry sync
+    mirror_.nby = nby;
+    mirror_.dirty.swap(dirty);
+    mirror_.order.swap(order);
+    mirror_.binStart.swap(binStart);
+    mirror_.binList.swap(binList);
+    mirror_.x0.resize((size_t)ns);
+    mirror_.x1.resize((size_t)ns);
+    mirror_.y0.resize((size_t)ns);
+    mirror_.y1.resize((size_t)ns);
+    for (int k = 0; k < ns; ++k) {
+        mirror_.x0[(size_t)k] = table[(size_t)k].x0;
+        mirror_.x1[(size_t)k] = table[(size_t)k].x1;
+        mirror_.y0[(size_t)k] = table[(size_t)k].y0;
+        mirror_.y1[(size_t)k] = table[(size_t)k].y1;
+    }
+    shapeDirty_.clear();
+    return true;
+}
+
+// The host mirrors over every dirty bin of the last composeShapes.  Under the shapes lies the AABB layer, or -- with meshes --
+// the cell's mesh as the device's owner plane names it (meshOwnerHost_, read back on the stream: this runs behind the sync).
+void Solver::composeMirrors(bool* airChanged) {
+    const int NX = g_.NX, NY = g_.NY, nby = mirror_.nby, nbins = (int)mirror_.dirty.size();
     const auto& beta = mat_.beta();
     const auto& R = mat_.R();
     const auto& by = mat_.by();
+    const auto& order = mirror_.order;
+    const auto& binStart = mirror_.binStart;
+    const auto& binList = mirror_.binList;
     bool changed = false;
     for (int b = 0; b < nbins; ++b) {
-        if (!dirty[(size_t)b]) continue;
+        if (!mirror_.dirty[(size_t)b]) continue;
         const int bx = b / nby, bY = b - bx * nby;
         const int xe = std::min(NX, (bx + 1) * kShapeBin), ye = std::min(NY, (bY + 1) * kShapeBin);
         for (int x = bx * kShapeBin; x < xe; ++x)
@@ -1003,23 +1034,303 @@ bool Solver::composeShapes(int aabbLo, int aabbHi, bool* airChanged) {
                 const size_t i = (size_t)x * NY + y;
                 int hit = -1;
                 for (int k = binStart[(size_t)b]; k < binStart[(size_t)b + 1]; ++k) {
-                    const DevShape& d = table[(size_t)binList[(size_t)k]];
-                    if (x < d.x0 || x >= d.x1 || y < d.y0 || y >= d.y1) continue;
-                    if (shapeCovers(shapeTable_[(size_t)order[(size_t)binList[(size_t)k]]], g_.dx, x, y)) {
+                    const size_t e = (size_t)binList[(size_t)k];
+                    if (x < mirror_.x0[e] || x >= mirror_.x1[e] || y < mirror_.y0[e] || y >= mirror_.y1[e]) continue;
+                    if (shapeCovers(shapeTable_[(size_t)order[e]], g_.dx, x, y)) {
                         hit = binList[(size_t)k];
                         break;
                     }
                 }
-                const uint8_t bv = hit >= 0 ? 0 : (beta[i] ? 1 : 0);
-                compBeta_[i] = hit >= 0 ? 0 : beta[i];
-                compR_[i] = hit >= 0 ? shapeTable_[(size_t)order[(size_t)hit]].R : R[i];
+                const int mesh = meshActive_ ? (int)meshOwnerHost_[i] - 1 : -1;
+                const bool wall = hit >= 0 || mesh >= 0;
+                const uint8_t bv = wall ? 0 : (beta[i] ? 1 : 0);
+                compBeta_[i] = wall ? 0 : beta[i];
+                compR_[i] = hit >= 0 ? shapeTable_[(size_t)order[(size_t)hit]].R : (mesh >= 0 ? meshTable_[(size_t)mesh].R : R[i]);
                 changed = changed || betaHost_[i] != bv;
                 betaHost_[i] = bv;
-                byHost_[i] = hit >= 0 ? 0 : by[i];
+                byHost_[i] = wall ? 0 : by[i];
             }
     }
     *airChanged = *airChanged || changed;
-    shapeDirty_.clear();
+    mirror_.dirty.clear();
+}
+
+// ----------------------------------------------------------------------------------------------------------------
+// mesh layer (pv_mesh.h)
+// ----------------------------------------------------------------------------------------------------------------
+
+long long Solver::meshTrisTotal() const {
+    long long n = 0;
+    for (const MeshSlot& m : meshTable_)
+        if (m.seq >= 0) n += m.nt;
+    return n;
+}
+
+int Solver::numMeshes() const {
+    int n = 0;
+    for (const MeshSlot& m : meshTable_) n += m.seq >= 0;
+    return n;
+}
+
+int Solver::meshTriangles(int id) const {
+    return (id < 0 || id >= (int)meshTable_.size() || meshTable_[(size_t)id].seq < 0) ? -1 : meshTable_[(size_t)id].nt;
+}
+
+void Solver::meshFreeSlot(MeshSlot& m) {
+    if (m.dev) {
+        hipStreamSynchronize(stream_);
+        hipFree(m.dev);
+        deviceBytes_ -= (long long)m.devBytes;
+    }
+    m = MeshSlot{};
+}
+
+int Solver::addMesh(const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius) {
+    if (numMeshes() >= kMeshMax) {
+        fail("mesh: 64 meshes are live already");
+        return -1;
+    }
+    const int id = meshFree_.empty() ? (int)meshTable_.size() : meshFree_.back();  // LIFO recycling, as the other tables
+    if (!meshSet(id, verts, nv, tris, nt, R, mode, radius)) return -1;
+    if (!meshFree_.empty() && meshFree_.back() == id) meshFree_.pop_back();
+    return id;
+}
+
+bool Solver::updateMesh(int id, const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius) {
+    if (meshTriangles(id) < 0) return fail("invalid mesh id");
+    return meshSet(id, verts, nv, tris, nt, R, mode, radius);
+}
+
+bool Solver::removeMesh(int id) {
+    if (!meshClear(id)) return false;
+    meshFree_.push_back(id);
+    return true;
+}
+
+// Slot `id` takes the mesh: the vertices and triangles go up once and stay on the device; everything else -- the section, the
+// bit plane -- is made from them by applyGeometry.  A refusal leaves the slot as it was.
+bool Solver::meshSet(int id, const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius) {
+    if (id < 0 || id >= kMeshMax) return fail("invalid mesh id");
+    if (isSlab()) return fail("meshes are not available on slabs");
+    const bool had = id < (int)meshTable_.size() && meshTable_[(size_t)id].seq >= 0;
+    if (meshTrisTotal() - (had ? meshTable_[(size_t)id].nt : 0) + nt > kMeshMaxTrisTotal)
+        return fail("mesh: more than 1 << 22 triangles over all meshes");
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice")) return false;
+    auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    MeshSlot n;
+    n.nv = nv;
+    n.nt = nt;
+    n.mode = mode;
+    n.R = R;
+    n.r = mode == kMeshShell ? radius : 0.f;
+    n.oTris = align((size_t)nv * 12);
+    n.oSeg = n.oTris + align((size_t)nt * 12);
+    n.oValid = n.oSeg + align((size_t)nt * 16);
+    n.oBits = n.oValid + align((size_t)nt);
+    const size_t bytes = n.oBits + align((size_t)((g_.gx + 31) / 32) * g_.NY * 4);
+    if (!dalloc(&n.dev, bytes, false)) return false;
+    n.devBytes = bytes;
+    // (pageable sources: the stream is synchronised before the caller's arrays can go away)
+    if (!hipOk(hipMemcpyAsync(n.dev, verts, (size_t)nv * 12, hipMemcpyHostToDevice, stream_), "mesh vertex upload") ||
+        !hipOk(hipMemcpyAsync(n.dev + n.oTris, tris, (size_t)nt * 12, hipMemcpyHostToDevice, stream_), "mesh triangle upload") ||
+        !hipOk(hipStreamSynchronize(stream_), "mesh upload sync")) {
+        hipFree(n.dev);
+        deviceBytes_ -= (long long)bytes;
+        return false;
+    }
+    if (!meshActive_) {  // the first mesh: the shape layer's planes and mirrors carry the composed material from here on
+        if (!shapesActive_) {
+            compBeta_ = mat_.beta();
+            compR_ = mat_.R();
+            shapesActive_ = true;
+        }
+        meshActive_ = true;
+        meshAllDirty_ = true;
+    }
+    if (id >= (int)meshTable_.size()) meshTable_.resize((size_t)id + 1);
+    MeshSlot& m = meshTable_[(size_t)id];
+    if (had) {  // an update keeps the transform; where the mesh was is re-derived
+        n.hasM = m.hasM;
+        std::memcpy(n.m, m.m, sizeof(n.m));
+        meshDirty_.insert(meshDirty_.end(), m.bounds, m.bounds + 4);
+        meshFreeSlot(m);
+    }
+    n.seq = meshSeqNext_++;
+    n.reslice = true;
+    m = n;
+    meshPending_ = true;
+    invalidateAnalysisMaps();
+    return true;
+}
+
+bool Solver::meshClear(int id) {
+    if (meshTriangles(id) < 0) return fail("invalid mesh id");
+    MeshSlot& m = meshTable_[(size_t)id];
+    meshDirty_.insert(meshDirty_.end(), m.bounds, m.bounds + 4);
+    meshFreeSlot(m);
+    meshPending_ = true;
+    invalidateAnalysisMaps();
+    return true;
+}
+
+bool Solver::setMeshTransform(int id, const float* m12) {
+    if (meshTriangles(id) < 0) return fail("invalid mesh id");
+    MeshSlot& m = meshTable_[(size_t)id];
+    m.hasM = true;
+    std::memcpy(m.m, m12, sizeof(m.m));
+    m.seq = meshSeqNext_++;  // (an update: the mesh becomes the most recent one)
+    m.reslice = true;
+    meshPending_ = true;
+    invalidateAnalysisMaps();
+    return true;
+}
+
+bool Solver::setSliceHeight(float h) {
+    if (!(h - h == 0.f)) return fail("slice height: not finite");
+    if (h == sliceH_) return true;
+    sliceH_ = h;
+    if (numMeshes() > 0) {
+        for (MeshSlot& m : meshTable_)
+            if (m.seq >= 0) m.reslice = true;
+        meshPending_ = true;
+        invalidateAnalysisMaps();
+    }
+    return true;
+}
+
+bool Solver::copyMeshSection(int id, float* out4, uint8_t* valid) {
+    if (meshTriangles(id) < 0) return fail("invalid mesh id");
+    if (!hipOk(hipSetDevice(device_), "hipSetDevice") || !applyGeometry()) return false;
+    const MeshSlot& m = meshTable_[(size_t)id];
+    if (out4 && !hipOk(hipMemcpyAsync(out4, m.dev + m.oSeg, (size_t)m.nt * 16, hipMemcpyDeviceToHost, stream_), "section copy"))
+        return false;
+    if (valid && !hipOk(hipMemcpyAsync(valid, m.dev + m.oValid, (size_t)m.nt, hipMemcpyDeviceToHost, stream_), "section copy"))
+        return false;
+    return hipOk(hipStreamSynchronize(stream_), "section sync");
+}
+
+// The mesh layer of one applyGeometry, stream-ordered in front of the shape compose: every mesh that changed (all of them after
+// a change of height) is sliced, scattered into its bit plane and -- solid -- scanned; the bounds the kernels found come back in
+// one small copy; then the rectangle that holds the old and new bounds and the changed AABB rows is re-derived from the AABB
+// layer, and every live mesh is applied over it, oldest first, so that the most recent one wins.  The owner plane's rows of that
+// rectangle are read back for the host mirrors (composeMirrors, behind the geometry sync), and the rectangle joins the shape
+// layer's dirty set.
+bool Solver::composeMeshes(int aabbLo, int aabbHi) {
+    const int NX = g_.NX, NY = g_.NY;
+    if (!matMeshDev_) {
+        MeshBounds* b = nullptr;
+        if (!dalloc(&matMeshDev_, (size_t)NX * NY, false) || !dalloc(&meshOwnerDev_, (size_t)NX * NY, false) ||
+            !dalloc(&b, (size_t)kMeshMax, false))
+            return false;
+        meshBoundsDev_ = b;
+        meshOwnerHost_.assign((size_t)NX * NY, 0);
+        meshBoundsHost_.assign((size_t)4 * kMeshMax, 0);
+        meshAllDirty_ = true;
+    }
+    int R[4] = {INT_MAX, 0, INT_MAX, 0};
+    auto grow = [&](int x0, int x1, int y0, int y1) {
+        if (x0 >= x1 || y0 >= y1) return;
+        R[0] = std::min(R[0], x0);
+        R[1] = std::max(R[1], x1);
+        R[2] = std::min(R[2], y0);
+        R[3] = std::max(R[3], y1);
+    };
+    if (meshAllDirty_) grow(0, NX, 0, NY);
+    if (aabbLo < aabbHi) grow(aabbLo, aabbHi, 0, NY);
+    for (size_t k = 0; k + 3 < meshDirty_.size(); k += 4) grow(meshDirty_[k], meshDirty_[k + 1], meshDirty_[k + 2], meshDirty_[k + 3]);
+    std::vector<int> live;
+    for (size_t i = 0; i < meshTable_.size(); ++i)
+        if (meshTable_[i].seq >= 0) live.push_back((int)i);
+    std::sort(live.begin(), live.end(), [&](int a, int b) { return meshTable_[(size_t)a].seq < meshTable_[(size_t)b].seq; });
+    MeshBounds* boundsDev = static_cast<MeshBounds*>(meshBoundsDev_);
+    bool any = false;
+    for (int id : live) {
+        MeshSlot& m = meshTable_[(size_t)id];
+        if (!m.reslice) continue;
+        any = true;
+        const int empty[4] = {INT_MAX, 0, INT_MAX, 0};
+        std::memcpy(&meshBoundsHost_[(size_t)4 * id], empty, sizeof(empty));
+    }
+    if (any) {
+        if (!hipOk(hipMemcpyAsync(boundsDev, meshBoundsHost_.data(), sizeof(MeshBounds) * kMeshMax, hipMemcpyHostToDevice, stream_),
+                   "mesh bounds upload"))
+            return false;
+        for (int id : live) {
+            MeshSlot& m = meshTable_[(size_t)id];
+            if (!m.reslice) continue;
+            grow(m.bounds[0], m.bounds[1], m.bounds[2], m.bounds[3]);  // where it was
+            unsigned* bits = reinterpret_cast<unsigned*>(m.dev + m.oBits);
+            if (!hipOk(hipMemsetAsync(bits, 0, m.devBytes - m.oBits, stream_), "mesh plane clear")) return false;
+            MeshSliceArgs sa;
+            sa.verts = reinterpret_cast<const float*>(m.dev);
+            sa.tris = reinterpret_cast<const int*>(m.dev + m.oTris);
+            sa.nt = m.nt;
+            sa.hasM = m.hasM ? 1 : 0;
+            std::memcpy(sa.m, m.m, sizeof(sa.m));
+            sa.h = sliceH_;
+            sa.seg = reinterpret_cast<float4*>(m.dev + m.oSeg);
+            sa.valid = m.dev + m.oValid;
+            launchMeshSlice(sa, stream_);
+            MeshScatterArgs ca;
+            ca.seg = sa.seg;
+            ca.valid = sa.valid;
+            ca.nt = m.nt;
+            ca.bits = bits;
+            ca.bounds = boundsDev + id;
+            ca.gx = g_.gx;
+            ca.gy = g_.gy;
+            ca.NY = NY;
+            ca.dx = g_.dx;
+            ca.shell = m.mode == kMeshShell ? 1 : 0;
+            ca.r = m.r;
+            ca.extent = std::max(g_.gsx, g_.gsy) * g_.dx;
+            launchMeshScatter(ca, stream_);
+            if (m.mode == kMeshSolid) launchMeshScan(bits, boundsDev + id, g_.gx, NY, stream_);
+        }
+        if (!hipOk(hipGetLastError(), "mesh slice launch") ||
+            !hipOk(hipMemcpyAsync(meshBoundsHost_.data(), boundsDev, sizeof(MeshBounds) * kMeshMax, hipMemcpyDeviceToHost, stream_),
+                   "mesh bounds copy") ||
+            !hipOk(hipStreamSynchronize(stream_), "mesh bounds sync"))
+            return false;
+        for (int id : live) {
+            MeshSlot& m = meshTable_[(size_t)id];
+            if (!m.reslice) continue;
+            const int* b = &meshBoundsHost_[(size_t)4 * id];
+            m.bounds[0] = std::max(0, std::min(b[0], g_.gx));
+            m.bounds[1] = std::max(0, std::min(b[1], g_.gx));
+            m.bounds[2] = std::max(0, std::min(b[2], g_.gy));
+            m.bounds[3] = std::max(0, std::min(b[3], g_.gy));
+            if (m.bounds[0] >= m.bounds[1] || m.bounds[2] >= m.bounds[3]) m.bounds[0] = m.bounds[1] = m.bounds[2] = m.bounds[3] = 0;
+            grow(m.bounds[0], m.bounds[1], m.bounds[2], m.bounds[3]);
+            m.reslice = false;
+        }
+    }
+    meshDirty_.clear();
+    meshAllDirty_ = false;
+    meshPending_ = false;
+    if (R[0] >= R[1] || R[2] >= R[3]) return true;
+    launchMeshRestore(matBaseDev_, matMeshDev_, meshOwnerDev_, R[0], R[1], R[2], R[3], NY, stream_);
+    for (int id : live) {
+        const MeshSlot& m = meshTable_[(size_t)id];
+        MeshApplyArgs aa;
+        aa.bits = reinterpret_cast<const unsigned*>(m.dev + m.oBits);
+        aa.mat = matMeshDev_;
+        aa.owner = meshOwnerDev_;
+        aa.x0 = std::max(R[0], m.bounds[0]);
+        aa.x1 = std::min(R[1], m.bounds[1]);
+        aa.y0 = std::max(R[2], m.bounds[2]);
+        aa.y1 = std::min(R[3], m.bounds[3]);
+        aa.NY = NY;
+        aa.Y = (1.f - m.R) / (1.f + m.R);  // (as applyGeometry for the AABB layer)
+        aa.id = id;
+        launchMeshApply(aa, stream_);
+    }
+    if (!hipOk(hipGetLastError(), "mesh apply launch") ||
+        !hipOk(hipMemcpyAsync(meshOwnerHost_.data() + (size_t)R[0] * NY, meshOwnerDev_ + (size_t)R[0] * NY, (size_t)(R[1] - R[0]) * NY,
+                              hipMemcpyDeviceToHost, stream_),
+               "mesh owner copy"))
+        return false;
+    shapeDirty_.insert(shapeDirty_.end(), R, R + 4);
     return true;
 }
 
@@ -1138,7 +1449,9 @@ bool Solver::classifyLayer() {
 }
 
 bool Solver::applyGeometry() {
-    if (!geometryDirty_ && !boundaryDirty_ && !layerDirty_ && mat_.dirtyLo() >= mat_.dirtyHi() && shapeDirty_.empty()) return true;
+    if (!geometryDirty_ && !boundaryDirty_ && !layerDirty_ && mat_.dirtyLo() >= mat_.dirtyHi() && shapeDirty_.empty() &&
+        !meshPending_)
+        return true;
     const auto t0 = std::chrono::steady_clock::now();
     int lo = mat_.dirtyLo(), hi = mat_.dirtyHi();
     if (shapesActive_ && !matBaseDev_) {
@@ -1172,6 +1485,8 @@ bool Solver::applyGeometry() {
                    "material upload"))
             return false;
     }
+    // (meshes: slice, rasterise and lay them over the AABB layer into the plane the shape compose reads as its base)
+    if (meshActive_ && !composeMeshes(lo, hi)) return false;
     if (shapesActive_ && !composeShapes(lo, hi, &airChanged)) return false;
     launchCoefs(matDev_, coef_, geo_, stream_);
     // non-absorbing grid edges: their faces are wall faces of admittance Y != 1 (pv_boundary.hip).  Edge tiles (class 2) match the
@@ -1188,6 +1503,7 @@ bool Solver::applyGeometry() {
     if (!hipOk(hipMemcpyAsync(&count, generalCount_, sizeof(int), hipMemcpyDeviceToHost, stream_), "count copy"))
         return false;
     if (!hipOk(hipStreamSynchronize(stream_), "geometry sync")) return false;
+    if (shapesActive_) composeMirrors(&airChanged);
     // (copies on the solver's own stream: a synchronous hipMemcpy runs on the LEGACY stream, which the runtime refuses while
     // any other host thread is capturing a run graph -- "operation would make the legacy stream depend on a capturing blocking
     // stream" -- and which invalidates that thread's capture: the live module's worker beside a caller's own solver)

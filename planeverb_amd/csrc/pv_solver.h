@@ -195,6 +195,24 @@ public:
     bool shapeSet(int id, const Shape& sh);
     bool shapeClear(int id);
 
+    // Mesh layer (pv_mesh.h; the model: include/planeverb_amd.h, "Triangle meshes"): triangle meshes kept on the device, sliced at
+    // sliceHeight() and rasterised between the AABB layer and the shape layer by applyGeometry.  The data is validated by the
+    // caller (pv_core.h validateMesh); the limits on live meshes and on triangles over all of them are checked here.  Ids are a
+    // table of their own with LIFO recycling.  A solver that never has a mesh allocates and launches nothing of this.
+    int addMesh(const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius);
+    bool updateMesh(int id, const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius);
+    bool setMeshTransform(int id, const float* m12);
+    bool removeMesh(int id);
+    int numMeshes() const;
+    int meshTriangles(int id) const;  // -1: no such mesh
+    bool setSliceHeight(float h);
+    float sliceHeight() const { return sliceH_; }
+    // the segments as the device sliced them, out4[4 nt] and valid[nt] (applyGeometry first: changes may be pending)
+    bool copyMeshSection(int id, float* out4, uint8_t* valid);
+    // raw access for the live context, which keeps the id table itself (as shapeSet / shapeClear)
+    bool meshSet(int id, const float* verts, int nv, const int* tris, int nt, float R, int mode, float radius);
+    bool meshClear(int id);
+
     // Grid edges (pv_boundary.h): absorption R of sides x = 0, x = gx, y = 0, y = gy, as PlaneverbAddGeometry takes it; all 0
     // (the default) is the reference's absorbing grid.  A change takes effect at the next run of any form.  Finite values only.
     bool setGridBoundary(const float R4[4]);
@@ -860,6 +878,42 @@ private:
     std::vector<unsigned char> shapeStage_;     // host image of that allocation
     std::vector<uint8_t> compBeta_;             // composed beta / R (copyMaterial)
     std::vector<float> compR_;
+    // what composeShapes leaves for composeMirrors, which fills the host mirrors behind the geometry sync
+    struct ShapeMirrorJob {
+        std::vector<uint8_t> dirty;             // per bin
+        std::vector<int> order, binStart, binList;
+        std::vector<int> x0, x1, y0, y1;        // the table entries' cell bounds
+        int nby = 0;
+    } mirror_;
+    void composeMirrors(bool* airChanged);
+
+    // mesh layer (pv_mesh.h); meshActive_ from the first mesh on (which also turns the shape layer's planes on: the shape
+    // compose then reads matMeshDev_ as its base)
+    struct MeshSlot {
+        int seq = -1;                           // sequence number of the last add / update / transform, -1 = empty slot
+        int nv = 0, nt = 0, mode = 0;
+        float R = 0.f, r = 0.f;
+        bool hasM = false;
+        float m[12] = {};
+        unsigned char* dev = nullptr;           // vertices, triangles, segments, valid marks, bit plane: one allocation
+        size_t devBytes = 0, oTris = 0, oSeg = 0, oValid = 0, oBits = 0;
+        bool reslice = false;                   // slice and rasterise again at the next applyGeometry
+        int bounds[4] = {0, 0, 0, 0};           // cells covered as of the last applyGeometry
+    };
+    bool meshActive_ = false, meshPending_ = false, meshAllDirty_ = false;
+    float sliceH_ = 0.f;
+    std::vector<MeshSlot> meshTable_;
+    std::vector<int> meshFree_;
+    int meshSeqNext_ = 0;
+    std::vector<int> meshDirty_;                // cell rectangles to re-derive from the AABB layer (removed meshes' bounds)
+    float* matMeshDev_ = nullptr;               // AABB layer overwritten by the meshes: the shape compose's base
+    uint8_t* meshOwnerDev_ = nullptr;           // per cell: 0 = AABB layer, else 1 + the id of the covering mesh
+    void* meshBoundsDev_ = nullptr;             // kMeshMax MeshBounds
+    std::vector<int> meshBoundsHost_;
+    std::vector<uint8_t> meshOwnerHost_;        // read-back of meshOwnerDev_ (the mirrors' base under the shapes)
+    long long meshTrisTotal() const;
+    void meshFreeSlot(MeshSlot& m);
+    bool composeMeshes(int aabbLo, int aabbHi);
 
     // row bands: band b covers tile rows [bandRow_[b], bandRow_[b+1])
     int nb_ = 1;
