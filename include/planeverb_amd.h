@@ -1340,6 +1340,82 @@ PVA_EXPORT int PvAmdHostSpectrumTables(int T, int fs, const float* hz, int n, fl
 PVA_EXPORT int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const float* hz, int n, const float* pulseT,
                                  float* out3n);
 
+/* ---- Waterfall: the cumulative spectral decay of chosen receivers, on a dense frequency grid ----
+ * Below about 1 kHz a room is its modes: which frequencies ring, and for how long.  The waterfall is the picture of that: a
+ * receiver's frequency response at up to 512 bins, and how that response decays slice by slice after the direct sound.  It is
+ * the transpose of the Spectrum above -- few cells, many bins -- in one pass on the device (pv_waterfall.hip) over what the LAST
+ * COMPLETED run left there: the pressure history, or in sparse-emitter mode the emitters' traces.  Definition (T = the run's
+ * steps, PvAmdInfo::T):
+ *   bins     n frequencies hz[j], 1 <= n <= PVA_WATERFALL_MAX_BINS, each finite and 0 <= hz[j] <= fs / 2; neither sorted nor
+ *            distinct (the Spectrum's rule with the larger cap);
+ *   slices   m of them, 1 <= m <= PVA_WATERFALL_MAX_SLICES; slice k starts k * ns steps after the receiver's onset, with
+ *            ns = (int)(sliceSeconds * (float)fs) in float32 (the echogram's expression); refused unless sliceSeconds is finite
+ *            and 1 <= ns <= (1 << 20);
+ *   tables   exactly those of the Spectrum: c[t * n + j] = (float)cos(ph), s[t * n + j] = (float)sin(ph), t = 0 .. T - 1, with
+ *            ph = (2.0 * M_PI * (double)hz[j] * (double)t) / (double)fs in double and the host libm's cos / sin: ABSOLUTE run
+ *            time.  The device evaluates no trigonometric function;
+ *   source   spow_j as the Spectrum defines it: the bits of PvAmdGetSpectrumSource for the same frequency;
+ *   record   of ONE receiver = result cell s = X * gy + Y with onset t0 = (int)delay[s] (the run's own onset map) and p(t) exactly
+ *            what PvAmdCopyHistoryPlane(t) returns at array cell (X, Y) -- in sparse-emitter mode what PvAmdCopyEmitterTrace
+ *            returns --, F = 2 + 2 n + m n floats:
+ *              re_j = +0.0f, im_j = +0.0f
+ *              for t = T - 1 down to t0:                      (DECREASING t: one backward walk gives every slice)
+ *                  re_j = re_j + (p(t) * c[t * n + j])
+ *                  im_j = im_j + (p(t) * s[t * n + j])
+ *                  if t == t0 + k * ns for a k in 0 .. m - 1:  R[k][j] = re_j,  I[k][j] = im_j
+ *              slices that start at or past T keep R = I = +0.0f
+ *            so X_k(f_j) = R[k][j] - i I[k][j] is the transform of the response with its first k * ns steps after the onset
+ *            removed: the cumulative spectral decay with a rectangular window.  The floats, in order:
+ *              [0]  (float)t0
+ *              [1]  (float) the count of slices with t0 + k * ns < T
+ *              R[0][0 .. n), then I[0][0 .. n): slice 0 is the receiver's complex frequency response (callers need the phase)
+ *              level[k][j] = 10.0f * log10f(((R * R) + (I * I)) / spow_j) of R[k][j], I[k][j], k = 0 .. m - 1, slice-major
+ *              (dB re the source).
+ * All arithmetic is float32; every product and every sum is rounded on its own; nothing is fused; denormals are kept; log10f is
+ * glibc's.  Nothing is special-cased: an empty slice gives 10 log10f(0 / spow) = -inf, spow_j = 0 gives what IEEE gives.
+ * Slice 0 is NOT bit-equal to PvAmdComputeSpectrum's re, im at the same cell and bin: the mathematical sum is the same, the
+ * order of summation is the opposite (each lies within the sequential-summation bound of the exact sum).
+ * A receiver off the map, in a wall, outside the run's history window or without an onset in that run holds F quiet NaNs
+ * (0x7fc00000).  A record's bits depend on its own cell alone: not on the other receivers of the call, their order, or the
+ * launch shape.  Reading ridge decay times off the levels is left to the caller, as the echogram leaves its levels; a window
+ * taper at T and rise-time windows are not provided.
+ * Receivers.  On a solver that keeps its history: 1 <= nPos <= PVA_WATERFALL_MAX_RECEIVERS positions, mapped to cells exactly as
+ * PvAmdSetOutputQueries maps its positions; duplicates are allowed.  On a sparse-emitter solver xyz must be NULL and nPos = 0:
+ * the receivers are the emitters PvAmdSetEmitters kept, in that order (at most 256; more is refused), the samples come from the
+ * emitter traces, and no emitter-record kind needs to be selected.
+ * Device storage: the tables, 2 x 4 x T x n bytes (n rounded up to a multiple of 64) from PvAmdSetWaterfall on -- 104 MB at
+ * T = 25 432 and 512 bins --, and the records, nPos x F x 4 bytes from the first PvAmdComputeWaterfall on (at most 34.6 MB;
+ * allocated again when nPos or F changes).
+ * Lifetime: that of the Spectrum's records -- a run, a geometry, boundary or layer change, a change of the setting and, in
+ * sparse-emitter mode, a change of the emitters invalidate the records; PvAmdCopyWaterfall then returns -1.  The waterfall and
+ * the nine map kinds do not invalidate each other.  With no setting nothing is allocated or launched.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "waterfall: ..."): no setting, no completed run, a last run that ended
+ * in error, PVA_OPT_SKIP_ANALYSIS (no onset map), slab groups and slab ranks, xyz = NULL with nPos > 0, nPos out of range,
+ * positions given on a sparse-emitter solver or no emitter registered there, nPos of the copy differing from the computed count. */
+#define PVA_WATERFALL_MAX_BINS      512
+#define PVA_WATERFALL_MAX_SLICES    64
+#define PVA_WATERFALL_MAX_RECEIVERS 256
+/* Set bins (copied) and slices, and upload the tables.  nBins = 0 clears the setting and frees tables and records; waits for a
+ * run in flight.  Refused with -1 and nothing changed: the bin rule, the slice rule and the caps above.  The new tables are built
+ * (host libm in double; host memory: the device table's image, 105 MB at T = 25 432 and 512 bins, and 13 MB beside it) and
+ * uploaded BESIDE the old ones, which are freed only once that has worked: a failed allocation or upload also returns -1 with
+ * the setting, the tables and the records of before in place.  A successful call frees the records of the setting before */
+PVA_EXPORT int PvAmdSetWaterfall(PvAmdSolver* s, const float* hz, int nBins, float sliceSeconds, int nSlices);
+/* the setting: up to cap bins into hz (may be NULL), the slice length as given and in steps, the slices (each may be NULL;
+ * written only while a setting exists); returns nBins */
+PVA_EXPORT int PvAmdGetWaterfall(PvAmdSolver* s, float* hz, int cap, float* sliceSeconds, int* sliceSteps, int* nSlices);
+/* F under the current setting, -1 without one */
+PVA_EXPORT int PvAmdWaterfallFloats(PvAmdSolver* s);
+/* Compute the records of the LAST COMPLETED run of s (waits for a run in flight).  Synchronous on the solver's own stream.
+ * *ms (optional): device time of the pass. */
+PVA_EXPORT int PvAmdComputeWaterfall(PvAmdSolver* s, const float* xyz, int nPos, float* ms);
+/* nPos x F floats, receiver-major; nPos = the computed count (the kept emitters' in sparse-emitter mode) */
+PVA_EXPORT int PvAmdCopyWaterfall(PvAmdSolver* s, float* out, int nPos);
+/* CPU only: the definition above applied to one impulse response p[T] with 0 <= onset < T and the pulse table pulseT[T]; the
+ * restatement the tests hold the kernel to.  The setting is checked by the rule of PvAmdSetWaterfall */
+PVA_EXPORT int PvAmdHostWaterfall(const float* p, int T, int fs, int onset, const float* hz, int n, float sliceSeconds, int nSlices,
+                                  const float* pulseT, float* outF);
+
 /* ---- Zone statistics: spatial statistics of a computed map over receiver areas ----
  * ISO 3382-1 reports its quantities as averages over receiver areas, with their spread.  A ZONE is a label per result cell;
  * PvAmdComputeZoneStats reduces one computed map of the nine kinds above to one record per zone and plane ON THE DEVICE

@@ -29,6 +29,13 @@ def echogram_setting(s):
     return float(v[0]), int(v[1])
 
 
+def waterfall_bins(s):
+    v = s.split(",")
+    if len(v) != 3 or int(v[2]) < 1:
+        raise argparse.ArgumentTypeError("expected F0,F1,N")
+    return np.linspace(float(v[0]), float(v[1]), int(v[2])).astype(np.float32)
+
+
 def rect4(s):
     v = [float(x) for x in s.split(",")]
     if len(v) != 4:
@@ -179,6 +186,12 @@ def main(argv=None):
                          "(bare flag: 0.01,0.08)")
     ap.add_argument("--spectrum", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the transfer function (re, im, level in dB re the source) of each emitter's cell at these frequencies")
+    ap.add_argument("--waterfall", metavar="F0,F1,N", type=waterfall_bins,
+                    help="add the waterfall (cumulative spectral decay) of each emitter's cell at the N bins np.linspace(F0, F1, N): "
+                         "the complex response of the whole decay and the level in dB re the source of every slice of "
+                         "--waterfall-slices; works with and without --sparse-emitters (at most %d emitters)" % api.WATERFALL_MAX_RECEIVERS)
+    ap.add_argument("--waterfall-slices", metavar="SEC,M", type=echogram_setting, default=(0.02, 16),
+                    help="with --waterfall: M slices, slice k starting k * SEC seconds after the onset (default 0.02,16)")
     ap.add_argument("--bands", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the band metrics (decay times and clarity of the band-filtered response) of each emitter's cell for "
                          "the bands centred at these frequencies")
@@ -258,6 +271,8 @@ def main(argv=None):
         ap.error("--in-run-records: at most 64 emitters (a run's output queries)")
     if a.sparse_emitters and len(emitters) > api.RECORD_QUERIES_MAX:
         ap.error("--sparse-emitters: at most %d emitters" % api.RECORD_QUERIES_MAX)
+    if a.waterfall is not None and len(emitters) > api.WATERFALL_MAX_RECEIVERS:
+        ap.error("--waterfall: at most %d emitters" % api.WATERFALL_MAX_RECEIVERS)
     with api.Solver(size, size, a.res, device=a.device, **(dict(streaming_analysis=1) if a.sparse_emitters else {})) as s:
         for b in boxes:
             s.add_geometry(b)
@@ -337,6 +352,13 @@ def main(argv=None):
         if whole and a.spectrum:
             s.set_spectrum_bins(a.spectrum)
             s.compute_spectrum()
+        if a.waterfall is not None:  # (one pass over the emitters' cells: the history, or in sparse-emitter mode the traces)
+            s.set_waterfall(a.waterfall, *a.waterfall_slices)
+            s.compute_waterfall(None if a.sparse_emitters else emitters)
+            wf = s.waterfall()
+            if a.sparse_emitters:
+                wf = dict((k, per_position(v)) for k, v in wf.items())
+            wf_hz, wf_seconds, wf_steps, _ = s.waterfall_setting()
         for i, e in enumerate(emitters):
             o = s.get_output(e)
             ga, gb, gc = api.reverb_bus_gains(o.rt60, o.wetGain)
@@ -380,6 +402,11 @@ def main(argv=None):
                 m = s.spectrum_at(e) if whole else qspec[api.QSPEC_SPECTRUM][i]
                 out["emitters"][-1]["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],
                                                    "im": [float(v) for v in m[:, 1]], "levelDb": [float(v) for v in m[:, 2]]}
+            if a.waterfall is not None:
+                out["emitters"][-1]["waterfall"] = {
+                    "hz": [float(v) for v in wf_hz], "sliceSeconds": wf_seconds, "sliceSteps": wf_steps, "onset": float(wf["onset"][i]),
+                    "re": [float(v) for v in wf["response"][i, :, 0]], "im": [float(v) for v in wf["response"][i, :, 1]],
+                    "levelDb": [[float(v) for v in row] for row in wf["level"][i]]}
         if a.zone:
             out["zones"] = zone_tables(s, a)
         if a.emission_records:

@@ -371,6 +371,12 @@ SYMBOLS = {
     "PvAmdGetSpectrum": (C.c_int, [_vp] + [C.c_float] * 3 + [_fp]),
     "PvAmdHostSpectrumTables": (C.c_int, [C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
     "PvAmdHostSpectrum": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp]),
+    "PvAmdSetWaterfall": (C.c_int, [_vp, _fp, C.c_int, C.c_float, C.c_int]),
+    "PvAmdGetWaterfall": (C.c_int, [_vp, _fp, C.c_int, _fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "PvAmdWaterfallFloats": (C.c_int, [_vp]),
+    "PvAmdComputeWaterfall": (C.c_int, [_vp, _fp, C.c_int, _fp]),
+    "PvAmdCopyWaterfall": (C.c_int, [_vp, _fp, C.c_int]),
+    "PvAmdHostWaterfall": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_float, C.c_int, _fp, _fp]),
     "PvAmdSetZones": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int]),
     "PvAmdGetZones": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "PvAmdZoneStatPlanes": (C.c_int, [_vp, C.c_int]),
@@ -1127,6 +1133,35 @@ def host_spectrum(p, fs, onset, hz, pulse):
     _check(lib().PvAmdHostSpectrum(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(h) if h.size else None,
                                    int(h.size), _f(q) if q.size else None, _f(out)))
     return out
+
+
+WATERFALL_MAX_BINS = 512       # PVA_WATERFALL_MAX_BINS
+WATERFALL_MAX_SLICES = 64      # PVA_WATERFALL_MAX_SLICES
+WATERFALL_MAX_RECEIVERS = 256  # PVA_WATERFALL_MAX_RECEIVERS
+
+
+def _waterfall_dict(rec, n, m):
+    """records [N, 2 + 2 n + m n] as the parts of the Waterfall section of include/planeverb_amd.h"""
+    N = rec.shape[0]
+    return {"onset": rec[:, 0].copy(), "slices": rec[:, 1].copy(),
+            "response": np.stack([rec[:, 2:2 + n], rec[:, 2 + n:2 + 2 * n]], axis=-1),
+            "level": rec[:, 2 + 2 * n:].reshape(N, m, n).copy()}
+
+
+def host_waterfall(p, fs, onset, hz, slice_seconds, n_slices, pulse):
+    """PvAmdHostWaterfall: the record of one impulse response p[T] with its onset step and the pulse table pulse[T] -- the
+    waterfall definition of include/planeverb_amd.h on the CPU -- as the dict Solver.waterfall returns for N = 1: onset [1],
+    slices [1], response [1, n, 2] (R, I of slice 0), level [1, m, n] (dB re the source)"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    q = np.ascontiguousarray(pulse, np.float32).reshape(-1)
+    h = np.ascontiguousarray(hz, np.float32).reshape(-1)
+    if q.size != a.size:
+        raise ValueError("the pulse table and the impulse response differ in length")
+    n, m = int(h.size), int(n_slices)
+    out = np.empty((1, 2 + 2 * n + max(m, 0) * n), np.float32)
+    _check(lib().PvAmdHostWaterfall(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(h) if h.size else None, n,
+                                    float(slice_seconds), m, _f(q) if q.size else None, _f(out)))
+    return _waterfall_dict(out, n, m)
 
 
 ZMAP_ROOM_METRICS, ZMAP_SPECTRUM = 1, 2  # PVA_ZMAP_*: the map kinds of Solver.set_zone_maps
@@ -2369,6 +2404,51 @@ class Solver:
     def spectrum_at(self, pos):
         """float32 [n, 3] at an emitter position (the cell get_output reads); NaNs off the map"""
         return self._map_at(lib().PvAmdGetSpectrum, pos, len(self.spectrum_bins()), 3)
+
+    def set_waterfall(self, hz, slice_seconds=0.0, n_slices=0):
+        """the bins (Hz, at most WATERFALL_MAX_BINS, each in [0, fs / 2]) and the slices (n_slices of slice_seconds each, at most
+        WATERFALL_MAX_SLICES) compute_waterfall evaluates; uploads the tables; an empty list clears the setting and frees the
+        device storage"""
+        h = np.ascontiguousarray(hz, np.float32).reshape(-1)
+        _check(lib().PvAmdSetWaterfall(self._h, _f(h) if h.size else None, int(h.size), float(slice_seconds), int(n_slices)))
+
+    def waterfall_setting(self):
+        """(hz float32 [n], slice_seconds, slice_steps, n_slices) as set; None without a setting"""
+        hz = np.empty(WATERFALL_MAX_BINS, np.float32)
+        sec, steps, m = C.c_float(0.0), C.c_int(0), C.c_int(0)
+        n = lib().PvAmdGetWaterfall(self._h, _f(hz), WATERFALL_MAX_BINS, C.byref(sec), C.byref(steps), C.byref(m))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return (hz[:n].copy(), sec.value, steps.value, m.value) if n else None
+
+    def compute_waterfall(self, positions=None):
+        """the waterfalls of the last completed run at `positions` ([N, 3], mapped to cells as set_output_queries maps them) --
+        on a sparse-emitter solver positions = None: the receivers are the emitters set_emitters kept --, on the device; returns
+        the device time of the pass in milliseconds"""
+        ms = C.c_float(0.0)
+        if positions is None:
+            _check(lib().PvAmdComputeWaterfall(self._h, None, 0, C.byref(ms)))
+            self._waterfall_count = len(self.emitter_cells())
+        else:
+            xyz = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+            _check(lib().PvAmdComputeWaterfall(self._h, _f(xyz) if xyz.size else None, int(xyz.shape[0]), C.byref(ms)))
+            self._waterfall_count = int(xyz.shape[0])
+        return ms.value
+
+    def waterfall(self, count=None):
+        """the records compute_waterfall left: onset [N] and slices [N] (the onset step, the slices that start inside the run),
+        response [N, n, 2] (R, I of slice 0: X(f) = R - i I) and level [N, m, n] (dB re the source, slice-major); NaN rows for
+        receivers without an onset in that run.  count: the computed receivers (default: those of the last compute_waterfall of
+        this object -- the kept emitters on a sparse-emitter solver)"""
+        st = self.waterfall_setting()
+        if st is None:
+            _check(lib().PvAmdCopyWaterfall(self._h, _f(np.empty(1, np.float32)), 0))  # (raises with the library's words)
+        n, m = len(st[0]), st[3]
+        if count is None:
+            count = getattr(self, "_waterfall_count", 0)
+        rec = np.empty((int(count), 2 + 2 * n + m * n), np.float32)
+        _check(lib().PvAmdCopyWaterfall(self._h, _f(rec), int(count)))
+        return _waterfall_dict(rec, n, m)
 
     def set_zones(self, labels, n_zones=None):
         """the zones zone_stats reduces over: labels = uint8 [gx, gy], 0 = no zone, 1 .. n_zones (at most ZONES_MAX; None: the

@@ -23,6 +23,7 @@
 #include "pv_query_records.h"
 #include "pv_query_spectral.h"
 #include "pv_spectrum.h"
+#include "pv_waterfall.h"
 #include "pv_zone_band_decay.h"
 #include "pv_zone_decay.h"
 #include "pv_zones.h"
@@ -1691,6 +1692,48 @@ int PvAmdGetSpectrum(PvAmdSolver* h, float ex, float ey, float ez, float* out3n)
     return analysisGet(h, kMapSpectrum, "", __func__, ex, ez, out3n);
 } PV_API_CATCH(-1)
 
+// waterfall (pv_waterfall.hip, pv_solver_waterfall.cpp; the setting: pv_waterfall.h waterfallSettingError)
+static_assert(PVA_WATERFALL_MAX_BINS == kWaterfallMaxBins && PVA_WATERFALL_MAX_SLICES == kWaterfallMaxSlices &&
+                  PVA_WATERFALL_MAX_RECEIVERS == kWaterfallMaxReceivers,
+              "planeverb_amd.h vs pv_waterfall.h");
+
+int PvAmdSetWaterfall(PvAmdSolver* h, const float* hz, int nBins, float sliceSeconds, int nSlices) try {
+    if (!h) {
+        g_lastError = "null solver handle";
+        return -1;
+    }
+    if (nBins != 0) {
+        if (const char* e = waterfallSettingError(hz, nBins, (int)h->spec.fs, sliceSeconds, nSlices)) {
+            g_lastError = e;
+            return -1;
+        }
+    }
+    if (!analysisHandle(h, "waterfall: ")) return -1;
+    return ret(h, h->s->setWaterfall(hz, nBins, sliceSeconds, nSlices));
+} PV_API_CATCH(-1)
+
+int PvAmdGetWaterfall(PvAmdSolver* h, float* hz, int cap, float* sliceSeconds, int* sliceSteps, int* nSlices) try {
+    if (!analysisHandle(h, "waterfall: ")) return -1;
+    return h->s->waterfall(hz, cap, sliceSeconds, sliceSteps, nSlices);
+} PV_API_CATCH(-1)
+
+int PvAmdWaterfallFloats(PvAmdSolver* h) try {
+    if (!analysisHandle(h, "waterfall: ")) return -1;
+    const int f = h->s->waterfallRecordFloats();
+    if (f < 0) g_lastError = "waterfall: no setting (PvAmdSetWaterfall)";
+    return f;
+} PV_API_CATCH(-1)
+
+int PvAmdComputeWaterfall(PvAmdSolver* h, const float* xyz, int nPos, float* ms) try {
+    if (!analysisHandle(h, "waterfall: ")) return -1;
+    return ret(h, h->s->computeWaterfall(xyz, nPos, ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyWaterfall(PvAmdSolver* h, float* out, int nPos) try {
+    if (!analysisCall(h, "waterfall: ", __func__, out)) return -1;
+    return ret(h, h->s->copyWaterfall(out, nPos));
+} PV_API_CATCH(-1)
+
 // zone statistics (pv_zones.hip; the labels: pv_zones.h zoneLabelsError)
 static_assert(sizeof(PvAmdZoneStat) == sizeof(ZoneStat), "64 bytes");
 static_assert(PVA_MAP_ROOM_METRICS == kMapRoomMetrics && PVA_MAP_SPECTRUM == kMapSpectrum && PVA_MAP_SPECTRUM + 1 == kAnalysisKinds,
@@ -2333,6 +2376,23 @@ int PvAmdHostSpectrum(const float* p, int T, int fs, int onset, const float* hz,
     spectrumTables(T, fs, hz, n, c.data(), s.data());
     spectrumSource(pulseT, T, c.data(), s.data(), n, src.data());
     spectrumOfIr(p, T, onset, c.data(), s.data(), n, src.data(), out3n);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostWaterfall(const float* p, int T, int fs, int onset, const float* hz, int n, float sliceSeconds, int nSlices, const float* pulseT,
+                       float* outF) try {
+    if (!p || !pulseT || !outF || T <= 0 || fs <= 0 || onset < 0 || onset >= T) {
+        g_lastError = "waterfall: PvAmdHostWaterfall: an impulse response p[T] and a pulse table of T floats, T > 0, fs > 0, 0 <= onset < T and an output of 2 + 2 n + m n floats";
+        return -1;
+    }
+    if (const char* e = waterfallSettingError(hz, n, fs, sliceSeconds, nSlices)) {
+        g_lastError = e;
+        return -1;
+    }
+    std::vector<float> c((size_t)T * n), s((size_t)T * n), src((size_t)3 * n);
+    spectrumTables(T, fs, hz, n, c.data(), s.data());
+    spectrumSource(pulseT, T, c.data(), s.data(), n, src.data());
+    waterfallOfIr(p, T, onset, c.data(), s.data(), n, waterfallSliceSteps(sliceSeconds, fs), nSlices, src.data(), outF);
     return 0;
 } PV_API_CATCH(-1)
 

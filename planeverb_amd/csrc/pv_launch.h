@@ -251,6 +251,32 @@ constexpr int kSpectrumTablePad = 64;
 bool spectrumBlockOk(int block);
 void launchSpectrum(const AnalyzeArgs& a, int block, int bins, const float* tab, const float* spow, float* out, hipStream_t stream);
 
+// ---- pv_waterfall.hip: per-receiver waterfalls (cumulative spectral decay)
+// Where a receiver's samples are and what of them may be read: sample t at samples[offset + t * stride], never below tLoad (the
+// larger of the onset and the first recorded step of the cell's tile; INT_MAX: nothing); onset < 0: no record (F quiet NaNs)
+struct WaterfallRx {
+    long long offset, stride;
+    int onset, tLoad;
+};
+struct WaterfallArgs {
+    const float* samples;   // the history (a.hist), or the emitter traces of sparse-emitter mode
+    const WaterfallRx* rx;  // nPos receivers
+    const float* tab;       // per block of 64 bins: kWaterfallTablePad zero rows, then rows 0 .. T - 1, each 64 {cos, sin} pairs
+                            // (the bins past n zero)
+    const float* spow;      // n source powers
+    float* rec;             // nPos records of waterfallFloats(n, m) floats (pv_waterfall.h)
+    int nPos, n, m, ns, T;
+};
+constexpr int kWaterfallTablePad = 128;
+// the receiver table of `cells` (result cell X * gy + Y, -1: off the map; device-visible) from the last run's window, onset map and
+// tileFirst; trace: receiver i's samples are row i of the emitter traces [nPos][T] instead of the history
+void launchWaterfallReceivers(const AnalyzeArgs& a, const long long* cells, int nPos, bool trace, WaterfallRx* rx, hipStream_t stream);
+// one pass with `block` receivers to a wave (waterfallBlockOk(block)); waterfallBlockFor: the block the launcher's rule picks on a
+// device of `cus` compute units (speed only: a record's bits do not depend on the block)
+bool waterfallBlockOk(int block);
+int waterfallBlockFor(int n, int nPos, int cus);
+void launchWaterfall(const WaterfallArgs& a, int block, hipStream_t stream);
+
 // ---- pv_copy.hip: read-backs and copies
 // slab halos: src[i] -> dst[i] for up to six blocks of n floats (n % 4 == 0, 16-byte aligned); dst[i] = NULL skips a block
 void launchHaloPush(const float* const src[6], float* const dst[6], long long n, const HaloHandoff& hand, hipStream_t stream);

@@ -377,6 +377,18 @@ public:
     int spectrumBins(float* hz, int cap) const;
     bool spectrumSource(float* out3n);
     bool computeSpectrum(float* ms);
+    // Waterfall (pv_solver_waterfall.cpp, pv_waterfall.hip; include/planeverb_amd.h names the record): the cumulative spectral decay
+    // of up to kWaterfallMaxReceivers receivers of the last completed run at the bins and slices set here.  setWaterfall: the
+    // caller has validated the setting (pv_waterfall.h waterfallSettingError); n = 0 clears and frees; waits for a run in flight;
+    // uploads the tables.  computeWaterfall: positions mapped as setOutputQueries maps them -- on a sparse-emitter solver xyz =
+    // nullptr, nPos = 0 and the receivers are the registered emitters, their samples the emitter traces; synchronised before it
+    // returns, *ms (optional) = its device time.  The records stay valid until the next run, geometry, boundary or layer change,
+    // change of the setting or, in sparse-emitter mode, of the emitters; they and the nine map kinds do not touch each other
+    bool setWaterfall(const float* hz, int n, float sliceSeconds, int nSlices);
+    int waterfall(float* hz, int cap, float* sliceSeconds, int* sliceSteps, int* nSlices) const;
+    int waterfallRecordFloats() const;  // -1 without a setting
+    bool computeWaterfall(const float* xyz, int nPos, float* ms);
+    bool copyWaterfall(float* out, int nPos);
     // The reductions over zones: pv_solver_zones.cpp.
     // Zone statistics (pv_zones.hip; include/planeverb_amd.h PvAmdZoneStat): a label per result cell, 0 = no zone, 1 .. nZones;
     // computeZoneStats reduces the valid map of one kind to nZones x planes records on the device -- no host copy of the map,
@@ -651,6 +663,7 @@ private:
     hipEvent_t mapEv_[2] = {nullptr, nullptr};
     void invalidateAnalysisMaps() {
         for (AnalysisMap& m : maps_) m.valid = false;
+        wfValid_ = false;  // (the waterfall's records have the maps' lifetime)
     }
     void dropAnalysisMap(AnalysisKind k, bool freeDev);  // a changed setting: records invalid, the device storage freed on request
     bool analysisSettingPresent(AnalysisKind k) const;
@@ -696,6 +709,23 @@ private:
     std::vector<SpecPass> specPasses_;
     float* specTab_ = nullptr;
     float* specPow_ = nullptr;
+    // waterfall (pv_waterfall.h): the setting; on the device from the setter on the tables as pv_waterfall.hip reads them (per
+    // block of 64 bins: kWaterfallTablePad zero rows and T rows of 64 {cos, sin} pairs -- 2 x 4 x T x n bytes for n a multiple of
+    // 64: 104 MB at T = 25 432 and 512 bins) and the source powers, the cell and receiver tables (kWaterfallMaxReceivers entries);
+    // from the first compute on the records, wfCount_ x F floats (at most 34.6 MB), reallocated when the count or F changes
+    std::vector<float> wfHz_;
+    float wfSeconds_ = 0.f;
+    int wfSteps_ = 0, wfSlices_ = 0;
+    float* wfTab_ = nullptr;
+    float* wfPow_ = nullptr;
+    long long* wfCells_ = nullptr;
+    void* wfRx_ = nullptr;  // WaterfallRx (pv_launch.h)
+    float* wfRec_ = nullptr;
+    size_t wfRecFloats_ = 0;
+    int wfCount_ = 0;
+    int wfCus_ = 0;  // the device's compute units: how many receivers a wave takes (pv_launch.h waterfallBlockFor)
+    bool wfValid_ = false;
+    void freeWaterfall();
     // zone statistics (pv_zones.h): the labels on the device and as given, and the pass's scratch -- per plane in flight, zone and
     // result row one ZoneRow and one double (48 bytes), the planes dealt in chunks that keep it within kZoneScratchBytes (one
     // plane's where that is more), then the nZones x planes records; grown on demand, kept.  The zone-decay pass uses the same

@@ -25,16 +25,29 @@ namespace pva {
 constexpr int kSpectrumMaxBins = 32;  // PVA_SPECTRUM_MAX_BINS
 constexpr int kSpectrumFloats = 3;    // re, im, level per bin
 
+// the rule of a list of bins with the cap as a parameter (the waterfall, pv_waterfall.h, shares it with a larger one): what is wrong
+enum BinsFault { kBinsOk, kBinsCount, kBinsNull, kBinsNotFinite, kBinsNegative, kBinsAboveNyquist };
+inline BinsFault spectrumBinsFault(const float* hz, int n, int fs, int cap) {
+    if (n < 1 || n > cap) return kBinsCount;
+    if (!hz) return kBinsNull;
+    for (int j = 0; j < n; ++j) {
+        if (!std::isfinite(hz[j])) return kBinsNotFinite;
+        if (hz[j] < 0.f) return kBinsNegative;
+        if ((double)hz[j] > 0.5 * (double)fs) return kBinsAboveNyquist;
+    }
+    return kBinsOk;
+}
+
 // the rule PvAmdSetSpectrumBins and the host calls share; nullptr: fine, else what is wrong
 inline const char* spectrumBinsError(const float* hz, int n, int fs) {
-    if (n < 1 || n > kSpectrumMaxBins) return "spectrum: 1 .. 32 bins (PVA_SPECTRUM_MAX_BINS)";
-    if (!hz) return "spectrum: null frequency list";
-    for (int j = 0; j < n; ++j) {
-        if (!std::isfinite(hz[j])) return "spectrum: a frequency that is not finite";
-        if (hz[j] < 0.f) return "spectrum: a negative frequency";
-        if ((double)hz[j] > 0.5 * (double)fs) return "spectrum: a frequency above fs / 2";
+    switch (spectrumBinsFault(hz, n, fs, kSpectrumMaxBins)) {
+        case kBinsCount: return "spectrum: 1 .. 32 bins (PVA_SPECTRUM_MAX_BINS)";
+        case kBinsNull: return "spectrum: null frequency list";
+        case kBinsNotFinite: return "spectrum: a frequency that is not finite";
+        case kBinsNegative: return "spectrum: a negative frequency";
+        case kBinsAboveNyquist: return "spectrum: a frequency above fs / 2";
+        default: return nullptr;
     }
-    return nullptr;
 }
 
 inline void spectrumTables(int T, int fs, const float* hz, int n, float* c, float* s) {
