@@ -1416,6 +1416,87 @@ PVA_EXPORT int PvAmdCopyWaterfall(PvAmdSolver* s, float* out, int nPos);
 PVA_EXPORT int PvAmdHostWaterfall(const float* p, int T, int fs, int onset, const float* hz, int n, float sliceSeconds, int nSlices,
                                   const float* pulseT, float* outF);
 
+/* ---- Source arrays: the combined response of weighted, delayed emitters ----
+ * Every other record here is for one source and one receiver.  A delayed fill system, a line of ceiling speakers or a steered
+ * sub array heard at a seat -- or, by reciprocity, a delay-and-sum microphone array listening to one source -- is a SUM: the
+ * stencil is linear and the recorded pressure at cell c is the response between the listener and c, so the response of an array
+ * at the listener is  sum_k g_k h_k(t - tau_k)  over its members' recorded responses.  PvAmdComputeArrays forms that sum on the
+ * device (pv_arrays.hip) from what the LAST COMPLETED run left there -- the pressure history, or in sparse-emitter mode the
+ * emitters' traces -- and computes the selected records of every sum.  Definition (T = the run's steps, PvAmdInfo::T):
+ *   setting   nArrays in 1 .. PVA_ARRAYS_MAX; array a has count[a] members, 1 .. PVA_ARRAY_MEMBERS_MAX; a member is five floats
+ *             {x, y, z, gain, delaySeconds}, the members of array 0 first; a negative gain is polarity; interp is
+ *             PVA_ARRAY_NEAREST or PVA_ARRAY_LAGRANGE3;
+ *   cell      a member's position maps to a result cell exactly as PvAmdSetOutputQueries maps its positions; a member off the map
+ *             is refused at set time; a member in a wall, or in a cell the run's history window does not hold, is legal and
+ *             contributes zeros.  p_m(t) is what PvAmdCopyHistoryPlane(t) returns at the member's cell: +0 where nothing was
+ *             stored, and +0 for t < 0.  Samples below the member's own onset are included;
+ *   taps      on the host, in double: d = (double)delaySeconds * (double)fs; refused unless gain and delaySeconds are finite,
+ *             delaySeconds >= 0 and d < T; n = floor(d), mu = d - n.
+ *               NEAREST               one tap {delay = (int)floor(d + 0.5), w = gain}; a delay that rounds to T is refused
+ *               LAGRANGE3, mu == 0    one tap {n, gain}
+ *               LAGRANGE3, mu != 0    n >= 1 is required; four taps at delays n - 1, n, n + 1, n + 2, with D = mu + 1.0 and
+ *                                       L0 = -((D - 1) (D - 2) (D - 3)) / 6     L1 = (D (D - 2) (D - 3)) / 2
+ *                                       L2 = -(D (D - 1) (D - 3)) / 2           L3 = (D (D - 1) (D - 2)) / 6
+ *                                     each product evaluated left to right in double, w_j = (float)((double)gain * L_j); taps
+ *                                     whose delay is >= T are kept and contribute nothing;
+ *   response  y_a(t), t = 0 .. T - 1, starts from +0.0f; over the array's members in the given order and each member's taps in
+ *             increasing delay:  y = y + (w * p_m(t - delay)).  All arithmetic is float32, every product and every sum rounded on
+ *             its own, nothing fused, denormals kept;
+ *   onset     the reference's rule (Analyzer.cpp:146-165) applied to y_a: the first t with fabsf(y_a(t)) > 0.00000316f as a
+ *             float, else FLT_MAX; NaN compares false;
+ *   records   for the selected kinds among PVA_QREC_ROOM_METRICS, PVA_QREC_DECAY_TIMES, PVA_QREC_ECHO_CRITERION,
+ *             PVA_QSPEC_BAND_METRICS, PVA_QSPEC_MODULATION and PVA_QSPEC_SPECTRUM the record of array a is by definition
+ *             PvAmdHost<Kind>(y_a, T, fs, onset_a, ...) under the solver's current bands, modulation frequencies, bins and pulse;
+ *             an array without an onset gives quiet NaNs.  The three velocity kinds are refused: a mix has no cell and no face
+ *             coefficients.
+ * A response's bits depend on its own members and taps alone: not on the other arrays, their order or its index.
+ * Sparse-emitter mode: every member's cell must be the cell of a kept registered emitter (PvAmdSetEmitters); this is checked by
+ * PvAmdComputeArrays, which names the array and the member; the samples are the emitter traces, and no emitter-record kind needs
+ * to be selected.
+ * Device storage, only while arrays are set: the tables and the mix planes, T x P x 4 bytes with P = nArrays rounded up to 64
+ * (26 MB at T = 25 432 and 256 arrays); the record block from the first compute with a kind selected.
+ * Lifetime: a run, a geometry, boundary or layer change, a successful PvAmdSetArrays or a changed PvAmdSetArrayRecords, a
+ * PvAmdSetBands / PvAmdSetModulationFrequencies / PvAmdSetSpectrumBins while a dependent kind is selected and, in sparse-emitter
+ * mode, a change of the emitters invalidate what PvAmdComputeArrays left; the read-backs then return -1.  With no arrays set
+ * nothing is allocated or launched, and a run enqueues exactly what it does without this section.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "arrays: ..."): slab groups and slab ranks, PVA_OPT_SKIP_ANALYSIS, no
+ * completed run or a last run in error, counts out of range, NULL tables, a bad member or interp, an unknown or velocity kind, a
+ * band or spectrum kind without bands or bins, the sampling-rate floor of the echo criterion, a read-back whose count, kind or
+ * stamp does not match. */
+#define PVA_ARRAYS_MAX        256
+#define PVA_ARRAY_MEMBERS_MAX 64
+#define PVA_ARRAY_NEAREST     0
+#define PVA_ARRAY_LAGRANGE3   1
+/* Set the arrays (copied): count[nArrays], members5 = five floats per member, array 0's members first.  nArrays = 0 clears the
+ * setting and frees everything.  Waits for a run in flight.  A refused or failed call leaves the setting of before */
+PVA_EXPORT int PvAmdSetArrays(PvAmdSolver* s, const int* count, int nArrays, const float* members5, int interp);
+/* the setting: up to cap counts (may be NULL) and interp (may be NULL; written only while a setting exists); returns nArrays */
+PVA_EXPORT int PvAmdGetArrays(PvAmdSolver* s, int* count, int cap, int* interp);
+/* the expanded taps of one array in the order the response takes them: up to cap of {member index inside the array, delay in
+ * steps, weight} (each may be NULL); returns the tap count, -1: no such array */
+PVA_EXPORT int PvAmdGetArrayTaps(PvAmdSolver* s, int array, int* memberIndex, int* delaySteps, float* weight, int cap);
+/* the record kinds PvAmdComputeArrays computes for every array: PVA_QREC_* bits (room metrics, decay times, echo criterion) and
+ * PVA_QSPEC_* bits; 0, 0 selects none.  Independent of the output queries' and the emitters' selections */
+PVA_EXPORT int PvAmdSetArrayRecords(PvAmdSolver* s, unsigned timeKinds, unsigned spectralKinds);
+PVA_EXPORT int PvAmdGetArrayRecordKinds(PvAmdSolver* s, unsigned* timeKinds, unsigned* spectralKinds);
+/* floats per array of ONE kind under the current settings; family 0: PVA_QREC_*, family 1: PVA_QSPEC_* */
+PVA_EXPORT int PvAmdArrayRecordFloats(PvAmdSolver* s, int family, unsigned kind);
+/* Mix, onsets and the selected records of the LAST COMPLETED run of s (waits for a run in flight).  Synchronous on the solver's
+ * own stream.  *ms (optional): device time of the call's kernels */
+PVA_EXPORT int PvAmdComputeArrays(PvAmdSolver* s, float* ms);
+/* y_a(t), T floats */
+PVA_EXPORT int PvAmdCopyArrayResponse(PvAmdSolver* s, int array, float* outT);
+/* the onsets of all arrays (FLT_MAX: none); nArrays = the arrays set */
+PVA_EXPORT int PvAmdGetArrayOnsets(PvAmdSolver* s, float* out, int nArrays);
+/* nArrays x floats of one selected kind, array-major: the layout of PvAmdGetEmitterRecords */
+PVA_EXPORT int PvAmdGetArrayRecords(PvAmdSolver* s, int family, unsigned kind, float* out, int nArrays);
+/* CPU only: the taps of one member by the rule above; returns the tap count (1 or 4) with delay4 / w4 written, or -1 */
+PVA_EXPORT int PvAmdHostArrayTaps(int fs, int T, float gain, float delaySeconds, int interp, int* delay4, float* w4);
+/* CPU only: the response of one array from its members' responses pMT[M][T] and its taps in order (tapMember in 0 .. M - 1; a
+ * sample at t - delay outside 0 .. T - 1 is +0): outT[T], *onset (optional) by the rule above */
+PVA_EXPORT int PvAmdHostArrayResponse(const float* pMT, int M, int T, const int* tapMember, const int* tapDelay,
+                                      const float* tapWeight, int nTaps, float* outT, float* onset);
+
 /* ---- Zone statistics: spatial statistics of a computed map over receiver areas ----
  * ISO 3382-1 reports its quantities as averages over receiver areas, with their spread.  A ZONE is a label per result cell;
  * PvAmdComputeZoneStats reduces one computed map of the nine kinds above to one record per zone and plane ON THE DEVICE

@@ -36,6 +36,17 @@ def waterfall_bins(s):
     return np.linspace(float(v[0]), float(v[1]), int(v[2])).astype(np.float32)
 
 
+def array_members(s):
+    """one array: x,z,gain,delay;x,z,gain,delay;... -> [((x, 0, z), gain, delaySeconds)]"""
+    out = []
+    for part in s.split(";"):
+        v = [float(x) for x in part.split(",")]
+        if len(v) != 4:
+            raise argparse.ArgumentTypeError("expected x,z,gain,delay;x,z,gain,delay;...")
+        out.append(((v[0], 0.0, v[1]), v[2], v[3]))
+    return out
+
+
 def rect4(s):
     v = [float(x) for x in s.split(",")]
     if len(v) != 4:
@@ -192,6 +203,14 @@ def main(argv=None):
                          "--waterfall-slices; works with and without --sparse-emitters (at most %d emitters)" % api.WATERFALL_MAX_RECEIVERS)
     ap.add_argument("--waterfall-slices", metavar="SEC,M", type=echogram_setting, default=(0.02, 16),
                     help="with --waterfall: M slices, slice k starting k * SEC seconds after the onset (default 0.02,16)")
+    ap.add_argument("--array", metavar="X,Z,GAIN,DELAY[;X,Z,GAIN,DELAY...]", type=array_members, action="append", default=[],
+                    help="a source array, repeatable (one array per flag, at most %d of at most %d members): the combined response "
+                         "at the listener of members at x, z with a gain (negative: polarity) and a delay in seconds, mixed on the "
+                         "GPU; adds an \"arrays\" list with each array's onset and its records of --room-metrics, --decay-times, "
+                         "--echo-criterion, --bands, --modulation and --spectrum; works with and without --sparse-emitters (there "
+                         "the members' positions are added to the registered emitters)" % (api.ARRAYS_MAX, api.ARRAY_MEMBERS_MAX))
+    ap.add_argument("--array-interp", choices=("nearest", "lagrange3"), default="lagrange3",
+                    help="with --array: a member's delay rounded to a step, or a third-order Lagrange fractional delay (default)")
     ap.add_argument("--bands", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the band metrics (decay times and clarity of the band-filtered response) of each emitter's cell for "
                          "the bands centred at these frequencies")
@@ -297,7 +316,8 @@ def main(argv=None):
             if a.spectrum:
                 s.set_spectrum_bins(a.spectrum)
             if a.sparse_emitters:
-                s.set_emitters(emitters)
+                # (the members of --array read the traces of registered emitters: theirs follow the emitters asked for)
+                s.set_emitters(list(emitters) + [m[0] for arr in a.array for m in arr])
                 s.set_emitter_records(kinds, spectral)
                 if a.zone:  # (the curves of --zone-decay absolute are accumulated inside the run)
                     s.set_zones(api.zone_labels_from_rects(s.dx, s.gx, s.gy, a.zone), len(a.zone))
@@ -359,6 +379,46 @@ def main(argv=None):
             if a.sparse_emitters:
                 wf = dict((k, per_position(v)) for k, v in wf.items())
             wf_hz, wf_seconds, wf_steps, _ = s.waterfall_setting()
+        if a.array:  # (one mix of the members' responses per array: off the history, or in sparse-emitter mode off the traces)
+            # (the bands and the bins are set by now: in front of the run, or with the whole-map passes above)
+            s.set_arrays(a.array, api.ARRAY_NEAREST if a.array_interp == "nearest" else api.ARRAY_LAGRANGE3)
+            s.set_array_records((api.QREC_ROOM_METRICS if a.room_metrics else 0) | (api.QREC_DECAY_TIMES if a.decay_times else 0) |
+                                (api.QREC_ECHO_CRITERION if a.echo_criterion else 0),
+                                (api.QSPEC_BAND_METRICS if a.bands else 0) | (api.QSPEC_MODULATION if a.modulation else 0) |
+                                (api.QSPEC_SPECTRUM if a.spectrum else 0))
+            s.compute_arrays()
+            onsets = s.array_onsets()
+            out["arrays"] = []
+            for i, arr in enumerate(a.array):
+                tm, td, tw = s.array_taps(i)
+                rec = {"members": [{"position": list(m[0]), "gain": m[1], "delaySeconds": m[2]} for m in arr], "interp": a.array_interp,
+                       "taps": {"member": [int(v) for v in tm], "delaySteps": [int(v) for v in td], "weight": [float(v) for v in tw]},
+                       "onset": float(onsets[i]) if onsets[i] < 1e30 else None}
+                out["arrays"].append(rec)
+            if a.room_metrics:
+                for rec, m in zip(out["arrays"], s.array_records(api.QREC_ROOM_METRICS)):
+                    rec["roomMetrics"] = dict((n, float(v)) for n, v in zip(api.ROOM_METRIC_NAMES, m))
+            if a.decay_times:
+                for rec, m in zip(out["arrays"], s.array_records(api.QREC_DECAY_TIMES)):
+                    rec["decayTimes"] = dict((n, float(v)) for n, v in zip(api.DECAY_TIME_NAMES, m))
+            if a.echo_criterion:
+                for rec, m in zip(out["arrays"], s.array_records(api.QREC_ECHO_CRITERION)):
+                    rec["echoCriterion"] = dict((n, float(v)) for n, v in zip(api.ECHO_CRITERION_NAMES, m))
+            if a.bands:
+                for rec, m in zip(out["arrays"], s.array_records(api.QSPEC_BAND_METRICS, spectral=True).reshape(len(a.array), -1, 12)):
+                    rec["bandMetrics"] = [
+                        dict([("hz", float(hz)), ("fraction", a.band_fraction)] + [(n, float(v)) for n, v in zip(api.BAND_METRIC_NAMES, r)])
+                        for hz, r in zip(a.bands, m)]
+            if a.modulation:
+                for rec, m in zip(out["arrays"], s.array_records(api.QSPEC_MODULATION, spectral=True).reshape(len(a.array), -1, 15)):
+                    rec["modulation"] = {
+                        "hz": [float(v) for v in s.modulation_frequencies()],
+                        "bands": [{"hz": float(hz), "fraction": a.band_fraction, "m": [float(v) for v in r[:-1]], "mti": float(r[-1])}
+                                  for hz, r in zip(a.bands, m)]}
+            if a.spectrum:
+                for rec, m in zip(out["arrays"], s.array_records(api.QSPEC_SPECTRUM, spectral=True).reshape(len(a.array), -1, 3)):
+                    rec["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],
+                                       "im": [float(v) for v in m[:, 1]], "levelDb": [float(v) for v in m[:, 2]]}
         for i, e in enumerate(emitters):
             o = s.get_output(e)
             ga, gb, gc = api.reverb_bus_gains(o.rt60, o.wetGain)

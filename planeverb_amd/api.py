@@ -377,6 +377,18 @@ SYMBOLS = {
     "PvAmdComputeWaterfall": (C.c_int, [_vp, _fp, C.c_int, _fp]),
     "PvAmdCopyWaterfall": (C.c_int, [_vp, _fp, C.c_int]),
     "PvAmdHostWaterfall": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_float, C.c_int, _fp, _fp]),
+    "PvAmdSetArrays": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int, _fp, C.c_int]),
+    "PvAmdGetArrays": (C.c_int, [_vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
+    "PvAmdGetArrayTaps": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_int]),
+    "PvAmdSetArrayRecords": (C.c_int, [_vp, C.c_uint, C.c_uint]),
+    "PvAmdGetArrayRecordKinds": (C.c_int, [_vp, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "PvAmdArrayRecordFloats": (C.c_int, [_vp, C.c_int, C.c_uint]),
+    "PvAmdComputeArrays": (C.c_int, [_vp, _fp]),
+    "PvAmdCopyArrayResponse": (C.c_int, [_vp, C.c_int, _fp]),
+    "PvAmdGetArrayOnsets": (C.c_int, [_vp, _fp, C.c_int]),
+    "PvAmdGetArrayRecords": (C.c_int, [_vp, C.c_int, C.c_uint, _fp, C.c_int]),
+    "PvAmdHostArrayTaps": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), _fp]),
+    "PvAmdHostArrayResponse": (C.c_int, [_fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_int, _fp, _fp]),
     "PvAmdSetZones": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int]),
     "PvAmdGetZones": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "PvAmdZoneStatPlanes": (C.c_int, [_vp, C.c_int]),
@@ -1162,6 +1174,40 @@ def host_waterfall(p, fs, onset, hz, slice_seconds, n_slices, pulse):
     _check(lib().PvAmdHostWaterfall(_f(a) if a.size else None, int(a.size), int(fs), int(onset), _f(h) if h.size else None, n,
                                     float(slice_seconds), m, _f(q) if q.size else None, _f(out)))
     return _waterfall_dict(out, n, m)
+
+
+ARRAYS_MAX = 256         # PVA_ARRAYS_MAX
+ARRAY_MEMBERS_MAX = 64   # PVA_ARRAY_MEMBERS_MAX
+ARRAY_NEAREST, ARRAY_LAGRANGE3 = 0, 1  # PVA_ARRAY_*: how a member's delay becomes taps
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def host_array_taps(fs, T, gain, delay_seconds, interp=ARRAY_LAGRANGE3):
+    """PvAmdHostArrayTaps: the taps of one array member (include/planeverb_amd.h, Source arrays) as (delays int32 [n], weights
+    float32 [n]), n = 1 or 4; raises where the member is refused"""
+    d, w = np.zeros(4, np.int32), np.zeros(4, np.float32)
+    n = lib().PvAmdHostArrayTaps(int(fs), int(T), float(gain), float(delay_seconds), int(interp), _ip(d), _f(w))
+    if n < 0:
+        raise PlaneverbError(last_error())
+    return d[:n].copy(), w[:n].copy()
+
+
+def host_array_response(p, tap_member, tap_delay, tap_weight):
+    """PvAmdHostArrayResponse: the response of one array from its members' responses p[M, T] and its taps in order, as
+    (y float32 [T], onset float32 -- FLT_MAX: none)"""
+    a = np.ascontiguousarray(p, np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    m, d = np.ascontiguousarray(tap_member, np.int32).reshape(-1), np.ascontiguousarray(tap_delay, np.int32).reshape(-1)
+    w = np.ascontiguousarray(tap_weight, np.float32).reshape(-1)
+    if not (m.size == d.size == w.size):
+        raise ValueError("the three tap lists differ in length")
+    out, onset = np.empty(a.shape[1], np.float32), C.c_float(0.0)
+    _check(lib().PvAmdHostArrayResponse(_f(a) if a.size else None, int(a.shape[0]), int(a.shape[1]), _ip(m) if m.size else None,
+                                        _ip(d) if d.size else None, _f(w) if w.size else None, int(m.size), _f(out), C.byref(onset)))
+    return out, np.float32(onset.value)
 
 
 ZMAP_ROOM_METRICS, ZMAP_SPECTRUM = 1, 2  # PVA_ZMAP_*: the map kinds of Solver.set_zone_maps
@@ -2449,6 +2495,78 @@ class Solver:
         rec = np.empty((int(count), 2 + 2 * n + m * n), np.float32)
         _check(lib().PvAmdCopyWaterfall(self._h, _f(rec), int(count)))
         return _waterfall_dict(rec, n, m)
+
+    def set_arrays(self, arrays, interp=ARRAY_LAGRANGE3):
+        """the source arrays compute_arrays mixes: a list of arrays, each a list of members (pos, gain, delay_seconds) with pos =
+        (x, y, z); at most ARRAYS_MAX arrays of at most ARRAY_MEMBERS_MAX members; an empty list clears the setting and frees the
+        device storage"""
+        count = np.array([len(a) for a in arrays], np.int32)
+        rows = [[float(p[0]), float(p[1]), float(p[2]), float(g), float(d)] for a in arrays for (p, g, d) in a]
+        mem = np.ascontiguousarray(rows, np.float32).reshape(-1, 5)
+        _check(lib().PvAmdSetArrays(self._h, _ip(count) if count.size else None, int(count.size), _f(mem) if mem.size else None, int(interp)))
+
+    def arrays(self):
+        """(counts int32 [n_arrays], interp) as set; None without a setting"""
+        count, interp = np.zeros(ARRAYS_MAX, np.int32), C.c_int(0)
+        n = lib().PvAmdGetArrays(self._h, _ip(count), ARRAYS_MAX, C.byref(interp))
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return (count[:n].copy(), interp.value) if n else None
+
+    def array_taps(self, i):
+        """the expanded taps of array i in the order its response takes them: (member int32 [n], delay_steps int32 [n], weight
+        float32 [n])"""
+        cap = 4 * ARRAY_MEMBERS_MAX
+        m, d, w = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+        n = lib().PvAmdGetArrayTaps(self._h, int(i), _ip(m), _ip(d), _f(w), cap)
+        if n < 0:
+            raise PlaneverbError(last_error())
+        return m[:n].copy(), d[:n].copy(), w[:n].copy()
+
+    def set_array_records(self, time_kinds, spectral_kinds=0):
+        """the record kinds compute_arrays computes for every array: a mask of QREC_ROOM_METRICS, QREC_DECAY_TIMES,
+        QREC_ECHO_CRITERION and a mask of QSPEC_*; both 0 selects none"""
+        _check(lib().PvAmdSetArrayRecords(self._h, int(time_kinds), int(spectral_kinds)))
+
+    def array_record_kinds(self):
+        """(time kinds, spectral kinds)"""
+        t, f = C.c_uint(0), C.c_uint(0)
+        _check(lib().PvAmdGetArrayRecordKinds(self._h, C.byref(t), C.byref(f)))
+        return int(t.value), int(f.value)
+
+    def compute_arrays(self):
+        """mix, onsets and the selected records of the arrays for the last completed run, on the device; returns the device time
+        in milliseconds"""
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdComputeArrays(self._h, C.byref(ms)))
+        return ms.value
+
+    def array_response(self, i):
+        """float32 [T]: the response of array i as compute_arrays left it"""
+        out = np.empty(self.T, np.float32)
+        _check(lib().PvAmdCopyArrayResponse(self._h, int(i), _f(out)))
+        return out
+
+    def array_onsets(self):
+        """float32 [n_arrays]: the onset step of every response, FLT_MAX where it has none"""
+        st = self.arrays()
+        n = len(st[0]) if st else 0
+        out = np.empty(max(n, 1), np.float32)
+        _check(lib().PvAmdGetArrayOnsets(self._h, _f(out), n))
+        return out[:n]
+
+    def array_records(self, kind, spectral=False):
+        """float32 [n_arrays, floats] of ONE selected kind (QSPEC_* with spectral=True): row a is PvAmdHost<Kind> of array a's
+        response with its onset, NaNs where it has none; the layout of emitter_records"""
+        fam = 1 if spectral else 0
+        floats = lib().PvAmdArrayRecordFloats(self._h, fam, int(kind))
+        if floats < 0:
+            raise PlaneverbError(last_error())
+        st = self.arrays()
+        n = len(st[0]) if st else 0
+        out = np.empty((max(n, 1), floats), np.float32)
+        _check(lib().PvAmdGetArrayRecords(self._h, fam, int(kind), _f(out), n))
+        return out[:n]
 
     def set_zones(self, labels, n_zones=None):
         """the zones zone_stats reduces over: labels = uint8 [gx, gy], 0 = no zone, 1 .. n_zones (at most ZONES_MAX; None: the

@@ -24,6 +24,7 @@
 #include "pv_query_spectral.h"
 #include "pv_spectrum.h"
 #include "pv_waterfall.h"
+#include "pv_arrays.h"
 #include "pv_zone_band_decay.h"
 #include "pv_zone_decay.h"
 #include "pv_zones.h"
@@ -1734,6 +1735,76 @@ int PvAmdCopyWaterfall(PvAmdSolver* h, float* out, int nPos) try {
     return ret(h, h->s->copyWaterfall(out, nPos));
 } PV_API_CATCH(-1)
 
+// source arrays (pv_arrays.hip, pv_solver_arrays.cpp; the definition: pv_arrays.h)
+static_assert(PVA_ARRAYS_MAX == kArraysMax && PVA_ARRAY_MEMBERS_MAX == kArrayMembersMax && PVA_ARRAY_NEAREST == kArrayNearest &&
+                  PVA_ARRAY_LAGRANGE3 == kArrayLagrange3,
+              "planeverb_amd.h vs pv_arrays.h");
+
+int PvAmdSetArrays(PvAmdSolver* h, const int* count, int nArrays, const float* members5, int interp) try {
+    if (!h) {
+        g_lastError = "null solver handle";
+        return -1;
+    }
+    if (nArrays != 0) {  // (what needs no grid, in front of creating a solver)
+        if (const char* e = arraysCountError(count, nArrays, members5)) {
+            g_lastError = e;
+            return -1;
+        }
+    }
+    if (!analysisHandle(h, "arrays: ")) return -1;
+    return ret(h, h->s->setArrays(count, nArrays, members5, interp));
+} PV_API_CATCH(-1)
+
+int PvAmdGetArrays(PvAmdSolver* h, int* count, int cap, int* interp) try {
+    if (!analysisHandle(h, "arrays: ")) return -1;
+    return h->s->arrays(count, cap, interp);
+} PV_API_CATCH(-1)
+
+int PvAmdGetArrayTaps(PvAmdSolver* h, int array, int* memberIndex, int* delaySteps, float* weight, int cap) try {
+    if (!analysisHandle(h, "arrays: ")) return -1;
+    const int n = h->s->arrayTapsOf(array, memberIndex, delaySteps, weight, cap);
+    if (n < 0) ret(h, false);
+    return n;
+} PV_API_CATCH(-1)
+
+int PvAmdSetArrayRecords(PvAmdSolver* h, unsigned timeKinds, unsigned spectralKinds) try {
+    if (!analysisHandle(h, "arrays: ")) return -1;
+    return ret(h, h->s->setArrayRecords(timeKinds, spectralKinds));
+} PV_API_CATCH(-1)
+
+int PvAmdGetArrayRecordKinds(PvAmdSolver* h, unsigned* timeKinds, unsigned* spectralKinds) try {
+    if (!analysisHandle(h, "arrays: ")) return -1;
+    h->s->arrayRecordKinds(timeKinds, spectralKinds);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdArrayRecordFloats(PvAmdSolver* h, int family, unsigned kind) try {
+    if (!analysisHandle(h, "arrays: ")) return -1;
+    const int n = h->s->arrayRecordFloats(family, kind);
+    if (n < 0) ret(h, false);
+    return n;
+} PV_API_CATCH(-1)
+
+int PvAmdComputeArrays(PvAmdSolver* h, float* ms) try {
+    if (!analysisHandle(h, "arrays: ")) return -1;
+    return ret(h, h->s->computeArrays(ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyArrayResponse(PvAmdSolver* h, int array, float* outT) try {
+    if (!analysisCall(h, "arrays: ", __func__, outT)) return -1;
+    return ret(h, h->s->copyArrayResponse(array, outT));
+} PV_API_CATCH(-1)
+
+int PvAmdGetArrayOnsets(PvAmdSolver* h, float* out, int nArrays) try {
+    if (!analysisCall(h, "arrays: ", __func__, out)) return -1;
+    return ret(h, h->s->arrayOnsets(out, nArrays));
+} PV_API_CATCH(-1)
+
+int PvAmdGetArrayRecords(PvAmdSolver* h, int family, unsigned kind, float* out, int nArrays) try {
+    if (!analysisCall(h, "arrays: ", __func__, out)) return -1;
+    return ret(h, h->s->arrayRecords(family, kind, out, nArrays));
+} PV_API_CATCH(-1)
+
 // zone statistics (pv_zones.hip; the labels: pv_zones.h zoneLabelsError)
 static_assert(sizeof(PvAmdZoneStat) == sizeof(ZoneStat), "64 bytes");
 static_assert(PVA_MAP_ROOM_METRICS == kMapRoomMetrics && PVA_MAP_SPECTRUM == kMapSpectrum && PVA_MAP_SPECTRUM + 1 == kAnalysisKinds,
@@ -2393,6 +2464,37 @@ int PvAmdHostWaterfall(const float* p, int T, int fs, int onset, const float* hz
     spectrumTables(T, fs, hz, n, c.data(), s.data());
     spectrumSource(pulseT, T, c.data(), s.data(), n, src.data());
     waterfallOfIr(p, T, onset, c.data(), s.data(), n, waterfallSliceSteps(sliceSeconds, fs), nSlices, src.data(), outF);
+    return 0;
+} PV_API_CATCH(-1)
+
+// source arrays: the taps of one member and the response of one array (pv_arrays.h), as the device computes them
+int PvAmdHostArrayTaps(int fs, int T, float gain, float delaySeconds, int interp, int* delay4, float* w4) try {
+    if (!delay4 || !w4) {
+        g_lastError = "arrays: PvAmdHostArrayTaps: room for four delays and four weights";
+        return -1;
+    }
+    const char* why = nullptr;
+    const int n = arrayTaps(fs, T, gain, delaySeconds, interp, delay4, w4, &why);
+    if (n < 0) g_lastError = why;
+    return n;
+} PV_API_CATCH(-1)
+
+int PvAmdHostArrayResponse(const float* pMT, int M, int T, const int* tapMember, const int* tapDelay, const float* tapWeight, int nTaps,
+                           float* outT, float* onset) try {
+    if (!pMT || !outT || M < 1 || T < 1 || nTaps < 0 || (nTaps > 0 && (!tapMember || !tapDelay || !tapWeight))) {
+        g_lastError = "arrays: PvAmdHostArrayResponse: member responses pMT[M][T], M > 0, T > 0, nTaps taps and an output of T floats";
+        return -1;
+    }
+    std::vector<ArrayTap> taps((size_t)nTaps);
+    for (int k = 0; k < nTaps; ++k) {
+        if (tapMember[k] < 0 || tapMember[k] >= M) {
+            g_lastError = "arrays: PvAmdHostArrayResponse: a tap of a member outside 0 .. M - 1";
+            return -1;
+        }
+        taps[(size_t)k] = ArrayTap{tapMember[k], tapDelay[k], tapWeight[k], 0};
+    }
+    const float on = arrayResponse(pMT, T, taps.data(), nTaps, outT);
+    if (onset) *onset = on;
     return 0;
 } PV_API_CATCH(-1)
 

@@ -277,6 +277,29 @@ bool waterfallBlockOk(int block);
 int waterfallBlockFor(int n, int nPos, int cus);
 void launchWaterfall(const WaterfallArgs& a, int block, hipStream_t stream);
 
+// ---- pv_arrays.hip: source arrays (the combined response of weighted, delayed members; pv_arrays.h)
+// Where a member's samples are: sample t at samples[offset + t * stride], never below tLoad (its tile's first recorded step, 0 for
+// an emitter trace; INT_MAX: no samples -- a cell outside the run's history window)
+struct ArrayRow {
+    long long offset, stride;
+    int tLoad, pad;
+};
+struct ArrayTap;
+struct ArrayMixArgs {
+    const float* samples;  // the history (a.hist), or the emitter traces of sparse-emitter mode
+    const ArrayRow* rows;  // one per member of the setting, in the setting's order
+    const ArrayTap* taps;  // array a's taps at tapOff[a] .. tapOff[a + 1] - 1, row = the member's index into rows
+    const int* tapOff;     // nArrays + 1 entries
+    float* mix;            // planes [T][P]: y_a(t) at mix[t * P + a]; columns nArrays .. P - 1 are written as zero
+    int nArrays, P, T;     // P = nArrays rounded up to 64
+};
+// the member rows of `src` (device-visible; per member its result cell X * gy + Y, or with trace the index of the registered emitter
+// whose trace it reads) from the last run's window and tileFirst
+void launchArrayRows(const AnalyzeArgs& a, const long long* src, int nRows, bool trace, ArrayRow* rows, hipStream_t stream);
+void launchArrayMix(const ArrayMixArgs& a, hipStream_t stream);
+// onsets[0 .. P): the first step of column a of the mix planes above the onset threshold as a float, FLT_MAX: none (and for a >= nArrays)
+void launchArrayOnsets(const float* mix, int T, int P, int nArrays, float* onsets, hipStream_t stream);
+
 // ---- pv_copy.hip: read-backs and copies
 // slab halos: src[i] -> dst[i] for up to six blocks of n floats (n % 4 == 0, 16-byte aligned); dst[i] = NULL skips a block
 void launchHaloPush(const float* const src[6], float* const dst[6], long long n, const HaloHandoff& hand, hipStream_t stream);

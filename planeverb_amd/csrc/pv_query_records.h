@@ -39,6 +39,7 @@ struct QueryRecordArgs {
     int nDs, nDm, nLs, nLm;  // echo criterion
     LobeEdges ed;            // lobes
     int nW;
+    int mix;                 // the lanes are source arrays, a.hist their mix planes, a.delay their onsets (cells is not read)
 };
 
 }  // namespace pva

@@ -14,6 +14,9 @@
 // In sparse-emitter mode (PvAmdSetEmitterRecords) the same kernel serves the registered emitters: the history planes are the
 // emitters' record traces and a lane's offsets are its columns there (recordLaneOfTrace); the bodies do not know the difference.
 //
+// For the source arrays (PvAmdComputeArrays, pv_arrays.hip) the same kernel serves the arrays after a completed run: the history
+// planes are the mix planes and a lane's offset is its column there (recordLaneOfMix); the record block is device memory.
+//
 // Lanes at or above nq have no slot and no cell; a query off the map, outside the window or without an onset gets quiet NaNs.
 // The stores are plain vector stores to host-coherent memory; they are visible to the host when the stream has drained, as
 // pv_gather_queries_kernel's are.
@@ -43,8 +46,10 @@ namespace {
 static_assert(PV_METRICS_S <= 8 && PV_DECAY_S <= 8 && PV_LATERAL_S <= 8 && PV_ECHOGRAM_S <= 8 && PV_ECHO_S <= 8 && PV_LOBES_S <= 8,
               "launchQueryRecords chooses the one-descriptor-per-chunk form for chunks of at most 8 planes");
 
-// TRACE: the lanes are the registered emitters of sparse-emitter mode and the history is their record traces (recordLaneOfTrace)
-template <bool CHUNK, bool TRACE>
+// FORM (pv_record_lane.h RecordLaneForm): kLaneCell, the registered queries' cells; kLaneTrace, the lanes are the registered emitters
+// of sparse-emitter mode and the history is their record traces (recordLaneOfTrace); kLaneMix, the lanes are the source arrays and
+// the history is their mix planes (recordLaneOfMix) -- a mix has no cell, so the three velocity kinds are not in that form
+template <bool CHUNK, int FORM>
 __global__ __launch_bounds__(64) void pv_query_records_kernel(const AnalyzeArgs a, const QueryRecordArgs q) {
     __shared__ double logTab[96];
     __shared__ double powLt[32];
@@ -68,8 +73,7 @@ __global__ __launch_bounds__(64) void pv_query_records_kernel(const AnalyzeArgs 
     const DynParams dyn = *a.dyn;
     const int i = 64 * (int)blockIdx.y + lane;  // the query (the group is wave-uniform)
     const bool slot = i < q.nq;
-    const long long cell = slot ? q.cells[i] : -1;
-    const RecordLane ln = TRACE ? recordLaneOfTrace(a, dyn, cell, i, slot) : recordLaneOfCell(a, dyn, cell, slot);
+    const RecordLane ln = recordLaneOfForm<FORM>(a, dyn, q.cells, i, slot);
     // (a lane without a slot never stores: it is not live, and the NaN fill asks for the slot)
     const SlotStore out{q.out + q.offset[kind] + (long long)(slot ? i : 0) * q.floats[kind]};
     switch (kind) {
@@ -80,16 +84,16 @@ __global__ __launch_bounds__(64) void pv_query_records_kernel(const AnalyzeArgs 
             decayTimesBody<PV_DECAY_S, PV_DECAY_NB, CHUNK, 0>(a, ln, out, LogTabLds{logTab}, q.tailN);
             break;
         case kQrecLateral:
-            lateralBody<PV_LATERAL_S, PV_LATERAL_NB, CHUNK>(a, dyn, ln, out, q.n5, q.latN80);
+            if constexpr (FORM != kLaneMix) lateralBody<PV_LATERAL_S, PV_LATERAL_NB, CHUNK>(a, dyn, ln, out, q.n5, q.latN80);
             break;
         case kQrecEchogram:
-            echogramBody<PV_ECHOGRAM_S, PV_ECHOGRAM_NB, CHUNK>(a, dyn, ln, out, q.ns, q.nSlots);
+            if constexpr (FORM != kLaneMix) echogramBody<PV_ECHOGRAM_S, PV_ECHOGRAM_NB, CHUNK>(a, dyn, ln, out, q.ns, q.nSlots);
             break;
         case kQrecEchoCriterion:
             echoBody<PV_ECHO_S, PV_ECHO_NB, CHUNK>(a, ln, out, PowTabLds{powLt, powEt}, q.nDs, q.nDm, q.nLs, q.nLm);
             break;
         case kQrecLobes:
-            lobesBody<PV_LOBES_S, PV_LOBES_NB, CHUNK>(a, dyn, ln, out, q.ed, q.nW);
+            if constexpr (FORM != kLaneMix) lobesBody<PV_LOBES_S, PV_LOBES_NB, CHUNK>(a, dyn, ln, out, q.ed, q.nW);
             break;
         default: break;
     }
@@ -103,12 +107,15 @@ void launchQueryRecords(const AnalyzeArgs& a, const QueryRecordArgs& q, hipStrea
     const dim3 grid((unsigned)__builtin_popcount(q.kinds), (unsigned)((q.nq + 63) / 64));
     // (the largest chunk of the six passes is 8 planes: one descriptor per chunk below 2^31 bytes, as in their own launchers)
     // (record traces -- a.hist = a.recTrace, planes of at most 3 x 1024 floats -- always take the chunk form)
-    if (a.recTrace)
-        hipLaunchKernelGGL((pv_query_records_kernel<true, true>), grid, dim3(64), 0, stream, a, q);
+    // (mix planes -- q.mix, a.hist = the planes of at most kArraysMax floats -- too)
+    if (q.mix)
+        hipLaunchKernelGGL((pv_query_records_kernel<true, kLaneMix>), grid, dim3(64), 0, stream, a, q);
+    else if (a.recTrace)
+        hipLaunchKernelGGL((pv_query_records_kernel<true, kLaneTrace>), grid, dim3(64), 0, stream, a, q);
     else if (a.histPlane * 4 * 8 < (1ll << 31))
-        hipLaunchKernelGGL((pv_query_records_kernel<true, false>), grid, dim3(64), 0, stream, a, q);
+        hipLaunchKernelGGL((pv_query_records_kernel<true, kLaneCell>), grid, dim3(64), 0, stream, a, q);
     else
-        hipLaunchKernelGGL((pv_query_records_kernel<false, false>), grid, dim3(64), 0, stream, a, q);
+        hipLaunchKernelGGL((pv_query_records_kernel<false, kLaneCell>), grid, dim3(64), 0, stream, a, q);
 }
 
 }  // namespace pva

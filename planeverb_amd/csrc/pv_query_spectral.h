@@ -40,6 +40,7 @@ struct QuerySpectralArgs {
     const float* specTab;                     // spectrum: the device tables of all slices, and the bins' source powers
     const float* specPow;
     QuerySpectralSlice slice[kQspecMaxSlices];
+    int mix;                 // the lanes are source arrays, a.hist their mix planes, a.delay their onsets (cells is not read)
 };
 
 }  // namespace pva

@@ -28,6 +28,9 @@
 // In sparse-emitter mode (PvAmdSetEmitterRecords) the same kernel serves the registered emitters from their record traces
 // (recordLaneOfTrace), as pv_query_records.hip does.
 //
+// For the source arrays (PvAmdComputeArrays) the lanes are the arrays and the history is their mix planes (recordLaneOfMix), as in
+// pv_query_records.hip.
+//
 // Lanes at or above nq have no slot and no cell; a query off the map, outside the window or without an onset gets quiet NaNs.
 // The stores are plain vector stores to host-coherent memory, all behind the loops; they are visible to the host when the stream
 // has drained.  The device tables are uploaded where the kinds are selected and where the settings change (both wait for a run in
@@ -55,8 +58,9 @@ static_assert(PV_BANDS_S <= 8 && PV_MODULATION_S <= 8 && PV_SPECTRUM_S <= 8,
               "launchQuerySpectral chooses the one-descriptor-per-chunk form for chunks of at most 8 planes");
 static_assert(PV_BANDS_B <= kBandsMax && kBandsMax + PV_BANDS_B - 1 <= kQspecCoefSets, "the padded last block of bands reads zero sets");
 
-// TRACE: the lanes are the registered emitters of sparse-emitter mode and the history is their record traces (recordLaneOfTrace)
-template <bool CHUNK, bool TRACE>
+// FORM (pv_record_lane.h RecordLaneForm): the registered queries' cells, the registered emitters of sparse-emitter mode with their
+// record traces as the history (recordLaneOfTrace), or the source arrays with their mix planes (recordLaneOfMix)
+template <bool CHUNK, int FORM>
 __global__ __launch_bounds__(64) void pv_query_spectral_kernel(const AnalyzeArgs a, const QuerySpectralArgs q) {
     __shared__ double logTab[96];
     // the work item (wave-uniform): kind and ordinal inside the kind
@@ -70,8 +74,7 @@ __global__ __launch_bounds__(64) void pv_query_spectral_kernel(const AnalyzeArgs
     const DynParams dyn = *a.dyn;
     const int i = 64 * (int)blockIdx.y + lane;  // the query (the group is wave-uniform)
     const bool slot = i < q.nq;
-    const long long cell = slot ? q.cells[i] : -1;
-    const RecordLane ln = TRACE ? recordLaneOfTrace(a, dyn, cell, i, slot) : recordLaneOfCell(a, dyn, cell, slot);
+    const RecordLane ln = recordLaneOfForm<FORM>(a, dyn, q.cells, i, slot);
     // (a lane without a slot never stores: it is not live, and the NaN fill asks for the slot)
     float* rec = q.out + q.offset[kind] + (long long)(slot ? i : 0) * q.floats[kind];
     switch (kind) {
@@ -116,12 +119,15 @@ void launchQuerySpectral(const AnalyzeArgs& a, const QuerySpectralArgs& q, hipSt
     const dim3 grid((unsigned)(q.items[0] + q.items[1] + q.items[2]), (unsigned)((q.nq + 63) / 64));
     // (the largest chunk of the three passes is 8 planes: one descriptor per chunk below 2^31 bytes, as in their own launchers)
     // (record traces -- a.hist = a.recTrace, planes of at most 3 x 1024 floats -- always take the chunk form)
-    if (a.recTrace)
-        hipLaunchKernelGGL((pv_query_spectral_kernel<true, true>), grid, dim3(64), 0, stream, a, q);
+    // (mix planes -- q.mix, a.hist = the planes of at most kArraysMax floats -- too)
+    if (q.mix)
+        hipLaunchKernelGGL((pv_query_spectral_kernel<true, kLaneMix>), grid, dim3(64), 0, stream, a, q);
+    else if (a.recTrace)
+        hipLaunchKernelGGL((pv_query_spectral_kernel<true, kLaneTrace>), grid, dim3(64), 0, stream, a, q);
     else if (a.histPlane * 4 * 8 < (1ll << 31))
-        hipLaunchKernelGGL((pv_query_spectral_kernel<true, false>), grid, dim3(64), 0, stream, a, q);
+        hipLaunchKernelGGL((pv_query_spectral_kernel<true, kLaneCell>), grid, dim3(64), 0, stream, a, q);
     else
-        hipLaunchKernelGGL((pv_query_spectral_kernel<false, false>), grid, dim3(64), 0, stream, a, q);
+        hipLaunchKernelGGL((pv_query_spectral_kernel<false, kLaneCell>), grid, dim3(64), 0, stream, a, q);
 }
 
 }  // namespace pva

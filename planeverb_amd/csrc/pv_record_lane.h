@@ -1,11 +1,13 @@
 // pv_record_lane.h -- which cell a lane of a per-cell record pass owns, and where its record goes.  The bodies of the record
 // passes (pv_metrics_dev.h, pv_decay_dev.h, pv_lateral_dev.h, pv_echogram_dev.h, pv_echo_dev.h, pv_lobes_dev.h) take both from
-// their caller, so the one body serves two kernels:
+// their caller, so the one body serves several lane forms:
 //  * the whole-map pass (pv_metrics.hip ...): lane = a consecutive OFFSET g of a history plane, record float k at out[k * plane + g];
 //  * the in-run query pass (pv_query_records.hip): lane i = registered output query i, g = the history offset of its cell, record
 //    float k at rec[k] of the query's slot in pinned host memory.
 //  * the emitter pass of sparse-emitter mode (the same two kernels): lane i = registered emitter i, g = its COLUMN of the record
 //    traces, which stand in for the history planes (recordLaneOfTrace).
+//  * the array pass (pv_arrays.hip, the same two kernels): lane i = source array i, g = its COLUMN of the mix planes, which stand in
+//    for the history planes, its onset from the table of the responses' own onsets (recordLaneOfMix).
 // Everything a body computes depends on the lane's own cell alone (time is wave-uniform, but what a lane adds at a step is decided
 // by selects on its own ranges), so the bits of a record do not depend on which other cells share the wave.
 #pragma once
@@ -132,6 +134,39 @@ __device__ __forceinline__ RecordLane recordLaneOfTrace(const AnalyzeArgs& a, co
     l.live = l.delay != FLT_MAX;
     recordLaneFirstSteps(a, l);
     return l;
+}
+
+// array pass (pv_arrays.hip, pv_solver_arrays.cpp): lane i = array i of the setting.  `a.hist` / `a.histPlane` are the mix planes'
+// ([T][P], a response being a column) and `a.delay` is the table of the responses' own onsets (P floats, FLT_MAX: none), so the
+// lane's offset is its COLUMN and its onset comes from that table.  A mix has no cell: no face coefficients, no neighbours, and
+// every step of a column was written, so the first steps are 0.  The velocity kinds are never launched with this lane
+__device__ __forceinline__ RecordLane recordLaneOfMix(const AnalyzeArgs& a, int i, bool slot) {
+    RecordLane l;
+    l.slot = slot;
+    l.g = slot && i < a.histPlane ? i : a.histPlane;
+    l.pc = PlaneCell{false, 0, 0, 0, 0, 0, 0, 0, 0};
+    l.hasX = l.hasY = false;
+    l.gX = l.gY = 0;
+    l.delay = l.g < a.histPlane ? a.delay[l.g] : FLT_MAX;
+    l.live = l.delay != FLT_MAX;
+    l.tFirst = l.live ? 0 : a.T;
+    l.tFx = l.tFy = INT_MAX;
+    return l;
+}
+
+// which of the three a record launch's lanes are
+enum RecordLaneForm { kLaneCell = 0, kLaneTrace = 1, kLaneMix = 2 };
+template <int FORM>
+__device__ __forceinline__ RecordLane recordLaneOfForm(const AnalyzeArgs& a, const DynParams& dyn, const long long* cells, int i, bool slot) {
+    if constexpr (FORM == kLaneMix) {
+        return recordLaneOfMix(a, i, slot);
+    } else {
+        const long long cell = slot ? cells[i] : -1;
+        if constexpr (FORM == kLaneTrace)
+            return recordLaneOfTrace(a, dyn, cell, i, slot);
+        else
+            return recordLaneOfCell(a, dyn, cell, slot);
+    }
 }
 
 // where a record goes: float k of the lane's record

@@ -698,6 +698,7 @@ Solver::~Solver() {
     for (float* p : {modTab_, specTab_, specPow_})
         if (p) hipFree(p);
     freeWaterfall();
+    freeArrays();
     for (unsigned char* p : {zoneLabels_, zoneScratch_})
         if (p) hipFree(p);
     freeZoneCurves();
@@ -3187,6 +3188,7 @@ bool Solver::setEmitters(const float* xyz, int n) {
         if (!dalloc(&emCells_, cells.size(), true) || !dalloc(&emTrace_, cells.size() * T_, true)) {
             numEmitters_ = 0;
             wfValid_ = false;  // (no emitters are left: the waterfall's records are nobody's)
+            arValid_ = false;
             return false;
         }
         emCap_ = (int)cells.size();
@@ -3199,6 +3201,7 @@ bool Solver::setEmitters(const float* xyz, int n) {
     for (size_t i = 0; i < cells.size(); ++i) emRecCells_[i] = cells[i];
     streamedOnce_ = false;  // (emTrace_'s rows are the old table's)
     wfValid_ = false;       // (and so are the waterfall's records)
+    arValid_ = false;       // (and what computeArrays mixed from them)
     numEmitters_ = (int)cells.size();
     // The uploads go through stream_, behind the zero fill dalloc() queued there (a synchronous hipMemcpy is not ordered with
     // a non-blocking stream: the fill could land AFTER it and leave every emitter at cell 0 -- seen as wet gain / RT60 = 0 in

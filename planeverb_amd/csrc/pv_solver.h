@@ -389,6 +389,24 @@ public:
     int waterfallRecordFloats() const;  // -1 without a setting
     bool computeWaterfall(const float* xyz, int nPos, float* ms);
     bool copyWaterfall(float* out, int nPos);
+    // Source arrays (pv_solver_arrays.cpp, pv_arrays.hip; the definition: pv_arrays.h): the combined response of weighted, delayed
+    // members at the listener, up to kArraysMax arrays of up to kArrayMembersMax members, mixed on the device from the history (in
+    // sparse-emitter mode: the emitter traces) of the last completed run; the onset of every response; and the selected record
+    // kinds of every response through the query record kernels (recordLaneOfMix).  setArrays: nArrays = 0 clears and frees; a
+    // refused or failed call leaves the setting of before; waits for a run in flight.  computeArrays is synchronised before it
+    // returns, *ms (optional) = its device time.  What it leaves stays valid until the next run, geometry, boundary or layer
+    // change, a successful setter, a change of bands / modulation frequencies / bins while a dependent kind is selected or, in
+    // sparse-emitter mode, a change of the emitters
+    bool setArrays(const int* count, int nArrays, const float* members5, int interp);
+    int arrays(int* count, int cap, int* interp) const;
+    int arrayTapsOf(int array, int* memberIndex, int* delaySteps, float* weight, int cap);  // the tap count, -1: no such array
+    bool setArrayRecords(unsigned timeKinds, unsigned spectralKinds);
+    void arrayRecordKinds(unsigned* timeKinds, unsigned* spectralKinds) const;
+    int arrayRecordFloats(int family, unsigned kind);  // -1: not one kind of the family, or its setting is missing
+    bool computeArrays(float* ms);
+    bool copyArrayResponse(int array, float* outT);
+    bool arrayOnsets(float* out, int nArrays);
+    bool arrayRecords(int family, unsigned kind, float* out, int nArrays);
     // The reductions over zones: pv_solver_zones.cpp.
     // Zone statistics (pv_zones.hip; include/planeverb_amd.h PvAmdZoneStat): a label per result cell, 0 = no zone, 1 .. nZones;
     // computeZoneStats reduces the valid map of one kind to nZones x planes records on the device -- no host copy of the map,
@@ -664,6 +682,7 @@ private:
     void invalidateAnalysisMaps() {
         for (AnalysisMap& m : maps_) m.valid = false;
         wfValid_ = false;  // (the waterfall's records have the maps' lifetime)
+        arValid_ = false;  // (and so has what computeArrays left)
     }
     void dropAnalysisMap(AnalysisKind k, bool freeDev);  // a changed setting: records invalid, the device storage freed on request
     bool analysisSettingPresent(AnalysisKind k) const;
@@ -726,6 +745,37 @@ private:
     int wfCus_ = 0;  // the device's compute units: how many receivers a wave takes (pv_launch.h waterfallBlockFor)
     bool wfValid_ = false;
     void freeWaterfall();
+    // source arrays (pv_arrays.h): the setting as given and its expanded tap table (tap.row = the member's index in the setting's
+    // order); on the device from the setter on the taps, their offsets per array, the members' sources and rows, the mix planes
+    // [T][arP_] (arP_ = the arrays rounded up to 64: 26 MB at T = 25 432 and 256 arrays) and the onsets; from the first compute
+    // with a kind selected on the record block.  Nothing of it exists while no arrays are set
+    std::vector<int> arCount_;
+    std::vector<float> arMembers_;     // five floats per member
+    std::vector<long long> arCells_;   // per member: its result cell
+    std::vector<int> arTapOffHost_;    // nArrays + 1
+    std::vector<int> arTapRow_, arTapDelay_;
+    std::vector<float> arTapW_;
+    int arInterp_ = 0, arP_ = 0;
+    void* arTaps_ = nullptr;  // ArrayTap (pv_arrays.h)
+    int* arTapOff_ = nullptr;
+    long long* arSrc_ = nullptr;
+    void* arRows_ = nullptr;  // ArrayRow (pv_launch.h)
+    float* arMix_ = nullptr;
+    float* arOnsets_ = nullptr;
+    float* arRec_ = nullptr;
+    size_t arRecCap_ = 0;
+    unsigned arKinds_[kRecordFamilies] = {0u, 0u};
+    // what the last computeArrays left: the stamp, the onsets and the records on the host, a kind's block of nArrays x floats at its offset
+    bool arValid_ = false;
+    unsigned arRunKinds_[kRecordFamilies] = {0u, 0u};
+    int arRunFloats_[kRecordFamilies][kQueryRecordKinds] = {};
+    size_t arRunOffset_[kRecordFamilies][kQueryRecordKinds] = {};
+    std::vector<float> arOnsetsHost_, arRecHost_;
+    void freeArrays();
+    std::string arrayKindsRefusal(unsigned timeKinds, unsigned spectralKinds) const;
+    void invalidateArrays(unsigned spectralKinds) {  // a changed band, modulation or bin setting
+        if (arKinds_[kRecSpectral] & spectralKinds) arValid_ = false;
+    }
     // zone statistics (pv_zones.h): the labels on the device and as given, and the pass's scratch -- per plane in flight, zone and
     // result row one ZoneRow and one double (48 bytes), the planes dealt in chunks that keep it within kZoneScratchBytes (one
     // plane's where that is more), then the nZones x planes records; grown on demand, kept.  The zone-decay pass uses the same

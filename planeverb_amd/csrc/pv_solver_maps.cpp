@@ -358,6 +358,7 @@ bool Solver::setBands(const float* centreHz, int n, int fraction) {
     dropAnalysisMap(kMapBandMetrics, n == 0);
     dropAnalysisMap(kMapModulation, n == 0);  // (the modulation records are per band)
     invalidateRecords(kRecSpectral, kQspecBandKinds);  // (the records in the pinned block are the old bands')
+    invalidateArrays(kQspecBandKinds);
     bandHz_.clear();
     bandCoefs_.clear();
     if (n == 0) return true;
@@ -403,6 +404,7 @@ bool Solver::setModulationFrequencies(const float* hz14) {
     modTabValid_ = false;
     for (int i = 0; i < kModFreqs; ++i) modHz_[i] = hz14 ? hz14[i] : kModDefaultHz[i];
     invalidateRecords(kRecSpectral, 1u << kQspecModulation);  // (the records in the pinned block are the old frequencies')
+    invalidateArrays(1u << kQspecModulation);
     // (the next run's launch reads the table: never uploaded from the enqueue path)
     return !(recs_[kRecSpectral].kinds & (1u << kQspecModulation)) || ensureModTable();
 }
@@ -453,6 +455,7 @@ bool Solver::setSpectrumBins(const float* hz, int n) {
         return fail("spectrum: the bins cannot be cleared while PVA_ZMAP_SPECTRUM is selected (PvAmdSetZoneMaps)");
     dropAnalysisMap(kMapSpectrum, n == 0);
     invalidateRecords(kRecSpectral, 1u << kQspecSpectrum);  // (the records in the pinned block are the old bins')
+    invalidateArrays(1u << kQspecSpectrum);
     for (float** p : {&specTab_, &specPow_})
         if (*p) {
             hipFree(*p);
