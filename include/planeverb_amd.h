@@ -235,7 +235,30 @@ typedef struct PvAmdTimings {
                                many of them make the next run's analysis look for an audible sample before anything else */
 } PvAmdTimings;
 
-/* option keys for PvAmdSetOption (must be set before the first run) */
+/* option keys for PvAmdSetOption (must be set before the first run)
+ *
+ * Run length (PVA_OPT_NUM_STEPS, numSteps).  Any numSteps > 0 is a run, and every record below means at that T what its
+ * definition says with T = numSteps: no length is refused, clamped or special-cased, and nothing is extrapolated past the
+ * record.  A RUN SHORTER than a definition's window ends the window at T:
+ *   - the eight outputs: the dry window [onset, min(onset + nDry, T)) and the wet window behind it are cut by T; a cell with
+ *     fewer than nDry + 2 + nCut steps between its onset and T is a late-onset cell (every reached cell of a run that short):
+ *     samples past T read as zero, the decay-time regression ends at T - nCut, which may lie below its start or below step 0, and
+ *     rt60 is what the reference's formula gives for the sums over that range -- +inf over an empty one, NaN over a single
+ *     step (0 / 0) --, nothing special-cased.  A run of one step reaches no cell: every onset is FLT_MAX;
+ *   - decay times, band metrics, zone decay: tEnd = T - tailN may be <= t0, or <= 0 when T <= tailN; then no step enters a fit,
+ *     every range is incomplete (NaN), depth is NaN, and E0 is still the sum over [t0, T);
+ *   - the 50 / 80 ms limits: where t0 + n50 >= T the late energy l50 is +0.0f, so c50 is what IEEE gives for e50 / 0 and d50 is 1
+ *     (l80 likewise); the lateral fraction sums over [onset, min(onset + n80, T)); the echo criterion's late windows are empty;
+ *   - echogram slots, lobe windows and waterfall slices that begin at or past T hold their +0.0f sums (a waterfall level of
+ *     -inf, and `slices` counts the others); one cut by T holds its partial sums;
+ *   - an array member's taps past T - 1 read +0.0f; a delay of T steps or more is refused by PvAmdSetArrays, at every T;
+ *   - sparse-emitter mode accumulates in passes of min(roundUp(T, K), 8 K) steps and returns the same bits as a solver that
+ *     keeps its history, whether T is less than one pass, exactly one or two, or one step more.
+ * An EXTENDED RUN (numSteps above the grid's own T) injects nothing after the grid's T -- the pulse table is zero from there --
+ * and goes on stepping and recording: planes 0 .. T_grid - 1, the onset map, and every output whose windows end below T_grid
+ * are those of the default run; every sum defined "to T" (E0, rt60's range, tEnd, the spectrum, the modulation) runs to
+ * numSteps.  tests/test_host_run_lengths.py and tests/test_gpu_run_lengths.py hold the host restatements and the kernels to
+ * this at 39 lengths from 1 to 500 steps. */
 enum {
     PVA_OPT_DENSE_HISTORY = 1, /* 1 = record every tile every step (no zero-tile skipping) */
     PVA_OPT_NUM_STEPS = 2,     /* override T (extension); 0 = reference value */

@@ -109,7 +109,7 @@ def efree_of(oracle, g):
 
 
 def hist_ts(T):
-    return sorted({0, 17, min(200, T - 1), T - 1})
+    return sorted({0, min(17, T - 1), min(200, T - 1), T - 1})
 
 
 def record(ring, prev, cells, keep_cube=False):

@@ -25,9 +25,10 @@ TILE = (12, 12)  # 144 cells a tile: one poisoned cell in each
 FLT_MAX = np.float32(np.finfo(np.float32).max)
 
 
-def block():
+def block(T=T):
     """(recorded history [T, A, B], onset map [A, B]): a front that leaves cell (5, 7) at one cell a step, decaying noise behind it,
-    a 4 x 4 wall that never sounds; onsets 0 .. 3 steps behind the front, T - 1 and T - 3 planted, none in the wall"""
+    a 4 x 4 wall that never sounds; onsets 0 .. 3 steps behind the front, T - 1 and T - 3 planted, none in the wall.  In a run too
+    short for the front to arrive (tests/test_host_run_lengths.py) a cell has no onset, and every onset lies in [t_first, T - 1]"""
     rng = np.random.default_rng(SEED)
     X, Y = np.meshgrid(np.arange(A), np.arange(B), indexing="ij")
     t_first = np.abs(X - 5) + np.abs(Y - 7)
@@ -38,7 +39,8 @@ def block():
     hist[:, wall] = 0
     delay = (t_first + rng.integers(0, 4, (A, B))).astype(np.float32)
     delay[20, 20], delay[21, 3] = T - 1, T - 3
-    delay[wall] = FLT_MAX
+    delay = np.clip(delay, t_first, T - 1).astype(np.float32)  # (changes nothing where T > 37: the front has passed every cell)
+    delay[wall | (t_first >= T)] = FLT_MAX
     return hist, delay
 
 
