@@ -1520,6 +1520,95 @@ PVA_EXPORT int PvAmdHostArrayTaps(int fs, int T, float gain, float delaySeconds,
 PVA_EXPORT int PvAmdHostArrayResponse(const float* pMT, int M, int T, const int* tapMember, const int* tapDelay,
                                       const float* tapWeight, int nTaps, float* outT, float* onset);
 
+/* ---- Auralisation: audio-rate responses and their convolution with dry signals ----
+ * Every record above is a number ABOUT a response.  The response itself leaves the library only raw, at the grid's own rate
+ * fs = PvAmdInfo::fs (1443 Hz at the 70 x 70 preset, 84 351 Hz at 4096 x 4096): no audio tool takes that rate.  This section
+ * resamples recorded responses to an audio rate with a Kaiser-windowed sinc and convolves them with dry signals, both on the device
+ * (pv_aural.hip), so a run can be listened to.  It is the PHYSICAL path the recorded history makes possible, not the reference's
+ * parametric PlaneverbDSP renderer.  Definition (T = the run's steps, PvAmdInfo::T; all device arithmetic float32, every product and
+ * every sum rounded on its own, nothing fused, denormals kept; the device evaluates no transcendental function):
+ *   setting   rate, an int in 1000 .. 384000; zeroCrossings Z, an int in 2 .. 64; beta, the Kaiser window's parameter, finite in
+ *             0 .. 20;
+ *   tables    built at set time on the host, in double:
+ *               c = rate < fs ? (double)rate / (double)fs : 1.0        half = (double)Z / c        K = 2 * (int)floor(half) + 1
+ *               L = (int)floor(((double)(T - 1) * (double)rate) / (double)fs) + 1   -- the response length in output samples: the
+ *                   last n whose source time is <= T - 1
+ *               for n = 0 .. L - 1:  u = ((double)n * (double)fs) / (double)rate,  first[n] = (int)ceil(u - half)
+ *               for slot j = 0 .. K - 1:  t = first[n] + j,  d = u - (double)t;
+ *                   fabs(d) > half:  w[n][j] = +0.0f
+ *                   else  a = c * d,  sinc = (a == 0.0) ? 1.0 : sin(M_PI * a) / (M_PI * a),  q = d / half,  q = 1.0 - q * q,
+ *                         if (q < 0.0) q = 0.0,  w[n][j] = (float)((c * sinc) * (I0(beta * sqrt(q)) / I0(beta)))
+ *               I0(x):  s = 1.0, term = 1.0, h = 0.5 * x;  for k = 1 .. 60:  term = term * ((h / k) * (h / k)),  s = s + term
+ *               sin and sqrt are the host libm's;
+ *   receivers PVA_AURAL_RECEIVERS on a history-keeping solver: 1 .. PVA_AURAL_MAX_RECEIVERS positions, mapped to cells exactly as
+ *             PvAmdSetOutputQueries maps them; duplicates are allowed; a position off the map is refused, and the error names its
+ *             index.  p_r(t) is what PvAmdCopyHistoryPlane(t) returns at the cell: +0 in a wall or outside the history window (the
+ *             rule of an array member).  On a sparse-emitter solver: xyz = NULL, nPos = 0; the receivers are the kept registered
+ *             emitters in their order, at most 256, and the samples their traces; no emitter-record kind needs to be selected.
+ *             PVA_AURAL_ARRAYS: xyz = NULL, nPos = 0; the receivers are the arrays, p_r(t) = y_a(t) of the last
+ *             PvAmdComputeArrays; refused while that result is invalid;
+ *   response  h_r[n], n = 0 .. L - 1, starts from +0.0f; for j = 0 .. K - 1 ascending:
+ *                 h = h + (w[n][j] * p_r(first[n] + j)),   p_r = +0.0f outside 0 .. T - 1.
+ *             Time is absolute: n = 0 is the emission, so the propagation delays between receivers are kept.  No onset and no NaN
+ *             rule applies: a receiver nothing reached gives the samples it has.  A response's bits depend on its own receiver
+ *             alone;
+ *   signals   signals[nSignals][N], mono float32 at `rate`, 1 <= nSignals <= PVA_AURAL_MAX_SIGNALS, 1 <= N <=
+ *             PVA_AURAL_MAX_SAMPLES; route[R] is a signal index per receiver, or -1 for a receiver that is not rendered; gain[R]
+ *             finite, a negative gain is polarity; M = N + L - 1;
+ *   output    of a routed receiver: o_r[m], m = 0 .. M - 1, starts from +0.0f; for k = max(0, m - N + 1) .. min(L - 1, m)
+ *             ascending:  o = o + (h_r[k] * x[m - k]).  Terms outside that range are not formed.  Unrouted receivers hold +0.0f;
+ *   mix       mix[m] starts from +0.0f; over the routed receivers in increasing r:  mix = mix + (gain[r] * o_r[m]).
+ * NaN, inf and denormal samples propagate as IEEE says.
+ * Device storage, only while a setting exists: the tables, L * K * 4 + L * 4 bytes, from PvAmdSetAuralisation on; the gathered
+ * samples, R * T * 4 bytes, and the responses, R * L * 4 bytes, from the first PvAmdComputeAuralResponses on; the signals and the
+ * outputs, R * M * 4 + M * 4 bytes, from the first PvAmdAuralise on.
+ * Lifetime: a run, a geometry, boundary or layer change, a changed setting, in sparse-emitter mode a change of the emitters and,
+ * for the array source, whatever invalidates the array responses invalidate the responses and the outputs; a new
+ * PvAmdComputeAuralResponses invalidates the outputs; the read-backs then return -1.  With no setting nothing is allocated or
+ * launched, and a run enqueues exactly what it does without this section.
+ * Refused (-1, nothing changed, PvAmdLastError says why, "aural: ..."): the ranges above, K > PVA_AURAL_MAX_TAPS,
+ * L * K > 2^24, R * M > 2^26, slab groups and slab ranks, no completed run or a last run in error, bad indices, NULL tables, no
+ * valid responses.  PVA_OPT_SKIP_ANALYSIS is no reason to refuse: no onset map is needed. */
+#define PVA_AURAL_MAX_TAPS      1024
+#define PVA_AURAL_MAX_RECEIVERS 256
+#define PVA_AURAL_MAX_SIGNALS   64
+#define PVA_AURAL_MAX_SAMPLES   (1 << 20)
+#define PVA_AURAL_RECEIVERS     0
+#define PVA_AURAL_ARRAYS        1
+#define PVA_AURAL_TILED         0
+#define PVA_AURAL_PLAIN         1
+/* Set the resampler (the tables are built and uploaded beside the old ones: a refused or failed call leaves the setting of
+ * before).  rate = 0 clears the setting and frees everything.  Waits for a run in flight */
+PVA_EXPORT int PvAmdSetAuralisation(PvAmdSolver* s, int rate, int zeroCrossings, float beta);
+/* the setting with the response length L and the taps per sample K (each may be NULL); -1 without a setting */
+PVA_EXPORT int PvAmdGetAuralisation(PvAmdSolver* s, int* rate, int* zeroCrossings, float* beta, int* L, int* K);
+/* the tables: first[n] and w[n][0 .. K) of the first min(capN, L) samples (each may be NULL); returns L, -1 without a setting */
+PVA_EXPORT int PvAmdGetAuralTaps(PvAmdSolver* s, int* first, float* w, int capN);
+/* The responses of the LAST COMPLETED run of s (waits for a run in flight).  Synchronous on the solver's own stream.  *ms
+ * (optional): device time of the call's kernels */
+PVA_EXPORT int PvAmdComputeAuralResponses(PvAmdSolver* s, int source, const float* xyz, int nPos, float* ms);
+/* h_r, L floats */
+PVA_EXPORT int PvAmdCopyAuralResponse(PvAmdSolver* s, int r, float* outL);
+/* Convolve and mix: route[R] and gain[R] with R the receivers of the responses.  Synchronous; *ms (optional): device time of the
+ * convolution and the mix */
+PVA_EXPORT int PvAmdAuralise(PvAmdSolver* s, const float* signals, int nSignals, int N, const int* route, const float* gain, float* ms);
+/* o_r, M floats (zeros for an unrouted receiver) */
+PVA_EXPORT int PvAmdCopyAuralOutput(PvAmdSolver* s, int r, float* outM);
+/* mix, M floats */
+PVA_EXPORT int PvAmdCopyAuralMix(PvAmdSolver* s, float* outM);
+/* the tiling of the convolution kernel: a block owns outputsPerBlock consecutive outputs and stages tapsPerChunk taps at a time */
+PVA_EXPORT void PvAmdAuralShape(int* outputsPerBlock, int* tapsPerChunk);
+/* which convolution kernel PvAmdAuralise launches: PVA_AURAL_TILED (the default, the one above) or PVA_AURAL_PLAIN (one lane per
+ * output, taps and samples from global memory: what the tiled form is measured against).  The same bits either way */
+PVA_EXPORT int PvAmdSetAuralForm(PvAmdSolver* s, int form);
+/* CPU only: the shape and the tables of a setting by the rule above: *L, *K (optional), and first[L], w[L * K] where both are given
+ * (capN >= L; both NULL: the shape alone); -1 where PvAmdSetAuralisation would refuse */
+PVA_EXPORT int PvAmdHostAuralTaps(int fs, int T, int rate, int zeroCrossings, float beta, int* first, float* w, int capN, int* L, int* K);
+/* CPU only: one response from samples p[T] and tables first[L], w[L * K]: outL[L] */
+PVA_EXPORT int PvAmdHostAuralResample(const float* p, int T, const int* first, const float* w, int L, int K, float* outL);
+/* CPU only: one output from a response h[L] and a signal x[N]: outM[N + L - 1] */
+PVA_EXPORT int PvAmdHostAuralConvolve(const float* h, int L, const float* x, int N, float* outM);
+
 /* ---- Zone statistics: spatial statistics of a computed map over receiver areas ----
  * ISO 3382-1 reports its quantities as averages over receiver areas, with their spread.  A ZONE is a label per result cell;
  * PvAmdComputeZoneStats reduces one computed map of the nine kinds above to one record per zone and plane ON THE DEVICE

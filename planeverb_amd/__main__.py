@@ -47,6 +47,50 @@ def array_members(s):
     return out
 
 
+def echogram_window(s):
+    v = s.split(",")
+    if len(v) != 2:
+        raise argparse.ArgumentTypeError("expected zeroCrossings,beta")
+    return int(v[0]), float(v[1])
+
+
+def read_signal(path, rate):
+    """a dry mono signal as float32 [N]: a 1-D .npy, or a 16-bit PCM mono .wav whose rate is `rate` (samples / 32768)"""
+    if path.lower().endswith(".wav"):
+        import wave
+        with wave.open(path, "rb") as f:
+            if f.getnchannels() != 1 or f.getsampwidth() != 2 or f.getcomptype() != "NONE":
+                raise ValueError("%s: expected 16-bit PCM mono" % path)
+            if f.getframerate() != rate:
+                raise ValueError("%s: its rate is %d, --aural-rate is %d" % (path, f.getframerate(), rate))
+            x = np.frombuffer(f.readframes(f.getnframes()), "<i2").astype(np.float32) / np.float32(32768.0)
+    else:
+        x = np.load(path)
+        if x.ndim != 1:
+            raise ValueError("%s: expected a 1-D array" % path)
+        x = x.astype(np.float32)
+    if not 1 <= x.size <= api.AURAL_MAX_SAMPLES:
+        raise ValueError("%s: 1 .. %d samples" % (path, api.AURAL_MAX_SAMPLES))
+    return np.ascontiguousarray(x)
+
+
+def write_signal(path, x, rate):
+    """float32 .npy as it is, or a 16-bit PCM mono .wav normalised to its peak (silence and non-finite samples: zeros)"""
+    if path.lower().endswith(".wav"):
+        import wave
+        y = np.where(np.isfinite(x), x, np.float32(0.0)).astype(np.float64)
+        peak = np.abs(y).max() if y.size else 0.0
+        pcm = np.round(y / peak * 32767.0).astype("<i2") if peak > 0 else np.zeros(y.size, "<i2")
+        with wave.open(path, "wb") as f:
+            f.setnchannels(1)
+            f.setsampwidth(2)
+            f.setframerate(rate)
+            f.writeframes(pcm.tobytes())
+    else:
+        with open(path, "wb") as f:  # (np.save would append .npy to another suffix)
+            np.save(f, np.ascontiguousarray(x, np.float32))
+
+
 def rect4(s):
     v = [float(x) for x in s.split(",")]
     if len(v) != 4:
@@ -211,6 +255,17 @@ def main(argv=None):
                          "the members' positions are added to the registered emitters)" % (api.ARRAYS_MAX, api.ARRAY_MEMBERS_MAX))
     ap.add_argument("--array-interp", choices=("nearest", "lagrange3"), default="lagrange3",
                     help="with --array: a member's delay rounded to a step, or a third-order Lagrange fractional delay (default)")
+    ap.add_argument("--auralise", metavar="SIGNAL.npy|SIGNAL.wav",
+                    help="render a dry mono signal at --aural-rate (a 1-D .npy, or a 16-bit PCM mono .wav of that rate) through the "
+                         "recorded responses, resampled and convolved on the GPU: through every --array's response, else through the "
+                         "response at every emitter's cell, mixed with gain 1; writes the mix to --aural-out and adds an "
+                         "\"auralisation\" object; works with and without --sparse-emitters (at most %d receivers)"
+                         % api.AURAL_MAX_RECEIVERS)
+    ap.add_argument("--aural-rate", type=int, default=48000, help="with --auralise: the audio rate in samples per second (default 48000)")
+    ap.add_argument("--aural-window", metavar="Z,BETA", type=echogram_window, default=(16, 9.0),
+                    help="with --auralise: the resampler's zero crossings per side and Kaiser beta (default 16,9)")
+    ap.add_argument("--aural-out", metavar="OUT.npy|OUT.wav", default="auralised.npy",
+                    help="with --auralise: where the mix goes: float32 .npy, or a peak-normalised 16-bit PCM .wav (default auralised.npy)")
     ap.add_argument("--bands", metavar="HZ[,HZ...]", type=lambda v: [float(x) for x in v.split(",")],
                     help="add the band metrics (decay times and clarity of the band-filtered response) of each emitter's cell for "
                          "the bands centred at these frequencies")
@@ -292,6 +347,13 @@ def main(argv=None):
         ap.error("--sparse-emitters: at most %d emitters" % api.RECORD_QUERIES_MAX)
     if a.waterfall is not None and len(emitters) > api.WATERFALL_MAX_RECEIVERS:
         ap.error("--waterfall: at most %d emitters" % api.WATERFALL_MAX_RECEIVERS)
+    if a.auralise:
+        if not a.array and len(emitters) > api.AURAL_MAX_RECEIVERS:
+            ap.error("--auralise: at most %d emitters" % api.AURAL_MAX_RECEIVERS)
+        try:
+            signal = read_signal(a.auralise, a.aural_rate)
+        except Exception as e:  # (an unreadable file, wave.Error, a shape or a rate that does not fit)
+            ap.error("--auralise: %s" % e)
     with api.Solver(size, size, a.res, device=a.device, **(dict(streaming_analysis=1) if a.sparse_emitters else {})) as s:
         for b in boxes:
             s.add_geometry(b)
@@ -419,6 +481,28 @@ def main(argv=None):
                 for rec, m in zip(out["arrays"], s.array_records(api.QSPEC_SPECTRUM, spectral=True).reshape(len(a.array), -1, 3)):
                     rec["spectrum"] = {"hz": [float(v) for v in s.spectrum_bins()], "re": [float(v) for v in m[:, 0]],
                                        "im": [float(v) for v in m[:, 1]], "levelDb": [float(v) for v in m[:, 2]]}
+        if a.auralise:  # (the signal through every array's response, else through the response at every emitter's cell; then the mix)
+            s.set_auralisation(a.aural_rate, *a.aural_window)
+            if a.array:
+                s.compute_aural_responses(source=api.AURAL_ARRAYS)
+                count = len(a.array)
+            elif a.sparse_emitters:
+                s.compute_aural_responses()
+                count = len(s.emitter_cells())
+            else:
+                kept = [e for e in emitters if api.host_cells(size, size, a.res, e[0], e[2])[1] is not None]
+                if not kept:
+                    ap.error("--auralise: no emitter on the map")
+                s.compute_aural_responses(kept)
+                count = len(kept)
+            ms = s.auralise(signal, [0] * count)
+            mix = s.aural_mix()
+            write_signal(a.aural_out, mix, a.aural_rate)
+            _, _, _, aural_l, aural_k = s.auralisation_setting()
+            out["auralisation"] = {"rate": a.aural_rate, "zeroCrossings": a.aural_window[0], "beta": a.aural_window[1],
+                                   "source": "arrays" if a.array else "emitters", "receivers": count, "signalSamples": int(signal.size),
+                                   "responseSamples": aural_l, "tapsPerSample": aural_k, "samples": int(mix.size),
+                                   "peak": float(np.abs(mix).max()), "convolve_ms": ms, "out": a.aural_out}
         for i, e in enumerate(emitters):
             o = s.get_output(e)
             ga, gb, gc = api.reverb_bus_gains(o.rt60, o.wetGain)

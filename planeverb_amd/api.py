@@ -389,6 +389,20 @@ SYMBOLS = {
     "PvAmdGetArrayRecords": (C.c_int, [_vp, C.c_int, C.c_uint, _fp, C.c_int]),
     "PvAmdHostArrayTaps": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(C.c_int), _fp]),
     "PvAmdHostArrayResponse": (C.c_int, [_fp, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.c_int, _fp, _fp]),
+    "PvAmdSetAuralisation": (C.c_int, [_vp, C.c_int, C.c_int, C.c_float]),
+    "PvAmdGetAuralisation": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), _fp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "PvAmdGetAuralTaps": (C.c_int, [_vp, C.POINTER(C.c_int), _fp, C.c_int]),
+    "PvAmdComputeAuralResponses": (C.c_int, [_vp, C.c_int, _fp, C.c_int, _fp]),
+    "PvAmdCopyAuralResponse": (C.c_int, [_vp, C.c_int, _fp]),
+    "PvAmdAuralise": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(C.c_int), _fp, _fp]),
+    "PvAmdCopyAuralOutput": (C.c_int, [_vp, C.c_int, _fp]),
+    "PvAmdCopyAuralMix": (C.c_int, [_vp, _fp]),
+    "PvAmdAuralShape": (None, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "PvAmdSetAuralForm": (C.c_int, [_vp, C.c_int]),
+    "PvAmdHostAuralTaps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int), _fp, C.c_int, C.POINTER(C.c_int),
+                                     C.POINTER(C.c_int)]),
+    "PvAmdHostAuralResample": (C.c_int, [_fp, C.c_int, C.POINTER(C.c_int), _fp, C.c_int, C.c_int, _fp]),
+    "PvAmdHostAuralConvolve": (C.c_int, [_fp, C.c_int, _fp, C.c_int, _fp]),
     "PvAmdSetZones": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.c_int]),
     "PvAmdGetZones": (C.c_int, [_vp, C.POINTER(C.c_ubyte), C.POINTER(C.c_int)]),
     "PvAmdZoneStatPlanes": (C.c_int, [_vp, C.c_int]),
@@ -1208,6 +1222,57 @@ def host_array_response(p, tap_member, tap_delay, tap_weight):
     _check(lib().PvAmdHostArrayResponse(_f(a) if a.size else None, int(a.shape[0]), int(a.shape[1]), _ip(m) if m.size else None,
                                         _ip(d) if d.size else None, _f(w) if w.size else None, int(m.size), _f(out), C.byref(onset)))
     return out, np.float32(onset.value)
+
+
+AURAL_MAX_TAPS = 1024        # PVA_AURAL_MAX_TAPS
+AURAL_MAX_RECEIVERS = 256    # PVA_AURAL_MAX_RECEIVERS
+AURAL_MAX_SIGNALS = 64       # PVA_AURAL_MAX_SIGNALS
+AURAL_MAX_SAMPLES = 1 << 20  # PVA_AURAL_MAX_SAMPLES
+AURAL_RECEIVERS, AURAL_ARRAYS = 0, 1  # PVA_AURAL_*: whose responses Solver.compute_aural_responses resamples
+AURAL_TILED, AURAL_PLAIN = 0, 1       # PVA_AURAL_*: the convolution kernel Solver.auralise launches
+
+
+def aural_shape():
+    """PvAmdAuralShape: (outputs per block, taps per chunk) of the convolution kernel's tiling"""
+    b, c = C.c_int(0), C.c_int(0)
+    lib().PvAmdAuralShape(C.byref(b), C.byref(c))
+    return b.value, c.value
+
+
+def host_aural_shape(fs, T, rate, zero_crossings=16, beta=9.0):
+    """(L, K) of a setting: the response length in output samples and the taps per sample; raises where it is refused"""
+    L, K = C.c_int(0), C.c_int(0)
+    _check(lib().PvAmdHostAuralTaps(int(fs), int(T), int(rate), int(zero_crossings), float(beta), None, None, 0, C.byref(L), C.byref(K)))
+    return L.value, K.value
+
+
+def host_aural_taps(fs, T, rate, zero_crossings=16, beta=9.0):
+    """PvAmdHostAuralTaps: the resampling tables of a setting (include/planeverb_amd.h, Auralisation) as (first int32 [L], w
+    float32 [L, K]); raises where the setting is refused"""
+    L, K = host_aural_shape(fs, T, rate, zero_crossings, beta)
+    first, w = np.empty(L, np.int32), np.empty((L, K), np.float32)
+    _check(lib().PvAmdHostAuralTaps(int(fs), int(T), int(rate), int(zero_crossings), float(beta), _ip(first), _f(w), L, None, None))
+    return first, w
+
+
+def host_aural_resample(p, first, w):
+    """PvAmdHostAuralResample: one response float32 [L] from samples p[T] and the tables (first [L], w [L, K])"""
+    a = np.ascontiguousarray(p, np.float32).reshape(-1)
+    f = np.ascontiguousarray(first, np.int32).reshape(-1)
+    ww = np.ascontiguousarray(w, np.float32).reshape(f.size, -1)
+    out = np.empty(f.size, np.float32)
+    _check(lib().PvAmdHostAuralResample(_f(a) if a.size else None, int(a.size), _ip(f) if f.size else None, _f(ww) if ww.size else None,
+                                        int(f.size), int(ww.shape[1]), _f(out)))
+    return out
+
+
+def host_aural_convolve(h, x):
+    """PvAmdHostAuralConvolve: one output float32 [N + L - 1] from a response h[L] and a signal x[N]"""
+    a = np.ascontiguousarray(h, np.float32).reshape(-1)
+    b = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.empty(max(a.size + b.size - 1, 1), np.float32)
+    _check(lib().PvAmdHostAuralConvolve(_f(a) if a.size else None, int(a.size), _f(b) if b.size else None, int(b.size), _f(out)))
+    return out
 
 
 ZMAP_ROOM_METRICS, ZMAP_SPECTRUM = 1, 2  # PVA_ZMAP_*: the map kinds of Solver.set_zone_maps
@@ -2567,6 +2632,93 @@ class Solver:
         out = np.empty((max(n, 1), floats), np.float32)
         _check(lib().PvAmdGetArrayRecords(self._h, fam, int(kind), _f(out), n))
         return out[:n]
+
+    def set_auralisation(self, rate, zero_crossings=16, beta=9.0):
+        """the audio rate compute_aural_responses resamples to (1000 .. 384000 samples per second) and the Kaiser-windowed sinc
+        it uses (zero crossings per side at the lower rate, the window's beta); builds and uploads the tables; rate = 0 clears
+        the setting and frees the device storage"""
+        _check(lib().PvAmdSetAuralisation(self._h, int(rate), int(zero_crossings), float(beta)))
+
+    def auralisation_setting(self):
+        """(rate, zero_crossings, beta, L, K) as set, with the response length L in output samples and the taps per sample K;
+        None without a setting"""
+        rate, z, beta, L, K = C.c_int(0), C.c_int(0), C.c_float(0.0), C.c_int(0), C.c_int(0)
+        if lib().PvAmdGetAuralisation(self._h, C.byref(rate), C.byref(z), C.byref(beta), C.byref(L), C.byref(K)) < 0:
+            if last_error().startswith("aural: no setting"):
+                return None
+            raise PlaneverbError(last_error())
+        return rate.value, z.value, beta.value, L.value, K.value
+
+    def _aural_shape(self):
+        st = self.auralisation_setting()
+        if st is None:
+            raise PlaneverbError("aural: no setting (PvAmdSetAuralisation)")
+        return st[3], st[4]
+
+    def aural_taps(self):
+        """the resampling tables as uploaded: (first int32 [L], w float32 [L, K])"""
+        L, K = self._aural_shape()
+        first, w = np.empty(L, np.int32), np.empty((L, K), np.float32)
+        if lib().PvAmdGetAuralTaps(self._h, _ip(first), _f(w), L) < 0:
+            raise PlaneverbError(last_error())
+        return first, w
+
+    def compute_aural_responses(self, positions=None, source=AURAL_RECEIVERS):
+        """the audio-rate responses of the last completed run, on the device: at `positions` ([N, 3], mapped to cells as
+        set_output_queries maps them); with positions = None on a sparse-emitter solver of the emitters set_emitters kept; with
+        source = AURAL_ARRAYS of the array responses compute_arrays left.  Returns the device time in milliseconds"""
+        ms = C.c_float(0.0)
+        if positions is None:
+            _check(lib().PvAmdComputeAuralResponses(self._h, int(source), None, 0, C.byref(ms)))
+            if source == AURAL_ARRAYS:
+                st = self.arrays()
+                self._aural_count = len(st[0]) if st else 0
+            else:
+                self._aural_count = len(self.emitter_cells())
+        else:
+            xyz = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+            _check(lib().PvAmdComputeAuralResponses(self._h, int(source), _f(xyz) if xyz.size else None, int(xyz.shape[0]), C.byref(ms)))
+            self._aural_count = int(xyz.shape[0])
+        return ms.value
+
+    def aural_response(self, r):
+        """float32 [L]: the response of receiver r at the audio rate, n = 0 the emission"""
+        out = np.empty(self._aural_shape()[0], np.float32)
+        _check(lib().PvAmdCopyAuralResponse(self._h, int(r), _f(out)))
+        return out
+
+    def set_aural_form(self, form):
+        """the convolution kernel auralise launches: AURAL_TILED (the default) or AURAL_PLAIN; the same bits either way"""
+        _check(lib().PvAmdSetAuralForm(self._h, int(form)))
+
+    def auralise(self, signals, route, gain=None):
+        """convolve the responses with dry signals and mix, on the device: signals float32 [n_signals, N] (or [N]) at the set rate,
+        route[r] the signal receiver r renders or -1, gain[r] its weight in the mix (default 1).  Returns the device time in
+        milliseconds; the outputs are N + L - 1 samples long"""
+        x = np.ascontiguousarray(signals, np.float32)
+        x = x.reshape(1, -1) if x.ndim == 1 else x
+        rt = np.ascontiguousarray(route, np.int32).reshape(-1)
+        g = np.ones(rt.size, np.float32) if gain is None else np.ascontiguousarray(gain, np.float32).reshape(-1)
+        count = getattr(self, "_aural_count", None)  # (None: no responses were computed through this object; the library says so)
+        if count is not None and (rt.size != count or g.size != count):
+            raise ValueError("route and gain take one entry per receiver of compute_aural_responses (%d)" % count)
+        ms = C.c_float(0.0)
+        _check(lib().PvAmdAuralise(self._h, _f(x) if x.size else None, int(x.shape[0]), int(x.shape[1]), _ip(rt) if rt.size else None,
+                                   _f(g) if g.size else None, C.byref(ms)))
+        self._aural_m = int(x.shape[1]) + self._aural_shape()[0] - 1
+        return ms.value
+
+    def aural_output(self, r):
+        """float32 [N + L - 1]: what receiver r renders, zeros where it is not routed"""
+        out = np.empty(max(getattr(self, "_aural_m", 0), 1), np.float32)
+        _check(lib().PvAmdCopyAuralOutput(self._h, int(r), _f(out)))
+        return out
+
+    def aural_mix(self):
+        """float32 [N + L - 1]: the gain-weighted sum of the routed receivers' outputs"""
+        out = np.empty(max(getattr(self, "_aural_m", 0), 1), np.float32)
+        _check(lib().PvAmdCopyAuralMix(self._h, _f(out)))
+        return out
 
     def set_zones(self, labels, n_zones=None):
         """the zones zone_stats reduces over: labels = uint8 [gx, gy], 0 = no zone, 1 .. n_zones (at most ZONES_MAX; None: the

@@ -25,6 +25,7 @@
 #include "pv_spectrum.h"
 #include "pv_waterfall.h"
 #include "pv_arrays.h"
+#include "pv_aural.h"
 #include "pv_zone_band_decay.h"
 #include "pv_zone_decay.h"
 #include "pv_zones.h"
@@ -1805,6 +1806,66 @@ int PvAmdGetArrayRecords(PvAmdSolver* h, int family, unsigned kind, float* out, 
     return ret(h, h->s->arrayRecords(family, kind, out, nArrays));
 } PV_API_CATCH(-1)
 
+// auralisation (pv_aural.hip, pv_solver_aural.cpp; the definition: pv_aural.h)
+static_assert(PVA_AURAL_MAX_TAPS == kAuralMaxTaps && PVA_AURAL_MAX_RECEIVERS == kAuralMaxReceivers && PVA_AURAL_MAX_SIGNALS == kAuralMaxSignals &&
+                  PVA_AURAL_MAX_SAMPLES == kAuralMaxSignalSamples && PVA_AURAL_RECEIVERS == kAuralReceivers && PVA_AURAL_ARRAYS == kAuralArrays &&
+                  PVA_AURAL_TILED == kAuralTiled && PVA_AURAL_PLAIN == kAuralPlain,
+              "planeverb_amd.h vs pv_aural.h");
+
+int PvAmdSetAuralisation(PvAmdSolver* h, int rate, int zeroCrossings, float beta) try {
+    if (!analysisHandle(h, "aural: ")) return -1;
+    return ret(h, h->s->setAuralisation(rate, zeroCrossings, beta));
+} PV_API_CATCH(-1)
+
+int PvAmdGetAuralisation(PvAmdSolver* h, int* rate, int* zeroCrossings, float* beta, int* L, int* K) try {
+    if (!analysisHandle(h, "aural: ")) return -1;
+    if (h->s->auralisation(rate, zeroCrossings, beta, L, K)) return 0;
+    g_lastError = "aural: no setting (PvAmdSetAuralisation)";
+    return -1;
+} PV_API_CATCH(-1)
+
+int PvAmdGetAuralTaps(PvAmdSolver* h, int* first, float* w, int capN) try {
+    if (!analysisHandle(h, "aural: ")) return -1;
+    const int n = h->s->auralTapsOf(first, w, capN);
+    if (n < 0) ret(h, false);
+    return n;
+} PV_API_CATCH(-1)
+
+int PvAmdComputeAuralResponses(PvAmdSolver* h, int source, const float* xyz, int nPos, float* ms) try {
+    if (!analysisHandle(h, "aural: ")) return -1;
+    return ret(h, h->s->computeAuralResponses(source, xyz, nPos, ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyAuralResponse(PvAmdSolver* h, int r, float* outL) try {
+    if (!analysisCall(h, "aural: ", __func__, outL)) return -1;
+    return ret(h, h->s->copyAuralResponse(r, outL));
+} PV_API_CATCH(-1)
+
+int PvAmdSetAuralForm(PvAmdSolver* h, int form) try {
+    if (!analysisHandle(h, "aural: ")) return -1;
+    return ret(h, h->s->setAuralForm(form));
+} PV_API_CATCH(-1)
+
+int PvAmdAuralise(PvAmdSolver* h, const float* signals, int nSignals, int N, const int* route, const float* gain, float* ms) try {
+    if (!analysisHandle(h, "aural: ")) return -1;
+    return ret(h, h->s->auralise(signals, nSignals, N, route, gain, ms));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyAuralOutput(PvAmdSolver* h, int r, float* outM) try {
+    if (!analysisCall(h, "aural: ", __func__, outM)) return -1;
+    return ret(h, h->s->copyAuralOutput(r, outM));
+} PV_API_CATCH(-1)
+
+int PvAmdCopyAuralMix(PvAmdSolver* h, float* outM) try {
+    if (!analysisCall(h, "aural: ", __func__, outM)) return -1;
+    return ret(h, h->s->copyAuralMix(outM));
+} PV_API_CATCH(-1)
+
+void PvAmdAuralShape(int* outputsPerBlock, int* tapsPerChunk) try {
+    if (outputsPerBlock) *outputsPerBlock = kAuralOutputsPerBlock;
+    if (tapsPerChunk) *tapsPerChunk = kAuralTapsPerChunk;
+} PV_API_CATCH_VOID
+
 // zone statistics (pv_zones.hip; the labels: pv_zones.h zoneLabelsError)
 static_assert(sizeof(PvAmdZoneStat) == sizeof(ZoneStat), "64 bytes");
 static_assert(PVA_MAP_ROOM_METRICS == kMapRoomMetrics && PVA_MAP_SPECTRUM == kMapSpectrum && PVA_MAP_SPECTRUM + 1 == kAnalysisKinds,
@@ -2495,6 +2556,43 @@ int PvAmdHostArrayResponse(const float* pMT, int M, int T, const int* tapMember,
     }
     const float on = arrayResponse(pMT, T, taps.data(), nTaps, outT);
     if (onset) *onset = on;
+    return 0;
+} PV_API_CATCH(-1)
+
+// auralisation: the tables, one response and one output (pv_aural.h), as the device computes them
+int PvAmdHostAuralTaps(int fsSigned, int T, int rate, int zeroCrossings, float beta, int* first, float* w, int capN, int* L, int* K) try {
+    int l = 0, k = 0;
+    const unsigned fs = fsSigned < 1 ? 0u : (unsigned)fsSigned;  // (0: refused below)
+    if (const char* e = auralShape(fs, T, rate, zeroCrossings, beta, &l, &k)) {
+        g_lastError = e;
+        return -1;
+    }
+    if (L) *L = l;
+    if (K) *K = k;
+    if (!first && !w) return 0;  // (the shape alone)
+    if (!first || !w || capN < l) {
+        g_lastError = "aural: PvAmdHostAuralTaps: room for L first steps and L * K weights (capN >= L), or neither table";
+        return -1;
+    }
+    auralTaps(fs, rate, zeroCrossings, beta, l, k, first, w);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostAuralResample(const float* p, int T, const int* first, const float* w, int L, int K, float* outL) try {
+    if (!p || !first || !w || !outL || T < 1 || L < 1 || K < 1 || K > kAuralMaxTaps || (long long)L * K > kAuralMaxTableFloats) {
+        g_lastError = "aural: PvAmdHostAuralResample: samples p[T], T > 0, tables first[L] and w[L * K] with 1 <= K <= 1024 and L * K <= 2^24, and an output of L floats";
+        return -1;
+    }
+    auralResample(p, T, first, w, L, K, outL);
+    return 0;
+} PV_API_CATCH(-1)
+
+int PvAmdHostAuralConvolve(const float* h, int L, const float* x, int N, float* outM) try {
+    if (!h || !x || !outM || L < 1 || N < 1 || L > (int)kAuralMaxTableFloats || N > kAuralMaxSignalSamples) {
+        g_lastError = "aural: PvAmdHostAuralConvolve: a response h[L], 1 <= L <= 2^24, a signal x[N], 1 <= N <= 2^20, and an output of N + L - 1 floats";
+        return -1;
+    }
+    auralConvolve(h, L, x, N, outM);
     return 0;
 } PV_API_CATCH(-1)
 

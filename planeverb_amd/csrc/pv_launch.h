@@ -300,6 +300,26 @@ void launchArrayMix(const ArrayMixArgs& a, hipStream_t stream);
 // onsets[0 .. P): the first step of column a of the mix planes above the onset threshold as a float, FLT_MAX: none (and for a >= nArrays)
 void launchArrayOnsets(const float* mix, int T, int P, int nArrays, float* onsets, hipStream_t stream);
 
+// ---- pv_aural.hip: auralisation (audio-rate responses and their convolution with dry signals; pv_aural.h)
+// rows[r][0 .. T): receiver r's samples gathered out of `samples` by its ArrayRow (+0.0f below tLoad)
+void launchAuralGather(const float* samples, const ArrayRow* src, int R, int T, float* rows, hipStream_t stream);
+// resp[r][0 .. L) from rows[r][0 .. T): first[L], wT the weights TRANSPOSED, slot j of sample n at wT[j * L + n]
+void launchAuralResample(const float* rows, int R, int T, const int* first, const float* wT, int L, int K, float* resp, hipStream_t stream);
+struct AuralConvolveArgs {
+    const float* resp;     // [R][L]
+    const float* signals;  // [nSignals][N]
+    const int* route;      // [R]: the signal of receiver r, -1: not rendered (its output is +0.0f)
+    float* out;            // [R][M], M = N + L - 1
+    int R, L, N;
+};
+// the tiling of the tiled form: outputs per block, taps per staged chunk
+constexpr int kAuralOutputsPerBlock = 256;
+constexpr int kAuralTapsPerChunk = 128;
+// form: kAuralTiled or kAuralPlain (pv_aural.h); the same bits either way
+void launchAuralConvolve(const AuralConvolveArgs& a, int form, hipStream_t stream);
+// mix[m] over the routed receivers in increasing r
+void launchAuralMix(const float* out, const int* route, const float* gain, int R, int M, float* mix, hipStream_t stream);
+
 // ---- pv_copy.hip: read-backs and copies
 // slab halos: src[i] -> dst[i] for up to six blocks of n floats (n % 4 == 0, 16-byte aligned); dst[i] = NULL skips a block
 void launchHaloPush(const float* const src[6], float* const dst[6], long long n, const HaloHandoff& hand, hipStream_t stream);

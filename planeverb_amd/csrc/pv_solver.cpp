@@ -699,6 +699,7 @@ Solver::~Solver() {
         if (p) hipFree(p);
     freeWaterfall();
     freeArrays();
+    freeAuralisation();
     for (unsigned char* p : {zoneLabels_, zoneScratch_})
         if (p) hipFree(p);
     freeZoneCurves();
@@ -3189,6 +3190,7 @@ bool Solver::setEmitters(const float* xyz, int n) {
             numEmitters_ = 0;
             wfValid_ = false;  // (no emitters are left: the waterfall's records are nobody's)
             arValid_ = false;
+            auRespValid_ = auOutValid_ = false;
             return false;
         }
         emCap_ = (int)cells.size();
@@ -3202,6 +3204,7 @@ bool Solver::setEmitters(const float* xyz, int n) {
     streamedOnce_ = false;  // (emTrace_'s rows are the old table's)
     wfValid_ = false;       // (and so are the waterfall's records)
     arValid_ = false;       // (and what computeArrays mixed from them)
+    auRespValid_ = auOutValid_ = false;  // (and what the auralisation resampled from them)
     numEmitters_ = (int)cells.size();
     // The uploads go through stream_, behind the zero fill dalloc() queued there (a synchronous hipMemcpy is not ordered with
     // a non-blocking stream: the fill could land AFTER it and leave every emitter at cell 0 -- seen as wet gain / RT60 = 0 in

@@ -407,6 +407,22 @@ public:
     bool copyArrayResponse(int array, float* outT);
     bool arrayOnsets(float* out, int nArrays);
     bool arrayRecords(int family, unsigned kind, float* out, int nArrays);
+    // Auralisation (pv_solver_aural.cpp, pv_aural.hip; the definition: pv_aural.h): the responses of up to kAuralMaxReceivers
+    // receivers of the last completed run -- positions mapped as setOutputQueries maps them, on a sparse-emitter solver the
+    // registered emitters' traces, or the array responses computeArrays left -- resampled to the rate set here, and their
+    // convolution with dry signals and mix.  setAuralisation: rate = 0 clears and frees; a refused or failed call leaves the
+    // setting of before; waits for a run in flight.  The computes are synchronised before they return, *ms (optional) = their
+    // device time.  Responses and outputs stay valid until the next run, geometry, boundary or layer change, change of the setting,
+    // in sparse-emitter mode of the emitters, and for the array source until the array responses go; new responses drop the outputs
+    bool setAuralisation(int rate, int zeroCrossings, float beta);
+    bool auralisation(int* rate, int* zeroCrossings, float* beta, int* L, int* K) const;  // false: no setting
+    int auralTapsOf(int* first, float* w, int capN);                                       // L, -1 without a setting
+    bool computeAuralResponses(int source, const float* xyz, int nPos, float* ms);
+    bool copyAuralResponse(int r, float* outL);
+    bool setAuralForm(int form);
+    bool auralise(const float* signals, int nSignals, int N, const int* route, const float* gain, float* ms);
+    bool copyAuralOutput(int r, float* outM);
+    bool copyAuralMix(float* outM);
     // The reductions over zones: pv_solver_zones.cpp.
     // Zone statistics (pv_zones.hip; include/planeverb_amd.h PvAmdZoneStat): a label per result cell, 0 = no zone, 1 .. nZones;
     // computeZoneStats reduces the valid map of one kind to nZones x planes records on the device -- no host copy of the map,
@@ -683,6 +699,7 @@ private:
         for (AnalysisMap& m : maps_) m.valid = false;
         wfValid_ = false;  // (the waterfall's records have the maps' lifetime)
         arValid_ = false;  // (and so has what computeArrays left)
+        auRespValid_ = auOutValid_ = false;  // (and the auralisation's responses and outputs)
     }
     void dropAnalysisMap(AnalysisKind k, bool freeDev);  // a changed setting: records invalid, the device storage freed on request
     bool analysisSettingPresent(AnalysisKind k) const;
@@ -776,6 +793,32 @@ private:
     void invalidateArrays(unsigned spectralKinds) {  // a changed band, modulation or bin setting
         if (arKinds_[kRecSpectral] & spectralKinds) arValid_ = false;
     }
+    unsigned long long arStamp_ = 0;  // counts the computeArrays that went through: what auralised array responses are held to
+    // auralisation (pv_aural.h): the setting and its tables on the host as given out (auW_ row-major [L][K]); on the device from
+    // the setter on first[L] and the weights transposed [K][L] -- L * K * 4 + L * 4 bytes --, the receivers' cells and rows
+    // (kAuralMaxReceivers entries); from computeAuralResponses on the gathered samples [R][T] and the responses [R][L]; from
+    // auralise on the signals, route and gains and the outputs [R][M] and the mix [M].  Nothing of it exists while no setting does
+    int auRate_ = 0, auZ_ = 0, auL_ = 0, auK_ = 0;
+    float auBeta_ = 0.f;
+    std::vector<int> auFirst_;
+    std::vector<float> auW_;
+    int* auFirstDev_ = nullptr;
+    float* auWT_ = nullptr;
+    long long* auCells_ = nullptr;
+    void* auRows_ = nullptr;  // ArrayRow (pv_launch.h)
+    float* auGather_ = nullptr;
+    float* auResp_ = nullptr;
+    float* auSig_ = nullptr;
+    int* auRoute_ = nullptr;
+    float* auGain_ = nullptr;
+    float* auOut_ = nullptr;
+    float* auMix_ = nullptr;
+    size_t auGatherCap_ = 0, auRespCap_ = 0, auSigCap_ = 0, auOutCap_ = 0, auMixCap_ = 0;
+    int auCount_ = 0, auSource_ = 0, auM_ = 0, auForm_ = 0;
+    unsigned long long auArStamp_ = 0;
+    bool auRespValid_ = false, auOutValid_ = false;
+    void freeAuralisation();
+    bool auralResponsesValid() const { return auRespValid_ && (auSource_ == 0 || (arValid_ && arStamp_ == auArStamp_)); }
     // zone statistics (pv_zones.h): the labels on the device and as given, and the pass's scratch -- per plane in flight, zone and
     // result row one ZoneRow and one double (48 bytes), the planes dealt in chunks that keep it within kZoneScratchBytes (one
     // plane's where that is more), then the nZones x planes records; grown on demand, kept.  The zone-decay pass uses the same

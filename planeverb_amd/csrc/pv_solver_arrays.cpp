@@ -329,6 +329,7 @@ bool Solver::computeArrays(float* ms) {
         }
     }
     arValid_ = true;
+    ++arStamp_;
     return true;
 }
 
