@@ -96,6 +96,20 @@ def convolve(h, x):
     return o
 
 
+def chunk_walk(L, N, B, C):
+    """The tiled kernel's walk of k restated from DESIGN.md 4.29, one string per block of B outputs: the block at m0 walks its k
+    range, max(0, m0 - N + 1) .. min(L - 1, the block's last output), in chunks of C taps from the range's first tap; a chunk at k0
+    is 'W' (whole: every (output, tap) pair of a FULL block and the chunk is a term of the definition) where
+    k0 + C - 1 <= min(L - 1, m0) and k0 >= m0 + B - N, else 'g' (general).  Not a reference of any value: the GPU cases assert
+    with it that they reach the pattern they were written for."""
+    M = N + L - 1
+    walks = []
+    for m0 in range(0, M, B):
+        k_begin, k_end = max(0, m0 - N + 1), min(L - 1, min(m0 + B - 1, M - 1))
+        walks.append("".join("W" if k0 + C - 1 <= min(L - 1, m0) and k0 >= m0 + B - N else "g" for k0 in range(k_begin, k_end + 1, C)))
+    return walks
+
+
 def mix(outputs, route, gain):
     """mix float32 [M] over the routed receivers in increasing r: mix = mix + (gain[r] * o_r[m])"""
     y = np.zeros(outputs.shape[1], F32)

@@ -1,7 +1,9 @@
 """CPU: the auralisation's host restatements (PvAmdHostAuralTaps, PvAmdHostAuralResample, PvAmdHostAuralConvolve: csrc/pv_aural.h)
 against the numpy restatement written from the header (tests/_aural_ref.py), the resampler against the function it samples, the
 convolution against float64 within the sequential-summation bound, the refusals, and the edge cases once more in a program of their
-own under ASan + UBSan.  tests/test_gpu_aural.py holds the kernels to the same numpy restatement."""
+own under ASan + UBSan.  tests/test_gpu_aural.py holds the kernels to the same numpy restatement.  The restated chunk walk of the
+tiled kernel (_aural_ref.chunk_walk), with which the cases of tests/test_gpu_aural_walk.py assert the path they reach, is pinned to
+brute force here."""
 import ctypes as C
 import os
 import re
@@ -168,6 +170,64 @@ def test_convolve_against_float64(pvlib):
         print("L %d N %d: worst error / bound %.3g, outputs above the sums-only bound: %d of them with one term, %d with more" % (
             L, N, (err / (gamma * mag + 1e-300)).max(), ((err > sums_only) & (terms == 1)).sum(), ((err > sums_only) & (terms > 1)).sum()))
         assert (err[terms > 1] <= sums_only[terms > 1]).all(), (L, N)
+
+
+def brute_walk(L, N, B, C):
+    """chunk_walk from the words alone: a chunk is W exactly when every pair (m in m0 .. m0 + B - 1, k in the chunk) has
+    0 <= m - k < N and k < L"""
+    M, walks = N + L - 1, []
+    for m0 in range(0, M, B):
+        m = np.arange(m0, m0 + B)[:, None]
+        k0, k_end, s = max(0, m0 - N + 1), min(L - 1, m0 + B - 1, M - 1), ""
+        while k0 <= k_end:
+            k = np.arange(k0, k0 + C)[None, :]
+            s += "W" if bool(((m - k >= 0) & (m - k < N) & (k < L)).all()) else "g"
+            k0 += C
+        walks.append(s)
+    return walks
+
+
+def test_chunk_walk_against_brute_force():
+    for L in range(1, 41):
+        for N in range(1, 41):
+            for B, C in ((8, 4), (4, 4), (8, 8), (12, 4)):
+                assert ref.chunk_walk(L, N, B, C) == brute_walk(L, N, B, C), (L, N, B, C)
+    assert any("WW" in s for s in ref.chunk_walk(40, 40, 8, 4)) and any("gW" in s for s in ref.chunk_walk(40, 40, 8, 4))
+    rng = np.random.default_rng(429)
+    pairs = [(int(a), int(b)) for a, b in rng.integers(1, 3001, (300, 2))] + [(301, 384), (301, 383), (256, 1000), (255, 1000)]
+    whole = 0
+    for L, N in pairs:
+        got = ref.chunk_walk(L, N, 256, 128)
+        assert got == brute_walk(L, N, 256, 128), (L, N)
+        assert len(got) == (N + L - 1 + 255) // 256 and all(got)  # (a block per 256 outputs, none with an empty k range)
+        whole += sum(s.count("W") for s in got)
+    assert whole > 1000
+    # a whole chunk needs N >= B + C, and at N = B + C a response that covers the chunk
+    assert not any("W" in s for L in (200, 301, 3000) for s in ref.chunk_walk(L, 383, 256, 128))
+    assert ref.chunk_walk(301, 384, 256, 128) == ["gg", "gWg", "gg"]
+    assert not any("W" in s for s in ref.chunk_walk(255, 384, 256, 128))  # (the chunk k0 = 128 would end at tap 255 = L)
+
+
+def test_what_the_first_convolution_shapes_covered(pvlib):
+    """Regression note.  Until the walk cases of tests/test_gpu_aural_walk.py, the (L, N) pairs of test_convolution and
+    test_convolution_short_responses ran exactly two whole chunks on the device, (L, N) = (128, 519) and (129, 519) at the block
+    m0 = 256: both the block's first chunk (k0 = 0, zero accumulators, kBegin = 0), neither followed by another whole one.  The
+    loop the measured shapes of profiles/aural.txt spend their time in was otherwise never compared with the definition."""
+    B, C = pvlib.aural_shape()
+    assert (B, C) == (256, 128)
+    pairs = []
+    for L in (301, 2407):  # test_convolution
+        k = (L + 100) // B + 1
+        pairs += [(L, n) for n in [1, 2, 65] + [k * B - L + 1 + d for d in (-1, 0, 1)]]
+    for L in (69, 128, 129):  # test_convolution_short_responses
+        pairs += [(L, n) for n in (1, 2, 65, C, B - L, B - L + 1, B - L + 2, 2 * B + 7)]
+    assert len(pairs) == 36
+    with_whole = dict((p, ref.chunk_walk(p[0], p[1], B, C)) for p in pairs if any("W" in s for s in ref.chunk_walk(p[0], p[1], B, C)))
+    assert with_whole == {(128, 519): ["g", "W", "g"], (129, 519): ["gg", "Wg", "gg"]}
+    # the shapes that were added for it
+    assert ref.chunk_walk(2407, 1000, B, C).count("ggWWWWWggg") >= 3
+    walk = ref.chunk_walk(2407, 2407, B, C)
+    assert (sum(s.count("W") for s in walk), sum(len(s) for s in walk), max(len(r) for s in walk for r in re.findall("W+", s))) == (152, 199, 16)
 
 
 def test_exports_present_and_guarded(pvlib):
